@@ -7,7 +7,10 @@ tts.Runtime.GenerateAudio for 64 concurrent utterances per GPU (text prompt of 2
 24 kHz PCM).  BASELINE.json configs[2] at N=1 and configs[3] (64 per GPU) at N=8: weak scaling, no
 data-path collective -- one RCCL broadcast of the weight arena at start-up.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the headline's last timed step returned (PCM, frame counts, EOS steps) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its N ranks itself (one child process per
 GPU, before anything in the parent touches the GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it is
@@ -382,7 +385,8 @@ def serve_continuous_pass(pkg, model, wl, voice, barrier, sync, slots=192, clien
             st["eng"].close()
 
 
-def run_workload(pkg, model, wl, prompts, voice, steps, warmup, barrier, sync, **cfg_kw):
+def run_workload(pkg, model, wl, prompts, voice, steps, warmup, barrier, sync, last=None, **cfg_kw):
+    """`steps` timed passes after `warmup` untimed ones; `last` (a list): the results of the last timed pass are appended to it."""
     cfgs = gen_cfgs(pkg, wl, len(prompts), voice, **cfg_kw)
     toks = [np.ascontiguousarray(p, np.int64) for p in prompts]
     out = None
@@ -409,7 +413,33 @@ def run_workload(pkg, model, wl, prompts, voice, steps, warmup, barrier, sync, *
     frames = sum(o.n_frames for o in out)
     assert all(o.n_frames == wl["frames"] and o.pcm.shape[0] == wl["frames"] * 1920 for o in out)
     assert os.environ.get("PTTS_PROBE_GARBAGE") or all(np.isfinite(o.pcm).all() for o in out[:2])   # (ablation builds of tools/probes feed garbage on purpose: timing only)
+    if last is not None:
+        last.append(out)
     return elapsed, lat, frames
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, results, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of the timed path received in its last timed pass, as .npy files (float32 / float64):
+    pcm [rows, samples] (float32, as returned), n_frames / eos_step / utterance [rows] (float64).  All utterances when they fit
+    in `budget` bytes, else a fixed, seeded (0) sample of whole utterances -- `utterance` names the rows kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(results)
+    pcm = np.stack([np.asarray(r.pcm, np.float32) for r in results])
+    rows = np.arange(n)
+    fit = max(1, (budget - 64 * 1024) // max(1, pcm[0].nbytes))   # room for the small arrays and the .npy headers
+    if fit < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=fit, replace=False))
+    arrays = {"pcm": pcm[rows],
+              "n_frames": np.array([results[i].n_frames for i in rows], np.float64),
+              "eos_step": np.array([results[i].eos_step for i in rows], np.float64),
+              "utterance": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"[bench] outputs of the last timed step: {len(rows)} of {n} utterances -> {out_dir} "
+        f"({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB)")
 
 
 def roofline_pass(pkg, model, wl, prompts, voice, traffic=None):
@@ -684,7 +714,11 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=63)
     ap.add_argument("--native-broadcast", action="store_true", help="N > 1: broadcast the weight arena with the library's own RCCL call (ptts_rccl_broadcast)")
     ap.add_argument("--startup-only", action="store_true", help="CPU rehearsal of the N-rank start-up (gloo): plan, fill, ONE broadcast, sharding; no GPU, no timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned as DIR/<name>.npy (rank 0's utterances, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become one.  Nothing here has touched the GPU; the ranks are fresh processes.
@@ -741,7 +775,11 @@ def main():
     all_prompts = pkg.synth.make_prompts(wl["batch"] * world, 25, 4000, seed=42)
     prompts = shard_prompts(all_prompts, rank, wl["batch"])
 
-    elapsed_own, lat, frames = run_workload(pkg, model, wl, prompts, voice, args.steps, args.warmup, barrier, sync)
+    last = []
+    elapsed_own, lat, frames = run_workload(pkg, model, wl, prompts, voice, args.steps, args.warmup, barrier, sync, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    del last
     dev = f"cuda:{local}"
     elapsed = max_over_ranks(elapsed_own, world, dev)
     per_rank_audio = wl["batch"] * wl["frames"] * FRAME_SEC * args.steps
