@@ -659,6 +659,18 @@ int ptts_decode_latents(ptts_model* h, const float* latents, int32_t n_utt, int3
 
 }  // extern "C"
 
+// the Mimi encoder with the staged observation points of tests (stages; capi_hooks.cpp ptts_debug_encode_stages)
+int ptts::capi::encode_stages(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out, float* const* stages) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        Model& m = *h->m;
+        require_encoder(m.d);
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        mimi_encode(m, pcm, n_samples, n_clips, latent_out, stages);
+    });
+}
+
 // LatentToMimi + MimiDecode with the staged observation point of tests (transformer_out; capi_hooks.cpp ptts_decode_stages)
 int ptts::capi::decode_stages(ptts_model* h, const float* latents, int32_t n_utt, int32_t frames, float* pcm, float* mimi_latent, float* transformer_out) {
     return guard([&] {
@@ -709,6 +721,43 @@ int ptts_speaker_project(ptts_model* h, const float* latent, int64_t frames, flo
         launch_gemm(g, m.stream);
         PTTS_HIP(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, m.stream));
         PTTS_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+int ptts_mimi_encode(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out) {
+    return encode_stages(h, pcm, n_samples, n_clips, latent_out, nullptr);
+}
+
+int64_t ptts_mimi_encode_frames(int64_t n_samples) {
+    if (n_samples < 0) return -PTTS_EINVAL;
+    return (n_samples + 1919) / 1920;   // (every checkpoint this build loads has the decoder's 16 x 6 x 5 x 4 = 1920-sample frame; the encoder's hop must match)
+}
+
+int ptts_voice_encode_audio(ptts_model* h, const float* pcm, int64_t n_samples, float* embedding_out, int64_t* frames) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        Model& m = *h->m;
+        require_encoder(m.d);
+        const Lin& l = m.d.speaker_proj;
+        if (l.w == NONE) throw Error(PTTS_EFORMAT, "load speaker_proj_weight: tensor not found in the model weights");
+        if (l.in != m.d.mimi_dim) throw Error(PTTS_EFORMAT, strfmt("speaker_proj_weight takes %d-wide latents, the encoder makes %d", l.in, m.d.mimi_dim));
+        if (!embedding_out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        const int64_t nf = n_samples > 0 ? (n_samples + m.d.enc.hop - 1) / m.d.enc.hop : 0;
+        DevBuf& io = m.work(17, (size_t)std::max<int64_t>(nf, 1) * (l.in + l.out) * sizeof(float));
+        float* lat = io.as<float>();
+        const int64_t f = mimi_encode_clip(m, pcm, n_samples, lat, nullptr);
+        float* dout = lat + (size_t)f * l.in;
+        GemmArgs g;   // the product ptts_speaker_project runs, on the latents where the encoder left them
+        g.A = lat; g.amap = RowMap{l.in, 0, 0};
+        g.W = m.arena + l.w; g.w_bf16 = 0; g.ldw = l.in;
+        g.C = dout; g.cmap = RowMap{l.out, 0, 0};
+        g.M = (int)f; g.N = l.out; g.K = l.in;
+        launch_gemm(g, m.stream);
+        PTTS_HIP(hipMemcpyAsync(embedding_out, dout, (size_t)f * l.out * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+        PTTS_HIP(hipStreamSynchronize(m.stream));
+        if (frames) *frames = f;
     });
 }
 

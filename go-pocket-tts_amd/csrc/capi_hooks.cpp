@@ -13,6 +13,24 @@ int ptts_decode_stages(ptts_model* h, const float* latents, int32_t n_utt, int32
     return decode_stages(h, latents, n_utt, frames, pcm, mimi_latent, transformer_out);
 }
 
+int ptts_debug_encode_stages(ptts_model* h, const float* pcm, int64_t n_samples, float* const* stages, int64_t* shapes) {
+    if (stages || !shapes) {
+        float* lat = stages ? stages[kEncStages - 1] : nullptr;
+        std::vector<float> own;
+        if (stages && !lat && h && h->m) {   // (the latent is always produced: a temporary buffer when stage 9 is not asked for)
+            own.resize((size_t)std::max<int64_t>(ptts_mimi_encode_frames(n_samples), 1) * h->m->d.mimi_dim);
+            lat = own.data();
+        }
+        const int rc = encode_stages(h, &pcm, &n_samples, 1, &lat, stages ? stages : nullptr);
+        if (rc != PTTS_OK || !shapes) return rc;
+    }
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        require_encoder(h->m->d);
+        mimi_encode_stage_shapes(h->m->d, n_samples, shapes);
+    });
+}
+
 const char* ptts_debug_last_attention_kernel(void) { return g_last_attn_kernel; }
 
 int ptts_debug_flow_cluster_inject(ptts_model* h, int32_t block) {

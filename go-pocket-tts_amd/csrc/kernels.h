@@ -375,6 +375,14 @@ void launch_slot_retire(const StepState& s, const int32_t* slots_dev, int n, hip
 void launch_fill_i32(int32_t* p, int32_t v, int n, hipStream_t stream);
 void launch_add_i32(int32_t* p, const int32_t* inc, int n, hipStream_t stream);
 
+// Mimi encoder pieces (encoder.hip; PARITY UNPINNED, inferred chain: DESIGN.md section 7)
+// the 1-channel input conv: out[t * ldo + c] = b[c] + sum_x w[c][x] pcm[t + x] for t < L (pcm holds k - 1 zero history samples in front)
+void launch_enc_head(const float* pcm, const void* w, int w_bf16, const float* b, int64_t L, int C, int k, float* out, int64_t ldo, hipStream_t stream);
+// out[M][N] = A[M][K] * W[N][K]^T + bias (A rows lda apart), split-K: raw planes partial[enc_ds_splits(M, N, K)][M][N] summed in slice order
+int enc_ds_splits(int M, int N, int K);
+void launch_enc_downsample(const float* A, int64_t lda, const void* W, int w_bf16, const float* bias, int M, int N, int K, float* partial, float* out,
+                           hipStream_t stream);
+
 // [B, C, T] <-> channels-last helpers for the op-level entry points
 void launch_bct_to_btc(const float* in, int b, int c, int t, float* out, int out_pad_rows, hipStream_t stream);
 void launch_btc_to_bct(const float* in, int in_pad_rows, int b, int c, int t, float* out, hipStream_t stream);

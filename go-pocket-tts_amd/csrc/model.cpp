@@ -375,6 +375,75 @@ struct Walker {
         *sin_off = add_f32((size_t)ROPE_SEQ * half, gen(false));
     }
 
+    // one Mimi transformer layer (mimi.go:245-441): the decoder's, and the encoder's under its own prefix
+    void mimi_layer(const std::string& p, Desc::ML& L) {
+        L.n1 = norm(p + ".norm1", 1e-5f);
+        L.n2 = norm(p + ".norm2", 1e-5f);
+        L.in_proj = linear(p + ".self_attn.in_proj", false);
+        L.out_proj = linear(p + ".self_attn.out_proj", false);
+        L.l1 = linear(p + ".linear1", false);
+        L.l2 = linear(p + ".linear2", false);
+        if (has(p + ".layer_scale_1.scale")) L.ls1 = add_f32((size_t)f.at(p + ".layer_scale_1.scale").count(), [&](float* dst) { f.decode_f32(p + ".layer_scale_1.scale", dst); });
+        if (has(p + ".layer_scale_2.scale")) L.ls2 = add_f32((size_t)f.at(p + ".layer_scale_2.scale").count(), [&](float* dst) { f.decode_f32(p + ".layer_scale_2.scale", dst); });
+        if (L.out_proj.out % d.mimi_heads) throw Error(PTTS_EFORMAT, strfmt("native: mimi d_model %d not divisible by heads %d", L.out_proj.out, d.mimi_heads));
+        if (bf16w && L.l1.in == 512 && L.l2.out == 512 && L.l1.out == L.l2.in && L.l1.out % 32 == 0 && L.l1.b == NONE && L.l2.b == NONE)
+            L.ffn_img = add_ffn_image(p + ".linear1.weight", p + ".linear2.weight", L.l1.out);
+        if (bf16w && L.in_proj.in == 512 && L.in_proj.out % 64 == 0 && L.in_proj.b == NONE)
+            L.qkv_img = add_w1_image(p + ".self_attn.in_proj.weight", L.in_proj.out);
+    }
+
+    // Mimi encoder, PARITY UNPINNED (inferred chain): head conv, 3 x (residual block, ELU, strided conv), ELU, tail conv,
+    // transformer, downsample conv.  Every width, kernel size and stride comes from the header; a stride is kernel / 2, as for the decoder's convtr.
+    void encoder() {
+        const std::string mi = "mimi.", em = mi + "encoder.model.";
+        auto& e = d.enc;
+        auto conv = [&](const std::string& name, int* k, int* cin, bool frag16) {
+            expect_rank(name + ".weight", 3);
+            return conv_as_gemm(name, k, cin, frag16);
+        };
+        int cin = 0;
+        e.head = conv(em + "0.conv", &e.head_k, &cin, false);
+        if (cin != 1) throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder head conv takes %d channels, want 1 (mono PCM)", cin));
+        e.ch[0] = e.head.out;
+        static const int rb_idx[3] = {1, 4, 7}, dn_idx[3] = {3, 6, 9};
+        for (int j = 0; j < 3; j++) {
+            const std::string rb = em + std::to_string(rb_idx[j]) + ".block.";
+            int c1 = 0, c2 = 0;
+            e.rb1[j] = conv(rb + "1.conv", &e.rb_k1[j], &c1, true);
+            e.rb2[j] = conv(rb + "3.conv", &e.rb_k2[j], &c2, true);
+            e.hidden[j] = e.rb1[j].out;
+            if (c1 != e.ch[j] || c2 != e.hidden[j] || e.rb2[j].out != e.ch[j])
+                throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder residual block %d channel mismatch (width %d)", j + 1, e.ch[j]));
+            e.down[j] = conv(em + std::to_string(dn_idx[j]) + ".conv", &e.down_k[j], &c1, false);
+            if (c1 != e.ch[j]) throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder down conv %d input channels %d, want %d", j + 1, c1, e.ch[j]));
+            if (e.down_k[j] < 2 || e.down_k[j] % 2) throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder down conv %d kernel %d, this build needs kernel = 2*stride", j + 1, e.down_k[j]));
+            e.down_s[j] = e.down_k[j] / 2;
+            e.ch[j + 1] = e.down[j].out;
+        }
+        e.tail = conv(em + "11.conv", &e.tail_k, &cin, false);
+        if (cin != e.ch[3] || e.tail.out != d.mimi_dim)
+            throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder tail conv [%d, %d, %d], want [%d, %d, k]", e.tail.out, cin, e.tail_k, d.mimi_dim, e.ch[3]));
+        e.layers = 0;
+        for (int i = 0; i < MAX_LAYERS; i++) {
+            const std::string p = mi + "encoder_transformer.transformer.layers." + std::to_string(i);
+            if (!has(p + ".norm1.weight")) break;
+            mimi_layer(p, e.ml[i]);
+            const auto& L = e.ml[i];
+            if (L.out_proj.out != d.mimi_dim || L.out_proj.out / d.mimi_heads != d.mimi_hd || L.in_proj.out != 3 * d.mimi_dim || L.l1.in != d.mimi_dim || L.l2.out != d.mimi_dim)
+                throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder transformer layer %d shapes do not match the decoder transformer's", i));
+            e.layers++;
+        }
+        if (e.layers == 0) throw Error(PTTS_EFORMAT, "native: no mimi encoder transformer layers found");
+        e.ds = conv(mi + "downsample.conv.conv", &e.ds_k, &cin, false);
+        if (cin != d.mimi_dim || e.ds.out != d.mimi_dim || e.ds_k < 2 || e.ds_k % 2)
+            throw Error(PTTS_EFORMAT, strfmt("native: mimi downsample conv [%d, %d, %d], want [%d, %d, 2*stride]", e.ds.out, cin, e.ds_k, d.mimi_dim, d.mimi_dim));
+        e.ds_s = e.ds_k / 2;
+        e.hop = (int64_t)e.down_s[0] * e.down_s[1] * e.down_s[2] * e.ds_s;
+        if (e.hop != d.samples_per_frame)
+            throw Error(PTTS_EFORMAT, strfmt("native: mimi encoder hop %lld samples, the decoder's frame is %lld", (long long)e.hop, (long long)d.samples_per_frame));
+        e.present = 1;
+    }
+
     void run() {
         d.n_params = 0;
         // ---------------- flow_lm ----------------
@@ -540,20 +609,7 @@ struct Walker {
         for (int i = 0; i < MAX_LAYERS; i++) {
             std::string p = mi + "decoder_transformer.transformer.layers." + std::to_string(i);
             if (!has(p + ".norm1.weight")) break;
-            auto& L = d.ml[i];
-            L.n1 = norm(p + ".norm1", 1e-5f);
-            L.n2 = norm(p + ".norm2", 1e-5f);
-            L.in_proj = linear(p + ".self_attn.in_proj", false);
-            L.out_proj = linear(p + ".self_attn.out_proj", false);
-            L.l1 = linear(p + ".linear1", false);
-            L.l2 = linear(p + ".linear2", false);
-            if (has(p + ".layer_scale_1.scale")) L.ls1 = add_f32((size_t)f.at(p + ".layer_scale_1.scale").count(), [&](float* dst) { f.decode_f32(p + ".layer_scale_1.scale", dst); });
-            if (has(p + ".layer_scale_2.scale")) L.ls2 = add_f32((size_t)f.at(p + ".layer_scale_2.scale").count(), [&](float* dst) { f.decode_f32(p + ".layer_scale_2.scale", dst); });
-            if (L.out_proj.out % d.mimi_heads) throw Error(PTTS_EFORMAT, strfmt("native: mimi d_model %d not divisible by heads %d", L.out_proj.out, d.mimi_heads));
-            if (bf16w && L.l1.in == 512 && L.l2.out == 512 && L.l1.out == L.l2.in && L.l1.out % 32 == 0 && L.l1.b == NONE && L.l2.b == NONE)
-                L.ffn_img = add_ffn_image(p + ".linear1.weight", p + ".linear2.weight", L.l1.out);
-            if (bf16w && L.in_proj.in == 512 && L.in_proj.out % 64 == 0 && L.in_proj.b == NONE)
-                L.qkv_img = add_w1_image(p + ".self_attn.in_proj.weight", L.in_proj.out);
+            mimi_layer(p, d.ml[i]);
             d.mimi_layers++;
         }
         if (d.mimi_layers == 0) throw Error(PTTS_EFORMAT, "native: no mimi decoder transformer layers found");
@@ -605,6 +661,8 @@ struct Walker {
             }
         }
         d.samples_per_frame = (int64_t)d.up_stride * d.strides[0] * d.strides[1] * d.strides[2];
+        d.enc = Desc::Enc{};   // (the fill pass starts from the planned Desc)
+        if (has(mi + "encoder.model.0.conv.weight")) encoder();   // without its keys nothing is reserved: the arena is the decoder-only one
         d.total_bytes = (cur + 255) & ~(size_t)255;
     }
 };

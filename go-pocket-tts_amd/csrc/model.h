@@ -63,6 +63,18 @@ struct Desc {
     size_t final_w = NONE, final_b = NONE;
     size_t final_wf = NONE, final_wf_lo = NONE;   // final conv as column 0 of a 16-column fragment-ordered matrix, bf16 hi + lo planes (resblock.hip)
     int64_t samples_per_frame = 0;
+    // Mimi encoder (optional: voice cloning from 24 kHz PCM, onnx/voice_encode.go:23-158).  PARITY UNPINNED: the reference has no native encoder
+    // (mimi.go:14,791-794), so the chain is inferred from the decoder and every size is taken from the checkpoint header.
+    struct Enc {
+        int present = 0;
+        int ch[4] = {0, 0, 0, 0};        // widths after the head, down 1, down 2, down 3 (f, 2f, 4f, 8f at full size)
+        int hidden[3] = {0, 0, 0};
+        int head_k = 0, rb_k1[3] = {0, 0, 0}, rb_k2[3] = {0, 0, 0}, down_k[3] = {0, 0, 0}, down_s[3] = {0, 0, 0}, tail_k = 0, ds_k = 0, ds_s = 0;
+        int layers = 0;
+        Lin head, rb1[3], rb2[3], down[3], tail, ds;   // convolutions as GEMM operands [Cout][tap * Cin + ic] (model.cpp conv_as_gemm)
+        ML ml[MAX_LAYERS];
+        int64_t hop = 0;                 // samples per latent frame: down_s[0] * down_s[1] * down_s[2] * ds_s
+    } enc;
     int64_t n_params = 0;
     size_t total_bytes = 0;
 };

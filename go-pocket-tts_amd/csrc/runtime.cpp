@@ -1020,8 +1020,10 @@ void mimi_zero_history(Model& m, MimiWs& w, hipStream_t s) {
 // ptts_mimi_layer_piece (staged parity checks).
 // norm1 -> in_proj (no bias) -> RoPE of q and k at positions pos0 + (row % rows_per_seg): x rows [R][C] -> qkv rows [R][3C].  n1: [R][C] scratch.
 void mimi_layer_qkv(Model& m, int l, const float* x, RowMap xmap, int R, float* qkv, RowMap qmap, int pos0, int rows_per_seg, float* n1, hipStream_t s) {
+    mimi_layer_qkv(m, m.d.ml[l], x, xmap, R, qkv, qmap, pos0, rows_per_seg, n1, s);
+}
+void mimi_layer_qkv(Model& m, const Desc::ML& L, const float* x, RowMap xmap, int R, float* qkv, RowMap qmap, int pos0, int rows_per_seg, float* n1, hipStream_t s) {
     const Desc& d = m.d;
-    const auto& L = d.ml[l];
     const int C = d.mimi_dim;
     if (L.qkv_img != NONE && d.mimi_hd == 64) {   // one kernel (ffn_fused.hip k_mimi_rowlin)
         RowLinArgs ra;
@@ -1047,8 +1049,10 @@ void mimi_layer_qkv(Model& m, int l, const float* x, RowMap xmap, int R, float* 
 
 // x += layer_scale_2 * linear2(gelu(linear1(norm2(x)))) on rows [R][C], in place.  n1: [R][C], ffb: [R][F] scratch (unused by the fused kernel).
 void mimi_layer_ffn(Model& m, int l, float* x, RowMap xmap, int R, float* n1, float* ffb, hipStream_t s) {
+    mimi_layer_ffn(m, m.d.ml[l], x, xmap, R, n1, ffb, s);
+}
+void mimi_layer_ffn(Model& m, const Desc::ML& L, float* x, RowMap xmap, int R, float* n1, float* ffb, hipStream_t s) {
     const Desc& d = m.d;
-    const auto& L = d.ml[l];
     const int C = d.mimi_dim, F = d.mimi_ffn;
     if (L.ffn_img != NONE) {   // one kernel (ffn_fused.hip k_mimi_ffn)
         FfnArgs fa;

@@ -191,6 +191,23 @@ void mimi_range(Model& m, MimiWs& w, const float* lat, int64_t lat_bstride, int 
 
 void mimi_layer_qkv(Model& m, int layer, const float* x, RowMap xmap, int R, float* qkv, RowMap qmap, int pos0, int rows_per_seg, float* n1, hipStream_t s);
 void mimi_layer_ffn(Model& m, int layer, float* x, RowMap xmap, int R, float* n1, float* ffb, hipStream_t s);
+// the same on any layer of that form (the encoder transformer's: Desc::Enc::ml)
+void mimi_layer_qkv(Model& m, const Desc::ML& L, const float* x, RowMap xmap, int R, float* qkv, RowMap qmap, int pos0, int rows_per_seg, float* n1, hipStream_t s);
+void mimi_layer_ffn(Model& m, const Desc::ML& L, float* x, RowMap xmap, int R, float* n1, float* ffb, hipStream_t s);
+
+// Mimi encoder (encoder.cpp; PARITY UNPINNED, inferred chain: DESIGN.md section 7): clip i (n_samples[i] samples of 24 kHz mono f32, host) ->
+// latent_out[i] (host, [mimi_encode_frames(n_samples[i])][mimi_dim]).  Clips are encoded one after another through one workspace sized for
+// the longest, each from zero history, so a clip's bits never depend on the others.  stages (optional, one clip): kEncStages host buffers, see
+// include/ptts_debug.h ptts_debug_encode_stages.
+// A clip is at most mimi_encode_max_frames(d) frames long (PTTS_EINVAL above): the transformer's RoPE table covers ROPE_SEQ rows at the
+// transformer's rate (8192 rows at 200 Hz: 512 frames = 40.96 s at full size).
+constexpr int kEncStages = 10;
+int64_t mimi_encode_max_frames(const Desc& d);
+void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, int n_clips, float* const* latent_out, float* const* stages = nullptr);
+// one clip -> device latents lat_dev [frames][mimi_dim] on m.stream (the caller holds m.mu); returns the frame count
+int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* lat_dev, float* const* stages = nullptr);
+void require_encoder(const Desc& d);
+void mimi_encode_stage_shapes(const Desc& d, int64_t n_samples, int64_t* shapes /* [kEncStages][2] (rows, channels) */);   // PTTS_EFORMAT naming the missing tensor on a checkpoint without encoder weights
 Model* model_open(Plan* plan, void* device_arena, int fill);
 Batch* batch_new(Model& m, int n_slots, int cap, int max_steps);
 void batch_reset(Batch& b);

@@ -93,7 +93,7 @@ ABI_SYMBOLS = [
     "ptts_plan_create", "ptts_plan_create_bytes", "ptts_plan_arena_bytes", "ptts_model_open_planned", "ptts_plan_free",
     "ptts_generate", "ptts_free_result", "ptts_text_embeddings", "ptts_batch_new", "ptts_batch_free", "ptts_batch_reset",
     "ptts_batch_set_voice_state", "ptts_batch_prompt", "ptts_batch_step", "ptts_batch_offsets", "ptts_batch_read_kv",
-    "ptts_decode_latents", "ptts_noise_rows", "ptts_speaker_project", "ptts_flow_direction", "ptts_op_linear", "ptts_op_layernorm", "ptts_op_rope",
+    "ptts_decode_latents", "ptts_noise_rows", "ptts_speaker_project", "ptts_mimi_encode", "ptts_mimi_encode_frames", "ptts_voice_encode_audio", "ptts_flow_direction", "ptts_op_linear", "ptts_op_layernorm", "ptts_op_rope",
     "ptts_op_attention_positions", "ptts_op_conv1d_leftpad", "ptts_op_convtr1d_righttrim", "ptts_version",
         "ptts_voice_create", "ptts_voice_free", "ptts_profile_enable", "ptts_profile_read", "ptts_plan_fill_host", "ptts_wav_header_streaming", "ptts_op_pcm16",
     "ptts_dispatcher_create", "ptts_dispatcher_create_custom", "ptts_dispatch_generate", "ptts_dispatcher_stats", "ptts_dispatcher_close",
@@ -108,6 +108,7 @@ ABI_SYMBOLS = [
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
+    "ptts_debug_encode_stages",
 ]
 
 
@@ -491,6 +492,45 @@ class Model:
         L.ptts_speaker_project.argtypes = [C.c_void_p, _FP, C.c_int64, _FP]
         _check(L.ptts_speaker_project(self.h, _fp(lat), lat.shape[0], _fp(out)))
         return out
+
+    # ---- the Mimi encoder (PARITY UNPINNED: inferred architecture, no reference fixture; include/ptts.h ptts_mimi_encode) ----
+    def encode_audio(self, pcm):
+        """mimi.encode_to_latent (onnx/voice_encode.go:23-158) on the GPU: 24 kHz mono f32 PCM -> the raw latent [ceil(n / 1920), 512].
+        A list of clips is encoded in one call and gives a list of latents (each clip's result is independent of the others)."""
+        single = not isinstance(pcm, (list, tuple))
+        clips = [_f32(pcm).reshape(-1)] if single else [_f32(p).reshape(-1) for p in pcm]
+        outs = [np.empty((max(mimi_encode_frames(c.size), 0), self.info.mimi_dim), np.float32) for c in clips]
+        n = len(clips)
+        pp = (_FP * n)(*[_fp(c) for c in clips])
+        ns = np.array([c.size for c in clips], np.int64)
+        po = (_FP * n)(*[_fp(o) for o in outs])
+        L = lib()
+        L.ptts_mimi_encode.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        _check(L.ptts_mimi_encode(self.h, pp, _ip(ns), n, po))
+        return outs[0] if single else outs
+
+    def voice_from_audio(self, pcm) -> VoiceEmbedding:
+        """EncodeVoice (onnx/voice_encode.go:23-158): encoder + speaker projection on the device -> a VoiceEmbedding [1, frames, d_model]
+        for RuntimeGenerateConfig.voice_embedding."""
+        x = _f32(pcm).reshape(-1)
+        out = np.empty((max(mimi_encode_frames(x.size), 0), self.info.d_model), np.float32)
+        frames = C.c_int64(0)
+        L = lib()
+        L.ptts_voice_encode_audio.argtypes = [C.c_void_p, _FP, C.c_int64, _FP, C.POINTER(C.c_int64)]
+        _check(L.ptts_voice_encode_audio(self.h, _fp(x), x.size, _fp(out), C.byref(frames)))
+        return VoiceEmbedding(out, (1, int(frames.value), self.info.d_model))
+
+    def encode_stages(self, pcm) -> list:
+        """Test hook (libptts_hooks.so ptts_debug_encode_stages): the encoder's ten observation points on one clip, channels-last arrays."""
+        x = _f32(pcm).reshape(-1)
+        H = hooks()
+        H.ptts_debug_encode_stages.argtypes = [C.c_void_p, _FP, C.c_int64, C.POINTER(_FP), _IP]
+        shapes = np.zeros((10, 2), np.int64)
+        _check(H.ptts_debug_encode_stages(self.h, _fp(x), x.size, None, _ip(shapes)))
+        outs = [np.empty((int(r), int(c)), np.float32) for r, c in shapes]
+        po = (_FP * len(outs))(*[_fp(o) for o in outs])
+        _check(H.ptts_debug_encode_stages(self.h, _fp(x), x.size, po, _ip(shapes)))
+        return outs
 
     def noise_rows(self, seed: int, temperature: float, rows: int) -> np.ndarray:
         """The device draw of makeGaussianNoise (flow_lm.go:386-408) a request with (noise_seed, temperature) consumes."""
@@ -896,6 +936,14 @@ def debug_tall_linear(x, w, *, bias=None, residual=None, epi=0, splitk=1, ln=Non
 def last_attention_kernel() -> str:
     """Which kernel this thread's last attention launch used (ptts_debug_last_attention_kernel)."""
     return hooks().ptts_debug_last_attention_kernel().decode()
+
+
+def mimi_encode_frames(n_samples: int) -> int:
+    """Frames the Mimi encoder makes of n samples: ceil(n / 1920) (ptts_mimi_encode_frames)."""
+    L = lib()
+    L.ptts_mimi_encode_frames.argtypes = [C.c_int64]
+    L.ptts_mimi_encode_frames.restype = C.c_int64
+    return int(L.ptts_mimi_encode_frames(int(n_samples)))
 
 
 def launch_counts(on: bool) -> dict:

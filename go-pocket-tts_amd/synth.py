@@ -36,6 +36,7 @@ class SynthConfig:
     input_linear_bias: bool = False
     speaker_proj: bool = False  # also write flow_lm.speaker_proj_weight [d_model, 512]
     layer_scale: float = 0.01  # Mimi layer_scale_{1,2}; ~1 makes the decoder transformer's branches count in full
+    encoder: bool = False      # also write the Mimi encoder (PARITY UNPINNED: the inferred chain of DESIGN.md section 7), from its own RNG stream
 
     @staticmethod
     def full() -> "SynthConfig":
@@ -183,7 +184,40 @@ def make_checkpoint(cfg: SynthConfig = SynthConfig(), seed: int = 1234) -> dict[
         conv(f"mimi.decoder.model.{idx_rb}.block.1.conv", ch[j + 1] // 2, ch[j + 1], 3)
         conv(f"mimi.decoder.model.{idx_rb}.block.3.conv", ch[j + 1], ch[j + 1] // 2, 1)
     conv("mimi.decoder.model.11.conv", 1, ch[3], 3)
+    if cfg.encoder:
+        _encoder_tensors(cfg, seed, t)
     return t
+
+
+def _encoder_tensors(cfg: SynthConfig, seed: int, t: dict) -> None:
+    """The Mimi encoder's tensors, PARITY UNPINNED (the key table is inferred), drawn from a stream of their own so that
+    every other tensor of a config is byte-identical with and without them."""
+    rng = np.random.default_rng([seed, 0x4D494D49])
+    M, f = cfg.mimi_dim, cfg.n_filters
+
+    def conv(name: str, oc: int, ic: int, k: int, bias: bool = True) -> None:
+        t[name + ".weight"] = (rng.standard_normal((oc, ic, k)) / np.sqrt(ic * k)).astype(np.float32)
+        if bias:
+            t[name + ".bias"] = (0.02 * rng.standard_normal(oc)).astype(np.float32)
+
+    em = "mimi.encoder.model."
+    conv(em + "0.conv", f, 1, 7)
+    for j, (idx_rb, idx_dn, stride) in enumerate(((1, 3, 4), (4, 6, 5), (7, 9, 6))):
+        w = f << j
+        conv(f"{em}{idx_rb}.block.1.conv", w // 2, w, 3)
+        conv(f"{em}{idx_rb}.block.3.conv", w, w // 2, 1)
+        conv(f"{em}{idx_dn}.conv", 2 * w, w, 2 * stride)
+    conv(em + "11.conv", M, 8 * f, 3)
+    for i in range(cfg.mimi_layers):
+        p = f"mimi.encoder_transformer.transformer.layers.{i}"
+        for nm in ("norm1", "norm2"):
+            t[f"{p}.{nm}.weight"] = (1.0 + 0.1 * rng.uniform(-1, 1, M)).astype(np.float32)
+            t[f"{p}.{nm}.bias"] = (0.02 * rng.standard_normal(M)).astype(np.float32)
+        for nm, out, inp in (("self_attn.in_proj", 3 * M, M), ("self_attn.out_proj", M, M), ("linear1", cfg.mimi_ffn, M), ("linear2", M, cfg.mimi_ffn)):
+            t[f"{p}.{nm}.weight"] = (rng.standard_normal((out, inp)) / np.sqrt(inp)).astype(np.float32)
+        for nm in ("layer_scale_1", "layer_scale_2"):
+            t[f"{p}.{nm}.scale"] = (max(cfg.layer_scale, 0.1) * (1.0 + 0.25 * rng.uniform(-1, 1, M))).astype(np.float32)
+    conv("mimi.downsample.conv.conv", M, M, 32, bias=False)
 
 
 INT8_STEP_MATRICES = ("self_attn.in_proj.weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight")

@@ -348,10 +348,23 @@ int  ptts_decode_latents(ptts_model* m, const float* latents, int32_t n_utt, int
                          float* pcm, float* mimi_latent);
 /* Voice cloning, the part the reference holds natively: projectSpeakerConditioning
  * (internal/onnx/voice_encode.go:119-158) -- Mimi-encoder latents [frames, 512] (host) times flow_lm.speaker_proj_weight
- * [d_model, 512] -> voice embedding [frames, d_model] (host), which a request then carries as `voice_embedding`.  The Mimi encoder
- * itself has no native reference (mimi.go:14,791-794: ErrMimiEncoderNotImplemented) and is not built.  PTTS_EFORMAT when the
+ * [d_model, 512] -> voice embedding [frames, d_model] (host), which a request then carries as `voice_embedding`.  PTTS_EFORMAT when the
  * checkpoint has no speaker projection tensor. */
 int  ptts_speaker_project(ptts_model* m, const float* latent, int64_t frames, float* out);
+/* The first half: the Mimi encoder (mimi.encode_to_latent, internal/onnx/voice_encode.go:23-158) on the GPU.  PARITY UNPINNED: inferred
+ * architecture, no reference fixture -- the reference has no native encoder (mimi.go:14,791-794: ErrMimiEncoderNotImplemented), so the chain is
+ * inferred from the decoder and exists only on checkpoints that carry mimi.encoder.* / mimi.encoder_transformer.* /
+ * mimi.downsample.* tensors.  pcm[i]: n_samples[i] samples of 24 kHz mono f32 (host; resampling and WAV parsing are the caller's), zero-padded
+ * to whole frames; latent_out[i] (host) receives the raw [ptts_mimi_encode_frames(n_samples[i]), 512] latent (no quantizer, no emb_mean/emb_std).
+ * Clips are independent: a clip's result does not depend on the others in the call.  PTTS_EINVAL for an empty clip or one longer than
+ * 512 frames (40.96 s); PTTS_EFORMAT, naming the missing tensor, on a checkpoint without encoder weights. */
+int  ptts_mimi_encode(ptts_model* m, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out);
+/* frames the encoder makes of n samples: ceil(n / 1920) (sample_rate / frame_rate); 0 for 0 samples (which ptts_mimi_encode rejects),
+ * -PTTS_EINVAL for a negative count */
+int64_t ptts_mimi_encode_frames(int64_t n_samples);
+/* both halves for one clip, the projection on the device: embedding_out (host) receives [frames, d_model], *frames the frame count.
+ * PTTS_EFORMAT naming the missing tensor without encoder weights or without the speaker projection. */
+int  ptts_voice_encode_audio(ptts_model* m, const float* pcm, int64_t n_samples, float* embedding_out, int64_t* frames);
 /* The device draw of FlowLM.makeGaussianNoise (flow_lm.go:386-408) for one request: out[rows, ldim] (host) receives exactly the
  * rows ptts_generate would consume for (noise_seed = seed, temperature) -- so that a test can hand the same noise to a reference. */
 int  ptts_noise_rows(ptts_model* m, uint64_t seed, float temperature, int32_t rows, float* out);

@@ -27,6 +27,15 @@ int  ptts_mimi_layer_piece(ptts_model* m, int32_t layer, int32_t which, const fl
 int  ptts_decode_stages(ptts_model* m, const float* latents, int32_t n_utt, int32_t frames,
                         float* pcm, float* mimi_latent, float* transformer_out);
 
+/* Staged observation of the Mimi encoder (ptts_mimi_encode; PARITY UNPINNED) on one clip: stages[i] (host, any may be NULL) receives, channels-last,
+ *   0 head conv [L0, f]          1 elu(residual block 1) [L0, f]   2 down conv 1 [L1, 2f]   3 elu(residual block 2) [L1, 2f]
+ *   4 down conv 2 [L2, 4f]        5 elu(residual block 3) [L2, 4f]  6 down conv 3 [L3, 8f]  7 tail conv [L3, 512]
+ *   8 transformer output [L3, 512]  9 latent [frames, 512]
+ * with L3 = 16 frames, L2 = 6 L3, L1 = 5 L2, L0 = 4 L1 at full size (the strides are the checkpoint's).  The residual stages are given after the ELU
+ * that every reader applies (the sum itself is never stored).  shapes [10][2] receives every stage's (rows, channels); with stages NULL that is all
+ * the call does. */
+int  ptts_debug_encode_stages(ptts_model* m, const float* pcm, int64_t n_samples, float* const* stages, int64_t* shapes);
+
 /* Kernel micro-benchmarks (tools/microbench.py; device-resident synthetic operands, HIP-event timing; not part of the
  * drop-in path).  ptts_debug_gemm also returns max |C_variant - C_other| between the two many-row GEMM kernels. */
 int ptts_debug_time_skinny(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t splitk, int32_t fuse_ln, int32_t iters, float* avg_us);
