@@ -278,109 +278,43 @@ void cont_admit(ContEngine& e, const ptts_request* const* reqs, ptts_result* con
     struct Timer { ContEngine& e; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
                    ~Timer() { e.tr_acc_admit_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); } } admit_timer{e};
     if (n <= 0) return;
-    Model& m = e.m;
     e.lock_model();
     Batch& b = *e.b;
-    const Desc& d = m.d;
     hipStream_t s = e.io;   // beside the step chain, which keeps running on m.stream for the slots that are generating
     const int turn = e.arena_turn;
     e.arena_turn ^= 1;
     UploadScope upload_scope(e.arenas[turn], e.arena_free[turn]);   // the copies queued from this arena two admissions ago are long done
-    const int B = e.B, D = d.d_model, ld = d.ldim;
-    std::vector<int> slot_of((size_t)n);
-    {
-        int next = 0;
-        for (int i = 0; i < n; i++) {
-            while (next < B && e.slots[(size_t)next].busy) next++;
-            if (next >= B) throw Error(PTTS_EINVAL, "continuous batch: more requests admitted than free slots");
-            slot_of[(size_t)i] = next++;
-        }
+    std::vector<SlotReq> list((size_t)n);
+    for (int i = 0, next = 0; i < n; i++, next++) {
+        while (next < e.B && e.slots[(size_t)next].busy) next++;
+        if (next >= e.B) throw Error(PTTS_EINVAL, "continuous batch: more requests admitted than free slots");
+        list[(size_t)i] = SlotReq{next, reqs[i], resolve_max_steps(*reqs[i])};
+        // a free slot forgets its previous voice prefix first
+        b.kv_len_host[(size_t)next] = 0;
+        b.pre_k_host[(size_t)next] = nullptr; b.pre_v_host[(size_t)next] = nullptr; b.pre_len_host[(size_t)next] = 0;
     }
-    // voices: a free slot forgets its previous prefix first
-    std::map<const Voice*, std::vector<int32_t>> by_voice;
-    for (int i = 0; i < n; i++) {
-        const int sl = slot_of[(size_t)i];
-        b.kv_len_host[(size_t)sl] = 0;
-        b.pre_k_host[(size_t)sl] = nullptr; b.pre_v_host[(size_t)sl] = nullptr; b.pre_len_host[(size_t)sl] = 0;
-    }
-    for (int i = 0; i < n; i++) {
-        const ptts_request& r = *reqs[i];
-        const int sl = slot_of[(size_t)i];
-        if (r.voice) by_voice[reinterpret_cast<const Voice*>(r.voice)].push_back(sl);
-        else if (r.voice_caches) batch_set_voice(b, sl, r.voice_caches, r.voice_cache_steps, r.voice_offsets);
-    }
-    for (auto& kv : by_voice) batch_apply_voice(b, *kv.first, kv.second);
-    // prompt rows of the newcomers, packed; the running slots have empty segments
-    std::vector<int64_t> row_off((size_t)B + 1, 0);
-    std::vector<int> req_of_slot((size_t)B, -1);
-    for (int i = 0; i < n; i++) req_of_slot[(size_t)slot_of[(size_t)i]] = i;
-    for (int sl = 0; sl < B; sl++) {
-        const int i = req_of_slot[(size_t)sl];
-        const int64_t tp = i < 0 ? 0 : reqs[i]->n_tokens + (reqs[i]->voice_embedding ? reqs[i]->voice_frames : 0);
-        row_off[(size_t)sl + 1] = row_off[(size_t)sl] + tp;
-    }
-    const int64_t R = row_off[(size_t)B];
-    DevBuf& rows = m.work(5, (size_t)R * D * sizeof(float));
-    {
-        std::vector<int64_t> ids;
-        for (int sl = 0; sl < B; sl++) {
-            const int i = req_of_slot[(size_t)sl];
-            if (i >= 0) ids.insert(ids.end(), reqs[i]->tokens, reqs[i]->tokens + reqs[i]->n_tokens);
-        }
-        DevBuf& dids = m.work(6, ids.size() * sizeof(int64_t));
-        h2d(dids.p, ids.data(), ids.size() * sizeof(int64_t), s);
-        int64_t id0 = 0;
-        for (int sl = 0; sl < B; sl++) {   // (text embeddings and voice embeddings as GenerateAudio concatenates them, :89-119)
-            const int i = req_of_slot[(size_t)sl];
-            if (i < 0) continue;
-            const ptts_request& r = *reqs[i];
-            float* dst = rows.as<float>() + row_off[(size_t)sl] * D;
-            const int64_t tv = r.voice_embedding ? r.voice_frames : 0;
-            if (tv) h2d(dst, r.voice_embedding, (size_t)tv * D * sizeof(float), s);
-            launch_embed_gather(m.at<float>(d.embed), dids.as<int64_t>() + id0, (int)r.n_tokens, D, dst + tv * D, s);
-            id0 += r.n_tokens;
-        }
-    }
-    batch_prompt(b, rows.as<float>(), row_off.data());
-    // bookkeeping and noise rows of the new slots
-    std::vector<SlotAdmit> adm((size_t)n);
-    std::vector<NoiseSpec> spec((size_t)B, NoiseSpec{0, 0.0f, 0});
-    bool any_draw = false;
-    int draw_rows = 0;
-    for (int i = 0; i < n; i++) {
-        const ptts_request& r = *reqs[i];
-        const int sl = slot_of[(size_t)i];
-        const int ms = resolve_max_steps(r);
-        adm[(size_t)i] = SlotAdmit{sl, ms, r.frames_after_eos, r.eos_threshold, b.kv_len_host[(size_t)sl], b.pre_len_host[(size_t)sl], b.pre_k_host[(size_t)sl],
-                                   b.pre_v_host[(size_t)sl]};
-        float* nrow = b.noise.as<float>() + (size_t)sl * b.max_steps * ld;
-        PTTS_HIP(hipMemsetAsync(nrow, 0, (size_t)b.max_steps * ld * sizeof(float), s));
-        if (r.noise) h2d(nrow, r.noise, (size_t)ms * ld * sizeof(float), s);
-        else if (r.temperature > 0.0f) {
-            if (ld % 4) throw Error(PTTS_EINVAL, "ptts-hip: the device noise draw needs a latent width that is a multiple of 4");
-            spec[(size_t)sl] = NoiseSpec{r.noise_seed ? r.noise_seed : m.next_noise_seed(), std::sqrt(r.temperature), ms};
-            any_draw = true;
-            draw_rows = std::max(draw_rows, ms);
-        }
-    }
-    if (any_draw) {
-        DevBuf& sb = m.work(12, spec.size() * sizeof(NoiseSpec));
-        h2d(sb.p, spec.data(), spec.size() * sizeof(NoiseSpec), s);
-        launch_noise_fill(sb.as<NoiseSpec>(), B, draw_rows, b.noise.as<float>(), (int64_t)b.max_steps * ld, ld, s);
-    }
+    // voices and prompts of the newcomers (the running slots have empty segments), then their noise rows
+    stage_prompt(b, list, s);
+    stage_noise(b, list, s);
+    // their bookkeeping: host side now, device side by the admit kernel once the prefill is done (activate_ready)
     ContEngine::Joining j;
+    std::vector<SlotAdmit> adm((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ptts_request& r = *reqs[i];
+        const int sl = list[(size_t)i].slot;
+        adm[(size_t)i] = SlotAdmit{sl, list[(size_t)i].max_steps, r.frames_after_eos, r.eos_threshold, b.kv_len_host[(size_t)sl], b.pre_len_host[(size_t)sl],
+                                   b.pre_k_host[(size_t)sl], b.pre_v_host[(size_t)sl]};
+        ContEngine::Slot& so = e.slots[(size_t)sl];
+        so = ContEngine::Slot{};
+        so.busy = true; so.req = reqs[i]; so.res = results[i]; so.tag = tags[i];
+        so.ms = list[(size_t)i].max_steps;
+        so.base_kv = b.kv_len_host[(size_t)sl];
+        so.joining = true;
+        j.slots.push_back(sl);
+    }
     j.ring = e.adm_turn;
     e.adm_turn = (e.adm_turn + 1) & 3;
     h2d(e.adm_dev[j.ring].p, adm.data(), adm.size() * sizeof(SlotAdmit), s);
-    for (int i = 0; i < n; i++) {
-        ContEngine::Slot& sl = e.slots[(size_t)slot_of[(size_t)i]];
-        sl = ContEngine::Slot{};
-        sl.busy = true; sl.req = reqs[i]; sl.res = results[i]; sl.tag = tags[i];
-        sl.ms = adm[(size_t)i].max_steps;
-        sl.base_kv = b.kv_len_host[(size_t)slot_of[(size_t)i]];
-        sl.joining = true;
-        j.slots.push_back(slot_of[(size_t)i]);
-    }
     j.ready = e.event();
     j.seq = e.seq;
     PTTS_HIP(hipEventRecord(j.ready, s));
@@ -501,60 +435,22 @@ static void start_decode(ContEngine& e, std::vector<ContEngine::Staged>& fin) {
         mimi_setup(m, mw, nb, T);
         mimi_zero_history(m, mw, s2);
         DevBuf& pcm = m.work(7, (size_t)nb * T * spf * sizeof(float));
-        // The result rows first: the decoder's last kernel stores every utterance's samples (f32 or int16) straight into its page-locked result buffer -- the kernel's
-        // stores ARE the device -> host transfer, as in the one-shot path (runtime.cpp generate_chunk): no PCM copy per utterance on the decoder's stream, no
-        // conversion launch.  (A pool that had to fall back to pageable memory, or a decoder shape the fused last stage does not take: the buffer + copy path below.)
-        const size_t row0 = (size_t)lt * 2 * (size_t)e.B + n_rows_used;
-        PcmRow* hrows = e.rows_host + row0;
-        bool direct = row0 + (size_t)nb <= (size_t)ContEngine::kLat * 2 * (size_t)e.B && n_rows_used + (size_t)nb <= 2 * (size_t)e.B;
-        for (int i = 0; i < nb; i++) {
-            const ContEngine::Staged& f = fin[at + (size_t)i];
-            ptts_result& r = *f.res;
-            r.n_frames = f.nf; r.eos_step = f.eos; r.n_samples = (int64_t)f.nf * spf; r.status = PTTS_OK;
-            const bool s16r = f.req->pcm_format == PTTS_PCM_S16;
-            void* dst = result_alloc((size_t)std::max<int64_t>(1, r.n_samples) * (s16r ? sizeof(int16_t) : sizeof(float)));
-            if (s16r) r.pcm16 = (int16_t*)dst; else r.pcm = (float*)dst;
-            if (!dst) { r.status = PTTS_ENOMEM; direct = false; continue; }
-            direct = direct && result_is_pinned(dst);
-            if (direct) hrows[i] = PcmRow{dst, (int32_t)std::min<int64_t>(r.n_samples, INT32_MAX), s16r ? 1 : 0};
+        // the result buffers first: through a PcmRow table of its own (kLat x 2 B entries, rewritten no sooner than kLat decode starts later) the decoder's
+        // last kernel stores the samples into them itself (results_alloc) -- no PCM copy per utterance on the decoder's stream, no conversion launch
+        std::vector<Delivery> g((size_t)nb);
+        ContEngine::Pending p;
+        for (size_t i = at; i < end; i++) {
+            g[i - at] = Delivery{fin[i].req, fin[i].res, fin[i].nf, fin[i].eos, false};
+            p.tags.push_back(fin[i].tag);
+            p.res.push_back(fin[i].res);
+            e.stage_free.push_back(fin[i].row);
         }
-        const PcmRow* drows = nullptr;
-        if (direct) {
-            PcmRow* dr = e.rows_dev.as<PcmRow>() + row0;
-            PTTS_HIP(hipMemcpyAsync(dr, hrows, (size_t)nb * sizeof(PcmRow), hipMemcpyHostToDevice, s2));   // (page-locked source, rewritten no sooner than kLat decode starts later)
-            drows = dr;
-            n_rows_used += (size_t)nb;
-        }
+        const size_t row0 = (size_t)lt * 2 * (size_t)e.B + n_rows_used;   // (fin holds at most 2 B utterances, one per staging row)
+        const PcmRow* drows = results_alloc(m, g, e.rows_host + row0, e.rows_dev.as<PcmRow>() + row0, s2);
+        if (drows) n_rows_used += (size_t)nb;
         bool stored = false;
         mimi_range(m, mw, lat, (int64_t)T * ld, 0, T, pcm.as<float>(), nullptr, s2, drows, &stored);
-        bool any_s16 = false;
-        for (int i = 0; i < nb; i++) any_s16 |= fin[at + (size_t)i].req->pcm_format == PTTS_PCM_S16;
-        DevBuf* s16 = nullptr;
-        if (!stored && any_s16) {
-            s16 = &m.work(8, (size_t)nb * T * spf * sizeof(int16_t));
-            launch_pcm16(pcm.as<float>(), s16->as<int16_t>(), (int64_t)nb * T * spf, s2);
-        }
-        ContEngine::Pending p;
-        for (int i = 0; i < nb; i++) {
-            const ContEngine::Staged& f = fin[at + (size_t)i];
-            ptts_result& r = *f.res;
-            const int nf = f.nf;
-            if (!stored && r.status == PTTS_OK && r.n_samples > 0) {
-                if (f.req->pcm_format == PTTS_PCM_S16)
-                    PTTS_HIP(hipMemcpyAsync(r.pcm16, s16->as<int16_t>() + (size_t)i * T * spf, (size_t)r.n_samples * sizeof(int16_t), hipMemcpyDeviceToHost, s2));
-                else
-                    PTTS_HIP(hipMemcpyAsync(r.pcm, pcm.as<float>() + (size_t)i * T * spf, (size_t)r.n_samples * sizeof(float), hipMemcpyDeviceToHost, s2));
-            }
-            if (f.req->want_latents && r.status == PTTS_OK) {
-                r.latents = (float*)malloc((size_t)std::max(1, nf) * ld * sizeof(float));
-                if (!r.latents) r.status = PTTS_ENOMEM;
-                else if (nf > 0)
-                    PTTS_HIP(hipMemcpyAsync(r.latents, lat + (size_t)i * T * ld, (size_t)nf * ld * sizeof(float), hipMemcpyDeviceToHost, s2));
-            }
-            p.tags.push_back(f.tag);
-            p.res.push_back(f.res);
-            e.stage_free.push_back(f.row);
-        }
+        results_deliver(m, g, stored, pcm.as<float>(), (int64_t)T * spf, lat, (int64_t)T * ld, s2);
         p.done = e.event();
         PTTS_HIP(hipEventRecord(p.done, s2));
         e.decoding.push_back(std::move(p));

@@ -1290,6 +1290,133 @@ void result_free(void* p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// request staging and result delivery, shared by generate() and the continuous batch (continuous.cpp)
+// ------------------------------------------------------------------------------------------------
+void stage_prompt(Batch& b, const std::vector<SlotReq>& list, hipStream_t s, hipEvent_t before_prefill) {
+    Model& m = *b.m;
+    const int D = m.d.d_model;
+    std::map<const Voice*, std::vector<int32_t>> by_voice;
+    for (const SlotReq& q : list) {
+        if (q.req->voice) by_voice[reinterpret_cast<const Voice*>(q.req->voice)].push_back(q.slot);
+        else if (q.req->voice_caches) batch_set_voice(b, q.slot, q.req->voice_caches, q.req->voice_cache_steps, q.req->voice_offsets);
+    }
+    for (auto& kv : by_voice) batch_apply_voice(b, *kv.first, kv.second);
+    // text (+ voice) embeddings packed as rows (runtime_native_safetensors.go:89-119); the slots not listed have empty segments
+    std::vector<int64_t> row_off((size_t)b.B + 1, 0), ids;
+    for (const SlotReq& q : list) {
+        row_off[(size_t)q.slot + 1] = q.req->n_tokens + (q.req->voice_embedding ? q.req->voice_frames : 0);
+        ids.insert(ids.end(), q.req->tokens, q.req->tokens + q.req->n_tokens);
+    }
+    for (int sl = 0; sl < b.B; sl++) row_off[(size_t)sl + 1] += row_off[(size_t)sl];
+    DevBuf& rows = m.work(5, (size_t)row_off[(size_t)b.B] * D * sizeof(float));
+    DevBuf& dids = m.work(6, ids.size() * sizeof(int64_t));
+    h2d(dids.p, ids.data(), ids.size() * sizeof(int64_t), s);
+    // token rows of consecutive requests are contiguous unless a voice embedding sits between them: one gather per such run
+    // (a batch without voice embeddings is ONE launch instead of one per request)
+    int64_t id0 = 0, run_id0 = 0, run_n = 0;
+    float* run_dst = rows.as<float>();
+    auto flush = [&]() {
+        if (run_n > 0) launch_embed_gather(m.at<float>(m.d.embed), dids.as<int64_t>() + run_id0, (int)run_n, D, run_dst, s);
+        run_n = 0;
+    };
+    for (const SlotReq& q : list) {
+        const ptts_request& r = *q.req;
+        float* dst = rows.as<float>() + row_off[(size_t)q.slot] * D;
+        const int64_t tv = r.voice_embedding ? r.voice_frames : 0;
+        if (tv) {
+            flush();
+            h2d(dst, r.voice_embedding, (size_t)tv * D * sizeof(float), s);
+        }
+        if (run_n == 0) { run_id0 = id0; run_dst = dst + tv * D; }
+        run_n += r.n_tokens;
+        id0 += r.n_tokens;
+    }
+    flush();
+    if (before_prefill) PTTS_HIP(hipEventRecord(before_prefill, s));
+    batch_prompt(b, rows.as<float>(), row_off.data());
+}
+
+void stage_noise(Batch& b, const std::vector<SlotReq>& list, hipStream_t s) {
+    Model& m = *b.m;
+    const int ld = m.d.ldim;
+    const int64_t slot_rows = (int64_t)b.max_steps * ld;
+    float* noise = b.noise.as<float>();
+    for (size_t i = 0; i < list.size();) {   // one memset per run of consecutive slots
+        size_t j = i + 1;
+        while (j < list.size() && list[j].slot == list[j - 1].slot + 1) j++;
+        PTTS_HIP(hipMemsetAsync(noise + list[i].slot * slot_rows, 0, (j - i) * slot_rows * sizeof(float), s));
+        i = j;
+    }
+    std::vector<NoiseSpec> spec((size_t)b.B, NoiseSpec{0, 0.0f, 0});
+    int draw_rows = 0;
+    for (const SlotReq& q : list) {
+        const ptts_request& r = *q.req;
+        if (r.noise) h2d(noise + q.slot * slot_rows, r.noise, (size_t)q.max_steps * ld * sizeof(float), s);
+        else if (r.temperature > 0.0f) {
+            if (ld % 4) throw Error(PTTS_EINVAL, "ptts-hip: the device noise draw needs a latent width that is a multiple of 4");
+            spec[(size_t)q.slot] = NoiseSpec{r.noise_seed ? r.noise_seed : m.next_noise_seed(), std::sqrt(r.temperature), q.max_steps};
+            draw_rows = std::max(draw_rows, q.max_steps);
+        }
+    }
+    if (draw_rows == 0) return;
+    DevBuf& sb = m.work(12, spec.size() * sizeof(NoiseSpec));
+    h2d(sb.p, spec.data(), spec.size() * sizeof(NoiseSpec), s);
+    launch_noise_fill(sb.as<NoiseSpec>(), b.B, draw_rows, noise, slot_rows, ld, s);
+}
+
+const PcmRow* results_alloc(const Model& m, const std::vector<Delivery>& g, PcmRow* host_rows, PcmRow* dev_rows, hipStream_t s) {
+    const int64_t spf = m.d.samples_per_frame;
+    bool all_pinned = true;
+    for (size_t i = 0; i < g.size(); i++) {
+        if (host_rows) host_rows[i] = PcmRow{nullptr, 0, 0};
+        const Delivery& u = g[i];
+        if (!u.res || u.filled) continue;
+        const bool s16 = u.req->pcm_format == PTTS_PCM_S16;
+        const int64_t ns = (int64_t)u.nf * spf;
+        void* p = result_alloc((size_t)std::max<int64_t>(1, ns) * (s16 ? sizeof(int16_t) : sizeof(float)));
+        if (s16) u.res->pcm16 = (int16_t*)p;
+        else u.res->pcm = (float*)p;
+        if (!p) continue;
+        all_pinned = all_pinned && result_is_pinned(p);
+        if (host_rows) host_rows[i] = PcmRow{p, (int32_t)std::min<int64_t>(ns, INT32_MAX), s16 ? 1 : 0};
+    }
+    if (!host_rows || !dev_rows || !all_pinned) return nullptr;
+    PTTS_HIP(hipMemcpyAsync(dev_rows, host_rows, g.size() * sizeof(PcmRow), hipMemcpyHostToDevice, s));   // page-locked source: no wait needed
+    return dev_rows;
+}
+
+void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, const float* pcm, int64_t pcm_stride, const float* lat, int64_t lat_stride,
+                     hipStream_t s) {
+    const int ld = m.d.ldim;
+    const int64_t spf = m.d.samples_per_frame;
+    const int64_t n = (int64_t)g.size();
+    const int16_t* pcm16 = nullptr;   // PCM16 egress on the device (audio/wav_stream.go:43-54), converted for the whole group at the first request that asks for it
+    for (int64_t i = 0; i < n; i++) {
+        const Delivery& u = g[(size_t)i];
+        if (!u.res) continue;
+        ptts_result& r = *u.res;
+        r.n_frames = u.nf; r.eos_step = u.eos; r.n_samples = (int64_t)u.nf * spf;
+        const bool s16 = u.req->pcm_format == PTTS_PCM_S16;
+        if (s16 ? !r.pcm16 : !r.pcm) { r.status = PTTS_ENOMEM; continue; }
+        if (!stored && !u.filled && r.n_samples > 0) {   // all copies are queued back to back: the caller waits once
+            if (s16 && !pcm16) {
+                DevBuf& buf = m.work(8, (size_t)(n * pcm_stride) * sizeof(int16_t));
+                launch_pcm16(pcm, buf.as<int16_t>(), n * pcm_stride, s);
+                pcm16 = buf.as<int16_t>();
+            }
+            if (s16) PTTS_HIP(hipMemcpyAsync(r.pcm16, pcm16 + i * pcm_stride, (size_t)r.n_samples * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+            else PTTS_HIP(hipMemcpyAsync(r.pcm, pcm + i * pcm_stride, (size_t)r.n_samples * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        if (u.req->want_latents) {
+            r.latents = (float*)malloc((size_t)std::max(1, u.nf) * ld * sizeof(float));
+            if (!r.latents) { r.status = PTTS_ENOMEM; continue; }
+            if (u.nf > 0) PTTS_HIP(hipMemcpyAsync(r.latents, lat + i * lat_stride, (size_t)u.nf * ld * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        r.status = PTTS_OK;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // GenerateAudio for a batch of independent utterance chunks
 // ------------------------------------------------------------------------------------------------
 int resolve_max_steps(const ptts_request& r) {  // runtime_native_safetensors.go:61-67, text/prepare.go:38-48
@@ -1369,35 +1496,83 @@ void enqueue_step(Batch& b, int lsd, bool use_graph, int nsteps) {
         launch_step_finish(b.st, b.cur_now(), b.eos.as<float>(), ld, b.B, b.latents.as<float>(), ls, m.stream);
 }
 
-static void fail_req(ptts_result& r, int code) {
-    r.status = code;
-}
+namespace {
+// One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
+// alike: copies, decoder launches and host functions queued on the two streams may still read `cancelled`, `stream_ranges` and
+// `stream_host`, so both streams are drained first, then the streaming buffers go back.
+struct Chunk {
+    Model& m;
+    const ptts_request* reqs; const std::vector<int>& idx; ptts_result* res;   // slot i: reqs[idx[i]], answered in res[idx[i]]
+    const int lsd;
+    const int B = (int)idx.size(), ld = m.d.ldim;
+    const int64_t spf = m.d.samples_per_frame;
+    const hipStream_t s = m.stream;
+    // The decoder's RoPE table ends at ROPE_SEQ positions (mimi.go:498): like the reference, a step budget beyond that is not an
+    // error by itself -- generating that many frames is (the decoder is sized for what can be decoded).
+    const int t_limit = ROPE_SEQ / m.d.up_stride;
+    std::vector<SlotReq> list;   // slot i: reqs[idx[i]] and its step budget
+    int ms_max = 0, T = 0;       // the largest step budget; the frames the decoder is sized for
+    Batch* b = nullptr;
+    std::vector<char> cancelled = std::vector<char>((size_t)B, 0);
+    DevBuf* pcm = nullptr;       // decoded samples, [B][T * spf]
+    int chunk = 1 << 30;         // frames per range decoded under the AR loop (streaming, PTTS_MIMI_CHUNK)
+    bool streaming = false;
+    // Streaming (pcm_callback): ranges of `chunk` frames are decoded on stream2 behind the AR loop, copied into the buffers the results
+    // will own (stream_host) and announced from a host function queued on that stream (a HIP runtime thread).
+    struct StreamRange {
+        const Chunk* c; int f0, f1;
+        int32_t* nf;   // pinned: n_frames of every slot, read after the range's last step
+    };
+    std::vector<void*> stream_host = std::vector<void*>((size_t)B, nullptr);
+    std::vector<std::unique_ptr<StreamRange>> stream_ranges;
+    DevBuf* stream_s16 = nullptr;
+    MimiWs mw;
+    int dec_group = 0;
+    int f_done = 0, f_emitted = 0, steps_run = 0;   // frames decoded, announced, generated
+    size_t ev_used = 0;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
 
-static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector<int>& idx, ptts_result* res, int lsd) {
-    const Desc& d = m.d;
-    hipStream_t s = m.stream;
-    UploadScope upload_scope(m.upload, s);
-    // PTTS_TRACE=1: host wall time of the phases of one call (stderr); each mark drains the stream first
-    static const bool trace = getenv("PTTS_TRACE") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
+    ~Chunk() {
+        (void)hipStreamSynchronize(m.stream2);
+        (void)hipStreamSynchronize(m.stream);
+        for (auto& r : stream_ranges) (void)hipHostFree(r->nf);
+        for (void* p : stream_host) result_free(p);   // buffers of cancelled / failed streaming requests
+    }
+    const ptts_request& req(int i) const { return reqs[idx[(size_t)i]]; }
+    Error too_long(int frames) const {
+        return Error(PTTS_EINVAL, strfmt("generate: mimi_decode: ops: rope cos/sin sequence length too small for pos=0 seq=%lld", (long long)frames * m.d.up_stride));
+    }
+    void mark(const char* what) {   // PTTS_TRACE=1: host wall time of the phases of one call (stderr); each mark drains the streams first
+        static const bool trace = getenv("PTTS_TRACE") != nullptr;
         if (!trace) return;
         (void)hipStreamSynchronize(s);
         (void)hipStreamSynchronize(m.stream2);
         auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[ptts] %-12s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
-    };
-    const int B = (int)idx.size(), D = d.d_model, ld = d.ldim;
-    std::vector<int> ms((size_t)B), tp((size_t)B), off((size_t)B);
-    int cap_need = 0, ms_max = 0;
+    }
+    hipEvent_t phase_event(int i) {   // measurement pass only (ptts_profile_enable): device time of the call's phases
+        if (!m.prof.phases_on) return nullptr;
+        if (!m.prof.phase[i]) PTTS_HIP(hipEventCreate(&m.prof.phase[i]));
+        return m.prof.phase[i];
+    }
+    void phase(int i, hipStream_t st) { if (hipEvent_t e = phase_event(i)) PTTS_HIP(hipEventRecord(e, st)); }
+    void setup(); void decoder_setup(); void ar_loop(); void deliver();   // the phases, in order
+    void decode_upto(int f1, const PcmRow* rows = nullptr, bool* rows_used = nullptr);
+    void emit_upto(int f1);
+};
+
+// the batch, the slots' step budgets and EOS settings, voices, prompts and sampling noise
+void Chunk::setup() {
+    int cap_need = 0;
     for (int i = 0; i < B; i++) {
-        const ptts_request& r = reqs[idx[i]];
-        ms[i] = resolve_max_steps(r);
-        tp[i] = (int)r.n_tokens + (r.voice_embedding ? (int)r.voice_frames : 0);
-        off[i] = r.voice ? reinterpret_cast<const Voice*>(r.voice)->offset : (r.voice_caches ? (int)r.voice_offsets[0] : 0);
-        cap_need = std::max(cap_need, off[i] + tp[i] + ms[i]);
-        ms_max = std::max(ms_max, ms[i]);
+        const ptts_request& r = req(i);
+        const int ms = resolve_max_steps(r);
+        const int tp = (int)r.n_tokens + (r.voice_embedding ? (int)r.voice_frames : 0);
+        const int off = r.voice ? reinterpret_cast<const Voice*>(r.voice)->offset : (r.voice_caches ? (int)r.voice_offsets[0] : 0);
+        list.push_back(SlotReq{i, &r, ms});
+        cap_need = std::max(cap_need, off + tp + ms);
+        ms_max = std::max(ms_max, ms);
     }
     int cap = (cap_need + 63) / 64 * 64;
     if (cap > ROPE_SEQ) throw Error(PTTS_EINVAL, strfmt("ops: rope cos/sin sequence length too small for pos=%d seq=1", cap_need));
@@ -1405,163 +1580,47 @@ static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector
         m.cached_batch.reset();
         m.cached_batch.reset(batch_new(m, B, cap, ms_max));
     }
-    Batch& b = *m.cached_batch;
-    batch_reset(b);
-    {
-        // (a slot stops at most one frame past what the decoder's RoPE table reaches: generating that frame is what the reference reports as the
-        // error, mimi.go:498 -- for that utterance alone; the other utterances of the batch are unaffected)
-        const int dec_limit = ROPE_SEQ / d.up_stride;
-        std::vector<int32_t> v_ms((size_t)B), v_fae((size_t)B);
-        for (int i = 0; i < B; i++) v_ms[(size_t)i] = std::min(ms[(size_t)i], dec_limit + 1);
-        std::vector<float> v_thr((size_t)B);
-        for (int i = 0; i < B; i++) { v_fae[i] = reqs[idx[i]].frames_after_eos; v_thr[i] = reqs[idx[i]].eos_threshold; }
-        h2d(b.st.max_steps, v_ms.data(), (size_t)B * 4, s);
-        h2d(b.st.frames_after_eos, v_fae.data(), (size_t)B * 4, s);
-        h2d(b.st.eos_threshold, v_thr.data(), (size_t)B * 4, s);
-    }
-    {
-        std::map<const Voice*, std::vector<int32_t>> by_voice;
-        for (int i = 0; i < B; i++) {
-            const ptts_request& r = reqs[idx[i]];
-            if (r.voice) by_voice[reinterpret_cast<const Voice*>(r.voice)].push_back(i);
-            else if (r.voice_caches) batch_set_voice(b, i, r.voice_caches, r.voice_cache_steps, r.voice_offsets);
-        }
-        for (auto& kv : by_voice) batch_apply_voice(b, *kv.first, kv.second);
-    }
-    // text (+ voice) embeddings packed as rows (runtime_native_safetensors.go:89-119)
-    std::vector<int64_t> row_off((size_t)B + 1, 0);
-    for (int i = 0; i < B; i++) row_off[i + 1] = row_off[i] + tp[i];
-    const int64_t R = row_off[B];
-    DevBuf& rows = m.work(5, (size_t)R * D * sizeof(float));
-    {
-        std::vector<int64_t> ids;
-        for (int i = 0; i < B; i++) ids.insert(ids.end(), reqs[idx[i]].tokens, reqs[idx[i]].tokens + reqs[idx[i]].n_tokens);
-        DevBuf& dids = m.work(6, ids.size() * sizeof(int64_t));
-        h2d(dids.p, ids.data(), ids.size() * sizeof(int64_t), s);
-        // token rows of consecutive requests are contiguous unless a voice embedding sits between them: one gather per such run
-        // (a batch without voice embeddings is ONE launch instead of one per request)
-        int64_t id0 = 0, run_id0 = 0, run_n = 0;
-        float* run_dst = rows.as<float>();
-        auto flush = [&]() {
-            if (run_n > 0) launch_embed_gather(m.at<float>(d.embed), dids.as<int64_t>() + run_id0, (int)run_n, D, run_dst, s);
-            run_n = 0;
-        };
-        for (int i = 0; i < B; i++) {
-            const ptts_request& r = reqs[idx[i]];
-            float* dst = rows.as<float>() + row_off[i] * D;
-            int64_t tv = r.voice_embedding ? r.voice_frames : 0;
-            if (tv) {
-                flush();
-                h2d(dst, r.voice_embedding, (size_t)tv * D * sizeof(float), s);
-            }
-            if (run_n == 0) { run_id0 = id0; run_dst = dst + tv * D; }
-            run_n += r.n_tokens;
-            id0 += r.n_tokens;
-        }
-        flush();
-    }
+    b = m.cached_batch.get();
+    batch_reset(*b);
+    // (a slot stops at most one frame past what the decoder's RoPE table reaches: generating that frame is what the reference reports as the
+    // error, mimi.go:498 -- for that utterance alone; the other utterances of the batch are unaffected)
+    std::vector<int32_t> v_ms((size_t)B), v_fae((size_t)B);
+    std::vector<float> v_thr((size_t)B);
+    for (int i = 0; i < B; i++) { v_ms[i] = std::min(list[i].max_steps, t_limit + 1); v_fae[i] = req(i).frames_after_eos; v_thr[i] = req(i).eos_threshold; }
+    h2d(b->st.max_steps, v_ms.data(), (size_t)B * 4, s);
+    h2d(b->st.frames_after_eos, v_fae.data(), (size_t)B * 4, s);
+    h2d(b->st.eos_threshold, v_thr.data(), (size_t)B * 4, s);
     mark("setup");
-    auto phase = [&](int i, hipStream_t st) {   // measurement pass only (ptts_profile_enable): device time of the call's phases
-        if (!m.prof.phases_on) return;
-        if (!m.prof.phase[i]) PTTS_HIP(hipEventCreate(&m.prof.phase[i]));
-        PTTS_HIP(hipEventRecord(m.prof.phase[i], st));
-    };
     m.prof.phases = false;
-    phase(0, s);
-    batch_prompt(b, rows.as<float>(), row_off.data());
+    stage_prompt(*b, list, s, phase_event(0));
     phase(1, s);
     mark("prefill");
-    // sampling noise (flow_lm.go:283-288,386-408): injected rows as they are; otherwise N(0,1) * sqrt(temperature) drawn on the
-    // device per (seed, step); temperature <= 0: zeros.  All of it is resident before the first step, so the AR loop (plain
-    // launches or graph replay) just reads row `step` of its slot.
-    bool any_noise = false, any_draw = false;
-    for (int i = 0; i < B; i++) {
-        const ptts_request& r = reqs[idx[i]];
-        any_noise |= r.noise != nullptr || r.temperature > 0.0f;
-        any_draw |= r.noise == nullptr && r.temperature > 0.0f;
-    }
-    b.has_noise = any_noise;
-    if (any_noise) {
-        size_t n = (size_t)B * b.max_steps * ld;
-        b.noise.ensure(n * sizeof(float));
-        PTTS_HIP(hipMemsetAsync(b.noise.p, 0, n * sizeof(float), s));
-        for (int i = 0; i < B; i++)
-            if (reqs[idx[i]].noise) h2d(b.noise.as<float>() + (size_t)i * b.max_steps * ld, reqs[idx[i]].noise, (size_t)ms[i] * ld * sizeof(float), s);
-        if (any_draw) {
-            if (ld % 4) throw Error(PTTS_EINVAL, "ptts-hip: the device noise draw needs a latent width that is a multiple of 4");
-            std::vector<NoiseSpec> spec((size_t)B);
-            for (int i = 0; i < B; i++) {
-                const ptts_request& r = reqs[idx[i]];
-                const bool draw = r.noise == nullptr && r.temperature > 0.0f;
-                spec[(size_t)i] = NoiseSpec{draw ? (r.noise_seed ? r.noise_seed : m.next_noise_seed()) : 0, draw ? std::sqrt(r.temperature) : 0.0f, draw ? ms[i] : 0};
-            }
-            DevBuf& sb = m.work(12, spec.size() * sizeof(NoiseSpec));
-            h2d(sb.p, spec.data(), spec.size() * sizeof(NoiseSpec), s);
-            launch_noise_fill(sb.as<NoiseSpec>(), B, ms_max, b.noise.as<float>(), (int64_t)b.max_steps * ld, ld, s);
-        }
-    }
-    m.tcomb_for(lsd);
-    // PTTS_GRAPH=0/1 overrides the option (A/B measurement, tools/eager_vs_graph.py)
-    static const int env_graph = [] { const char* e = getenv("PTTS_GRAPH"); return e ? atoi(e) : -1; }();
-    const bool use_graph = (env_graph >= 0 ? env_graph != 0 : m.opts.use_graph != 0) && !m.prof.on;
-    bool may_stop = false, any_cb = false;
-    for (int i = 0; i < B; i++) {
-        may_stop |= reqs[idx[i]].eos_threshold < 1e30f;
-        any_cb |= reqs[idx[i]].step_callback != nullptr;
-    }
-    std::vector<char> cancelled((size_t)B, 0);
-    std::vector<int32_t> act((size_t)B, 1);
-    // Mimi decode of finished frame ranges runs on a second stream while the AR loop keeps stepping: the loop is a chain
-    // of latency-bound launches that leaves most of the chip idle, the decoder is throughput work, and every decoder op is
-    // causal, so frames [f0, f1) can be decoded as soon as step f1-1 has finished.
-    const int64_t spf = d.samples_per_frame;
-    // The decoder's RoPE table ends at ROPE_SEQ positions (mimi.go:498): like the reference, a step budget beyond that is not an
-    // error by itself -- generating that many frames is (the decoder is sized for what can be decoded).
-    const int t_limit = ROPE_SEQ / d.up_stride;
-    const int T = std::min(ms_max, t_limit);
-    auto too_long = [&](int frames) {
-        return Error(PTTS_EINVAL, strfmt("generate: mimi_decode: ops: rope cos/sin sequence length too small for pos=0 seq=%lld", (long long)frames * d.up_stride));
-    };
-    DevBuf& pcm = m.work(7, (size_t)B * T * spf * sizeof(float));
+    b->has_noise = false;
+    for (int i = 0; i < B; i++) b->has_noise |= req(i).noise != nullptr || req(i).temperature > 0.0f;
+    if (!b->has_noise) return;
+    b->noise.ensure((size_t)B * b->max_steps * ld * sizeof(float));
+    stage_noise(*b, list, s);
+}
+
+// Mimi decode of finished frame ranges runs on a second stream while the AR loop keeps stepping: the loop is a chain of latency-bound
+// launches that leaves most of the chip idle, the decoder is throughput work, and every decoder op is causal, so frames [f0, f1) can be
+// decoded as soon as step f1-1 has finished.
+void Chunk::decoder_setup() {
+    T = std::min(ms_max, t_limit);
+    pcm = &m.work(7, (size_t)B * T * spf * sizeof(float));
     const char* env_chunk = getenv("PTTS_MIMI_CHUNK");
-    int chunk = env_chunk && atoi(env_chunk) > 0 ? atoi(env_chunk) : 1 << 30;   // default: decode after the loop (measured: overlapping
-                                                                                // slows the AR launches by as much as it hides)
-    // Streaming (pcm_callback): ranges of `chunk` frames are decoded on stream2 behind the AR loop, copied into the buffers
-    // the results will own and announced from a host function queued on that stream (a HIP runtime thread).
-    struct StreamChunk {
-        const ptts_request* reqs; const int* idx; const char* cancelled; void* const* host; int B;
-        int f0, f1; int64_t spf;
-        int32_t* nf;   // pinned: n_frames of every slot, read after the range's last step
-    };
-    bool streaming = false;
-    for (int i = 0; i < B; i++) streaming |= reqs[idx[i]].pcm_callback != nullptr;
-    std::vector<void*> stream_host((size_t)B, nullptr);
-    std::vector<std::unique_ptr<StreamChunk>> stream_chunks;
-    std::vector<int32_t*> stream_nf;
-    DevBuf* stream_s16 = nullptr;
-    // Error path: a throw below may leave copies, decoder launches and host functions queued on the two streams that still read
-    // `cancelled`, `stream_chunks`, `stream_host` (declared above, destroyed after this guard): drain both streams first, then
-    // give the streaming buffers back.  Dismissed on the normal path, which does the same things in order.
-    struct Unwind {
-        Model& m; std::vector<void*>& host; std::vector<int32_t*>& nf; bool armed = true;
-        ~Unwind() {
-            if (!armed) return;
-            (void)hipStreamSynchronize(m.stream2);
-            (void)hipStreamSynchronize(m.stream);
-            for (int32_t* p : nf) (void)hipHostFree(p);
-            nf.clear();
-            for (void*& p : host) { result_free(p); p = nullptr; }
-        }
-    } unwind{m, stream_host, stream_nf};
+    chunk = env_chunk && atoi(env_chunk) > 0 ? atoi(env_chunk) : 1 << 30;   // default: decode after the loop (measured: overlapping
+                                                                            // slows the AR launches by as much as it hides)
+    for (int i = 0; i < B; i++) streaming |= req(i).pcm_callback != nullptr;
     if (streaming) {
         chunk = 1 << 30;
         bool any_s16 = false;
         for (int i = 0; i < B; i++) {
-            const ptts_request& r = reqs[idx[i]];
+            const ptts_request& r = req(i);
             if (!r.pcm_callback) continue;
             chunk = std::min(chunk, r.stream_frames > 0 ? (int)r.stream_frames : 12);
             const size_t esz = r.pcm_format == PTTS_PCM_S16 ? sizeof(int16_t) : sizeof(float);
-            stream_host[(size_t)i] = result_alloc((size_t)std::max<int64_t>(1, (int64_t)ms[i] * spf) * esz);
+            stream_host[(size_t)i] = result_alloc((size_t)std::max<int64_t>(1, (int64_t)list[i].max_steps * spf) * esz);
             if (!stream_host[(size_t)i]) throw Error(PTTS_ENOMEM, "ptts-hip: out of host memory");
             any_s16 |= r.pcm_format == PTTS_PCM_S16;
         }
@@ -1570,219 +1629,173 @@ static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector
     // Decoder workspace (~2.7 MB of f32 activations per latent frame and utterance).  A batch of more than kMimiGroup utterances that is decoded in one go after the
     // loop (the default) goes through the decoder group after group in the SAME buffers (stream order keeps them apart); a batch whose frame ranges are decoded under
     // the loop (streaming, PTTS_MIMI_CHUNK) needs every utterance's history from range to range and keeps one workspace for all of them.
-    const int dec_group = (B > kMimiGroup && !streaming && chunk > ms_max) ? kMimiGroup : B;
-    MimiWs mw;
+    dec_group = (B > kMimiGroup && !streaming && chunk > ms_max) ? kMimiGroup : B;
     mimi_setup(m, mw, dec_group, T);
     mimi_zero_history(m, mw, m.stream2);   // nine small launches: under the AR loop instead of between the loop and the decoder
-    int f_done = 0, f_emitted = 0, steps_run = 0;
-    size_t ev_used = 0;
-    auto next_event = [&]() {
-        if (m.events.size() <= ev_used) { hipEvent_t e; PTTS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m.events.push_back(e); }
-        return m.events[ev_used++];
-    };
-    const PcmRow* pcm_rows = nullptr;
-    bool* rows_used = nullptr;
-    auto decode_upto = [&](int f1) {
-        if (f1 <= f_done) return;
-        if (f1 > T) throw too_long(f1);
-        hipEvent_t e = next_event();
-        PTTS_HIP(hipEventRecord(e, s));
-        PTTS_HIP(hipStreamWaitEvent(m.stream2, e, 0));
-        const int64_t lstride = (int64_t)b.max_steps * ld;
-        int direct = 0, groups = 0;
-        for (int g0 = 0; g0 < B; g0 += dec_group, groups++) {
-            const int nb = std::min(dec_group, B - g0);
-            MimiWs wg;
-            MimiWs* w = &mw;
-            if (nb != mw.B) { mimi_setup(m, wg, nb, T); w = &wg; }   // the last, smaller group: its own layout inside the same (grow-only) buffer
-            if (g0 > 0) w->zeroed = false;                           // (a group's history rows: zeroed again in front of its decode)
-            bool used = false;
-            mimi_range(m, *w, b.latents.as<float>() + (int64_t)g0 * lstride, lstride, f_done, f1, pcm.as<float>() + (size_t)g0 * T * spf, nullptr, m.stream2,
-                       (f_done == 0 && pcm_rows) ? pcm_rows + g0 : nullptr, &used);
-            direct += used ? 1 : 0;
-        }
-        if (direct != 0 && direct != groups) throw Error(PTTS_EINVAL, "ptts-hip: internal: the decoder's groups disagree about the direct PCM rows");
-        if (rows_used) *rows_used = direct != 0;
-        f_done = f1;
-    };
-    auto emit_upto = [&](int f1) {   // hand frames [f_emitted, f1) to the streaming callbacks (they are decoded: f1 <= f_done)
-        if (!streaming || f1 <= f_emitted) return;
-        const int f0 = f_emitted;
-        hipStream_t s2 = m.stream2;
-        if (stream_s16) launch_pcm16_rows(pcm.as<float>(), stream_s16->as<int16_t>(), B, (int64_t)T * spf, (int64_t)f0 * spf, (int64_t)(f1 - f0) * spf, s2);
-        for (int i = 0; i < B; i++) {
-            if (!stream_host[(size_t)i]) continue;
-            const int fe = std::min(f1, ms[i]);
-            if (fe <= f0) continue;
-            const bool s16 = reqs[idx[i]].pcm_format == PTTS_PCM_S16;
-            const size_t esz = s16 ? sizeof(int16_t) : sizeof(float);
-            const char* src = s16 ? (const char*)stream_s16->p : (const char*)pcm.p;
-            PTTS_HIP(hipMemcpyAsync((char*)stream_host[(size_t)i] + (size_t)f0 * spf * esz, src + ((size_t)i * T * spf + (size_t)f0 * spf) * esz,
-                                    (size_t)(fe - f0) * spf * esz, hipMemcpyDeviceToHost, s2));
-        }
-        int32_t* nfp = nullptr;
-        PTTS_HIP(hipHostMalloc((void**)&nfp, (size_t)B * sizeof(int32_t), hipHostMallocDefault));
-        stream_nf.push_back(nfp);
-        PTTS_HIP(hipMemcpyAsync(nfp, b.st.n_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
-        stream_chunks.emplace_back(new StreamChunk{reqs, idx.data(), cancelled.data(), stream_host.data(), B, f0, f1, spf, nfp});
-        PTTS_HIP(hipLaunchHostFunc(s2, [](void* p) {
-            const StreamChunk& c = *static_cast<const StreamChunk*>(p);
-            for (int i = 0; i < c.B; i++) {
-                const ptts_request& r = c.reqs[c.idx[i]];
-                if (!r.pcm_callback || !c.host[i] || c.cancelled[i]) continue;
-                const int end = std::min(c.f1, (int)c.nf[i]);   // frames past the utterance's end are not audio
-                if (end <= c.f0) continue;
-                const size_t esz = r.pcm_format == PTTS_PCM_S16 ? sizeof(int16_t) : sizeof(float);
-                r.pcm_callback(r.pcm_user, (int64_t)c.f0 * c.spf, (int64_t)(end - c.f0) * c.spf, (const char*)c.host[i] + (size_t)c.f0 * c.spf * esz);
-            }
-        }, stream_chunks.back().get()));
-        f_emitted = f1;
-    };
+}
+
+void Chunk::ar_loop() {
+    m.tcomb_for(lsd);
+    // PTTS_GRAPH=0/1 overrides the option (A/B measurement, tools/eager_vs_graph.py)
+    static const int env_graph = [] { const char* e = getenv("PTTS_GRAPH"); return e ? atoi(e) : -1; }();
+    const bool use_graph = (env_graph >= 0 ? env_graph != 0 : m.opts.use_graph != 0) && !m.prof.on;
+    bool may_stop = false, any_cb = false, any_cancel_flag = false;
+    for (int i = 0; i < B; i++) {
+        may_stop |= req(i).eos_threshold < 1e30f;
+        any_cb |= req(i).step_callback != nullptr;
+        any_cancel_flag |= req(i).cancel != nullptr;
+    }
+    std::vector<int32_t> act((size_t)B, 1);
     // graph replay without per-step host work (no step callbacks, no cancel flags, no ranges to decode on the way): several
     // steps per graph.  Slots that finish inside a graph are skipped by every kernel of the remaining steps (active flags).
     // 5 steps per graph; 25 when no request of the batch can end by EOS (threshold = +inf: every budget is known, so no replayed step can turn out to
     // have been for nothing) -- measured on the 125-step batch: 1 -> 5 steps: -0.2..-0.6 ms, 5 -> 25: -0.5 ms, 125: -0.15 (one big graph is slower again)
     static const int env_gsteps = [] { const char* e = getenv("PTTS_GRAPH_STEPS"); return e ? std::max(1, atoi(e)) : 0; }();
-    bool any_cancel_flag = false;
-    for (int i = 0; i < B; i++) any_cancel_flag |= reqs[idx[i]].cancel != nullptr;
     const int gsteps = (use_graph && !any_cb && !any_cancel_flag && chunk > ms_max) ? (env_gsteps ? env_gsteps : (may_stop ? 5 : 25)) : 1;
     const int ms_loop = std::min(ms_max, t_limit + 1);
     for (int step = 0; step < ms_loop;) {
         int n_cancel = 0;
         for (int i = 0; i < B; i++) {  // ctx.Err() check before every step (:156-159)
-            const ptts_request& r = reqs[idx[i]];
+            const ptts_request& r = req(i);
             if (r.cancel && *r.cancel) cancelled[i] = 1;
             n_cancel += cancelled[i];
         }
         if (n_cancel == B) break;
         const int n_now = (gsteps > 1 && step + gsteps <= ms_loop) ? gsteps : (gsteps > 5 && step + 5 <= ms_loop) ? 5 : 1;   // the tail: smaller graphs
-        enqueue_step(b, lsd, use_graph, n_now);
+        enqueue_step(*b, lsd, use_graph, n_now);
         step += n_now;
         steps_run = step;
         if (steps_run % chunk == 0) { decode_upto(steps_run); emit_upto(steps_run); }
         if (any_cb) {  // StepCallback runs synchronously after the step (:194-196)
             std::vector<int32_t> before = act, broke((size_t)B);
-            d2h(act.data(), b.st.active, (size_t)B * 4, s);
-            d2h(broke.data(), b.st.broke, (size_t)B * 4, s);
+            d2h(act.data(), b->st.active, (size_t)B * 4, s);
+            d2h(broke.data(), b->st.broke, (size_t)B * 4, s);
             for (int i = 0; i < B; i++) {  // not called for the iteration that leaves through `break` (:185-187)
-                const ptts_request& r = reqs[idx[i]];
-                if (r.step_callback && before[i] && !broke[i] && !cancelled[i]) r.step_callback(r.callback_user, step, ms[i]);
+                const ptts_request& r = req(i);
+                if (r.step_callback && before[i] && !broke[i] && !cancelled[i]) r.step_callback(r.callback_user, step, list[i].max_steps);
             }
-            bool any = false;
-            for (int i = 0; i < B; i++) any |= act[i] != 0;
-            if (!any) break;
+            if (std::none_of(act.begin(), act.end(), [](int32_t a) { return a != 0; })) break;
         } else if (may_stop && step / 8 != (step - n_now) / 8) {   // every eighth step (or the first graph boundary past it)
-            PTTS_HIP(hipMemcpyAsync(b.n_active_pinned, b.st.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            PTTS_HIP(hipMemcpyAsync(b->n_active_pinned, b->st.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             PTTS_HIP(hipStreamSynchronize(s));
-            if (*b.n_active_pinned <= 0) break;
+            if (*b->n_active_pinned <= 0) break;
         }
     }
     phase(2, s);
     mark("ar loop");
-    // n_frames and eos_step sit side by side in the state block: one copy into page-locked memory, one wait
-    PTTS_HIP(hipMemcpyAsync(b.n_active_pinned + 1, b.st.n_frames, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    b.n_active_pinned[1 + 2 * B] = 0;
-    if (b.fc_ok) PTTS_HIP(hipMemcpyAsync(b.n_active_pinned + 1 + 2 * B, b.fc_fault(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PTTS_HIP(hipStreamSynchronize(s));
-    if (b.n_active_pinned[1 + 2 * B]) flow_cluster_fault(b);
-    const std::vector<int32_t> nf(b.n_active_pinned + 1, b.n_active_pinned + 1 + B), es(b.n_active_pinned + 1 + B, b.n_active_pinned + 1 + 2 * B);
-    int Tmax = 0;
-    std::vector<char> overlong((size_t)B, 0);   // utterances that ran past the decoder's reach: failed one by one, like the reference's one GenerateAudio call
+}
+
+// frames [f_done, f1) of every utterance through the decoder on stream2, behind the steps queued so far; rows (whole range only): the
+// decoder's direct store (results_alloc), *rows_used: whether it took it
+void Chunk::decode_upto(int f1, const PcmRow* rows, bool* rows_used) {
+    if (f1 <= f_done) return;
+    if (f1 > T) throw too_long(f1);
+    if (m.events.size() <= ev_used) { hipEvent_t e; PTTS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m.events.push_back(e); }
+    hipEvent_t e = m.events[ev_used++];
+    PTTS_HIP(hipEventRecord(e, s));
+    PTTS_HIP(hipStreamWaitEvent(m.stream2, e, 0));
+    const int64_t lstride = (int64_t)b->max_steps * ld;
+    int direct = 0, groups = 0;
+    for (int g0 = 0; g0 < B; g0 += dec_group, groups++) {
+        const int nb = std::min(dec_group, B - g0);
+        MimiWs wg;
+        MimiWs* w = &mw;
+        if (nb != mw.B) { mimi_setup(m, wg, nb, T); w = &wg; }   // the last, smaller group: its own layout inside the same (grow-only) buffer
+        if (g0 > 0) w->zeroed = false;                           // (a group's history rows: zeroed again in front of its decode)
+        bool used = false;
+        mimi_range(m, *w, b->latents.as<float>() + (int64_t)g0 * lstride, lstride, f_done, f1, pcm->as<float>() + (size_t)g0 * T * spf, nullptr, m.stream2,
+                   (f_done == 0 && rows) ? rows + g0 : nullptr, &used);
+        direct += used ? 1 : 0;
+    }
+    if (direct != 0 && direct != groups) throw Error(PTTS_EINVAL, "ptts-hip: internal: the decoder's groups disagree about the direct PCM rows");
+    if (rows_used) *rows_used = direct != 0;
+    f_done = f1;
+}
+
+// hand frames [f_emitted, f1) to the streaming callbacks (they are decoded: f1 <= f_done)
+void Chunk::emit_upto(int f1) {
+    if (!streaming || f1 <= f_emitted) return;
+    const int f0 = f_emitted;
+    hipStream_t s2 = m.stream2;
+    if (stream_s16) launch_pcm16_rows(pcm->as<float>(), stream_s16->as<int16_t>(), B, (int64_t)T * spf, (int64_t)f0 * spf, (int64_t)(f1 - f0) * spf, s2);
     for (int i = 0; i < B; i++) {
-        overlong[(size_t)i] = !cancelled[i] && nf[i] > t_limit;
-        if (overlong[(size_t)i]) set_last_error(too_long(nf[i]).what());
-        if (!cancelled[i] && !overlong[(size_t)i]) Tmax = std::max(Tmax, nf[i]);
+        if (!stream_host[(size_t)i]) continue;
+        const int fe = std::min(f1, list[i].max_steps);
+        if (fe <= f0) continue;
+        const bool s16 = req(i).pcm_format == PTTS_PCM_S16;
+        const size_t esz = s16 ? sizeof(int16_t) : sizeof(float);
+        const char* src = s16 ? (const char*)stream_s16->p : (const char*)pcm->p;
+        PTTS_HIP(hipMemcpyAsync((char*)stream_host[(size_t)i] + (size_t)f0 * spf * esz, src + ((size_t)i * T * spf + (size_t)f0 * spf) * esz,
+                                (size_t)(fe - f0) * spf * esz, hipMemcpyDeviceToHost, s2));
     }
-    if (Tmax > 0) {
-        DevBuf* pcm_s16 = nullptr;   // PCM16 egress on the device (audio/wav_stream.go:43-54) for the requests that ask for it
-        bool any_s16 = false;
-        for (int i = 0; i < B; i++) any_s16 |= reqs[idx[i]].pcm_format == PTTS_PCM_S16 && !cancelled[i] && !stream_host[(size_t)i];
-        if (any_s16) pcm_s16 = &m.work(8, (size_t)B * T * spf * sizeof(int16_t));
-        std::vector<void*> host_dst((size_t)B, nullptr);   // page-locked result buffers allocated ahead of the decoder (direct rows)
-        bool direct_done = false;                          // the decoder's last kernel wrote the samples into host_dst itself
-        // results of utterances [b0, b1): buffers, and the copies queued on s
-        auto finish_rows = [&](int b0, int b1) {
-        for (int i = b0; i < b1; i++) {
-            ptts_result& r = res[idx[i]];
-            if (cancelled[i]) { fail_req(r, PTTS_ECANCELLED); continue; }
-            if (overlong[(size_t)i]) { fail_req(r, PTTS_EINVAL); result_free(host_dst[(size_t)i]); host_dst[(size_t)i] = nullptr; continue; }
-            r.n_frames = nf[i];
-            r.eos_step = es[i];
-            r.n_samples = (int64_t)nf[i] * spf;
-            if (stream_host[(size_t)i]) {   // streamed: the buffer already holds every sample that was announced
-                if (reqs[idx[i]].pcm_format == PTTS_PCM_S16) r.pcm16 = (int16_t*)stream_host[(size_t)i];
-                else r.pcm = (float*)stream_host[(size_t)i];
-                stream_host[(size_t)i] = nullptr;
-            } else if (reqs[idx[i]].pcm_format == PTTS_PCM_S16) {
-                r.pcm16 = (int16_t*)(host_dst[(size_t)i] ? host_dst[(size_t)i] : result_alloc((size_t)std::max<int64_t>(1, r.n_samples) * sizeof(int16_t)));
-                host_dst[(size_t)i] = nullptr;
-                if (!r.pcm16) { fail_req(r, PTTS_ENOMEM); continue; }
-                if (r.n_samples > 0 && !direct_done)
-                    PTTS_HIP(hipMemcpyAsync(r.pcm16, pcm_s16->as<int16_t>() + (size_t)i * T * spf, (size_t)r.n_samples * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-            } else {
-                r.pcm = (float*)(host_dst[(size_t)i] ? host_dst[(size_t)i] : result_alloc((size_t)std::max<int64_t>(1, r.n_samples) * sizeof(float)));
-                host_dst[(size_t)i] = nullptr;
-                if (!r.pcm) { fail_req(r, PTTS_ENOMEM); continue; }
-                if (r.n_samples > 0 && !direct_done)   // all copies are queued back to back; one wait below
-                    PTTS_HIP(hipMemcpyAsync(r.pcm, pcm.as<float>() + (size_t)i * T * spf, (size_t)r.n_samples * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            if (reqs[idx[i]].want_latents) {
-                r.latents = (float*)malloc((size_t)std::max(1, nf[i]) * ld * sizeof(float));
-                if (!r.latents) { fail_req(r, PTTS_ENOMEM); continue; }
-                d2h(r.latents, b.latents.as<float>() + (size_t)i * b.max_steps * ld, (size_t)nf[i] * ld * sizeof(float), s);
-            }
-            r.status = PTTS_OK;
+    int32_t* nfp = nullptr;
+    PTTS_HIP(hipHostMalloc((void**)&nfp, (size_t)B * sizeof(int32_t), hipHostMallocDefault));
+    stream_ranges.emplace_back(new StreamRange{this, f0, f1, nfp});
+    PTTS_HIP(hipMemcpyAsync(nfp, b->st.n_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+    PTTS_HIP(hipLaunchHostFunc(s2, [](void* p) {
+        const StreamRange& sr = *static_cast<const StreamRange*>(p);
+        const Chunk& c = *sr.c;
+        for (int i = 0; i < c.B; i++) {
+            const ptts_request& r = c.req(i);
+            if (!r.pcm_callback || !c.stream_host[(size_t)i] || c.cancelled[(size_t)i]) continue;
+            const int end = std::min(sr.f1, (int)sr.nf[i]);   // frames past the utterance's end are not audio
+            if (end <= sr.f0) continue;
+            const size_t esz = r.pcm_format == PTTS_PCM_S16 ? sizeof(int16_t) : sizeof(float);
+            r.pcm_callback(r.pcm_user, (int64_t)sr.f0 * c.spf, (int64_t)(end - sr.f0) * c.spf, (const char*)c.stream_host[(size_t)i] + (size_t)sr.f0 * c.spf * esz);
         }
-        };
-        // Whole batch decoded in one go (the default): the decoder's last kernel stores every utterance's samples straight into
-        // its page-locked result buffer (f32 or int16) -- the kernel's stores ARE the device->host transfer: no device PCM buffer,
-        // no copies, no copy kernels competing with the decoder.
-        const bool try_direct = !streaming && f_done == 0;
-        const PcmRow* d_rows = nullptr;
-        if (try_direct) {
-            PcmRow* rows = b.rows_pinned;
-            for (int i = 0; i < B; i++) rows[i] = PcmRow{nullptr, 0, 0};
-            for (int i = 0; i < B; i++) {
-                if (cancelled[i] || overlong[(size_t)i]) continue;
-                const bool s16 = reqs[idx[i]].pcm_format == PTTS_PCM_S16;
-                const int64_t ns = (int64_t)nf[i] * spf;
-                host_dst[(size_t)i] = result_alloc((size_t)std::max<int64_t>(1, ns) * (s16 ? sizeof(int16_t) : sizeof(float)));
-                if (!host_dst[(size_t)i]) continue;   // reported as PTTS_ENOMEM by finish_rows
-                rows[i] = PcmRow{host_dst[(size_t)i], (int32_t)std::min<int64_t>(ns, INT32_MAX), s16 ? 1 : 0};
-            }
-            // a kernel may only store into page-locked memory: if the pool had to fall back to pageable blocks (hipHostMalloc
-            // failed), the whole batch takes the device buffer + copy path instead
-            bool all_pinned = true;
-            for (int i = 0; i < B; i++) all_pinned &= !host_dst[(size_t)i] || result_is_pinned(host_dst[(size_t)i]);
-            if (all_pinned) {
-                DevBuf& rb = m.work(11, (size_t)B * sizeof(PcmRow));
-                PTTS_HIP(hipMemcpyAsync(rb.p, rows, (size_t)B * sizeof(PcmRow), hipMemcpyHostToDevice, s));   // page-locked source: no wait needed
-                d_rows = rb.as<PcmRow>();
-            }
-        }
-        pcm_rows = d_rows; rows_used = &direct_done;
-        if (m.prof.phases_on) { PTTS_HIP(hipStreamWaitEvent(m.stream2, m.prof.phase[2], 0)); phase(3, m.stream2); }
-        decode_upto(std::min(steps_run, Tmax));   // frames past every utterance's end are never decoded
-        pcm_rows = nullptr; rows_used = nullptr;
-        emit_upto(std::min(steps_run, Tmax));
-        phase(4, m.stream2);
-        m.prof.phases = m.prof.phases_on && f_done > 0;
-        PTTS_HIP(hipStreamSynchronize(m.stream2));
-        for (int32_t* p : stream_nf) (void)hipHostFree(p);
-        stream_nf.clear();
-        mark("mimi");
-        if (pcm_s16 && !direct_done) launch_pcm16(pcm.as<float>(), pcm_s16->as<int16_t>(), (int64_t)B * T * spf, s);
-        finish_rows(0, B);
-        for (void* p : host_dst) result_free(p);   // rows that were allocated but not handed out (failed requests)
-        PTTS_HIP(hipStreamSynchronize(s));
-        mark("results d2h");
-    } else {
-        PTTS_HIP(hipStreamSynchronize(m.stream2));
-        for (int32_t* p : stream_nf) (void)hipHostFree(p);
-        for (int i = 0; i < B; i++) fail_req(res[idx[i]], overlong[(size_t)i] ? PTTS_EINVAL : PTTS_ECANCELLED);
+    }, stream_ranges.back().get()));
+    f_emitted = f1;
+}
+
+// the frame counts back; the decode of what has not been decoded under the loop; the results
+void Chunk::deliver() {
+    // n_frames and eos_step sit side by side in the state block: one copy into page-locked memory, one wait
+    int32_t* const hp = b->n_active_pinned;
+    PTTS_HIP(hipMemcpyAsync(hp + 1, b->st.n_frames, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    hp[1 + 2 * B] = 0;
+    if (b->fc_ok) PTTS_HIP(hipMemcpyAsync(hp + 1 + 2 * B, b->fc_fault(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PTTS_HIP(hipStreamSynchronize(s));
+    if (hp[1 + 2 * B]) flow_cluster_fault(*b);
+    const int32_t* nf = hp + 1;
+    int Tmax = 0;
+    std::vector<Delivery> g((size_t)B);   // row i of the decode: slot i (cancelled and over-long utterances are decoded, not delivered)
+    for (int i = 0; i < B; i++) {
+        const bool overlong = !cancelled[i] && nf[i] > t_limit;   // ran past the decoder's reach: failed one by one, like the reference's one GenerateAudio call
+        if (overlong) set_last_error(too_long(nf[i]).what());
+        if (cancelled[i] || overlong) { res[idx[i]].status = cancelled[i] ? PTTS_ECANCELLED : PTTS_EINVAL; continue; }
+        g[(size_t)i] = Delivery{&req(i), &res[idx[i]], nf[i], hp[1 + B + i], stream_host[(size_t)i] != nullptr};
+        Tmax = std::max(Tmax, nf[i]);
     }
-    for (void* p : stream_host) result_free(p);   // buffers of cancelled / failed streaming requests
-    unwind.armed = false;
+    // Whole batch decoded in one go (the default): the decoder's last kernel stores the samples into the result buffers itself
+    const bool try_direct = !streaming && f_done == 0;
+    const PcmRow* rows = results_alloc(m, g, try_direct ? b->rows_pinned : nullptr, try_direct ? m.work(11, (size_t)B * sizeof(PcmRow)).as<PcmRow>() : nullptr, s);
+    if (m.prof.phases_on) { PTTS_HIP(hipStreamWaitEvent(m.stream2, m.prof.phase[2], 0)); phase(3, m.stream2); }
+    bool stored = false;
+    decode_upto(std::min(steps_run, Tmax), rows, &stored);   // frames past every utterance's end are never decoded
+    emit_upto(std::min(steps_run, Tmax));
+    phase(4, m.stream2);
+    m.prof.phases = m.prof.phases_on && f_done > 0;
+    PTTS_HIP(hipStreamSynchronize(m.stream2));
+    mark("mimi");
+    for (int i = 0; i < B; i++) {   // streamed: the buffer already holds every sample that was announced
+        if (!g[(size_t)i].filled) continue;
+        if (req(i).pcm_format == PTTS_PCM_S16) res[idx[i]].pcm16 = (int16_t*)stream_host[(size_t)i];
+        else res[idx[i]].pcm = (float*)stream_host[(size_t)i];
+        stream_host[(size_t)i] = nullptr;
+    }
+    results_deliver(m, g, stored, pcm->as<float>(), (int64_t)T * spf, b->latents.as<float>(), (int64_t)b->max_steps * ld, s);
+    PTTS_HIP(hipStreamSynchronize(s));
+    mark("results d2h");
+}
+}  // namespace
+
+static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector<int>& idx, ptts_result* res, int lsd) {
+    UploadScope upload_scope(m.upload, m.stream);
+    Chunk c{m, reqs, idx, res, lsd};
+    c.setup();
+    c.decoder_setup();
+    c.ar_loop();
+    c.deliver();
 }
 
 std::string request_error(const Desc& d, const ptts_request& q) {   // the argument checks of GenerateAudio (runtime_native_safetensors.go:52-119)

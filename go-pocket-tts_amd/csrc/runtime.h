@@ -237,6 +237,34 @@ void d2h(void* dst, const void* src, size_t bytes, hipStream_t s);
 int resolve_max_steps(const ptts_request& r);                                   // runtime_native_safetensors.go:61-67
 void enqueue_step(Batch& b, int lsd, bool use_graph, int nsteps = 1);           // nsteps > 1 only with use_graph
 void mimi_zero_history(Model& m, MimiWs& w, hipStream_t s);
+// Request staging and result delivery, one copy for generate() (every slot of its batch) and the continuous batch (its newcomers /
+// each group of finished utterances).  The callers keep their own bookkeeping: batch_reset or the slots' host state, the step
+// budgets and EOS settings, their UploadScope.
+struct SlotReq { int slot; const ptts_request* req; int max_steps; };   // max_steps: resolve_max_steps(*req)
+// voices (device voices grouped per Voice, host caches slot by slot), prompt rows packed per slot (list: ascending slots; the others get
+// empty segments), embedding gather, batch_prompt; before_prefill (optional) is recorded on s just in front of batch_prompt
+void stage_prompt(Batch& b, const std::vector<SlotReq>& list, hipStream_t s, hipEvent_t before_prefill = nullptr);
+// the listed slots' noise rows (b.noise, [B][max_steps][ldim]), sampling noise as flow_lm.go:283-288,386-408 makes it: injected rows as
+// they are; otherwise N(0,1) * sqrt(temperature) drawn on the device per (seed, step), one launch_noise_fill; temperature <= 0: zeros.
+// All of it is resident before the slot's first step, so the AR loop (plain launches or graph replay) just reads row `step` of its slot.
+void stage_noise(Batch& b, const std::vector<SlotReq>& list, hipStream_t s);
+// one decoded row of a group of finished utterances that one mimi_range call decodes
+struct Delivery {
+    const ptts_request* req = nullptr;
+    ptts_result* res = nullptr;   // nullptr: decoded but not delivered (cancelled, failed)
+    int nf = 0, eos = -1;
+    bool filled = false;          // res already holds a buffer with every sample (streamed): no allocation, no copy
+};
+// before the decode: result buffers into the results (PCM16 or f32), and the device PcmRow table for mimi_range's direct store (host_rows:
+// page-locked, g.size() entries, uploaded on s into dev_rows).  With it the decoder's last kernel stores every utterance's samples straight
+// into its page-locked result buffer: the kernel's stores ARE the device -> host transfer -- no copies, no conversion launch.  A kernel may
+// only store into page-locked memory: if the pool had to fall back to pageable blocks, nullptr (the group takes the device buffer + copy
+// path).  A failed allocation leaves its row empty (the request ends with PTTS_ENOMEM); the others keep the direct store.
+const PcmRow* results_alloc(const Model& m, const std::vector<Delivery>& g, PcmRow* host_rows, PcmRow* dev_rows, hipStream_t s);
+// after it: unless the decoder stored the samples itself, PCM16 conversion and the copies out of pcm (row i at i * pcm_stride); the
+// latents (row i at lat + i * lat_stride); status, n_frames, eos_step, n_samples.  Everything is queued on s.
+void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, const float* pcm, int64_t pcm_stride, const float* lat, int64_t lat_stride,
+                     hipStream_t s);
 Model* model_share(Model& base);   // another engine over base's weight arena (base must outlive it)
 Model* model_replicate(Model& base, int device);   // the model on another GPU of this process: own arena, copied from base's by hipMemcpyPeer
 void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res);
