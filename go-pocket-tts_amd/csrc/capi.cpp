@@ -360,7 +360,7 @@ int ptts_voice_create(ptts_model* h, const float* const* caches, const int64_t* 
 void ptts_voice_free(ptts_voice* v) {
     if (!v) return;
     Voice* vv = reinterpret_cast<Voice*>(v);
-    (void)hipSetDevice(vv->m->device);
+    (void)hipSetDevice(vv->device);
     delete vv;
 }
 
@@ -697,6 +697,63 @@ int ptts::capi::decode_stages(ptts_model* h, const float* latents, int32_t n_utt
     });
 }
 
+// encoder + speaker projection (EncodeVoice, onnx/voice_encode.go:23-158): PTTS_EFORMAT naming what the checkpoint lacks
+static void require_voice_encoder(const Desc& d) {
+    require_encoder(d);
+    const Lin& l = d.speaker_proj;
+    if (l.w == NONE) throw Error(PTTS_EFORMAT, "load speaker_proj_weight: tensor not found in the model weights");
+    if (l.in != d.mimi_dim) throw Error(PTTS_EFORMAT, strfmt("speaker_proj_weight takes %d-wide latents, the encoder makes %d", l.in, d.mimi_dim));
+}
+
+// one clip -> its voice embedding in out (host, [ceil(n / hop)][d_model]); returns the frame count.  The caller holds m.mu.
+static int64_t encode_embedding(Model& m, const float* pcm, int64_t n_samples, float* out) {
+    const Lin& l = m.d.speaker_proj;
+    const int64_t nf = n_samples > 0 ? (n_samples + m.d.enc.hop - 1) / m.d.enc.hop : 0;
+    DevBuf& io = m.work(17, (size_t)std::max<int64_t>(nf, 1) * (l.in + l.out) * sizeof(float));
+    float* lat = io.as<float>();
+    const int64_t f = mimi_encode_clip(m, pcm, n_samples, lat, nullptr);
+    float* dout = lat + (size_t)f * l.in;
+    GemmArgs g;   // the product ptts_speaker_project runs, on the latents where the encoder left them
+    g.A = lat; g.amap = RowMap{l.in, 0, 0};
+    g.W = m.arena + l.w; g.w_bf16 = 0; g.ldw = l.in;
+    g.C = dout; g.cmap = RowMap{l.out, 0, 0};
+    g.M = (int)f; g.N = l.out; g.K = l.in;
+    launch_gemm(g, m.stream);
+    PTTS_HIP(hipMemcpyAsync(out, dout, (size_t)f * l.out * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+    PTTS_HIP(hipStreamSynchronize(m.stream));
+    return f;
+}
+
+static void voices_out(std::vector<std::unique_ptr<Voice>>& vs, ptts_voice** out) {
+    for (size_t i = 0; i < vs.size(); i++) out[i] = reinterpret_cast<ptts_voice*>(vs[i].release());
+}
+
+static void bytes_out(const std::vector<uint8_t>& b, uint8_t** data, size_t* len) {
+    uint8_t* p = (uint8_t*)malloc(std::max<size_t>(b.size(), 1));
+    if (!p) throw std::bad_alloc();
+    std::memcpy(p, b.data(), b.size());
+    *data = p;
+    *len = b.size();
+}
+
+// a device voice as a model-state file (the caller holds nothing; the voice's engine is locked here)
+static std::vector<uint8_t> voice_file_bytes(const ptts_voice* hv) {
+    if (!hv) throw Error(PTTS_EINVAL, "native: voice model state is nil");
+    const Voice& v = *reinterpret_cast<const Voice*>(hv);
+    Model& m = *v.m;
+    const Desc& d = m.d;
+    const size_t per = (size_t)2 * v.offset * d.heads * d.hd;
+    std::vector<float> all(per * d.n_layers);
+    {
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        voice_export(v, 0, d.n_layers, all.data());
+    }
+    std::vector<const float*> caches((size_t)d.n_layers);
+    for (int l = 0; l < d.n_layers; l++) caches[(size_t)l] = all.data() + per * l;
+    return voice_state_file(caches.data(), v.offset, d.n_layers, d.heads, d.hd);
+}
+
 extern "C" {
 
 int ptts_speaker_project(ptts_model* h, const float* latent, int64_t frames, float* out) {
@@ -737,29 +794,97 @@ int ptts_voice_encode_audio(ptts_model* h, const float* pcm, int64_t n_samples, 
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
         Model& m = *h->m;
-        require_encoder(m.d);
-        const Lin& l = m.d.speaker_proj;
-        if (l.w == NONE) throw Error(PTTS_EFORMAT, "load speaker_proj_weight: tensor not found in the model weights");
-        if (l.in != m.d.mimi_dim) throw Error(PTTS_EFORMAT, strfmt("speaker_proj_weight takes %d-wide latents, the encoder makes %d", l.in, m.d.mimi_dim));
+        require_voice_encoder(m.d);
         if (!embedding_out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
         std::lock_guard<std::mutex> lock(m.mu);
         m.use_device();
-        const int64_t nf = n_samples > 0 ? (n_samples + m.d.enc.hop - 1) / m.d.enc.hop : 0;
-        DevBuf& io = m.work(17, (size_t)std::max<int64_t>(nf, 1) * (l.in + l.out) * sizeof(float));
-        float* lat = io.as<float>();
-        const int64_t f = mimi_encode_clip(m, pcm, n_samples, lat, nullptr);
-        float* dout = lat + (size_t)f * l.in;
-        GemmArgs g;   // the product ptts_speaker_project runs, on the latents where the encoder left them
-        g.A = lat; g.amap = RowMap{l.in, 0, 0};
-        g.W = m.arena + l.w; g.w_bf16 = 0; g.ldw = l.in;
-        g.C = dout; g.cmap = RowMap{l.out, 0, 0};
-        g.M = (int)f; g.N = l.out; g.K = l.in;
-        launch_gemm(g, m.stream);
-        PTTS_HIP(hipMemcpyAsync(embedding_out, dout, (size_t)f * l.out * sizeof(float), hipMemcpyDeviceToHost, m.stream));
-        PTTS_HIP(hipStreamSynchronize(m.stream));
+        const int64_t f = encode_embedding(m, pcm, n_samples, embedding_out);
         if (frames) *frames = f;
     });
 }
+
+int ptts_voice_from_embeddings(ptts_model* h, const float* const* emb, const int64_t* frames, int64_t width, int32_t n, ptts_voice** out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model flow_lm unavailable");
+        if (!out) throw Error(PTTS_EINVAL, "ptts-hip: voice build: null output array");
+        Model& m = *h->m;
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        auto vs = voice_build(m, emb, frames, width, n);
+        voices_out(vs, out);
+    });
+}
+
+int ptts_voice_from_audio(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n, ptts_voice** out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        Model& m = *h->m;
+        require_voice_encoder(m.d);
+        if (n <= 0) throw Error(PTTS_EINVAL, strfmt("ptts-hip: voice build needs at least one clip, got %d", n));
+        if (!pcm || !n_samples || !out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
+        const int64_t hop = m.d.enc.hop, D = m.d.d_model;
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        std::vector<std::vector<float>> embs((size_t)n);
+        std::vector<const float*> ptrs((size_t)n);
+        std::vector<int64_t> frames((size_t)n);
+        for (int i = 0; i < n; i++) {
+            if (!pcm[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: clip %d is null", i));
+            embs[(size_t)i].resize((size_t)std::max<int64_t>((n_samples[i] + hop - 1) / hop, 1) * D);
+            frames[(size_t)i] = encode_embedding(m, pcm[i], n_samples[i], embs[(size_t)i].data());
+            ptrs[(size_t)i] = embs[(size_t)i].data();
+        }
+        auto vs = voice_build(m, ptrs.data(), frames.data(), D, n);
+        voices_out(vs, out);
+    });
+}
+
+int ptts_voice_offset(const ptts_voice* v, int64_t* offset) {
+    return guard([&] {
+        if (!v || !offset) throw Error(PTTS_EINVAL, "native: voice model state is nil");
+        *offset = reinterpret_cast<const Voice*>(v)->offset;
+    });
+}
+
+int ptts_voice_read_state(const ptts_voice* hv, int32_t layer, float* cache) {
+    return guard([&] {
+        if (!hv || !cache) throw Error(PTTS_EINVAL, "native: voice model state is nil");
+        const Voice& v = *reinterpret_cast<const Voice*>(hv);
+        std::lock_guard<std::mutex> lock(v.m->mu);
+        v.m->use_device();
+        voice_read_state(v, layer, cache);
+    });
+}
+
+int ptts_voice_write(const ptts_voice* v, const char* path) {
+    return guard([&] {
+        if (!path) throw Error(PTTS_EINVAL, "ptts-hip: null path");
+        write_file(path, voice_file_bytes(v));
+    });
+}
+
+int ptts_voice_write_bytes(const ptts_voice* v, uint8_t** data, size_t* len) {
+    return guard([&] {
+        if (!data || !len) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
+        bytes_out(voice_file_bytes(v), data, len);
+    });
+}
+
+int ptts_voice_state_write_bytes(const float* const* caches, int64_t offset, int32_t n_layers, int32_t heads, int32_t head_dim, uint8_t** data, size_t* len) {
+    return guard([&] {
+        if (!data || !len) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
+        bytes_out(voice_state_file(caches, offset, n_layers, heads, head_dim), data, len);
+    });
+}
+
+int ptts_voice_embedding_write(const float* emb, int64_t frames, int64_t dim, const char* path) {
+    return guard([&] {
+        if (!path) throw Error(PTTS_EINVAL, "ptts-hip: null path");
+        write_file(path, voice_embedding_file(emb, frames, dim));
+    });
+}
+
+void ptts_free_bytes(uint8_t* data) { free(data); }
 
 int ptts_noise_rows(ptts_model* h, uint64_t seed, float temperature, int32_t rows, float* out) {
     return guard([&] {

@@ -233,6 +233,15 @@ void launch_voice_scatter(const float* raw, int t, int heads, int hd, int offset
 // copies a compact device voice (K, V as [H][offset][hd] in the cache dtype) into the first `offset` rows of several slots
 void launch_voice_apply(const void* vk, const void* vv, int offset, int heads, int hd, const int32_t* slots, int n_slots,
                         void* kcache, void* vcache, int elem_bytes, int64_t cap, hipStream_t stream);
+// the reverse of launch_voice_apply for many voices at once (voice_build): voice i receives the first dst[i].offset rows of slot dst[i].slot of
+// every layer and head of a batch cache [L][B][H][cap][hd], as [L][H][offset][hd] in the cache dtype; one launch for all voices and layers.
+// hd * elem_bytes must be a multiple of 16, all buffers 16-byte aligned; max_offset bounds dst[i].offset (sizes the grid)
+struct VoiceDst { void* k; void* v; int32_t offset; int32_t slot; };
+void launch_voice_extract(const void* kcache, const void* vcache, int B, int64_t cap, int heads, int hd, int elem_bytes, int n_layers,
+                          const VoiceDst* dst_dev, int n_voices, int max_offset, hipStream_t stream);
+// the inverse of launch_voice_scatter: a compact voice (K, V as [L][H][offset][hd] in the cache dtype) -> per layer the reference's
+// [2, 1, offset, H, hd] f32 cache, layer after layer in out; bf16 widened exactly.  hd % 8 == 0, buffers 16-byte aligned
+void launch_voice_export(const void* vk, const void* vv, int offset, int heads, int hd, int n_layers, int kv_bf16, float* out, hipStream_t stream);
 // final causal conv Cin -> 1, kernel k, ELU on the input (mimi.go:781-783): in [B][pad+T][C] channels-last
 void launch_conv_final(const float* in, int in_pad_rows, const float* w /*[k*C]*/, const float* bias, int b, int t, int t0, int t1,
                        int c, int k, int elu_in /* 0: the producer already applied ELU */, float* out /*[B][T]*/, hipStream_t stream);   // samples [t0, t1) of every utterance

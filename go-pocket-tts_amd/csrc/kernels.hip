@@ -716,6 +716,68 @@ void launch_voice_apply(const void* vk, const void* vv, int offset, int heads, i
                        heads, row16, slots, n_slots, (uint4*)kcache, (uint4*)vcache, cap);
 }
 
+// batch cache -> compact device voices (voice_build): grid (chunks, voice, layer), one 16-byte chunk per thread; voice i takes the first
+// offset rows of slot `slot` of every head.  Reads are whole cache rows of one (slot, head), stores are contiguous.
+__global__ void k_voice_extract(const uint4* kc, const uint4* vc, int B, int64_t cap, int heads, int row16, const VoiceDst* dst) {
+    const VoiceDst o = dst[blockIdx.y];
+    const int l = blockIdx.z;
+    const int64_t per_layer = (int64_t)heads * o.offset * row16;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per_layer) return;
+    const int c = (int)(i % row16);
+    const int row = (int)((i / row16) % o.offset);
+    const int h = (int)(i / ((int64_t)row16 * o.offset));
+    const int64_t src = ((((int64_t)l * B + o.slot) * heads + h) * cap + row) * row16 + c;
+    reinterpret_cast<uint4*>(o.k)[(int64_t)l * per_layer + i] = kc[src];
+    reinterpret_cast<uint4*>(o.v)[(int64_t)l * per_layer + i] = vc[src];
+}
+void launch_voice_extract(const void* kcache, const void* vcache, int B, int64_t cap, int heads, int hd, int elem_bytes, int n_layers,
+                          const VoiceDst* dst_dev, int n_voices, int max_offset, hipStream_t stream) {
+    const int row16 = hd * elem_bytes / 16;
+    const int64_t per_layer = (int64_t)heads * max_offset * row16;
+    if (per_layer <= 0 || n_voices <= 0 || n_layers <= 0) return;
+    note_launch("k_voice_extract");
+    hipLaunchKernelGGL(k_voice_extract, dim3((unsigned)((per_layer + 255) / 256), (unsigned)n_voices, (unsigned)n_layers), dim3(256), 0, stream,
+                       (const uint4*)kcache, (const uint4*)vcache, B, cap, heads, row16, dst_dev);
+}
+
+// compact voice -> the reference's per-layer cache [2, 1, offset, H, hd] f32 (the layout k_voice_scatter reads), every layer in one launch:
+// one thread per 16-byte source chunk (8 bf16 or 4 f32 elements); bf16 is widened exactly in the store
+template <bool KVBF16>
+__global__ void k_voice_export(const uint4* vk, const uint4* vv, int offset, int heads, int hd, int n_layers, float* out) {
+    constexpr int V = KVBF16 ? 8 : 4;   // elements per 16-byte load
+    const int hdv = hd / V;
+    const int64_t per_which = (int64_t)offset * heads * hdv;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per_which * 2 * n_layers) return;
+    const int c = (int)(i % hdv);
+    const int h = (int)((i / hdv) % heads);
+    const int t = (int)((i / ((int64_t)hdv * heads)) % offset);
+    const int which = (int)((i / per_which) % 2);
+    const int l = (int)(i / (per_which * 2));
+    const int64_t src = ((int64_t)l * heads * offset + (int64_t)h * offset + t) * hdv + c;   // [layer][head][row][chunk]
+    const uint4 q = (which ? vv : vk)[src];
+    float4* o = reinterpret_cast<float4*>(out + i * V);      // [layer][which][row][head][element]: the thread's V elements in order
+    if (KVBF16) {
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
+        #pragma unroll
+        for (int j = 0; j < 2; j++)
+            o[j] = make_float4(bf16_bits_to_f32((unsigned short)(w[2 * j] & 0xffff)), bf16_bits_to_f32((unsigned short)(w[2 * j] >> 16)),
+                               bf16_bits_to_f32((unsigned short)(w[2 * j + 1] & 0xffff)), bf16_bits_to_f32((unsigned short)(w[2 * j + 1] >> 16)));
+    } else {
+        o[0] = make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w));
+    }
+}
+void launch_voice_export(const void* vk, const void* vv, int offset, int heads, int hd, int n_layers, int kv_bf16, float* out, hipStream_t stream) {
+    const int V = kv_bf16 ? 8 : 4;
+    const int64_t tot = (int64_t)2 * n_layers * offset * heads * (hd / V);
+    if (tot <= 0) return;
+    note_launch("k_voice_export");
+    dim3 g((unsigned)((tot + 255) / 256));
+    if (kv_bf16) hipLaunchKernelGGL(k_voice_export<true>, g, dim3(256), 0, stream, (const uint4*)vk, (const uint4*)vv, offset, heads, hd, n_layers, out);
+    else hipLaunchKernelGGL(k_voice_export<false>, g, dim3(256), 0, stream, (const uint4*)vk, (const uint4*)vv, offset, heads, hd, n_layers, out);
+}
+
 // K16 (last layer): ELU then causal conv C -> 1 (mimi.go:781-783).  A block produces 256 consecutive samples of one
 // utterance: the (256 + k - 1) x C input window is one contiguous span in the channels-last buffer, staged into LDS with
 // coalesced 16-byte loads (ELU applied on the way); each thread then reduces its k*C window from LDS.  Rows are padded

@@ -375,6 +375,7 @@ Voice* voice_create(Model& m, const float* const* caches, const int64_t* steps, 
     check_voice(d, caches, steps, offsets, ROPE_SEQ);
     std::unique_ptr<Voice> v(new Voice());
     v->m = &m;
+    v->device = m.device;
     v->offset = (int)offsets[0];
     const size_t lb = v->layer_bytes();
     v->k.ensure(std::max<size_t>(lb * d.n_layers, 256));

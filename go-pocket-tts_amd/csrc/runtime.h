@@ -166,6 +166,7 @@ bool result_is_pinned(const void* p);   // false for the pageable fallback block
 // a voice model state resident in HBM: K and V per layer as [H][offset][hd] in the cache dtype
 struct Voice {
     Model* m = nullptr;
+    int device = 0;   // m->device (freeing a voice never reads its model)
     int offset = 0;
     DevBuf k, v;
     size_t layer_bytes() const { return (size_t)m->d.heads * offset * m->d.hd * (m->opts.kv == PTTS_KV_BF16 ? 2 : 4); }
@@ -173,6 +174,15 @@ struct Voice {
 Voice* voice_create(Model& m, const float* const* caches, const int64_t* steps, const int64_t* offsets);
 void batch_apply_voice(Batch& b, const Voice& v, const std::vector<int32_t>& slots);
 bool voice_usable_by(const Voice& v, const Model& m);   // same GPU and cache geometry (e.g. engines made by model_share)
+// cloned voices as model states (voice_build.cpp): embedding i (host [frames[i]][width] f32, width == d_model, 1 <= frames[i] <= ROPE_SEQ)
+// prefilled alone from position 0 -- one batch_prompt of the embeddings as ragged prompts (per kStepMaxRows of them) -- and its first frames[i]
+// KV rows of every layer moved into a compact Voice (offset = frames[i]) by one launch_voice_extract: what voice_create makes of the same caches.
+// The caller holds m.mu; runs on m.stream.  Nothing is kept on a failure.
+std::vector<std::unique_ptr<Voice>> voice_build(Model& m, const float* const* emb, const int64_t* frames, int64_t width, int n);
+// layers [layer0, layer0 + n_layers) of a voice as the reference's caches, each [2, 1, offset, H, Dh] f32, one after the other in out (host);
+// the exact inverse of what launch_voice_scatter reads (a bf16 cache widened exactly).  The caller holds v.m->mu.
+void voice_export(const Voice& v, int layer0, int n_layers, float* out);
+void voice_read_state(const Voice& v, int layer, float* out);
 
 // buffers of one Mimi decode (all channels-last, spanning the whole utterance so that frame ranges can be decoded in order)
 struct MimiWs {
@@ -310,6 +320,11 @@ VoiceFile* voice_file_from_bytes(const void* data, size_t len);
 void voice_file_embedding(const VoiceFile& v, const float** data, int64_t shape[3]);
 void voice_file_require_state(const VoiceFile& v);
 void voice_file_state(const VoiceFile& v, int n_layers, int heads, int head_dim, const float** caches, int64_t* steps, int64_t* offsets);
+// the writer (voicefile_write.cpp): a model-state file (per layer `transformer.layers.{l}.self_attn/cache` F32 [2,1,offset,heads,head_dim] from
+// caches[l] and `/offset` I64 [1]; no padding rows) and a legacy-embedding file (`audio_prompt` F32 [1, frames, dim]), as file bytes
+std::vector<uint8_t> voice_state_file(const float* const* caches, int64_t offset, int n_layers, int heads, int head_dim);
+std::vector<uint8_t> voice_embedding_file(const float* emb, int64_t frames, int64_t dim);
+void write_file(const std::string& path, const std::vector<uint8_t>& bytes);   // PTTS_EIO on failure
 
 // optional post-processing of a finished utterance (dsp.cpp; internal/audio/dsp.go)
 void dsp_peak_normalize(float* s, int64_t n);

@@ -103,6 +103,8 @@ ABI_SYMBOLS = [
     "ptts_tokenizer_encode_cb", "ptts_text_nfkc", "ptts_rccl_unique_id", "ptts_rccl_broadcast", "ptts_dsp_apply",
     "ptts_voice_file_open", "ptts_voice_file_open_bytes", "ptts_voice_file_close", "ptts_voice_file_kind", "ptts_voice_file_embedding",
     "ptts_voice_file_modules", "ptts_voice_file_module", "ptts_voice_file_state", "ptts_voice_open", "ptts_voice_open_bytes",
+    "ptts_voice_from_embeddings", "ptts_voice_from_audio", "ptts_voice_offset", "ptts_voice_read_state", "ptts_voice_write", "ptts_voice_write_bytes",
+    "ptts_voice_state_write_bytes", "ptts_voice_embedding_write", "ptts_free_bytes",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -177,6 +179,17 @@ def lib():
         L.ptts_voice_file_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_FP), _IP, _IP]
         L.ptts_voice_open.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
         L.ptts_voice_open_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.ptts_voice_from_embeddings.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        L.ptts_voice_from_audio.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(C.c_void_p)]
+        L.ptts_voice_offset.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.ptts_voice_read_state.argtypes = [C.c_void_p, C.c_int32, _FP]
+        L.ptts_voice_write.argtypes = [C.c_void_p, C.c_char_p]
+        L.ptts_voice_write_bytes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+        L.ptts_voice_state_write_bytes.argtypes = [C.POINTER(_FP), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.POINTER(C.c_uint8)),
+                                                   C.POINTER(C.c_size_t)]
+        L.ptts_voice_embedding_write.argtypes = [_FP, C.c_int64, C.c_int64, C.c_char_p]
+        L.ptts_free_bytes.argtypes = [C.POINTER(C.c_uint8)]
+        L.ptts_free_bytes.restype = None
         L.ptts_profile_enable.argtypes = [C.c_void_p, C.c_int32]
         L.ptts_profile_read.argtypes = [C.c_void_p, C.POINTER(_Profile)]
         L.ptts_op_linear.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int64, C.c_int64, _FP]
@@ -237,6 +250,11 @@ class VoiceEmbedding:
     """tts.VoiceEmbedding (runtime.go:11-14): shape [1, T, D]."""
     data: np.ndarray
     shape: Sequence[int]
+
+    def save(self, path: str) -> None:
+        """A legacy-embedding voice file: `audio_prompt` F32 [1, T, D] (ptts_voice_embedding_write)."""
+        d = _f32(self.data).reshape(-1, int(self.shape[-1]))
+        _check(lib().ptts_voice_embedding_write(_fp(d), d.shape[0], d.shape[1], os.fsencode(path)))
 
 
 @dataclass
@@ -415,7 +433,7 @@ class Model:
         ptrs, steps, offs, arrs = _voice_arrays(state, self.info.n_layers)
         h = C.c_void_p()
         _check(lib().ptts_voice_create(self.h, ptrs, _ip(steps), _ip(offs), C.byref(h)))
-        return DeviceVoice(h.value, int(offs[0]))
+        return DeviceVoice(h.value, int(offs[0]), self.info)
 
     def mimi_layer_qkv(self, layer: int, x, pos0: int = 0, rows_per_seg: int = 0) -> np.ndarray:
         """norm1 -> in_proj -> RoPE(q, k) of Mimi decoder-transformer layer `layer` on rows x [R, 512] -> [R, 1536] (ptts_mimi_layer_piece)."""
@@ -444,7 +462,39 @@ class Model:
             _check(lib().ptts_voice_open_bytes(self.h, buf, len(buf), C.byref(h)))
         else:
             _check(lib().ptts_voice_open(self.h, os.fsencode(src), C.byref(h)))
-        return DeviceVoice(h.value, -1)
+        return DeviceVoice(h.value, None, self.info)
+
+    def voice_from_embedding(self, emb):
+        """A voice embedding (VoiceEmbedding or [T, d_model] array; a list: one build for all) as a model state in HBM
+        (ptts_voice_from_embeddings): served like a stock voice instead of being prefilled again by every request."""
+        single = not isinstance(emb, (list, tuple))
+        items = [emb] if single else list(emb)
+        arrs = [_f32(e.data if isinstance(e, VoiceEmbedding) else e) for e in items]
+        arrs = [a.reshape(-1, a.shape[-1]) if a.ndim else a for a in arrs]
+        n = len(arrs)
+        width = arrs[0].shape[-1] if n and arrs[0].ndim else 0
+        for a in arrs:
+            if a.ndim != 2 or a.shape[-1] != width:
+                raise PttsError(PTTS_EINVAL, f"voice embeddings must be [T, D] with one D, got {[list(x.shape) for x in arrs]}")
+        pp = (_FP * max(n, 1))(*[_fp(a) for a in arrs])
+        fr = np.array([a.shape[0] for a in arrs] or [0], np.int64)
+        hs = (C.c_void_p * max(n, 1))()
+        _check(lib().ptts_voice_from_embeddings(self.h, pp, _ip(fr), width, n, hs))
+        out = [DeviceVoice(hs[i], int(fr[i]), self.info) for i in range(n)]
+        return out[0] if single else out
+
+    def voice_state_from_audio(self, pcm):
+        """24 kHz mono clips (a list: one call) -> encoder + speaker projection + one model-state build (ptts_voice_from_audio).
+        PARITY UNPINNED like voice_from_audio: the encoder's chain is inferred."""
+        single = not isinstance(pcm, (list, tuple))
+        clips = [_f32(pcm).reshape(-1)] if single else [_f32(p).reshape(-1) for p in pcm]
+        n = len(clips)
+        pp = (_FP * max(n, 1))(*[_fp(c) for c in clips])
+        ns = np.array([c.size for c in clips] or [0], np.int64)
+        hs = (C.c_void_p * max(n, 1))()
+        _check(lib().ptts_voice_from_audio(self.h, pp, _ip(ns), n, hs))
+        out = [DeviceVoice(hs[i], None, self.info) for i in range(n)]
+        return out[0] if single else out
 
     def profile_enable(self, on):   # False / 0: off; True / 1: per-launch events + phases; 2: phases only
         _check(lib().ptts_profile_enable(self.h, int(on)))
@@ -643,8 +693,39 @@ class Model:
 
 
 class DeviceVoice:
-    def __init__(self, handle: int, offset: int):
-        self.h, self.offset = handle, offset
+    """A voice model state in HBM (ptts_voice).  offset: the keys it holds (ptts_voice_offset)."""
+
+    def __init__(self, handle: int, offset: Optional[int] = None, info: Optional["ModelInfo"] = None):
+        self.h, self.info = handle, info
+        if offset is None or offset < 0:
+            o = C.c_int64()
+            _check(lib().ptts_voice_offset(self.h, C.byref(o)))
+            offset = int(o.value)
+        self.offset = offset
+
+    def read_state(self, layer: int) -> np.ndarray:
+        """Layer `layer` as the reference's cache [2, 1, offset, H, Dh] f32 (ptts_voice_read_state)."""
+        out = np.empty((2, 1, self.offset, self.info.n_heads, self.info.d_model // self.info.n_heads), np.float32)
+        _check(lib().ptts_voice_read_state(self.h, layer, _fp(out)))
+        return out
+
+    def state(self) -> VoiceModelState:
+        """The voice as safetensors.VoiceModelState: per layer "cache" [2, 1, offset, H, Dh] and "offset" [1]."""
+        return VoiceModelState({f"transformer.layers.{i}.self_attn": {"cache": self.read_state(i), "offset": np.array([self.offset], np.int64)}
+                                for i in range(self.info.n_layers)})
+
+    def to_bytes(self) -> bytes:
+        """The voice as a model-state voice file, in memory (ptts_voice_write_bytes)."""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        _check(lib().ptts_voice_write_bytes(self.h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().ptts_free_bytes(p)
+
+    def save(self, path: str) -> None:
+        """The voice as a model-state voice file (ptts_voice_write): what Model.open_voice and load_voice_conditioning read."""
+        _check(lib().ptts_voice_write(self.h, os.fsencode(path)))
 
     def close(self):
         if self.h:
@@ -721,6 +802,20 @@ class VoiceFile:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def voice_state_file_bytes(caches: Sequence[np.ndarray], offset: int) -> bytes:
+    """A model-state voice file from host caches (caches[l]: [2, 1, offset, H, Dh] f32; ptts_voice_state_write_bytes)."""
+    cs = [_f32(c) for c in caches]
+    if not cs or any(c.ndim != 5 or c.shape[:3] != (2, 1, offset) or c.shape != cs[0].shape for c in cs):
+        raise PttsError(PTTS_EINVAL, f"voice caches must be [2, 1, {offset}, H, Dh], got {[list(c.shape) for c in cs]}")
+    pp = (_FP * len(cs))(*[_fp(c) for c in cs])
+    p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    _check(lib().ptts_voice_state_write_bytes(pp, offset, len(cs), cs[0].shape[3], cs[0].shape[4], C.byref(p), C.byref(n)))
+    try:
+        return C.string_at(p, n.value)
+    finally:
+        lib().ptts_free_bytes(p)
 
 
 def load_voice_conditioning(voice_path: str) -> dict:

@@ -312,6 +312,31 @@ int  ptts_voice_file_state(const ptts_voice_file* f, int32_t n_layers, int32_t h
 int  ptts_voice_open(ptts_model* m, const char* path, ptts_voice** out);
 int  ptts_voice_open_bytes(ptts_model* m, const void* data, size_t len, ptts_voice** out);
 
+/* ---- cloned voices as model states.  The reference's `pocket-tts export-voice --format model-state` (cmd/pockettts/export_voice.go) runs the
+ *      Python package to turn a voice into per-layer KV caches; here the state is built on the GPU.  A voice embedding prepended to the prompt
+ *      (runtime_native_safetensors.go:104-119) is prefilled again by every request; its model state is prefilled once and then shared by
+ *      requests like a stock voice (ptts_request.voice). ---- */
+/* emb[i]: host [frames[i], width] f32 voice embedding (width == d_model, 1 <= frames[i] <= 8192).  One prefill of all n embeddings, each alone
+ * from position 0 (voice first, no text), and their KV rows into n new device voices out[0..n) with offset frames[i]: exactly what
+ * ptts_voice_create makes of the same caches.  PTTS_EINVAL (nothing allocated) for a bad count, width, frame count or null pointer. */
+int  ptts_voice_from_embeddings(ptts_model* m, const float* const* emb, const int64_t* frames, int64_t width, int32_t n, ptts_voice** out /* [n] */);
+/* ptts_voice_encode_audio per clip (PARITY UNPINNED: the inferred encoder), then one ptts_voice_from_embeddings of the n embeddings.
+ * PTTS_EFORMAT naming the missing tensor on a checkpoint without encoder or speaker projection weights. */
+int  ptts_voice_from_audio(ptts_model* m, const float* const* pcm, const int64_t* n_samples, int32_t n, ptts_voice** out /* [n] */);
+int  ptts_voice_offset(const ptts_voice* v, int64_t* offset);   /* keys the voice holds */
+/* layer `layer` of a device voice as the reference's cache [2, 1, offset, H, Dh] f32 (flow_transformer.go:517-566; a bf16 cache widened exactly):
+ * what ptts_voice_create takes back */
+int  ptts_voice_read_state(const ptts_voice* v, int32_t layer, float* cache /* [2,1,offset,H,Dh] */);
+/* a device voice as a model-state voice file (reader.go:127-155,273-308): per layer `transformer.layers.{l}.self_attn/cache` F32 [2,1,offset,H,Dh]
+ * and `/offset` I64 [1], no padding rows.  _bytes: the file in memory (*data released with ptts_free_bytes). */
+int  ptts_voice_write(const ptts_voice* v, const char* path);
+int  ptts_voice_write_bytes(const ptts_voice* v, uint8_t** data, size_t* len);
+/* the same file from host caches (caches[l]: [2, 1, offset, heads, head_dim] f32); host only */
+int  ptts_voice_state_write_bytes(const float* const* caches, int64_t offset, int32_t n_layers, int32_t heads, int32_t head_dim, uint8_t** data, size_t* len);
+/* a legacy-embedding voice file (reader.go:69-85,219-230): `audio_prompt` F32 [1, frames, dim] from emb [frames, dim] (host only) */
+int  ptts_voice_embedding_write(const float* emb, int64_t frames, int64_t dim, const char* path);
+void ptts_free_bytes(uint8_t* data);
+
 /* Measurement hook for bench.py: while enabled the AR step runs eagerly (no graph) with a HIP event pair around
  * every launch of the dominant (weight-streaming linear) kernel on the model's stream. */
 typedef struct ptts_profile {
