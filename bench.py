@@ -7,19 +7,25 @@ tts.Runtime.GenerateAudio for 64 concurrent utterances per GPU (text prompt of 2
 24 kHz PCM).  BASELINE.json configs[2] at N=1 and configs[3] (64 per GPU) at N=8: weak scaling, no
 data-path collective -- one RCCL broadcast of the weight arena at start-up.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps and prints the result line.  --full adds
+everything else the benchmark measures (the --no-* options trim it): rocprofv3 counter and trace passes, `roofline`, the extras
+beside the headline (plain launches, temperature 0.7, serve legs, wider batches, two engines, batch 1 at f32, int8 weights) and
+`cpu_baseline`.
 
 --dump-outputs DIR writes what the headline's last timed step returned (PCM, frame counts, EOS steps) as DIR/<name>.npy;
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its N ranks itself (one child process per
 GPU, before anything in the parent touches the GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it is
-one of the ranks.  Rank 0 prints one JSON line.  `roofline` prices the dominant kernel (the AR step's weight-streaming
+one of the ranks.  Rank 0 prints one JSON line.  With --full, `roofline` prices the dominant kernel (the AR step's weight-streaming
 linear) against HBM, `roofline.mimi` the decoder against the bf16 matrix peak; `cpu_baseline` times the CPU oracle (a C
 restatement of the reference's AVX2/FMA path: the Go binary itself cannot be built here) on the host cores, on a bounded
 sample, on rank 0 at N=1 only.
 """
 import argparse
+import atexit
 import csv
 import glob
 import json
@@ -55,8 +61,10 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def checkpoint_path(pkg, file_dtype: str, rank: int, barrier) -> str:
-    d = os.path.join(tempfile.gettempdir(), f"ptts_bench_{os.getuid()}")
+def checkpoint_path(pkg, file_dtype: str, rank: int, barrier, directory=None) -> str:
+    """The seeded synthetic checkpoint (the same bytes wherever it is written), kept in `directory` -- by default one per user that later
+    callers reuse."""
+    d = directory or os.path.join(tempfile.gettempdir(), f"ptts_bench_{os.getuid()}")
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, f"synthetic_b6369a24_shapes_{file_dtype.lower()}.safetensors")
     if rank == 0 and not os.path.exists(path):
@@ -68,6 +76,19 @@ def checkpoint_path(pkg, file_dtype: str, rank: int, barrier) -> str:
         log(f"[bench] synthetic checkpoint ({file_dtype}) written in {time.time()-t0:.1f}s: {path}")
     barrier()
     return path
+
+
+def run_dir(rank: int, world: int, device: int) -> str:
+    """A directory of this run's own (rank 0 makes it, every rank gets its name, it goes when rank 0 exits): the benchmark writes its
+    checkpoints there instead of reusing files an earlier run left behind."""
+    d = [tempfile.mkdtemp(prefix="ptts_bench_run_") if rank == 0 else None]
+    if rank == 0:
+        atexit.register(shutil.rmtree, d[0], True)
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+        dist.broadcast_object_list(d, src=0, device=torch.device(f"cuda:{device}"))
+    return d[0]
 
 
 def voice_modules(pkg, cfg):
@@ -706,6 +727,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="b64_10s_bf16", choices=list(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="beside the headline, run everything else the benchmark measures (traffic and trace passes, roofline, "
+                                                         "the extras, cpu_baseline); the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-b1", action="store_true")
     ap.add_argument("--no-two-engines", action="store_true", help="skip the two-engine, plain-launch and temperature extras (profiling: concurrent kernels "
@@ -736,7 +759,7 @@ def main():
     NATIVE_BROADCAST = bool(args.native_broadcast)
 
     traffic = None
-    if rank == 0 and world == 1 and not args.no_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic:
         # before this process initialises the GPU: the counter passes run as child processes of their own
         t0 = time.time()
         try:
@@ -767,7 +790,8 @@ def main():
     pkg = ptts_amd.load()
     cfg = pkg.synth.SynthConfig.full()
     wl = WORKLOADS[args.workload]
-    path = checkpoint_path(pkg, wl["file"], rank, barrier)
+    rdir = run_dir(rank, world, local)
+    path = checkpoint_path(pkg, wl["file"], rank, barrier, rdir)
     t0 = time.time()
     model, arena = open_model(pkg, path, wl, rank, world, local)
     log(f"[bench] rank {rank}: model resident in {time.time()-t0:.1f}s ({model.info.arena_bytes/1e6:.0f} MB arena, {model.info.n_params/1e6:.1f} M params)")
@@ -797,7 +821,7 @@ def main():
         "p50_utterance_latency_ms": round(1e3 * statistics.median(lat), 2),
         "per_rank_xrt": per_rank_xrt,
     }
-    if rank == 0 and world == 1 and not args.no_two_engines:
+    if args.full and rank == 0 and world == 1 and not args.no_two_engines:
         # the same workload with the step's kernels launched one by one instead of replayed from the graph (the library's
         # default: no idle gap between replays; reported beside the headline, which keeps BASELINE's named configuration)
         model.set_use_graph(False)
@@ -811,7 +835,7 @@ def main():
         result["temperature_0p7"] = {"value": round(wl["batch"] * wl["frames"] * FRAME_SEC * args.steps / e3, 1), "unit": "x real-time",
                                      "ms_per_step": round(1e3 * e3 / args.steps, 3),
                                      "config": "same workload at temperature 0.7: N(0,1)*sqrt(T) per (request, step) drawn on the device (flow_lm.go:386-408)"}
-    if not args.no_two_engines and args.workload == "b64_10s_bf16":
+    if args.full and not args.no_two_engines and args.workload == "b64_10s_bf16":
         # every rank, its own GPU: the serve-mode shape of configs[3] (per-GPU shard of the worker pool); aggregate = sum of the ranks' audio
         # over the slowest rank's wall time, like `value`
         # (a pass that fails on ONE rank must not leave the others waiting in a collective: every rank runs the pass on its own, then all of them agree on
@@ -855,20 +879,20 @@ def main():
             result["serve_mode"] = dict(serve.pop("uniform"), **serve)
         elif serve:
             result["serve_mode"] = serve
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             result["roofline"] = roofline_pass(pkg, model, wl, prompts, voice, traffic)
         except Exception as e:  # noqa: BLE001
             log(f"[bench] roofline pass failed: {e}")
             result["roofline"] = None
-    if rank == 0 and world == 1 and not args.no_two_engines and args.workload == "b64_10s_bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_two_engines and args.workload == "b64_10s_bf16":
         # more rows per AR step through one engine (a step's time hardly depends on its rows): labelled extras beside the unchanged 64-per-GPU headline
         for bw in (128, 256):
             try:
                 result[f"b{bw}"] = wide_batch_pass(pkg, model, wl, bw, voice, max(3, args.steps), sync)
             except Exception as e:  # noqa: BLE001
                 log(f"[bench] b{bw} pass failed: {e}")
-    if rank == 0 and world == 1 and not args.no_b1 and not args.no_two_engines and args.workload == "b64_10s_bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_b1 and not args.no_two_engines and args.workload == "b64_10s_bf16":
         # serving configuration, reported beside the headline (not `value`): two engines over the same weights, each running
         # the same 64-utterance passes back to back, so that one pass's Mimi decode overlaps the other's prefill + AR loop
         try:
@@ -903,11 +927,11 @@ def main():
     model.close()
     del arena
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_b1 and args.workload != "b1_5s_f32":
             # BASELINE.json configs[1]: batch 1, f32 weights, 5-s utterance (latency-oriented)
             wl1 = WORKLOADS["b1_5s_f32"]
-            p1 = checkpoint_path(pkg, wl1["file"], 0, lambda: None)
+            p1 = checkpoint_path(pkg, wl1["file"], 0, lambda: None, rdir)
             m1, _ = open_model(pkg, p1, wl1, 0, 1, local)
             v1 = m1.upload_voice(pkg.VoiceModelState(voice_modules(pkg, cfg)))
             e1, lat1, _ = run_workload(pkg, m1, wl1, all_prompts[:1], v1, max(3, args.steps), 2, lambda: None, sync)
@@ -939,7 +963,7 @@ def main():
                 log(f"[bench] int8 pass failed: {e}")
         if not args.no_cpu_baseline:
             try:
-                p32 = checkpoint_path(pkg, "F32", 0, lambda: None)
+                p32 = checkpoint_path(pkg, "F32", 0, lambda: None, rdir)
                 result["cpu_baseline"] = cpu_baseline(pkg, p32, cfg, args.cpu_frames)
             except Exception as e:  # noqa: BLE001
                 log(f"[bench] cpu baseline failed: {e}")

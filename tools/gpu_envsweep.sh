@@ -1,9 +1,9 @@
 #!/bin/bash
 # GPU box: does a HIP-runtime knob move the dependent-launch floor?  headline (graph replay) + plain launches per setting
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; out=${PTTS_OUT_DIR:-out}; mkdir -p "$out"
 run() {
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-b1 --no-traffic --steps 6 > gpurun_out/r2o_env.json 2> gpurun_out/r2o_env.err
-  python3 -c "import json,sys;d=json.load(open('gpurun_out/r2o_env.json'));print('$1', 'graph', d['ms_per_step'], 'plain', d.get('plain_launches',{}).get('ms_per_step'), 'two_engines', d.get('two_engines',{}).get('value'))" 2>&1 | tail -1
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-b1 --no-traffic --steps 6 > $out/r2o_env.json 2> $out/r2o_env.err
+  python3 -c "import json,sys;d=json.load(open('$out/r2o_env.json'));print('$1', 'graph', d['ms_per_step'], 'plain', d.get('plain_launches',{}).get('ms_per_step'), 'two_engines', d.get('two_engines',{}).get('value'))" 2>&1 | tail -1
 }
 run baseline
 ROC_SYSTEM_SCOPE_SIGNAL=0 run ROC_SYSTEM_SCOPE_SIGNAL=0
