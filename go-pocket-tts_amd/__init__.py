@@ -6,4 +6,5 @@ synth.py   synthetic checkpoints / voices / prompts (no real weights exist offli
 """
 from . import runtime, synth  # noqa: F401
 from .runtime import (Batch, Cancelled, DeviceVoice, Dispatcher, GenerateResult, Model, PttsError, Runtime, RuntimeGenerateConfig, Service, TTSConfig,  # noqa: F401
-                      VoiceEmbedding, VoiceFile, VoiceModelState, load_voice_conditioning, KV_BF16, KV_F32, WEIGHTS_BF16, WEIGHTS_F32, WEIGHTS_INT8)
+                      VoiceEmbedding, VoiceFile, VoiceModelState, load_voice_conditioning, KV_BF16, KV_F32, WEIGHTS_BF16, WEIGHTS_F32, WEIGHTS_INT8,
+                      PCM_F32, PCM_S16, PCM_ULAW, PCM_ALAW, resample_length, wav_header)

@@ -22,7 +22,7 @@ void ptts_default_opts(ptts_opts* o) {
 }
 
 const char* ptts_last_error(void) { return last_error_ref().c_str(); }
-const char* ptts_version(void) { return "ptts-hip 0.2 gfx950"; }
+const char* ptts_version(void) { return "ptts-hip 0.3 gfx950"; }
 
 int ptts_plan_create(const char* path, const ptts_opts* opts, ptts_plan** out) {
     return guard([&] {
@@ -188,9 +188,11 @@ void ptts_free_result(ptts_result* r) {
     if (!r) return;
     result_free(r->pcm);
     result_free(r->pcm16);
+    result_free(r->pcm8);
     free(r->latents);
     r->pcm = nullptr;
     r->pcm16 = nullptr;
+    r->pcm8 = nullptr;
     r->latents = nullptr;
     r->n_samples = 0;
     r->n_frames = 0;
@@ -660,14 +662,15 @@ int ptts_decode_latents(ptts_model* h, const float* latents, int32_t n_utt, int3
 }  // extern "C"
 
 // the Mimi encoder with the staged observation points of tests (stages; capi_hooks.cpp ptts_debug_encode_stages)
-int ptts::capi::encode_stages(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out, float* const* stages) {
+int ptts::capi::encode_stages(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out, float* const* stages,
+                              const int32_t* rates) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
         Model& m = *h->m;
         require_encoder(m.d);
         std::lock_guard<std::mutex> lock(m.mu);
         m.use_device();
-        mimi_encode(m, pcm, n_samples, n_clips, latent_out, stages);
+        mimi_encode(m, pcm, n_samples, n_clips, latent_out, stages, rates);
     });
 }
 
@@ -706,12 +709,13 @@ static void require_voice_encoder(const Desc& d) {
 }
 
 // one clip -> its voice embedding in out (host, [ceil(n / hop)][d_model]); returns the frame count.  The caller holds m.mu.
-static int64_t encode_embedding(Model& m, const float* pcm, int64_t n_samples, float* out) {
+static int64_t encode_embedding(Model& m, const float* pcm, int64_t n_samples, float* out, int rate = kNativeRate) {
     const Lin& l = m.d.speaker_proj;
-    const int64_t nf = n_samples > 0 ? (n_samples + m.d.enc.hop - 1) / m.d.enc.hop : 0;
+    const int64_t n24 = mimi_encode_samples(std::max<int64_t>(n_samples, 0), rate);
+    const int64_t nf = n24 > 0 ? (n24 + m.d.enc.hop - 1) / m.d.enc.hop : 0;
     DevBuf& io = m.work(17, (size_t)std::max<int64_t>(nf, 1) * (l.in + l.out) * sizeof(float));
     float* lat = io.as<float>();
-    const int64_t f = mimi_encode_clip(m, pcm, n_samples, lat, nullptr);
+    const int64_t f = mimi_encode_clip(m, pcm, n_samples, lat, nullptr, rate);
     float* dout = lat + (size_t)f * l.in;
     GemmArgs g;   // the product ptts_speaker_project runs, on the latents where the encoder left them
     g.A = lat; g.amap = RowMap{l.in, 0, 0};
@@ -815,28 +819,40 @@ int ptts_voice_from_embeddings(ptts_model* h, const float* const* emb, const int
     });
 }
 
+static void voice_from_audio(ptts_model* h, const float* const* pcm, const int64_t* n_samples, const int32_t* rates, int32_t n, ptts_voice** out) {
+    if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+    Model& m = *h->m;
+    require_voice_encoder(m.d);
+    if (n <= 0) throw Error(PTTS_EINVAL, strfmt("ptts-hip: voice build needs at least one clip, got %d", n));
+    if (!pcm || !n_samples || !out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
+    const int64_t hop = m.d.enc.hop, D = m.d.d_model;
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    std::vector<std::vector<float>> embs((size_t)n);
+    std::vector<const float*> ptrs((size_t)n);
+    std::vector<int64_t> frames((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (!pcm[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: clip %d is null", i));
+        const int rate = rates ? rates[i] : kNativeRate;
+        const int64_t n24 = mimi_encode_samples(std::max<int64_t>(n_samples[i], 0), rate);
+        embs[(size_t)i].resize((size_t)std::max<int64_t>((n24 + hop - 1) / hop, 1) * D);
+        frames[(size_t)i] = encode_embedding(m, pcm[i], n_samples[i], embs[(size_t)i].data(), rate);
+        ptrs[(size_t)i] = embs[(size_t)i].data();
+    }
+    auto vs = voice_build(m, ptrs.data(), frames.data(), D, n);
+    voices_out(vs, out);
+}
+
 int ptts_voice_from_audio(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n, ptts_voice** out) {
-    return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
-        Model& m = *h->m;
-        require_voice_encoder(m.d);
-        if (n <= 0) throw Error(PTTS_EINVAL, strfmt("ptts-hip: voice build needs at least one clip, got %d", n));
-        if (!pcm || !n_samples || !out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
-        const int64_t hop = m.d.enc.hop, D = m.d.d_model;
-        std::lock_guard<std::mutex> lock(m.mu);
-        m.use_device();
-        std::vector<std::vector<float>> embs((size_t)n);
-        std::vector<const float*> ptrs((size_t)n);
-        std::vector<int64_t> frames((size_t)n);
-        for (int i = 0; i < n; i++) {
-            if (!pcm[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: clip %d is null", i));
-            embs[(size_t)i].resize((size_t)std::max<int64_t>((n_samples[i] + hop - 1) / hop, 1) * D);
-            frames[(size_t)i] = encode_embedding(m, pcm[i], n_samples[i], embs[(size_t)i].data());
-            ptrs[(size_t)i] = embs[(size_t)i].data();
-        }
-        auto vs = voice_build(m, ptrs.data(), frames.data(), D, n);
-        voices_out(vs, out);
-    });
+    return guard([&] { voice_from_audio(h, pcm, n_samples, nullptr, n, out); });
+}
+
+int ptts_voice_from_audio_rates(ptts_model* h, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates, int32_t n, ptts_voice** out) {
+    return guard([&] { voice_from_audio(h, pcm, n_samples, sample_rates, n, out); });
+}
+
+int ptts_mimi_encode_rates(ptts_model* h, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates, int32_t n_clips, float* const* latent_out) {
+    return encode_stages(h, pcm, n_samples, n_clips, latent_out, nullptr, sample_rates);
 }
 
 int ptts_voice_offset(const ptts_voice* v, int64_t* offset) {
@@ -986,6 +1002,104 @@ int ptts_op_linear(const float* x, const float* w, const float* bias, int64_t ro
         PTTS_HIP(hipDeviceSynchronize());
         down(y, dy.p, (size_t)rows * out * 4);
     });
+}
+
+int64_t ptts_resample_length(int64_t n_in, int32_t in_rate, int32_t out_rate) {
+    const std::string e = rate_pair_error(in_rate, out_rate);
+    if (!e.empty()) { set_last_error(e); return -PTTS_EINVAL; }
+    if (n_in < 0) { set_last_error(strfmt("ptts-hip: resample: negative sample count %lld", (long long)n_in)); return -PTTS_EINVAL; }
+    return resample_length(n_in, in_rate, out_rate);
+}
+
+// n host rows -> n host rows through one device buffer each way: rows packed 256-byte aligned, one k_resample launch per ResampleRing::kRows rows
+static void device_convert(Model& m, const float* const* in, const int64_t* n_in, int32_t n, const RateFilter* f, const int64_t* n_out, int fmt,
+                           void* const* out) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> ioff((size_t)n), ooff((size_t)n);
+    size_t ib = 0, ob = 0;
+    for (int i = 0; i < n; i++) {
+        ioff[(size_t)i] = ib; ib += ((size_t)n_in[i] * sizeof(float) + 255) & ~(size_t)255;
+        ooff[(size_t)i] = ob; ob += ((size_t)n_out[i] * pcm_bytes(fmt) + 255) & ~(size_t)255;
+    }
+    char* di = m.work(25, ib).as<char>();
+    char* dout = m.work(26, ob).as<char>();
+    std::vector<ResampleRow> rows;
+    for (int i = 0; i < n; i++) {
+        if (n_in[i] > 0) PTTS_HIP(hipMemcpyAsync(di + ioff[(size_t)i], in[i], (size_t)n_in[i] * sizeof(float), hipMemcpyHostToDevice, s));
+        if (n_out[i] > 0) rows.push_back(resample_row(f, (const float*)(di + ioff[(size_t)i]), n_in[i], dout + ooff[(size_t)i], 0, n_out[i], fmt));
+    }
+    resample_launch(m, rows, s);
+    for (int i = 0; i < n; i++)
+        if (n_out[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], dout + ooff[(size_t)i], (size_t)n_out[i] * pcm_bytes(fmt), hipMemcpyDeviceToHost, s));
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
+int ptts_resample(ptts_model* h, const float* const* in, const int64_t* n_in, int32_t n, int32_t in_rate, int32_t out_rate, float* const* out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        const std::string e = rate_pair_error(in_rate, out_rate);
+        if (!e.empty()) throw Error(PTTS_EINVAL, e);
+        if (n < 0 || (n > 0 && (!in || !n_in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: resample: null argument");
+        std::vector<int64_t> n_out((size_t)n);
+        for (int i = 0; i < n; i++) {
+            if (n_in[i] < 0 || (n_in[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: resample: row %d is empty or null", i));
+            n_out[(size_t)i] = resample_length(n_in[i], in_rate, out_rate);
+        }
+        if (in_rate == out_rate) {   // the identity: no taps, no launch
+            for (int i = 0; i < n; i++) if (n_in[i] > 0) std::memcpy(out[i], in[i], (size_t)n_in[i] * sizeof(float));
+            return;
+        }
+        Model& m = *h->m;
+        const RateFilter* f;
+        {
+            std::lock_guard<std::mutex> lock(m.mu);
+            m.use_device();
+            f = rate_filter(m, in_rate, out_rate, m.stream);
+        }
+        device_convert(m, in, n_in, n, f, n_out.data(), RS_F32, (void* const*)out);
+    });
+}
+
+int ptts_pcm_encode(ptts_model* h, const float* in, int64_t n, int32_t pcm_format, void* out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        if (pcm_format < PTTS_PCM_F32 || pcm_format > PTTS_PCM_ALAW) throw Error(PTTS_EINVAL, strfmt("ptts-hip: pcm_format %d is not a PTTS_PCM_* format", pcm_format));
+        if (n < 0 || (n > 0 && (!in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: pcm encode: null argument");
+        if (n == 0) return;
+        device_convert(*h->m, &in, &n, 1, nullptr, &n, pcm_format, &out);
+    });
+}
+
+int ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm_format, int64_t n_samples) {
+    const int rate = sample_rate ? sample_rate : kNativeRate;
+    std::string e = rate_error(rate, false);
+    if (e.empty() && (pcm_format < PTTS_PCM_F32 || pcm_format > PTTS_PCM_ALAW)) e = strfmt("ptts-hip: wav header: pcm_format %d is not a PTTS_PCM_* format", pcm_format);
+    const bool pcm16 = pcm_format == PTTS_PCM_S16;
+    const int len = pcm16 ? 44 : 58;
+    const uint32_t bytes_per = (uint32_t)pcm_bytes(pcm_format);
+    if (e.empty() && (!out || cap < len)) e = strfmt("ptts-hip: wav header: %d bytes of room, the header takes %d", cap, len);
+    if (e.empty() && n_samples >= 0 && (uint64_t)n_samples * bytes_per > 0xFFFFFFFFull - (uint64_t)len) e = "ptts-hip: wav header: more data than a RIFF file holds";
+    if (!e.empty()) { set_last_error(e); return -PTTS_EINVAL; }
+    const bool streaming = n_samples < 0;
+    const uint32_t data = streaming ? 0xFFFFFFFFu : (uint32_t)(n_samples * bytes_per);
+    const uint32_t riff = streaming ? 0xFFFFFFFFu : data + (uint32_t)len - 8;
+    uint8_t* p = out;
+    auto tag = [&](const char* t) { std::memcpy(p, t, 4); p += 4; };
+    auto u32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) *p++ = (uint8_t)(v >> (8 * k)); };
+    auto u16 = [&](uint32_t v) { *p++ = (uint8_t)v; *p++ = (uint8_t)(v >> 8); };
+    // WAVE format tags: 1 PCM, 3 IEEE float, 6 A-law, 7 mu-law
+    const uint32_t fmt_tag = pcm16 ? 1 : pcm_format == PTTS_PCM_F32 ? 3 : pcm_format == PTTS_PCM_ALAW ? 6 : 7;
+    tag("RIFF"); u32(riff); tag("WAVE");
+    tag("fmt "); u32(pcm16 ? 16 : 18);
+    u16(fmt_tag); u16(1); u32((uint32_t)rate); u32((uint32_t)rate * bytes_per); u16(bytes_per); u16(8 * bytes_per);
+    if (!pcm16) {
+        u16(0);                                                      // cbSize
+        tag("fact"); u32(4); u32(streaming ? 0xFFFFFFFFu : (uint32_t)n_samples);
+    }
+    tag("data"); u32(data);
+    return len;
 }
 
 int ptts_op_pcm16(const float* samples, int64_t n, int16_t* out) {

@@ -42,6 +42,10 @@ int ptts_debug_flow_cluster_inject(ptts_model* h, int32_t block) {
     });
 }
 
+int64_t ptts_debug_resample_launches(int32_t reset) {
+    return reset ? g_resample_launches.exchange(0) : g_resample_launches.load();
+}
+
 int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap) {
     static thread_local std::map<std::string, int64_t> census;
     std::string s;

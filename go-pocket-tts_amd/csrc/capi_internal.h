@@ -65,7 +65,8 @@ inline void down(void* h, const void* d, size_t n) { if (n) PTTS_HIP(hipMemcpy(h
 int decode_stages(ptts_model* h, const float* latents, int32_t n_utt, int32_t frames, float* pcm, float* mimi_latent, float* transformer_out);
 
 // the Mimi encoder (ptts_mimi_encode: stages null; ptts_debug_encode_stages: one clip, kEncStages observation buffers)
-int encode_stages(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out, float* const* stages);
+int encode_stages(ptts_model* h, const float* const* pcm, const int64_t* n_samples, int32_t n_clips, float* const* latent_out, float* const* stages,
+                  const int32_t* rates = nullptr);
 
 }  // namespace capi
 }  // namespace ptts

@@ -125,15 +125,34 @@ void mimi_encode_stage_shapes(const Desc& d, int64_t n_samples, int64_t* shapes)
     std::memcpy(shapes, sh, sizeof sh);
 }
 
-int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* lat_dev, float* const* stages) {
+int64_t mimi_encode_samples(int64_t n_samples, int rate) {
+    if (rate == kNativeRate) return n_samples;
+    const std::string err = rate_pair_error(rate, kNativeRate);
+    if (!err.empty()) throw Error(PTTS_EINVAL, "voice encode: " + err);
+    return resample_length(n_samples, rate, kNativeRate);
+}
+
+// the frames of a clip of n_samples at `rate` (resampled to 24 kHz); PTTS_EINVAL naming the resampled length beyond the cap
+static int64_t clip_frames(const Desc& d, int64_t n_samples, int rate) {
+    const int64_t n24 = mimi_encode_samples(n_samples, rate);
+    const int64_t frames = (n24 + d.enc.hop - 1) / d.enc.hop;
+    if (frames > mimi_encode_max_frames(d)) {
+        if (rate != kNativeRate)
+            throw Error(PTTS_EINVAL, strfmt("voice encode: %lld samples at %d Hz resample to %lld samples at 24000 Hz (%lld frames), more than the %lld frames one "
+                                            "clip may have", (long long)n_samples, rate, (long long)n24, (long long)frames, (long long)mimi_encode_max_frames(d)));
+        throw Error(PTTS_EINVAL, strfmt("voice encode: %lld samples (%lld frames) exceed the %lld frames one clip may have", (long long)n_samples,
+                                        (long long)frames, (long long)mimi_encode_max_frames(d)));
+    }
+    return frames;
+}
+
+int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* lat_dev, float* const* stages, int rate) {
     const Desc& d = m.d;
     const auto& e = d.enc;
     require_encoder(d);
     if (!pcm || n_samples <= 0) throw Error(PTTS_EINVAL, "voice encode: audio is empty");
-    const int64_t frames = (n_samples + e.hop - 1) / e.hop;
-    if (frames > mimi_encode_max_frames(d))
-        throw Error(PTTS_EINVAL, strfmt("voice encode: %lld samples (%lld frames) exceed the %lld frames one clip may have", (long long)n_samples,
-                                        (long long)frames, (long long)mimi_encode_max_frames(d)));
+    const int64_t n24 = mimi_encode_samples(n_samples, rate);
+    const int64_t frames = clip_frames(d, n_samples, rate);
     hipStream_t s = m.stream;
     const int C = d.mimi_dim;
     EncWs w = enc_layout(d, frames, nullptr);
@@ -142,7 +161,12 @@ int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* l
     float* const* st = stages;
     // zero history in front of every buffer, zero samples after the clip's end
     zero(w.pcm, (size_t)(w.Pp + w.L[0]), s);
-    PTTS_HIP(hipMemcpyAsync(w.pcm + w.Pp, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+    if (rate == kNativeRate) PTTS_HIP(hipMemcpyAsync(w.pcm + w.Pp, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+    else {   // the clip at its own rate, resampled by k_resample straight into the encoder's input (no host round trip)
+        DevBuf& src = m.work(26, (size_t)n_samples * sizeof(float));
+        PTTS_HIP(hipMemcpyAsync(src.p, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+        resample_launch(m, {resample_row(rate_filter(m, rate, kNativeRate, s), src.as<float>(), n_samples, w.pcm + w.Pp, 0, n24, RS_F32)}, s);
+    }
     for (int j = 0; j < 3; j++) {
         zero(w.u[j], (size_t)w.P[j] * e.ch[j], s);
         zero(w.uo[j], (size_t)w.P[j] * e.ch[j], s);
@@ -203,7 +227,7 @@ int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* l
     return frames;
 }
 
-void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, int n_clips, float* const* latent_out, float* const* stages) {
+void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, int n_clips, float* const* latent_out, float* const* stages, const int32_t* rates) {
     const Desc& d = m.d;
     require_encoder(d);
     if (n_clips <= 0 || !pcm || !n_samples || !latent_out) throw Error(PTTS_EINVAL, "voice encode: no clips");
@@ -212,7 +236,8 @@ void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, in
     for (int i = 0; i < n_clips; i++) {
         if (!pcm[i] || n_samples[i] <= 0) throw Error(PTTS_EINVAL, strfmt("voice encode: audio of clip %d is empty", i));
         if (!latent_out[i]) throw Error(PTTS_EINVAL, strfmt("voice encode: no output buffer for clip %d", i));
-        longest = std::max(longest, (n_samples[i] + d.enc.hop - 1) / d.enc.hop);
+        const int rate = rates ? rates[i] : kNativeRate;
+        longest = std::max(longest, rate == kNativeRate ? (n_samples[i] + d.enc.hop - 1) / d.enc.hop : clip_frames(d, n_samples[i], rate));
     }
     if (longest > mimi_encode_max_frames(d))
         throw Error(PTTS_EINVAL, strfmt("voice encode: a clip of %lld frames exceeds the %lld frames one clip may have", (long long)longest,
@@ -221,7 +246,7 @@ void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, in
     m.work(16, enc_layout(d, longest, nullptr).floats * sizeof(float));
     DevBuf& lat = m.work(17, (size_t)longest * d.mimi_dim * sizeof(float));
     for (int i = 0; i < n_clips; i++) {
-        const int64_t f = mimi_encode_clip(m, pcm[i], n_samples[i], lat.as<float>(), stages);
+        const int64_t f = mimi_encode_clip(m, pcm[i], n_samples[i], lat.as<float>(), stages, rates ? rates[i] : kNativeRate);
         PTTS_HIP(hipMemcpyAsync(latent_out[i], lat.p, (size_t)f * d.mimi_dim * sizeof(float), hipMemcpyDeviceToHost, m.stream));
         PTTS_HIP(hipStreamSynchronize(m.stream));
     }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -250,6 +251,33 @@ void launch_zero_rows(float* base, int64_t batch_stride, int b, int64_t n, hipSt
 void launch_pcm16(const float* in, int16_t* out, int64_t n, hipStream_t stream);
 // the same on samples [off, off + n) of each of `rows` rows (row_stride samples apart; off, n, row_stride % 8 == 0)
 void launch_pcm16_rows(const float* in, int16_t* out, int rows, int64_t row_stride, int64_t off, int64_t n, hipStream_t stream);
+
+// Rate and format conversion of delivered audio (resample.hip, k_resample): one launch converts a table of rows, each with its own rate
+// pair, taps and output format.  Output j of a row sits at input position j*M/L: y[j] = sum over ascending k of x[base + dlo + k] * h[p][k]
+// (base = floor(j*M/L), p = j*M mod L), one f32 fmaf chain from 0; inputs outside [0, n_in) read as zero.  taps == nullptr: the identity
+// (L = M = 1, y[j] = x[j]).  The result is stored as f32, as WritePCM16Samples' int16, or as G.711 mu-law / A-law of that int16.
+enum ResampleFmt : int32_t { RS_F32 = 0, RS_S16 = 1, RS_ULAW = 2, RS_ALAW = 3 };   // = PTTS_PCM_*
+constexpr int kResampleThreads = 256;
+constexpr int kResampleMaxTile = 4 * kResampleThreads;   // outputs per workgroup (4 consecutive per lane)
+constexpr int kResampleWindow = 6144;                    // floats of input window a workgroup stages in LDS (at most)
+constexpr int kResampleTapsLds = 10240;                  // tap tables up to this many floats are staged in LDS; larger ones are read through the caches
+struct ResampleRow {
+    const float* src;      // input samples (device)
+    void* dst;             // output j goes to element j of dst (device or page-locked host memory), in the row's format
+    const float* taps;     // phase-major [L][K] (device, 16-byte aligned, padded to a multiple of 4 floats), nullptr: identity
+    // streaming hand-overs: the utterance's active flag and frame count as the host snapshot them (device; nullptr: n_in and o1 as given).
+    // If the utterance has ended inside the input (fin, *nf * spf < n_in, or !*act with *nf * spf <= n_in -- the flag is snapshot before the
+    // count, so an inactive utterance comes with its final count), its input ends at *nf * spf and every output up to
+    // ceil(n_in * L / M) -- at most o_cap -- is written
+    const int32_t* nf; const int32_t* act;
+    int64_t n_in, o0, o1, o_cap;   // outputs [o0, o1) are written (o_cap >= o1 bounds the grid)
+    int32_t L, M, K, dlo;
+    int32_t fmt, tile, spf, fin;   // tile: outputs per workgroup (multiple of 4, <= kResampleMaxTile)
+};
+// rows_dev: device copy of the n rows; lds_bytes / max_tiles: the largest dynamic LDS and tile count any row needs (resample.cpp sizes them)
+void launch_resample(const ResampleRow* rows_dev, int n, int max_tiles, size_t lds_bytes, hipStream_t stream);
+// k_resample launches of the whole process, every thread (the dispatcher's workers included): ptts_debug_resample_launches
+extern std::atomic<int64_t> g_resample_launches;
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

@@ -1367,21 +1367,23 @@ void stage_noise(Batch& b, const std::vector<SlotReq>& list, hipStream_t s) {
 
 const PcmRow* results_alloc(const Model& m, const std::vector<Delivery>& g, PcmRow* host_rows, PcmRow* dev_rows, hipStream_t s) {
     const int64_t spf = m.d.samples_per_frame;
-    bool all_pinned = true;
+    bool all_pinned = true, converts = false;
     for (size_t i = 0; i < g.size(); i++) {
         if (host_rows) host_rows[i] = PcmRow{nullptr, 0, 0};
         const Delivery& u = g[i];
         if (!u.res || u.filled) continue;
-        const bool s16 = u.req->pcm_format == PTTS_PCM_S16;
-        const int64_t ns = (int64_t)u.nf * spf;
-        void* p = result_alloc((size_t)std::max<int64_t>(1, ns) * (s16 ? sizeof(int16_t) : sizeof(float)));
-        if (s16) u.res->pcm16 = (int16_t*)p;
-        else u.res->pcm = (float*)p;
+        const int fmt = u.req->pcm_format;
+        const bool s16 = fmt == PTTS_PCM_S16;
+        const int64_t ns = egress_length(*u.req, (int64_t)u.nf * spf);
+        void* p = result_alloc((size_t)std::max<int64_t>(1, ns) * pcm_bytes(fmt));
+        set_result_buffer(*u.res, fmt, p);
         if (!p) continue;
         all_pinned = all_pinned && result_is_pinned(p);
+        converts = converts || request_converts(*u.req);
         if (host_rows) host_rows[i] = PcmRow{p, (int32_t)std::min<int64_t>(ns, INT32_MAX), s16 ? 1 : 0};
     }
-    if (!host_rows || !dev_rows || !all_pinned) return nullptr;
+    // a group with rows at another rate or in G.711 is decoded into the device buffer: results_deliver converts those rows from there
+    if (!host_rows || !dev_rows || !all_pinned || converts) return nullptr;
     PTTS_HIP(hipMemcpyAsync(dev_rows, host_rows, g.size() * sizeof(PcmRow), hipMemcpyHostToDevice, s));   // page-locked source: no wait needed
     return dev_rows;
 }
@@ -1392,21 +1394,26 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
     const int64_t spf = m.d.samples_per_frame;
     const int64_t n = (int64_t)g.size();
     const int16_t* pcm16 = nullptr;   // PCM16 egress on the device (audio/wav_stream.go:43-54), converted for the whole group at the first request that asks for it
+    std::vector<int64_t> conv;        // rows at another rate or in G.711: one k_resample launch for all of them
     for (int64_t i = 0; i < n; i++) {
         const Delivery& u = g[(size_t)i];
         if (!u.res) continue;
         ptts_result& r = *u.res;
-        r.n_frames = u.nf; r.eos_step = u.eos; r.n_samples = (int64_t)u.nf * spf;
-        const bool s16 = u.req->pcm_format == PTTS_PCM_S16;
-        if (s16 ? !r.pcm16 : !r.pcm) { r.status = PTTS_ENOMEM; continue; }
+        const int fmt = u.req->pcm_format;
+        r.n_frames = u.nf; r.eos_step = u.eos; r.n_samples = egress_length(*u.req, (int64_t)u.nf * spf);
+        const bool s16 = fmt == PTTS_PCM_S16;
+        if (!result_buffer(r, fmt)) { r.status = PTTS_ENOMEM; continue; }
         if (!stored && !u.filled && r.n_samples > 0) {   // all copies are queued back to back: the caller waits once
-            if (s16 && !pcm16) {
-                DevBuf& buf = m.work(8, (size_t)(n * pcm_stride) * sizeof(int16_t));
-                launch_pcm16(pcm, buf.as<int16_t>(), n * pcm_stride, s);
-                pcm16 = buf.as<int16_t>();
+            if (request_converts(*u.req)) conv.push_back(i);
+            else {
+                if (s16 && !pcm16) {
+                    DevBuf& buf = m.work(8, (size_t)(n * pcm_stride) * sizeof(int16_t));
+                    launch_pcm16(pcm, buf.as<int16_t>(), n * pcm_stride, s);
+                    pcm16 = buf.as<int16_t>();
+                }
+                if (s16) PTTS_HIP(hipMemcpyAsync(r.pcm16, pcm16 + i * pcm_stride, (size_t)r.n_samples * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+                else PTTS_HIP(hipMemcpyAsync(r.pcm, pcm + i * pcm_stride, (size_t)r.n_samples * sizeof(float), hipMemcpyDeviceToHost, s));
             }
-            if (s16) PTTS_HIP(hipMemcpyAsync(r.pcm16, pcm16 + i * pcm_stride, (size_t)r.n_samples * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-            else PTTS_HIP(hipMemcpyAsync(r.pcm, pcm + i * pcm_stride, (size_t)r.n_samples * sizeof(float), hipMemcpyDeviceToHost, s));
         }
         if (u.req->want_latents) {
             r.latents = (float*)malloc((size_t)std::max(1, u.nf) * ld * sizeof(float));
@@ -1415,6 +1422,35 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         }
         r.status = PTTS_OK;
     }
+    if (conv.empty()) return;
+    // k_resample stores straight into page-locked result buffers (like the decoder's direct store); a pageable one gets a device row and a copy
+    size_t scratch = 0;
+    for (int64_t i : conv) {
+        const ptts_result& r = *g[(size_t)i].res;
+        const int fmt = g[(size_t)i].req->pcm_format;
+        if (!result_is_pinned(result_buffer(r, fmt))) scratch += ((size_t)r.n_samples * pcm_bytes(fmt) + 255) & ~(size_t)255;
+    }
+    char* sb = scratch ? m.work(24, scratch).as<char>() : nullptr;
+    std::vector<ResampleRow> rows;
+    std::vector<std::pair<void*, const void*>> copies;
+    std::vector<size_t> copy_bytes;
+    for (int64_t i : conv) {
+        const Delivery& u = g[(size_t)i];
+        const ptts_result& r = *u.res;
+        const int fmt = u.req->pcm_format;
+        void* dst = result_buffer(r, fmt);
+        if (!result_is_pinned(dst)) {
+            const size_t bytes = (size_t)r.n_samples * pcm_bytes(fmt);
+            copies.emplace_back(dst, sb);
+            copy_bytes.push_back(bytes);
+            dst = sb;
+            sb += (bytes + 255) & ~(size_t)255;
+        }
+        rows.push_back(resample_row(rate_filter(m, kNativeRate, request_rate(*u.req), s), pcm + i * pcm_stride, (int64_t)u.nf * spf, dst, 0, r.n_samples, fmt));
+    }
+    resample_launch(m, rows, s);
+    for (size_t k = 0; k < copies.size(); k++)
+        PTTS_HIP(hipMemcpyAsync(copies[k].first, copies[k].second, copy_bytes[k], hipMemcpyDeviceToHost, s));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1522,9 +1558,19 @@ struct Chunk {
     // will own (stream_host) and announced from a host function queued on that stream (a HIP runtime thread).
     struct StreamRange {
         const Chunk* c; int f0, f1;
-        int32_t* nf;   // pinned: n_frames of every slot, read after the range's last step
+        int32_t* nf;   // pinned: n_frames of every slot, read after the range's last step (converting rows: then the active flags, [B, 2B))
+        bool last;     // the final hand-over: every utterance is flushed
+        std::vector<int64_t> ready;   // converting rows: the outputs this range delivers if the utterance goes on
     };
     std::vector<void*> stream_host = std::vector<void*>((size_t)B, nullptr);
+    // streaming at another rate or in G.711 (k_resample per hand-over): outputs converted so far if the utterance goes on (the next range's o0),
+    // outputs announced (host function), and the device rows the hand-overs are converted into (stream_stage, stage_row bytes apart) and copied
+    // from into the result buffers, like the f32 / PCM16 hand-overs: the host function reads what the copies have landed
+    bool any_conv = false;
+    std::vector<int64_t> stream_next = std::vector<int64_t>((size_t)B, 0);
+    mutable std::vector<int64_t> stream_sent = std::vector<int64_t>((size_t)B, 0);
+    char* stream_stage = nullptr;
+    size_t stage_row = 0;
     std::vector<std::unique_ptr<StreamRange>> stream_ranges;
     DevBuf* stream_s16 = nullptr;
     MimiWs mw;
@@ -1560,7 +1606,7 @@ struct Chunk {
     void phase(int i, hipStream_t st) { if (hipEvent_t e = phase_event(i)) PTTS_HIP(hipEventRecord(e, st)); }
     void setup(); void decoder_setup(); void ar_loop(); void deliver();   // the phases, in order
     void decode_upto(int f1, const PcmRow* rows = nullptr, bool* rows_used = nullptr);
-    void emit_upto(int f1);
+    void emit_upto(int f1, bool last = false);
 };
 
 // the batch, the slots' step budgets and EOS settings, voices, prompts and sampling noise
@@ -1620,12 +1666,16 @@ void Chunk::decoder_setup() {
             const ptts_request& r = req(i);
             if (!r.pcm_callback) continue;
             chunk = std::min(chunk, r.stream_frames > 0 ? (int)r.stream_frames : 12);
-            const size_t esz = r.pcm_format == PTTS_PCM_S16 ? sizeof(int16_t) : sizeof(float);
-            stream_host[(size_t)i] = result_alloc((size_t)std::max<int64_t>(1, (int64_t)list[i].max_steps * spf) * esz);
+            const size_t bytes = (size_t)std::max<int64_t>(1, egress_length(r, (int64_t)list[i].max_steps * spf)) * pcm_bytes(r.pcm_format);
+            stream_host[(size_t)i] = result_alloc(bytes);
             if (!stream_host[(size_t)i]) throw Error(PTTS_ENOMEM, "ptts-hip: out of host memory");
-            any_s16 |= r.pcm_format == PTTS_PCM_S16;
+            const bool conv = request_converts(r);
+            any_s16 |= r.pcm_format == PTTS_PCM_S16 && !conv;
+            any_conv |= conv;
+            if (conv) stage_row = std::max(stage_row, (bytes + 255) & ~(size_t)255);
         }
         if (any_s16) stream_s16 = &m.work(8, (size_t)B * T * spf * sizeof(int16_t));
+        if (stage_row) stream_stage = m.work(28, stage_row * (size_t)B).as<char>();
     }
     // Decoder workspace (~2.7 MB of f32 activations per latent frame and utterance).  A batch of more than kMimiGroup utterances that is decoded in one go after the
     // loop (the default) goes through the decoder group after group in the SAME buffers (stream order keeps them apart); a batch whose frame ranges are decoded under
@@ -1713,14 +1763,16 @@ void Chunk::decode_upto(int f1, const PcmRow* rows, bool* rows_used) {
     f_done = f1;
 }
 
-// hand frames [f_emitted, f1) to the streaming callbacks (they are decoded: f1 <= f_done)
-void Chunk::emit_upto(int f1) {
-    if (!streaming || f1 <= f_emitted) return;
+// hand frames [f_emitted, f1) to the streaming callbacks (they are decoded: f1 <= f_done).  Rows at another rate or in G.711 are converted by one
+// k_resample launch: every output whose filter support lies inside the decoded input, the rest with the next hand-over -- all of it once the
+// utterance has ended (its input ends there: outputs past it read zeros) or with the last hand-over.  Offsets count output samples.
+void Chunk::emit_upto(int f1, bool last) {
+    if (!streaming || (f1 <= f_emitted && !(last && any_conv))) return;
     const int f0 = f_emitted;
     hipStream_t s2 = m.stream2;
-    if (stream_s16) launch_pcm16_rows(pcm->as<float>(), stream_s16->as<int16_t>(), B, (int64_t)T * spf, (int64_t)f0 * spf, (int64_t)(f1 - f0) * spf, s2);
+    if (stream_s16 && f1 > f0) launch_pcm16_rows(pcm->as<float>(), stream_s16->as<int16_t>(), B, (int64_t)T * spf, (int64_t)f0 * spf, (int64_t)(f1 - f0) * spf, s2);
     for (int i = 0; i < B; i++) {
-        if (!stream_host[(size_t)i]) continue;
+        if (!stream_host[(size_t)i] || request_converts(req(i))) continue;
         const int fe = std::min(f1, list[i].max_steps);
         if (fe <= f0) continue;
         const bool s16 = req(i).pcm_format == PTTS_PCM_S16;
@@ -1730,22 +1782,69 @@ void Chunk::emit_upto(int f1) {
                                 (size_t)(fe - f0) * spf * esz, hipMemcpyDeviceToHost, s2));
     }
     int32_t* nfp = nullptr;
-    PTTS_HIP(hipHostMalloc((void**)&nfp, (size_t)B * sizeof(int32_t), hipHostMallocDefault));
-    stream_ranges.emplace_back(new StreamRange{this, f0, f1, nfp});
-    PTTS_HIP(hipMemcpyAsync(nfp, b->st.n_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+    PTTS_HIP(hipHostMalloc((void**)&nfp, (size_t)2 * B * sizeof(int32_t), hipHostMallocDefault));
+    stream_ranges.emplace_back(new StreamRange{this, f0, f1, nfp, last, std::vector<int64_t>((size_t)B, 0)});
+    StreamRange& range = *stream_ranges.back();
+    if (any_conv) {
+        // one snapshot of (active, n_frames) for this range's k_resample rows AND its host function, so that both agree on which utterances
+        // have ended.  The AR loop goes on meanwhile: active is copied first, so an utterance seen inactive comes with its final frame count
+        DevBuf& snap = m.work(27, (size_t)2 * B * sizeof(int32_t));
+        int32_t* sa = snap.as<int32_t>();
+        int32_t* sn = sa + B;
+        PTTS_HIP(hipMemcpyAsync(sa, b->st.active, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s2));
+        PTTS_HIP(hipMemcpyAsync(sn, b->st.n_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s2));
+        std::vector<ResampleRow> rows;
+        std::vector<std::pair<int, ResampleRow>> staged;
+        for (int i = 0; i < B; i++) {
+            const ptts_request& r = req(i);
+            if (!stream_host[(size_t)i] || !request_converts(r)) continue;
+            const RateFilter* f = rate_filter(m, kNativeRate, request_rate(r), s2);
+            const int64_t n_dec = (int64_t)std::min(f1, list[i].max_steps) * spf;   // (no utterance runs past its step budget: its buffer's size)
+            const int64_t o0 = stream_next[(size_t)i], o1 = std::max(o0, resample_ready(f, n_dec));
+            void* dst = stream_stage + (size_t)i * stage_row;
+            ResampleRow row = resample_row(f, pcm->as<float>() + (size_t)i * T * spf, n_dec, dst, o0, o1, r.pcm_format);
+            row.o_cap = egress_length(r, n_dec);
+            row.nf = sn + i; row.act = sa + i; row.spf = (int32_t)spf; row.fin = last ? 1 : 0;
+            rows.push_back(row);
+            staged.emplace_back(i, row);
+            range.ready[(size_t)i] = o1;
+            stream_next[(size_t)i] = o1;
+        }
+        resample_launch(m, rows, s2);
+        for (const auto& st : staged) {   // the range's outputs [o0, o_cap); what is not final yet is copied again by a later range
+            const size_t esz = pcm_bytes(st.second.fmt);
+            if (st.second.o_cap > st.second.o0)
+                PTTS_HIP(hipMemcpyAsync((char*)stream_host[(size_t)st.first] + st.second.o0 * esz, (const char*)st.second.dst + st.second.o0 * esz,
+                                        (size_t)(st.second.o_cap - st.second.o0) * esz, hipMemcpyDeviceToHost, s2));
+        }
+        PTTS_HIP(hipMemcpyAsync(nfp, sn, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+        PTTS_HIP(hipMemcpyAsync(nfp + B, sa, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+    } else {
+        PTTS_HIP(hipMemcpyAsync(nfp, b->st.n_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+    }
     PTTS_HIP(hipLaunchHostFunc(s2, [](void* p) {
         const StreamRange& sr = *static_cast<const StreamRange*>(p);
         const Chunk& c = *sr.c;
         for (int i = 0; i < c.B; i++) {
             const ptts_request& r = c.req(i);
             if (!r.pcm_callback || !c.stream_host[(size_t)i] || c.cancelled[(size_t)i]) continue;
+            const size_t esz = pcm_bytes(r.pcm_format);
+            if (request_converts(r)) {   // the same arithmetic as the range's k_resample row, on the same snapshot
+                const int64_t n_dec = (int64_t)std::min(sr.f1, c.list[i].max_steps) * c.spf, e = (int64_t)sr.nf[i] * c.spf;
+                const bool ended = sr.last || e < n_dec || (sr.nf[c.B + i] == 0 && e <= n_dec);
+                const int64_t end = ended ? egress_length(r, std::min(n_dec, e)) : sr.ready[(size_t)i];
+                const int64_t sent = c.stream_sent[(size_t)i];
+                if (end <= sent) continue;
+                r.pcm_callback(r.pcm_user, sent, end - sent, (const char*)c.stream_host[(size_t)i] + (size_t)sent * esz);
+                c.stream_sent[(size_t)i] = end;
+                continue;
+            }
             const int end = std::min(sr.f1, (int)sr.nf[i]);   // frames past the utterance's end are not audio
             if (end <= sr.f0) continue;
-            const size_t esz = r.pcm_format == PTTS_PCM_S16 ? sizeof(int16_t) : sizeof(float);
             r.pcm_callback(r.pcm_user, (int64_t)sr.f0 * c.spf, (int64_t)(end - sr.f0) * c.spf, (const char*)c.stream_host[(size_t)i] + (size_t)sr.f0 * c.spf * esz);
         }
-    }, stream_ranges.back().get()));
-    f_emitted = f1;
+    }, &range));
+    f_emitted = std::max(f_emitted, f1);
 }
 
 // the frame counts back; the decode of what has not been decoded under the loop; the results
@@ -1773,15 +1872,14 @@ void Chunk::deliver() {
     if (m.prof.phases_on) { PTTS_HIP(hipStreamWaitEvent(m.stream2, m.prof.phase[2], 0)); phase(3, m.stream2); }
     bool stored = false;
     decode_upto(std::min(steps_run, Tmax), rows, &stored);   // frames past every utterance's end are never decoded
-    emit_upto(std::min(steps_run, Tmax));
+    emit_upto(std::min(steps_run, Tmax), true);
     phase(4, m.stream2);
     m.prof.phases = m.prof.phases_on && f_done > 0;
     PTTS_HIP(hipStreamSynchronize(m.stream2));
     mark("mimi");
     for (int i = 0; i < B; i++) {   // streamed: the buffer already holds every sample that was announced
         if (!g[(size_t)i].filled) continue;
-        if (req(i).pcm_format == PTTS_PCM_S16) res[idx[i]].pcm16 = (int16_t*)stream_host[(size_t)i];
-        else res[idx[i]].pcm = (float*)stream_host[(size_t)i];
+        set_result_buffer(res[idx[i]], req(i).pcm_format, stream_host[(size_t)i]);
         stream_host[(size_t)i] = nullptr;
     }
     results_deliver(m, g, stored, pcm->as<float>(), (int64_t)T * spf, b->latents.as<float>(), (int64_t)b->max_steps * ld, s);
@@ -1806,6 +1904,12 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
     if (q.noise && q.noise_rows > 0 && q.noise_rows < resolve_max_steps(q))
         return strfmt("generate: injected noise has %d rows, the step budget is %d", q.noise_rows, resolve_max_steps(q));
     if (std::isnan(q.temperature)) return "generate: temperature is NaN";
+    if (q.pcm_format < PTTS_PCM_F32 || q.pcm_format > PTTS_PCM_ALAW)
+        return strfmt("generate: pcm_format %d is not PTTS_PCM_F32, PTTS_PCM_S16, PTTS_PCM_ULAW or PTTS_PCM_ALAW", q.pcm_format);
+    if (q.sample_rate != 0) {
+        const std::string e = rate_pair_error(kNativeRate, q.sample_rate);
+        if (!e.empty()) return "generate: " + e;
+    }
     for (int64_t t = 0; t < q.n_tokens; t++)
         if (q.tokens[t] < 0 || q.tokens[t] >= d.n_bins)
             return strfmt("generate: text embeddings: native: token id %lld (%lld) out of range [0,%d)", (long long)t, (long long)q.tokens[t], d.n_bins);

@@ -34,6 +34,39 @@ struct DevBuf {
 
 struct Batch;
 
+// ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
+constexpr int kNativeRate = 24000;            // the decoder's rate: requests at 0 / 24000 in f32 or PCM16 are delivered as before, without k_resample
+constexpr int kResampleMaxL = 512;            // bounds of a reduced rate pair's tap table: L phases, L * K taps
+constexpr int kResampleMaxTaps = 65536;
+// one reduced rate pair (L = out / g, M = in / g) and its polyphase taps: the prototype h(t) at t = p / L - d for phase p and
+// d = dlo + k, rounded once to f32, 0 where |t| >= W.  W = 80 max(L, M) / (3 L) input samples, so the support test is the integer
+// 3 |p - d L| < A with A = 80 max(L, M)
+struct RateFilter {
+    int L = 1, M = 1, K = 0, dlo = 0, tile = 0;
+    int64_t A = 0;
+    size_t n_taps = 0;            // [L][K], padded to a multiple of 4
+    float* staged = nullptr;      // page-locked host copy the upload reads
+    DevBuf taps;
+    hipEvent_t ready = nullptr;   // recorded behind the upload on `up`; a launch on another stream waits for it (no host wait anywhere)
+    hipStream_t up = nullptr;
+    RateFilter() = default;
+    RateFilter(const RateFilter&) = delete;
+    RateFilter& operator=(const RateFilter&) = delete;
+    ~RateFilter();
+};
+// page-locked staging and device copies of k_resample's row tables: kRing turns of kRows rows, a turn reused once its launch has run
+struct ResampleRing {
+    static constexpr int kRing = 8, kRows = 256;
+    ResampleRow* host = nullptr;
+    DevBuf dev;
+    hipEvent_t done[kRing] = {};
+    int turn = 0;
+    ResampleRing() = default;
+    ResampleRing(const ResampleRing&) = delete;
+    ResampleRing& operator=(const ResampleRing&) = delete;
+    ~ResampleRing();
+};
+
 struct Prof {   // bench.py measurement hook (ptts_profile_*)
     bool on = false;
     std::vector<hipEvent_t> ev;
@@ -65,6 +98,8 @@ struct Model {
     std::vector<std::unique_ptr<DevBuf>> ws;       // grow-only workspaces (Mimi decode, prefill)
     std::unique_ptr<Batch> cached_batch;
     Prof prof;
+    std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
+    ResampleRing rs_ring;
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
     // re-issued as the 2 x depth launches (same bits) -- fc_fallbacks counts the events -- and this engine's batches keep the launches from then on
@@ -213,9 +248,13 @@ void mimi_layer_ffn(Model& m, const Desc::ML& L, float* x, RowMap xmap, int R, f
 // transformer's rate (8192 rows at 200 Hz: 512 frames = 40.96 s at full size).
 constexpr int kEncStages = 10;
 int64_t mimi_encode_max_frames(const Desc& d);
-void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, int n_clips, float* const* latent_out, float* const* stages = nullptr);
+// rates (optional, per clip, 8000..192000): clips at other rates than 24000 are resampled on the device into the encoder's input; the frame cap
+// applies to the resampled length
+void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, int n_clips, float* const* latent_out, float* const* stages = nullptr,
+                 const int32_t* rates = nullptr);
 // one clip -> device latents lat_dev [frames][mimi_dim] on m.stream (the caller holds m.mu); returns the frame count
-int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* lat_dev, float* const* stages = nullptr);
+int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* lat_dev, float* const* stages = nullptr, int rate = kNativeRate);
+int64_t mimi_encode_samples(int64_t n_samples, int rate);   // the 24 kHz samples a clip of n_samples at `rate` becomes (PTTS_EINVAL: a bad rate)
 void require_encoder(const Desc& d);
 void mimi_encode_stage_shapes(const Desc& d, int64_t n_samples, int64_t* shapes /* [kEncStages][2] (rows, channels) */);   // PTTS_EFORMAT naming the missing tensor on a checkpoint without encoder weights
 Model* model_open(Plan* plan, void* device_arena, int fill);
@@ -275,6 +314,34 @@ const PcmRow* results_alloc(const Model& m, const std::vector<Delivery>& g, PcmR
 // latents (row i at lat + i * lat_stride); status, n_frames, eos_step, n_samples.  Everything is queued on s.
 void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, const float* pcm, int64_t pcm_stride, const float* lat, int64_t lat_stride,
                      hipStream_t s);
+// rates (resample.cpp): positive multiples of 25 Hz, 8000..48000 for output and 8000..192000 for input; the message names a bad rate or a
+// pair whose tap table exceeds kResampleMaxL / kResampleMaxTaps (empty: fine)
+std::string rate_error(int64_t rate, bool input);
+std::string rate_pair_error(int in_rate, int out_rate);
+int64_t resample_length(int64_t n_in, int in_rate, int out_rate);           // ceil(n_in L / M); the pair must be valid
+// the pair's filter, built and uploaded on first use (nullptr: in_rate == out_rate, the identity); throws PTTS_EINVAL for a bad pair
+const RateFilter* rate_filter(Model& m, int in_rate, int out_rate, hipStream_t s);
+int64_t resample_ready(const RateFilter* f, int64_t n_dec);                  // outputs whose filter support lies inside the first n_dec inputs
+ResampleRow resample_row(const RateFilter* f, const float* src, int64_t n_in, void* dst, int64_t o0, int64_t o1, int fmt);
+void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t s);   // one k_resample launch per ResampleRing::kRows rows
+// a request's egress: its rate (0 -> 24000), whether it needs k_resample (another rate, or G.711), the bytes per sample of its format, and
+// its result buffer (pcm / pcm16 / pcm8 by format)
+inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
+inline bool request_converts(const ptts_request& r) {
+    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW;
+}
+inline size_t pcm_bytes(int fmt) { return fmt == PTTS_PCM_F32 ? 4 : fmt == PTTS_PCM_S16 ? 2 : 1; }
+inline void* result_buffer(const ptts_result& r, int fmt) {
+    return fmt == PTTS_PCM_F32 ? (void*)r.pcm : fmt == PTTS_PCM_S16 ? (void*)r.pcm16 : (void*)r.pcm8;
+}
+inline void set_result_buffer(ptts_result& r, int fmt, void* p) {
+    if (fmt == PTTS_PCM_F32) r.pcm = (float*)p;
+    else if (fmt == PTTS_PCM_S16) r.pcm16 = (int16_t*)p;
+    else r.pcm8 = (uint8_t*)p;
+}
+inline int64_t egress_length(const ptts_request& r, int64_t n24) {   // samples at the request's rate of n24 decoded ones
+    return request_rate(r) == kNativeRate ? n24 : resample_length(n24, kNativeRate, request_rate(r));
+}
 Model* model_share(Model& base);   // another engine over base's weight arena (base must outlive it)
 Model* model_replicate(Model& base, int device);   // the model on another GPU of this process: own arena, copied from base's by hipMemcpyPeer
 void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res);

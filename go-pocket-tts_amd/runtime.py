@@ -24,6 +24,8 @@ LIB_PATH = os.environ.get("PTTS_LIB_PATH") or os.path.join(_HERE, "libptts_hip.s
 PTTS_OK, PTTS_EINVAL, PTTS_EIO, PTTS_EFORMAT, PTTS_ENODEVICE, PTTS_ECANCELLED, PTTS_ENOMEM = range(7)
 WEIGHTS_F32, WEIGHTS_BF16, WEIGHTS_INT8 = 0, 1, 2
 KV_F32, KV_BF16 = 0, 1
+PCM_F32, PCM_S16, PCM_ULAW, PCM_ALAW = 0, 1, 2, 3   # ptts_request.pcm_format
+_PCM_DTYPES = {PCM_F32: "<f4", PCM_S16: "<i2", PCM_ULAW: "|u1", PCM_ALAW: "|u1"}
 
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int64)
@@ -61,7 +63,7 @@ class _Request(C.Structure):
                 ("voice_caches", C.POINTER(_FP)), ("voice_cache_steps", _IP), ("voice_offsets", _IP), ("noise", _FP),
                 ("step_callback", _STEP_CB), ("callback_user", C.c_void_p), ("cancel", C.POINTER(C.c_int32)),
                 ("want_latents", C.c_int32), ("pcm_format", C.c_int32), ("voice", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_rows", C.c_int32), ("reserved", C.c_int32 * 1),
-                ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p), ("stream_frames", C.c_int32), ("reserved2", C.c_int32 * 3)]
+                ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p), ("stream_frames", C.c_int32), ("sample_rate", C.c_int32), ("reserved2", C.c_int32 * 2)]
 
 
 class _Profile(C.Structure):
@@ -71,14 +73,14 @@ class _Profile(C.Structure):
 
 class _Result(C.Structure):
     _fields_ = [("pcm", _FP), ("n_samples", C.c_int64), ("latents", _FP), ("n_frames", C.c_int32), ("eos_step", C.c_int32),
-                ("status", C.c_int32), ("pcm16", C.POINTER(C.c_int16)), ("reserved", C.c_int32 * 2)]
+                ("status", C.c_int32), ("pcm16", C.POINTER(C.c_int16)), ("pcm8", C.POINTER(C.c_uint8))]
 
 
 # the same layout as a numpy record (generate_batch reads a whole batch of results as one table)
-_RESULT_DTYPE = np.dtype({"names": ["pcm", "n_samples", "latents", "n_frames", "eos_step", "status", "pcm16", "reserved"],
-                          "formats": ["<u8", "<i8", "<u8", "<i4", "<i4", "<i4", "<u8", ("<i4", 2)],
+_RESULT_DTYPE = np.dtype({"names": ["pcm", "n_samples", "latents", "n_frames", "eos_step", "status", "pcm16", "pcm8"],
+                          "formats": ["<u8", "<i8", "<u8", "<i4", "<i4", "<i4", "<u8", "<u8"],
                           "offsets": [_Result.pcm.offset, _Result.n_samples.offset, _Result.latents.offset, _Result.n_frames.offset,
-                                      _Result.eos_step.offset, _Result.status.offset, _Result.pcm16.offset, _Result.reserved.offset],
+                                      _Result.eos_step.offset, _Result.status.offset, _Result.pcm16.offset, _Result.pcm8.offset],
                           "itemsize": C.sizeof(_Result)})
 
 class _VoiceTensor(C.Structure):   # ptts_voice_tensor
@@ -105,12 +107,13 @@ ABI_SYMBOLS = [
     "ptts_voice_file_modules", "ptts_voice_file_module", "ptts_voice_file_state", "ptts_voice_open", "ptts_voice_open_bytes",
     "ptts_voice_from_embeddings", "ptts_voice_from_audio", "ptts_voice_offset", "ptts_voice_read_state", "ptts_voice_write", "ptts_voice_write_bytes",
     "ptts_voice_state_write_bytes", "ptts_voice_embedding_write", "ptts_free_bytes",
+    "ptts_resample_length", "ptts_resample", "ptts_pcm_encode", "ptts_mimi_encode_rates", "ptts_voice_from_audio_rates", "ptts_wav_header",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
-    "ptts_debug_encode_stages",
+    "ptts_debug_encode_stages", "ptts_debug_resample_launches",
 ]
 
 
@@ -198,6 +201,13 @@ def lib():
         L.ptts_op_attention_positions.argtypes = [_FP, _FP, _FP] + [C.c_int64] * 5 + [_IP, _IP, C.c_int64, _FP]
         L.ptts_op_conv1d_leftpad.argtypes = [_FP, _FP, _FP] + [C.c_int64] * 5 + [_FP]
         L.ptts_op_convtr1d_righttrim.argtypes = [_FP, _FP, _FP] + [C.c_int64] * 7 + [_FP]
+        L.ptts_resample_length.restype = C.c_int64
+        L.ptts_resample_length.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.ptts_resample.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_FP)]
+        L.ptts_pcm_encode.argtypes = [C.c_void_p, _FP, C.c_int64, C.c_int32, C.c_void_p]
+        L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
+        L.ptts_voice_from_audio_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
+        L.ptts_wav_header.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 
@@ -284,8 +294,10 @@ class RuntimeGenerateConfig:
     cancel: Optional[np.ndarray] = None  # int32[1]; nonzero = cancelled (the ctx of GenerateAudio)
     want_latents: bool = False
     pcm16: bool = False   # PCM egress on the device: GenerateResult.pcm is int16 = audio.WritePCM16Samples (wav_stream.go:43-54)
+    g711: str = ""        # "ulaw" / "alaw": GenerateResult.pcm is uint8 G.711 of that int16, encoded on the device (takes precedence over pcm16)
+    sample_rate: int = 0  # output rate in Hz (0: 24000); other rates are resampled on the device (k_resample)
     # frame-granular streaming: pcm_callback(sample_offset, samples) is called from a library thread for consecutive ranges of
-    # `stream_frames` frames while generation is still running (samples: a copy, float32 or int16 per pcm16)
+    # `stream_frames` frames while generation is still running (samples: a copy, float32, int16 or uint8 per the format; offsets count samples at sample_rate)
     pcm_callback: Optional[Callable[[int, np.ndarray], None]] = None
     stream_frames: int = 0
 
@@ -483,16 +495,17 @@ class Model:
         out = [DeviceVoice(hs[i], int(fr[i]), self.info) for i in range(n)]
         return out[0] if single else out
 
-    def voice_state_from_audio(self, pcm):
-        """24 kHz mono clips (a list: one call) -> encoder + speaker projection + one model-state build (ptts_voice_from_audio).
-        PARITY UNPINNED like voice_from_audio: the encoder's chain is inferred."""
+    def voice_state_from_audio(self, pcm, sample_rate=24000):
+        """Mono clips (a list: one call) at sample_rate (one rate, or one per clip; resampled to 24 kHz on the device) -> encoder + speaker
+        projection + one model-state build (ptts_voice_from_audio_rates).  PARITY UNPINNED like voice_from_audio: the encoder's chain is inferred."""
         single = not isinstance(pcm, (list, tuple))
         clips = [_f32(pcm).reshape(-1)] if single else [_f32(p).reshape(-1) for p in pcm]
         n = len(clips)
         pp = (_FP * max(n, 1))(*[_fp(c) for c in clips])
         ns = np.array([c.size for c in clips] or [0], np.int64)
+        rates = _rates(sample_rate, n)
         hs = (C.c_void_p * max(n, 1))()
-        _check(lib().ptts_voice_from_audio(self.h, pp, _ip(ns), n, hs))
+        _check(lib().ptts_voice_from_audio_rates(self.h, pp, _ip(ns), rates.ctypes.data_as(C.POINTER(C.c_int32)), n, hs))
         out = [DeviceVoice(hs[i], None, self.info) for i in range(n)]
         return out[0] if single else out
 
@@ -544,24 +557,47 @@ class Model:
         return out
 
     # ---- the Mimi encoder (PARITY UNPINNED: inferred architecture, no reference fixture; include/ptts.h ptts_mimi_encode) ----
-    def encode_audio(self, pcm):
-        """mimi.encode_to_latent (onnx/voice_encode.go:23-158) on the GPU: 24 kHz mono f32 PCM -> the raw latent [ceil(n / 1920), 512].
-        A list of clips is encoded in one call and gives a list of latents (each clip's result is independent of the others)."""
+    def encode_audio(self, pcm, sample_rate=24000):
+        """mimi.encode_to_latent (onnx/voice_encode.go:23-158) on the GPU: mono f32 PCM at sample_rate (one rate, or one per clip; resampled to
+        24 kHz on the device) -> the raw latent [ceil(n24 / 1920), 512].  A list of clips is encoded in one call and gives a list of latents (each
+        clip's result is independent of the others)."""
         single = not isinstance(pcm, (list, tuple))
         clips = [_f32(pcm).reshape(-1)] if single else [_f32(p).reshape(-1) for p in pcm]
-        outs = [np.empty((max(mimi_encode_frames(c.size), 0), self.info.mimi_dim), np.float32) for c in clips]
         n = len(clips)
+        rates = _rates(sample_rate, n)
+        n24 = [c.size if int(r) == 24000 else max(resample_length(c.size, int(r), 24000), 0) for c, r in zip(clips, rates)]
+        outs = [np.empty((max(mimi_encode_frames(k), 0), self.info.mimi_dim), np.float32) for k in n24]
         pp = (_FP * n)(*[_fp(c) for c in clips])
         ns = np.array([c.size for c in clips], np.int64)
         po = (_FP * n)(*[_fp(o) for o in outs])
-        L = lib()
-        L.ptts_mimi_encode.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
-        _check(L.ptts_mimi_encode(self.h, pp, _ip(ns), n, po))
+        _check(lib().ptts_mimi_encode_rates(self.h, pp, _ip(ns), rates.ctypes.data_as(C.POINTER(C.c_int32)), n, po))
         return outs[0] if single else outs
 
-    def voice_from_audio(self, pcm) -> VoiceEmbedding:
+    def resample(self, x, in_rate: int, out_rate: int):
+        """ptts_resample: mono f32 rows (an array, or a list: one launch for all) from in_rate to out_rate on the device."""
+        single = not isinstance(x, (list, tuple))
+        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+        n = len(rows)
+        outs = [np.empty(max(resample_length(r.size, in_rate, out_rate), 0), np.float32) for r in rows]
+        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+        po = (_FP * max(n, 1))(*[_fp(o) for o in outs])
+        ns = np.array([r.size for r in rows] or [0], np.int64)
+        _check(lib().ptts_resample(self.h, pp, _ip(ns), n, int(in_rate), int(out_rate), po))
+        return outs[0] if single else outs
+
+    def pcm_encode(self, x, pcm_format: int) -> np.ndarray:
+        """ptts_pcm_encode: the device egress conversion of 24 kHz f32 samples into PCM_F32 / PCM_S16 / PCM_ULAW / PCM_ALAW."""
+        x = _f32(x).reshape(-1)
+        out = np.empty(x.size, _PCM_DTYPES.get(int(pcm_format), "<f4"))
+        _check(lib().ptts_pcm_encode(self.h, _fp(x), x.size, int(pcm_format), out.ctypes.data))
+        return out
+
+    def voice_from_audio(self, pcm, sample_rate=24000) -> VoiceEmbedding:
         """EncodeVoice (onnx/voice_encode.go:23-158): encoder + speaker projection on the device -> a VoiceEmbedding [1, frames, d_model]
-        for RuntimeGenerateConfig.voice_embedding."""
+        for RuntimeGenerateConfig.voice_embedding.  A clip at another sample_rate is resampled to 24 kHz on the device first."""
+        if int(sample_rate) != 24000:
+            lat = self.encode_audio(pcm, sample_rate)
+            return VoiceEmbedding(self.speaker_project(lat), (1, lat.shape[0], self.info.d_model))   # (the layout of the 24 kHz call's data)
         x = _f32(pcm).reshape(-1)
         out = np.empty((max(mimi_encode_frames(x.size), 0), self.info.d_model), np.float32)
         frames = C.c_int64(0)
@@ -626,9 +662,10 @@ class Model:
         if cfg.cancel is not None:
             r.cancel = cfg.cancel.ctypes.data_as(C.POINTER(C.c_int32))
         r.want_latents = 1 if cfg.want_latents else 0
-        r.pcm_format = 1 if cfg.pcm16 else 0
+        r.pcm_format = _pcm_format(cfg)
+        r.sample_rate = int(getattr(cfg, "sample_rate", 0))
         if cfg.pcm_callback is not None:
-            dt = np.int16 if r.pcm_format else np.float32
+            dt = np.dtype(_PCM_DTYPES.get(r.pcm_format, "<f4"))
 
             def _pcm(_u, off, n, ptr, f=cfg.pcm_callback, dt=dt):
                 f(int(off), np.frombuffer(C.string_at(ptr, int(n) * np.dtype(dt).itemsize), dtype=dt))
@@ -639,17 +676,15 @@ class Model:
             r.stream_frames = int(cfg.stream_frames)
 
     def _take_result(self, rs, cfg) -> "GenerateResult":
-        s16 = bool(getattr(cfg, "pcm16", False))   # PCM16 egress: int16 samples encoded on the device
+        fmt = _pcm_format(cfg)   # PCM16 / G.711 egress: int16 / uint8 samples encoded on the device
+        field = {PCM_F32: "pcm", PCM_S16: "pcm16"}.get(fmt, "pcm8")
         if rs.n_samples:
             # zero-copy: the array views the library's (page-locked) result buffer and gives it back to the pool
             # when it is garbage-collected
-            pcm = np.asarray(_OwnedBuffer(rs.pcm16 if s16 else rs.pcm, int(rs.n_samples), "<i2" if s16 else "<f4"))
-            if s16:
-                rs.pcm16 = None
-            else:
-                rs.pcm = None
+            pcm = np.asarray(_OwnedBuffer(getattr(rs, field), int(rs.n_samples), _PCM_DTYPES[fmt]))
+            setattr(rs, field, None)
         else:
-            pcm = np.zeros(0, np.int16 if s16 else np.float32)
+            pcm = np.zeros(0, _PCM_DTYPES[fmt])
         lat = None
         if cfg.want_latents:
             lat = np.ctypeslib.as_array(rs.latents, (rs.n_frames, self.info.ldim)).copy()
@@ -672,21 +707,22 @@ class Model:
                     out.append(self._take_result(ress[i], cfgs[i]))
             else:
                 nf, es, ns = raw["n_frames"].tolist(), raw["eos_step"].tolist(), raw["n_samples"].tolist()
-                a32, a16 = raw["pcm"].tolist(), raw["pcm16"].tolist()
+                a32, a16, a8 = raw["pcm"].tolist(), raw["pcm16"].tolist(), raw["pcm8"].tolist()
                 raw["pcm"][:] = 0                                   # ownership moves to the arrays below (zero-copy, freed on collection)
                 raw["pcm16"][:] = 0
+                raw["pcm8"][:] = 0
                 for i in range(n):
-                    s16 = a16[i] != 0
-                    addr = a16[i] if s16 else a32[i]
+                    fmt = _pcm_format(cfgs[i])
+                    addr = a8[i] if fmt >= PCM_ULAW else a16[i] if fmt == PCM_S16 else a32[i]
                     if ns[i] and addr:
-                        pcm = np.asarray(_OwnedBuffer(addr, ns[i], "<i2" if s16 else "<f4"))
+                        pcm = np.asarray(_OwnedBuffer(addr, ns[i], _PCM_DTYPES[fmt]))
                     else:
                         if addr:
                             _free_addr(addr)
-                        pcm = np.zeros(0, np.int16 if cfgs[i].pcm16 else np.float32)
+                        pcm = np.zeros(0, _PCM_DTYPES[fmt])
                     out.append(GenerateResult(pcm, nf[i], es[i], None))
         finally:
-            if raw["pcm"].any() or raw["pcm16"].any() or raw["latents"].any():
+            if raw["pcm"].any() or raw["pcm16"].any() or raw["pcm8"].any() or raw["latents"].any():
                 for i in range(n):
                     lib().ptts_free_result(C.byref(ress[i]))
         return out
@@ -1041,6 +1077,14 @@ def mimi_encode_frames(n_samples: int) -> int:
     return int(L.ptts_mimi_encode_frames(int(n_samples)))
 
 
+def resample_launches(reset: bool = True) -> int:
+    """k_resample launches of the whole process, every thread (ptts_debug_resample_launches); reset: start counting again from 0."""
+    H = hooks()
+    H.ptts_debug_resample_launches.restype = C.c_int64
+    H.ptts_debug_resample_launches.argtypes = [C.c_int32]
+    return int(H.ptts_debug_resample_launches(1 if reset else 0))
+
+
 def launch_counts(on: bool) -> dict:
     """Kernel launches noted on this thread since the previous call ({kernel: count}); switches the census on / off."""
     buf = C.create_string_buffer(4096)
@@ -1073,6 +1117,34 @@ def wav_header_streaming() -> bytes:
     buf = (C.c_uint8 * 44)()
     lib().ptts_wav_header_streaming(buf)
     return bytes(buf)
+
+
+def _pcm_format(cfg) -> int:
+    g = getattr(cfg, "g711", "") or ""
+    if g:
+        if g not in ("ulaw", "alaw"):
+            raise PttsError(PTTS_EINVAL, f'g711 must be "ulaw" or "alaw", got {g!r}')
+        return PCM_ULAW if g == "ulaw" else PCM_ALAW
+    return PCM_S16 if getattr(cfg, "pcm16", False) else PCM_F32
+
+
+def _rates(sample_rate, n: int) -> np.ndarray:
+    r = np.asarray(sample_rate, np.int32).reshape(-1)
+    return np.ascontiguousarray(np.broadcast_to(r, (max(n, 1),)) if r.size == 1 else r, np.int32)
+
+
+def resample_length(n_in: int, in_rate: int, out_rate: int) -> int:
+    """ptts_resample_length (no GPU): ceil(n_in L / M); < 0 (-PTTS_EINVAL) for a bad rate or pair."""
+    return int(lib().ptts_resample_length(int(n_in), int(in_rate), int(out_rate)))
+
+
+def wav_header(sample_rate: int = 24000, pcm_format: int = PCM_S16, n_samples: int = -1) -> bytes:
+    """ptts_wav_header: the WAV header of n_samples mono samples (< 0: a streaming header) in pcm_format at sample_rate."""
+    buf = (C.c_uint8 * 64)()
+    n = lib().ptts_wav_header(buf, 64, int(sample_rate), int(pcm_format), int(n_samples))
+    if n < 0:
+        raise PttsError(-n, lib().ptts_last_error().decode(errors="replace"))
+    return bytes(buf[:n])
 
 
 def op_pcm16(samples) -> np.ndarray:

@@ -112,8 +112,10 @@ typedef void (*ptts_step_callback)(void* user, int32_t step, int32_t max_steps);
 
 typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_samples, const void* samples);
 
-#define PTTS_PCM_F32 0
-#define PTTS_PCM_S16 1
+#define PTTS_PCM_F32  0
+#define PTTS_PCM_S16  1
+#define PTTS_PCM_ULAW 2   /* G.711 mu-law bytes of the PCM16 sample (result.pcm8) */
+#define PTTS_PCM_ALAW 3   /* G.711 A-law bytes of the PCM16 sample (result.pcm8) */
 
 typedef struct ptts_request {
     const int64_t* tokens; int64_t n_tokens;          /* must be non-empty (:57-59) */
@@ -136,7 +138,8 @@ typedef struct ptts_request {
     ptts_step_callback step_callback; void* callback_user;
     const volatile int32_t* cancel;                   /* polled between steps; nonzero -> PTTS_ECANCELLED */
     int32_t want_latents;                             /* 1: also return the latent frames */
-    int32_t pcm_format;                               /* PTTS_PCM_F32 (0): result.pcm; PTTS_PCM_S16 (1): result.pcm16, encoded on the device */
+    int32_t pcm_format;                               /* PTTS_PCM_F32 (0): result.pcm; PTTS_PCM_S16 (1): result.pcm16, encoded on the device;
+                                                       * PTTS_PCM_ULAW (2) / PTTS_PCM_ALAW (3): result.pcm8, G.711 of that int16, encoded on the device */
     /* a voice model state already resident in HBM (ptts_voice_create); exclusive with the two host forms above.
      * The reference loads the voice file once per Synthesize call and rebuilds the FlowLM state from it for
      * every chunk (service.go:127,216-246, flow_lm.go:134-145); the device copy is that cached voice. */
@@ -151,7 +154,11 @@ typedef struct ptts_request {
      * pcm_format).  The callback must not call into this library.  stream_frames: frames per hand-over (<= 0: 12 = 0.96 s). */
     ptts_pcm_callback pcm_callback; void* pcm_user;
     int32_t stream_frames;
-    int32_t reserved2[3];
+    /* output rate in Hz (0: 24000, the decoder's own): a multiple of 25 from 8000 to 48000.  Other than 24000 (or a G.711 format), the
+     * decoded samples go through k_resample on the device -- the polyphase filter of DESIGN.md section 8 (N3) -- and n_samples, stream
+     * offsets and buffers count samples at this rate: n_frames * 0.08 * sample_rate.  Other values: PTTS_EINVAL naming the rate. */
+    int32_t sample_rate;
+    int32_t reserved2[2];
 } ptts_request;
 
 typedef struct ptts_result {
@@ -161,7 +168,8 @@ typedef struct ptts_result {
     int32_t status;                                   /* per-request PTTS_* code */
     int16_t* pcm16;                                   /* PTTS_PCM_S16: n_samples little-endian samples, v = int16(clamp(s, -1, 1) * 32767)
                                                        * exactly as audio.WritePCM16Samples (internal/audio/wav_stream.go:43-54); pcm is NULL then */
-    int32_t reserved[2];
+    uint8_t* pcm8;                                    /* PTTS_PCM_ULAW / PTTS_PCM_ALAW: n_samples G.711 bytes (ITU-T G.711, the classic linear2ulaw /
+                                                       * linear2alaw of the PCM16 sample); pcm and pcm16 are NULL then.  Freed by ptts_free_result */
 } ptts_result;
 
 /* A second ENGINE over the weights of `base` (its own streams, KV caches, workspaces; the weight arena is shared and
@@ -414,7 +422,32 @@ int ptts_op_convtr1d_righttrim(const float* x /* [B,Cin,L] */, const float* w /*
 /* audio.WritePCM16Samples on the device (internal/audio/wav_stream.go:43-54), without the byte packing */
 int ptts_op_pcm16(const float* samples, int64_t n, int16_t* out);
 
-/* build/version string, e.g. "ptts-hip 0.2 gfx950" */
+/* ---- sample rates and egress formats.  Rates are multiples of 25 Hz: 8000..48000 out, 8000..192000 in; the filter
+ *      is the windowed-sinc polyphase of DESIGN.md (Kaiser, beta 8.6, 24 zero crossings, cutoff 0.45 of the lower Nyquist rate), one f32 fmaf chain
+ *      per output in ascending input order -- so batched, streamed and one-shot conversions give the same bits.  A rate pair whose reduced
+ *      tap table exceeds the kernel's bound (512 phases, 65536 taps) is refused with PTTS_EINVAL naming both rates. ---- */
+/* samples that n_in samples at in_rate become at out_rate: ceil(n_in * L / M).  No GPU.  -PTTS_EINVAL for a bad rate, pair or count */
+int64_t ptts_resample_length(int64_t n_in, int32_t in_rate, int32_t out_rate);
+/* n rows of host samples resampled on the device in one launch: out[i] (host) receives ptts_resample_length(n_in[i], in_rate, out_rate) floats.
+ * in_rate == out_rate copies. */
+int  ptts_resample(ptts_model* m, const float* const* in, const int64_t* n_in, int32_t n, int32_t in_rate, int32_t out_rate, float* const* out);
+/* the device egress conversion at 24 kHz: n host samples -> out (host) in pcm_format (f32 as is, PCM16 as ptts_op_pcm16, G.711 of that int16) */
+int  ptts_pcm_encode(ptts_model* m, const float* in, int64_t n, int32_t pcm_format, void* out);
+/* ptts_mimi_encode / ptts_voice_from_audio for clips at their own rates (sample_rates[i], 8000..192000; NULL: all 24000): each clip is uploaded
+ * as it is and k_resample writes its 24 kHz samples straight into the encoder's input.  The 512-frame cap applies to the resampled length
+ * (ptts_mimi_encode_frames(ptts_resample_length(n_samples[i], sample_rates[i], 24000))) and the error names it. */
+int  ptts_mimi_encode_rates(ptts_model* m, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates, int32_t n_clips,
+                            float* const* latent_out);
+int  ptts_voice_from_audio_rates(ptts_model* m, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates, int32_t n,
+                                 ptts_voice** out /* [n] */);
+/* A WAV header for mono audio of n_samples samples (n_samples < 0: streaming, every size 0xFFFFFFFF) in pcm_format at sample_rate (0: 24000):
+ * PCM16 -> the 44-byte PCM header (at 24000 and n_samples < 0 exactly ptts_wav_header_streaming's); f32 (format 3), A-law (6), mu-law (7) ->
+ * an 18-byte fmt chunk (cbSize 0) plus a fact chunk: 58 bytes.  Returns the header length, -PTTS_EINVAL for a bad argument or cap too small. */
+int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm_format, int64_t n_samples);
+
+/* build/version string, e.g. "ptts-hip 0.3 gfx950".  0.3: ptts_request.sample_rate, PTTS_PCM_ULAW / PTTS_PCM_ALAW with ptts_result.pcm8
+ * (in the place of reserved fields: the struct sizes are those of 0.2), ptts_resample_length, ptts_resample, ptts_pcm_encode,
+ * ptts_mimi_encode_rates, ptts_voice_from_audio_rates, ptts_wav_header */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of

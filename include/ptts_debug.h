@@ -63,6 +63,9 @@ const char* ptts_debug_last_attention_kernel(void);
  * cap - 1 characters, returns the full length), clears it, and switches counting on (1) or off (0) from here on.  Calls that
  * run their launches on the calling thread (every entry point except the dispatcher's) are covered. */
 int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap);
+/* k_resample launches of the whole process since the last reset, on every thread (the launch census above sees the calling thread only, and the
+ * continuous engine converts on the dispatcher's worker threads); reset != 0: returns the count and sets it to 0 */
+int64_t ptts_debug_resample_launches(int32_t reset);
 
 /* Test hook for the bounded hand-offs of k_flow_cluster (csrc/flow_cluster.hip): the model's NEXT plain-launched AR step runs the flow net's residual
  * blocks with one workgroup withholding what it should publish for block `block` (1-based; 0 clears).  Its peers' sweeps give up after their bound, the
