@@ -1062,6 +1062,42 @@ int ptts_resample(ptts_model* h, const float* const* in, const int64_t* n_in, in
     });
 }
 
+// the device chain of ptts_request.dsp on host rows: upload (rows packed 256-byte aligned), the same launches, download
+int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts, float* const* out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        if (rows < 0 || (rows > 0 && (!in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: dsp: null argument");
+        if (opts) {
+            const std::string e = dsp_opts_error(*opts);
+            if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        }
+        for (int i = 0; i < rows; i++)
+            if (n[i] < 0 || (n[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: dsp: row %d is negative or null", i));
+        if (!dsp_active(opts)) {   // nothing switched on: a copy, no launch
+            for (int i = 0; i < rows; i++) if (n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            return;
+        }
+        Model& m = *h->m;
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        hipStream_t s = m.stream;
+        std::vector<size_t> off((size_t)rows);
+        size_t bytes = 0;
+        for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
+        char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
+        std::vector<DspJob> jobs;
+        for (int i = 0; i < rows; i++) {
+            if (n[i] <= 0) continue;
+            PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
+            jobs.push_back(DspJob{(float*)(buf + off[(size_t)i]), n[i], opts});
+        }
+        dsp_launch(m, jobs, s);
+        for (int i = 0; i < rows; i++)
+            if (n[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
+        PTTS_HIP(hipStreamSynchronize(s));
+    });
+}
+
 int ptts_pcm_encode(ptts_model* h, const float* in, int64_t n, int32_t pcm_format, void* out) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");

@@ -46,6 +46,14 @@ int64_t ptts_debug_resample_launches(int32_t reset) {
     return reset ? g_resample_launches.exchange(0) : g_resample_launches.load();
 }
 
+int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out) {
+    return guard([&] {
+        if (n < 0 || (n > 0 && (!in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: dsp: null argument");
+        if (n > 0 && out != in) std::memmove(out, in, (size_t)n * sizeof(float));
+        dsp_dc_block_blocked(out, n, kNativeRate);
+    });
+}
+
 int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap) {
     static thread_local std::map<std::string, int64_t> census;
     std::string s;

@@ -279,6 +279,24 @@ void launch_resample(const ResampleRow* rows_dev, int n, int max_tiles, size_t l
 // k_resample launches of the whole process, every thread (the dispatcher's workers included): ptts_debug_resample_launches
 extern std::atomic<int64_t> g_resample_launches;
 
+// Post-processing of decoded 24 kHz audio in place (dsp.hip): ptts_dsp_apply's chain -- peak normalise, DC block,
+// fade in, fade out -- on a table of ragged rows.  k_dsp_peak (normalise rows: max |x| as the uint32 image, atomicMax), k_dsp_summary +
+// k_dsp_carry (DC rows: the zero-state end state of every full tile, then the state entering each tile in tile order; dsp_block.h) and
+// k_dsp_apply (gain, the recurrence of every run from its entering state, the fade gains, one store).  Tiles are kDspTile samples on the
+// row's own grid, so a row's bits do not depend on the rows beside it.
+enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2 };
+struct DspRow {
+    float* x;              // the row's samples (device), rewritten in place
+    int64_t n;             // samples; nothing at or beyond n is touched
+    int64_t fade_in, fade_out;   // samples of each fade (0: none, <= n)
+    uint32_t* peak;        // normalise rows: one word, zero before k_dsp_peak
+    double* tiles;         // DC rows: [ceil(n / kDspTile)][4] = E_f (2), S_f (2)
+    int32_t flags, pad;
+};
+struct DspScan;
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; any_norm / any_dc: whether a row has the flag
+void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, bool any_norm, bool any_dc, const DspScan& scan, hipStream_t stream);
+
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.
 // final_conv with rows: utterance b's samples [0, lim) go straight to dst (f32, or int16 through WritePCM16Samples' arithmetic) --

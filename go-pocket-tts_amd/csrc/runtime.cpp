@@ -1395,6 +1395,15 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
     const int64_t n = (int64_t)g.size();
     const int16_t* pcm16 = nullptr;   // PCM16 egress on the device (audio/wav_stream.go:43-54), converted for the whole group at the first request that asks for it
     std::vector<int64_t> conv;        // rows at another rate or in G.711: one k_resample launch for all of them
+    if (!stored) {   // post-processing (ptts_request.dsp): every such row of the group at once, in place in the decoder's buffer, in front of the egress
+        std::vector<DspJob> jobs;
+        for (int64_t i = 0; i < n; i++) {
+            const Delivery& u = g[(size_t)i];
+            if (u.res && !u.filled && u.nf > 0 && dsp_active(u.req->dsp) && result_buffer(*u.res, u.req->pcm_format))
+                jobs.push_back(DspJob{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, u.req->dsp});
+        }
+        if (!jobs.empty()) dsp_launch(m, jobs, s);
+    }
     for (int64_t i = 0; i < n; i++) {
         const Delivery& u = g[(size_t)i];
         if (!u.res) continue;
@@ -1909,6 +1918,14 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
     if (q.sample_rate != 0) {
         const std::string e = rate_pair_error(kNativeRate, q.sample_rate);
         if (!e.empty()) return "generate: " + e;
+    }
+    if (q.dsp) {
+        const std::string e = dsp_opts_error(*q.dsp);
+        if (!e.empty()) return "generate: " + e;
+        if (q.pcm_callback) {   // the peak and the end are not known when samples are handed over; the filter and the fade in are refused with it for now
+            const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : nullptr;
+            if (f) return strfmt("generate: dsp: %s cannot be combined with pcm_callback", f);
+        }
     }
     for (int64_t t = 0; t < q.n_tokens; t++)
         if (q.tokens[t] < 0 || q.tokens[t] >= d.n_bins)

@@ -67,6 +67,19 @@ struct ResampleRing {
     ~ResampleRing();
 };
 
+// page-locked staging and device copies of the DSP kernels' row tables (dsp_device.cpp), as ResampleRing
+struct DspRing {
+    static constexpr int kRing = 8, kRows = 256;
+    DspRow* host = nullptr;
+    DevBuf dev;
+    hipEvent_t done[kRing] = {};
+    int turn = 0;
+    DspRing() = default;
+    DspRing(const DspRing&) = delete;
+    DspRing& operator=(const DspRing&) = delete;
+    ~DspRing();
+};
+
 struct Prof {   // bench.py measurement hook (ptts_profile_*)
     bool on = false;
     std::vector<hipEvent_t> ev;
@@ -100,6 +113,7 @@ struct Model {
     Prof prof;
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
     ResampleRing rs_ring;
+    DspRing dsp_ring;
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
     // re-issued as the 2 x depth launches (same bits) -- fc_fallbacks counts the events -- and this engine's batches keep the launches from then on
@@ -327,8 +341,14 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
 // a request's egress: its rate (0 -> 24000), whether it needs k_resample (another rate, or G.711), the bytes per sample of its format, and
 // its result buffer (pcm / pcm16 / pcm8 by format)
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
-inline bool request_converts(const ptts_request& r) {
-    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW;
+// post-processing on the device (dsp_device.cpp, dsp.hip): whether a request's ptts_dsp_opts switch anything on; the message of a bad one
+// (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
+inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0); }
+std::string dsp_opts_error(const ptts_dsp_opts& o);
+struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; };
+void dsp_launch(Model& m, const std::vector<DspJob>& jobs, hipStream_t s);
+inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)
+    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || dsp_active(r.dsp);
 }
 inline size_t pcm_bytes(int fmt) { return fmt == PTTS_PCM_F32 ? 4 : fmt == PTTS_PCM_S16 ? 2 : 1; }
 inline void* result_buffer(const ptts_result& r, int fmt) {
@@ -398,6 +418,9 @@ void dsp_peak_normalize(float* s, int64_t n);
 void dsp_dc_block(float* s, int64_t n, int sample_rate);
 void dsp_fade_in(float* s, int64_t n, int sample_rate, double ms);
 void dsp_fade_out(float* s, int64_t n, int sample_rate, double ms);
+struct DspScan;
+DspScan dsp_scan_coeffs(int sample_rate);                          // the DC block's section and the powers of its state matrix (dsp_block.h)
+void dsp_dc_block_blocked(float* s, int64_t n, int sample_rate);   // dsp_dc_block in the device's blocked form, on the host
 
 // the weight broadcast of a multi-GPU start-up (broadcast.cpp)
 void rccl_unique_id(uint8_t out[128]);

@@ -56,6 +56,10 @@ class _Info(C.Structure):
                 ("arena_bytes", C.c_int64), ("weights", C.c_int32), ("kv", C.c_int32)]
 
 
+class DspOpts(C.Structure):   # ptts_dsp_opts
+    _fields_ = [("normalize", C.c_int32), ("dc_block", C.c_int32), ("fade_in_ms", C.c_double), ("fade_out_ms", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 class _Request(C.Structure):
     _fields_ = [("tokens", _IP), ("n_tokens", C.c_int64), ("temperature", C.c_float), ("eos_threshold", C.c_float),
                 ("max_steps", C.c_int32), ("estimated_max_steps", C.c_int32), ("lsd_steps", C.c_int32),
@@ -63,7 +67,7 @@ class _Request(C.Structure):
                 ("voice_caches", C.POINTER(_FP)), ("voice_cache_steps", _IP), ("voice_offsets", _IP), ("noise", _FP),
                 ("step_callback", _STEP_CB), ("callback_user", C.c_void_p), ("cancel", C.POINTER(C.c_int32)),
                 ("want_latents", C.c_int32), ("pcm_format", C.c_int32), ("voice", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_rows", C.c_int32), ("reserved", C.c_int32 * 1),
-                ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p), ("stream_frames", C.c_int32), ("sample_rate", C.c_int32), ("reserved2", C.c_int32 * 2)]
+                ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p), ("stream_frames", C.c_int32), ("sample_rate", C.c_int32), ("dsp", C.POINTER(DspOpts))]
 
 
 class _Profile(C.Structure):
@@ -108,12 +112,13 @@ ABI_SYMBOLS = [
     "ptts_voice_from_embeddings", "ptts_voice_from_audio", "ptts_voice_offset", "ptts_voice_read_state", "ptts_voice_write", "ptts_voice_write_bytes",
     "ptts_voice_state_write_bytes", "ptts_voice_embedding_write", "ptts_free_bytes",
     "ptts_resample_length", "ptts_resample", "ptts_pcm_encode", "ptts_mimi_encode_rates", "ptts_voice_from_audio_rates", "ptts_wav_header",
+    "ptts_dsp_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
-    "ptts_debug_encode_stages", "ptts_debug_resample_launches",
+    "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
 ]
 
 
@@ -300,6 +305,12 @@ class RuntimeGenerateConfig:
     # `stream_frames` frames while generation is still running (samples: a copy, float32, int16 or uint8 per the format; offsets count samples at sample_rate)
     pcm_callback: Optional[Callable[[int, np.ndarray], None]] = None
     stream_frames: int = 0
+    # post-processing on the device (ptts_request.dsp): dsp_apply's chain on this request's own 24 kHz audio, in front of the egress above
+    normalize: bool = False
+    dc_block: bool = False
+    fade_in_ms: float = 0.0
+    fade_out_ms: float = 0.0
+    dsp_opts: Optional[DspOpts] = None   # a ptts_dsp_opts handed over as it is (takes precedence; an all-off struct is a valid request)
 
 
 def _free_addr(addr: int):
@@ -585,6 +596,21 @@ class Model:
         _check(lib().ptts_resample(self.h, pp, _ip(ns), n, int(in_rate), int(out_rate), po))
         return outs[0] if single else outs
 
+    def dsp_rows(self, x, normalize: bool = False, dc_block: bool = False, fade_in_ms: float = 0.0, fade_out_ms: float = 0.0, opts: Optional[DspOpts] = None):
+        """ptts_dsp_rows: dsp_apply's chain on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all)."""
+        single = not isinstance(x, (list, tuple))
+        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+        n = len(rows)
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        o = opts if opts is not None else DspOpts(1 if normalize else 0, 1 if dc_block else 0, float(fade_in_ms), float(fade_out_ms))
+        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
+        ns = np.array([r.size for r in rows] or [0], np.int64)
+        L = lib()
+        L.ptts_dsp_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), C.POINTER(_FP)]
+        _check(L.ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), po))
+        return outs[0] if single else outs
+
     def pcm_encode(self, x, pcm_format: int) -> np.ndarray:
         """ptts_pcm_encode: the device egress conversion of 24 kHz f32 samples into PCM_F32 / PCM_S16 / PCM_ULAW / PCM_ALAW."""
         x = _f32(x).reshape(-1)
@@ -664,6 +690,10 @@ class Model:
         r.want_latents = 1 if cfg.want_latents else 0
         r.pcm_format = _pcm_format(cfg)
         r.sample_rate = int(getattr(cfg, "sample_rate", 0))
+        dsp = _dsp_opts(cfg)
+        if dsp is not None:
+            keep.append(dsp)
+            r.dsp = C.pointer(dsp)
         if cfg.pcm_callback is not None:
             dt = np.dtype(_PCM_DTYPES.get(r.pcm_format, "<f4"))
 
@@ -1239,6 +1269,27 @@ def dsp_apply(samples, normalize: bool = False, dc_block: bool = False, fade_in_
     L.ptts_dsp_apply.argtypes = [_FP, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double]
     _check(L.ptts_dsp_apply(_fp(out), out.size, 1 if normalize else 0, 1 if dc_block else 0, float(fade_in_ms), float(fade_out_ms)))
     return out
+
+
+def _dsp_opts(cfg) -> Optional[DspOpts]:
+    """The ptts_dsp_opts of a RuntimeGenerateConfig: None when nothing is set (the request carries NULL)."""
+    raw = getattr(cfg, "dsp_opts", None)
+    if raw is not None:
+        return raw
+    nz, dc = bool(getattr(cfg, "normalize", False)), bool(getattr(cfg, "dc_block", False))
+    fi, fo = float(getattr(cfg, "fade_in_ms", 0.0)), float(getattr(cfg, "fade_out_ms", 0.0))
+    if not (nz or dc or fi != 0.0 or fo != 0.0):
+        return None
+    return DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
+
+
+def dsp_blocked_host(samples) -> np.ndarray:
+    """Test hook (libptts_hooks.so ptts_debug_dsp_blocked_host): the DC block in the device kernels' blocked form, evaluated on the host."""
+    x = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    H = hooks()
+    H.ptts_debug_dsp_blocked_host.argtypes = [_FP, C.c_int64, _FP]
+    _check(H.ptts_debug_dsp_blocked_host(_fp(x), x.size, _fp(x)))
+    return x
 
 
 def rccl_unique_id() -> bytes:

@@ -117,6 +117,22 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
 #define PTTS_PCM_ULAW 2   /* G.711 mu-law bytes of the PCM16 sample (result.pcm8) */
 #define PTTS_PCM_ALAW 3   /* G.711 A-law bytes of the PCM16 sample (result.pcm8) */
 
+/* Post-processing of a request's audio on the device: the request's result is what
+ *     ptts_dsp_apply(samples, n, normalize, dc_block, fade_in_ms, fade_out_ms)
+ * makes of THAT REQUEST'S OWN 24 kHz f32 audio (n = n_frames * 1920; no padded frame is ever read), and THEN the request's egress
+ * (sample_rate, pcm_format) exactly as specified without it.  Order: normalise -> DC block -> fade in -> fade out, every intermediate
+ * rounded to f32 where ptts_dsp_apply rounds it.  Normalise and the fades give ptts_dsp_apply's bits; the DC block is the same float64
+ * recurrence evaluated as a blocked scan and agrees with it to one f32 step at the row's peak.  It is per request: the reference's CLI
+ * runs the chain over a whole text's concatenated chunks (cmd/pockettts/synth.go:361-390); a host that wants that for a multi-chunk
+ * text keeps using ptts_dsp_apply, or ptts_dsp_rows, on the concatenation. */
+typedef struct ptts_dsp_opts {
+    int32_t normalize;      /* PeakNormalize */
+    int32_t dc_block;       /* DCBlock, 20 Hz, Q 0.707, at 24 kHz */
+    double  fade_in_ms;     /* <= 0: none */
+    double  fade_out_ms;
+    int32_t reserved[4];    /* must be 0 */
+} ptts_dsp_opts;
+
 typedef struct ptts_request {
     const int64_t* tokens; int64_t n_tokens;          /* must be non-empty (:57-59) */
     float   temperature;                              /* RuntimeGenerateConfig.Temperature: sampling noise = N(0,1) * sqrt(max(t, 0)), drawn on the
@@ -158,7 +174,11 @@ typedef struct ptts_request {
      * decoded samples go through k_resample on the device -- the polyphase filter of DESIGN.md section 8 (N3) -- and n_samples, stream
      * offsets and buffers count samples at this rate: n_frames * 0.08 * sample_rate.  Other values: PTTS_EINVAL naming the rate. */
     int32_t sample_rate;
-    int32_t reserved2[2];
+    /* post-processing on the device, in front of the egress above (borrowed for the call).  NULL, or a struct with nothing switched on:
+     * none.  PTTS_EINVAL naming the field for a negative or NaN fade, a non-zero reserved word, and for any switch together with
+     * pcm_callback (the peak and the end of the utterance are not known when samples are handed over; dc_block and fade_in_ms are refused
+     * with it as well, for now). */
+    const ptts_dsp_opts* dsp;
 } ptts_request;
 
 typedef struct ptts_result {
@@ -198,10 +218,15 @@ void ptts_free_result(ptts_result* r);
 void ptts_wav_header_streaming(uint8_t out[44]);
 
 /* Optional post-processing of a finished utterance, in place, in the order the CLI applies it (cmd/pockettts/synth.go:361-390):
- * PeakNormalize, DCBlock (20 Hz high-pass), FadeIn, FadeOut (internal/audio/dsp.go:12-78); 24 kHz.  Host samples, host code.
+ * PeakNormalize, DCBlock (20 Hz high-pass), FadeIn, FadeOut (internal/audio/dsp.go:12-78); 24 kHz.  Host samples, host code (the device
+ * form: ptts_request.dsp, ptts_dsp_rows).
  * Normalise and the fades are bit-exact restatements; the DC block's biquad comes from a third-party module in the reference and
  * is held to the properties the reference's tests state (parity unpinned). */
 int  ptts_dsp_apply(float* samples, int64_t n, int32_t normalize, int32_t dc_block, double fade_in_ms, double fade_out_ms);
+/* The same chain on the device, by the kernels a request's `dsp` runs: rows of host samples at 24 kHz (in[i]: n[i] floats, any length
+ * >= 0), one launch sequence for all rows, out[i] (host, n[i] floats; in[i] == out[i] allowed) receives the result.  opts NULL or with
+ * nothing switched on copies.  PTTS_EINVAL as for ptts_request.dsp. */
+int  ptts_dsp_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts, float* const* out);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -447,7 +472,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
 
 /* build/version string, e.g. "ptts-hip 0.3 gfx950".  0.3: ptts_request.sample_rate, PTTS_PCM_ULAW / PTTS_PCM_ALAW with ptts_result.pcm8
  * (in the place of reserved fields: the struct sizes are those of 0.2), ptts_resample_length, ptts_resample, ptts_pcm_encode,
- * ptts_mimi_encode_rates, ptts_voice_from_audio_rates, ptts_wav_header */
+ * ptts_mimi_encode_rates, ptts_voice_from_audio_rates, ptts_wav_header.  Later additions keep the number (hosts test for the symbol):
+ * ptts_request.dsp (in the place of reserved2: the struct's size and every other offset are unchanged) with ptts_dsp_opts, and ptts_dsp_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of

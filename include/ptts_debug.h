@@ -67,6 +67,11 @@ int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap);
  * continuous engine converts on the dispatcher's worker threads); reset != 0: returns the count and sets it to 0 */
 int64_t ptts_debug_resample_launches(int32_t reset);
 
+/* The DC block of ptts_dsp_apply in the blocked form the device kernels run (csrc/dsp_block.h: runs of 30 samples from zero state, their end
+ * states folded in run order, the frame tiles' states carried in frame order), evaluated on the host by the host instantiation of the very
+ * functions the kernels call: n samples at 24 kHz, in -> out (in == out allowed).  No GPU. */
+int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out);
+
 /* Test hook for the bounded hand-offs of k_flow_cluster (csrc/flow_cluster.hip): the model's NEXT plain-launched AR step runs the flow net's residual
  * blocks with one workgroup withholding what it should publish for block `block` (1-based; 0 clears).  Its peers' sweeps give up after their bound, the
  * launch runs to its end, and the call that contained the step fails with PTTS_ENODEVICE ("hand-off timed out"); the exchange state is cleared, the next
