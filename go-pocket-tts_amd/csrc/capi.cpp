@@ -71,6 +71,23 @@ int ptts_dsp_apply(float* samples, int64_t n, int32_t normalize, int32_t dc_bloc
     });
 }
 
+int ptts_loudness(const float* samples, int64_t n, double* lufs) {
+    return guard([&] {
+        if ((!samples && n > 0) || n < 0 || !lufs) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");
+        *lufs = loud_lufs(loud_measure(samples, n));
+    });
+}
+
+int ptts_loudness_normalize(float* samples, int64_t n, double target_lufs, double* measured) {
+    return guard([&] {
+        if ((!samples && n > 0) || n < 0) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");
+        const std::string e = loud_target_error(target_lufs);
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        const double M = loud_normalize(samples, n, target_lufs);
+        if (measured) *measured = loud_lufs(M);
+    });
+}
+
 int ptts_rccl_unique_id(uint8_t out[128]) {
     return guard([&] {
         if (!out) throw Error(PTTS_EINVAL, "ptts-hip: null argument");
@@ -1096,6 +1113,27 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
             if (n[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
         PTTS_HIP(hipStreamSynchronize(s));
     });
+}
+
+static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
+    if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+    if (rows < 0 || (rows > 0 && (!in || !n || (target && !out) || (!target && !lufs)))) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");
+    if (target) {
+        const std::string e = loud_target_error(*target);
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+    }
+    for (int i = 0; i < rows; i++)
+        if (n[i] < 0 || (n[i] > 0 && (!in[i] || (target && !out[i])))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: loudness: row %d is negative or null", i));
+    loudness_rows_device(*h->m, in, n, rows, target ? *target : 0.0, target ? out : nullptr, lufs, nullptr);
+    if (lufs) for (int i = 0; i < rows; i++) lufs[i] = loud_lufs(lufs[i]);
+}
+
+int ptts_loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, double* lufs) {
+    return guard([&] { loudness_rows(h, in, n, rows, nullptr, nullptr, lufs); });
+}
+
+int ptts_loudness_normalize_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out, double* measured) {
+    return guard([&] { loudness_rows(h, in, n, rows, &target_lufs, out, measured); });
 }
 
 int ptts_pcm_encode(ptts_model* h, const float* in, int64_t n, int32_t pcm_format, void* out) {

@@ -3,6 +3,7 @@
 // reference links therefore exports no fault injection, no micro-benchmarks and no launch census.
 #include "capi_internal.h"
 #include "../../include/ptts_debug.h"
+#include "loudness_block.h"
 
 using namespace ptts;
 using namespace ptts::capi;
@@ -51,6 +52,30 @@ int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out) {
         if (n < 0 || (n > 0 && (!in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: dsp: null argument");
         if (n > 0 && out != in) std::memmove(out, in, (size_t)n * sizeof(float));
         dsp_dc_block_blocked(out, n, kNativeRate);
+    });
+}
+
+int ptts_debug_loudness_energies(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, double* const* out) {
+    return guard([&] {
+        if (rows < 0 || (rows > 0 && (!in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");
+        for (int i = 0; i < rows; i++)
+            if (n[i] < 0 || (n[i] > 0 && !in[i]) || (n[i] >= kLoudSub && !out[i])) throw Error(PTTS_EINVAL, strfmt("ptts-hip: loudness: row %d is negative or null", i));
+        std::vector<std::vector<double>> sub((size_t)rows);
+        if (h) {
+            if (!h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+            loudness_rows_device(*h->m, in, n, rows, 0.0, nullptr, nullptr, sub.data());
+        } else {
+            for (int i = 0; i < rows; i++) loud_sub_energies(in[i], n[i], sub[(size_t)i]);
+        }
+        for (int i = 0; i < rows; i++)
+            if (n[i] >= kLoudSub) std::memcpy(out[i], sub[(size_t)i].data(), (size_t)(n[i] / kLoudSub) * sizeof(double));
+    });
+}
+
+int ptts_debug_kweighting(int32_t sample_rate, double out[10]) {
+    return guard([&] {
+        if (!out || sample_rate <= 0) throw Error(PTTS_EINVAL, "ptts-hip: loudness: bad argument");
+        loud_kweight_coeffs(sample_rate, out);
     });
 }
 

@@ -10,6 +10,8 @@
 //                  (t_0 = S_f, t_(l+1) = A^30 t_l + e_l in run order), the rounding to f32, the two fade gains as two f32 products, one store.
 // The filter's input is the f32 product x * gain wherever it is read, so the peak is complete before k_dsp_summary starts (stream order).
 // Tiles lie on the row's own grid: a row's bits are a function of the row alone.  Nothing at or beyond n is read or written.
+// A loudness row (DSP_LOUD, loudness.hip) has its gain in a word k_loud_gate wrote; k_dsp_summary and k_dsp_apply are templates on whether the
+// table has such a row, so a table without one launches the instantiation that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
 #include "dsp_block.h"
 
@@ -20,7 +22,12 @@ namespace {
 constexpr int kPeakThreads = 256, kPeakChunk = 4 * kDspTile;
 
 struct Gain { bool on; float g; };
+template <bool LOUD>
 __device__ __forceinline__ Gain row_gain(const DspRow& r) {   // dsp_peak_normalize: gain = 1.0f / peak, a row of zeros stays as it is
+    if (LOUD && (r.flags & DSP_LOUD)) {   // loud_measure_gain's: a gain of 1 leaves the samples as they are
+        const float g = *reinterpret_cast<const float*>(r.loud + 1);
+        return Gain{g != 1.0f, g};
+    }
     if (!(r.flags & DSP_NORMALIZE)) return Gain{false, 1.0f};
     const float peak = __uint_as_float(*r.peak);
     if (peak == 0.0f) return Gain{false, 1.0f};
@@ -45,7 +52,7 @@ __device__ __forceinline__ void load_tile(const DspRow& r, int64_t base, int cnt
 __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restrict__ rows) {
     __shared__ float part[kPeakThreads / WAVE];
     const DspRow& r = rows[blockIdx.y];
-    if (!(r.flags & DSP_NORMALIZE)) return;
+    if (!(r.flags & (DSP_NORMALIZE | DSP_LOUD))) return;
     const int64_t i0 = (int64_t)blockIdx.x * kPeakChunk;
     if (i0 >= r.n) return;
     const int64_t i1 = min(i0 + (int64_t)kPeakChunk, r.n);
@@ -71,6 +78,7 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
     }
 }
 
+template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes][2];
@@ -78,7 +86,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restr
     const DspRow& r = rows[blockIdx.y];
     const int64_t base = (int64_t)blockIdx.x * kDspTile;
     if (!(r.flags & DSP_DC) || base + kDspTile >= r.n) return;   // only a full tile that another one follows hands a state on
-    load_tile(r, base, kDspTile, tile, row_gain(r));
+    load_tile(r, base, kDspTile, tile, row_gain<LOUD>(r));
     __syncthreads();
     const int l = threadIdx.x;
     double z1 = 0.0, z2 = 0.0;
@@ -117,6 +125,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restric
     }
 }
 
+template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restrict__ rows, const DspScan sc) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes][2], t[kDspLanes][2];
@@ -125,7 +134,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
     const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
     if (base >= n) return;
     const int cnt = (int)min((int64_t)kDspTile, n - base);
-    const Gain g = row_gain(r);
+    const Gain g = row_gain<LOUD>(r);
     const bool dc = (r.flags & DSP_DC) != 0;
     const int64_t fin = r.fade_in, fout0 = n - r.fade_out;   // fade in below fin, fade out from fout0 on
     if (!g.on && !dc && base >= fin && base + cnt <= fout0) return;   // a tile that no step changes
@@ -170,22 +179,26 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
 
 }  // namespace
 
-void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, bool any_norm, bool any_dc, const DspScan& scan, hipStream_t stream) {
+void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, bool any_norm, bool any_dc, const DspScan& scan, hipStream_t stream, bool any_loud,
+                const LoudScan* loud, bool apply) {
     if (n <= 0 || max_tiles <= 0) return;
-    if (any_norm) {
+    if (any_norm || (any_loud && apply)) {   // (a measurement alone has no ceiling to keep)
         note_launch("k_dsp_peak");
         hipLaunchKernelGGL(k_dsp_peak, dim3((unsigned)((max_tiles + 3) / 4), (unsigned)n), dim3(kPeakThreads), 0, stream, rows_dev);
     }
+    if (any_loud) launch_loudness(rows_dev, n, max_tiles, *loud, stream);
+    if (!apply) return;
     if (any_dc) {
         if (max_tiles > 1) {
             note_launch("k_dsp_summary");
-            hipLaunchKernelGGL(k_dsp_summary, dim3((unsigned)(max_tiles - 1), (unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
+            hipLaunchKernelGGL(any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, dim3((unsigned)(max_tiles - 1), (unsigned)n), dim3(kDspLanes), 0, stream,
+                               rows_dev, scan);
         }
         note_launch("k_dsp_carry");
         hipLaunchKernelGGL(k_dsp_carry, dim3((unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
     }
     note_launch("k_dsp_apply");
-    hipLaunchKernelGGL(k_dsp_apply, dim3((unsigned)max_tiles, (unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
+    hipLaunchKernelGGL(any_loud ? k_dsp_apply<true> : k_dsp_apply<false>, dim3((unsigned)max_tiles, (unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
 }
 
 }  // namespace ptts

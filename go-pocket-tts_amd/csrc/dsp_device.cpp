@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "dsp_block.h"
+#include "loudness_block.h"
 #include "runtime.h"
 
 namespace ptts {
@@ -16,7 +17,6 @@ std::string dsp_opts_error(const ptts_dsp_opts& o) {
 }
 
 DspRing::~DspRing() {
-    for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e);
     if (host) (void)hipHostFree(host);
 }
 
@@ -28,18 +28,23 @@ int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: mi
 }
 }  // namespace
 
-void dsp_launch(Model& m, const std::vector<DspJob>& jobs, hipStream_t s) {
+void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
+    const LoudScan& loud = loud_scan();
+    if (jobs.empty()) return;
     DspRing& R = m.dsp_ring;
     constexpr int kRows = DspRing::kRows;
     if (!R.host) {
-        PTTS_HIP(hipHostMalloc((void**)&R.host, sizeof(DspRow) * kRows * DspRing::kRing, hipHostMallocDefault));
-        R.dev.ensure(sizeof(DspRow) * kRows * DspRing::kRing);
+        PTTS_HIP(hipHostMalloc((void**)&R.host, DspRing::kTurnBytes * DspRing::kRing, hipHostMallocDefault));
+        R.dev.ensure(DspRing::kTurnBytes * DspRing::kRing);
     }
-    // scratch: a peak word per row, then [tiles][4] doubles per DC row
+    // scratch: a peak word per row, then [tiles][4] doubles per DC row and 2 + [tiles][12] per loudness row (kernels.h DspRow)
     size_t tile_doubles = 0;
-    for (const DspJob& j : jobs)
-        if (j.opts->dc_block) tile_doubles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4;
+    for (const DspJob& j : jobs) {
+        if (j.n <= 0) continue;
+        if (j.opts && j.opts->dc_block) tile_doubles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4;
+        if (j.loud) tile_doubles += 2 + (size_t)((j.n + kDspTile - 1) / kDspTile) * 12;
+    }
     const size_t peak_bytes = (jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
     char* scratch = m.work(29, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
     uint32_t* peaks = reinterpret_cast<uint32_t*>(scratch);
@@ -48,39 +53,83 @@ void dsp_launch(Model& m, const std::vector<DspJob>& jobs, hipStream_t s) {
     std::vector<DspRow> rows;
     rows.reserve(jobs.size());
     for (size_t k = 0; k < jobs.size(); k++) {
-        const DspJob& j = jobs[k];
-        if (j.n <= 0 || !dsp_active(j.opts)) continue;
+        DspJob& j = jobs[k];
+        j.loud_out = nullptr;
+        const bool on = dsp_active(j.opts);
+        if (j.n <= 0 || !(on || j.loud)) continue;
         DspRow r{};
         r.x = j.x; r.n = j.n;
-        r.fade_in = fade_samples(j.opts->fade_in_ms, j.n);
-        r.fade_out = fade_samples(j.opts->fade_out_ms, j.n);
+        r.fade_in = on ? fade_samples(j.opts->fade_in_ms, j.n) : 0;
+        r.fade_out = on ? fade_samples(j.opts->fade_out_ms, j.n) : 0;
         r.peak = peaks + k;
-        r.flags = (j.opts->normalize ? DSP_NORMALIZE : 0) | (j.opts->dc_block ? DSP_DC : 0);
-        if (j.opts->dc_block) { r.tiles = tiles; tiles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4; }
+        r.flags = (on && j.opts->normalize ? DSP_NORMALIZE : 0) | (on && j.opts->dc_block ? DSP_DC : 0) | (j.loud ? DSP_LOUD : 0);
+        if (r.flags & DSP_DC) { r.tiles = tiles; tiles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4; }
+        if (j.loud) {
+            r.loud = j.loud_out = tiles;
+            r.target = j.target_power;
+            tiles += 2 + (size_t)((j.n + kDspTile - 1) / kDspTile) * 12;
+        }
         rows.push_back(r);
     }
     for (size_t at = 0; at < rows.size(); at += kRows) {
         const int n = (int)std::min<size_t>(kRows, rows.size() - at);
         int64_t max_tiles = 0;
-        bool any_norm = false, any_dc = false;
+        bool any_norm = false, any_dc = false, any_loud = false;
         for (int i = 0; i < n; i++) {
             const DspRow& r = rows[at + (size_t)i];
             max_tiles = std::max(max_tiles, (r.n + kDspTile - 1) / kDspTile);
             any_norm = any_norm || (r.flags & DSP_NORMALIZE);
             any_dc = any_dc || (r.flags & DSP_DC);
+            any_loud = any_loud || (r.flags & DSP_LOUD);
         }
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: dsp: too many samples for one launch");
         const int t = R.turn;
         R.turn = (t + 1) % DspRing::kRing;
-        if (R.done[t]) PTTS_HIP(hipEventSynchronize(R.done[t]));   // the launches that last read this turn's table have run
-        else PTTS_HIP(hipEventCreateWithFlags(&R.done[t], hipEventDisableTiming));
-        DspRow* h = R.host + (size_t)t * kRows;
-        DspRow* d = R.dev.as<DspRow>() + (size_t)t * kRows;
-        std::memcpy(h, rows.data() + at, (size_t)n * sizeof(DspRow));
-        PTTS_HIP(hipMemcpyAsync(d, h, (size_t)n * sizeof(DspRow), hipMemcpyHostToDevice, s));
-        launch_dsp(d, n, (int)max_tiles, any_norm, any_dc, scan, s);
-        PTTS_HIP(hipEventRecord(R.done[t], s));
+        R.ack.wait(t);   // the launches that last read this turn's table have run
+        char* h = R.host + (size_t)t * DspRing::kTurnBytes;
+        char* dt = R.dev.as<char>() + (size_t)t * DspRing::kTurnBytes;
+        std::memcpy(h + RingAck::kHead, rows.data() + at, (size_t)n * sizeof(DspRow));
+        R.ack.upload(t, h, dt, (size_t)n * sizeof(DspRow), s);
+        launch_dsp(reinterpret_cast<const DspRow*>(dt + RingAck::kHead), n, (int)max_tiles, any_norm, any_dc, scan, s, any_loud, &loud, apply);
+        R.ack.done(t, dt, s);
     }
+}
+
+// ptts_loudness_rows / ptts_loudness_normalize_rows: rows packed 256-byte aligned in one device buffer, the launches of a request's `loudness`
+void loudness_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out, double* M,
+                          std::vector<double>* sub) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> off((size_t)rows);
+    size_t bytes = 0;
+    for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
+    char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
+    const double T = out ? loud_target_power(target_lufs) : 1.0;
+    std::vector<DspJob> jobs;
+    std::vector<int> job_row;
+    for (int i = 0; i < rows; i++) {
+        if (M) M[i] = 0.0;
+        if (sub) sub[i].clear();
+        if (n[i] <= 0) continue;
+        PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
+        DspJob j{(float*)(buf + off[(size_t)i]), n[i], nullptr};
+        j.loud = true; j.target_power = T;
+        jobs.push_back(j);
+        job_row.push_back(i);
+    }
+    dsp_launch(m, jobs, s, out != nullptr);
+    for (size_t k = 0; k < jobs.size(); k++) {
+        const int i = job_row[k];
+        const size_t F = (size_t)((n[i] + kDspTile - 1) / kDspTile);
+        if (M) PTTS_HIP(hipMemcpyAsync(M + i, jobs[k].loud_out, sizeof(double), hipMemcpyDeviceToHost, s));
+        if (sub) {
+            sub[i].resize(F * kLoudSubsPerTile);
+            PTTS_HIP(hipMemcpyAsync(sub[i].data(), jobs[k].loud_out + 2 + F * 8, F * kLoudSubsPerTile * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        if (out) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    PTTS_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace ptts

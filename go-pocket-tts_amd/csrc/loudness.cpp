@@ -1,0 +1,143 @@
+// loudness.cpp -- integrated loudness after ITU-R BS.1770-4 (mono, the decoder's 24 kHz) and the gain to a target, on the host: ptts_loudness
+// and ptts_loudness_normalize.  The host function is the blocked evaluation of loudness_block.h itself -- the functions loudness.hip's kernels
+// call, instantiated for the host, in the order the kernels run them -- so a request's `loudness`, ptts_loudness_rows and
+// ptts_loudness_normalize_rows give these bits.  DESIGN.md section 8 (N3).
+#include <cmath>
+
+#include "loudness_block.h"
+#include "runtime.h"
+
+namespace ptts {
+
+namespace {
+// BS.1770's two K-weighting stages re-derived for the sample rate (the standard tabulates them at 48 kHz only): the bilinear forms whose
+// parameters reproduce that table
+DspBiquad k_shelf(double fs) {
+    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    const double K = std::tan(M_PI * f0 / fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+    const double a0 = 1.0 + K / Q + K * K;
+    return DspBiquad{(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0};
+}
+DspBiquad k_highpass(double fs) {
+    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+    const double K = std::tan(M_PI * f0 / fs);
+    const double a0 = 1.0 + K / Q + K * K;
+    return DspBiquad{1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0};
+}
+}  // namespace
+
+void loud_kweight_coeffs(int sample_rate, double out[10]) {
+    const DspBiquad s = k_shelf((double)sample_rate), h = k_highpass((double)sample_rate);
+    const double v[10] = {s.b0, s.b1, s.b2, s.a1, s.a2, h.b0, h.b1, h.b2, h.a1, h.a2};
+    for (int i = 0; i < 10; i++) out[i] = v[i];
+}
+
+// the cascade's state matrix over (shelf z1, shelf z2, high-pass z1, high-pass z2) -- with x = 0: u = z1, y = c0 u + z3 -- and its powers
+// A^kDspRun, A^kDspTile by repeated multiplication
+LoudScan loud_scan_coeffs(int sample_rate) {
+    LoudScan sc;
+    sc.s1 = k_shelf((double)sample_rate);
+    sc.s2 = k_highpass((double)sample_rate);
+    const DspBiquad &a = sc.s1, &b = sc.s2;
+    const double A[16] = {-a.a1, 1.0, 0.0, 0.0,
+                          -a.a2, 0.0, 0.0, 0.0,
+                          b.b1 - b.a1 * b.b0, 0.0, -b.a1, 1.0,
+                          b.b2 - b.a2 * b.b0, 0.0, -b.a2, 0.0};
+    double P[16];
+    for (int i = 0; i < 16; i++) P[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int k = 1; k <= kDspTile; k++) {
+        double Q[16];
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++) {
+                double v = 0.0;
+                for (int m = 0; m < 4; m++) v += A[4 * i + m] * P[4 * m + j];
+                Q[4 * i + j] = v;
+            }
+        for (int j = 0; j < 16; j++) P[j] = Q[j];
+        if (k == kDspRun) for (int j = 0; j < 16; j++) sc.a_run[j] = P[j];
+    }
+    for (int j = 0; j < 16; j++) sc.a_tile[j] = P[j];
+    sc.abs_gate = std::pow(10.0, (-70.0 + 0.691) / 10.0);
+    return sc;
+}
+
+const LoudScan& loud_scan() {
+    static const LoudScan sc = loud_scan_coeffs(kNativeRate);
+    return sc;
+}
+
+double loud_target_power(double target_lufs) { return std::pow(10.0, (target_lufs + 0.691) / 10.0); }
+double loud_lufs(double M) { return M > 0.0 ? -0.691 + 10.0 * std::log10(M) : (std::isnan(M) ? M : -INFINITY); }
+
+std::string loud_target_error(double target_lufs) {
+    if (!(target_lufs >= -70.0 && target_lufs <= -1.0)) return strfmt("loudness: target %g LUFS is outside -70 .. -1", target_lufs);
+    return std::string();
+}
+
+// what k_loud_summary, k_loud_carry and k_loud_energy compute for one row: 4 sub-block energies per tile
+void loud_sub_energies(const float* x, int64_t n, std::vector<double>& sub) {
+    const LoudScan& sc = loud_scan();
+    const int64_t F = (n + kDspTile - 1) / kDspTile;
+    sub.assign((size_t)F * kLoudSubsPerTile, 0.0);
+    double S[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t f = 0; f < F; f++) {
+        const int64_t base = f * kDspTile;
+        const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
+        const float* tile = x + base;
+        double e[kDspLanes][4], q[kDspLanes];
+        for (int l = 0; l < kDspLanes; l++) {
+            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
+            for (int i = 0; i < 4; i++) e[l][i] = 0.0;
+            (void)loud_run(sc, tile + l * kDspRun, c, e[l]);
+        }
+        double E[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {S[0], S[1], S[2], S[3]};
+        for (int l = 0; l < kDspLanes; l++) {
+            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
+            double z[4] = {t[0], t[1], t[2], t[3]};
+            q[l] = loud_run(sc, tile + l * kDspRun, c, z);
+            loud_advance(sc.a_run, t, e[l]);
+            loud_advance(sc.a_run, E, e[l]);
+        }
+        for (int k = 0; k < kLoudSubsPerTile; k++) sub[(size_t)f * kLoudSubsPerTile + (size_t)k] = loud_sub_energy(q + k * kLoudRunsPerSub);
+        loud_advance(sc.a_tile, S, E);
+    }
+}
+
+// what k_loud_gate computes: the doubly gated mean square of the row's whole 400 ms blocks; 0: no block above the gates
+double loud_gated_mean(const double* sub, int64_t n) {
+    const LoudScan& sc = loud_scan();
+    const int64_t nb = loud_blocks(n);
+    LoudAcc first{0.0, 0}, second{0.0, 0};
+    for (int64_t j = 0; j < nb; j++) loud_gate_add(first, loud_block_energy(sub, j), sc.abs_gate, sc.abs_gate);
+    if (!first.cnt) return 0.0;
+    const double rel = loud_rel_gate(first);
+    for (int64_t j = 0; j < nb; j++) loud_gate_add(second, loud_block_energy(sub, j), sc.abs_gate, rel);
+    return second.cnt ? loud_div(second.sum, (double)second.cnt) : 0.0;
+}
+
+double loud_measure(const float* x, int64_t n) {
+    std::vector<double> sub;
+    loud_sub_energies(x, n, sub);
+    return loud_gated_mean(sub.data(), n);
+}
+
+float loud_measure_gain(const float* x, int64_t n, double target_power, double* M_out) {
+    const double M = loud_measure(x, n);
+    if (M_out) *M_out = M;
+    float peak = 0.0f;   // dsp_peak_normalize's: NaNs never win
+    for (int64_t i = 0; i < n; i++) {
+        const float a = (float)std::fabs((double)x[i]);
+        if (a > peak) peak = a;
+    }
+    return loud_gain(M, target_power, peak);
+}
+
+double loud_normalize(float* x, int64_t n, double target_lufs) {
+    double M = 0.0;
+    const float g = loud_measure_gain(x, n, loud_target_power(target_lufs), &M);
+    if (g != 1.0f)
+        for (int64_t i = 0; i < n; i++) x[i] = x[i] * g;
+    return M;
+}
+
+}  // namespace ptts

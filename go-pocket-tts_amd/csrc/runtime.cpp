@@ -1395,12 +1395,15 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
     const int64_t n = (int64_t)g.size();
     const int16_t* pcm16 = nullptr;   // PCM16 egress on the device (audio/wav_stream.go:43-54), converted for the whole group at the first request that asks for it
     std::vector<int64_t> conv;        // rows at another rate or in G.711: one k_resample launch for all of them
-    if (!stored) {   // post-processing (ptts_request.dsp): every such row of the group at once, in place in the decoder's buffer, in front of the egress
+    if (!stored) {   // post-processing (ptts_request.dsp, .loudness): every such row of the group at once, in place in the decoder's buffer, in front of the egress
         std::vector<DspJob> jobs;
         for (int64_t i = 0; i < n; i++) {
             const Delivery& u = g[(size_t)i];
-            if (u.res && !u.filled && u.nf > 0 && dsp_active(u.req->dsp) && result_buffer(*u.res, u.req->pcm_format))
-                jobs.push_back(DspJob{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, u.req->dsp});
+            if (u.res && !u.filled && u.nf > 0 && (dsp_active(u.req->dsp) || u.req->loudness) && result_buffer(*u.res, u.req->pcm_format)) {
+                DspJob j{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, u.req->dsp};
+                if (u.req->loudness) { j.loud = true; j.target_power = loud_target_power((double)u.req->loudness / 100.0); }
+                jobs.push_back(j);
+            }
         }
         if (!jobs.empty()) dsp_launch(m, jobs, s);
     }
@@ -1926,6 +1929,11 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
             const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : nullptr;
             if (f) return strfmt("generate: dsp: %s cannot be combined with pcm_callback", f);
         }
+    }
+    if (q.loudness) {   // 0.01 LUFS; one gain slot with normalise; not known when a stream's samples are handed over
+        if (q.loudness < -7000 || q.loudness > -100) return strfmt("generate: loudness %d is not 0 (off) or a target from -7000 to -100 (0.01 LUFS)", q.loudness);
+        if (q.dsp && q.dsp->normalize) return "generate: loudness cannot be combined with dsp normalize (one gain)";
+        if (q.pcm_callback) return "generate: loudness cannot be combined with pcm_callback";
     }
     for (int64_t t = 0; t < q.n_tokens; t++)
         if (q.tokens[t] < 0 || q.tokens[t] >= d.n_bins)

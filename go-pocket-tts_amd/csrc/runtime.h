@@ -54,12 +54,31 @@ struct RateFilter {
     RateFilter& operator=(const RateFilter&) = delete;
     ~RateFilter();
 };
+// When a turn of a row-table ring may be reused, without an event: a turn's upload carries a sequence number in front of its rows, a small
+// copy queued behind the turn's launches hands the number back into page-locked memory, and the host waits for it there.  (The rings waited
+// on lazily created events with hipEventSynchronize before; that call was seen to fail now and then with a stream-capture error -- "stream is
+// capturing", "event last recorded in a capturing stream" -- on events that were never recorded into a capture.  This wait has no such state.)
+struct RingAck {
+    static constexpr int kRing = 8, kHead = 16;   // bytes in front of a turn's rows: the number, padded so that the rows stay 16-byte aligned
+    uint64_t* back = nullptr;                     // page-locked [kRing]: what turn t last handed back
+    uint64_t expect[kRing] = {};                  // ... and what its last launches will hand back (0: never used)
+    uint64_t seq = 0;
+    RingAck() = default;
+    RingAck(const RingAck&) = delete;
+    RingAck& operator=(const RingAck&) = delete;
+    ~RingAck();
+    void wait(int t);                                             // until turn t's last launches have run (throws PTTS_ENODEVICE after 60 s)
+    // host_turn / dev_turn: the turn's blocks of kHead + row_bytes bytes; stamps the number, queues the upload of head and rows on s
+    void upload(int t, char* host_turn, char* dev_turn, size_t row_bytes, hipStream_t s);
+    void done(int t, const char* dev_turn, hipStream_t s);        // behind the turn's launches on s
+};
 // page-locked staging and device copies of k_resample's row tables: kRing turns of kRows rows, a turn reused once its launch has run
 struct ResampleRing {
-    static constexpr int kRing = 8, kRows = 256;
-    ResampleRow* host = nullptr;
+    static constexpr int kRing = RingAck::kRing, kRows = 256;
+    static constexpr size_t kTurnBytes = RingAck::kHead + sizeof(ResampleRow) * kRows;
+    char* host = nullptr;
     DevBuf dev;
-    hipEvent_t done[kRing] = {};
+    RingAck ack;
     int turn = 0;
     ResampleRing() = default;
     ResampleRing(const ResampleRing&) = delete;
@@ -69,10 +88,11 @@ struct ResampleRing {
 
 // page-locked staging and device copies of the DSP kernels' row tables (dsp_device.cpp), as ResampleRing
 struct DspRing {
-    static constexpr int kRing = 8, kRows = 256;
-    DspRow* host = nullptr;
+    static constexpr int kRing = RingAck::kRing, kRows = 256;
+    static constexpr size_t kTurnBytes = RingAck::kHead + sizeof(DspRow) * kRows;
+    char* host = nullptr;
     DevBuf dev;
-    hipEvent_t done[kRing] = {};
+    RingAck ack;
     int turn = 0;
     DspRing() = default;
     DspRing(const DspRing&) = delete;
@@ -345,10 +365,14 @@ inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample
 // (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
 inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0); }
 std::string dsp_opts_error(const ptts_dsp_opts& o);
-struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; };
-void dsp_launch(Model& m, const std::vector<DspJob>& jobs, hipStream_t s);
+// loud: the row is measured (BS.1770, loudness.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
+// dsp_launch sets loud_out to the row's two device words (the mean square M as a double, then the f32 gain), valid until the model's next
+// DSP launch.  opts may be NULL for a loudness row.
+struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; };
+// apply false: loudness rows are measured only (M and the sub-block energies), no sample is rewritten
+void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
 inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)
-    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || dsp_active(r.dsp);
+    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || dsp_active(r.dsp) || r.loudness != 0;
 }
 inline size_t pcm_bytes(int fmt) { return fmt == PTTS_PCM_F32 ? 4 : fmt == PTTS_PCM_S16 ? 2 : 1; }
 inline void* result_buffer(const ptts_result& r, int fmt) {
@@ -421,6 +445,24 @@ void dsp_fade_out(float* s, int64_t n, int sample_rate, double ms);
 struct DspScan;
 DspScan dsp_scan_coeffs(int sample_rate);                          // the DC block's section and the powers of its state matrix (dsp_block.h)
 void dsp_dc_block_blocked(float* s, int64_t n, int sample_rate);   // dsp_dc_block in the device's blocked form, on the host
+
+// integrated loudness, ITU-R BS.1770-4 mono at 24 kHz (loudness.cpp; loudness_block.h is the arithmetic, shared with loudness.hip)
+struct LoudScan;
+void loud_kweight_coeffs(int sample_rate, double out[10]);         // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
+LoudScan loud_scan_coeffs(int sample_rate);
+const LoudScan& loud_scan();                                       // at kNativeRate
+double loud_target_power(double target_lufs);                      // 10^((target + 0.691) / 10)
+double loud_lufs(double M);                                        // -0.691 + 10 log10(M); -inf for M == 0
+std::string loud_target_error(double target_lufs);                 // empty: -70 <= target <= -1
+void loud_sub_energies(const float* x, int64_t n, std::vector<double>& sub);   // [4 ceil(n / 1920)]: 480-sample energies, blocked form
+double loud_gated_mean(const double* sub, int64_t n);              // the doubly gated mean square M (0: nothing above the gates)
+double loud_measure(const float* x, int64_t n);                    // M of a row
+float loud_measure_gain(const float* x, int64_t n, double target_power, double* M_out);   // min((float)sqrt(T / M), 1 / peak), or 1
+double loud_normalize(float* x, int64_t n, double target_lufs);    // in place; returns M as measured before
+// the device form on host rows (dsp_device.cpp): upload, the launches of a request's `loudness`, download.  out NULL: measurement only.
+// M (optional) [rows]; sub (optional): per row its [4 ceil(n / 1920)] sub-block energies as the device computed them
+void loudness_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out, double* M,
+                          std::vector<double>* sub);
 
 // the weight broadcast of a multi-GPU start-up (broadcast.cpp)
 void rccl_unique_id(uint8_t out[128]);

@@ -66,7 +66,7 @@ class _Request(C.Structure):
                 ("frames_after_eos", C.c_int32), ("voice_embedding", _FP), ("voice_frames", C.c_int64),
                 ("voice_caches", C.POINTER(_FP)), ("voice_cache_steps", _IP), ("voice_offsets", _IP), ("noise", _FP),
                 ("step_callback", _STEP_CB), ("callback_user", C.c_void_p), ("cancel", C.POINTER(C.c_int32)),
-                ("want_latents", C.c_int32), ("pcm_format", C.c_int32), ("voice", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_rows", C.c_int32), ("reserved", C.c_int32 * 1),
+                ("want_latents", C.c_int32), ("pcm_format", C.c_int32), ("voice", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_rows", C.c_int32), ("loudness", C.c_int32),
                 ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p), ("stream_frames", C.c_int32), ("sample_rate", C.c_int32), ("dsp", C.POINTER(DspOpts))]
 
 
@@ -112,13 +112,14 @@ ABI_SYMBOLS = [
     "ptts_voice_from_embeddings", "ptts_voice_from_audio", "ptts_voice_offset", "ptts_voice_read_state", "ptts_voice_write", "ptts_voice_write_bytes",
     "ptts_voice_state_write_bytes", "ptts_voice_embedding_write", "ptts_free_bytes",
     "ptts_resample_length", "ptts_resample", "ptts_pcm_encode", "ptts_mimi_encode_rates", "ptts_voice_from_audio_rates", "ptts_wav_header",
-    "ptts_dsp_rows",
+    "ptts_dsp_rows", "ptts_loudness", "ptts_loudness_normalize", "ptts_loudness_rows", "ptts_loudness_normalize_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
+    "ptts_debug_loudness_energies", "ptts_debug_kweighting",
 ]
 
 
@@ -311,6 +312,9 @@ class RuntimeGenerateConfig:
     fade_in_ms: float = 0.0
     fade_out_ms: float = 0.0
     dsp_opts: Optional[DspOpts] = None   # a ptts_dsp_opts handed over as it is (takes precedence; an all-off struct is a valid request)
+    # loudness normalisation on the device (ptts_request.loudness): 0 off, else the BS.1770 target in 0.01 LUFS (-2300: EBU R 128, -1600: streaming);
+    # the result is loudness_normalize(this request's own 24 kHz audio, loudness / 100), then the switches above, then the egress
+    loudness: int = 0
 
 
 def _free_addr(addr: int):
@@ -611,6 +615,37 @@ class Model:
         _check(L.ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), po))
         return outs[0] if single else outs
 
+    def _loudness_rows(self, x, target):
+        single = not isinstance(x, (list, tuple))
+        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+        n = len(rows)
+        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+        ns = np.array([r.size for r in rows] or [0], np.int64)
+        lufs = np.zeros(max(n, 1), np.float64)
+        dp = lufs.ctypes.data_as(C.POINTER(C.c_double))
+        L = lib()
+        if target is None:
+            L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(C.c_double)]
+            _check(L.ptts_loudness_rows(self.h, pp, _ip(ns), n, dp))
+            return float(lufs[0]) if single else lufs[:n]
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
+        L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), C.POINTER(C.c_double)]
+        _check(L.ptts_loudness_normalize_rows(self.h, pp, _ip(ns), n, float(target), po, dp))
+        return (outs[0], float(lufs[0])) if single else (outs, lufs[:n])
+
+    def loudness_rows(self, x):
+        """ptts_loudness_rows: BS.1770-4 integrated loudness (LUFS, -inf: nothing above the gates) of mono f32 rows at 24 kHz, measured on the device."""
+        return self._loudness_rows(x, None)
+
+    def loudness_normalize_rows(self, x, target_lufs: float):
+        """ptts_loudness_normalize_rows: (rows at the target -- never above peak 1 --, the loudness measured before), on the device."""
+        return self._loudness_rows(x, float(target_lufs))
+
+    def loudness_energies(self, x):
+        """Test hook (libptts_hooks.so ptts_debug_loudness_energies): the rows' 480-sample K-weighted energies as the device kernels compute them."""
+        return loudness_energies(x, self)
+
     def pcm_encode(self, x, pcm_format: int) -> np.ndarray:
         """ptts_pcm_encode: the device egress conversion of 24 kHz f32 samples into PCM_F32 / PCM_S16 / PCM_ULAW / PCM_ALAW."""
         x = _f32(x).reshape(-1)
@@ -694,6 +729,7 @@ class Model:
         if dsp is not None:
             keep.append(dsp)
             r.dsp = C.pointer(dsp)
+        r.loudness = int(getattr(cfg, "loudness", 0))
         if cfg.pcm_callback is not None:
             dt = np.dtype(_PCM_DTYPES.get(r.pcm_format, "<f4"))
 
@@ -1281,6 +1317,52 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
     if not (nz or dc or fi != 0.0 or fo != 0.0):
         return None
     return DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
+
+
+def loudness(samples) -> float:
+    """ptts_loudness: integrated loudness after ITU-R BS.1770-4 of mono f32 samples at 24 kHz, in LUFS (-inf: nothing above the gates).  Host code."""
+    x = _f32(samples).reshape(-1)
+    out = C.c_double(0.0)
+    L = lib()
+    L.ptts_loudness.argtypes = [_FP, C.c_int64, C.POINTER(C.c_double)]
+    _check(L.ptts_loudness(_fp(x), x.size, C.byref(out)))
+    return float(out.value)
+
+
+def loudness_normalize(samples, target_lufs: float):
+    """ptts_loudness_normalize: (a new array at the target -- never above peak 1 --, the loudness measured before).  Host code."""
+    x = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    out = C.c_double(0.0)
+    L = lib()
+    L.ptts_loudness_normalize.argtypes = [_FP, C.c_int64, C.c_double, C.POINTER(C.c_double)]
+    _check(L.ptts_loudness_normalize(_fp(x), x.size, float(target_lufs), C.byref(out)))
+    return x, float(out.value)
+
+
+def loudness_energies(x, model=None):
+    """Test hook (libptts_hooks.so ptts_debug_loudness_energies): the sums of squares of the K-weighted samples over each whole 480-sample sub-block
+    of mono f32 rows at 24 kHz -- by the device kernels with a model, by the host instantiation of their functions without."""
+    single = not isinstance(x, (list, tuple))
+    rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+    n = len(rows)
+    outs = [np.zeros(r.size // 480, np.float64) for r in rows]
+    DP = C.POINTER(C.c_double)
+    pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+    po = (DP * max(n, 1))(*[o.ctypes.data_as(DP) for o in outs])
+    ns = np.array([r.size for r in rows] or [0], np.int64)
+    H = hooks()
+    H.ptts_debug_loudness_energies.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DP)]
+    _check(H.ptts_debug_loudness_energies(model.h if model is not None else None, pp, _ip(ns), n, po))
+    return outs[0] if single else outs
+
+
+def kweighting(sample_rate: int) -> np.ndarray:
+    """Test hook (ptts_debug_kweighting): the K-weighting sections for a sample rate, [shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2]."""
+    out = np.zeros(10, np.float64)
+    H = hooks()
+    H.ptts_debug_kweighting.argtypes = [C.c_int32, C.POINTER(C.c_double)]
+    _check(H.ptts_debug_kweighting(int(sample_rate), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
 
 
 def dsp_blocked_host(samples) -> np.ndarray:

@@ -163,7 +163,14 @@ typedef struct ptts_request {
     uint64_t noise_seed;                              /* device draw: the stream of this request; 0 = a fresh one per request from the model's
                                                        * own generator, seeded with the clock at open like the reference's (runtime_native_safetensors.go:27-32) */
     int32_t noise_rows;                               /* rows behind `noise`; must cover the resolved step budget (0: not checked, the caller vouches) */
-    int32_t reserved[1];
+    /* Loudness normalisation on the device: 0 off; otherwise the target integrated loudness in units of 0.01 LUFS,
+     * -7000 .. -100 (-2300: EBU R 128, -1600: streaming, IVR).  The request's result is what
+     *     ptts_loudness_normalize(samples, n, loudness / 100.0, NULL)
+     * makes of THAT REQUEST'S OWN 24 kHz f32 audio, bit for bit, THEN `dsp` (the gain sits where normalise's gain sits: the DC block reads
+     * x * gain, the fades follow), THEN the egress.  Loudness is measured on the raw decoded audio, so the final audio is at the target up to
+     * what the DC block and the fades remove.  PTTS_EINVAL naming the field for another value, together with dsp->normalize (one gain slot),
+     * and together with pcm_callback (the loudness is not known when samples are handed over). */
+    int32_t loudness;
     /* Frame-granular streaming (the /tts/stream path, server.go:354-396, at finer grain than the reference's per-chunk
      * PCMChunk): finished frame ranges are decoded while the AR loop is still running and handed over in order, each sample
      * exactly once, from a library thread; `samples` points into the buffer the result will own (float or int16 per
@@ -227,6 +234,29 @@ int  ptts_dsp_apply(float* samples, int64_t n, int32_t normalize, int32_t dc_blo
  * >= 0), one launch sequence for all rows, out[i] (host, n[i] floats; in[i] == out[i] allowed) receives the result.  opts NULL or with
  * nothing switched on copies.  PTTS_EINVAL as for ptts_request.dsp. */
 int  ptts_dsp_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts, float* const* out);
+
+/* Integrated loudness after ITU-R BS.1770-4, mono, at 24 kHz, and normalisation to a target.  float64 throughout:
+ * the K-weighting (high shelf, high-pass; the bilinear forms that reproduce the standard's 48 kHz table, evaluated for 24 kHz) as a cascade of
+ * two direct form II transposed sections, 400 ms blocks every 100 ms (whole blocks only: block j is samples [2400 j, 2400 j + 9600)), the
+ * absolute gate at -70 LUFS and the relative gate 10 LU under the mean of the absolutely gated blocks, both applied to the mean squares;
+ * LUFS = -0.691 + 10 log10(mean of the gated blocks).  The recurrence is evaluated in the blocked form of the device kernels, with every
+ * summation order fixed, so the host functions and the device forms (ptts_request.loudness, ptts_loudness_rows,
+ * ptts_loudness_normalize_rows) give the same bits.
+ * ptts_loudness: *lufs receives the loudness, -INFINITY when no block passes the gates (fewer than 9600 samples, silence, below -70 LUFS).
+ * ptts_loudness_normalize, in place: samples *= gain with gain = min((float)sqrt(T / M), 1.0f / peak) -- T = 10^((target + 0.691) / 10), M the
+ * gated mean square, peak the sample peak of ptts_dsp_apply's normalise -- one f32 product per sample; the ceiling means the result never
+ * clips and may stay under the target (no true-peak limiting).  The gain stays 1 (samples untouched) when no block passes the gates or M is
+ * not finite.  *measured (optional) receives the loudness before the gain.  target_lufs: -70 .. -1, else PTTS_EINVAL.
+ * Non-finite samples are not treated specially, as in normalise: a NaN never wins the peak and a block whose energy is NaN fails both gates
+ * (every comparison with it is false); an infinite sample makes the peak infinite and the ceiling 0. */
+int  ptts_loudness(const float* samples, int64_t n, double* lufs);
+int  ptts_loudness_normalize(float* samples, int64_t n, double target_lufs, double* measured);
+/* The same on the device, by the kernels a request's `loudness` runs, shaped like ptts_dsp_rows: rows of host samples at 24 kHz (in[i]: n[i]
+ * floats, any length >= 0), one launch sequence for all rows.  lufs / measured: [rows] (measured optional); out[i]: n[i] floats, in[i] == out[i]
+ * allowed.  A host that wants one loudness over a text's chunks calls these on the concatenation. */
+int  ptts_loudness_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double* lufs);
+int  ptts_loudness_normalize_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out,
+                                  double* measured);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -473,7 +503,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
 /* build/version string, e.g. "ptts-hip 0.3 gfx950".  0.3: ptts_request.sample_rate, PTTS_PCM_ULAW / PTTS_PCM_ALAW with ptts_result.pcm8
  * (in the place of reserved fields: the struct sizes are those of 0.2), ptts_resample_length, ptts_resample, ptts_pcm_encode,
  * ptts_mimi_encode_rates, ptts_voice_from_audio_rates, ptts_wav_header.  Later additions keep the number (hosts test for the symbol):
- * ptts_request.dsp (in the place of reserved2: the struct's size and every other offset are unchanged) with ptts_dsp_opts, and ptts_dsp_rows */
+ * ptts_request.dsp (in the place of reserved2: the struct's size and every other offset are unchanged) with ptts_dsp_opts, and ptts_dsp_rows;
+ * ptts_request.loudness (in the place of reserved[1], likewise), ptts_loudness, ptts_loudness_normalize, ptts_loudness_rows,
+ * ptts_loudness_normalize_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of

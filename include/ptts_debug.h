@@ -72,6 +72,13 @@ int64_t ptts_debug_resample_launches(int32_t reset);
  * functions the kernels call: n samples at 24 kHz, in -> out (in == out allowed).  No GPU. */
 int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out);
 
+/* Loudness (ptts_loudness; csrc/loudness_block.h): the energies of the rows' whole 480-sample sub-blocks -- out[i] receives n[i] / 480 doubles, the
+ * sums of squares of the K-weighted samples -- as the device kernels of a request's `loudness` compute them (m != NULL), or by the host
+ * instantiation of the functions those kernels call (m == NULL, no GPU).  Twenty of them in order, over 9600, are one 400 ms block. */
+int ptts_debug_loudness_energies(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double* const* out);
+/* The K-weighting sections as ptts_loudness derives them for a sample rate: shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2.  No GPU. */
+int ptts_debug_kweighting(int32_t sample_rate, double out[10]);
+
 /* Test hook for the bounded hand-offs of k_flow_cluster (csrc/flow_cluster.hip): the model's NEXT plain-launched AR step runs the flow net's residual
  * blocks with one workgroup withholding what it should publish for block `block` (1-based; 0 clears).  Its peers' sweeps give up after their bound, the
  * launch runs to its end, and the call that contained the step fails with PTTS_ENODEVICE ("hand-off timed out"); the exchange state is cleared, the next
