@@ -364,6 +364,110 @@ int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t
     });
 }
 
+// The step linear (csrc/skinny.hip) on host operands: every operand is uploaded, every output buffer is pre-filled with 0xff bytes (NaN where the
+// kernel stores nothing) and comes back whole.  The weights go through the loader's own packers (model.h).
+int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_step_linear: null argument");
+        const ptts_step_linear_args& t = *pa;
+        if (!t.x || !t.W || !t.C || t.M <= 0 || t.N <= 0 || t.K <= 0 || t.lda < t.K || t.ldc < t.N || t.wfmt < 0 || t.wfmt > 2 || t.epi < EPI_NONE || t.epi > EPI_RESADD_ELU ||
+            t.splitk < 1 || t.splitk > 64 || t.psplit < 0 || (t.path != 0 && t.path != 1) || (t.zrows != 0 && t.zrows < t.M))
+            throw Error(PTTS_EINVAL, "ptts_debug_step_linear: bad arguments");
+        const int M = t.M, N = t.N, K = t.K, S = t.splitk;
+        const bool fused = t.ln || t.planes || t.shift || t.mscale || t.ln_w || t.ln_b || t.pgate;
+        if ((t.epi >= EPI_RESADD && !t.R) || (t.epi == EPI_SCALE_RESADD && !t.scale) || (t.epi == EPI_GATE_RESADD && (!t.gate || t.ldg < N)) || (t.tail && !t.tail_out) ||
+            (t.planes && t.psplit < 1) || ((t.shift || t.mscale) && t.ldmod < K) || (fused && S > 1) || (t.tail && S > 1) || (t.path == 1 && (fused || S > 1)) ||
+            (t.wfmt == 2 && (!t.w_eff || !t.w_scale)))
+            throw Error(PTTS_EINVAL, "ptts_debug_step_linear: operands do not fit the form asked for");
+        const size_t nk = (size_t)N * K, mk = (size_t)M * K;
+        // weights: the loader's packers
+        std::vector<float> rm(t.W, t.W + nk), wscale;
+        std::vector<uint8_t> wt(step_tiled_bytes((size_t)N, (size_t)K, t.wfmt == 2 ? 1 : (t.wfmt == 1 ? 2 : 4)));
+        std::vector<uint16_t> rm16;
+        if (t.wfmt == 2) {
+            std::vector<int8_t> q;
+            quantize_rows(rm, (size_t)N, (size_t)K, wscale, q);   // rm -> W^
+            pack_step_tiled_i8(q.data(), (size_t)N, (size_t)K, wt.data());
+            std::memcpy(t.w_eff, rm.data(), nk * 4);
+            std::memcpy(t.w_scale, wscale.data(), (size_t)N * 4);
+        } else {
+            pack_step_tiled(rm.data(), (size_t)N, (size_t)K, t.wfmt == 1, wt.data());
+            if (t.wfmt == 1) { rm16.resize(nk); for (size_t i = 0; i < nk; i++) rm16[i] = f32_to_bf16_rne(rm[i]); }
+        }
+        require_device();
+        const int64_t zrows = t.zrows ? t.zrows : M;
+        const size_t c_bytes = (size_t)M * t.ldc * 4, p_bytes = (size_t)S * zrows * N * 4, mod_bytes = (size_t)M * std::max(t.ldmod, 1) * 4;
+        Tmp dX((size_t)M * t.lda * 4), dW(nk * 4), dWt(wt.size()), dWs((size_t)N * 4), dB((size_t)N * 4), dAv((size_t)N * 4), dSc((size_t)N * 4), dR(c_bytes), dG((size_t)M * std::max(t.ldg, 1) * 4),
+            dC(c_bytes), dPart(p_bytes), dTail((size_t)M * 4), dLw((size_t)K * 4), dLb((size_t)K * 4), dSh(mod_bytes), dMs(mod_bytes), dPl((size_t)std::max(t.psplit, 1) * mk * 4), dPb((size_t)K * 4),
+            dXo(mk * 4), dYo(mk * 4);
+        up(dX.p, t.x, (size_t)M * t.lda * 4);
+        if (t.wfmt == 1) up(dW.p, rm16.data(), nk * 2); else up(dW.p, rm.data(), nk * 4);
+        up(dWt.p, wt.data(), wt.size());
+        PTTS_HIP(hipMemset(dC.p, 0xff, c_bytes)); PTTS_HIP(hipMemset(dPart.p, 0xff, p_bytes)); PTTS_HIP(hipMemset(dTail.p, 0xff, (size_t)M * 4));
+        PTTS_HIP(hipMemset(dXo.p, 0xff, mk * 4)); PTTS_HIP(hipMemset(dYo.p, 0xff, mk * 4));
+        GemmArgs g;
+        g.A = dX.as<float>(); g.amap = RowMap{t.lda, 0, 0};
+        g.W = dW.p; g.w_bf16 = t.wfmt == 1; g.ldw = K; g.Wt = dWt.p;
+        if (t.wfmt == 2) { up(dWs.p, wscale.data(), (size_t)N * 4); g.wt_i8 = 1; g.wscale = dWs.as<float>(); }
+        if (t.bias) { up(dB.p, t.bias, (size_t)N * 4); g.bias = dB.as<float>(); }
+        if (t.addvec) { up(dAv.p, t.addvec, (size_t)(t.tail ? N - 1 : N) * 4); g.addvec = dAv.as<float>(); }
+        if (t.scale) { up(dSc.p, t.scale, (size_t)N * 4); g.scale = dSc.as<float>(); }
+        if (t.gate) { up(dG.p, t.gate, (size_t)M * t.ldg * 4); g.gate = dG.as<float>(); g.ldg = t.ldg; }
+        g.C = dC.as<float>(); g.cmap = RowMap{t.ldc, 0, 0};
+        if (t.R) {   // r_in_c: the in-place residual (R is C: every element read and written by the same lane)
+            up(t.r_in_c ? dC.p : dR.p, t.R, c_bytes);
+            g.R = t.r_in_c ? dC.as<float>() : dR.as<float>();
+        }
+        g.alpha = t.alpha; g.epi = t.epi;
+        if (t.tail) g.tail = dTail.as<float>();
+        if (t.zrows) g.zstride = zrows * N;
+        g.M = M; g.N = N; g.K = K;
+        SkinnyFuse fu;
+        if (fused) {
+            fu.ln = t.ln; fu.eps = t.eps;
+            if (t.ln_w) { up(dLw.p, t.ln_w, (size_t)K * 4); fu.ln_w = dLw.as<float>(); }
+            if (t.ln_b) { up(dLb.p, t.ln_b, (size_t)K * 4); fu.ln_b = dLb.as<float>(); }
+            if (t.shift) { up(dSh.p, t.shift, mod_bytes); fu.shift = dSh.as<float>(); }
+            if (t.mscale) { up(dMs.p, t.mscale, mod_bytes); fu.scale = dMs.as<float>(); }
+            fu.ldmod = t.ldmod;
+            if (t.planes) {
+                up(dPl.p, t.planes, (size_t)t.psplit * mk * 4);
+                fu.partial = dPl.as<float>(); fu.psplit = t.psplit; fu.pstride = (int64_t)mk;
+                if (t.pbias) { up(dPb.p, t.pbias, (size_t)K * 4); fu.pbias = dPb.as<float>(); }
+            }
+            if (t.pgate) { fu.pgate = dXo.as<float>(); fu.ldpg = 1; }   // (never launched: the step kernel takes no gated pending sum)
+            fu.x_out = dXo.as<float>(); fu.y_out = dYo.as<float>();
+        }
+        // refused before any launch: whatever the predicates of the kernel refuse
+        if (t.path == 0) {
+            if (!(fused ? skinny_fuse_supported(g, fu) : skinny_supported(g, S))) throw Error(PTTS_EINVAL, "ptts_debug_step_linear: not taken by the step kernel (skinny_supported / skinny_fuse_supported)");
+        } else {
+            GemmArgs c = g;
+            c.M = std::min(M, 64);
+            if (M > kSkinnyChunkRows || (M > 64 && t.tail) || !skinny_supported(c, 1)) throw Error(PTTS_EINVAL, "ptts_debug_step_linear: launch_gemm would not hand this product to the step kernel");
+        }
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        g_launch_census = &census;
+        try {
+            if (t.path == 0) launch_skinny(g, fu, S, dPart.as<float>(), nullptr);
+            else launch_gemm(g, nullptr);
+        } catch (...) { g_launch_census = census_before; throw; }
+        g_launch_census = census_before;
+        PTTS_HIP(hipDeviceSynchronize());
+        if (t.launches) {
+            t.launches[0] = (int32_t)census["k_skinny"];
+            int64_t all = 0;
+            for (const auto& kv : census) all += kv.second;
+            t.launches[1] = (int32_t)all;
+        }
+        down(t.C, S > 1 ? dPart.p : dC.p, S > 1 ? p_bytes : c_bytes);
+        if (t.tail_out) down(t.tail_out, dTail.p, (size_t)M * 4);
+        if (t.x_out) down(t.x_out, dXo.p, mk * 4);
+        if (t.y_out) down(t.y_out, dYo.p, mk * 4);
+    });
+}
+
 int ptts_mimi_layer_piece(ptts_model* h, int32_t layer, int32_t which, const float* x, int64_t rows, int32_t pos0, int32_t rows_per_seg, float* out) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");

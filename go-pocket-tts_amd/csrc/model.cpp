@@ -9,6 +9,62 @@
 #include "model.h"
 
 namespace ptts {
+
+// ---- the step kernels' weight formats (declared in model.h: the loader below and the step-linear test hook pack with the same code) ----
+// Row n of W becomes q[n][k] in [-127, 127] and a scale s[n] = max_k |W[n][k]| / 127 (1 for an all-zero row);
+// q = rint(W / s) (ties to even), the effective weight is W^ = q * s, which replaces rm.
+void quantize_rows(std::vector<float>& rm, size_t out, size_t in, std::vector<float>& scale, std::vector<int8_t>& q) {
+    scale.assign(out, 1.0f);
+    q.assign(out * in, 0);
+    for (size_t n = 0; n < out; n++) {
+        float mx = 0.0f;
+        for (size_t k = 0; k < in; k++) mx = std::max(mx, std::fabs(rm[n * in + k]));
+        const float s = mx > 0.0f ? mx / 127.0f : 1.0f;
+        scale[n] = s;
+        for (size_t k = 0; k < in; k++) {
+            float v = std::nearbyint(rm[n * in + k] / s);
+            v = std::min(127.0f, std::max(-127.0f, v));
+            q[n * in + k] = (int8_t)v;
+            rm[n * in + k] = v * s;
+        }
+    }
+}
+size_t step_tiled_bytes(size_t out, size_t in, int bytes_per_weight) {
+    return ((out + 15) / 16) * ((in + 127) / 128) * 16 * 128 * (size_t)bytes_per_weight;
+}
+// Fragment-ordered copy for the AR-step kernel: per (16-row tile, 128-deep super-step) one block of WV KiB in which
+// MFMA step s of lane l reads 16 contiguous bytes at [s][l]: W[tile*16 + (l & 15)][ss*128 + (l >> 4)*32 + s*E .. +E),
+// E = 8 (bf16) or 4 (f32).  Every wave-level weight load of the step is then one contiguous 1-KiB burst.
+void pack_step_tiled(const float* rm, size_t out, size_t in, bool bf16w, uint8_t* dst) {
+    const int E = bf16w ? 8 : 4, WV = bf16w ? 4 : 8;
+    const size_t nt = (out + 15) / 16, nss = (in + 127) / 128;
+    for (size_t t = 0; t < nt; t++)
+        for (size_t ss = 0; ss < nss; ss++)
+            for (int sidx = 0; sidx < WV; sidx++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int j = 0; j < E; j++) {
+                        size_t n = t * 16 + (size_t)(lane & 15), k = ss * 128 + (size_t)(lane >> 4) * 32 + (size_t)sidx * E + j;
+                        float v = (n < out && k < in) ? rm[n * in + k] : 0.0f;
+                        size_t e = ((((t * nss + ss) * WV + sidx) * 64 + lane) * E + j);
+                        if (bf16w) reinterpret_cast<uint16_t*>(dst)[e] = f32_to_bf16_rne(v);
+                        else reinterpret_cast<float*>(dst)[e] = v;
+                    }
+}
+// tiled int8 copy of quantize_rows' q.  Layout: per (16-row tile, 128-deep super-step) 2 KiB:
+// load u (0, 1) of lane l is 16 bytes = MFMA steps 2u and 2u + 1, byte j -> k = ss*128 + (l >> 4)*32 + (2u + j/8)*8 + j%8
+void pack_step_tiled_i8(const int8_t* q, size_t out, size_t in, uint8_t* dst) {
+    const size_t nt = (out + 15) / 16, nss = (in + 127) / 128;
+    for (size_t t = 0; t < nt; t++)
+        for (size_t ss = 0; ss < nss; ss++)
+            for (int u = 0; u < 2; u++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int j = 0; j < 16; j++) {
+                        const size_t n = t * 16 + (size_t)(lane & 15), k = ss * 128 + (size_t)(lane >> 4) * 32 + (size_t)(2 * u + j / 8) * 8 + (size_t)(j % 8);
+                        const int v = (n < out && k < in) ? q[n * in + k] : 0;
+                        dst[((((t * nss + ss) * 2 + u) * 64 + lane) * 16) + j] = (uint8_t)(v + 128);
+                    }
+}
+
 namespace {
 
 struct Walker {
@@ -56,36 +112,13 @@ struct Walker {
         if (shape(n).size() != rank) throw Error(PTTS_EFORMAT, strfmt("native: tensor \"%s\" rank %zu, want %zu", n.c_str(), shape(n).size(), rank));
     }
 
-    // Fragment-ordered copy for the AR-step kernel: per (16-row tile, 128-deep super-step) one block of WV KiB in which
-    // MFMA step s of lane l reads 16 contiguous bytes at [s][l]: W[tile*16 + (l & 15)][ss*128 + (l >> 4)*32 + s*E .. +E),
-    // E = 8 (bf16) or 4 (f32).  Every wave-level weight load of the step is then one contiguous 1-KiB burst.
     // ---- PTTS_WEIGHTS_INT8: weight-only int8 for the matrices the AR step streams ----
-    // Row n of W becomes q[n][k] in [-127, 127] and a scale s[n] = max_k |W[n][k]| / 127 (1 for an all-zero row);
-    // q = rint(W / s) (ties to even), the effective weight is W^ = q * s.  The step kernel streams q (1 byte per weight, stored
-    // offset-binary q + 128, in its fragment order) and multiplies by s[n] in the epilogue; everything else that touches the
-    // matrix (prefill GEMMs, the 32-wide linears of k_step_begin) reads a row-major f32 copy of W^, so that the whole
-    // model computes with ONE set of weights -- the ones an f32 oracle is given in the parity tests.
-    static void quantize_rows(std::vector<float>& rm, size_t out, size_t in, std::vector<float>& scale, std::vector<int8_t>& q) {
-        scale.assign(out, 1.0f);
-        q.assign(out * in, 0);
-        for (size_t n = 0; n < out; n++) {
-            float mx = 0.0f;
-            for (size_t k = 0; k < in; k++) mx = std::max(mx, std::fabs(rm[n * in + k]));
-            const float s = mx > 0.0f ? mx / 127.0f : 1.0f;
-            scale[n] = s;
-            for (size_t k = 0; k < in; k++) {
-                float v = std::nearbyint(rm[n * in + k] / s);
-                v = std::min(127.0f, std::max(-127.0f, v));
-                q[n * in + k] = (int8_t)v;
-                rm[n * in + k] = v * s;
-            }
-        }
-    }
-    // tiled int8 copy + scales of a row-major matrix (rm is replaced by W^).  Layout: per (16-row tile, 128-deep super-step) 2 KiB:
-    // load u (0, 1) of lane l is 16 bytes = MFMA steps 2u and 2u + 1, byte j -> k = ss*128 + (l >> 4)*32 + (2u + j/8)*8 + j%8
+    // The step kernel streams quantize_rows' q (1 byte per weight, stored offset-binary q + 128, in its fragment order) and multiplies by
+    // s[n] in the epilogue; everything else that touches the matrix (prefill GEMMs, the 32-wide linears of k_step_begin) reads a row-major
+    // f32 copy of W^, so that the whole model computes with ONE set of weights -- the ones an f32 oracle is given in the parity tests.
+    // tiled int8 copy + scales of a row-major matrix (rm is replaced by W^)
     void add_tiled_i8(Lin& l, std::vector<float>* rm) {
-        const size_t nt = ((size_t)l.out + 15) / 16, nss = ((size_t)l.in + 127) / 128;
-        l.wt = reserve(nt * nss * 2048);
+        l.wt = reserve(step_tiled_bytes((size_t)l.out, (size_t)l.in, 1));
         l.wscale = reserve((size_t)l.out * 4);
         l.wt_i8 = 1;
         if (!host) return;
@@ -93,16 +126,7 @@ struct Walker {
         std::vector<int8_t> q;
         quantize_rows(*rm, (size_t)l.out, (size_t)l.in, scale, q);
         std::memcpy(host + l.wscale, scale.data(), scale.size() * 4);
-        uint8_t* dst = host + l.wt;
-        for (size_t t = 0; t < nt; t++)
-            for (size_t ss = 0; ss < nss; ss++)
-                for (int u = 0; u < 2; u++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < 16; j++) {
-                            const size_t n = t * 16 + (size_t)(lane & 15), k = ss * 128 + (size_t)(lane >> 4) * 32 + (size_t)(2 * u + j / 8) * 8 + (size_t)(j % 8);
-                            const int v = (n < (size_t)l.out && k < (size_t)l.in) ? q[n * l.in + k] : 0;
-                            dst[((((t * nss + ss) * 2 + u) * 64 + lane) * 16) + j] = (uint8_t)(v + 128);
-                        }
+        pack_step_tiled_i8(q.data(), (size_t)l.out, (size_t)l.in, host + l.wt);
     }
     // a matrix the AR step streams, with its row-major copy (own_rowmajor) or only the tiled one (a stack of matrices whose
     // rows already exist row-major elsewhere)
@@ -131,25 +155,11 @@ struct Walker {
             add_tiled_i8(l, &rm);
             return;
         }
-        const int E = bf16w ? 8 : 4, WV = bf16w ? 4 : 8;
-        const size_t nt = ((size_t)l.out + 15) / 16, nss = ((size_t)l.in + 127) / 128;
-        const size_t count = nt * nss * 16 * 128;
-        l.wt = reserve(count * (bf16w ? 2 : 4));
+        l.wt = reserve(step_tiled_bytes((size_t)l.out, (size_t)l.in, bf16w ? 2 : 4));
         if (!host) return;
         std::vector<float> rm((size_t)l.out * l.in);
         fill_rowmajor(rm.data());
-        uint8_t* dst = host + l.wt;
-        for (size_t t = 0; t < nt; t++)
-            for (size_t ss = 0; ss < nss; ss++)
-                for (int sidx = 0; sidx < WV; sidx++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < E; j++) {
-                            size_t n = t * 16 + (size_t)(lane & 15), k = ss * 128 + (size_t)(lane >> 4) * 32 + (size_t)sidx * E + j;
-                            float v = (n < (size_t)l.out && k < (size_t)l.in) ? rm[n * l.in + k] : 0.0f;
-                            size_t e = ((((t * nss + ss) * WV + sidx) * 64 + lane) * E + j);
-                            if (bf16w) reinterpret_cast<uint16_t*>(dst)[e] = f32_to_bf16_rne(v);
-                            else reinterpret_cast<float*>(dst)[e] = v;
-                        }
+        pack_step_tiled(rm.data(), (size_t)l.out, (size_t)l.in, bf16w, host + l.wt);
     }
     // Fragment-ordered bf16 copy for resblock.hip: [16-column tile][32-deep k step][lane][8] with lane l holding
     // W[tile*16 + (l & 15)][step*32 + (l >> 4)*8 .. +8) -- the row operand of v_mfma_f32_16x16x32_bf16, so a wave's fragment

@@ -22,6 +22,13 @@ struct Lin {   // linear.go:11-16 (also a convolution expressed as a GEMM)
     size_t wf = NONE, wf_lo = NONE;   // copy in 16x16x32 MFMA fragment order for the fused SEANet block (resblock.hip); lo plane: f32 weights only
     int in = 0, out = 0, bf16 = 0;
 };
+// The step kernels' weight formats (model.cpp; skinny.hip reads them): the fragment-ordered copy of a row-major [out][in] matrix in f32 or bf16
+// (zero-padded to 16 rows x 128 k), the per-row int8 quantisation (rm becomes W^ = q * scale) and its fragment-ordered copy (bytes q + 128).
+size_t step_tiled_bytes(size_t out, size_t in, int bytes_per_weight);
+void pack_step_tiled(const float* rm, size_t out, size_t in, bool bf16w, uint8_t* dst);
+void quantize_rows(std::vector<float>& rm, size_t out, size_t in, std::vector<float>& scale, std::vector<int8_t>& q);
+void pack_step_tiled_i8(const int8_t* q, size_t out, size_t in, uint8_t* dst);
+
 struct Norm {  // linear.go:184-189
     size_t w = NONE, b = NONE;
     int d = 0;

@@ -620,7 +620,11 @@ static int pick_split(int M, int N, int K, bool w_bf16) {
     int need = (K + 1023) / 1024;
     int blocks = ((N + 63) / 64) * ((M + 15) / 16);
     int want = (256 + blocks - 1) / blocks;
-    return std::max(need, std::min(want, K / 512));
+    int S = std::max(need, std::min(want, K / 512));
+    // the slices are whole 128-deep super-steps: at widths that are no multiple of 512 the rounding can leave the last of many slices empty (K = 3080 over 6:
+    // 5 x 640 >= K), which the step kernel does not take (skinny_supported).  `need` slices of at most 1024 never do: (need - 1) * 1024 < K
+    while (S > need && (S - 1) * (((K + S - 1) / S + 127) / 128 * 128) >= K) S--;
+    return S;
 }
 
 // one transformer-style block input: rows of x (with a pending residual update) -> LayerNorm -> linear

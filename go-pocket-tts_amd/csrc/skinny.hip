@@ -580,14 +580,17 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
 bool skinny_supported(const GemmArgs& a, int splitk) {
     if (splitk < 1) splitk = 1;
     const int kslice = splitk > 1 ? ((a.K + splitk - 1) / splitk + 127) / 128 * 128 : a.K;
-    return a.Wt && a.M <= kStepMaxRows && a.K % 8 == 0 && kslice <= (splitk > 1 && (a.w_bf16 || a.wt_i8) ? SK_KMAX2 : SK_KMAX) && (!a.wt_i8 || a.wscale) && a.amap.rows_per_batch == 0 && a.cmap.rows_per_batch == 0 &&
+    // (a split whose last slice starts at or beyond K is refused: the kernel's row loads are unconditional within a slice and would start behind the row)
+    return a.Wt && a.M <= kStepMaxRows && a.K % 8 == 0 && kslice <= (splitk > 1 && (a.w_bf16 || a.wt_i8) ? SK_KMAX2 : SK_KMAX) && (int64_t)(splitk - 1) * kslice < a.K &&
+           (!a.wt_i8 || a.wscale) && a.amap.rows_per_batch == 0 && a.cmap.rows_per_batch == 0 &&
            a.amap.ld % 4 == 0 && aligned16(a.A) && aligned16(a.W) && a.ldw % 8 == 0 && a.aop == AOP_NONE;
 }
 
 bool skinny_fuse_supported(const GemmArgs& a, const SkinnyFuse& f) {
     // the fused prologue needs whole rows in one block: K is the row width, one K slice, dense rows
     return skinny_supported(a, 1) && a.K <= SK_KMAX && a.amap.ld == a.K && a.K % 4 == 0 && (!f.scale || f.ldmod % 4 == 0) &&
-           !f.pgate && (!f.ln_w == !f.ln_b) && (!f.partial || f.psplit >= 1) && (f.ln || !(f.ln_w || f.scale)) &&
+           !f.pgate && (!f.ln_w == !f.ln_b) && (!f.scale == !f.shift) && (!f.partial || f.psplit >= 1) && (f.ln || !(f.ln_w || f.scale)) &&
+           (!(f.partial && f.ln) || f.ln_w) &&   // a pending sum in front of a LayerNorm: instantiated with the affine only (launch_w)
            (!f.fin || (a.N <= 64 && a.K <= 512 && f.ln && f.scale && !f.ln_w && !f.partial)) &&   // fin: instantiated for the flow net's final layer only
            (!f.chain || (f.fin && a.N == SO_K && a.epi == EPI_AXPY && !a.tail && f.chain_noise_stride % 2 == 0));   // chain: the frame is the whole row of C (ldim == 32)
 }
@@ -669,7 +672,8 @@ static void launch_w(const GemmArgs& a, const SkinnyFuse& fu, int splitk, float*
         case PRO_LN | PRO_MOD: launch_pro<WBF16, PRO_LN | PRO_MOD>(a, fu, splitk, partial, grid, stream); break;
         case PRO_LN: launch_pro<WBF16, PRO_LN>(a, fu, splitk, partial, grid, stream); break;
         case PRO_PARTIAL: launch_pro<WBF16, PRO_PARTIAL>(a, fu, splitk, partial, grid, stream); break;   // split-K sum + residual, no norm
-        default: launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_MOD | PRO_PARTIAL>(a, fu, splitk, partial, grid, stream); break;
+        case PRO_LN | PRO_AFFINE | PRO_MOD | PRO_PARTIAL: launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_MOD | PRO_PARTIAL>(a, fu, splitk, partial, grid, stream); break;
+        default: throw Error(PTTS_EINVAL, strfmt("ptts-hip: internal: the step kernel has no instance for prologue form %d", pro));   // (skinny_fuse_supported refuses these)
     }
 }
 

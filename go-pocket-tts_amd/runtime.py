@@ -119,7 +119,7 @@ HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
-    "ptts_debug_loudness_energies", "ptts_debug_kweighting",
+    "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear",
 ]
 
 
@@ -1128,6 +1128,64 @@ def debug_tall_linear(x, w, *, bias=None, residual=None, epi=0, splitk=1, ln=Non
                                     _fp(w), _fp(b) if b is not None else nul, _fp(r) if r is not None else nul, 1 if out_planes else 0, _fp(out),
                                     _fp(xo) if xo is not None else nul))
     return (out[0] if s == 1 else out), xo
+
+
+class _StepLinearArgs(C.Structure):   # ptts_step_linear_args
+    _fields_ = ([(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldc", "wfmt", "epi", "splitk", "tail", "path", "ldg", "ln", "ldmod", "psplit", "r_in_c", "zrows",
+                                          "pgate", "reserved")] +
+                [("alpha", C.c_float), ("eps", C.c_float)] +
+                [(n, _FP) for n in ("x", "W", "bias", "addvec", "R", "scale", "gate", "ln_w", "ln_b", "shift", "mscale", "planes", "pbias",
+                                    "C", "tail_out", "x_out", "y_out", "w_eff", "w_scale")] +
+                [("launches", C.POINTER(C.c_int32))])
+
+
+def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, inplace=False, scale=None, gate=None, alpha=1.0, epi=0, tail=False,
+                      ldc=None, splitk=1, zrows=0, ln=False, ln_wb=None, eps=1e-5, shift=None, mscale=None, planes=None, pbias=None, pgate=False, path=0):
+    """The step linear (csrc/skinny.hip) on host operands (ptts_debug_step_linear, include/ptts_debug.h).  x [M, lda] (K columns are multiplied: default
+    lda), w [N, K] f32; wfmt 0 f32 / 1 bf16 / 2 int8; residual [M, ldc] (inplace: the kernel runs with R == C), gate [M, ldg]; ln_wb = (weight, bias);
+    shift / mscale [M, ldmod]; planes [psplit, M, K]; path 0: launch_skinny, 1: launch_gemm.  Returns a dict: "out" ([M, ldc], or the planes
+    [splitk, zrows or M, N]), "tail", "x_out", "y_out" (whole buffers: NaN where nothing was stored), "w_eff" / "w_scale" (int8), "k_skinny" / "launches"
+    (the census of the call)."""
+    x, w = _f32(x), _f32(w)
+    m, lda = x.shape
+    n, k = w.shape
+    ldc = n if ldc is None else int(ldc)
+    s = max(1, int(splitk))
+    keep = []   # the arrays the struct points into
+
+    def ptr(a):
+        if a is None:
+            return C.cast(None, _FP)
+        a = _f32(a)
+        keep.append(a)
+        return _fp(a)
+
+    a = _StepLinearArgs()
+    a.M, a.N, a.K, a.lda, a.ldc, a.wfmt, a.epi, a.splitk, a.tail, a.path = m, n, k, lda, ldc, int(wfmt), int(epi), s, 1 if tail else 0, int(path)
+    a.ldg = 0 if gate is None else int(np.asarray(gate).shape[1])
+    a.ln = 1 if ln else 0
+    mod = shift if shift is not None else mscale
+    a.ldmod = 0 if mod is None else int(np.asarray(mod).shape[1])
+    a.psplit = 0 if planes is None else int(np.asarray(planes).shape[0])
+    a.r_in_c, a.zrows, a.pgate = (1 if inplace else 0), int(zrows), (1 if pgate else 0)
+    a.alpha, a.eps = float(alpha), float(eps)
+    a.x, a.W, a.bias, a.addvec, a.R, a.scale, a.gate = ptr(x), ptr(w), ptr(bias), ptr(addvec), ptr(residual), ptr(scale), ptr(gate)
+    a.ln_w, a.ln_b = (ptr(ln_wb[0]), ptr(ln_wb[1])) if ln_wb is not None else (ptr(None), ptr(None))
+    a.shift, a.mscale, a.planes, a.pbias = ptr(shift), ptr(mscale), ptr(planes), ptr(pbias)
+    out = np.empty((s, int(zrows) or m, n) if s > 1 else (m, ldc), np.float32)
+    tl = np.empty(m, np.float32)
+    fused = bool(ln or planes is not None or shift is not None or mscale is not None or ln_wb is not None or pgate)
+    xo = np.empty((m, k), np.float32) if fused else None
+    yo = np.empty((m, k), np.float32) if fused else None
+    we = np.empty((n, k), np.float32) if int(wfmt) == 2 else None
+    ws = np.empty(n, np.float32) if int(wfmt) == 2 else None
+    cnt = (C.c_int32 * 2)()
+    a.C, a.tail_out, a.x_out, a.y_out, a.w_eff, a.w_scale = ptr(out), ptr(tl), ptr(xo), ptr(yo), ptr(we), ptr(ws)
+    a.launches = C.cast(cnt, C.POINTER(C.c_int32))
+    H = hooks()
+    H.ptts_debug_step_linear.argtypes = [C.POINTER(_StepLinearArgs)]
+    _check(H.ptts_debug_step_linear(C.byref(a)))
+    return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
 
 
 def last_attention_kernel() -> str:

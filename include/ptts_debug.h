@@ -55,6 +55,29 @@ int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t
                            const float* ln_w, const float* ln_b, float eps, const float* W, const float* bias, const float* R, int32_t out_planes, float* out,
                            float* x_out);
 
+/* The step linear (csrc/skinny.hip: k_skinny, the kernel every AR step spends its time in) stand-alone on host operands.  C = epi(prologue(x) W^T + bias):
+ *   x [M][lda] (lda >= K), W [N][K] f32 row-major; wfmt 0: f32 weights, 1: rounded to bf16, 2: per-row int8 (w_eff [N][K] receives W^ = q s, w_scale [N] the
+ *   row scales); the tiled copy the kernel streams is made by the packers the model loader uses.
+ *   Epilogue: epi 0..8 (kernels.h Epi) with bias [N], addvec [N, or N - 1 with tail], R [M][ldc] (r_in_c: R is uploaded INTO C and the kernel runs with
+ *   R == C), scale [N], gate [M][ldg], alpha; tail: the last column goes as acc + bias to tail_out [M] instead of C.
+ *   splitk > 1: C receives the planes [splitk][zrows or M][N] (plane 0 = R + (sums + bias) when R is given, raw sums otherwise); zrows > 0 launches with
+ *   GemmArgs::zstride = zrows N (the planes of a row chunk of a taller operand).  Otherwise C is [M][ldc].
+ *   Fused prologue (splitk 1, lda == K): planes [psplit][M][K] (+ pbias [K]) are added to the rows in order -> x_out [M][K]; ln: LayerNorm (eps) with the
+ *   optional affine ln_w / ln_b [K] and the optional modulation y (1 + mscale[m]) + shift[m] (rows [M][ldmod]) -> y_out [M][K]; pgate != 0 asks for the
+ *   gated pending sum the kernel does not have (refused).
+ *   path 0: launch_skinny; 1: launch_gemm (the <= 64-row hand-over and the 64-row chunks up to 256 rows; no split, no prologue).
+ * C, tail_out, x_out and y_out are filled with 0xff bytes before the launch and returned whole (padding columns included).  launches [2] receives the
+ * census of the call: k_skinny launches, all noted launches.  PTTS_EINVAL, before anything is launched, for whatever skinny_supported /
+ * skinny_fuse_supported (or launch_gemm's hand-over condition) refuse. */
+typedef struct ptts_step_linear_args {
+    int32_t M, N, K, lda, ldc, wfmt, epi, splitk, tail, path, ldg, ln, ldmod, psplit, r_in_c, zrows, pgate, reserved;
+    float alpha, eps;
+    const float *x, *W, *bias, *addvec, *R, *scale, *gate, *ln_w, *ln_b, *shift, *mscale, *planes, *pbias;
+    float *C, *tail_out, *x_out, *y_out, *w_eff, *w_scale;
+    int32_t* launches;
+} ptts_step_linear_args;
+int ptts_debug_step_linear(const ptts_step_linear_args* a);
+
 /* name of the kernel the calling thread's last attention launch used ("k_attn_step", "k_attn_window", "k_attn_window<ragged>",
  * "k_attention"): lets a parity test assert that it exercised the kernel it means to */
 const char* ptts_debug_last_attention_kernel(void);

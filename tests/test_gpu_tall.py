@@ -6,7 +6,7 @@ What they replace: Linear.Forward (internal/native/linear.go:117-182) behind Lay
 32- or 64-row tile, a last column block with one 16-column tile, split-K planes, the bf16 hi / lo plane epilogue) are checked value by value.
 
 Tolerance: activations enter the matrix pipe as bf16 hi + lo (|x - hi - lo| <= 2^-17 |x|), weights are bf16 exactly, sums are f32 over K <= 4096:
-|error| <= 3e-5 * (sum_k |a_k w_k| + |bias| + |R|) bounds both with a margin of ~4 (the same bound the 64-row step linear is tested with)."""
+|error| <= 3e-5 * (sum_k |a_k w_k| + |bias| + |R|) bounds both with a margin of ~4 (the same bound the 64-row step linear is tested with: tests/test_gpu_step_linear.py)."""
 import math
 import os
 import sys
