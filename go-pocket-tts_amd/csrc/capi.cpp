@@ -1028,7 +1028,7 @@ int64_t ptts_resample_length(int64_t n_in, int32_t in_rate, int32_t out_rate) {
     return resample_length(n_in, in_rate, out_rate);
 }
 
-// n host rows -> n host rows through one device buffer each way: rows packed 256-byte aligned, one k_resample launch per ResampleRing::kRows rows
+// n host rows -> n host rows through one device buffer each way: rows packed 256-byte aligned, one k_resample launch per RowRing::kRows rows
 static void device_convert(Model& m, const float* const* in, const int64_t* n_in, int32_t n, const RateFilter* f, const int64_t* n_out, int fmt,
                            void* const* out) {
     std::lock_guard<std::mutex> lock(m.mu);

@@ -3,7 +3,7 @@
 // reference links therefore exports no fault injection, no micro-benchmarks and no launch census.
 #include "capi_internal.h"
 #include "../../include/ptts_debug.h"
-#include "loudness_block.h"
+#include "scan_block.h"
 
 using namespace ptts;
 using namespace ptts::capi;

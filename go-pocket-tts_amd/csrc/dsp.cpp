@@ -1,7 +1,7 @@
 // dsp.cpp -- SURVEY.md 8f N3, the optional post-processing of a finished utterance (internal/audio/dsp.go:12-78; applied by the CLI
 // in the order normalise -> DC block -> fade in -> fade out, cmd/pockettts/synth.go:361-390).  This file is the host form on host samples
 // (ptts_dsp_apply), and the yardstick of the device form: a request's ptts_dsp_opts and ptts_dsp_rows run the same chain on the GPU
-// (dsp.hip, dsp_device.cpp), the filter's recurrence as a blocked scan (dsp_block.h) whose host instantiation is dsp_dc_block_blocked below.
+// (dsp.hip, dsp_device.cpp), the filter's recurrence as a blocked scan (scan_block.h) whose host instantiation is dsp_dc_block_blocked below.
 //
 // PeakNormalize, FadeIn and FadeOut follow dsp.go operation for operation (float32 products, the same gain expressions): bit-exact
 // against the oracle.  DCBlock delegates, in the reference, to github.com/cwbudde/algo-dsp (design.Highpass(20 Hz, Q 0.707) +
@@ -10,7 +10,7 @@
 // UNPINNED for this one function.
 #include <cmath>
 
-#include "dsp_block.h"
+#include "scan_block.h"
 #include "runtime.h"
 
 namespace ptts {
@@ -60,46 +60,20 @@ void dsp_fade_out(float* s, int64_t n, int sample_rate, double ms) {   // dsp.go
     }
 }
 
-// the section of dsp_dc_block and the powers A^kDspRun, A^kDspTile of its state matrix A = [[-a1, 1], [-a2, 0]], by repeated multiplication
+// the section of dsp_dc_block and the powers A^kDspRun, A^kDspTile of its state matrix A = [[-a1, 1], [-a2, 0]]
 DspScan dsp_scan_coeffs(int sample_rate) {
     DspScan sc;
     sc.c = dc_block_section(sample_rate);
     const double A[4] = {-sc.c.a1, 1.0, -sc.c.a2, 0.0};
-    double P[4] = {1.0, 0.0, 0.0, 1.0};
-    for (int k = 1; k <= kDspTile; k++) {
-        const double Q[4] = {A[0] * P[0] + A[1] * P[2], A[0] * P[1] + A[1] * P[3], A[2] * P[0] + A[3] * P[2], A[2] * P[1] + A[3] * P[3]};
-        for (int j = 0; j < 4; j++) P[j] = Q[j];
-        if (k == kDspRun) for (int j = 0; j < 4; j++) sc.a_run[j] = P[j];
-    }
-    for (int j = 0; j < 4; j++) sc.a_tile[j] = P[j];
+    scan_powers<2>(A, sc.a_run, sc.a_tile);
     return sc;
 }
 
-// dsp_dc_block in the blocked form the device runs (dsp_block.h), tile by tile and run by run with the same functions: what k_dsp_summary,
-// k_dsp_carry and k_dsp_apply compute for one row without a gain
+// dsp_dc_block in the blocked form the device runs (scan_block.h), with the same functions: what k_dsp_summary, k_dsp_carry and k_dsp_apply
+// compute for one row without a gain
 void dsp_dc_block_blocked(float* s, int64_t n, int sample_rate) {
     const DspScan sc = dsp_scan_coeffs(sample_rate);
-    double S1 = 0.0, S2 = 0.0;
-    for (int64_t base = 0; base < n; base += kDspTile) {
-        const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
-        float* tile = s + base;
-        double e[kDspLanes][2];
-        for (int l = 0; l < kDspLanes; l++) {
-            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
-            double z1 = 0.0, z2 = 0.0;
-            dsp_run(sc.c, tile + l * kDspRun, nullptr, c, z1, z2);
-            e[l][0] = z1; e[l][1] = z2;
-        }
-        double E1 = 0.0, E2 = 0.0, t1 = S1, t2 = S2;
-        for (int l = 0; l < kDspLanes; l++) {
-            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
-            double z1 = t1, z2 = t2;
-            dsp_run(sc.c, tile + l * kDspRun, tile + l * kDspRun, c, z1, z2);
-            dsp_advance(sc.a_run, t1, t2, e[l][0], e[l][1]);
-            dsp_advance(sc.a_run, E1, E2, e[l][0], e[l][1]);
-        }
-        dsp_advance(sc.a_tile, S1, S2, E1, E2);
-    }
+    scan_walk(sc, s, n, [&](int64_t i0, int count, double* z) { sc.run(s + i0, count, z, s + i0); });
 }
 
 }  // namespace ptts

@@ -1,19 +1,29 @@
-// dsp.hip -- ptts_dsp_apply's chain on the device (kernels.h DspRow): peak normalise, DC block, fade in, fade out
-// on ragged rows of decoded 24 kHz audio, in place, in front of k_resample.
+// dsp.hip -- post-processing of ragged rows of decoded 24 kHz audio on the device, in front of k_resample (kernels.h DspRow; scan_block.h;
+// DESIGN.md section 8, N3): ptts_dsp_apply's chain -- peak normalise, DC block, fade in, fade out -- in place, and integrated loudness
+// (ITU-R BS.1770-4, mono) with the gain that takes a row to its target.
 //
-//   k_dsp_peak     normalise rows: max |x| of the row.  A max is order-independent and non-negative floats order like their bit patterns, so
-//                  the workgroups' atomicMax on the uint32 image gives the host's peak whatever the schedule.  NaNs never win (as on the host).
-//   k_dsp_summary  DC rows: one workgroup per full tile that another tile follows; lane l runs run l from zero state, lane 0 folds the 64
-//                  end states in run order into E_f (dsp_block.h).
-//   k_dsp_carry    DC rows: one workgroup per row; S_0 = 0, S_(f+1) = A^1920 S_f + E_f in tile order.
-//   k_dsp_apply    every tile: gain (an IEEE f32 division, one f32 product per sample), the runs' recurrence from their entering states
-//                  (t_0 = S_f, t_(l+1) = A^30 t_l + e_l in run order), the rounding to f32, the two fade gains as two f32 products, one store.
-// The filter's input is the f32 product x * gain wherever it is read, so the peak is complete before k_dsp_summary starts (stream order).
-// Tiles lie on the row's own grid: a row's bits are a function of the row alone.  Nothing at or beyond n is read or written.
-// A loudness row (DSP_LOUD, loudness.hip) has its gain in a word k_loud_gate wrote; k_dsp_summary and k_dsp_apply are templates on whether the
-// table has such a row, so a table without one launches the instantiation that does not know the flag: the code it ran before the flag existed.
+//   k_dsp_peak      normalise and loudness rows: max |x| of the row.  A max is order-independent and non-negative floats order like their bit
+//                   patterns, so the workgroups' atomicMax on the uint32 image gives the host's peak whatever the schedule.  NaNs never win.
+//   k_*_summary     one workgroup per full tile that another tile follows; lane l runs run l from zero state, lane 0 folds the 64 end states
+//                   in run order into E_f (scan_summary).
+//   k_*_carry       one workgroup per row; S_0 = 0, S_(f+1) = A^1920 S_f + E_f in tile order (scan_carry).
+//   k_dsp_apply     every tile: gain (an IEEE f32 division, one f32 product per sample), the runs' recurrence from their entering states
+//                   (scan_enter: t_0 = S_f, t_(l+1) = A^30 t_l + e_l in run order), the rounding to f32, the two fade gains as two f32
+//                   products, one store.
+//   k_loud_energy   every tile: the runs' entering states, each run's sum of squared outputs in sample order, and the tile's four sub-block
+//                   energies (16 run sums each, in run order) as doubles.
+//   k_loud_gate     one workgroup per row: block energies (20 sub-blocks in order, over 9600; lanes take a block each), the absolute and the
+//                   relative gate and the means in block order by lane 0, M and the f32 gain min((float)sqrt(T / M), 1 / peak).
+// k_dsp_* are the DC block's (DspScan, DSP_DC rows, on the f32 product x * gain wherever it is read), k_loud_* the K-weighting's (LoudScan,
+// DSP_LOUD rows, on the RAW samples: nothing is written to them, k_dsp_apply applies the gain).  Stream order has the peak complete before
+// k_loud_gate and k_dsp_summary start, and the loudness gain before k_dsp_summary.  One wave per workgroup and at most 12.5 KB of LDS: a CU
+// holds a dozen workgroups, the passes are reads of the rows at HBM rate.  Tiles lie on the row's own grid and every sum has one order: a
+// row's bits are a function of the row alone, and they are the bits of the host instantiations (dsp.cpp, loudness.cpp).  Nothing at or beyond
+// n is read or written.
+// k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row, so a table without one launches the instantiation
+// that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
-#include "dsp_block.h"
+#include "scan_block.h"
 
 namespace ptts {
 
@@ -22,6 +32,7 @@ namespace {
 constexpr int kPeakThreads = 256, kPeakChunk = 4 * kDspTile;
 
 struct Gain { bool on; float g; };
+constexpr Gain kNoGain{false, 1.0f};
 template <bool LOUD>
 __device__ __forceinline__ Gain row_gain(const DspRow& r) {   // dsp_peak_normalize: gain = 1.0f / peak, a row of zeros stays as it is
     if (LOUD && (r.flags & DSP_LOUD)) {   // loud_measure_gain's: a gain of 1 leaves the samples as they are
@@ -34,7 +45,7 @@ __device__ __forceinline__ Gain row_gain(const DspRow& r) {   // dsp_peak_normal
     return Gain{true, __fdiv_rn(1.0f, peak)};
 }
 
-// samples [base, base + cnt) of the row into tile[0, cnt), times the gain; 16-byte loads where the row's alignment allows
+// samples [base, base + cnt) of the row into tile[0, cnt), times the gain if it is on; 16-byte loads where the row's alignment allows
 __device__ __forceinline__ void load_tile(const DspRow& r, int64_t base, int cnt, float* tile, const Gain g) {
     const float* src = r.x + base;
     const bool vec = ((uintptr_t)src & 15) == 0;
@@ -66,7 +77,6 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
         } else {
             for (int u = 0; u < 4 && q + u < i1; u++) v[u] = r.x[q + u];
         }
-#pragma unroll
         for (int u = 0; u < 4; u++) { const float a = fabsf(v[u]); if (a > pk) pk = a; }
     }
     pk = wave_max(pk);   // (pk is never NaN)
@@ -78,57 +88,105 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
     }
 }
 
-template <bool LOUD>
-__global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
+// only a full tile that another one follows hands a state on
+__device__ __forceinline__ bool tile_hands_on(const DspRow& r) { return (int64_t)(blockIdx.x + 1) * kDspTile < r.n; }
+// samples of the lane's run in a tile of cnt
+__device__ __forceinline__ int run_count(int cnt) { return max(0, min(kDspRun, cnt - (int)threadIdx.x * kDspRun)); }
+
+// tile blockIdx.x of the row, which hands a state on: E_f into the row's per-tile states
+template <class Sys>
+__device__ __forceinline__ void scan_summary(const Sys& sc, const DspRow& r, double* states, const Gain g) {
+    constexpr int N = Sys::N;
     __shared__ float4 tile4[kDspTile / 4];
-    __shared__ double e[kDspLanes][2];
+    __shared__ double e[kDspLanes][N];
     float* tile = reinterpret_cast<float*>(tile4);
-    const DspRow& r = rows[blockIdx.y];
-    const int64_t base = (int64_t)blockIdx.x * kDspTile;
-    if (!(r.flags & DSP_DC) || base + kDspTile >= r.n) return;   // only a full tile that another one follows hands a state on
-    load_tile(r, base, kDspTile, tile, row_gain<LOUD>(r));
+    load_tile(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile, g);
     __syncthreads();
     const int l = threadIdx.x;
-    double z1 = 0.0, z2 = 0.0;
-    dsp_run(sc.c, tile + l * kDspRun, nullptr, kDspRun, z1, z2);
-    e[l][0] = z1; e[l][1] = z2;
+    double z[N] = {};
+    sc.run(tile + l * kDspRun, kDspRun, z);
+    for (int i = 0; i < N; i++) e[l][i] = z[i];
     __syncthreads();
     if (l == 0) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int j = 0; j < kDspLanes; j++) dsp_advance(sc.a_run, s1, s2, e[j][0], e[j][1]);
-        r.tiles[(int64_t)blockIdx.x * 4 + 0] = s1;
-        r.tiles[(int64_t)blockIdx.x * 4 + 1] = s2;
+        double s[N] = {};
+        for (int j = 0; j < kDspLanes; j++) scan_advance<N>(sc.a_run, s, e[j]);
+        double* E = scan_E<N>(states, blockIdx.x);
+        for (int i = 0; i < N; i++) E[i] = s[i];
     }
 }
 
-__global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restrict__ rows, const DspScan sc) {
-    __shared__ double ein[kDspLanes][2], sout[kDspLanes][2];
-    const DspRow& r = rows[blockIdx.x];
-    if (!(r.flags & DSP_DC) || r.n <= 0) return;
-    const int64_t F = (r.n + kDspTile - 1) / kDspTile;
+// a row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time
+template <class Sys>
+__device__ __forceinline__ void scan_carry(const Sys& sc, int64_t F, double* states) {
+    constexpr int N = Sys::N;
+    __shared__ double ein[kDspLanes][N], sout[kDspLanes][N];
     const int l = threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;   // lane 0's: the state entering tile c0 + j
+    double s[N] = {};   // lane 0's: the state entering tile c0 + j
     for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
         const int64_t f = c0 + l;
-        if (f < F - 1) { ein[l][0] = r.tiles[f * 4 + 0]; ein[l][1] = r.tiles[f * 4 + 1]; }
+        if (f < F - 1) for (int i = 0; i < N; i++) ein[l][i] = scan_E<N>(states, f)[i];
         __syncthreads();
         if (l == 0) {
             const int m = (int)min((int64_t)kDspLanes, F - c0);
             for (int j = 0; j < m; j++) {
-                sout[j][0] = s1; sout[j][1] = s2;
-                if (c0 + j < F - 1) dsp_advance(sc.a_tile, s1, s2, ein[j][0], ein[j][1]);
+                for (int i = 0; i < N; i++) sout[j][i] = s[i];
+                if (c0 + j < F - 1) scan_advance<N>(sc.a_tile, s, ein[j]);
             }
         }
         __syncthreads();
-        if (f < F) { r.tiles[f * 4 + 2] = sout[l][0]; r.tiles[f * 4 + 3] = sout[l][1]; }
+        if (f < F) for (int i = 0; i < N; i++) scan_S<N>(states, f)[i] = sout[l][i];
         __syncthreads();
     }
+}
+
+// z <- the state entering the lane's run (c samples at `run`, in LDS) of tile blockIdx.x: every run from zero state, then lane 0's fold in run
+// order from S_f.  (Behind a run that is not full no run follows: its t is not read.)
+template <class Sys>
+__device__ __forceinline__ void scan_enter(const Sys& sc, const float* run, int c, double* states, double* z) {
+    constexpr int N = Sys::N;
+    __shared__ double e[kDspLanes][N], t[kDspLanes][N];
+    const int l = threadIdx.x;
+    for (int i = 0; i < N; i++) z[i] = 0.0;
+    sc.run(run, c, z);
+    for (int i = 0; i < N; i++) e[l][i] = z[i];
+    __syncthreads();
+    if (l == 0) {
+        const double* S = scan_S<N>(states, blockIdx.x);
+        double s[N];
+        for (int i = 0; i < N; i++) s[i] = S[i];
+        for (int j = 0; j < kDspLanes; j++) {
+            for (int i = 0; i < N; i++) t[j][i] = s[i];
+            scan_advance<N>(sc.a_run, s, e[j]);
+        }
+    }
+    __syncthreads();
+    for (int i = 0; i < N; i++) z[i] = t[l][i];
+}
+
+template <bool LOUD>
+__global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
+    const DspRow& r = rows[blockIdx.y];
+    if ((r.flags & DSP_DC) && tile_hands_on(r)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_loud_summary(const DspRow* __restrict__ rows, const LoudScan sc) {
+    const DspRow& r = rows[blockIdx.y];
+    if ((r.flags & DSP_LOUD) && tile_hands_on(r)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restrict__ rows, const DspScan sc) {
+    const DspRow& r = rows[blockIdx.x];
+    if ((r.flags & DSP_DC) && r.n > 0) scan_carry(sc, scan_tiles(r.n), r.tiles);
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_loud_carry(const DspRow* __restrict__ rows, const LoudScan sc) {
+    const DspRow& r = rows[blockIdx.x];
+    if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud));
 }
 
 template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restrict__ rows, const DspScan sc) {
     __shared__ float4 tile4[kDspTile / 4];
-    __shared__ double e[kDspLanes][2], t[kDspLanes][2];
     float* tile = reinterpret_cast<float*>(tile4);
     const DspRow& r = rows[blockIdx.y];
     const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
@@ -141,22 +199,11 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
     load_tile(r, base, cnt, tile, g);
     __syncthreads();
     if (dc) {
-        const int l = threadIdx.x;
-        const int c = max(0, min(kDspRun, cnt - l * kDspRun));
-        double z1 = 0.0, z2 = 0.0;
-        dsp_run(sc.c, tile + l * kDspRun, nullptr, c, z1, z2);
-        e[l][0] = z1; e[l][1] = z2;
-        __syncthreads();
-        if (l == 0) {   // (behind a run that is not full no run follows: its t is not read)
-            double s1 = r.tiles[(int64_t)blockIdx.x * 4 + 2], s2 = r.tiles[(int64_t)blockIdx.x * 4 + 3];
-            for (int j = 0; j < kDspLanes; j++) {
-                t[j][0] = s1; t[j][1] = s2;
-                dsp_advance(sc.a_run, s1, s2, e[j][0], e[j][1]);
-            }
-        }
-        __syncthreads();
-        z1 = t[l][0]; z2 = t[l][1];
-        dsp_run(sc.c, tile + l * kDspRun, tile + l * kDspRun, c, z1, z2);
+        float* run = tile + threadIdx.x * kDspRun;
+        const int c = run_count(cnt);
+        double z[DspScan::N];
+        scan_enter(sc, run, c, r.tiles, z);
+        sc.run(run, c, z, run);
         __syncthreads();
     }
     float* dst = r.x + base;
@@ -177,28 +224,89 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
     }
 }
 
+__global__ __launch_bounds__(kDspLanes) void k_loud_energy(const DspRow* __restrict__ rows, const LoudScan sc) {
+    __shared__ float4 tile4[kDspTile / 4];
+    __shared__ double q[kDspLanes];
+    float* tile = reinterpret_cast<float*>(tile4);
+    const DspRow& r = rows[blockIdx.y];
+    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    if (!(r.flags & DSP_LOUD) || base >= n) return;
+    const int cnt = (int)min((int64_t)kDspTile, n - base);
+    load_tile(r, base, cnt, tile, kNoGain);
+    __syncthreads();
+    const int l = threadIdx.x, c = run_count(cnt);
+    double z[LoudScan::N];
+    scan_enter(sc, tile + l * kDspRun, c, loud_states(r.loud), z);
+    q[l] = sc.run(tile + l * kDspRun, c, z);
+    __syncthreads();
+    // (a sub-block the row ends in holds the sum over the samples that are there; no whole 400 ms block contains it, so the gate never reads it)
+    if (l < kLoudSubsPerTile) loud_subs(r.loud, scan_tiles(n))[(int64_t)blockIdx.x * kLoudSubsPerTile + l] = loud_sub_energy(q + l * kLoudRunsPerSub);
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_loud_gate(const DspRow* __restrict__ rows, const LoudScan sc) {
+    __shared__ double z[kDspLanes];
+    __shared__ double rel_s;
+    const DspRow& r = rows[blockIdx.x];
+    if (!(r.flags & DSP_LOUD)) return;
+    const int64_t nb = loud_blocks(r.n);
+    const double* sub = loud_subs(r.loud, scan_tiles(r.n));
+    const int l = threadIdx.x;
+    LoudAcc first{0.0, 0}, second{0.0, 0};   // lane 0's
+    for (int pass = 0; pass < 2; pass++) {
+        const double rel = pass ? rel_s : sc.abs_gate;
+        for (int64_t c0 = 0; c0 < nb; c0 += kDspLanes) {
+            if (c0 + l < nb) z[l] = loud_block_energy(sub, c0 + l);
+            __syncthreads();
+            if (l == 0) {
+                const int m = (int)min((int64_t)kDspLanes, nb - c0);
+                for (int j = 0; j < m; j++) loud_gate_add(pass ? second : first, z[j], sc.abs_gate, rel);
+            }
+            __syncthreads();
+        }
+        if (pass == 0) {
+            if (l == 0) rel_s = first.cnt ? loud_rel_gate(first) : 0.0;
+            __syncthreads();
+        }
+    }
+    if (l == 0) {
+        const double M = (first.cnt && second.cnt) ? loud_div(second.sum, (double)second.cnt) : 0.0;
+        r.loud[0] = M;
+        *reinterpret_cast<float*>(r.loud + 1) = loud_gain(M, r.target, __uint_as_float(*r.peak));
+    }
+}
+
 }  // namespace
 
-void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, bool any_norm, bool any_dc, const DspScan& scan, hipStream_t stream, bool any_loud,
-                const LoudScan* loud, bool apply) {
+void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream) {
     if (n <= 0 || max_tiles <= 0) return;
-    if (any_norm || (any_loud && apply)) {   // (a measurement alone has no ceiling to keep)
+    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)(max_tiles - 1), (unsigned)n), lanes(kDspLanes);
+    if (p.any_norm || (p.any_loud && p.apply)) {   // (a measurement alone has no ceiling to keep)
         note_launch("k_dsp_peak");
         hipLaunchKernelGGL(k_dsp_peak, dim3((unsigned)((max_tiles + 3) / 4), (unsigned)n), dim3(kPeakThreads), 0, stream, rows_dev);
     }
-    if (any_loud) launch_loudness(rows_dev, n, max_tiles, *loud, stream);
-    if (!apply) return;
-    if (any_dc) {
+    if (p.any_loud) {   // behind k_dsp_peak, in front of every kernel that reads a gain
+        if (max_tiles > 1) {
+            note_launch("k_loud_summary");
+            hipLaunchKernelGGL(k_loud_summary, handing, lanes, 0, stream, rows_dev, *p.loud);
+        }
+        note_launch("k_loud_carry");
+        hipLaunchKernelGGL(k_loud_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
+        note_launch("k_loud_energy");
+        hipLaunchKernelGGL(k_loud_energy, tiles, lanes, 0, stream, rows_dev, *p.loud);
+        note_launch("k_loud_gate");
+        hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
+    }
+    if (!p.apply) return;
+    if (p.any_dc) {
         if (max_tiles > 1) {
             note_launch("k_dsp_summary");
-            hipLaunchKernelGGL(any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, dim3((unsigned)(max_tiles - 1), (unsigned)n), dim3(kDspLanes), 0, stream,
-                               rows_dev, scan);
+            hipLaunchKernelGGL(p.any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, handing, lanes, 0, stream, rows_dev, *p.scan);
         }
         note_launch("k_dsp_carry");
-        hipLaunchKernelGGL(k_dsp_carry, dim3((unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
+        hipLaunchKernelGGL(k_dsp_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.scan);
     }
     note_launch("k_dsp_apply");
-    hipLaunchKernelGGL(any_loud ? k_dsp_apply<true> : k_dsp_apply<false>, dim3((unsigned)max_tiles, (unsigned)n), dim3(kDspLanes), 0, stream, rows_dev, scan);
+    hipLaunchKernelGGL(p.any_loud ? k_dsp_apply<true> : k_dsp_apply<false>, tiles, lanes, 0, stream, rows_dev, *p.scan);
 }
 
 }  // namespace ptts

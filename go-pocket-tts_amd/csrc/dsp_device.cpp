@@ -2,8 +2,7 @@
 // tables and scratch of the DSP kernels, their launches.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes them.
 #include <cmath>
 
-#include "dsp_block.h"
-#include "loudness_block.h"
+#include "scan_block.h"
 #include "runtime.h"
 
 namespace ptts {
@@ -16,10 +15,6 @@ std::string dsp_opts_error(const ptts_dsp_opts& o) {
     return std::string();
 }
 
-DspRing::~DspRing() {
-    if (host) (void)hipHostFree(host);
-}
-
 namespace {
 int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: min((int64)(ms / 1000 * 24000), n)
     if (!(ms > 0)) return 0;
@@ -30,20 +25,14 @@ int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: mi
 
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
-    const LoudScan& loud = loud_scan();
     if (jobs.empty()) return;
-    DspRing& R = m.dsp_ring;
-    constexpr int kRows = DspRing::kRows;
-    if (!R.host) {
-        PTTS_HIP(hipHostMalloc((void**)&R.host, DspRing::kTurnBytes * DspRing::kRing, hipHostMallocDefault));
-        R.dev.ensure(DspRing::kTurnBytes * DspRing::kRing);
-    }
-    // scratch: a peak word per row, then [tiles][4] doubles per DC row and 2 + [tiles][12] per loudness row (kernels.h DspRow)
+    constexpr int kRows = RowRing<DspRow>::kRows;
+    // scratch: a peak word per row, then the per-tile states of each DC row and the block of each loudness row (scan_block.h)
     size_t tile_doubles = 0;
     for (const DspJob& j : jobs) {
         if (j.n <= 0) continue;
-        if (j.opts && j.opts->dc_block) tile_doubles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4;
-        if (j.loud) tile_doubles += 2 + (size_t)((j.n + kDspTile - 1) / kDspTile) * 12;
+        if (j.opts && j.opts->dc_block) tile_doubles += scan_state_doubles<DspScan::N>(scan_tiles(j.n));
+        if (j.loud) tile_doubles += loud_doubles(scan_tiles(j.n));
     }
     const size_t peak_bytes = (jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
     char* scratch = m.work(29, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
@@ -63,35 +52,28 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         r.fade_out = on ? fade_samples(j.opts->fade_out_ms, j.n) : 0;
         r.peak = peaks + k;
         r.flags = (on && j.opts->normalize ? DSP_NORMALIZE : 0) | (on && j.opts->dc_block ? DSP_DC : 0) | (j.loud ? DSP_LOUD : 0);
-        if (r.flags & DSP_DC) { r.tiles = tiles; tiles += (size_t)((j.n + kDspTile - 1) / kDspTile) * 4; }
+        if (r.flags & DSP_DC) { r.tiles = tiles; tiles += scan_state_doubles<DspScan::N>(scan_tiles(j.n)); }
         if (j.loud) {
             r.loud = j.loud_out = tiles;
             r.target = j.target_power;
-            tiles += 2 + (size_t)((j.n + kDspTile - 1) / kDspTile) * 12;
+            tiles += loud_doubles(scan_tiles(j.n));
         }
         rows.push_back(r);
     }
     for (size_t at = 0; at < rows.size(); at += kRows) {
         const int n = (int)std::min<size_t>(kRows, rows.size() - at);
         int64_t max_tiles = 0;
-        bool any_norm = false, any_dc = false, any_loud = false;
+        DspLaunch p{false, false, false, apply, &scan, &loud_scan()};
         for (int i = 0; i < n; i++) {
             const DspRow& r = rows[at + (size_t)i];
-            max_tiles = std::max(max_tiles, (r.n + kDspTile - 1) / kDspTile);
-            any_norm = any_norm || (r.flags & DSP_NORMALIZE);
-            any_dc = any_dc || (r.flags & DSP_DC);
-            any_loud = any_loud || (r.flags & DSP_LOUD);
+            max_tiles = std::max(max_tiles, scan_tiles(r.n));
+            p.any_norm = p.any_norm || (r.flags & DSP_NORMALIZE);
+            p.any_dc = p.any_dc || (r.flags & DSP_DC);
+            p.any_loud = p.any_loud || (r.flags & DSP_LOUD);
         }
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: dsp: too many samples for one launch");
-        const int t = R.turn;
-        R.turn = (t + 1) % DspRing::kRing;
-        R.ack.wait(t);   // the launches that last read this turn's table have run
-        char* h = R.host + (size_t)t * DspRing::kTurnBytes;
-        char* dt = R.dev.as<char>() + (size_t)t * DspRing::kTurnBytes;
-        std::memcpy(h + RingAck::kHead, rows.data() + at, (size_t)n * sizeof(DspRow));
-        R.ack.upload(t, h, dt, (size_t)n * sizeof(DspRow), s);
-        launch_dsp(reinterpret_cast<const DspRow*>(dt + RingAck::kHead), n, (int)max_tiles, any_norm, any_dc, scan, s, any_loud, &loud, apply);
-        R.ack.done(t, dt, s);
+        launch_dsp(m.dsp_ring.stage(rows.data() + at, n, s), n, (int)max_tiles, p, s);
+        m.dsp_ring.done(s);
     }
 }
 
@@ -121,11 +103,11 @@ void loudness_rows_device(Model& m, const float* const* in, const int64_t* n, in
     dsp_launch(m, jobs, s, out != nullptr);
     for (size_t k = 0; k < jobs.size(); k++) {
         const int i = job_row[k];
-        const size_t F = (size_t)((n[i] + kDspTile - 1) / kDspTile);
+        const int64_t F = scan_tiles(n[i]);
         if (M) PTTS_HIP(hipMemcpyAsync(M + i, jobs[k].loud_out, sizeof(double), hipMemcpyDeviceToHost, s));
         if (sub) {
-            sub[i].resize(F * kLoudSubsPerTile);
-            PTTS_HIP(hipMemcpyAsync(sub[i].data(), jobs[k].loud_out + 2 + F * 8, F * kLoudSubsPerTile * sizeof(double), hipMemcpyDeviceToHost, s));
+            sub[i].resize((size_t)F * kLoudSubsPerTile);
+            PTTS_HIP(hipMemcpyAsync(sub[i].data(), loud_subs(jobs[k].loud_out, F), sub[i].size() * sizeof(double), hipMemcpyDeviceToHost, s));
         }
         if (out) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
     }

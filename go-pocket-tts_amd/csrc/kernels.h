@@ -281,34 +281,31 @@ extern std::atomic<int64_t> g_resample_launches;
 
 // Post-processing of decoded 24 kHz audio in place (dsp.hip): ptts_dsp_apply's chain -- peak normalise, DC block,
 // fade in, fade out -- on a table of ragged rows.  k_dsp_peak (normalise rows: max |x| as the uint32 image, atomicMax), k_dsp_summary +
-// k_dsp_carry (DC rows: the zero-state end state of every full tile, then the state entering each tile in tile order; dsp_block.h) and
+// k_dsp_carry (DC rows: the zero-state end state of every full tile, then the state entering each tile in tile order; scan_block.h) and
 // k_dsp_apply (gain, the recurrence of every run from its entering state, the fade gains, one store).  Tiles are kDspTile samples on the
 // row's own grid, so a row's bits do not depend on the rows beside it.
-// Loudness rows (DSP_LOUD; loudness.hip, loudness_block.h): k_dsp_peak as for normalise, then k_loud_summary + k_loud_carry (the K-weighting
-// cascade's four states per tile, as the DC block's two), k_loud_energy (each tile's four sub-block energies) and k_loud_gate (block energies,
-// both gates, the mean square M and the row's f32 gain with the 1 / peak ceiling) on the RAW samples; k_dsp_summary and k_dsp_apply then take the
-// row's gain from that word where normalise's gain sits.  Tables without such a row launch the kernels they launched before it existed.
+// Loudness rows (DSP_LOUD): k_dsp_peak as for normalise, then k_loud_summary + k_loud_carry (the K-weighting cascade's four states per tile,
+// as the DC block's two), k_loud_energy (each tile's four sub-block energies) and k_loud_gate (block energies, both gates, the mean square M
+// and the row's f32 gain with the 1 / peak ceiling) on the RAW samples; k_dsp_summary and k_dsp_apply then take the row's gain from that word
+// where normalise's gain sits.  Tables without such a row launch the kernels they launched before it existed.
 enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4 };
 struct DspRow {
     float* x;              // the row's samples (device), rewritten in place
     int64_t n;             // samples; nothing at or beyond n is touched
     int64_t fade_in, fade_out;   // samples of each fade (0: none, <= n)
     uint32_t* peak;        // normalise and loudness rows: one word, zero before k_dsp_peak
-    double* tiles;         // DC rows: [ceil(n / kDspTile)][4] = E_f (2), S_f (2)
+    double* tiles;         // DC rows: the DC block's per-tile states (scan_block.h scan_E / scan_S)
     int32_t flags, pad;
-    // loudness rows: [0] the gated mean square M (0: nothing above the gates), [1] the f32 gain in its first four bytes, then
-    // [F = ceil(n / kDspTile)][8] = E_f (4), S_f (4), then [4 F] sub-block energies
-    double* loud;
+    double* loud;          // loudness rows: M, the gain, the K-weighting's per-tile states, the sub-block energies (scan_block.h loud_states / loud_subs)
     double target;         // 10^((target LUFS + 0.691) / 10)
 };
 struct DspScan;
 struct LoudScan;
-// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; any_norm / any_dc / any_loud: whether a row has the
-// flag (loud: the scan of the K-weighting, needed with any_loud); apply false: the measuring launches only, the samples stay as they are
-void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, bool any_norm, bool any_dc, const DspScan& scan, hipStream_t stream,
-                bool any_loud = false, const LoudScan* loud = nullptr, bool apply = true);
-// the four loudness launches for the table's DSP_LOUD rows (behind k_dsp_peak, in front of every kernel that reads a gain)
-void launch_loudness(const DspRow* rows_dev, int n, int max_tiles, const LoudScan& scan, hipStream_t stream);
+// which flags occur in a table's rows, and the systems' coefficients (loud: needed with any_loud); apply false: the measuring launches only,
+// the samples stay as they are
+struct DspLaunch { bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; };
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
+void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

@@ -1,10 +1,10 @@
 // loudness.cpp -- integrated loudness after ITU-R BS.1770-4 (mono, the decoder's 24 kHz) and the gain to a target, on the host: ptts_loudness
-// and ptts_loudness_normalize.  The host function is the blocked evaluation of loudness_block.h itself -- the functions loudness.hip's kernels
+// and ptts_loudness_normalize.  The host function is the blocked evaluation of scan_block.h itself -- the functions dsp.hip's k_loud_* kernels
 // call, instantiated for the host, in the order the kernels run them -- so a request's `loudness`, ptts_loudness_rows and
 // ptts_loudness_normalize_rows give these bits.  DESIGN.md section 8 (N3).
 #include <cmath>
 
-#include "loudness_block.h"
+#include "scan_block.h"
 #include "runtime.h"
 
 namespace ptts {
@@ -33,7 +33,7 @@ void loud_kweight_coeffs(int sample_rate, double out[10]) {
 }
 
 // the cascade's state matrix over (shelf z1, shelf z2, high-pass z1, high-pass z2) -- with x = 0: u = z1, y = c0 u + z3 -- and its powers
-// A^kDspRun, A^kDspTile by repeated multiplication
+// A^kDspRun, A^kDspTile
 LoudScan loud_scan_coeffs(int sample_rate) {
     LoudScan sc;
     sc.s1 = k_shelf((double)sample_rate);
@@ -43,20 +43,7 @@ LoudScan loud_scan_coeffs(int sample_rate) {
                           -a.a2, 0.0, 0.0, 0.0,
                           b.b1 - b.a1 * b.b0, 0.0, -b.a1, 1.0,
                           b.b2 - b.a2 * b.b0, 0.0, -b.a2, 0.0};
-    double P[16];
-    for (int i = 0; i < 16; i++) P[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int k = 1; k <= kDspTile; k++) {
-        double Q[16];
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) {
-                double v = 0.0;
-                for (int m = 0; m < 4; m++) v += A[4 * i + m] * P[4 * m + j];
-                Q[4 * i + j] = v;
-            }
-        for (int j = 0; j < 16; j++) P[j] = Q[j];
-        if (k == kDspRun) for (int j = 0; j < 16; j++) sc.a_run[j] = P[j];
-    }
-    for (int j = 0; j < 16; j++) sc.a_tile[j] = P[j];
+    scan_powers<4>(A, sc.a_run, sc.a_tile);
     sc.abs_gate = std::pow(10.0, (-70.0 + 0.691) / 10.0);
     return sc;
 }
@@ -77,30 +64,10 @@ std::string loud_target_error(double target_lufs) {
 // what k_loud_summary, k_loud_carry and k_loud_energy compute for one row: 4 sub-block energies per tile
 void loud_sub_energies(const float* x, int64_t n, std::vector<double>& sub) {
     const LoudScan& sc = loud_scan();
-    const int64_t F = (n + kDspTile - 1) / kDspTile;
-    sub.assign((size_t)F * kLoudSubsPerTile, 0.0);
-    double S[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t f = 0; f < F; f++) {
-        const int64_t base = f * kDspTile;
-        const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
-        const float* tile = x + base;
-        double e[kDspLanes][4], q[kDspLanes];
-        for (int l = 0; l < kDspLanes; l++) {
-            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
-            for (int i = 0; i < 4; i++) e[l][i] = 0.0;
-            (void)loud_run(sc, tile + l * kDspRun, c, e[l]);
-        }
-        double E[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {S[0], S[1], S[2], S[3]};
-        for (int l = 0; l < kDspLanes; l++) {
-            const int c = std::max(0, std::min(kDspRun, cnt - l * kDspRun));
-            double z[4] = {t[0], t[1], t[2], t[3]};
-            q[l] = loud_run(sc, tile + l * kDspRun, c, z);
-            loud_advance(sc.a_run, t, e[l]);
-            loud_advance(sc.a_run, E, e[l]);
-        }
-        for (int k = 0; k < kLoudSubsPerTile; k++) sub[(size_t)f * kLoudSubsPerTile + (size_t)k] = loud_sub_energy(q + k * kLoudRunsPerSub);
-        loud_advance(sc.a_tile, S, E);
-    }
+    std::vector<double> q((size_t)scan_tiles(n) * kDspLanes, 0.0);   // every run's sum of squares
+    scan_walk(sc, x, n, [&](int64_t i0, int count, double* z) { q[(size_t)(i0 / kDspRun)] = sc.run(x + i0, count, z); });
+    sub.resize(q.size() / kLoudRunsPerSub);
+    for (size_t k = 0; k < sub.size(); k++) sub[k] = loud_sub_energy(q.data() + k * kLoudRunsPerSub);
 }
 
 // what k_loud_gate computes: the doubly gated mean square of the row's whole 400 ms blocks; 0: no block above the gates

@@ -6,9 +6,7 @@
 // computed in float64 and rounded once to f32 (no per-phase normalisation).  Output j sits at input position j M / L; it sums
 // x[i] h(j M / L - i) over the i with |j M / L - i| < W in ascending i.  W = 80 / (3 rho) = 80 max(L, M) / (3 L), so with A = 80 max(L, M)
 // the support test |p / L - d| < W is the exact integer test 3 |p - d L| < A.
-#include <chrono>
 #include <numeric>
-#include <thread>
 
 #include "runtime.h"
 
@@ -135,48 +133,8 @@ RateFilter::~RateFilter() {
     if (staged) (void)hipHostFree(staged);
 }
 
-ResampleRing::~ResampleRing() {
-    if (host) (void)hipHostFree(host);
-}
-
-RingAck::~RingAck() {
-    if (back) (void)hipHostFree(back);
-}
-
-void RingAck::wait(int t) {
-    if (!expect[t]) return;
-    const volatile uint64_t* p = back + t;
-    if (*p == expect[t]) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spins = 0; *p != expect[t]; spins++) {
-        if (spins < 256) continue;
-        std::this_thread::yield();
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60))
-            throw Error(PTTS_ENODEVICE, "ptts-hip: a row table's launches did not finish within 60 s");
-    }
-}
-
-void RingAck::upload(int t, char* host_turn, char* dev_turn, size_t row_bytes, hipStream_t s) {
-    if (!back) {
-        PTTS_HIP(hipHostMalloc((void**)&back, sizeof(uint64_t) * kRing, hipHostMallocDefault));
-        std::memset(back, 0, sizeof(uint64_t) * kRing);
-    }
-    expect[t] = ++seq;
-    std::memcpy(host_turn, &expect[t], sizeof(uint64_t));
-    PTTS_HIP(hipMemcpyAsync(dev_turn, host_turn, kHead + row_bytes, hipMemcpyHostToDevice, s));
-}
-
-void RingAck::done(int t, const char* dev_turn, hipStream_t s) {
-    PTTS_HIP(hipMemcpyAsync(back + t, dev_turn, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-}
-
 void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t s) {
-    ResampleRing& R = m.rs_ring;
-    constexpr int kRows = ResampleRing::kRows;
-    if (!R.host) {
-        PTTS_HIP(hipHostMalloc((void**)&R.host, ResampleRing::kTurnBytes * ResampleRing::kRing, hipHostMallocDefault));
-        R.dev.ensure(ResampleRing::kTurnBytes * ResampleRing::kRing);
-    }
+    constexpr int kRows = RowRing<ResampleRow>::kRows;
     for (size_t at = 0; at < rows.size(); at += kRows) {
         const int n = (int)std::min<size_t>(kRows, rows.size() - at);
         int64_t tiles = 0;
@@ -192,15 +150,8 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
         }
         if (tiles == 0) continue;
         if (tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: resample: too many samples for one launch");
-        const int t = R.turn;
-        R.turn = (t + 1) % ResampleRing::kRing;
-        R.ack.wait(t);   // the launch that last read this turn's table has run
-        char* h = R.host + (size_t)t * ResampleRing::kTurnBytes;
-        char* d = R.dev.as<char>() + (size_t)t * ResampleRing::kTurnBytes;
-        std::memcpy(h + RingAck::kHead, rows.data() + at, (size_t)n * sizeof(ResampleRow));
-        R.ack.upload(t, h, d, (size_t)n * sizeof(ResampleRow), s);
-        launch_resample(reinterpret_cast<const ResampleRow*>(d + RingAck::kHead), n, (int)tiles, lds, s);
-        R.ack.done(t, d, s);
+        launch_resample(m.rs_ring.stage(rows.data() + at, n, s), n, (int)tiles, lds, s);
+        m.rs_ring.done(s);
     }
 }
 

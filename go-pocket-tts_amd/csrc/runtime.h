@@ -7,6 +7,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "row_ring.h"
 
 namespace ptts {
 
@@ -54,52 +55,6 @@ struct RateFilter {
     RateFilter& operator=(const RateFilter&) = delete;
     ~RateFilter();
 };
-// When a turn of a row-table ring may be reused, without an event: a turn's upload carries a sequence number in front of its rows, a small
-// copy queued behind the turn's launches hands the number back into page-locked memory, and the host waits for it there.  (The rings waited
-// on lazily created events with hipEventSynchronize before; that call was seen to fail now and then with a stream-capture error -- "stream is
-// capturing", "event last recorded in a capturing stream" -- on events that were never recorded into a capture.  This wait has no such state.)
-struct RingAck {
-    static constexpr int kRing = 8, kHead = 16;   // bytes in front of a turn's rows: the number, padded so that the rows stay 16-byte aligned
-    uint64_t* back = nullptr;                     // page-locked [kRing]: what turn t last handed back
-    uint64_t expect[kRing] = {};                  // ... and what its last launches will hand back (0: never used)
-    uint64_t seq = 0;
-    RingAck() = default;
-    RingAck(const RingAck&) = delete;
-    RingAck& operator=(const RingAck&) = delete;
-    ~RingAck();
-    void wait(int t);                                             // until turn t's last launches have run (throws PTTS_ENODEVICE after 60 s)
-    // host_turn / dev_turn: the turn's blocks of kHead + row_bytes bytes; stamps the number, queues the upload of head and rows on s
-    void upload(int t, char* host_turn, char* dev_turn, size_t row_bytes, hipStream_t s);
-    void done(int t, const char* dev_turn, hipStream_t s);        // behind the turn's launches on s
-};
-// page-locked staging and device copies of k_resample's row tables: kRing turns of kRows rows, a turn reused once its launch has run
-struct ResampleRing {
-    static constexpr int kRing = RingAck::kRing, kRows = 256;
-    static constexpr size_t kTurnBytes = RingAck::kHead + sizeof(ResampleRow) * kRows;
-    char* host = nullptr;
-    DevBuf dev;
-    RingAck ack;
-    int turn = 0;
-    ResampleRing() = default;
-    ResampleRing(const ResampleRing&) = delete;
-    ResampleRing& operator=(const ResampleRing&) = delete;
-    ~ResampleRing();
-};
-
-// page-locked staging and device copies of the DSP kernels' row tables (dsp_device.cpp), as ResampleRing
-struct DspRing {
-    static constexpr int kRing = RingAck::kRing, kRows = 256;
-    static constexpr size_t kTurnBytes = RingAck::kHead + sizeof(DspRow) * kRows;
-    char* host = nullptr;
-    DevBuf dev;
-    RingAck ack;
-    int turn = 0;
-    DspRing() = default;
-    DspRing(const DspRing&) = delete;
-    DspRing& operator=(const DspRing&) = delete;
-    ~DspRing();
-};
-
 struct Prof {   // bench.py measurement hook (ptts_profile_*)
     bool on = false;
     std::vector<hipEvent_t> ev;
@@ -132,8 +87,8 @@ struct Model {
     std::unique_ptr<Batch> cached_batch;
     Prof prof;
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
-    ResampleRing rs_ring;
-    DspRing dsp_ring;
+    RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
+    RowRing<DspRow> dsp_ring;       // the DSP kernels' (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
     // re-issued as the 2 x depth launches (same bits) -- fc_fallbacks counts the events -- and this engine's batches keep the launches from then on
@@ -357,7 +312,7 @@ int64_t resample_length(int64_t n_in, int in_rate, int out_rate);           // c
 const RateFilter* rate_filter(Model& m, int in_rate, int out_rate, hipStream_t s);
 int64_t resample_ready(const RateFilter* f, int64_t n_dec);                  // outputs whose filter support lies inside the first n_dec inputs
 ResampleRow resample_row(const RateFilter* f, const float* src, int64_t n_in, void* dst, int64_t o0, int64_t o1, int fmt);
-void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t s);   // one k_resample launch per ResampleRing::kRows rows
+void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t s);   // one k_resample launch per RowRing::kRows rows
 // a request's egress: its rate (0 -> 24000), whether it needs k_resample (another rate, or G.711), the bytes per sample of its format, and
 // its result buffer (pcm / pcm16 / pcm8 by format)
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
@@ -365,7 +320,7 @@ inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample
 // (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
 inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0); }
 std::string dsp_opts_error(const ptts_dsp_opts& o);
-// loud: the row is measured (BS.1770, loudness.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
+// loud: the row is measured (BS.1770, dsp.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
 // dsp_launch sets loud_out to the row's two device words (the mean square M as a double, then the f32 gain), valid until the model's next
 // DSP launch.  opts may be NULL for a loudness row.
 struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; };
@@ -443,10 +398,10 @@ void dsp_dc_block(float* s, int64_t n, int sample_rate);
 void dsp_fade_in(float* s, int64_t n, int sample_rate, double ms);
 void dsp_fade_out(float* s, int64_t n, int sample_rate, double ms);
 struct DspScan;
-DspScan dsp_scan_coeffs(int sample_rate);                          // the DC block's section and the powers of its state matrix (dsp_block.h)
+DspScan dsp_scan_coeffs(int sample_rate);                          // the DC block's section and the powers of its state matrix (scan_block.h)
 void dsp_dc_block_blocked(float* s, int64_t n, int sample_rate);   // dsp_dc_block in the device's blocked form, on the host
 
-// integrated loudness, ITU-R BS.1770-4 mono at 24 kHz (loudness.cpp; loudness_block.h is the arithmetic, shared with loudness.hip)
+// integrated loudness, ITU-R BS.1770-4 mono at 24 kHz (loudness.cpp; scan_block.h is the arithmetic, shared with dsp.hip)
 struct LoudScan;
 void loud_kweight_coeffs(int sample_rate, double out[10]);         // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
 LoudScan loud_scan_coeffs(int sample_rate);

@@ -90,12 +90,12 @@ int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap);
  * continuous engine converts on the dispatcher's worker threads); reset != 0: returns the count and sets it to 0 */
 int64_t ptts_debug_resample_launches(int32_t reset);
 
-/* The DC block of ptts_dsp_apply in the blocked form the device kernels run (csrc/dsp_block.h: runs of 30 samples from zero state, their end
+/* The DC block of ptts_dsp_apply in the blocked form the device kernels run (csrc/scan_block.h: runs of 30 samples from zero state, their end
  * states folded in run order, the frame tiles' states carried in frame order), evaluated on the host by the host instantiation of the very
  * functions the kernels call: n samples at 24 kHz, in -> out (in == out allowed).  No GPU. */
 int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out);
 
-/* Loudness (ptts_loudness; csrc/loudness_block.h): the energies of the rows' whole 480-sample sub-blocks -- out[i] receives n[i] / 480 doubles, the
+/* Loudness (ptts_loudness; csrc/scan_block.h): the energies of the rows' whole 480-sample sub-blocks -- out[i] receives n[i] / 480 doubles, the
  * sums of squares of the K-weighted samples -- as the device kernels of a request's `loudness` compute them (m != NULL), or by the host
  * instantiation of the functions those kernels call (m == NULL, no GPU).  Twenty of them in order, over 9600, are one 400 ms block. */
 int ptts_debug_loudness_energies(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double* const* out);

@@ -5,7 +5,7 @@ import math
 import numpy as np
 
 RATE = 24000
-LENGTHS = [1, 29, 1919, 1920, 1921, 48000, 240000]
+LENGTHS = [1, 29, 1919, 1920, 1921, 48000, 122880, 122881, 240000]   # 122880 = 64 tiles: one chunk of the carry kernel, then one tile over it
 
 
 def signal(n, seed=0, offset=0.3):

@@ -1,5 +1,5 @@
 """ITU-R BS.1770-4 integrated loudness (mono), restated sequentially in float64 numpy: the yardstick of ptts_loudness and of the device kernels
-(go-pocket-tts_amd/csrc/loudness_block.h, loudness.hip).  K-weighting by the bilinear forms that reproduce the standard's
+(go-pocket-tts_amd/csrc/scan_block.h, dsp.hip).  K-weighting by the bilinear forms that reproduce the standard's
 48 kHz table, evaluated for the sample rate; 400 ms blocks every 100 ms; the gates in the logarithmic domain, as the standard words them."""
 import math
 

@@ -1,4 +1,4 @@
-"""CPU-side checks of the device post-processing (go-pocket-tts_amd/csrc/dsp.hip, dsp_block.h): the numpy restatement the GPU
+"""CPU-side checks of the device post-processing (go-pocket-tts_amd/csrc/dsp.hip, scan_block.h): the numpy restatement the GPU
 tests use is tied to ptts_dsp_apply; the blocked form of the DC block -- the host instantiation of the functions the kernels call -- agrees with the
 sequential recurrence to one f32 step; ptts_request kept its size and `dsp` sits where reserved2 sat."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Loudness normalisation on the GPU (go-pocket-tts_amd/csrc/loudness.hip, loudness_block.h): the device computes the bits of
+"""Loudness normalisation on the GPU (go-pocket-tts_amd/csrc/dsp.hip, scan_block.h): the device computes the bits of
 the host's blocked BS.1770 evaluation -- sub-block energies, loudness, gain and normalised samples -- whatever rows share the launch; a request's
 `loudness` is ptts_loudness_normalize of that request's own 24 kHz audio, in front of `dsp` and the egress; requests without it run what they ran
 before."""
@@ -13,7 +13,7 @@ import test_gpu_dsp as TD   # the egress relations and their bounds (_check_dc, 
 
 pytestmark = pytest.mark.gpu
 
-LENGTHS = [0, 1, 479, 480, 1920, 1921, 9599, 9600, 9601, 240000, 487680]
+LENGTHS = [0, 1, 479, 480, 1920, 1921, 9599, 9600, 9601, 122880, 122881, 240000, 487680]   # 122880 = 64 tiles: one chunk of the carry kernel
 FILL = [100 + 997 * i for i in range(64)]        # the 64 other rows of a shared launch: ragged, 100 .. 62911 samples
 DC_FADES = dict(dc_block=True, fade_in_ms=50.0, fade_out_ms=80.0)
 STEPS = [7, 3, 9, 6, 12, 5]                       # frames of 1920 samples: 3 is under one 400 ms block (gain 1), the others are measured

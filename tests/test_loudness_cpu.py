@@ -1,4 +1,4 @@
-"""CPU-side checks of the loudness normalisation (go-pocket-tts_amd/csrc/loudness.cpp, loudness_block.h): ptts_loudness --
+"""CPU-side checks of the loudness normalisation (go-pocket-tts_amd/csrc/loudness.cpp, scan_block.h): ptts_loudness --
 the blocked float64 evaluation the device kernels run, instantiated for the host -- against the sequential BS.1770-4 restatement of _loudness_ref.py;
 the K-weighting coefficients against the standard's 48 kHz table; the rows that stay as they are; ptts_request kept its size and `loudness` sits
 where reserved[1] sat."""

@@ -1,4 +1,4 @@
-"""Loudness normalisation on the device (loudness.hip) on the headline workload: 64 x 10 s, bf16, graph step, one device voice.
+"""Loudness normalisation on the device (dsp.hip) on the headline workload: 64 x 10 s, bf16, graph step, one device voice.
 Legs, run interleaved in one process, whole-call median of --runs rounds after --warmup: (a) no post-processing; (b) `loudness` at -16 LUFS, native
 f32; (c) `loudness` at -16 LUFS as 8 kHz mu-law; (d) leg (a) followed by ptts_loudness_normalize on the host over the 64 results, one thread -- what the
 device launches replace; and ptts_loudness_normalize_rows on 64 x 10 s host rows.  Writes profiles/loudness_bench.json (PTTS_OUT_DIR: elsewhere).
