@@ -5,6 +5,7 @@
 #include "runtime.h"
 
 #include "capi_internal.h"
+#include "eq.h"
 
 using namespace ptts;
 using namespace ptts::capi;
@@ -1111,6 +1112,43 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
         dsp_launch(m, jobs, s);
         for (int i = 0; i < rows; i++)
             if (n[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
+        PTTS_HIP(hipStreamSynchronize(s));
+    });
+}
+
+// the device form of ptts_eq_apply on host rows: upload (rows packed 256-byte aligned), the launches of a request's `eq`, download
+int ptts_eq_rows(ptts_model* h, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        if (rows < 0 || (rows > 0 && (!eq || !in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: eq: null argument");
+        std::vector<const EqScan*> sys((size_t)rows, nullptr);
+        for (int i = 0; i < rows; i++) {
+            if (n[i] < 0 || (n[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d is negative or null", i));
+            if (eq[i] && !(sys[(size_t)i] = eq_lookup(eq[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d: the handle is not a live equaliser of ptts_eq_create", i));
+        }
+        Model& m = *h->m;
+        std::lock_guard<std::mutex> lock(m.mu);
+        m.use_device();
+        hipStream_t s = m.stream;
+        std::vector<size_t> off((size_t)rows);
+        size_t bytes = 0;
+        for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; if (sys[(size_t)i]) bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
+        char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
+        std::vector<DspJob> jobs;
+        for (int i = 0; i < rows; i++) {
+            if (n[i] <= 0) continue;
+            if (!sys[(size_t)i]) {   // no equaliser: a copy
+                if (out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+                continue;
+            }
+            PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
+            DspJob j{(float*)(buf + off[(size_t)i]), n[i], nullptr};
+            j.eq = sys[(size_t)i];
+            jobs.push_back(j);
+        }
+        dsp_launch(m, jobs, s);
+        for (int i = 0; i < rows; i++)
+            if (n[i] > 0 && sys[(size_t)i]) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
         PTTS_HIP(hipStreamSynchronize(s));
     });
 }

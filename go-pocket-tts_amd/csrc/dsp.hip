@@ -14,14 +14,19 @@
 //                   energies (16 run sums each, in run order) as doubles.
 //   k_loud_gate     one workgroup per row: block energies (20 sub-blocks in order, over 9600; lanes take a block each), the absolute and the
 //                   relative gate and the means in block order by lane 0, M and the f32 gain min((float)sqrt(T / M), 1 / peak).
+//   k_eq_summary, k_eq_carry, k_eq_apply   equaliser rows (DSP_EQ), behind k_dsp_apply on what it stored: the same three steps for the row's own
+//                   cascade (EqSys<S>, N = 2 S states, the coefficients read from the table's equalisers behind its rows), then the two fade
+//                   gains, which k_dsp_apply leaves to k_eq_apply for such a row.  The fold s <- A^30 s + e_l is N independent sums, each in its
+//                   fixed order: lane i < N computes component i (lanes_advance), the other components reach it by v_readlane.  The bits are
+//                   scan_advance's; the serial chain is one sum long, not N.
 // k_dsp_* are the DC block's (DspScan, DSP_DC rows, on the f32 product x * gain wherever it is read), k_loud_* the K-weighting's (LoudScan,
 // DSP_LOUD rows, on the RAW samples: nothing is written to them, k_dsp_apply applies the gain).  Stream order has the peak complete before
 // k_loud_gate and k_dsp_summary start, and the loudness gain before k_dsp_summary.  One wave per workgroup and at most 12.5 KB of LDS: a CU
 // holds a dozen workgroups, the passes are reads of the rows at HBM rate.  Tiles lie on the row's own grid and every sum has one order: a
 // row's bits are a function of the row alone, and they are the bits of the host instantiations (dsp.cpp, loudness.cpp).  Nothing at or beyond
 // n is read or written.
-// k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row, so a table without one launches the instantiation
-// that does not know the flag: the code it ran before the flag existed.
+// k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row (k_dsp_apply: and an equaliser row), so a table without
+// one launches the instantiation that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
 #include "scan_block.h"
 
@@ -184,31 +189,12 @@ __global__ __launch_bounds__(kDspLanes) void k_loud_carry(const DspRow* __restri
     if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud));
 }
 
-template <bool LOUD>
-__global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restrict__ rows, const DspScan sc) {
-    __shared__ float4 tile4[kDspTile / 4];
-    float* tile = reinterpret_cast<float*>(tile4);
-    const DspRow& r = rows[blockIdx.y];
-    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
-    if (base >= n) return;
-    const int cnt = (int)min((int64_t)kDspTile, n - base);
-    const Gain g = row_gain<LOUD>(r);
-    const bool dc = (r.flags & DSP_DC) != 0;
-    const int64_t fin = r.fade_in, fout0 = n - r.fade_out;   // fade in below fin, fade out from fout0 on
-    if (!g.on && !dc && base >= fin && base + cnt <= fout0) return;   // a tile that no step changes
-    load_tile(r, base, cnt, tile, g);
-    __syncthreads();
-    if (dc) {
-        float* run = tile + threadIdx.x * kDspRun;
-        const int c = run_count(cnt);
-        double z[DspScan::N];
-        scan_enter(sc, run, c, r.tiles, z);
-        sc.run(run, c, z, run);
-        __syncthreads();
-    }
+// tile[0, cnt) -- samples [base, base + cnt) of the row -- times the two fade gains, into the row
+__device__ __forceinline__ void store_tile(const DspRow& r, int64_t base, int cnt, const float* tile, int64_t fin, int64_t fade_out) {
+    const int64_t n = r.n, fout0 = n - fade_out;
     float* dst = r.x + base;
     const bool vec = ((uintptr_t)dst & 15) == 0;
-    const float fin_f = (float)fin, fout_f = (float)r.fade_out;
+    const float fin_f = (float)fin, fout_f = (float)fade_out;
     for (int q = threadIdx.x * 4; q < cnt; q += kDspLanes * 4) {
         float v[4];
         const int nv = min(4, cnt - q);
@@ -222,6 +208,178 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
         if (vec && nv == 4) *reinterpret_cast<float4*>(dst + q) = make_float4(v[0], v[1], v[2], v[3]);
         else for (int u = 0; u < nv; u++) dst[q + u] = v[u];
     }
+}
+
+// EQ: the table has an equaliser row; such a row's fades are k_eq_apply's, behind its filter
+template <bool LOUD, bool EQ>
+__global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restrict__ rows, const DspScan sc) {
+    __shared__ float4 tile4[kDspTile / 4];
+    float* tile = reinterpret_cast<float*>(tile4);
+    const DspRow& r = rows[blockIdx.y];
+    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    if (base >= n) return;
+    const int cnt = (int)min((int64_t)kDspTile, n - base);
+    const Gain g = row_gain<LOUD>(r);
+    const bool dc = (r.flags & DSP_DC) != 0;
+    const bool fades = !(EQ && (r.flags & DSP_EQ));
+    const int64_t fin = fades ? r.fade_in : 0, fade_out = fades ? r.fade_out : 0, fout0 = n - fade_out;   // fade in below fin, fade out from fout0 on
+    if (!g.on && !dc && base >= fin && base + cnt <= fout0) return;   // a tile that no step changes
+    load_tile(r, base, cnt, tile, g);
+    __syncthreads();
+    if (dc) {
+        float* run = tile + threadIdx.x * kDspRun;
+        const int c = run_count(cnt);
+        double z[DspScan::N];
+        scan_enter(sc, run, c, r.tiles, z);
+        sc.run(run, c, z, run);
+        __syncthreads();
+    }
+    store_tile(r, base, cnt, tile, fin, fade_out);
+}
+
+// ---- equaliser rows ----
+
+__device__ __forceinline__ double lane_bcast(double v, int lane) {   // lane's v in every lane (lane: the same in all of them)
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// scan_advance, a component per lane: s <- P s + e with s_i, e_i and row i of P in lane i (i < N; the lanes behind repeat lane N - 1).  Sum i is
+// scan_advance's sum i, product by product.  All 64 lanes call it together.
+template <int N>
+__device__ __forceinline__ double lanes_advance(const double (&prow)[N], double si, double ei) {
+#pragma clang fp contract(off)
+    double v = prow[0] * lane_bcast(si, 0);
+#pragma unroll
+    for (int m = 1; m < N; m++) v = v + prow[m] * lane_bcast(si, m);
+    return v + ei;
+}
+
+// tile blockIdx.x of an equaliser row, which hands a state on (the tile is in LDS): E_f into the row's per-tile states.  e: [kDspLanes][N]
+template <class Sys>
+__device__ __forceinline__ void eq_summary(const Sys sc, const DspRow& r, const float* tile, double* e) {
+    constexpr int N = Sys::N;
+    const int l = threadIdx.x, i = min(l, N - 1);
+    double z[N] = {};
+    sc.run(tile + l * kDspRun, kDspRun, z);
+#pragma unroll
+    for (int k = 0; k < N; k++) e[l * N + k] = z[k];
+    __syncthreads();
+    double prow[N];
+#pragma unroll
+    for (int m = 0; m < N; m++) prow[m] = sc.a_run[N * i + m];
+    double s = 0.0;
+    for (int j = 0; j < kDspLanes; j++) s = lanes_advance<N>(prow, s, e[j * N + i]);
+    if (l < N) scan_E<N>(r.eq_tiles, blockIdx.x)[l] = s;
+}
+
+// an equaliser row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time.  ein: [kDspLanes][N]
+template <class Sys>
+__device__ __forceinline__ void eq_carry(const Sys sc, int64_t F, double* states, double* ein) {
+    constexpr int N = Sys::N;
+    const int l = threadIdx.x, i = min(l, N - 1);
+    double prow[N];
+#pragma unroll
+    for (int m = 0; m < N; m++) prow[m] = sc.a_tile[N * i + m];
+    double s = 0.0;   // component i of the state entering tile c0 + j
+    for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
+        const int64_t f = c0 + l;
+        if (f < F - 1) {
+#pragma unroll
+            for (int k = 0; k < N; k++) ein[l * N + k] = scan_E<N>(states, f)[k];
+        }
+        __syncthreads();
+        const int m = (int)min((int64_t)kDspLanes, F - c0);
+        for (int j = 0; j < m; j++) {
+            if (l < N) scan_S<N>(states, c0 + j)[l] = s;
+            if (c0 + j < F - 1) s = lanes_advance<N>(prow, s, ein[j * N + i]);
+        }
+        __syncthreads();
+    }
+}
+
+// the lane's run (c samples at `run`, in LDS) of tile blockIdx.x of an equaliser row, filtered in place from its entering state: every run from
+// zero state, the fold in run order from S_f (t_l takes e_l's place in et: [kDspLanes][N]), the run again
+template <class Sys>
+__device__ __forceinline__ void eq_filter(const Sys sc, const DspRow& r, float* run, int c, double* et) {
+    constexpr int N = Sys::N;
+    const int l = threadIdx.x, i = min(l, N - 1);
+    double z[N] = {};
+    sc.run(run, c, z);
+#pragma unroll
+    for (int k = 0; k < N; k++) et[l * N + k] = z[k];
+    __syncthreads();
+    double prow[N];
+#pragma unroll
+    for (int m = 0; m < N; m++) prow[m] = sc.a_run[N * i + m];
+    double s = scan_S<N>(r.eq_tiles, blockIdx.x)[i];
+    for (int j = 0; j < kDspLanes; j++) {
+        double ej = 0.0;
+        if (l < N) { ej = et[j * N + l]; et[j * N + l] = s; }
+        s = lanes_advance<N>(prow, s, ej);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) z[k] = et[l * N + k];
+    sc.run(run, c, z, run);
+    __syncthreads();
+}
+
+constexpr int kEqStates = 2 * kEqMaxSections;
+
+__global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
+    __shared__ float4 tile4[kDspTile / 4];
+    __shared__ double e[kDspLanes * kEqStates];
+    const DspRow& r = rows[blockIdx.y];
+    if (!(r.flags & DSP_EQ) || !tile_hands_on(r)) return;
+    float* tile = reinterpret_cast<float*>(tile4);
+    load_tile(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile, kNoGain);
+    __syncthreads();
+    const EqScan& q = eqs[r.eq];
+    switch (q.S) {
+        case 1: eq_summary(EqSys<1>(q), r, tile, e); break;
+        case 2: eq_summary(EqSys<2>(q), r, tile, e); break;
+        case 3: eq_summary(EqSys<3>(q), r, tile, e); break;
+        case 4: eq_summary(EqSys<4>(q), r, tile, e); break;
+        default: break;
+    }
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_eq_carry(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
+    __shared__ double ein[kDspLanes * kEqStates];
+    const DspRow& r = rows[blockIdx.x];
+    if (!(r.flags & DSP_EQ) || r.n <= 0) return;
+    const EqScan& q = eqs[r.eq];
+    const int64_t F = scan_tiles(r.n);
+    switch (q.S) {
+        case 1: eq_carry(EqSys<1>(q), F, r.eq_tiles, ein); break;
+        case 2: eq_carry(EqSys<2>(q), F, r.eq_tiles, ein); break;
+        case 3: eq_carry(EqSys<3>(q), F, r.eq_tiles, ein); break;
+        case 4: eq_carry(EqSys<4>(q), F, r.eq_tiles, ein); break;
+        default: break;
+    }
+}
+
+__global__ __launch_bounds__(kDspLanes) void k_eq_apply(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
+    __shared__ float4 tile4[kDspTile / 4];
+    __shared__ double et[kDspLanes * kEqStates];
+    const DspRow& r = rows[blockIdx.y];
+    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    if (!(r.flags & DSP_EQ) || base >= n) return;
+    float* tile = reinterpret_cast<float*>(tile4);
+    const int cnt = (int)min((int64_t)kDspTile, n - base);
+    load_tile(r, base, cnt, tile, kNoGain);
+    __syncthreads();
+    float* run = tile + threadIdx.x * kDspRun;
+    const int c = run_count(cnt);
+    const EqScan& q = eqs[r.eq];
+    switch (q.S) {
+        case 1: eq_filter(EqSys<1>(q), r, run, c, et); break;
+        case 2: eq_filter(EqSys<2>(q), r, run, c, et); break;
+        case 3: eq_filter(EqSys<3>(q), r, run, c, et); break;
+        case 4: eq_filter(EqSys<4>(q), r, run, c, et); break;
+        default: break;
+    }
+    store_tile(r, base, cnt, tile, r.fade_in, r.fade_out);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_energy(const DspRow* __restrict__ rows, const LoudScan sc) {
@@ -306,7 +464,19 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         hipLaunchKernelGGL(k_dsp_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.scan);
     }
     note_launch("k_dsp_apply");
-    hipLaunchKernelGGL(p.any_loud ? k_dsp_apply<true> : k_dsp_apply<false>, tiles, lanes, 0, stream, rows_dev, *p.scan);
+    if (!p.any_eq) {
+        hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, false> : k_dsp_apply<false, false>), tiles, lanes, 0, stream, rows_dev, *p.scan);
+        return;
+    }
+    hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, true> : k_dsp_apply<false, true>), tiles, lanes, 0, stream, rows_dev, *p.scan);
+    if (max_tiles > 1) {   // behind k_dsp_apply: the equaliser reads what it stored
+        note_launch("k_eq_summary");
+        hipLaunchKernelGGL(k_eq_summary, handing, lanes, 0, stream, rows_dev, p.eqs);
+    }
+    note_launch("k_eq_carry");
+    hipLaunchKernelGGL(k_eq_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, p.eqs);
+    note_launch("k_eq_apply");
+    hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
 }
 
 }  // namespace ptts

@@ -3,15 +3,19 @@
 #include <cmath>
 
 #include "scan_block.h"
+#include "eq.h"
 #include "runtime.h"
 
 namespace ptts {
 
+static_assert(sizeof(EqScan) == kDspEqBytes, "kernels.h sizes the DSP ring's tail by it");
+
 std::string dsp_opts_error(const ptts_dsp_opts& o) {
     if (std::isnan(o.fade_in_ms) || o.fade_in_ms < 0) return strfmt("dsp: fade_in_ms %g is negative or not a number", o.fade_in_ms);
     if (std::isnan(o.fade_out_ms) || o.fade_out_ms < 0) return strfmt("dsp: fade_out_ms %g is negative or not a number", o.fade_out_ms);
-    for (int i = 0; i < 4; i++)
+    for (int i = 2; i < 4; i++)   // (reserved[0..1] hold eq)
         if (o.reserved[i]) return strfmt("dsp: reserved[%d] is %d, must be 0", i, o.reserved[i]);
+    if (o.eq && !eq_lookup(o.eq)) return strfmt("dsp: eq %p is not a live handle of ptts_eq_create", (const void*)o.eq);
     return std::string();
 }
 
@@ -27,12 +31,21 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
     if (jobs.empty()) return;
     constexpr int kRows = RowRing<DspRow>::kRows;
-    // scratch: a peak word per row, then the per-tile states of each DC row and the block of each loudness row (scan_block.h)
+    // a row's equaliser: the job's own, or its options' (a handle freed since the request was checked: PTTS_EINVAL, nothing is launched)
+    std::vector<const EqScan*> job_eq(jobs.size(), nullptr);
+    for (size_t k = 0; k < jobs.size(); k++) {
+        const DspJob& j = jobs[k];
+        job_eq[k] = j.eq;
+        if (!j.eq && j.opts && j.opts->eq && !(job_eq[k] = eq_lookup(j.opts->eq))) throw Error(PTTS_EINVAL, "ptts-hip: " + dsp_opts_error(*j.opts));
+    }
+    // scratch: a peak word per row, then the per-tile states of each DC row and each equaliser row and the block of each loudness row (scan_block.h)
     size_t tile_doubles = 0;
-    for (const DspJob& j : jobs) {
+    for (size_t k = 0; k < jobs.size(); k++) {
+        const DspJob& j = jobs[k];
         if (j.n <= 0) continue;
         if (j.opts && j.opts->dc_block) tile_doubles += scan_state_doubles<DspScan::N>(scan_tiles(j.n));
         if (j.loud) tile_doubles += loud_doubles(scan_tiles(j.n));
+        if (job_eq[k]) tile_doubles += (size_t)scan_tiles(j.n) * 4 * (size_t)job_eq[k]->S;
     }
     const size_t peak_bytes = (jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
     char* scratch = m.work(29, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
@@ -40,12 +53,13 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
     double* tiles = reinterpret_cast<double*>(scratch + peak_bytes);
     PTTS_HIP(hipMemsetAsync(peaks, 0, peak_bytes, s));
     std::vector<DspRow> rows;
+    std::vector<const EqScan*> row_eq;
     rows.reserve(jobs.size());
     for (size_t k = 0; k < jobs.size(); k++) {
         DspJob& j = jobs[k];
         j.loud_out = nullptr;
         const bool on = dsp_active(j.opts);
-        if (j.n <= 0 || !(on || j.loud)) continue;
+        if (j.n <= 0 || !(on || j.loud || job_eq[k])) continue;
         DspRow r{};
         r.x = j.x; r.n = j.n;
         r.fade_in = on ? fade_samples(j.opts->fade_in_ms, j.n) : 0;
@@ -58,22 +72,49 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             r.target = j.target_power;
             tiles += loud_doubles(scan_tiles(j.n));
         }
+        if (job_eq[k] && apply) {
+            r.flags |= DSP_EQ;
+            r.eq_tiles = tiles;
+            tiles += (size_t)scan_tiles(j.n) * 4 * (size_t)job_eq[k]->S;
+        }
         rows.push_back(r);
+        row_eq.push_back(job_eq[k]);
     }
-    for (size_t at = 0; at < rows.size(); at += kRows) {
-        const int n = (int)std::min<size_t>(kRows, rows.size() - at);
+    // a table: up to kRows rows with up to kDspMaxEq distinct equalisers, which travel behind the rows in the same turn of the ring
+    std::vector<EqScan> eqs;
+    std::vector<const EqScan*> eq_of;
+    for (size_t at = 0; at < rows.size();) {
+        int n = 0;
         int64_t max_tiles = 0;
         DspLaunch p{false, false, false, apply, &scan, &loud_scan()};
-        for (int i = 0; i < n; i++) {
-            const DspRow& r = rows[at + (size_t)i];
+        eqs.clear();
+        eq_of.clear();
+        for (; n < kRows && at + (size_t)n < rows.size(); n++) {
+            DspRow& r = rows[at + (size_t)n];
+            if (r.flags & DSP_EQ) {
+                const EqScan* e = row_eq[at + (size_t)n];
+                size_t at_eq = 0;
+                while (at_eq < eq_of.size() && eq_of[at_eq] != e) at_eq++;
+                if (at_eq == eq_of.size()) {
+                    if (eq_of.size() == (size_t)kDspMaxEq) break;   // the next table's
+                    eq_of.push_back(e);
+                    eqs.push_back(*e);
+                }
+                r.eq = (int32_t)at_eq;
+                p.any_eq = true;
+            }
             max_tiles = std::max(max_tiles, scan_tiles(r.n));
             p.any_norm = p.any_norm || (r.flags & DSP_NORMALIZE);
             p.any_dc = p.any_dc || (r.flags & DSP_DC);
             p.any_loud = p.any_loud || (r.flags & DSP_LOUD);
         }
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: dsp: too many samples for one launch");
-        launch_dsp(m.dsp_ring.stage(rows.data() + at, n, s), n, (int)max_tiles, p, s);
+        const void* eqs_dev = nullptr;
+        const DspRow* rows_dev = m.dsp_ring.stage(rows.data() + at, n, s, eqs.data(), eqs.size() * sizeof(EqScan), &eqs_dev);
+        p.eqs = static_cast<const EqScan*>(eqs_dev);
+        launch_dsp(rows_dev, n, (int)max_tiles, p, s);
         m.dsp_ring.done(s);
+        at += (size_t)n;
     }
 }
 

@@ -1,0 +1,27 @@
+// eq.h -- what eq.cpp (the host side of a request's equaliser, no HIP header) shares with the device side (dsp_device.cpp, capi.cpp, runtime.cpp).
+#pragma once
+#include <string>
+
+#include "../../include/ptts.h"
+#include "scan_block.h"
+
+struct ptts_eq { ptts::EqScan sc; };
+
+namespace ptts {
+
+std::string strfmt(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // (common.h's, restated: this header includes no HIP header)
+void set_last_error(const std::string& m);
+
+// empty: section `index` of a cascade is well formed
+std::string eq_section_error(const ptts_eq_section& s, int index);
+// the RBJ cookbook section, normalised by a0 (s: well formed)
+DspBiquad eq_design(const ptts_eq_section& s);
+// sections, the cascade's state matrix and its powers A^kDspRun, A^kDspTile (c: n = 1 .. kEqMaxSections sections)
+EqScan eq_scan_coeffs(const DspBiquad* c, int n);
+// the cascade over x[0, n) in place, in the blocked form of scan_block.h: what k_eq_summary, k_eq_carry and k_eq_apply compute for one row
+void eq_apply_blocked(const EqScan& sc, float* x, int64_t n);
+// the process-wide registry of live handles: the handle's system, or null when e is not one ptts_eq_create returned and ptts_eq_free has not
+// yet taken (e itself is not read)
+const EqScan* eq_lookup(const ptts_eq* e);
+
+}  // namespace ptts

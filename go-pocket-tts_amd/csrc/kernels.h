@@ -288,22 +288,30 @@ extern std::atomic<int64_t> g_resample_launches;
 // as the DC block's two), k_loud_energy (each tile's four sub-block energies) and k_loud_gate (block energies, both gates, the mean square M
 // and the row's f32 gain with the 1 / peak ceiling) on the RAW samples; k_dsp_summary and k_dsp_apply then take the row's gain from that word
 // where normalise's gain sits.  Tables without such a row launch the kernels they launched before it existed.
-enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4 };
+// Equaliser rows (DSP_EQ): k_eq_summary + k_eq_carry + k_eq_apply behind k_dsp_apply, on what it stored (gain and DC block applied, rounded
+// to f32): the row's own cascade of 1 .. 4 sections (scan_block.h EqScan, 2 .. 8 states per tile), then the fades, which k_dsp_apply leaves to
+// k_eq_apply for such a row.  A table's distinct equalisers (at most kDspMaxEq) travel behind its rows; a row names its own by index.
+enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8 };
+constexpr int kDspMaxEq = 16;
+constexpr size_t kDspEqBytes = 1192;   // sizeof(EqScan)
 struct DspRow {
     float* x;              // the row's samples (device), rewritten in place
     int64_t n;             // samples; nothing at or beyond n is touched
     int64_t fade_in, fade_out;   // samples of each fade (0: none, <= n)
     uint32_t* peak;        // normalise and loudness rows: one word, zero before k_dsp_peak
     double* tiles;         // DC rows: the DC block's per-tile states (scan_block.h scan_E / scan_S)
-    int32_t flags, pad;
+    int32_t flags, eq;     // eq: equaliser rows: the index of the row's equaliser among the table's
     double* loud;          // loudness rows: M, the gain, the K-weighting's per-tile states, the sub-block energies (scan_block.h loud_states / loud_subs)
     double target;         // 10^((target LUFS + 0.691) / 10)
+    double* eq_tiles;      // equaliser rows: the cascade's per-tile states, 2 S doubles each for E_f and S_f
 };
 struct DspScan;
 struct LoudScan;
+struct EqScan;
 // which flags occur in a table's rows, and the systems' coefficients (loud: needed with any_loud); apply false: the measuring launches only,
 // the samples stay as they are
-struct DspLaunch { bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; };
+// any_eq: eqs is the device copy of the table's equalisers
+struct DspLaunch { bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr; };
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
 

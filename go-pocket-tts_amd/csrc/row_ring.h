@@ -28,10 +28,12 @@ struct RingAck {
 };
 
 // kRing turns of kRows rows, allocated on first use.  A launch sequence is stage(), the launches on the same stream, done().
-template <class Row>
+// kTail: room behind a turn's rows for up to that many bytes the rows refer to by index (the DSP rows' equalisers), which travel in the
+// same copy.
+template <class Row, size_t kTail = 0>
 struct RowRing {
     static constexpr int kRing = RingAck::kRing, kRows = 256;
-    static constexpr size_t kTurnBytes = RingAck::kHead + sizeof(Row) * kRows;
+    static constexpr size_t kTurnBytes = RingAck::kHead + ((sizeof(Row) * kRows + 15) & ~(size_t)15) + kTail;
     RowRing() = default;
     RowRing(const RowRing&) = delete;
     RowRing& operator=(const RowRing&) = delete;
@@ -40,14 +42,23 @@ struct RowRing {
         if (dev) (void)hipFree(dev);
     }
     // rows[0, n), n <= kRows, into the next turn (waits until that turn's last launches have run) and, on s, to the device: the device copy
-    const Row* stage(const Row* rows, int n, hipStream_t s) {
+    // tail[0, tail_bytes), tail_bytes <= kTail, goes behind the rows (16-byte aligned) in the same copy: *tail_dev receives its device copy
+    const Row* stage(const Row* rows, int n, hipStream_t s, const void* tail = nullptr, size_t tail_bytes = 0, const void** tail_dev = nullptr) {
         if (!host) PTTS_HIP(hipHostMalloc((void**)&host, kTurnBytes * kRing, hipHostMallocDefault));
         if (!dev) PTTS_HIP(hipMalloc((void**)&dev, kTurnBytes * kRing));
+        if (tail_bytes > kTail) throw Error(PTTS_EINVAL, "ptts-hip: a row table's tail does not fit its ring");
         turn = (turn + 1) % kRing;
         ack.wait(turn);
         char* h = host + (size_t)turn * kTurnBytes;
-        std::memcpy(h + RingAck::kHead, rows, (size_t)n * sizeof(Row));
-        ack.upload(turn, h, dev_turn(), (size_t)n * sizeof(Row), s);
+        size_t bytes = (size_t)n * sizeof(Row);
+        std::memcpy(h + RingAck::kHead, rows, bytes);
+        if (tail_bytes) {
+            bytes = (bytes + 15) & ~(size_t)15;
+            std::memcpy(h + RingAck::kHead + bytes, tail, tail_bytes);
+            *tail_dev = dev_turn() + RingAck::kHead + bytes;
+            bytes += tail_bytes;
+        }
+        ack.upload(turn, h, dev_turn(), bytes, s);
         return reinterpret_cast<const Row*>(dev_turn() + RingAck::kHead);
     }
     void done(hipStream_t s) { ack.done(turn, dev_turn(), s); }   // behind the launches that read the staged rows

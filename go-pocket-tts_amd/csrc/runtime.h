@@ -88,7 +88,7 @@ struct Model {
     Prof prof;
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
-    RowRing<DspRow> dsp_ring;       // the DSP kernels' (dsp_device.cpp)
+    RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
     // re-issued as the 2 x depth launches (same bits) -- fc_fallbacks counts the events -- and this engine's batches keep the launches from then on
@@ -318,12 +318,13 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
 // post-processing on the device (dsp_device.cpp, dsp.hip): whether a request's ptts_dsp_opts switch anything on; the message of a bad one
 // (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
-inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0); }
+inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq); }
 std::string dsp_opts_error(const ptts_dsp_opts& o);
 // loud: the row is measured (BS.1770, dsp.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
 // dsp_launch sets loud_out to the row's two device words (the mean square M as a double, then the f32 gain), valid until the model's next
 // DSP launch.  opts may be NULL for a loudness row.
-struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; };
+// eq: the row's equaliser (a live handle's system, eq.h eq_lookup; takes precedence over opts->eq, which dsp_launch looks up itself)
+struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; const EqScan* eq = nullptr; };
 // apply false: loudness rows are measured only (M and the sub-block energies), no sample is rewritten
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
 inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)

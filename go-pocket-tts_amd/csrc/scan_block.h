@@ -12,7 +12,8 @@
 //     E_f = the same fold from t_0 = 0;   S_(f+1) = A^kDspTile S_f + E_f           (in tile order)
 //     run l again  the recurrence itself, started from t_l                         (Sys::run: its outputs, or the sum of their squares)
 // Two systems: the DC block (DspScan, N = 2: one section, y = b0 x + z1, A = [[-a1, 1], [-a2, 0]]) and the K-weighting of BS.1770-4 at
-// 24 kHz (LoudScan, N = 4: a high shelf, then a high-pass, z = (shelf z1, shelf z2, high-pass z1, high-pass z2)).
+// 24 kHz (LoudScan, N = 4: a high shelf, then a high-pass, z = (shelf z1, shelf z2, high-pass z1, high-pass z2)).  A third, per request: the
+// equaliser (EqScan seen as EqSys<S>, N = 2 S for S = 1 .. 4 sections of the caller's choice; eq.cpp's eq_apply_blocked IS ptts_eq_apply).
 // Loudness energies: a sub-block is kLoudSub = 480 samples = 16 runs (a tile has 4, the 100 ms hop 5, the 400 ms block 20); its energy is the
 // sum of its runs' sums of squares in run order; block j (samples [2400 j, 2400 j + 9600), whole blocks only) is the sum of its 20 sub-blocks
 // in order, over 9600.  Gating is linear: the absolute gate z > abs_gate, the relative gate z > 0.1 * mean of the absolutely gated z, M the
@@ -117,6 +118,52 @@ struct LoudScan {
         return q;
     }
 };
+
+// a request's equaliser (eq.cpp, ptts_eq): S = 1 .. 4 sections chosen by the caller, N = 2 S states z = (section 0 z1, z2, section 1 z1, ...);
+// a_run and a_tile are N x N row-major, packed at the front.  It travels to the device as it is, behind a table's rows (dsp_device.cpp).
+constexpr int kEqMaxSections = 4;
+struct EqScan {
+    int32_t S, pad;
+    DspBiquad c[kEqMaxSections];
+    double a_run[4 * kEqMaxSections * kEqMaxSections], a_tile[4 * kEqMaxSections * kEqMaxSections];
+};
+// ... seen as a system of S sections: only those are evaluated (an identity section in an unused place would turn -0 into +0).  y (optional,
+// may be x) receives the outputs rounded to f32
+template <int S_>
+struct EqSys {
+    static constexpr int S = S_, N = 2 * S_;
+    const DspBiquad* c;
+    const double *a_run, *a_tile;
+    PTTS_HD explicit EqSys(const EqScan& e) : c(e.c), a_run(e.a_run), a_tile(e.a_tile) {}
+    PTTS_HD void run(const float* x, int count, double* z, float* y = nullptr) const {
+#pragma clang fp contract(off)
+        double w[N];
+        for (int k = 0; k < N; k++) w[k] = z[k];
+        for (int i = 0; i < count; i++) {
+            double v = (double)x[i];
+            for (int k = 0; k < S; k++) {
+                const DspBiquad& q = c[k];
+                const double u = q.b0 * v + w[2 * k];
+                w[2 * k] = q.b1 * v - q.a1 * u + w[2 * k + 1];
+                w[2 * k + 1] = q.b2 * v - q.a2 * u;
+                v = u;
+            }
+            if (y) y[i] = (float)v;
+        }
+        for (int k = 0; k < N; k++) z[k] = w[k];
+    }
+};
+// f(EqSys<S>) for the equaliser's section count (1 .. kEqMaxSections, checked where it was made)
+template <class F>
+PTTS_HD inline void eq_dispatch(const EqScan& e, F&& f) {
+    switch (e.S) {
+        case 1: f(EqSys<1>(e)); break;
+        case 2: f(EqSys<2>(e)); break;
+        case 3: f(EqSys<3>(e)); break;
+        case 4: f(EqSys<4>(e)); break;
+        default: break;
+    }
+}
 
 // A row's per-tile states in scratch: [F = ceil(n / kDspTile)][2 N] doubles, E_f (N) then S_f (N)
 PTTS_HD inline int64_t scan_tiles(int64_t n) { return (n + kDspTile - 1) / kDspTile; }

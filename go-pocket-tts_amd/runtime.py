@@ -56,8 +56,20 @@ class _Info(C.Structure):
                 ("arena_bytes", C.c_int64), ("weights", C.c_int32), ("kv", C.c_int32)]
 
 
+class _DspTail(C.Union):   # the anonymous union at the end of ptts_dsp_opts: eq lies over reserved[0..1]
+    _fields_ = [("reserved", C.c_int32 * 4), ("eq", C.c_void_p)]
+
+
 class DspOpts(C.Structure):   # ptts_dsp_opts
-    _fields_ = [("normalize", C.c_int32), ("dc_block", C.c_int32), ("fade_in_ms", C.c_double), ("fade_out_ms", C.c_double), ("reserved", C.c_int32 * 4)]
+    _anonymous_ = ("_tail",)
+    _fields_ = [("normalize", C.c_int32), ("dc_block", C.c_int32), ("fade_in_ms", C.c_double), ("fade_out_ms", C.c_double), ("_tail", _DspTail)]
+
+
+class EqSection(C.Structure):   # ptts_eq_section
+    _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("freq_hz", C.c_double), ("gain_db", C.c_double), ("q", C.c_double)]
+
+
+EQ_LOWPASS, EQ_HIGHPASS, EQ_LOWSHELF, EQ_HIGHSHELF, EQ_PEAKING = 1, 2, 3, 4, 5   # ptts_eq_section.type
 
 
 class _Request(C.Structure):
@@ -113,6 +125,7 @@ ABI_SYMBOLS = [
     "ptts_voice_state_write_bytes", "ptts_voice_embedding_write", "ptts_free_bytes",
     "ptts_resample_length", "ptts_resample", "ptts_pcm_encode", "ptts_mimi_encode_rates", "ptts_voice_from_audio_rates", "ptts_wav_header",
     "ptts_dsp_rows", "ptts_loudness", "ptts_loudness_normalize", "ptts_loudness_rows", "ptts_loudness_normalize_rows",
+    "ptts_eq_design", "ptts_eq_response", "ptts_eq_create", "ptts_eq_free", "ptts_eq_apply", "ptts_eq_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -315,6 +328,8 @@ class RuntimeGenerateConfig:
     # loudness normalisation on the device (ptts_request.loudness): 0 off, else the BS.1770 target in 0.01 LUFS (-2300: EBU R 128, -1600: streaming);
     # the result is loudness_normalize(this request's own 24 kHz audio, loudness / 100), then the switches above, then the egress
     loudness: int = 0
+    # a per-request equaliser (ptts_dsp_opts.eq): an Eq, applied behind the DC block and in front of the fades; the caller keeps it alive
+    eq: Optional["Eq"] = None
 
 
 def _free_addr(addr: int):
@@ -613,6 +628,23 @@ class Model:
         L = lib()
         L.ptts_dsp_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), C.POINTER(_FP)]
         _check(L.ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), po))
+        return outs[0] if single else outs
+
+    def eq_rows(self, x, eq):
+        """ptts_eq_rows: Eq.apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).  eq: one Eq for
+        every row, or one per row (None copies that row)."""
+        single = not isinstance(x, (list, tuple))
+        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+        n = len(rows)
+        eqs = list(eq) if isinstance(eq, (list, tuple)) else [eq] * n
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        pe = (C.c_void_p * max(n, 1))(*[e.h if e is not None else None for e in eqs])
+        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
+        ns = np.array([r.size for r in rows] or [0], np.int64)
+        L = lib()
+        L.ptts_eq_rows.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        _check(L.ptts_eq_rows(self.h, pe, pp, _ip(ns), n, po))
         return outs[0] if single else outs
 
     def _loudness_rows(self, x, target):
@@ -1372,9 +1404,83 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
         return raw
     nz, dc = bool(getattr(cfg, "normalize", False)), bool(getattr(cfg, "dc_block", False))
     fi, fo = float(getattr(cfg, "fade_in_ms", 0.0)), float(getattr(cfg, "fade_out_ms", 0.0))
-    if not (nz or dc or fi != 0.0 or fo != 0.0):
+    eq = getattr(cfg, "eq", None)
+    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None):
         return None
-    return DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
+    o = DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
+    if eq is not None:
+        o.eq = eq.h
+    return o
+
+
+def _eq_sections(sections):
+    """(type, freq_hz, gain_db, q) tuples, or EqSection structs, as a ptts_eq_section array."""
+    arr = (EqSection * max(len(sections), 1))()
+    for i, s in enumerate(sections):
+        arr[i] = s if isinstance(s, EqSection) else EqSection(int(s[0]), 0, float(s[1]), float(s[2]), float(s[3]))
+    return arr
+
+
+def eq_design(section) -> np.ndarray:
+    """ptts_eq_design: b0, b1, b2, a1, a2 of one RBJ cookbook section at 24 kHz (float64, normalised by a0).  Host code."""
+    arr = _eq_sections([section])
+    out = np.zeros(5, np.float64)
+    L = lib()
+    L.ptts_eq_design.argtypes = [C.POINTER(EqSection), C.POINTER(C.c_double)]
+    _check(L.ptts_eq_design(arr, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def eq_response(sections, freq_hz: float) -> float:
+    """ptts_eq_response: the magnitude in dB of the cascade of 1 .. 4 sections at freq_hz.  Host code."""
+    arr = _eq_sections(sections)
+    out = C.c_double(0.0)
+    L = lib()
+    L.ptts_eq_response.argtypes = [C.POINTER(EqSection), C.c_int32, C.c_double, C.POINTER(C.c_double)]
+    _check(L.ptts_eq_response(arr, len(sections), float(freq_hz), C.byref(out)))
+    return float(out.value)
+
+
+class Eq:
+    """A per-request equaliser (ptts_eq): a cascade of 1 .. 4 biquad sections, (type, freq_hz, gain_db, q) each.  It belongs to no model; keep it
+    alive while requests that name it (RuntimeGenerateConfig.eq) are running."""
+
+    def __init__(self, sections):
+        self.sections = list(sections)
+        arr = _eq_sections(self.sections)
+        L = lib()
+        L.ptts_eq_create.argtypes = [C.POINTER(EqSection), C.c_int32, C.POINTER(C.c_void_p)]
+        L.ptts_eq_free.argtypes = [C.c_void_p]
+        L.ptts_eq_free.restype = None
+        h = C.c_void_p()
+        self.h = None
+        _check(L.ptts_eq_create(arr, len(self.sections), C.byref(h)))
+        self.h = h.value
+
+    def apply(self, samples) -> np.ndarray:
+        """ptts_eq_apply: the cascade over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
+        out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+        L = lib()
+        L.ptts_eq_apply.argtypes = [C.c_void_p, _FP, C.c_int64]
+        _check(L.ptts_eq_apply(self.h, _fp(out), out.size))
+        return out
+
+    def rows(self, model, x):
+        """ptts_eq_rows: apply() on the device of `model`."""
+        return model.eq_rows(x, self)
+
+    def response(self, freq_hz: float) -> float:
+        return eq_response(self.sections, freq_hz)
+
+    def free(self):
+        if self.h:
+            lib().ptts_eq_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():
+            return
+        self.free()
 
 
 def loudness(samples) -> float:

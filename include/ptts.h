@@ -124,13 +124,29 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * rounded to f32 where ptts_dsp_apply rounds it.  Normalise and the fades give ptts_dsp_apply's bits; the DC block is the same float64
  * recurrence evaluated as a blocked scan and agrees with it to one f32 step at the row's peak.  It is per request: the reference's CLI
  * runs the chain over a whole text's concatenated chunks (cmd/pockettts/synth.go:361-390); a host that wants that for a multi-chunk
- * text keeps using ptts_dsp_apply, or ptts_dsp_rows, on the concatenation. */
+ * text keeps using ptts_dsp_apply, or ptts_dsp_rows, on the concatenation.
+ *
+ * The equaliser (`eq`, a handle of ptts_eq_create below: a cascade of one to four biquad sections chosen by the caller) sits behind the DC
+ * block and in front of the fades.  The whole order of a request's chain: the loudness or normalise gain -> DC block -> equaliser -> fade in
+ * -> fade out -> egress.  The host statement of the result: ptts_loudness_normalize, or ptts_dsp_apply(normalize, dc_block, 0, 0); then
+ * ptts_eq_apply; then ptts_dsp_apply(0, 0, fade_in_ms, fade_out_ms); then the egress.  The equaliser gives ptts_eq_apply's bits.  Peak and
+ * loudness are measured on the raw decoded audio, in front of the equaliser: a boosting equaliser can push samples past +-1, and the PCM16
+ * and G.711 egress clamps them as it always does (f32 leaves as it is).  There is no limiter. */
+#if defined(__GNUC__)
+#define PTTS_ANON __extension__
+#else
+#define PTTS_ANON
+#endif
+typedef struct ptts_eq ptts_eq;
 typedef struct ptts_dsp_opts {
     int32_t normalize;      /* PeakNormalize */
     int32_t dc_block;       /* DCBlock, 20 Hz, Q 0.707, at 24 kHz */
     double  fade_in_ms;     /* <= 0: none */
     double  fade_out_ms;
-    int32_t reserved[4];    /* must be 0 */
+    PTTS_ANON union {
+        int32_t reserved[4];    /* reserved[2] and reserved[3] must be 0 */
+        const ptts_eq* eq;      /* lies over reserved[0..1]: NULL, or a live handle of ptts_eq_create (borrowed for the call) */
+    };
 } ptts_dsp_opts;
 
 typedef struct ptts_request {
@@ -182,9 +198,9 @@ typedef struct ptts_request {
      * offsets and buffers count samples at this rate: n_frames * 0.08 * sample_rate.  Other values: PTTS_EINVAL naming the rate. */
     int32_t sample_rate;
     /* post-processing on the device, in front of the egress above (borrowed for the call).  NULL, or a struct with nothing switched on:
-     * none.  PTTS_EINVAL naming the field for a negative or NaN fade, a non-zero reserved word, and for any switch together with
-     * pcm_callback (the peak and the end of the utterance are not known when samples are handed over; dc_block and fade_in_ms are refused
-     * with it as well, for now). */
+     * none.  PTTS_EINVAL naming the field for a negative or NaN fade, a non-zero reserved word, an `eq` that is not a live handle of
+     * ptts_eq_create ("dsp: eq"), and for any switch together with pcm_callback (the peak and the end of the utterance are not known when
+     * samples are handed over; dc_block, fade_in_ms and eq are refused with it as well, for now). */
     const ptts_dsp_opts* dsp;
 } ptts_request;
 
@@ -257,6 +273,39 @@ int  ptts_loudness_normalize(float* samples, int64_t n, double target_lufs, doub
 int  ptts_loudness_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double* lufs);
 int  ptts_loudness_normalize_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out,
                                   double* measured);
+
+/* A per-request equaliser at 24 kHz: a cascade of one to four biquad sections of the published RBJ cookbook in its
+ * Q form -- w0 = 2 pi freq_hz / 24000, alpha = sin(w0) / (2 q), shelves and peaking with A = 10^(gain_db / 40) -- designed in float64,
+ * normalised by a0, run in direct form II transposed with float64 state, each output rounded once to f32.
+ * Ranges: freq_hz 10 .. 11000, q 0.1 .. 10, gain_db -24 .. +24 for PTTS_EQ_LOWSHELF / HIGHSHELF / PEAKING and exactly 0 for PTTS_EQ_LOWPASS /
+ * HIGHPASS, reserved 0, every value finite; anything else is PTTS_EINVAL and the error names the section index and the field.
+ * Telephony band-limiting in front of 8 kHz mu-law, as a worked example:
+ *     ptts_eq_section s[2] = {{PTTS_EQ_HIGHPASS, 0, 300.0, 0.0, 0.7071}, {PTTS_EQ_LOWPASS, 0, 3400.0, 0.0, 0.7071}};
+ *     ptts_eq* eq; ptts_eq_create(s, 2, &eq);
+ *     ptts_dsp_opts o = {0}; o.eq = eq;   request.dsp = &o; request.sample_rate = 8000; request.pcm_format = PTTS_PCM_ULAW;
+ *     ... ptts_generate ...               ptts_eq_free(eq);   (once no request that names it is running)
+ * ptts_eq_design: coeffs receives b0, b1, b2, a1, a2 of one section (y = b0 x + b1 x1 + b2 x2 - a1 y1 - a2 y2).  Host only.
+ * ptts_eq_response: *gain_db receives 20 log10 |H| of the cascade of n (1 .. 4) sections at freq_hz (above 0, below 12000).  Host only.
+ * ptts_eq_create: the handle of a cascade of n (1 .. 4) sections.  It belongs to no model: it holds host memory only and works with every
+ * model, every ptts_model_share engine and every dispatcher of the process.  The caller keeps it alive while requests that name it are running,
+ * as with ptts_request.voice.  ptts_eq_free(NULL) does nothing.
+ * ptts_eq_apply: the cascade over host samples, in place, evaluated in the blocked form the device kernels run (runs of 30 samples, tiles of
+ * 1920): the device forms -- ptts_dsp_opts.eq, ptts_eq_rows -- give these bits.  It agrees with the sample-by-sample recurrence to one f32
+ * step at the row's peak.
+ * ptts_eq_rows: the same on the device, by the kernels a request's `eq` runs, shaped like ptts_dsp_rows; eq[i] may differ per row, NULL copies
+ * the row.  PTTS_EINVAL naming the row for a handle that is not live. */
+#define PTTS_EQ_LOWPASS   1
+#define PTTS_EQ_HIGHPASS  2
+#define PTTS_EQ_LOWSHELF  3
+#define PTTS_EQ_HIGHSHELF 4
+#define PTTS_EQ_PEAKING   5
+typedef struct ptts_eq_section { int32_t type; int32_t reserved; double freq_hz, gain_db, q; } ptts_eq_section;
+int  ptts_eq_design(const ptts_eq_section* s, double coeffs[5]);
+int  ptts_eq_response(const ptts_eq_section* s, int32_t n, double freq_hz, double* gain_db);
+int  ptts_eq_create(const ptts_eq_section* s, int32_t n, ptts_eq** out);
+void ptts_eq_free(ptts_eq* e);
+int  ptts_eq_apply(const ptts_eq* e, float* samples, int64_t n);
+int  ptts_eq_rows(ptts_model* m, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -505,7 +554,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_mimi_encode_rates, ptts_voice_from_audio_rates, ptts_wav_header.  Later additions keep the number (hosts test for the symbol):
  * ptts_request.dsp (in the place of reserved2: the struct's size and every other offset are unchanged) with ptts_dsp_opts, and ptts_dsp_rows;
  * ptts_request.loudness (in the place of reserved[1], likewise), ptts_loudness, ptts_loudness_normalize, ptts_loudness_rows,
- * ptts_loudness_normalize_rows */
+ * ptts_loudness_normalize_rows; ptts_dsp_opts.eq (over reserved[0..1] of ptts_dsp_opts: its size and every offset are unchanged) with
+ * ptts_eq_section, ptts_eq_design, ptts_eq_response, ptts_eq_create, ptts_eq_free, ptts_eq_apply, ptts_eq_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
