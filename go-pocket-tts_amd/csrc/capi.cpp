@@ -1174,6 +1174,17 @@ int ptts_loudness_normalize_rows(ptts_model* h, const float* const* in, const in
     return guard([&] { loudness_rows(h, in, n, rows, &target_lufs, out, measured); });
 }
 
+// the device form of ptts_true_peak on host rows: upload, the measuring launch of a request's ceiling, the rows' words back
+int ptts_true_peak_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, float* peaks) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        if (rows < 0 || (rows > 0 && (!in || !n || !peaks))) throw Error(PTTS_EINVAL, "ptts-hip: true peak: null argument");
+        for (int i = 0; i < rows; i++)
+            if (n[i] < 0 || (n[i] > 0 && !in[i])) throw Error(PTTS_EINVAL, strfmt("ptts-hip: true peak: row %d is negative or null", i));
+        true_peak_rows_device(*h->m, in, n, rows, peaks);
+    });
+}
+
 int ptts_pcm_encode(ptts_model* h, const float* in, int64_t n, int32_t pcm_format, void* out) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");

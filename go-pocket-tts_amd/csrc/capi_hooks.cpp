@@ -4,6 +4,7 @@
 #include "capi_internal.h"
 #include "../../include/ptts_debug.h"
 #include "scan_block.h"
+#include "true_peak.h"
 
 using namespace ptts;
 using namespace ptts::capi;
@@ -76,6 +77,34 @@ int ptts_debug_kweighting(int32_t sample_rate, double out[10]) {
     return guard([&] {
         if (!out || sample_rate <= 0) throw Error(PTTS_EINVAL, "ptts-hip: loudness: bad argument");
         loud_kweight_coeffs(sample_rate, out);
+    });
+}
+
+int64_t ptts_debug_dsp_opts_error(const ptts_dsp_opts* opts, char* out, int64_t cap) {
+    const std::string s = opts ? dsp_opts_error(*opts) : std::string();
+    if (out && cap > 0) {
+        const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1);
+        std::memcpy(out, s.data(), n);
+        out[n] = 0;
+    }
+    return (int64_t)s.size();
+}
+
+int ptts_debug_true_peak_taps(float* out, int32_t* L, int32_t* K, int32_t* dlo) {
+    if (L) *L = kTpPhases;
+    if (K) *K = kTpTaps;
+    if (dlo) *dlo = kTpDlo;
+    const TpTaps& t = tp_taps();
+    if (out)
+        for (int p = 0; p < kTpPhases; p++)
+            for (int k = 0; k < kTpTaps; k++) out[p * kTpTaps + k] = t.h[k][p];
+    return PTTS_OK;
+}
+
+int ptts_debug_true_peak_oversample(const float* samples, int64_t n, float* y) {
+    return guard([&] {
+        if (n < 0 || (n > 0 && (!samples || !y))) throw Error(PTTS_EINVAL, "ptts-hip: true peak: null argument");
+        (void)tp_measure(samples, n, y);
     });
 }
 

@@ -19,6 +19,7 @@
 //                   gains, which k_dsp_apply leaves to k_eq_apply for such a row.  The fold s <- A^30 s + e_l is N independent sums, each in its
 //                   fixed order: lane i < N computes component i (lanes_advance), the other components reach it by v_readlane.  The bits are
 //                   scan_advance's; the serial chain is one sum long, not N.
+//   k_tp_peak, k_tp_scale   true-peak rows (DSP_TP), behind everything above: true_peak.hip.
 // k_dsp_* are the DC block's (DspScan, DSP_DC rows, on the f32 product x * gain wherever it is read), k_loud_* the K-weighting's (LoudScan,
 // DSP_LOUD rows, on the RAW samples: nothing is written to them, k_dsp_apply applies the gain).  Stream order has the peak complete before
 // k_loud_gate and k_dsp_summary start, and the loudness gain before k_dsp_summary.  One wave per workgroup and at most 12.5 KB of LDS: a CU
@@ -454,7 +455,10 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         note_launch("k_loud_gate");
         hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
     }
-    if (!p.apply) return;
+    if (!p.apply) {
+        if (p.any_tp) launch_tp_peak(rows_dev, n, max_tiles, *p.taps, stream);   // a measurement alone
+        return;
+    }
     if (p.any_dc) {
         if (max_tiles > 1) {
             note_launch("k_dsp_summary");
@@ -466,17 +470,21 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
     note_launch("k_dsp_apply");
     if (!p.any_eq) {
         hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, false> : k_dsp_apply<false, false>), tiles, lanes, 0, stream, rows_dev, *p.scan);
-        return;
+    } else {
+        hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, true> : k_dsp_apply<false, true>), tiles, lanes, 0, stream, rows_dev, *p.scan);
+        if (max_tiles > 1) {   // behind k_dsp_apply: the equaliser reads what it stored
+            note_launch("k_eq_summary");
+            hipLaunchKernelGGL(k_eq_summary, handing, lanes, 0, stream, rows_dev, p.eqs);
+        }
+        note_launch("k_eq_carry");
+        hipLaunchKernelGGL(k_eq_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, p.eqs);
+        note_launch("k_eq_apply");
+        hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
     }
-    hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, true> : k_dsp_apply<false, true>), tiles, lanes, 0, stream, rows_dev, *p.scan);
-    if (max_tiles > 1) {   // behind k_dsp_apply: the equaliser reads what it stored
-        note_launch("k_eq_summary");
-        hipLaunchKernelGGL(k_eq_summary, handing, lanes, 0, stream, rows_dev, p.eqs);
+    if (p.any_tp) {   // the last stage (true_peak.hip): on what the chain stored
+        launch_tp_peak(rows_dev, n, max_tiles, *p.taps, stream);
+        launch_tp_scale(rows_dev, n, max_tiles, stream);
     }
-    note_launch("k_eq_carry");
-    hipLaunchKernelGGL(k_eq_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, p.eqs);
-    note_launch("k_eq_apply");
-    hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
 }
 
 }  // namespace ptts

@@ -4,6 +4,7 @@
 
 #include "scan_block.h"
 #include "eq.h"
+#include "true_peak.h"
 #include "runtime.h"
 
 namespace ptts {
@@ -13,10 +14,15 @@ static_assert(sizeof(EqScan) == kDspEqBytes, "kernels.h sizes the DSP ring's tai
 std::string dsp_opts_error(const ptts_dsp_opts& o) {
     if (std::isnan(o.fade_in_ms) || o.fade_in_ms < 0) return strfmt("dsp: fade_in_ms %g is negative or not a number", o.fade_in_ms);
     if (std::isnan(o.fade_out_ms) || o.fade_out_ms < 0) return strfmt("dsp: fade_out_ms %g is negative or not a number", o.fade_out_ms);
-    for (int i = 2; i < 4; i++)   // (reserved[0..1] hold eq)
-        if (o.reserved[i]) return strfmt("dsp: reserved[%d] is %d, must be 0", i, o.reserved[i]);
     if (o.eq && !eq_lookup(o.eq)) return strfmt("dsp: eq %p is not a live handle of ptts_eq_create", (const void*)o.eq);
+    DspExt ext;   // (no reserved word is left to check: whatever lies in reserved[2..3] is a handle the registry knows, or refused unread)
+    if (o.ext && !ext_lookup(o.ext, &ext)) return strfmt("dsp: ext %p (reserved[2..3]) is not a live handle of ptts_dsp_ext_create", (const void*)o.ext);
     return std::string();
+}
+
+bool dsp_ext_active(const ptts_dsp_ext* e) {
+    DspExt ext;
+    return ext_lookup(e, &ext) && ext.true_peak;
 }
 
 namespace {
@@ -38,7 +44,14 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         job_eq[k] = j.eq;
         if (!j.eq && j.opts && j.opts->eq && !(job_eq[k] = eq_lookup(j.opts->eq))) throw Error(PTTS_EINVAL, "ptts-hip: " + dsp_opts_error(*j.opts));
     }
-    // scratch: a peak word per row, then the per-tile states of each DC row and each equaliser row and the block of each loudness row (scan_block.h)
+    // a row's ceiling: the job's own, or its options' (the same rule for a handle freed since; the ceiling is copied by value)
+    std::vector<DspExt> job_tp(jobs.size());
+    for (size_t k = 0; k < jobs.size(); k++) {
+        const DspJob& j = jobs[k];
+        job_tp[k] = DspExt{j.tp, j.ceiling};
+        if (!j.tp && j.opts && j.opts->ext && !ext_lookup(j.opts->ext, &job_tp[k])) throw Error(PTTS_EINVAL, "ptts-hip: " + dsp_opts_error(*j.opts));
+    }
+    // scratch: a peak word and a true-peak word per row, then the per-tile states of each DC row and each equaliser row and the block of each loudness row (scan_block.h)
     size_t tile_doubles = 0;
     for (size_t k = 0; k < jobs.size(); k++) {
         const DspJob& j = jobs[k];
@@ -47,7 +60,7 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         if (j.loud) tile_doubles += loud_doubles(scan_tiles(j.n));
         if (job_eq[k]) tile_doubles += (size_t)scan_tiles(j.n) * 4 * (size_t)job_eq[k]->S;
     }
-    const size_t peak_bytes = (jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t peak_bytes = (2 * jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;   // [jobs] sample peaks, then [jobs] true peaks
     char* scratch = m.work(29, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
     uint32_t* peaks = reinterpret_cast<uint32_t*>(scratch);
     double* tiles = reinterpret_cast<double*>(scratch + peak_bytes);
@@ -58,8 +71,9 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
     for (size_t k = 0; k < jobs.size(); k++) {
         DspJob& j = jobs[k];
         j.loud_out = nullptr;
+        j.tp_out = nullptr;
         const bool on = dsp_active(j.opts);
-        if (j.n <= 0 || !(on || j.loud || job_eq[k])) continue;
+        if (j.n <= 0 || !(on || j.loud || job_eq[k] || job_tp[k].true_peak)) continue;
         DspRow r{};
         r.x = j.x; r.n = j.n;
         r.fade_in = on ? fade_samples(j.opts->fade_in_ms, j.n) : 0;
@@ -76,6 +90,11 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             r.flags |= DSP_EQ;
             r.eq_tiles = tiles;
             tiles += (size_t)scan_tiles(j.n) * 4 * (size_t)job_eq[k]->S;
+        }
+        if (job_tp[k].true_peak) {
+            r.flags |= DSP_TP;
+            r.tp = j.tp_out = peaks + jobs.size() + k;
+            r.ceiling = job_tp[k].ceiling;
         }
         rows.push_back(r);
         row_eq.push_back(job_eq[k]);
@@ -107,7 +126,9 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             p.any_norm = p.any_norm || (r.flags & DSP_NORMALIZE);
             p.any_dc = p.any_dc || (r.flags & DSP_DC);
             p.any_loud = p.any_loud || (r.flags & DSP_LOUD);
+            p.any_tp = p.any_tp || (r.flags & DSP_TP);
         }
+        p.taps = &tp_taps();
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: dsp: too many samples for one launch");
         const void* eqs_dev = nullptr;
         const DspRow* rows_dev = m.dsp_ring.stage(rows.data() + at, n, s, eqs.data(), eqs.size() * sizeof(EqScan), &eqs_dev);
@@ -116,6 +137,31 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         m.dsp_ring.done(s);
         at += (size_t)n;
     }
+}
+
+// ptts_true_peak_rows: rows packed 256-byte aligned in one device buffer, the measuring launch of a request's ceiling
+void true_peak_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, float* peaks) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> off((size_t)rows);
+    size_t bytes = 0;
+    for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
+    char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
+    std::vector<DspJob> jobs;
+    std::vector<int> job_row;
+    for (int i = 0; i < rows; i++) {
+        peaks[i] = 0.0f;
+        if (n[i] <= 0) continue;
+        PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
+        DspJob j{(float*)(buf + off[(size_t)i]), n[i], nullptr};
+        j.tp = true;
+        jobs.push_back(j);
+        job_row.push_back(i);
+    }
+    dsp_launch(m, jobs, s, false);
+    for (size_t k = 0; k < jobs.size(); k++) PTTS_HIP(hipMemcpyAsync(peaks + job_row[k], jobs[k].tp_out, sizeof(float), hipMemcpyDeviceToHost, s));
+    PTTS_HIP(hipStreamSynchronize(s));
 }
 
 // ptts_loudness_rows / ptts_loudness_normalize_rows: rows packed 256-byte aligned in one device buffer, the launches of a request's `loudness`

@@ -1,5 +1,5 @@
 // eq.cpp -- a request's equaliser on the host (include/ptts.h ptts_eq_*): the design of its sections (the published
-// RBJ cookbook, Q form, float64), the handle with the cascade's state matrix and its powers, the registry of live handles, and ptts_eq_apply:
+// RBJ cookbook, Q form, float64), the handle with the cascade's state matrix and its powers, the registry of live handles (every kind's: true_peak.cpp's too), and ptts_eq_apply:
 // the cascade in the blocked form of scan_block.h -- the functions dsp.hip's k_eq_* kernels call, instantiated for the host -- so a request's
 // `eq` and ptts_eq_rows give these bits.  No HIP header: the file builds with a plain C++ compiler (tests/test_eq_cpu.py does, with sanitizers).
 #include <cmath>
@@ -7,6 +7,7 @@
 #include <mutex>
 #include <new>
 #include <set>
+#include <utility>
 
 #include "eq.h"
 
@@ -15,9 +16,9 @@ namespace ptts {
 namespace {
 constexpr double kEqRate = 24000.0;
 
-std::mutex g_eq_mu;
-std::set<const ptts_eq*>& eq_live() {
-    static std::set<const ptts_eq*>* s = new std::set<const ptts_eq*>();   // (never destroyed: handles may be freed while the process exits)
+std::mutex g_live_mu;
+std::set<std::pair<const void*, int>>& live() {
+    static std::set<std::pair<const void*, int>>* s = new std::set<std::pair<const void*, int>>();   // (never destroyed: handles may be freed while the process exits)
     return *s;
 }
 
@@ -117,10 +118,22 @@ void eq_apply_blocked(const EqScan& sc, float* x, int64_t n) {
     });
 }
 
-const EqScan* eq_lookup(const ptts_eq* e) {
-    std::lock_guard<std::mutex> lock(g_eq_mu);
-    return e && eq_live().count(e) ? &e->sc : nullptr;
+void handle_add(const void* h, HandleKind kind) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    live().insert({h, kind});
 }
+
+bool handle_take(const void* h, HandleKind kind) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    return live().erase({h, kind}) != 0;
+}
+
+bool handle_live(const void* h, HandleKind kind) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    return h && live().count({h, kind});
+}
+
+const EqScan* eq_lookup(const ptts_eq* e) { return handle_live(e, HANDLE_EQ) ? &e->sc : nullptr; }
 
 }  // namespace ptts
 
@@ -162,20 +175,14 @@ int ptts_eq_create(const ptts_eq_section* s, int32_t n, ptts_eq** out) {
     for (int i = 0; i < n; i++) c[i] = eq_design(s[i]);
     ptts_eq* h = new (std::nothrow) ptts_eq{eq_scan_coeffs(c, n)};
     if (!h) { set_last_error("ptts-hip: out of host memory"); return PTTS_ENOMEM; }
-    {
-        std::lock_guard<std::mutex> lock(g_eq_mu);
-        eq_live().insert(h);
-    }
+    handle_add(h, HANDLE_EQ);
     *out = h;
     return PTTS_OK;
 }
 
 void ptts_eq_free(ptts_eq* e) {
     if (!e) return;
-    {
-        std::lock_guard<std::mutex> lock(g_eq_mu);
-        if (!eq_live().erase(e)) return;   // not a live handle: nothing of ours to free
-    }
+    if (!handle_take(e, HANDLE_EQ)) return;   // not a live handle: nothing of ours to free
     delete e;
 }
 

@@ -20,7 +20,13 @@ DspBiquad eq_design(const ptts_eq_section& s);
 EqScan eq_scan_coeffs(const DspBiquad* c, int n);
 // the cascade over x[0, n) in place, in the blocked form of scan_block.h: what k_eq_summary, k_eq_carry and k_eq_apply compute for one row
 void eq_apply_blocked(const EqScan& sc, float* x, int64_t n);
-// the process-wide registry of live handles: the handle's system, or null when e is not one ptts_eq_create returned and ptts_eq_free has not
+// the process-wide registry of live handles, one for every kind of per-request handle: an address is looked up under its mutex together with
+// its kind (an equaliser is no ptts_dsp_ext) and never read
+enum HandleKind : int { HANDLE_EQ = 1, HANDLE_DSP_EXT = 2 };
+void handle_add(const void* h, HandleKind kind);
+bool handle_take(const void* h, HandleKind kind);    // true: it was live, and is no more
+bool handle_live(const void* h, HandleKind kind);
+// the handle's system, or null when e is not one ptts_eq_create returned and ptts_eq_free has not
 // yet taken (e itself is not read)
 const EqScan* eq_lookup(const ptts_eq* e);
 

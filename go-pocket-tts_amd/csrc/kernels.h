@@ -291,7 +291,10 @@ extern std::atomic<int64_t> g_resample_launches;
 // Equaliser rows (DSP_EQ): k_eq_summary + k_eq_carry + k_eq_apply behind k_dsp_apply, on what it stored (gain and DC block applied, rounded
 // to f32): the row's own cascade of 1 .. 4 sections (scan_block.h EqScan, 2 .. 8 states per tile), then the fades, which k_dsp_apply leaves to
 // k_eq_apply for such a row.  A table's distinct equalisers (at most kDspMaxEq) travel behind its rows; a row names its own by index.
-enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8 };
+// True-peak rows (DSP_TP; true_peak.hip, true_peak.h): k_tp_peak + k_tp_scale behind the table's last kernel, on what the chain stored: the row's
+// true peak (eight-fold oversampled, atomicMax on its own zeroed word) and, where it exceeds the row's ceiling, one gain over the whole row.  A
+// row with the ceiling as its only switch passes through k_dsp_apply untouched.  Tables without such a row launch what they launched before.
+enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8, DSP_TP = 16 };
 constexpr int kDspMaxEq = 16;
 constexpr size_t kDspEqBytes = 1192;   // sizeof(EqScan)
 struct DspRow {
@@ -304,16 +307,27 @@ struct DspRow {
     double* loud;          // loudness rows: M, the gain, the K-weighting's per-tile states, the sub-block energies (scan_block.h loud_states / loud_subs)
     double target;         // 10^((target LUFS + 0.691) / 10)
     double* eq_tiles;      // equaliser rows: the cascade's per-tile states, 2 S doubles each for E_f and S_f
+    uint32_t* tp;          // true-peak rows: one word, zero before k_tp_peak, then the row's true peak as its uint32 image
+    float ceiling;         // true-peak rows: the linear ceiling c = (float)pow(10, dBTP / 20)
 };
+static_assert(sizeof(DspRow) == 96, "a turn of the DSP ring holds 256 of them");
 struct DspScan;
 struct LoudScan;
 struct EqScan;
 // which flags occur in a table's rows, and the systems' coefficients (loud: needed with any_loud); apply false: the measuring launches only,
 // the samples stay as they are
 // any_eq: eqs is the device copy of the table's equalisers
-struct DspLaunch { bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr; };
+// any_tp: the table has a true-peak row (taps: the meter's, true_peak.h); with apply false such a row is measured only
+struct TpTaps;
+struct DspLaunch {
+    bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr;
+    bool any_tp = false; const TpTaps* taps = nullptr;
+};
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
+// launch_dsp's last two (true_peak.hip): the true peak of every DSP_TP row into its word; the gain c / TP over the rows whose word exceeds c
+void launch_tp_peak(const DspRow* rows_dev, int n, int max_tiles, const TpTaps& taps, hipStream_t stream);
+void launch_tp_scale(const DspRow* rows_dev, int n, int max_tiles, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

@@ -8,40 +8,15 @@
 // the support test |p / L - d| < W is the exact integer test 3 |p - d L| < A.
 #include <numeric>
 
+#include "rate_taps.h"
 #include "runtime.h"
 
 namespace ptts {
 
 namespace {
-constexpr double kKaiserBeta = 8.6;
 constexpr int64_t kMaxOut = 48000, kMaxIn = 192000, kMinRate = 8000;
 
-double bessel_i0(double x) {   // power series; converges quickly for the arguments here (<= beta)
-    double sum = 1.0, term = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 200; k++) {
-        term *= q / ((double)k * k);
-        sum += term;
-        if (term < sum * 1e-18) break;
-    }
-    return sum;
-}
-
-int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
-
-struct Shape { int L, M, K, dlo; int64_t A; };
-Shape pair_shape(int in_rate, int out_rate) {
-    const int g = std::gcd(in_rate, out_rate);
-    Shape s;
-    s.L = out_rate / g; s.M = in_rate / g;
-    s.A = 80 * (int64_t)std::max(s.L, s.M);
-    // d of phase p runs over (3p - A) / (3L) < d < (3p + A) / (3L); the widest range over the phases is from p = 0 to p = L - 1
-    s.dlo = (int)(floor_div(-s.A, 3 * (int64_t)s.L) + 1);
-    const int64_t p = s.L - 1, num = 3 * p + s.A, den = 3 * (int64_t)s.L;
-    const int64_t dhi = (num + den - 1) / den - 1;
-    s.K = (int)(dhi - s.dlo + 1);
-    return s;
-}
+using Shape = RateShape;   // (rate_taps.h: the design, shared with the true-peak meter)
 
 int pair_tile(const Shape& s) {   // outputs per workgroup: the input window of a tile stays within kResampleWindow floats
     const int64_t t = ((int64_t)(kResampleWindow - s.K - 8) * s.L) / s.M + 1;
@@ -61,7 +36,7 @@ std::string rate_pair_error(int in_rate, int out_rate) {
     std::string e = rate_error(in_rate, true);
     if (e.empty()) e = rate_error(out_rate, false);
     if (!e.empty() || in_rate == out_rate) return e;
-    const Shape s = pair_shape(in_rate, out_rate);
+    const Shape s = rate_shape(in_rate, out_rate);
     if (s.L > kResampleMaxL || (int64_t)s.L * s.K > kResampleMaxTaps || s.K + 8 >= kResampleWindow)
         return strfmt("ptts-hip: resampling %d Hz -> %d Hz needs a %d x %d tap table, more than k_resample takes (%d phases, %d taps)", in_rate, out_rate,
                       s.L, s.K, kResampleMaxL, kResampleMaxTaps);
@@ -84,23 +59,13 @@ const RateFilter* rate_filter(Model& m, int in_rate, int out_rate, hipStream_t s
         if (slot->up != s) PTTS_HIP(hipStreamWaitEvent(s, slot->ready, 0));   // (the upload's event: complete long ago in the normal case)
         return slot.get();
     }
-    const Shape sh = pair_shape(in_rate, out_rate);
+    const Shape sh = rate_shape(in_rate, out_rate);
     std::unique_ptr<RateFilter> f(new RateFilter());
     f->L = sh.L; f->M = sh.M; f->K = sh.K; f->dlo = sh.dlo; f->A = sh.A; f->tile = pair_tile(sh);
-    const double rho = std::min(1.0, (double)sh.L / sh.M), fc = 0.5 * rho * 0.9, W = 24.0 / (2.0 * fc), i0b = bessel_i0(kKaiserBeta);
     f->n_taps = ((size_t)sh.L * sh.K + 3) & ~(size_t)3;
     PTTS_HIP(hipHostMalloc((void**)&f->staged, f->n_taps * sizeof(float), hipHostMallocDefault));
     std::memset(f->staged, 0, f->n_taps * sizeof(float));
-    for (int p = 0; p < sh.L; p++)
-        for (int k = 0; k < sh.K; k++) {
-            const int64_t d = sh.dlo + k;
-            if (3 * std::llabs((int64_t)p - d * sh.L) >= sh.A) continue;   // outside |t| < W: 0
-            const double t = (double)p / sh.L - (double)d;
-            const double x = 2.0 * fc * t;
-            const double sinc = x == 0.0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
-            const double r = t / W, win = bessel_i0(kKaiserBeta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
-            f->staged[(size_t)p * sh.K + k] = (float)(2.0 * fc * sinc * win);
-        }
+    rate_taps(sh, f->staged);
     f->taps.ensure(f->n_taps * sizeof(float));
     // (first use: queued on s from page-locked memory, nothing waits on the host; launches on s follow it, other streams wait for `ready`)
     PTTS_HIP(hipMemcpyAsync(f->taps.p, f->staged, f->n_taps * sizeof(float), hipMemcpyHostToDevice, s));

@@ -1930,7 +1930,7 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
         const std::string e = dsp_opts_error(*q.dsp);
         if (!e.empty()) return "generate: " + e;
         if (q.pcm_callback) {   // the peak and the end are not known when samples are handed over; the filter and the fade in are refused with it for now
-            const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : q.dsp->eq ? "eq" : nullptr;
+            const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : q.dsp->eq ? "eq" : q.dsp->ext ? "ext" : nullptr;
             if (f) return strfmt("generate: dsp: %s cannot be combined with pcm_callback", f);
         }
     }

@@ -318,13 +318,22 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
 // post-processing on the device (dsp_device.cpp, dsp.hip): whether a request's ptts_dsp_opts switch anything on; the message of a bad one
 // (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
-inline bool dsp_active(const ptts_dsp_opts* o) { return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq); }
+// (ext counts when it is a live handle with true_peak set; an address the registry does not know is never read)
+bool dsp_ext_active(const ptts_dsp_ext* e);
+inline bool dsp_active(const ptts_dsp_opts* o) {
+    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && dsp_ext_active(o->ext)));
+}
 std::string dsp_opts_error(const ptts_dsp_opts& o);
 // loud: the row is measured (BS.1770, dsp.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
 // dsp_launch sets loud_out to the row's two device words (the mean square M as a double, then the f32 gain), valid until the model's next
 // DSP launch.  opts may be NULL for a loudness row.
 // eq: the row's equaliser (a live handle's system, eq.h eq_lookup; takes precedence over opts->eq, which dsp_launch looks up itself)
-struct DspJob { float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; const EqScan* eq = nullptr; };
+// tp: the row's true peak is measured (true_peak.hip) and held at or under `ceiling` (linear); set by the caller, or by dsp_launch from a live
+// opts->ext, which it looks up itself.  dsp_launch sets tp_out to the row's device word (the true peak's uint32 image), valid like loud_out.
+struct DspJob {
+    float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; const EqScan* eq = nullptr;
+    bool tp = false; float ceiling = 1.0f; uint32_t* tp_out = nullptr;
+};
 // apply false: loudness rows are measured only (M and the sub-block energies), no sample is rewritten
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
 inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)
@@ -417,6 +426,8 @@ float loud_measure_gain(const float* x, int64_t n, double target_power, double* 
 double loud_normalize(float* x, int64_t n, double target_lufs);    // in place; returns M as measured before
 // the device form on host rows (dsp_device.cpp): upload, the launches of a request's `loudness`, download.  out NULL: measurement only.
 // M (optional) [rows]; sub (optional): per row its [4 ceil(n / 1920)] sub-block energies as the device computed them
+// ptts_true_peak_rows: the measuring launch alone over rows of host samples; peaks [rows] receives each row's true peak
+void true_peak_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, float* peaks);
 void loudness_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out, double* M,
                           std::vector<double>* sub);
 

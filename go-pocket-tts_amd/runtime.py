@@ -56,13 +56,22 @@ class _Info(C.Structure):
                 ("arena_bytes", C.c_int64), ("weights", C.c_int32), ("kv", C.c_int32)]
 
 
-class _DspTail(C.Union):   # the anonymous union at the end of ptts_dsp_opts: eq lies over reserved[0..1]
-    _fields_ = [("reserved", C.c_int32 * 4), ("eq", C.c_void_p)]
+class _DspHandles(C.Structure):   # eq lies over reserved[0..1], ext over reserved[2..3]
+    _fields_ = [("eq", C.c_void_p), ("ext", C.c_void_p)]
+
+
+class _DspTail(C.Union):   # the anonymous union at the end of ptts_dsp_opts
+    _anonymous_ = ("_handles",)
+    _fields_ = [("reserved", C.c_int32 * 4), ("_handles", _DspHandles)]
 
 
 class DspOpts(C.Structure):   # ptts_dsp_opts
     _anonymous_ = ("_tail",)
     _fields_ = [("normalize", C.c_int32), ("dc_block", C.c_int32), ("fade_in_ms", C.c_double), ("fade_out_ms", C.c_double), ("_tail", _DspTail)]
+
+
+class DspExtOpts(C.Structure):   # ptts_dsp_ext_opts
+    _fields_ = [("size", C.c_uint32), ("true_peak", C.c_int32), ("ceiling_dbtp", C.c_double)]
 
 
 class EqSection(C.Structure):   # ptts_eq_section
@@ -126,13 +135,15 @@ ABI_SYMBOLS = [
     "ptts_resample_length", "ptts_resample", "ptts_pcm_encode", "ptts_mimi_encode_rates", "ptts_voice_from_audio_rates", "ptts_wav_header",
     "ptts_dsp_rows", "ptts_loudness", "ptts_loudness_normalize", "ptts_loudness_rows", "ptts_loudness_normalize_rows",
     "ptts_eq_design", "ptts_eq_response", "ptts_eq_create", "ptts_eq_free", "ptts_eq_apply", "ptts_eq_rows",
+    "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
-    "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear",
+    "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
+    "ptts_debug_dsp_opts_error",
 ]
 
 
@@ -330,6 +341,9 @@ class RuntimeGenerateConfig:
     loudness: int = 0
     # a per-request equaliser (ptts_dsp_opts.eq): an Eq, applied behind the DC block and in front of the fades; the caller keeps it alive
     eq: Optional["Eq"] = None
+    # a true-peak ceiling in dBTP (ptts_dsp_opts.ext; -60 .. 0, None: off): the last stage of the chain, true_peak_limit of what the stages above
+    # made of this request's 24 kHz audio -- a static gain where the utterance's true peak exceeds the ceiling, not a limiter
+    true_peak_dbtp: Optional[float] = None
 
 
 def _free_addr(addr: int):
@@ -646,6 +660,19 @@ class Model:
         L.ptts_eq_rows.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
         _check(L.ptts_eq_rows(self.h, pe, pp, _ip(ns), n, po))
         return outs[0] if single else outs
+
+    def true_peak_rows(self, x):
+        """ptts_true_peak_rows: true_peak() of mono f32 rows at 24 kHz (an array, or a list: one launch for all), measured on the device."""
+        single = not isinstance(x, (list, tuple))
+        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+        n = len(rows)
+        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
+        ns = np.array([r.size for r in rows] or [0], np.int64)
+        peaks = np.zeros(max(n, 1), np.float32)
+        L = lib()
+        L.ptts_true_peak_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _FP]
+        _check(L.ptts_true_peak_rows(self.h, pp, _ip(ns), n, _fp(peaks)))
+        return peaks[0] if single else peaks[:n]
 
     def _loudness_rows(self, x, target):
         single = not isinstance(x, (list, tuple))
@@ -1405,12 +1432,94 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
     nz, dc = bool(getattr(cfg, "normalize", False)), bool(getattr(cfg, "dc_block", False))
     fi, fo = float(getattr(cfg, "fade_in_ms", 0.0)), float(getattr(cfg, "fade_out_ms", 0.0))
     eq = getattr(cfg, "eq", None)
-    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None):
+    tp = getattr(cfg, "true_peak_dbtp", None)
+    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None):
         return None
     o = DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
     if eq is not None:
         o.eq = eq.h
+    if tp is not None:
+        o._ext = DspExt(true_peak_dbtp=float(tp))   # (kept by the struct, which the request keeps: the handle lives as long as the call)
+        o.ext = o._ext.h
     return o
+
+
+class DspExt:
+    """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: the handle switches
+    nothing on).  It belongs to no model; keep it alive while requests that name it are running."""
+
+    def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None):
+        o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
+                                                     0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
+        L = lib()
+        L.ptts_dsp_ext_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.ptts_dsp_ext_free.argtypes = [C.c_void_p]
+        L.ptts_dsp_ext_free.restype = None
+        h = C.c_void_p()
+        self.h = None
+        _check(L.ptts_dsp_ext_create(C.byref(o), C.byref(h)))
+        self.h = h.value
+
+    def free(self):
+        if self.h:
+            lib().ptts_dsp_ext_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():
+            return
+        self.free()
+
+
+def true_peak(samples) -> float:
+    """ptts_true_peak: the true peak (linear, an f32) of mono f32 samples at 24 kHz, eight times oversampled.  Host code."""
+    x = _f32(samples).reshape(-1)
+    out = C.c_float(0.0)
+    L = lib()
+    L.ptts_true_peak.argtypes = [_FP, C.c_int64, C.POINTER(C.c_float)]
+    _check(L.ptts_true_peak(_fp(x), x.size, C.byref(out)))
+    return np.float32(out.value)
+
+
+def true_peak_limit(samples, ceiling_dbtp: float):
+    """ptts_true_peak_limit: (a new array scaled by ceiling / true peak where the true peak exceeds the ceiling, the true peak before).  Host code."""
+    x = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    out = C.c_float(0.0)
+    L = lib()
+    L.ptts_true_peak_limit.argtypes = [_FP, C.c_int64, C.c_double, C.POINTER(C.c_float)]
+    _check(L.ptts_true_peak_limit(_fp(x), x.size, float(ceiling_dbtp), C.byref(out)))
+    return x, np.float32(out.value)
+
+
+def dsp_opts_error(opts: DspOpts) -> str:
+    """Test hook (ptts_debug_dsp_opts_error): the message the library refuses these options with, "" when they are fine.  No GPU."""
+    buf = C.create_string_buffer(512)
+    H = hooks()
+    H.ptts_debug_dsp_opts_error.restype = C.c_int64
+    H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
+    H.ptts_debug_dsp_opts_error(C.byref(opts), buf, len(buf))
+    return buf.value.decode(errors="replace")
+
+
+def true_peak_taps():
+    """Test hook (ptts_debug_true_peak_taps): (the meter's f32 taps [L][K], dlo)."""
+    L_, K_, dlo = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    H = hooks()
+    H.ptts_debug_true_peak_taps.argtypes = [_FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    _check(H.ptts_debug_true_peak_taps(None, C.byref(L_), C.byref(K_), C.byref(dlo)))
+    out = np.zeros((L_.value, K_.value), np.float32)
+    _check(H.ptts_debug_true_peak_taps(_fp(out), None, None, None))
+    return out, int(dlo.value)
+
+
+def true_peak_oversample(samples) -> np.ndarray:
+    """Test hook (ptts_debug_true_peak_oversample): the eight-fold oversampled signal true_peak() takes its maximum over, [8 n] f32.  Host code."""
+    x = _f32(samples).reshape(-1)
+    y = np.zeros(8 * x.size, np.float32)
+    H = hooks()
+    H.ptts_debug_true_peak_oversample.argtypes = [_FP, C.c_int64, _FP]
+    _check(H.ptts_debug_true_peak_oversample(_fp(x), x.size, _fp(y)))
+    return y
 
 
 def _eq_sections(sections):

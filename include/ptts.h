@@ -131,21 +131,32 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * -> fade out -> egress.  The host statement of the result: ptts_loudness_normalize, or ptts_dsp_apply(normalize, dc_block, 0, 0); then
  * ptts_eq_apply; then ptts_dsp_apply(0, 0, fade_in_ms, fade_out_ms); then the egress.  The equaliser gives ptts_eq_apply's bits.  Peak and
  * loudness are measured on the raw decoded audio, in front of the equaliser: a boosting equaliser can push samples past +-1, and the PCM16
- * and G.711 egress clamps them as it always does (f32 leaves as it is).  There is no limiter. */
+ * and G.711 egress clamps them as it always does (f32 leaves as it is) -- unless the request sets a true-peak ceiling.
+ *
+ * The true-peak ceiling (`ext`, a handle of ptts_dsp_ext_create below with true_peak = 1) is the last stage.  The whole order of a request's
+ * chain: the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out -> true-peak ceiling -> egress.  The host statement of
+ * the result: everything before the ceiling as above, then ptts_true_peak_limit(samples, n, ceiling_dbtp, NULL), then the egress; the device
+ * gives ptts_true_peak_limit's bits.  It is a STATIC ceiling, not a limiter: the true peak of the whole utterance is measured and, where it
+ * exceeds the ceiling, every sample is scaled by the one gain ceiling / true peak -- nothing pumps, and an utterance under the ceiling is not
+ * touched.  The ceiling holds for the 24 kHz signal: rate conversion and PCM16 or G.711 quantisation come after it and may add a little. */
 #if defined(__GNUC__)
 #define PTTS_ANON __extension__
 #else
 #define PTTS_ANON
 #endif
 typedef struct ptts_eq ptts_eq;
+typedef struct ptts_dsp_ext ptts_dsp_ext;
 typedef struct ptts_dsp_opts {
     int32_t normalize;      /* PeakNormalize */
     int32_t dc_block;       /* DCBlock, 20 Hz, Q 0.707, at 24 kHz */
     double  fade_in_ms;     /* <= 0: none */
     double  fade_out_ms;
     PTTS_ANON union {
-        int32_t reserved[4];    /* reserved[2] and reserved[3] must be 0 */
-        const ptts_eq* eq;      /* lies over reserved[0..1]: NULL, or a live handle of ptts_eq_create (borrowed for the call) */
+        int32_t reserved[4];    /* no word is left: eq lies over reserved[0..1], ext over reserved[2..3] */
+        PTTS_ANON struct {
+            const ptts_eq* eq;           /* NULL, or a live handle of ptts_eq_create (borrowed for the call) */
+            const ptts_dsp_ext* ext;     /* NULL, or a live handle of ptts_dsp_ext_create (borrowed for the call): further per-request options */
+        };
     };
 } ptts_dsp_opts;
 
@@ -198,9 +209,10 @@ typedef struct ptts_request {
      * offsets and buffers count samples at this rate: n_frames * 0.08 * sample_rate.  Other values: PTTS_EINVAL naming the rate. */
     int32_t sample_rate;
     /* post-processing on the device, in front of the egress above (borrowed for the call).  NULL, or a struct with nothing switched on:
-     * none.  PTTS_EINVAL naming the field for a negative or NaN fade, a non-zero reserved word, an `eq` that is not a live handle of
-     * ptts_eq_create ("dsp: eq"), and for any switch together with pcm_callback (the peak and the end of the utterance are not known when
-     * samples are handed over; dc_block, fade_in_ms and eq are refused with it as well, for now). */
+     * none.  PTTS_EINVAL naming the field for a negative or NaN fade, an `eq` that is not a live handle of ptts_eq_create ("dsp: eq"), an
+     * `ext` that is not a live handle of ptts_dsp_ext_create ("dsp: ext ... (reserved[2..3])": junk in those words is refused, never read),
+     * and for any switch together with pcm_callback (the peak and the end of the utterance are not known when samples are handed over;
+     * dc_block, fade_in_ms, eq and ext are refused with it as well, for now). */
     const ptts_dsp_opts* dsp;
 } ptts_request;
 
@@ -261,7 +273,7 @@ int  ptts_dsp_rows(ptts_model* m, const float* const* in, const int64_t* n, int3
  * ptts_loudness: *lufs receives the loudness, -INFINITY when no block passes the gates (fewer than 9600 samples, silence, below -70 LUFS).
  * ptts_loudness_normalize, in place: samples *= gain with gain = min((float)sqrt(T / M), 1.0f / peak) -- T = 10^((target + 0.691) / 10), M the
  * gated mean square, peak the sample peak of ptts_dsp_apply's normalise -- one f32 product per sample; the ceiling means the result never
- * clips and may stay under the target (no true-peak limiting).  The gain stays 1 (samples untouched) when no block passes the gates or M is
+ * clips and may stay under the target (the SAMPLE peak is held; for the true peak see ptts_true_peak_limit).  The gain stays 1 (samples untouched) when no block passes the gates or M is
  * not finite.  *measured (optional) receives the loudness before the gain.  target_lufs: -70 .. -1, else PTTS_EINVAL.
  * Non-finite samples are not treated specially, as in normalise: a NaN never wins the peak and a block whose energy is NaN fails both gates
  * (every comparison with it is false); an infinite sample makes the peak infinite and the ceiling 0. */
@@ -306,6 +318,39 @@ int  ptts_eq_create(const ptts_eq_section* s, int32_t n, ptts_eq** out);
 void ptts_eq_free(ptts_eq* e);
 int  ptts_eq_apply(const ptts_eq* e, float* samples, int64_t n);
 int  ptts_eq_rows(ptts_model* m, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
+
+/* Further per-request options of ptts_dsp_opts, behind a handle made from a size-versioned struct: the caller sets size =
+ * sizeof(ptts_dsp_ext_opts) as it compiled it, fields beyond that size read as 0, and a later library version adds fields at the end.
+ * ptts_dsp_ext_create answers PTTS_EINVAL naming the field for a size smaller than the two fields below ("size"), a size larger than the
+ * library knows with a non-zero byte beyond what it knows ("size"), a true_peak other than 0 or 1, and a ceiling_dbtp that is not a finite
+ * value from -60 to 0.  The handle holds host memory only and belongs to no model, like a ptts_eq; the caller keeps it alive while requests
+ * that name it are running.  ptts_dsp_ext_free(NULL) does nothing. */
+typedef struct ptts_dsp_ext_opts {
+    uint32_t size;          /* sizeof(ptts_dsp_ext_opts) as the caller compiled it; fields beyond it read as 0 */
+    int32_t  true_peak;     /* 1: keep the request's audio at or under ceiling_dbtp */
+    double   ceiling_dbtp;  /* -60 .. 0, finite (EBU R 128: -1) */
+} ptts_dsp_ext_opts;
+int  ptts_dsp_ext_create(const ptts_dsp_ext_opts* o, ptts_dsp_ext** out);
+void ptts_dsp_ext_free(ptts_dsp_ext* e);
+
+/* True peak at 24 kHz.  The row is oversampled eight times, to the 192 kHz of ITU-R BS.1770-4 Annex 2, by the
+ * polyphase filter of this library's resampler for the pair 24000 -> 192000 (8 phases of 54 taps, cutoff 0.45 cycles per sample, Kaiser beta
+ * 8.6, float64 rounded once to f32): y[8 i + p], for i in [0, n) and p in [0, 8), is one f32 fmaf chain from 0.0f over ascending k = 0 .. 53
+ * of x[i - 26 + k] * h[p][k], samples outside [0, n) reading as zero; nothing before sample 0 or at or beyond sample n is an output.
+ *     TP = max(max |x[i]|, max |y[j]|)
+ * as an f32, linear (20 log10 is the caller's).  A NaN never wins, as in normalise.  TP is never below the sample peak, so a ceiling at or
+ * under 0 dBTP also means that no sample clips.  Host and device run the same function and give the same bits.
+ * KNOWN LIMIT: content above about 10 kHz lies in the filter's transition band and is under-read (a 10 kHz tone reads 0.16 dB low).  Speech
+ * from this decoder has little energy there.
+ * ptts_true_peak: *peak receives TP; n = 0 gives 0.  Host.
+ * ptts_true_peak_limit, in place, host: c = (float)pow(10, ceiling_dbtp / 20); if TP > c every sample becomes the f32 product x * g with
+ * g = c / TP (an IEEE f32 division), otherwise nothing is written.  *peak_before (optional) receives TP.  ceiling_dbtp: -60 .. 0, finite, else
+ * PTTS_EINVAL.  A static gain, not a limiter.
+ * ptts_true_peak_rows: TP of rows of host samples on the device, by the measuring kernel a request's ceiling runs; shaped like
+ * ptts_loudness_rows.  peaks: [rows]. */
+int  ptts_true_peak(const float* samples, int64_t n, float* peak);
+int  ptts_true_peak_limit(float* samples, int64_t n, double ceiling_dbtp, float* peak_before);
+int  ptts_true_peak_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, float* peaks);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -555,7 +600,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_request.dsp (in the place of reserved2: the struct's size and every other offset are unchanged) with ptts_dsp_opts, and ptts_dsp_rows;
  * ptts_request.loudness (in the place of reserved[1], likewise), ptts_loudness, ptts_loudness_normalize, ptts_loudness_rows,
  * ptts_loudness_normalize_rows; ptts_dsp_opts.eq (over reserved[0..1] of ptts_dsp_opts: its size and every offset are unchanged) with
- * ptts_eq_section, ptts_eq_design, ptts_eq_response, ptts_eq_create, ptts_eq_free, ptts_eq_apply, ptts_eq_rows */
+ * ptts_eq_section, ptts_eq_design, ptts_eq_response, ptts_eq_create, ptts_eq_free, ptts_eq_apply, ptts_eq_rows; ptts_dsp_opts.ext (over
+ * reserved[2..3], likewise) with ptts_dsp_ext_opts, ptts_dsp_ext_create, ptts_dsp_ext_free, ptts_true_peak, ptts_true_peak_limit,
+ * ptts_true_peak_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of

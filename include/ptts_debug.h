@@ -109,6 +109,15 @@ int ptts_debug_kweighting(int32_t sample_rate, double out[10]);
 int ptts_debug_flow_cluster_inject(ptts_model* m, int32_t block);
 
 
+/* The check every entry point runs on a ptts_dsp_opts, without a model: out (cap bytes, terminated) receives its message, empty when the options are
+ * fine; returns the message's length.  No GPU. */
+int64_t ptts_debug_dsp_opts_error(const ptts_dsp_opts* opts, char* out, int64_t cap);
+/* The true-peak meter's taps (ptts_true_peak; csrc/true_peak.h): out [8][54] receives h[p][k] as f32, *L the phases (8), *K the taps per phase
+ * (54), *dlo the input offset of tap 0 (-26).  Any pointer may be NULL.  No GPU. */
+int ptts_debug_true_peak_taps(float* out /* [8][54] */, int32_t* L, int32_t* K, int32_t* dlo);
+/* ... and its oversampled signal on the host: y [8 n] receives y[8 i + p] of ptts_true_peak's definition for samples [n].  No GPU. */
+int ptts_debug_true_peak_oversample(const float* samples, int64_t n, float* y /* [8 n] */);
+
 #ifdef __cplusplus
 }
 #endif
