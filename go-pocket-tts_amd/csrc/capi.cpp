@@ -1029,47 +1029,57 @@ int64_t ptts_resample_length(int64_t n_in, int32_t in_rate, int32_t out_rate) {
     return resample_length(n_in, in_rate, out_rate);
 }
 
-// n host rows -> n host rows through one device buffer each way: rows packed 256-byte aligned, one k_resample launch per RowRing::kRows rows
+// the argument checks the host-rows entry points share, under the entry point's name in the messages
+struct RowsCheck {
+    const char* what; const char* bad = "negative";
+    void args(int32_t rows, bool any_null) const { if (rows < 0 || (rows > 0 && any_null)) throw Error(PTTS_EINVAL, strfmt("ptts-hip: %s: null argument", what)); }
+    void row(int i, int64_t n, bool any_null) const { if (n < 0 || (n > 0 && any_null)) throw Error(PTTS_EINVAL, strfmt("ptts-hip: %s: row %d is %s or null", what, i, bad)); }
+};
+
+static Model& model_of(ptts_model* h) {
+    if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+    return *h->m;
+}
+
+// n host rows -> n host rows through one device buffer each way (runtime.h PackedRows), one k_resample launch per RowRing::kRows rows
 static void device_convert(Model& m, const float* const* in, const int64_t* n_in, int32_t n, const RateFilter* f, const int64_t* n_out, int fmt,
                            void* const* out) {
     std::lock_guard<std::mutex> lock(m.mu);
     m.use_device();
     hipStream_t s = m.stream;
-    std::vector<size_t> ioff((size_t)n), ooff((size_t)n);
-    size_t ib = 0, ob = 0;
+    std::vector<size_t> ib((size_t)n), ob((size_t)n);
     for (int i = 0; i < n; i++) {
-        ioff[(size_t)i] = ib; ib += ((size_t)n_in[i] * sizeof(float) + 255) & ~(size_t)255;
-        ooff[(size_t)i] = ob; ob += ((size_t)n_out[i] * pcm_bytes(fmt) + 255) & ~(size_t)255;
+        ib[(size_t)i] = (size_t)n_in[i] * sizeof(float);
+        ob[(size_t)i] = (size_t)n_out[i] * pcm_bytes(fmt);
     }
-    char* di = m.work(25, ib).as<char>();
-    char* dout = m.work(26, ob).as<char>();
+    PackedRows di(m, WORK_CONVERT_IN, std::move(ib)), dout(m, WORK_CONVERT_OUT, std::move(ob));
     std::vector<ResampleRow> rows;
     for (int i = 0; i < n; i++) {
-        if (n_in[i] > 0) PTTS_HIP(hipMemcpyAsync(di + ioff[(size_t)i], in[i], (size_t)n_in[i] * sizeof(float), hipMemcpyHostToDevice, s));
-        if (n_out[i] > 0) rows.push_back(resample_row(f, (const float*)(di + ioff[(size_t)i]), n_in[i], dout + ooff[(size_t)i], 0, n_out[i], fmt));
+        if (n_in[i] > 0) di.upload(i, in[i], s);
+        if (n_out[i] > 0) rows.push_back(resample_row(f, (const float*)di.row(i), n_in[i], dout.row(i), 0, n_out[i], fmt));
     }
     resample_launch(m, rows, s);
     for (int i = 0; i < n; i++)
-        if (n_out[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], dout + ooff[(size_t)i], (size_t)n_out[i] * pcm_bytes(fmt), hipMemcpyDeviceToHost, s));
+        if (n_out[i] > 0) dout.download(i, out[i], s);
     PTTS_HIP(hipStreamSynchronize(s));
 }
 
 int ptts_resample(ptts_model* h, const float* const* in, const int64_t* n_in, int32_t n, int32_t in_rate, int32_t out_rate, float* const* out) {
     return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        Model& m = model_of(h);
         const std::string e = rate_pair_error(in_rate, out_rate);
         if (!e.empty()) throw Error(PTTS_EINVAL, e);
-        if (n < 0 || (n > 0 && (!in || !n_in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: resample: null argument");
+        const RowsCheck check{"resample", "empty"};
+        check.args(n, !in || !n_in || !out);
         std::vector<int64_t> n_out((size_t)n);
         for (int i = 0; i < n; i++) {
-            if (n_in[i] < 0 || (n_in[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: resample: row %d is empty or null", i));
+            check.row(i, n_in[i], !in[i] || !out[i]);
             n_out[(size_t)i] = resample_length(n_in[i], in_rate, out_rate);
         }
         if (in_rate == out_rate) {   // the identity: no taps, no launch
             for (int i = 0; i < n; i++) if (n_in[i] > 0) std::memcpy(out[i], in[i], (size_t)n_in[i] * sizeof(float));
             return;
         }
-        Model& m = *h->m;
         const RateFilter* f;
         {
             std::lock_guard<std::mutex> lock(m.mu);
@@ -1080,89 +1090,52 @@ int ptts_resample(ptts_model* h, const float* const* in, const int64_t* n_in, in
     });
 }
 
-// the device chain of ptts_request.dsp on host rows: upload (rows packed 256-byte aligned), the same launches, download
+// the device chain of ptts_request.dsp on host rows (dsp_rows_device: upload, the same launches, download)
 int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts, float* const* out) {
     return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
-        if (rows < 0 || (rows > 0 && (!in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: dsp: null argument");
-        if (opts) {
-            const std::string e = dsp_opts_error(*opts);
-            if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
-        }
-        for (int i = 0; i < rows; i++)
-            if (n[i] < 0 || (n[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: dsp: row %d is negative or null", i));
-        if (!dsp_active(opts)) {   // nothing switched on: a copy, no launch
+        Model& m = model_of(h);
+        const RowsCheck check{"dsp"};
+        check.args(rows, !in || !n || !out);
+        DspSpec spec;
+        const std::string e = dsp_resolve(opts, &spec);
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i] || !out[i]);
+        if (!spec.any()) {   // nothing switched on: a copy, no lock, no launch
             for (int i = 0; i < rows; i++) if (n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
             return;
         }
-        Model& m = *h->m;
-        std::lock_guard<std::mutex> lock(m.mu);
-        m.use_device();
-        hipStream_t s = m.stream;
-        std::vector<size_t> off((size_t)rows);
-        size_t bytes = 0;
-        for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
-        char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
-        std::vector<DspJob> jobs;
-        for (int i = 0; i < rows; i++) {
-            if (n[i] <= 0) continue;
-            PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
-            jobs.push_back(DspJob{(float*)(buf + off[(size_t)i]), n[i], opts});
-        }
-        dsp_launch(m, jobs, s);
-        for (int i = 0; i < rows; i++)
-            if (n[i] > 0) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
-        PTTS_HIP(hipStreamSynchronize(s));
+        dsp_rows_device(m, in, n, rows, std::vector<DspSpec>((size_t)rows, spec).data(), true, {out});
     });
 }
 
-// the device form of ptts_eq_apply on host rows: upload (rows packed 256-byte aligned), the launches of a request's `eq`, download
+// the device form of ptts_eq_apply on host rows: the launches of a request's `eq`; a row without an equaliser is copied on the host
 int ptts_eq_rows(ptts_model* h, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
     return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
-        if (rows < 0 || (rows > 0 && (!eq || !in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: eq: null argument");
-        std::vector<const EqScan*> sys((size_t)rows, nullptr);
+        Model& m = model_of(h);
+        const RowsCheck check{"eq"};
+        check.args(rows, !eq || !in || !n || !out);
+        std::vector<DspSpec> specs((size_t)rows);
         for (int i = 0; i < rows; i++) {
-            if (n[i] < 0 || (n[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d is negative or null", i));
-            if (eq[i] && !(sys[(size_t)i] = eq_lookup(eq[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d: the handle is not a live equaliser of ptts_eq_create", i));
+            check.row(i, n[i], !in[i] || !out[i]);
+            if (eq[i] && !(specs[(size_t)i].eq = eq_lookup(eq[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d: the handle is not a live equaliser of ptts_eq_create", i));
         }
-        Model& m = *h->m;
-        std::lock_guard<std::mutex> lock(m.mu);
-        m.use_device();
-        hipStream_t s = m.stream;
-        std::vector<size_t> off((size_t)rows);
-        size_t bytes = 0;
-        for (int i = 0; i < rows; i++) { off[(size_t)i] = bytes; if (sys[(size_t)i]) bytes += ((size_t)n[i] * sizeof(float) + 255) & ~(size_t)255; }
-        char* buf = m.work(30, std::max<size_t>(bytes, 256)).as<char>();
-        std::vector<DspJob> jobs;
-        for (int i = 0; i < rows; i++) {
-            if (n[i] <= 0) continue;
-            if (!sys[(size_t)i]) {   // no equaliser: a copy
-                if (out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
-                continue;
-            }
-            PTTS_HIP(hipMemcpyAsync(buf + off[(size_t)i], in[i], (size_t)n[i] * sizeof(float), hipMemcpyHostToDevice, s));
-            DspJob j{(float*)(buf + off[(size_t)i]), n[i], nullptr};
-            j.eq = sys[(size_t)i];
-            jobs.push_back(j);
-        }
-        dsp_launch(m, jobs, s);
-        for (int i = 0; i < rows; i++)
-            if (n[i] > 0 && sys[(size_t)i]) PTTS_HIP(hipMemcpyAsync(out[i], buf + off[(size_t)i], (size_t)n[i] * sizeof(float), hipMemcpyDeviceToHost, s));
-        PTTS_HIP(hipStreamSynchronize(s));
+        dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
     });
 }
 
+// target NULL: measurement only (lufs is required); otherwise out is, and lufs receives what was measured before
 static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
-    if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
-    if (rows < 0 || (rows > 0 && (!in || !n || (target && !out) || (!target && !lufs)))) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");
+    Model& m = model_of(h);
+    const RowsCheck check{"loudness"};
+    check.args(rows, !in || !n || (target && !out) || (!target && !lufs));
     if (target) {
         const std::string e = loud_target_error(*target);
         if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
     }
-    for (int i = 0; i < rows; i++)
-        if (n[i] < 0 || (n[i] > 0 && (!in[i] || (target && !out[i])))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: loudness: row %d is negative or null", i));
-    loudness_rows_device(*h->m, in, n, rows, target ? *target : 0.0, target ? out : nullptr, lufs, nullptr);
+    for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i] || (target && !out[i]));
+    DspSpec spec;
+    dsp_spec_loudness(spec, target);
+    dsp_rows_device(m, in, n, rows, std::vector<DspSpec>((size_t)rows, spec).data(), target != nullptr, {target ? out : nullptr, lufs});
     if (lufs) for (int i = 0; i < rows; i++) lufs[i] = loud_lufs(lufs[i]);
 }
 
@@ -1174,24 +1147,26 @@ int ptts_loudness_normalize_rows(ptts_model* h, const float* const* in, const in
     return guard([&] { loudness_rows(h, in, n, rows, &target_lufs, out, measured); });
 }
 
-// the device form of ptts_true_peak on host rows: upload, the measuring launch of a request's ceiling, the rows' words back
+// the device form of ptts_true_peak on host rows: the measuring launch of a request's ceiling alone, the rows' words back
 int ptts_true_peak_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, float* peaks) {
     return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
-        if (rows < 0 || (rows > 0 && (!in || !n || !peaks))) throw Error(PTTS_EINVAL, "ptts-hip: true peak: null argument");
-        for (int i = 0; i < rows; i++)
-            if (n[i] < 0 || (n[i] > 0 && !in[i])) throw Error(PTTS_EINVAL, strfmt("ptts-hip: true peak: row %d is negative or null", i));
-        true_peak_rows_device(*h->m, in, n, rows, peaks);
+        Model& m = model_of(h);
+        const RowsCheck check{"true peak"};
+        check.args(rows, !in || !n || !peaks);
+        for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i]);
+        DspSpec spec;
+        spec.true_peak = true;
+        dsp_rows_device(m, in, n, rows, std::vector<DspSpec>((size_t)rows, spec).data(), false, {nullptr, nullptr, nullptr, peaks});
     });
 }
 
 int ptts_pcm_encode(ptts_model* h, const float* in, int64_t n, int32_t pcm_format, void* out) {
     return guard([&] {
-        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        Model& m = model_of(h);
         if (pcm_format < PTTS_PCM_F32 || pcm_format > PTTS_PCM_ALAW) throw Error(PTTS_EINVAL, strfmt("ptts-hip: pcm_format %d is not a PTTS_PCM_* format", pcm_format));
         if (n < 0 || (n > 0 && (!in || !out))) throw Error(PTTS_EINVAL, "ptts-hip: pcm encode: null argument");
         if (n == 0) return;
-        device_convert(*h->m, &in, &n, 1, nullptr, &n, pcm_format, &out);
+        device_convert(m, &in, &n, 1, nullptr, &n, pcm_format, &out);
     });
 }
 

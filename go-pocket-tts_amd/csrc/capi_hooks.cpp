@@ -64,7 +64,9 @@ int ptts_debug_loudness_energies(ptts_model* h, const float* const* in, const in
         std::vector<std::vector<double>> sub((size_t)rows);
         if (h) {
             if (!h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
-            loudness_rows_device(*h->m, in, n, rows, 0.0, nullptr, nullptr, sub.data());
+            DspSpec spec;
+            dsp_spec_loudness(spec, nullptr);
+            dsp_rows_device(*h->m, in, n, rows, std::vector<DspSpec>((size_t)rows, spec).data(), false, {nullptr, nullptr, sub.data()});
         } else {
             for (int i = 0; i < rows; i++) loud_sub_energies(in[i], n[i], sub[(size_t)i]);
         }

@@ -163,7 +163,7 @@ int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* l
     zero(w.pcm, (size_t)(w.Pp + w.L[0]), s);
     if (rate == kNativeRate) PTTS_HIP(hipMemcpyAsync(w.pcm + w.Pp, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
     else {   // the clip at its own rate, resampled by k_resample straight into the encoder's input (no host round trip)
-        DevBuf& src = m.work(26, (size_t)n_samples * sizeof(float));
+        DevBuf& src = m.work(WORK_ENCODER_CLIP, (size_t)n_samples * sizeof(float));
         PTTS_HIP(hipMemcpyAsync(src.p, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
         resample_launch(m, {resample_row(rate_filter(m, rate, kNativeRate, s), src.as<float>(), n_samples, w.pcm + w.Pp, 0, n24, RS_F32)}, s);
     }

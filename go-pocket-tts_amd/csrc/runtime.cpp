@@ -1403,9 +1403,13 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         std::vector<DspJob> jobs;
         for (int64_t i = 0; i < n; i++) {
             const Delivery& u = g[(size_t)i];
-            if (u.res && !u.filled && u.nf > 0 && (dsp_active(u.req->dsp) || u.req->loudness) && result_buffer(*u.res, u.req->pcm_format)) {
-                DspJob j{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, u.req->dsp};
-                if (u.req->loudness) { j.loud = true; j.target_power = loud_target_power((double)u.req->loudness / 100.0); }
+            if (u.res && !u.filled && u.nf > 0 && request_postprocesses(*u.req) && result_buffer(*u.res, u.req->pcm_format)) {
+                // resolved now, not at admission: a handle freed since the request was checked ends the call with PTTS_EINVAL, nothing is launched
+                DspJob j{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, DspSpec()};
+                const std::string e = dsp_resolve(u.req->dsp, &j.spec);
+                if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+                const double target_lufs = (double)u.req->loudness / 100.0;   // 0.01 LUFS
+                if (u.req->loudness) dsp_spec_loudness(j.spec, &target_lufs);
                 jobs.push_back(j);
             }
         }
@@ -1446,7 +1450,7 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         const int fmt = g[(size_t)i].req->pcm_format;
         if (!result_is_pinned(result_buffer(r, fmt))) scratch += ((size_t)r.n_samples * pcm_bytes(fmt) + 255) & ~(size_t)255;
     }
-    char* sb = scratch ? m.work(24, scratch).as<char>() : nullptr;
+    char* sb = scratch ? m.work(WORK_EGRESS_PAGEABLE, scratch).as<char>() : nullptr;
     std::vector<ResampleRow> rows;
     std::vector<std::pair<void*, const void*>> copies;
     std::vector<size_t> copy_bytes;

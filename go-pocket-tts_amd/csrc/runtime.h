@@ -8,6 +8,8 @@
 #include "kernels.h"
 #include "model.h"
 #include "row_ring.h"
+#include "dsp_spec.h"
+#include "host_rows.h"
 
 namespace ptts {
 
@@ -34,6 +36,18 @@ struct DevBuf {
 };
 
 struct Batch;
+
+// Model::work's buffers of the egress and of the host-rows entry points, by name (the other slots are still numbers at their call sites).  Every
+// user holds Model::mu from its first use of a buffer until the work that reads it is queued on Model::stream (device_convert even waits for
+// it), so two names for one number never hold data at the same time.
+enum WorkSlot : size_t {
+    WORK_EGRESS_PAGEABLE = 24,   // results_deliver: converted rows whose result buffer is pageable, copied out from here
+    WORK_CONVERT_IN = 25,        // device_convert (ptts_resample, ptts_pcm_encode): the packed input rows
+    WORK_CONVERT_OUT = 26,       // ... and the packed output rows
+    WORK_ENCODER_CLIP = 26,      // mimi_encode_clip: a voice clip at its own rate, in front of k_resample.  Shares WORK_CONVERT_OUT's storage (see above)
+    WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words and per-tile scan states
+    WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin
+};
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
 constexpr int kNativeRate = 24000;            // the decoder's rate: requests at 0 / 24000 in f32 or PCM16 are delivered as before, without k_resample
@@ -116,6 +130,19 @@ struct Model {
     }
     const float* tcomb_for(int lsd_steps);
     void compute_tcomb(float s, float t, float* dst /* device [flow_dim] */);
+};
+
+// host rows packed into one work buffer of the model (host_rows.h: 256-byte aligned, a skipped row takes no bytes), and the copies of a row in
+// and out, queued on s.  The caller holds Model::mu.
+struct PackedRows {
+    std::vector<size_t> bytes, off;
+    char* base = nullptr;
+    PackedRows(Model& m, WorkSlot slot, std::vector<size_t> row_bytes, const bool* skip = nullptr) : bytes(std::move(row_bytes)), off(bytes.size()) {
+        base = m.work(slot, std::max<size_t>(pack_rows(bytes.data(), skip, (int)bytes.size(), off.data()), kRowAlign)).as<char>();
+    }
+    char* row(int i) const { return base + off[(size_t)i]; }
+    void upload(int i, const void* src, hipStream_t s) const { PTTS_HIP(hipMemcpyAsync(row(i), src, bytes[(size_t)i], hipMemcpyHostToDevice, s)); }
+    void download(int i, void* dst, hipStream_t s) const { PTTS_HIP(hipMemcpyAsync(dst, row(i), bytes[(size_t)i], hipMemcpyDeviceToHost, s)); }
 };
 
 // n_slots independent FlowLMState (flow_lm.go:45-49) in HBM + the per-step workspace
@@ -316,29 +343,27 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
 // a request's egress: its rate (0 -> 24000), whether it needs k_resample (another rate, or G.711), the bytes per sample of its format, and
 // its result buffer (pcm / pcm16 / pcm8 by format)
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
-// post-processing on the device (dsp_device.cpp, dsp.hip): whether a request's ptts_dsp_opts switch anything on; the message of a bad one
-// (empty: fine); one row of the chain (x: n samples at 24 kHz on the device, rewritten in place); the launches for a table of rows on s
-// (ext counts when it is a live handle with true_peak set; an address the registry does not know is never read)
-bool dsp_ext_active(const ptts_dsp_ext* e);
-inline bool dsp_active(const ptts_dsp_opts* o) {
-    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && dsp_ext_active(o->ext)));
-}
-std::string dsp_opts_error(const ptts_dsp_opts& o);
-// loud: the row is measured (BS.1770, dsp.hip) on its raw samples; target_power = 10^((target LUFS + 0.691) / 10) is what its gain aims at.
-// dsp_launch sets loud_out to the row's two device words (the mean square M as a double, then the f32 gain), valid until the model's next
-// DSP launch.  opts may be NULL for a loudness row.
-// eq: the row's equaliser (a live handle's system, eq.h eq_lookup; takes precedence over opts->eq, which dsp_launch looks up itself)
-// tp: the row's true peak is measured (true_peak.hip) and held at or under `ceiling` (linear); set by the caller, or by dsp_launch from a live
-// opts->ext, which it looks up itself.  dsp_launch sets tp_out to the row's device word (the true peak's uint32 image), valid like loud_out.
-struct DspJob {
-    float* x; int64_t n; const ptts_dsp_opts* opts; bool loud = false; double target_power = 0.0; double* loud_out = nullptr; const EqScan* eq = nullptr;
-    bool tp = false; float ceiling = 1.0f; uint32_t* tp_out = nullptr;
-};
-// apply false: loudness rows are measured only (M and the sub-block energies), no sample is rewritten
-void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
+// post-processing on the device (dsp_device.cpp, dsp.hip).  A row is resolved into a DspSpec (dsp_spec.h) before it is launched; whether a
+// request has any at all is asked without resolving it (dsp_active: one registry look-up at the most, no error)
+inline bool request_postprocesses(const ptts_request& r) { return dsp_active(r.dsp) || r.loudness != 0; }
 inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)
-    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || dsp_active(r.dsp) || r.loudness != 0;
+    return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || request_postprocesses(r);
 }
+double loud_target_power(double target_lufs);   // 10^((target + 0.691) / 10)
+// a row's loudness: measured, and normalised to *target_lufs (NULL: measured only, for a dsp_launch with apply == false)
+inline void dsp_spec_loudness(DspSpec& spec, const double* target_lufs) { spec.loud = true; spec.target_power = target_lufs ? loud_target_power(*target_lufs) : 1.0; }
+// one row of the chain: x, n samples at 24 kHz on the device, rewritten in place as spec says.  dsp_launch sets loud_out to a loudness row's two
+// device words (the mean square M as a double, then the f32 gain) and tp_out to a true-peak row's (the true peak's uint32 image); both are valid
+// until the model's next DSP launch
+struct DspJob { float* x; int64_t n; DspSpec spec; double* loud_out = nullptr; uint32_t* tp_out = nullptr; };
+// the launches for a table of rows on s.  apply false: loudness and true-peak rows are measured only, no sample is rewritten
+void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
+// the chain on host rows, one round trip: rows packed into one device buffer and uploaded, dsp_launch, the outputs read back, one wait.  Takes
+// Model::mu.  A row of no samples, or whose spec switches nothing on, takes no device bytes (and is copied on the host when out is given).
+// Outputs, each optional: out [rows] the samples (out[i] == in[i] is fine); M [rows] the mean squares of loudness rows (0: none); sub [rows] their
+// [4 ceil(n / 1920)] sub-block energies as the device computed them; true_peaks [rows] (0: none)
+struct DspRowsOut { float* const* out = nullptr; double* M = nullptr; std::vector<double>* sub = nullptr; float* true_peaks = nullptr; };
+void dsp_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const DspSpec* per_row, bool apply, const DspRowsOut& o);
 inline size_t pcm_bytes(int fmt) { return fmt == PTTS_PCM_F32 ? 4 : fmt == PTTS_PCM_S16 ? 2 : 1; }
 inline void* result_buffer(const ptts_result& r, int fmt) {
     return fmt == PTTS_PCM_F32 ? (void*)r.pcm : fmt == PTTS_PCM_S16 ? (void*)r.pcm16 : (void*)r.pcm8;
@@ -416,7 +441,6 @@ struct LoudScan;
 void loud_kweight_coeffs(int sample_rate, double out[10]);         // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
 LoudScan loud_scan_coeffs(int sample_rate);
 const LoudScan& loud_scan();                                       // at kNativeRate
-double loud_target_power(double target_lufs);                      // 10^((target + 0.691) / 10)
 double loud_lufs(double M);                                        // -0.691 + 10 log10(M); -inf for M == 0
 std::string loud_target_error(double target_lufs);                 // empty: -70 <= target <= -1
 void loud_sub_energies(const float* x, int64_t n, std::vector<double>& sub);   // [4 ceil(n / 1920)]: 480-sample energies, blocked form
@@ -424,12 +448,6 @@ double loud_gated_mean(const double* sub, int64_t n);              // the doubly
 double loud_measure(const float* x, int64_t n);                    // M of a row
 float loud_measure_gain(const float* x, int64_t n, double target_power, double* M_out);   // min((float)sqrt(T / M), 1 / peak), or 1
 double loud_normalize(float* x, int64_t n, double target_lufs);    // in place; returns M as measured before
-// the device form on host rows (dsp_device.cpp): upload, the launches of a request's `loudness`, download.  out NULL: measurement only.
-// M (optional) [rows]; sub (optional): per row its [4 ceil(n / 1920)] sub-block energies as the device computed them
-// ptts_true_peak_rows: the measuring launch alone over rows of host samples; peaks [rows] receives each row's true peak
-void true_peak_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, float* peaks);
-void loudness_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out, double* M,
-                          std::vector<double>* sub);
 
 // the weight broadcast of a multi-GPU start-up (broadcast.cpp)
 void rccl_unique_id(uint8_t out[128]);

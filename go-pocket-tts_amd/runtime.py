@@ -29,6 +29,7 @@ _PCM_DTYPES = {PCM_F32: "<f4", PCM_S16: "<i2", PCM_ULAW: "|u1", PCM_ALAW: "|u1"}
 
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int64)
+_DP = C.POINTER(C.c_double)
 _STEP_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
 _PCM_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 
@@ -235,6 +236,11 @@ def lib():
         L.ptts_resample_length.argtypes = [C.c_int64, C.c_int32, C.c_int32]
         L.ptts_resample.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_FP)]
         L.ptts_pcm_encode.argtypes = [C.c_void_p, _FP, C.c_int64, C.c_int32, C.c_void_p]
+        L.ptts_dsp_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), C.POINTER(_FP)]
+        L.ptts_eq_rows.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        L.ptts_true_peak_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _FP]
+        L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
+        L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
         L.ptts_voice_from_audio_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.ptts_wav_header.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
@@ -261,6 +267,9 @@ def hooks():
         H.ptts_debug_launch_counts.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
         H.ptts_mimi_layer_piece.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _FP, C.c_int64, C.c_int32, C.c_int32, _FP]
         H.ptts_debug_flow_cluster_inject.argtypes = [C.c_void_p, C.c_int32]
+        H.ptts_debug_loudness_energies.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_DP)]
+        H.ptts_debug_dsp_opts_error.restype = C.c_int64
+        H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
         _hooks = H
     return _hooks
 
@@ -273,6 +282,18 @@ def _check(rc: int):
 
 def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def _row_ptrs(arrays, ptr=_FP):
+    """The pointer array over a list of arrays (never of length 0: an empty list gives one NULL entry)."""
+    return (ptr * max(len(arrays), 1))(*[C.cast(a.ctypes.data, ptr) for a in arrays])
+
+
+def _rows_in(x):
+    """An array, or a list of arrays, as mono f32 rows for a rows entry point: (single, rows, n, their pointer array, their lengths as int64)."""
+    single = not isinstance(x, (list, tuple))
+    rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
+    return single, rows, len(rows), _row_ptrs(rows), np.array([r.size for r in rows] or [0], np.int64)
 
 
 def _fp(a: Optional[np.ndarray]):
@@ -611,86 +632,51 @@ class Model:
         rates = _rates(sample_rate, n)
         n24 = [c.size if int(r) == 24000 else max(resample_length(c.size, int(r), 24000), 0) for c, r in zip(clips, rates)]
         outs = [np.empty((max(mimi_encode_frames(k), 0), self.info.mimi_dim), np.float32) for k in n24]
-        pp = (_FP * n)(*[_fp(c) for c in clips])
         ns = np.array([c.size for c in clips], np.int64)
-        po = (_FP * n)(*[_fp(o) for o in outs])
-        _check(lib().ptts_mimi_encode_rates(self.h, pp, _ip(ns), rates.ctypes.data_as(C.POINTER(C.c_int32)), n, po))
+        _check(lib().ptts_mimi_encode_rates(self.h, _row_ptrs(clips), _ip(ns), rates.ctypes.data_as(C.POINTER(C.c_int32)), n, _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def resample(self, x, in_rate: int, out_rate: int):
         """ptts_resample: mono f32 rows (an array, or a list: one launch for all) from in_rate to out_rate on the device."""
-        single = not isinstance(x, (list, tuple))
-        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-        n = len(rows)
+        single, rows, n, pp, ns = _rows_in(x)
         outs = [np.empty(max(resample_length(r.size, in_rate, out_rate), 0), np.float32) for r in rows]
-        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-        po = (_FP * max(n, 1))(*[_fp(o) for o in outs])
-        ns = np.array([r.size for r in rows] or [0], np.int64)
-        _check(lib().ptts_resample(self.h, pp, _ip(ns), n, int(in_rate), int(out_rate), po))
+        _check(lib().ptts_resample(self.h, pp, _ip(ns), n, int(in_rate), int(out_rate), _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def dsp_rows(self, x, normalize: bool = False, dc_block: bool = False, fade_in_ms: float = 0.0, fade_out_ms: float = 0.0, opts: Optional[DspOpts] = None):
         """ptts_dsp_rows: dsp_apply's chain on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all)."""
-        single = not isinstance(x, (list, tuple))
-        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-        n = len(rows)
+        single, rows, n, pp, ns = _rows_in(x)
         outs = [np.empty(r.size, np.float32) for r in rows]
         o = opts if opts is not None else DspOpts(1 if normalize else 0, 1 if dc_block else 0, float(fade_in_ms), float(fade_out_ms))
-        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
-        ns = np.array([r.size for r in rows] or [0], np.int64)
-        L = lib()
-        L.ptts_dsp_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), C.POINTER(_FP)]
-        _check(L.ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), po))
+        _check(lib().ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def eq_rows(self, x, eq):
         """ptts_eq_rows: Eq.apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).  eq: one Eq for
         every row, or one per row (None copies that row)."""
-        single = not isinstance(x, (list, tuple))
-        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-        n = len(rows)
+        single, rows, n, pp, ns = _rows_in(x)
         eqs = list(eq) if isinstance(eq, (list, tuple)) else [eq] * n
         outs = [np.empty(r.size, np.float32) for r in rows]
         pe = (C.c_void_p * max(n, 1))(*[e.h if e is not None else None for e in eqs])
-        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
-        ns = np.array([r.size for r in rows] or [0], np.int64)
-        L = lib()
-        L.ptts_eq_rows.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
-        _check(L.ptts_eq_rows(self.h, pe, pp, _ip(ns), n, po))
+        _check(lib().ptts_eq_rows(self.h, pe, pp, _ip(ns), n, _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def true_peak_rows(self, x):
         """ptts_true_peak_rows: true_peak() of mono f32 rows at 24 kHz (an array, or a list: one launch for all), measured on the device."""
-        single = not isinstance(x, (list, tuple))
-        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-        n = len(rows)
-        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-        ns = np.array([r.size for r in rows] or [0], np.int64)
+        single, rows, n, pp, ns = _rows_in(x)
         peaks = np.zeros(max(n, 1), np.float32)
-        L = lib()
-        L.ptts_true_peak_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _FP]
-        _check(L.ptts_true_peak_rows(self.h, pp, _ip(ns), n, _fp(peaks)))
+        _check(lib().ptts_true_peak_rows(self.h, pp, _ip(ns), n, _fp(peaks)))
         return peaks[0] if single else peaks[:n]
 
     def _loudness_rows(self, x, target):
-        single = not isinstance(x, (list, tuple))
-        rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-        n = len(rows)
-        pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-        ns = np.array([r.size for r in rows] or [0], np.int64)
+        single, rows, n, pp, ns = _rows_in(x)
         lufs = np.zeros(max(n, 1), np.float64)
-        dp = lufs.ctypes.data_as(C.POINTER(C.c_double))
-        L = lib()
+        dp = lufs.ctypes.data_as(_DP)
         if target is None:
-            L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(C.c_double)]
-            _check(L.ptts_loudness_rows(self.h, pp, _ip(ns), n, dp))
+            _check(lib().ptts_loudness_rows(self.h, pp, _ip(ns), n, dp))
             return float(lufs[0]) if single else lufs[:n]
         outs = [np.empty(r.size, np.float32) for r in rows]
-        po = (_FP * max(n, 1))(*[_fp(v) for v in outs])
-        L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), C.POINTER(C.c_double)]
-        _check(L.ptts_loudness_normalize_rows(self.h, pp, _ip(ns), n, float(target), po, dp))
+        _check(lib().ptts_loudness_normalize_rows(self.h, pp, _ip(ns), n, float(target), _row_ptrs(outs), dp))
         return (outs[0], float(lufs[0])) if single else (outs, lufs[:n])
 
     def loudness_rows(self, x):
@@ -1494,10 +1480,7 @@ def true_peak_limit(samples, ceiling_dbtp: float):
 def dsp_opts_error(opts: DspOpts) -> str:
     """Test hook (ptts_debug_dsp_opts_error): the message the library refuses these options with, "" when they are fine.  No GPU."""
     buf = C.create_string_buffer(512)
-    H = hooks()
-    H.ptts_debug_dsp_opts_error.restype = C.c_int64
-    H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
-    H.ptts_debug_dsp_opts_error(C.byref(opts), buf, len(buf))
+    hooks().ptts_debug_dsp_opts_error(C.byref(opts), buf, len(buf))
     return buf.value.decode(errors="replace")
 
 
@@ -1615,17 +1598,9 @@ def loudness_normalize(samples, target_lufs: float):
 def loudness_energies(x, model=None):
     """Test hook (libptts_hooks.so ptts_debug_loudness_energies): the sums of squares of the K-weighted samples over each whole 480-sample sub-block
     of mono f32 rows at 24 kHz -- by the device kernels with a model, by the host instantiation of their functions without."""
-    single = not isinstance(x, (list, tuple))
-    rows = [_f32(x).reshape(-1)] if single else [_f32(r).reshape(-1) for r in x]
-    n = len(rows)
+    single, rows, n, pp, ns = _rows_in(x)
     outs = [np.zeros(r.size // 480, np.float64) for r in rows]
-    DP = C.POINTER(C.c_double)
-    pp = (_FP * max(n, 1))(*[_fp(r) for r in rows])
-    po = (DP * max(n, 1))(*[o.ctypes.data_as(DP) for o in outs])
-    ns = np.array([r.size for r in rows] or [0], np.int64)
-    H = hooks()
-    H.ptts_debug_loudness_energies.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DP)]
-    _check(H.ptts_debug_loudness_energies(model.h if model is not None else None, pp, _ip(ns), n, po))
+    _check(hooks().ptts_debug_loudness_energies(model.h if model is not None else None, pp, _ip(ns), n, _row_ptrs(outs, _DP)))
     return outs[0] if single else outs
 
 
