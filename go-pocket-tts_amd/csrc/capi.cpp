@@ -1123,6 +1123,25 @@ int ptts_eq_rows(ptts_model* h, const ptts_eq* const* eq, const float* const* in
     });
 }
 
+// the device form of ptts_compress_apply on host rows: the launches of a request's compressor; a row without one is copied on the host
+int ptts_compress_rows(ptts_model* h, const ptts_compressor_opts* const* c, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+    return guard([&] {
+        Model& m = model_of(h);
+        const RowsCheck check{"compressor"};
+        check.args(rows, !c || !in || !n || !out);
+        std::vector<DspSpec> specs((size_t)rows);
+        for (int i = 0; i < rows; i++) {
+            check.row(i, n[i], !in[i] || !out[i]);
+            if (!c[i]) continue;
+            const std::string e = cmp_opts_error(c[i]);
+            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
+            specs[(size_t)i].compress = true;
+            specs[(size_t)i].cmp = cmp_design(*c[i]);
+        }
+        dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
+    });
+}
+
 // target NULL: measurement only (lufs is required); otherwise out is, and lufs receives what was measured before
 static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
     Model& m = model_of(h);

@@ -1,0 +1,129 @@
+// compressor.cpp -- the host side of a request's dynamic range compressor (include/ptts.h ptts_compressor_opts, ptts_compress_*,
+// ptts_dsp_ext_set_compressor): the checks of the caller's options, the design (the only place where libm is asked: exp
+// for the two time constants, pow for the knee's lower edge), and ptts_compress_apply: compressor.h's functions in their blocked form -- the
+// functions compressor.hip's k_cmp_* kernels call, instantiated for the host -- so a request's compressor and ptts_compress_rows give these
+// bits.  No HIP header: the file builds with a plain C++ compiler (tests/test_compressor_cpu.py does, with sanitizers).
+#include <cmath>
+#include <cstddef>
+
+#include "true_peak.h"
+
+namespace ptts {
+
+namespace {
+int fail(const std::string& e) {
+    set_last_error("ptts-hip: " + e);
+    return PTTS_EINVAL;
+}
+
+bool range_error(const char* field, double v, double lo, double hi, std::string& out) {
+    if (std::isfinite(v) && v >= lo && v <= hi) return false;
+    out = strfmt("compressor: %s %g is not a finite value from %g to %g", field, v, lo, hi);
+    return true;
+}
+}  // namespace
+
+std::string cmp_opts_error(const ptts_compressor_opts* c) {
+    if (!c) return "compressor: null options";
+    constexpr size_t kKnown = sizeof(ptts_compressor_opts);
+    if (c->size < kKnown) return strfmt("compressor: size %u is smaller than the fields up to makeup_db (%zu bytes)", c->size, kKnown);
+    if (c->size > kKnown) {   // a caller newer than this library: whatever it says beyond what is known here must be "off"
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(c);
+        for (size_t i = kKnown; i < c->size; i++)
+            if (b[i]) return strfmt("compressor: size %u: byte %zu is not 0, and this library knows %zu bytes", c->size, i, kKnown);
+    }
+    if (c->reserved) return strfmt("compressor: reserved is %d, must be 0", c->reserved);
+    std::string e;
+    if (range_error("threshold_db", c->threshold_db, -60.0, 0.0, e)) return e;
+    if (range_error("ratio", c->ratio, 1.0, 100.0, e)) return e;
+    if (range_error("knee_db", c->knee_db, 0.0, 24.0, e)) return e;
+    if (range_error("attack_ms", c->attack_ms, 0.05, 200.0, e)) return e;
+    if (range_error("release_ms", c->release_ms, 5.0, 5000.0, e)) return e;
+    if (range_error("makeup_db", c->makeup_db, -24.0, 24.0, e)) return e;
+    return std::string();
+}
+
+CmpScan cmp_design(const ptts_compressor_opts& c) {
+#pragma clang fp contract(off)
+    CmpScan d{};
+    d.rho = std::exp(-1.0 / (c.release_ms * 24.0));
+    d.alpha = std::exp(-1.0 / (c.attack_ms * 24.0));
+    d.beta = 1.0 - d.alpha;
+    scan_powers<1>(&d.rho, &d.rho_run, &d.rho_tile);
+    scan_powers<1>(&d.alpha, &d.alpha_run, &d.alpha_tile);
+    d.thr_db = c.threshold_db;
+    d.knee_db = c.knee_db;
+    d.slope = 1.0 / c.ratio - 1.0;
+    d.knee_q = c.knee_db > 0.0 ? d.slope / (2.0 * c.knee_db) : 0.0;
+    d.makeup_db = c.makeup_db;
+    d.s_lo = std::pow(10.0, (c.threshold_db - 0.5 * c.knee_db) / 20.0);
+    d.g_lo = cmp_exp2((0.0 + c.makeup_db) * kCmpLog2PerDb);   // the curve's own value where it says 0 dB
+    return d;
+}
+
+void cmp_apply_blocked(const CmpScan& d, float* x, int64_t n) {
+    double Sp = 0.0, Ss = 0.0;
+    for (int64_t base = 0; base < n; base += kDspTile) {
+        const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
+        const auto count = [cnt](int l) { return std::max(0, std::min(kDspRun, cnt - l * kDspRun)); };
+        float* tile = x + base;
+        double tp[kDspLanes], ts[kDspLanes];
+        double t = Sp, Ep = 0.0;
+        for (int l = 0; l < kDspLanes; l++) {
+            const double e = cmp_run_p(d, tile + l * kDspRun, count(l), 0.0);
+            tp[l] = t;
+            t = cmp_fold_p(d.rho_run, t, e);
+            Ep = cmp_fold_p(d.rho_run, Ep, e);
+        }
+        double u[1] = {Ss}, Es[1] = {0.0};
+        for (int l = 0; l < kDspLanes; l++) {
+            const double e[1] = {cmp_run_s(d, tile + l * kDspRun, count(l), tp[l], 0.0)};
+            ts[l] = u[0];
+            scan_advance<1>(&d.alpha_run, u, e);
+            scan_advance<1>(&d.alpha_run, Es, e);
+        }
+        for (int l = 0; l < kDspLanes; l++) cmp_run_y(d, tile + l * kDspRun, count(l), tp[l], ts[l], tile + l * kDspRun);
+        Sp = cmp_fold_p(d.rho_tile, Sp, Ep);
+        double S1[1] = {Ss};
+        scan_advance<1>(&d.alpha_tile, S1, Es);
+        Ss = S1[0];
+    }
+}
+
+}  // namespace ptts
+
+using namespace ptts;
+
+extern "C" {
+
+int ptts_dsp_ext_set_compressor(ptts_dsp_ext* e, const ptts_compressor_opts* c) {
+    DspExt v;   // (the design is made outside the registry's mutex)
+    if (c) {
+        const std::string err = cmp_opts_error(c);
+        if (!err.empty()) return fail(err);
+        v.compress = true;
+        v.cmp = cmp_design(*c);
+    }
+    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.compress = v.compress; e->v.cmp = v.cmp; }))
+        return fail(strfmt("compressor: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
+    return PTTS_OK;
+}
+
+int ptts_compress_gain(const ptts_compressor_opts* c, double level_db, double* gain_db) {
+    if (!gain_db) return fail("compressor: null argument");
+    const std::string err = cmp_opts_error(c);
+    if (!err.empty()) return fail(err);
+    if (!std::isfinite(level_db)) return fail(strfmt("compressor: level_db %g is not finite", level_db));
+    *gain_db = 20.0 * std::log10(cmp_gain(cmp_design(*c), std::pow(10.0, level_db / 20.0)));
+    return PTTS_OK;
+}
+
+int ptts_compress_apply(const ptts_compressor_opts* c, float* samples, int64_t n) {
+    const std::string err = cmp_opts_error(c);
+    if (!err.empty()) return fail(err);
+    if ((!samples && n > 0) || n < 0) return fail("compressor: null samples");
+    cmp_apply_blocked(cmp_design(*c), samples, n);
+    return PTTS_OK;
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 namespace ptts {
 
 static_assert(sizeof(EqScan) == kDspEqBytes, "kernels.h sizes the DSP ring's tail by it");
+static_assert(sizeof(CmpScan) == kCmpScanBytes, "kernels.h sizes the compressor ring's tail by it");
 
 namespace {
 int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: min((int64)(ms / 1000 * 24000), n)
@@ -16,13 +17,57 @@ int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: mi
     const double f = ms / 1000.0 * (double)kNativeRate;
     return f >= (double)n ? n : (int64_t)f;
 }
+
+// The compressor's tables (compressor.hip), in front of everything that measures or rewrites a row: the jobs whose spec has one, up to kRows
+// rows with up to kCmpMaxDesigns distinct designs a table, which travel behind the rows in the same turn of the ring.  tiles: the rows' per-tile
+// states are taken from it, cmp_state_doubles each
+void cmp_launch(Model& m, const std::vector<DspJob>& jobs, double*& tiles, hipStream_t s) {
+    constexpr int kRows = RowRing<CmpRow>::kRows;
+    std::vector<CmpRow> rows;
+    std::vector<const CmpScan*> row_design;
+    for (const DspJob& j : jobs) {
+        if (j.n <= 0 || !j.spec.compress) continue;
+        const int64_t F = scan_tiles(j.n);
+        CmpRow r{};
+        r.x = j.x; r.n = j.n;
+        r.p_tiles = tiles;
+        r.s_tiles = tiles + scan_state_doubles<1>(F);
+        tiles += cmp_state_doubles(F);
+        rows.push_back(r);
+        row_design.push_back(&j.spec.cmp);
+    }
+    std::vector<CmpScan> designs;
+    for (size_t at = 0; at < rows.size();) {
+        int n = 0;
+        int64_t max_tiles = 0;
+        designs.clear();
+        for (; n < kRows && at + (size_t)n < rows.size(); n++) {
+            CmpRow& r = rows[at + (size_t)n];
+            const CmpScan& d = *row_design[at + (size_t)n];
+            size_t k = 0;
+            while (k < designs.size() && std::memcmp(&designs[k], &d, sizeof d) != 0) k++;
+            if (k == designs.size()) {
+                if (designs.size() == (size_t)kCmpMaxDesigns) break;   // the next table's
+                designs.push_back(d);
+            }
+            r.design = (int32_t)k;
+            max_tiles = std::max(max_tiles, scan_tiles(r.n));
+        }
+        if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: compressor: too many samples for one launch");
+        const void* designs_dev = nullptr;
+        const CmpRow* rows_dev = m.cmp_ring.stage(rows.data() + at, n, s, designs.data(), designs.size() * sizeof(CmpScan), &designs_dev);
+        launch_compressor(rows_dev, n, (int)max_tiles, static_cast<const CmpScan*>(designs_dev), s);
+        m.cmp_ring.done(s);
+        at += (size_t)n;
+    }
+}
 }  // namespace
 
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
     if (jobs.empty()) return;
     constexpr int kRows = RowRing<DspRow>::kRows;
-    // scratch: a peak word and a true-peak word per row, then the per-tile states of each DC row and each equaliser row and the block of each loudness row (scan_block.h)
+    // scratch: a peak word and a true-peak word per row, then the per-tile states of each compressor row, each DC row and each equaliser row and the block of each loudness row (scan_block.h)
     size_t tile_doubles = 0;
     for (size_t k = 0; k < jobs.size(); k++) {
         const DspJob& j = jobs[k];
@@ -30,12 +75,14 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         if (j.spec.dc_block) tile_doubles += scan_state_doubles<DspScan::N>(scan_tiles(j.n));
         if (j.spec.loud) tile_doubles += loud_doubles(scan_tiles(j.n));
         if (j.spec.eq) tile_doubles += (size_t)scan_tiles(j.n) * 4 * (size_t)j.spec.eq->S;
+        if (j.spec.compress && apply) tile_doubles += cmp_state_doubles(scan_tiles(j.n));
     }
     const size_t peak_bytes = (2 * jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;   // [jobs] sample peaks, then [jobs] true peaks
     char* scratch = m.work(WORK_DSP_SCRATCH, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
     uint32_t* peaks = reinterpret_cast<uint32_t*>(scratch);
     double* tiles = reinterpret_cast<double*>(scratch + peak_bytes);
     PTTS_HIP(hipMemsetAsync(peaks, 0, peak_bytes, s));
+    if (apply) cmp_launch(m, jobs, tiles, s);   // the first stage: what follows measures and rewrites the compressed samples (a measurement alone has no compressor: nothing may be rewritten)
     std::vector<DspRow> rows;
     std::vector<const EqScan*> row_eq;
     rows.reserve(jobs.size());
@@ -44,7 +91,7 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         const DspSpec& sp = j.spec;
         j.loud_out = nullptr;
         j.tp_out = nullptr;
-        if (j.n <= 0 || !sp.any()) continue;
+        if (j.n <= 0 || !sp.rest()) continue;   // (a compressor alone: no row of the DSP table)
         DspRow r{};
         r.x = j.x; r.n = j.n;
         r.fade_in = fade_samples(sp.fade_in_ms, j.n);

@@ -17,12 +17,14 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->fade_out_ms = o->fade_out_ms;
     out->true_peak = ext.true_peak;
     out->ceiling = ext.ceiling;
+    out->compress = ext.compress;
+    out->cmp = ext.cmp;
     return std::string();
 }
 
 bool dsp_active(const ptts_dsp_opts* o) {
     DspExt ext;
-    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && ext.true_peak));
+    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && (ext.true_peak || ext.compress)));
 }
 
 }  // namespace ptts

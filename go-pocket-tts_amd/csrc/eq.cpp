@@ -133,6 +133,13 @@ bool handle_live(const void* h, HandleKind kind) {
     return h && live().count({h, kind});
 }
 
+bool handle_locked(const void* h, HandleKind kind, void (*f)(void* ctx), void* ctx) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    if (!h || !live().count({h, kind})) return false;
+    f(ctx);
+    return true;
+}
+
 const EqScan* eq_lookup(const ptts_eq* e) { return handle_live(e, HANDLE_EQ) ? &e->sc : nullptr; }
 
 }  // namespace ptts

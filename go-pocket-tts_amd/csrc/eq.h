@@ -1,6 +1,7 @@
 // eq.h -- what eq.cpp (the host side of a request's equaliser, no HIP header) shares with the device side (dsp_device.cpp, capi.cpp, runtime.cpp).
 #pragma once
 #include <string>
+#include <type_traits>
 
 #include "../../include/ptts.h"
 #include "scan_block.h"
@@ -26,6 +27,12 @@ enum HandleKind : int { HANDLE_EQ = 1, HANDLE_DSP_EXT = 2 };
 void handle_add(const void* h, HandleKind kind);
 bool handle_take(const void* h, HandleKind kind);    // true: it was live, and is no more
 bool handle_live(const void* h, HandleKind kind);
+// f() under the registry's mutex if h is live (false: it is not, and f was not called): what reads or writes a handle whose owner may change it
+bool handle_locked(const void* h, HandleKind kind, void (*f)(void* ctx), void* ctx);
+template <class F>
+inline bool handle_with(const void* h, HandleKind kind, F&& f) {   // (no type erasure: every delivered row's ext_lookup comes through here)
+    return handle_locked(h, kind, [](void* ctx) { (*static_cast<std::remove_reference_t<F>*>(ctx))(); }, &f);
+}
 // the handle's system, or null when e is not one ptts_eq_create returned and ptts_eq_free has not
 // yet taken (e itself is not read)
 const EqScan* eq_lookup(const ptts_eq* e);

@@ -286,7 +286,7 @@ extern std::atomic<int64_t> g_resample_launches;
 // row's own grid, so a row's bits do not depend on the rows beside it.
 // Loudness rows (DSP_LOUD): k_dsp_peak as for normalise, then k_loud_summary + k_loud_carry (the K-weighting cascade's four states per tile,
 // as the DC block's two), k_loud_energy (each tile's four sub-block energies) and k_loud_gate (block energies, both gates, the mean square M
-// and the row's f32 gain with the 1 / peak ceiling) on the RAW samples; k_dsp_summary and k_dsp_apply then take the row's gain from that word
+// and the row's f32 gain with the 1 / peak ceiling) on the samples as they come (raw, or as the compressor in front left them); k_dsp_summary and k_dsp_apply then take the row's gain from that word
 // where normalise's gain sits.  Tables without such a row launch the kernels they launched before it existed.
 // Equaliser rows (DSP_EQ): k_eq_summary + k_eq_carry + k_eq_apply behind k_dsp_apply, on what it stored (gain and DC block applied, rounded
 // to f32): the row's own cascade of 1 .. 4 sections (scan_block.h EqScan, 2 .. 8 states per tile), then the fades, which k_dsp_apply leaves to
@@ -328,6 +328,25 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
 // launch_dsp's last two (true_peak.hip): the true peak of every DSP_TP row into its word; the gain c / TP over the rows whose word exceeds c
 void launch_tp_peak(const DspRow* rows_dev, int n, int max_tiles, const TpTaps& taps, hipStream_t stream);
 void launch_tp_scale(const DspRow* rows_dev, int n, int max_tiles, hipStream_t stream);
+
+// A request's compressor (compressor.hip, compressor.h): the first stage of the post-processing, on a table of its
+// own in front of launch_dsp's.  k_cmp_summary_p + k_cmp_carry_p (the peak detector's state entering each tile: a scan in the (max, times)
+// semiring), k_cmp_summary_s + k_cmp_carry_s (the same for the attack smoothing, a linear scan with one state whose runs recompute the detector
+// from its entering state) and k_cmp_apply (both states entering every run, the gain curve, one store), in place.  A table's distinct designs
+// (at most kCmpMaxDesigns) travel behind its rows; a row names its own by index.
+constexpr int kCmpMaxDesigns = 16;
+constexpr size_t kCmpScanBytes = 128;   // sizeof(CmpScan)
+struct CmpRow {
+    float* x;              // the row's samples (device), rewritten in place
+    int64_t n;             // samples; nothing at or beyond n is touched
+    double* p_tiles;       // the detector's per-tile states, [ceil(n / kDspTile)][2]: E_f, S_f (scan_block.h scan_E<1> / scan_S<1>)
+    double* s_tiles;       // the smoothing's, likewise
+    int32_t design, pad;   // the index of the row's design among the table's
+};
+static_assert(sizeof(CmpRow) == 40, "a turn of the compressor ring holds 256 of them");
+struct CmpScan;
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
+void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

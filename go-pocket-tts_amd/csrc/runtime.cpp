@@ -1403,14 +1403,16 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         std::vector<DspJob> jobs;
         for (int64_t i = 0; i < n; i++) {
             const Delivery& u = g[(size_t)i];
-            if (u.res && !u.filled && u.nf > 0 && request_postprocesses(*u.req) && result_buffer(*u.res, u.req->pcm_format)) {
+            if (u.res && !u.filled && u.nf > 0 && (u.req->dsp || u.req->loudness) && result_buffer(*u.res, u.req->pcm_format)) {
                 // resolved now, not at admission: a handle freed since the request was checked ends the call with PTTS_EINVAL, nothing is launched
+                // (whether the row has work is asked of the resolved spec; request_postprocesses, which counts an ext unseen, has kept every
+                // such request away from the decoder's direct store, so `stored` is false for a group that holds one)
                 DspJob j{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, DspSpec()};
                 const std::string e = dsp_resolve(u.req->dsp, &j.spec);
                 if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
                 const double target_lufs = (double)u.req->loudness / 100.0;   // 0.01 LUFS
                 if (u.req->loudness) dsp_spec_loudness(j.spec, &target_lufs);
-                jobs.push_back(j);
+                if (j.spec.any()) jobs.push_back(j);
             }
         }
         if (!jobs.empty()) dsp_launch(m, jobs, s);

@@ -102,6 +102,7 @@ struct Model {
     Prof prof;
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
+    RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
@@ -344,8 +345,11 @@ void resample_launch(Model& m, const std::vector<ResampleRow>& rows, hipStream_t
 // its result buffer (pcm / pcm16 / pcm8 by format)
 inline int request_rate(const ptts_request& r) { return r.sample_rate ? r.sample_rate : kNativeRate; }
 // post-processing on the device (dsp_device.cpp, dsp.hip).  A row is resolved into a DspSpec (dsp_spec.h) before it is launched; whether a
-// request has any at all is asked without resolving it (dsp_active: one registry look-up at the most, no error)
-inline bool request_postprocesses(const ptts_request& r) { return dsp_active(r.dsp) || r.loudness != 0; }
+// request may have any at all is asked without resolving it (dsp_active: one registry look-up at the most, no error).  An ext counts unseen
+// here, as an eq does in dsp_active: the answer decides before the decode whether the decoder may store straight into the result
+// (results_alloc), and must not turn to "no" because the handle died since admission -- such a request stays on the device-buffer path, where
+// results_deliver resolves it and refuses it.  (A live ext that switches nothing on costs its request the direct store, nothing else.)
+inline bool request_postprocesses(const ptts_request& r) { return dsp_active(r.dsp) || (r.dsp && r.dsp->ext) || r.loudness != 0; }
 inline bool request_converts(const ptts_request& r) {   // (a request with post-processing leaves through the device buffer as well)
     return request_rate(r) != kNativeRate || r.pcm_format == PTTS_PCM_ULAW || r.pcm_format == PTTS_PCM_ALAW || request_postprocesses(r);
 }

@@ -7,8 +7,6 @@
 #include "rate_taps.h"
 #include "true_peak.h"
 
-struct ptts_dsp_ext { ptts::DspExt v; };
-
 #if defined(__x86_64__) && (defined(__GNUC__) || defined(__clang__)) && !defined(__HIP_DEVICE_COMPILE__)
 #define PTTS_TP_FMA 1
 #endif
@@ -83,9 +81,7 @@ std::string tp_ceiling_error(double c) {
 }
 
 bool ext_lookup(const ptts_dsp_ext* e, DspExt* out) {
-    if (!handle_live(e, HANDLE_DSP_EXT)) return false;
-    *out = e->v;
-    return true;
+    return handle_with(e, HANDLE_DSP_EXT, [&] { *out = e->v; });
 }
 
 }  // namespace ptts
@@ -107,8 +103,10 @@ int ptts_dsp_ext_create(const ptts_dsp_ext_opts* o, ptts_dsp_ext** out) {
     if (o->true_peak != 0 && o->true_peak != 1) return fail(strfmt("dsp ext: true_peak %d is not 0 or 1", o->true_peak));
     const std::string e = tp_ceiling_error(o->ceiling_dbtp);
     if (!e.empty()) return fail("dsp ext: " + e);
-    ptts_dsp_ext* h = new (std::nothrow) ptts_dsp_ext{DspExt{o->true_peak == 1, tp_ceiling(o->ceiling_dbtp)}};
+    ptts_dsp_ext* h = new (std::nothrow) ptts_dsp_ext{};
     if (!h) { set_last_error("ptts-hip: out of host memory"); return PTTS_ENOMEM; }
+    h->v.true_peak = o->true_peak == 1;
+    h->v.ceiling = tp_ceiling(o->ceiling_dbtp);
     handle_add(h, HANDLE_DSP_EXT);
     *out = h;
     return PTTS_OK;

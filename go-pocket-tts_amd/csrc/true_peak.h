@@ -12,6 +12,7 @@
 #pragma once
 #include <cmath>
 
+#include "compressor.h"
 #include "eq.h"
 
 namespace ptts {
@@ -54,8 +55,11 @@ std::string tp_ceiling_error(double ceiling_dbtp);
 // c = (float)pow(10, dBTP / 20)
 inline float tp_ceiling(double ceiling_dbtp) { return (float)std::pow(10.0, ceiling_dbtp / 20.0); }
 
-// what a live ptts_dsp_ext says, by value (false: e is NULL or not live, and e is not read)
-struct DspExt { bool true_peak = false; float ceiling = 1.0f; };
+// what a live ptts_dsp_ext says, by value (false: e is NULL or not live, and e is not read): the ceiling, and the compressor that
+// ptts_dsp_ext_set_compressor attached (compressor.cpp), as designed.  Copied out under the registry's mutex, which the setter takes too
+struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; };
 bool ext_lookup(const ptts_dsp_ext* e, DspExt* out);
 
 }  // namespace ptts
+
+struct ptts_dsp_ext { ptts::DspExt v; };   // (true_peak.cpp makes and frees it, compressor.cpp sets its compressor)

@@ -75,6 +75,18 @@ class DspExtOpts(C.Structure):   # ptts_dsp_ext_opts
     _fields_ = [("size", C.c_uint32), ("true_peak", C.c_int32), ("ceiling_dbtp", C.c_double)]
 
 
+class CompressorOpts(C.Structure):   # ptts_compressor_opts
+    """A dynamic range compressor's options (ptts_compressor_opts): threshold_db -60 .. 0, ratio 1 .. 100, knee_db 0 .. 24, attack_ms 0.05 .. 200,
+    release_ms 5 .. 5000, makeup_db -24 .. 24.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32), ("threshold_db", C.c_double), ("ratio", C.c_double), ("knee_db", C.c_double),
+                ("attack_ms", C.c_double), ("release_ms", C.c_double), ("makeup_db", C.c_double)]
+
+    def __init__(self, threshold_db: float = -24.0, ratio: float = 4.0, knee_db: float = 6.0, attack_ms: float = 5.0, release_ms: float = 120.0,
+                 makeup_db: float = 0.0, size: Optional[int] = None, reserved: int = 0):
+        super().__init__(C.sizeof(CompressorOpts) if size is None else int(size), int(reserved), float(threshold_db), float(ratio), float(knee_db),
+                         float(attack_ms), float(release_ms), float(makeup_db))
+
+
 class EqSection(C.Structure):   # ptts_eq_section
     _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("freq_hz", C.c_double), ("gain_db", C.c_double), ("q", C.c_double)]
 
@@ -137,6 +149,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_rows", "ptts_loudness", "ptts_loudness_normalize", "ptts_loudness_rows", "ptts_loudness_normalize_rows",
     "ptts_eq_design", "ptts_eq_response", "ptts_eq_create", "ptts_eq_free", "ptts_eq_apply", "ptts_eq_rows",
     "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
+    "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -239,6 +252,10 @@ def lib():
         L.ptts_dsp_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), C.POINTER(_FP)]
         L.ptts_eq_rows.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
         L.ptts_true_peak_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _FP]
+        L.ptts_dsp_ext_set_compressor.argtypes = [C.c_void_p, C.POINTER(CompressorOpts)]
+        L.ptts_compress_gain.argtypes = [C.POINTER(CompressorOpts), C.c_double, _DP]
+        L.ptts_compress_apply.argtypes = [C.POINTER(CompressorOpts), _FP, C.c_int64]
+        L.ptts_compress_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CompressorOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -365,6 +382,9 @@ class RuntimeGenerateConfig:
     # a true-peak ceiling in dBTP (ptts_dsp_opts.ext; -60 .. 0, None: off): the last stage of the chain, true_peak_limit of what the stages above
     # made of this request's 24 kHz audio -- a static gain where the utterance's true peak exceeds the ceiling, not a limiter
     true_peak_dbtp: Optional[float] = None
+    # a dynamic range compressor (ptts_dsp_opts.ext, ptts_dsp_ext_set_compressor; None: off): the FIRST stage of the chain, compress_apply of this
+    # request's own raw 24 kHz audio; loudness and normalise are measured behind it
+    compressor: Optional[CompressorOpts] = None
 
 
 def _free_addr(addr: int):
@@ -659,6 +679,16 @@ class Model:
         outs = [np.empty(r.size, np.float32) for r in rows]
         pe = (C.c_void_p * max(n, 1))(*[e.h if e is not None else None for e in eqs])
         _check(lib().ptts_eq_rows(self.h, pe, pp, _ip(ns), n, _row_ptrs(outs)))
+        return outs[0] if single else outs
+
+    def compress_rows(self, x, compressor):
+        """ptts_compress_rows: compress_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
+        compressor: one CompressorOpts for every row, or one per row (None copies that row)."""
+        single, rows, n, pp, ns = _rows_in(x)
+        cs = list(compressor) if isinstance(compressor, (list, tuple)) else [compressor] * n
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        pc = (C.POINTER(CompressorOpts) * max(n, 1))(*[C.pointer(c) if c is not None else None for c in cs])
+        _check(lib().ptts_compress_rows(self.h, pc, pp, _ip(ns), n, _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def true_peak_rows(self, x):
@@ -1419,22 +1449,24 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
     fi, fo = float(getattr(cfg, "fade_in_ms", 0.0)), float(getattr(cfg, "fade_out_ms", 0.0))
     eq = getattr(cfg, "eq", None)
     tp = getattr(cfg, "true_peak_dbtp", None)
-    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None):
+    cmp_ = getattr(cfg, "compressor", None)
+    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None or cmp_ is not None):
         return None
     o = DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
     if eq is not None:
         o.eq = eq.h
-    if tp is not None:
-        o._ext = DspExt(true_peak_dbtp=float(tp))   # (kept by the struct, which the request keeps: the handle lives as long as the call)
+    if tp is not None or cmp_ is not None:
+        o._ext = DspExt(true_peak_dbtp=None if tp is None else float(tp), compressor=cmp_)   # (kept by the struct, which the request keeps: the handle lives as long as the call)
         o.ext = o._ext.h
     return o
 
 
 class DspExt:
-    """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: the handle switches
-    nothing on).  It belongs to no model; keep it alive while requests that name it are running."""
+    """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off) and a compressor
+    (a CompressorOpts; None: off).  With neither the handle switches nothing on.  It belongs to no model; keep it alive while requests that name it
+    are running, and set its compressor before they start."""
 
-    def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None):
+    def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -1445,6 +1477,12 @@ class DspExt:
         self.h = None
         _check(L.ptts_dsp_ext_create(C.byref(o), C.byref(h)))
         self.h = h.value
+        if compressor is not None:
+            self.set_compressor(compressor)
+
+    def set_compressor(self, compressor: Optional[CompressorOpts]):
+        """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
+        _check(lib().ptts_dsp_ext_set_compressor(self.h, None if compressor is None else C.byref(compressor)))
 
     def free(self):
         if self.h:
@@ -1455,6 +1493,20 @@ class DspExt:
         if sys is None or sys.is_finalizing():
             return
         self.free()
+
+
+def compress_gain(compressor: CompressorOpts, level_db: float) -> float:
+    """ptts_compress_gain: the static curve at level_db, in dB, makeup gain included, through the library's own log2 and exp2.  Host code."""
+    out = C.c_double(0.0)
+    _check(lib().ptts_compress_gain(C.byref(compressor), float(level_db), C.byref(out)))
+    return float(out.value)
+
+
+def compress_apply(compressor: CompressorOpts, samples) -> np.ndarray:
+    """ptts_compress_apply: the compressor over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
+    out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    _check(lib().ptts_compress_apply(C.byref(compressor), _fp(out), out.size))
+    return out
 
 
 def true_peak(samples) -> float:

@@ -138,7 +138,12 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * the result: everything before the ceiling as above, then ptts_true_peak_limit(samples, n, ceiling_dbtp, NULL), then the egress; the device
  * gives ptts_true_peak_limit's bits.  It is a STATIC ceiling, not a limiter: the true peak of the whole utterance is measured and, where it
  * exceeds the ceiling, every sample is scaled by the one gain ceiling / true peak -- nothing pumps, and an utterance under the ceiling is not
- * touched.  The ceiling holds for the 24 kHz signal: rate conversion and PCM16 or G.711 quantisation come after it and may add a little. */
+ * touched.  The ceiling holds for the 24 kHz signal: rate conversion and PCM16 or G.711 quantisation come after it and may add a little.
+ *
+ * The compressor (attached to the `ext` handle by ptts_dsp_ext_set_compressor below) is the FIRST stage, on the request's own raw 24 kHz
+ * audio.  The whole order of a request's chain: compressor -> the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out
+ * -> true-peak ceiling -> egress.  The host statement of the result: ptts_compress_apply, then everything as above; the device gives
+ * ptts_compress_apply's bits.  Peak and loudness are measured on the COMPRESSED audio, so a request still lands on its LUFS target. */
 #if defined(__GNUC__)
 #define PTTS_ANON __extension__
 #else
@@ -194,8 +199,8 @@ typedef struct ptts_request {
      * -7000 .. -100 (-2300: EBU R 128, -1600: streaming, IVR).  The request's result is what
      *     ptts_loudness_normalize(samples, n, loudness / 100.0, NULL)
      * makes of THAT REQUEST'S OWN 24 kHz f32 audio, bit for bit, THEN `dsp` (the gain sits where normalise's gain sits: the DC block reads
-     * x * gain, the fades follow), THEN the egress.  Loudness is measured on the raw decoded audio, so the final audio is at the target up to
-     * what the DC block and the fades remove.  PTTS_EINVAL naming the field for another value, together with dsp->normalize (one gain slot),
+     * x * gain, the fades follow), THEN the egress.  Loudness is measured on the decoded audio as the compressor leaves it (the raw decoded
+     * audio for a request without one), so the final audio is at the target up to what the DC block and the fades remove.  PTTS_EINVAL naming the field for another value, together with dsp->normalize (one gain slot),
      * and together with pcm_callback (the loudness is not known when samples are handed over). */
     int32_t loudness;
     /* Frame-granular streaming (the /tts/stream path, server.go:354-396, at finer grain than the reference's per-chunk
@@ -351,6 +356,42 @@ void ptts_dsp_ext_free(ptts_dsp_ext* e);
 int  ptts_true_peak(const float* samples, int64_t n, float* peak);
 int  ptts_true_peak_limit(float* samples, int64_t n, double ceiling_dbtp, float* peak_before);
 int  ptts_true_peak_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, float* peaks);
+
+/* Dynamic range compressor at 24 kHz: feed-forward, float64.  Per sample, from p = s = 0:
+ *     p = max(|x|, rho p)   with rho = exp(-1 / (release_ms * 24))      (a NaN never wins)
+ *     s = alpha s + (1 - alpha) p   with alpha = exp(-1 / (attack_ms * 24))
+ *     y = (float)(x * g(s)),   20 log10 g = curve(20 log10 s) + makeup_db
+ * The curve is the soft-knee one of Giannoulis, Massberg and Reiss (JAES 2012): with L the level and T, R, W the threshold, ratio and knee,
+ * 0 where 2 (L - T) < -W, (1 / R - 1)(L - T) where 2 (L - T) > W, (1 / R - 1)(L - T + W / 2)^2 / (2 W) between.  Both recurrences are evaluated
+ * as blocked scans on a fixed grid (runs of 30 samples, tiles of 1920; csrc/compressor.h), and that form is the definition: host and device run
+ * the same function and give the same bits.  It agrees with the sample-by-sample statement (libm's log10 and pow) to one f32 step at the
+ * row's peak.  No look-ahead, no side-chain filter, not a limiter: a transient shorter than the attack passes.
+ * Non-finite samples are not treated specially: a NaN sample comes out as NaN and touches nothing else; an infinite sample holds the level
+ * at +inf for the rest of the row, which a ratio above 1 thereby silences (csrc/compressor.h).
+ * ptts_compressor_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_dsp_ext_set_compressor attaches the compressor to a live handle of ptts_dsp_ext_create (c NULL: off again); a handle that is not live is
+ * PTTS_EINVAL and is not read.  Set it before requests name the handle, not while they run.  Refused together with pcm_callback like every
+ * other switch of `ext`.
+ * ptts_compress_gain: *gain_db receives the static curve at level_db (finite) including the makeup gain, through the library's own log2 and
+ * exp2.  Host.
+ * ptts_compress_apply: the compressor over samples[0, n) in place.  Host.
+ * ptts_compress_rows: the same on rows of host samples on the device, by the kernels a request's compressor runs; shaped like ptts_eq_rows.
+ * c[i] NULL copies row i. */
+typedef struct ptts_compressor_opts {
+    uint32_t size;          /* sizeof(ptts_compressor_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  reserved;      /* 0 */
+    double   threshold_db;  /* -60 .. 0 (dBFS of the detector's level) */
+    double   ratio;         /* 1 .. 100 (1: the curve does nothing) */
+    double   knee_db;       /* 0 .. 24 (0: hard knee) */
+    double   attack_ms;     /* 0.05 .. 200 */
+    double   release_ms;    /* 5 .. 5000 */
+    double   makeup_db;     /* -24 .. +24 */
+} ptts_compressor_opts;
+int  ptts_dsp_ext_set_compressor(ptts_dsp_ext* e, const ptts_compressor_opts* c);
+int  ptts_compress_gain(const ptts_compressor_opts* c, double level_db, double* gain_db);
+int  ptts_compress_apply(const ptts_compressor_opts* c, float* samples, int64_t n);
+int  ptts_compress_rows(ptts_model* m, const ptts_compressor_opts* const* c, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -602,7 +643,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_loudness_normalize_rows; ptts_dsp_opts.eq (over reserved[0..1] of ptts_dsp_opts: its size and every offset are unchanged) with
  * ptts_eq_section, ptts_eq_design, ptts_eq_response, ptts_eq_create, ptts_eq_free, ptts_eq_apply, ptts_eq_rows; ptts_dsp_opts.ext (over
  * reserved[2..3], likewise) with ptts_dsp_ext_opts, ptts_dsp_ext_create, ptts_dsp_ext_free, ptts_true_peak, ptts_true_peak_limit,
- * ptts_true_peak_rows */
+ * ptts_true_peak_rows; ptts_compressor_opts with ptts_dsp_ext_set_compressor (the handle is the extension point: no struct grows),
+ * ptts_compress_gain, ptts_compress_apply, ptts_compress_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
