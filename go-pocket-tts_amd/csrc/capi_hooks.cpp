@@ -499,6 +499,165 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     });
 }
 
+// ---- the fused SEANet blocks (csrc/resblock.hip, csrc/resblock_up.hip) stand-alone ----
+// the launch form resblock_plan / resblock_up_plan choose (no GPU: `cus` is an argument)
+int ptts_debug_resblock_plan(int32_t C, int32_t final_conv, int32_t w_bf16, int32_t fuse_up, int32_t B, int32_t rows, int32_t form, int32_t grid, int32_t cus, int32_t* out) {
+    return guard([&] {
+        if (!out || B < 1 || rows < 1 || cus < 1 || form < RES_FORM_AUTO || form > RES_FORM_PERS) throw Error(PTTS_EINVAL, "ptts_debug_resblock_plan: bad arguments");
+        const ResPlan p = fuse_up ? resblock_up_plan(B, rows, form, grid, cus) : resblock_plan(C, final_conv, w_bf16, B, rows, form, grid, cus);
+        out[0] = p.nw; out[1] = p.pers; out[2] = p.grid; out[3] = p.tiles; out[4] = p.tout;
+    });
+}
+
+// the loader's packers on a caller's matrix (no GPU)
+int ptts_debug_seanet_pack(int32_t kind, const float* rm, int32_t out, int32_t in, uint16_t* hi, uint16_t* lo) {
+    return guard([&] {
+        if (!rm || !hi || in < 32 || in % 32 || (kind != 2 && (out < 16 || out % 16)) || kind < 0 || kind > 2 || (kind == 2 && !lo))
+            throw Error(PTTS_EINVAL, "ptts_debug_seanet_pack: bad arguments");
+        if (kind == 0) pack_frag16(rm, (size_t)out, (size_t)in, hi, lo);
+        else if (kind == 1) {
+            if (out != 256) throw Error(PTTS_EINVAL, "ptts_debug_seanet_pack: the fused transposed convolution has 4 x 64 rows");
+            std::vector<float> rg((size_t)out * in);
+            regroup_convtr_rows(rm, out, in, out / 4, rg.data());
+            pack_frag16(rg.data(), (size_t)out, (size_t)in, hi, lo);
+        } else pack_final_frag(rm, (size_t)in, hi, lo);
+    });
+}
+
+// what the loader itself packed (no GPU): the plan's arena is filled on the host and the item's planes are copied out
+int ptts_debug_plan_seanet_frags(ptts_plan* hp, int32_t item, uint16_t* hi, uint16_t* lo, int64_t cap, int64_t* count, int32_t* dims) {
+    return guard([&] {
+        if (!hp || !count || !dims || item < 0 || item > 7) throw Error(PTTS_EINVAL, "ptts_debug_plan_seanet_frags: bad arguments");
+        const Desc& d = hp->p.desc;
+        size_t wf = NONE, wl = NONE, n = 0;
+        if (item < 7) {
+            const Lin& l = item < 3 ? d.rb1[item] : (item < 6 ? d.rb2[item - 3] : d.up[2]);
+            wf = l.wf; wl = l.wf_lo; dims[0] = l.out; dims[1] = l.in;
+            if (wf != NONE) n = frag16_count((size_t)l.out, (size_t)l.in);
+        } else {
+            wf = d.final_wf; wl = d.final_wf_lo; dims[0] = 1; dims[1] = d.final_k * d.sea_ch[3];
+            if (wf != NONE) n = frag16_count(16, (size_t)dims[1]);
+        }
+        dims[2] = wl != NONE;
+        *count = (int64_t)n;
+        if (!n || !hi) return;
+        if ((int64_t)n > cap || (wl != NONE && !lo)) throw Error(PTTS_EINVAL, "ptts_debug_plan_seanet_frags: buffers too small");
+        std::vector<uint8_t> host(d.total_bytes);
+        plan_fill(hp->p, host.data());
+        std::memcpy(hi, host.data() + wf, n * 2);
+        if (wl != NONE) std::memcpy(lo, host.data() + wl, n * 2);
+    });
+}
+
+// ONE launch of k_resblock / k_resblock_up on host operands.  Everything is checked before anything is launched; every output is pre-filled with
+// 0xff bytes and comes back whole; the slack rows of u and xin are NaN.  The weights go through the loader's own packers (model.h).
+int ptts_debug_resblock(const ptts_resblock_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_resblock: null argument");
+        const ptts_resblock_args& t = *pa;
+        const bool fin = t.final_conv != 0, up_ = t.fuse_up != 0, bf = t.w_bf16 != 0;
+        if (t.B < 1 || t.B > 64 || t.L < 1 || t.L > (1 << 16) || t.t0 < 0 || t.t1 <= t.t0 || t.t1 > t.L || t.pad < 0 || t.pad > 64 || t.slack < 0 || t.slack > 64 ||
+            t.form < RES_FORM_AUTO || t.form > RES_FORM_PERS || !t.w1 || !t.w2 || (!up_ && !t.u) || (fin ? (!t.wf || !t.pcm) : !t.uo))
+            throw Error(PTTS_EINVAL, "ptts_debug_resblock: bad arguments");
+        if (!((t.C == 64 && t.H == 32) || (t.C == 128 && t.H == 64))) throw Error(PTTS_EINVAL, "ptts_debug_resblock: unsupported widths (C / H is 64 / 32 or 128 / 64)");
+        if (t.pad < 2) throw Error(PTTS_EINVAL, "ptts_debug_resblock: pad < 2 (the kernel reads two rows of history)");
+        if (t.rows) {
+            if (!fin) throw Error(PTTS_EINVAL, "ptts_debug_resblock: row destinations need the final convolution");
+            if (t.t0 % 4) throw Error(PTTS_EINVAL, "ptts_debug_resblock: t0 % 4 != 0 with row destinations");
+            if (!t.row_out || t.row_bytes % 16 || t.row_bytes < (int64_t)t.L * 4) throw Error(PTTS_EINVAL, "ptts_debug_resblock: row_bytes must be a multiple of 16 and hold L f32 samples");
+            for (int b = 0; b < t.B; b++) if (t.rows[2 * b] < 0) throw Error(PTTS_EINVAL, "ptts_debug_resblock: negative lim");
+        }
+        if (up_) {
+            if (!bf) throw Error(PTTS_EINVAL, "ptts_debug_resblock: f32 weights with the fused form (its weights live in registers and LDS as bf16)");
+            if (t.C != 64 || !fin) throw Error(PTTS_EINVAL, "ptts_debug_resblock: the fused form is the 64-wide block with the final convolution");
+            if (!t.xin || !t.wup || t.x_pad < 1 || t.x_pad > 64 || t.x_slack < 0 || t.x_slack > 64 || t.x_L < 1) throw Error(PTTS_EINVAL, "ptts_debug_resblock: bad arguments of the fused form");
+            if ((int64_t)t.x_L * 4 != t.L) throw Error(PTTS_EINVAL, "ptts_debug_resblock: x_L * 4 != L");
+            if (t.t0 % 4) throw Error(PTTS_EINVAL, "ptts_debug_resblock: t0 % 4 != 0 with the fused form");
+            if (t.form == RES_FORM_TILE) throw Error(PTTS_EINVAL, "ptts_debug_resblock: the fused form is persistent only");
+        }
+        // the launch form: the production choice, or the caller's
+        ResPlan plan;
+        if (t.form == RES_FORM_AUTO) {
+            require_device();
+            plan = up_ ? resblock_up_plan(t.B, t.t1 - t.t0, RES_FORM_AUTO, 0, resblock_cus()) : resblock_plan(t.C, fin, bf, t.B, t.t1 - t.t0, RES_FORM_AUTO, 0, resblock_cus());
+            if (plan.grid == 0) throw Error(PTTS_EINVAL, "ptts_debug_resblock: the fused form is not taken at this size (resblock_up_supported's threshold); ask for form 2 with a grid");
+        } else {
+            plan = up_ ? resblock_up_plan(t.B, t.t1 - t.t0, t.form, t.grid, 1) : resblock_plan(t.C, fin, bf, t.B, t.t1 - t.t0, t.form, t.grid, 1);
+            if (plan.nw == 0) throw Error(PTTS_EINVAL, "ptts_debug_resblock: no persistent form of this block (bf16 weights; 64-wide with the final convolution, 128-wide without)");
+        }
+        const int64_t total = (int64_t)t.B * plan.tiles;
+        if (plan.pers && (plan.grid < 1 || plan.grid > total))
+            throw Error(PTTS_EINVAL, strfmt("ptts_debug_resblock: grid %d outside [1, B * tiles = %lld]: a block's first tile would lie past the last utterance", plan.grid, (long long)total));
+        if (!plan.pers && plan.grid != total) throw Error(PTTS_EINVAL, "ptts_debug_resblock: one block per tile");
+
+        // weights: the loader's packers
+        const int C = t.C, H = t.H, B = t.B, L = t.L;
+        const size_t n1 = frag16_count((size_t)H, (size_t)3 * C), n2 = frag16_count((size_t)C, (size_t)H), nf = frag16_count(16, (size_t)3 * C), nu = frag16_count(256, 256);
+        std::vector<uint16_t> w1h(n1), w1l(n1), w2h(n2), w2l(n2), wfh(nf), wfl(nf), wuh(nu);
+        pack_frag16(t.w1, (size_t)H, (size_t)3 * C, w1h.data(), bf ? nullptr : w1l.data());
+        pack_frag16(t.w2, (size_t)C, (size_t)H, w2h.data(), bf ? nullptr : w2l.data());
+        if (fin) pack_final_frag(t.wf, (size_t)3 * C, wfh.data(), wfl.data());
+        if (up_) {
+            std::vector<float> rg((size_t)256 * 256);
+            regroup_convtr_rows(t.wup, 256, 256, 64, rg.data());
+            pack_frag16(rg.data(), 256, 256, wuh.data(), nullptr);
+        }
+        require_device();
+        const int64_t urows = (int64_t)t.pad + L + t.slack, u_bs = urows * C, xrows = up_ ? (int64_t)t.x_pad + t.x_L + t.x_slack : 1, x_bs = xrows * 128;
+        const size_t u_bytes = (size_t)B * u_bs * 4, x_bytes = (size_t)B * x_bs * 4, pcm_bytes = (size_t)B * L * 4, row_bytes = t.rows ? (size_t)B * t.row_bytes : 0;
+        Tmp dU(u_bytes), dUo(u_bytes), dX(x_bytes), dPcm(pcm_bytes), dRows(row_bytes), dPr((size_t)B * sizeof(PcmRow)),
+            dW1(n1 * 2), dW1l(n1 * 2), dW2(n2 * 2), dW2l(n2 * 2), dWf(nf * 2), dWfl(nf * 2), dWu(nu * 2), dB1((size_t)H * 4), dB2((size_t)C * 4), dBf(16), dBu(64 * 4);
+        {   // rows [pad + L] of every utterance as given, NaN in the slack rows behind them
+            std::vector<float> img((size_t)B * u_bs, std::nanf(""));
+            if (t.u) for (int b = 0; b < B; b++) std::memcpy(img.data() + (size_t)b * u_bs, t.u + (size_t)b * (t.pad + L) * C, (size_t)(t.pad + L) * C * 4);
+            up(dU.p, img.data(), u_bytes);
+            if (up_) {
+                std::vector<float> xi((size_t)B * x_bs, std::nanf(""));
+                for (int b = 0; b < B; b++) std::memcpy(xi.data() + (size_t)b * x_bs, t.xin + (size_t)b * (t.x_pad + t.x_L) * 128, (size_t)(t.x_pad + t.x_L) * 128 * 4);
+                up(dX.p, xi.data(), x_bytes);
+            }
+        }
+        PTTS_HIP(hipMemset(dUo.p, 0xff, u_bytes)); PTTS_HIP(hipMemset(dPcm.p, 0xff, pcm_bytes));
+        if (row_bytes) PTTS_HIP(hipMemset(dRows.p, 0xff, row_bytes));
+        up(dW1.p, w1h.data(), n1 * 2); up(dW2.p, w2h.data(), n2 * 2);
+        if (!bf) { up(dW1l.p, w1l.data(), n1 * 2); up(dW2l.p, w2l.data(), n2 * 2); }
+        ResArgs a;
+        a.u = dU.as<float>(); a.u_bs = u_bs; a.pad = t.pad;
+        a.w1 = dW1.p; a.w2 = dW2.p;
+        if (!bf) { a.w1_lo = dW1l.p; a.w2_lo = dW2l.p; }
+        if (t.b1) { up(dB1.p, t.b1, (size_t)H * 4); a.b1 = dB1.as<float>(); }
+        if (t.b2) { up(dB2.p, t.b2, (size_t)C * 4); a.b2 = dB2.as<float>(); }
+        a.B = B; a.L = L; a.t0 = t.t0; a.t1 = t.t1; a.C = C; a.H = H; a.k1 = 3; a.k2 = 1; a.w_bf16 = bf; a.final_conv = fin;
+        if (fin) {
+            up(dWf.p, wfh.data(), nf * 2); up(dWfl.p, wfl.data(), nf * 2);
+            a.kf = 3; a.wf_hi = dWf.p; a.wf_lo = dWfl.p;
+            if (t.bf) { up(dBf.p, t.bf, 4); a.bf = dBf.as<float>(); }
+            a.pcm = dPcm.as<float>(); a.pcm_bs = L;
+            if (t.rows) {
+                std::vector<PcmRow> pr((size_t)B);
+                for (int b = 0; b < B; b++) pr[b] = PcmRow{dRows.as<uint8_t>() + (size_t)b * t.row_bytes, t.rows[2 * b], t.rows[2 * b + 1] != 0};
+                up(dPr.p, pr.data(), (size_t)B * sizeof(PcmRow));
+                a.pcm_rows = dPr.as<PcmRow>();
+            }
+        } else a.uo = dUo.as<float>();
+        if (up_) {
+            up(dWu.p, wuh.data(), nu * 2);
+            a.fuse_up = 1; a.xin = dX.as<float>(); a.x_bs = x_bs; a.x_pad = t.x_pad; a.x_L = t.x_L; a.CI = 128; a.up_stride = 4; a.wup = dWu.p;
+            if (t.bup) { up(dBu.p, t.bup, 64 * 4); a.bup = dBu.as<float>(); }
+        }
+        // refused before any launch: whatever the kernels' own predicates refuse
+        if (!(up_ ? resblock_up_shape_supported(a) : resblock_supported(a))) throw Error(PTTS_EINVAL, "ptts_debug_resblock: refused by resblock_supported / resblock_up_shape_supported");
+        if (up_) launch_resblock_up_as(a, plan, nullptr);
+        else launch_resblock_as(a, plan, nullptr);
+        PTTS_HIP(hipGetLastError());
+        PTTS_HIP(hipDeviceSynchronize());
+        if (t.launched) { t.launched[0] = plan.nw; t.launched[1] = plan.pers; t.launched[2] = plan.grid; t.launched[3] = plan.tiles; t.launched[4] = plan.tout; }
+        if (t.uo) down(t.uo, dUo.p, u_bytes);
+        if (t.pcm) down(t.pcm, dPcm.p, pcm_bytes);
+        if (t.rows) down(t.row_out, dRows.p, row_bytes);
+    });
+}
+
 int ptts_mimi_layer_piece(ptts_model* h, int32_t layer, int32_t which, const float* x, int64_t rows, int32_t pos0, int32_t rows_per_seg, float* out) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");

@@ -369,10 +369,22 @@ struct ResArgs {
     int fuse_up = 0; const float* xin = nullptr; int64_t x_bs = 0; int x_pad = 0, x_L = 0, CI = 0, up_stride = 0;
     const void* wup = nullptr; const float* bup = nullptr;
 };
-bool resblock_supported(const ResArgs& a);
-void launch_resblock(const ResArgs& a, hipStream_t stream);
-bool resblock_up_supported(const ResArgs& a);
+bool resblock_supported(const ResArgs& a);                    // the shape conditions; the block has no size threshold of its own
+void launch_resblock(const ResArgs& a, hipStream_t stream);   // = launch_resblock_as(a, resblock_plan(..., RES_FORM_AUTO, 0, resblock_cus()))
+bool resblock_up_shape_supported(const ResArgs& a);           // the fused form's shape conditions ...
+bool resblock_up_supported(const ResArgs& a);                 // ... and its size threshold (resblock_up_plan's automatic choice has a grid)
 void launch_resblock_up(const ResArgs& a, hipStream_t stream);
+// The launch form: one tile of `tout` new rows per block (grid = B * tiles), or `grid` persistent blocks of nw waves that walk the B * tiles tiles
+// (blockIdx.x, + gridDim.x, ...; 1 <= grid <= B * tiles: a block whose first tile is past the end would index past B).  resblock_plan / resblock_up_plan
+// are the only places that choose: form AUTO is the production choice (thresholds against `cus` compute units), TILE / PERS with `grid` are for the
+// block's test hook; grid 0 in the result: the form does not exist for this block (PERS), or the fused kernel is not taken (AUTO below its threshold).
+enum { RES_FORM_AUTO = 0, RES_FORM_TILE = 1, RES_FORM_PERS = 2 };
+struct ResPlan { int nw = 0, pers = 0, grid = 0, tiles = 0, tout = 0; };
+int resblock_cus();
+ResPlan resblock_plan(int C, int final_conv, int w_bf16, int B, int rows, int form, int grid, int cus);
+ResPlan resblock_up_plan(int B, int rows, int form, int grid, int cus);
+void launch_resblock_as(const ResArgs& a, const ResPlan& p, hipStream_t stream);
+void launch_resblock_up_as(const ResArgs& a, const ResPlan& p, hipStream_t stream);
 
 
 // The feed-forward half of a Mimi decoder-transformer layer as one kernel (ffn_fused.hip): x += ls * linear2(gelu(linear1(LayerNorm(x)))),

@@ -65,6 +65,47 @@ void pack_step_tiled_i8(const int8_t* q, size_t out, size_t in, uint8_t* dst) {
                     }
 }
 
+// Fragment-ordered bf16 copy for resblock.hip: [16-column tile][32-deep k step][lane][8] with lane l holding
+// W[tile*16 + (l & 15)][step*32 + (l >> 4)*8 .. +8) -- the row operand of v_mfma_f32_16x16x32_bf16, so a wave's fragment
+// load is one contiguous 1-KiB burst.  lo (f32 weights) receives a second plane with the bf16 residual (w - hi), the same
+// split the kernels apply to activations.  out % 16 == 0, in % 32 == 0.
+size_t frag16_count(size_t out, size_t in) { return (out / 16) * (in / 32) * 64 * 8; }
+void pack_frag16(const float* rm, size_t out, size_t in, uint16_t* hi, uint16_t* lo) {
+    const size_t nt = out / 16, ks = in / 32;
+    for (size_t t = 0; t < nt; t++)
+        for (size_t s = 0; s < ks; s++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const float v = rm[(t * 16 + (size_t)(lane & 15)) * in + s * 32 + (size_t)(lane >> 4) * 8 + j];
+                    const size_t e = ((t * ks + s) * 64 + lane) * 8 + j;
+                    const uint16_t h = f32_to_bf16_rne(v);
+                    hi[e] = h;
+                    if (lo) lo[e] = f32_to_bf16_rne(v - bf16_to_f32(h));
+                }
+}
+// The last transposed convolution inside the fused block (resblock_up.hip): the rows [(phase, channel)] of its GEMM operand regrouped so
+// that row q of the 16-row tile T holds phase q >> 2 of channel 8 (T >> 1) + 4 (T & 1) + (q & 3) -- a lane of the product then
+// owns four channels of ONE phase and the 64 lanes of a wave 64 consecutive output rows (conflict-free LDS writes)
+void regroup_convtr_rows(const float* rm, int out, int in, int oc, float* dst) {
+    for (int T = 0; T < out / 16; T++)
+        for (int q = 0; q < 16; q++) {
+            const int n = (q >> 2) * oc + 8 * (T >> 1) + 4 * (T & 1) + (q & 3);
+            std::copy(rm + (size_t)n * in, rm + (size_t)(n + 1) * in, dst + (size_t)(T * 16 + q) * in);
+        }
+}
+// The final convolution C -> 1 (w [k][ic]: w[tap * ic + c]) as column 0 of a 16-column fragment-ordered matrix, bf16 hi + lo planes; n % 32 == 0
+void pack_final_frag(const float* w, size_t n, uint16_t* hi, uint16_t* lo) {
+    for (size_t s = 0; s < n / 32; s++)
+        for (int lane = 0; lane < 64; lane++)
+            for (int j = 0; j < 8; j++) {
+                const size_t kk = s * 32 + (size_t)(lane >> 4) * 8 + j;   // = tap * ic + c
+                const float v = (lane & 15) == 0 ? w[kk] : 0.0f;
+                const uint16_t h = f32_to_bf16_rne(v);
+                hi[(s * 64 + lane) * 8 + j] = h;
+                lo[(s * 64 + lane) * 8 + j] = f32_to_bf16_rne(v - bf16_to_f32(h));
+            }
+}
+
 namespace {
 
 struct Walker {
@@ -161,30 +202,16 @@ struct Walker {
         fill_rowmajor(rm.data());
         pack_step_tiled(rm.data(), (size_t)l.out, (size_t)l.in, bf16w, host + l.wt);
     }
-    // Fragment-ordered bf16 copy for resblock.hip: [16-column tile][32-deep k step][lane][8] with lane l holding
-    // W[tile*16 + (l & 15)][step*32 + (l >> 4)*8 .. +8) -- the row operand of v_mfma_f32_16x16x32_bf16, so a wave's fragment
-    // load is one contiguous 1-KiB burst.  f32 weights get a second plane with the bf16 residual (w - hi), the same
-    // split the kernels apply to activations.
+    // the fragment-ordered copy for resblock.hip (pack_frag16 above); f32 weights get the lo plane as well
     void add_frag16(Lin& l, const std::function<void(float*)>& fill_rowmajor) {
         if (l.out % 16 != 0 || l.in % 32 != 0) return;
-        const size_t nt = (size_t)l.out / 16, ks = (size_t)l.in / 32, count = nt * ks * 64 * 8;
+        const size_t count = frag16_count((size_t)l.out, (size_t)l.in);
         l.wf = reserve(count * 2);
         if (!bf16w) l.wf_lo = reserve(count * 2);
         if (!host) return;
         std::vector<float> rm((size_t)l.out * l.in);
         fill_rowmajor(rm.data());
-        uint16_t* hi = reinterpret_cast<uint16_t*>(host + l.wf);
-        uint16_t* lo = bf16w ? nullptr : reinterpret_cast<uint16_t*>(host + l.wf_lo);
-        for (size_t t = 0; t < nt; t++)
-            for (size_t s = 0; s < ks; s++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 8; j++) {
-                        const float v = rm[(t * 16 + (size_t)(lane & 15)) * l.in + s * 32 + (size_t)(lane >> 4) * 8 + j];
-                        const size_t e = ((t * ks + s) * 64 + lane) * 8 + j;
-                        const uint16_t h = f32_to_bf16_rne(v);
-                        hi[e] = h;
-                        if (lo) lo[e] = f32_to_bf16_rne(v - bf16_to_f32(h));
-                    }
+        pack_frag16(rm.data(), (size_t)l.out, (size_t)l.in, reinterpret_cast<uint16_t*>(host + l.wf), bf16w ? nullptr : reinterpret_cast<uint16_t*>(host + l.wf_lo));
     }
     // linear1 [F][512] and linear2 [512][F] of a Mimi transformer layer as the LDS images of k_mimi_ffn (ffn_fused.hip), bf16: per chunk c of 32 hidden
     // units 64 KB that are copied to LDS as they are --
@@ -346,17 +373,11 @@ struct Walker {
         };
         l.w = add_mat((size_t)l.out * l.in, fill, &l.bf16);
         if (frag16 && bf16w && stride == 4 && oc == 64) {
-            // the last transposed convolution inside the fused block (resblock_up.hip): fragment-ordered, with the output columns regrouped so
-            // that column q of the 16-column tile T holds phase q >> 2 of channel 8 (T >> 1) + 4 (T & 1) + (q & 3) -- a lane of the product then
-            // owns four channels of ONE phase and the 64 lanes of a wave 64 consecutive output rows (conflict-free LDS writes)
+            // the last transposed convolution inside the fused block (resblock_up.hip): fragment-ordered, its rows regrouped (regroup_convtr_rows)
             add_frag16(l, [&](float* dst) {
                 std::vector<float> rm((size_t)l.out * l.in);
                 fill(rm.data());
-                for (int T = 0; T < l.out / 16; T++)
-                    for (int q = 0; q < 16; q++) {
-                        const int n = (q >> 2) * oc + 8 * (T >> 1) + 4 * (T & 1) + (q & 3);
-                        std::copy(rm.begin() + (size_t)n * l.in, rm.begin() + (size_t)(n + 1) * l.in, dst + (size_t)(T * 16 + q) * l.in);
-                    }
+                regroup_convtr_rows(rm.data(), l.out, l.in, oc, dst);
             });
         }
         if (has(name + ".bias"))
@@ -651,22 +672,13 @@ struct Walker {
             if (has(cn + ".bias")) d.final_b = add_f32(1, [&](float* dst) { f.decode_f32(cn + ".bias", dst); });
             d.n_params += (int64_t)ic * k;
             if ((ic * k) % 32 == 0) {   // one-column matrix in MFMA fragment order for the fused last block
-                const size_t ks = (size_t)ic * k / 32, count = ks * 64 * 8;
+                const size_t count = frag16_count(16, (size_t)ic * k);
                 d.final_wf = reserve(count * 2);
                 d.final_wf_lo = reserve(count * 2);
                 if (host) {
-                    std::vector<float> w = load(cn + ".weight");
-                    uint16_t* hi = reinterpret_cast<uint16_t*>(host + d.final_wf);
-                    uint16_t* lo = reinterpret_cast<uint16_t*>(host + d.final_wf_lo);
-                    for (size_t s = 0; s < ks; s++)
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int j = 0; j < 8; j++) {
-                                const size_t kk = s * 32 + (size_t)(lane >> 4) * 8 + j;   // = tap * ic + c
-                                const float v = (lane & 15) == 0 ? w[(kk % ic) * k + kk / ic] : 0.0f;
-                                const uint16_t h = f32_to_bf16_rne(v);
-                                hi[(s * 64 + lane) * 8 + j] = h;
-                                lo[(s * 64 + lane) * 8 + j] = f32_to_bf16_rne(v - bf16_to_f32(h));
-                            }
+                    std::vector<float> w = load(cn + ".weight"), tm((size_t)ic * k);
+                    for (int c = 0; c < ic; c++) for (int x = 0; x < k; x++) tm[(size_t)x * ic + c] = w[(size_t)c * k + x];
+                    pack_final_frag(tm.data(), tm.size(), reinterpret_cast<uint16_t*>(host + d.final_wf), reinterpret_cast<uint16_t*>(host + d.final_wf_lo));
                 }
             }
         }

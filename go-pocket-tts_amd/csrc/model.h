@@ -28,6 +28,13 @@ size_t step_tiled_bytes(size_t out, size_t in, int bytes_per_weight);
 void pack_step_tiled(const float* rm, size_t out, size_t in, bool bf16w, uint8_t* dst);
 void quantize_rows(std::vector<float>& rm, size_t out, size_t in, std::vector<float>& scale, std::vector<int8_t>& q);
 void pack_step_tiled_i8(const int8_t* q, size_t out, size_t in, uint8_t* dst);
+// The fused SEANet blocks' weight formats (model.cpp; resblock.hip and resblock_up.hip read them; the loader and the block's test hook pack with the
+// same code): a row-major [out][in] matrix in 16x16x32 MFMA fragment order as bf16 hi (+ lo: f32 weights) planes of frag16_count entries, the row
+// regrouping of the fused transposed convolution's operand, and the final convolution [k * ic] as a one-column fragment matrix (hi + lo).
+size_t frag16_count(size_t out, size_t in);
+void pack_frag16(const float* rm, size_t out, size_t in, uint16_t* hi, uint16_t* lo);
+void regroup_convtr_rows(const float* rm, int out, int in, int oc, float* dst);
+void pack_final_frag(const float* w, size_t n, uint16_t* hi, uint16_t* lo);
 
 struct Norm {  // linear.go:184-189
     size_t w = NONE, b = NONE;

@@ -313,43 +313,51 @@ bool resblock_supported(const ResArgs& a) {
            (a.final_conv ? (a.kf == 3 && a.wf_hi && a.wf_lo && (a.pcm_rows ? a.t0 % 4 == 0 : a.pcm != nullptr)) : (a.uo != nullptr && aligned16(a.uo))) && a.u_bs % 4 == 0 && a.t1 > a.t0;
 }
 
-template <int C, int H, int NW>
-static void launch_rb(const ResArgs& a, hipStream_t stream) {
-    const int tout = NW * 16 - (a.final_conv ? 4 : 2);
-    const int tiles = (a.t1 - a.t0 + tout - 1) / tout;
-    dim3 grid((unsigned)(a.B * tiles));
-    if (a.final_conv) {
-        if constexpr (C == 64) {
-            static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-            const int resident = 2 * cus;                    // 77 KB of LDS and 116 registers per lane: two blocks per CU
-            if (a.w_bf16 && a.B * tiles >= resident * 8) {   // enough tiles per block to amortise its 28-KB weight copy
-                hipLaunchKernelGGL((k_resblock<C, H, NW, true, true, true>), dim3((unsigned)resident), dim3(NW * 64), 0, stream, a);
-                return;
-            }
-        }
-        if (a.w_bf16) hipLaunchKernelGGL((k_resblock<C, H, NW, true, true>), grid, dim3(NW * 64), 0, stream, a);
-        else hipLaunchKernelGGL((k_resblock<C, H, NW, true, false>), grid, dim3(NW * 64), 0, stream, a);
+int resblock_cus() {
+    static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    return cus;
+}
+
+// The one place that chooses the launch form.  One tile per block: 128-row tiles at C = 64 (~50 KB of LDS: three blocks per CU), 64-row tiles at
+// C = 128 (same footprint).  Persistent (bf16 weights; the last block and the 128-wide plain block only):
+//   C = 64 + final conv: 77 KB of LDS and 116 registers per lane, two blocks per CU; taken when every block gets >= 8 tiles to amortise its 28-KB weight copy
+//   C = 128 plain:       96-row tiles, 139 KB of LDS with the 64 KB of weights, one block per CU (1458 -> 1055 us at batch 64); the same 8 tiles per block
+ResPlan resblock_plan(int C, int final_conv, int w_bf16, int B, int rows, int form, int grid, int cus) {
+    ResPlan p;
+    const int halo = final_conv ? 4 : 2;
+    const bool can_pers = w_bf16 && ((C == 64 && final_conv) || (C == 128 && !final_conv));
+    const int pnw = C == 64 ? 8 : 6, ptout = pnw * 16 - halo, ptiles = (rows + ptout - 1) / ptout;
+    const int resident = C == 64 ? 2 * cus : cus;
+    if (form == RES_FORM_PERS ? can_pers : (form == RES_FORM_AUTO && can_pers && B * ptiles >= resident * 8)) {
+        p.nw = pnw; p.pers = 1; p.tout = ptout; p.tiles = ptiles; p.grid = form == RES_FORM_PERS ? grid : resident;
+        return p;
+    }
+    if (form == RES_FORM_PERS) return p;          // no persistent instance of this block: grid 0
+    p.nw = C == 64 ? 8 : 4; p.tout = p.nw * 16 - halo; p.tiles = (rows + p.tout - 1) / p.tout; p.grid = B * p.tiles;
+    return p;
+}
+
+void launch_resblock_as(const ResArgs& a, const ResPlan& p, hipStream_t stream) {
+    note_launch(a.final_conv ? "k_resblock+final" : "k_resblock");
+    const dim3 grid((unsigned)p.grid), block((unsigned)p.nw * 64);
+    const bool fin = a.final_conv != 0, bf = a.w_bf16 != 0;
+    if (a.C == 64) {
+        if (p.pers) hipLaunchKernelGGL((k_resblock<64, 32, 8, true, true, true>), grid, block, 0, stream, a);
+        else if (fin && bf) hipLaunchKernelGGL((k_resblock<64, 32, 8, true, true>), grid, block, 0, stream, a);
+        else if (fin) hipLaunchKernelGGL((k_resblock<64, 32, 8, true, false>), grid, block, 0, stream, a);
+        else if (bf) hipLaunchKernelGGL((k_resblock<64, 32, 8, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_resblock<64, 32, 8, false, false>), grid, block, 0, stream, a);
     } else {
-        if constexpr (C == 128) {
-            if (a.w_bf16) {   // persistent as well: 1458 -> 1055 us at batch 64
-                constexpr int PNW = 6;                                  // 96-row tiles: 139 KB of LDS with the 64 KB of weights, one block per CU
-                static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-                const int ptiles = (a.t1 - a.t0 + PNW * 16 - 2 - 1) / (PNW * 16 - 2);
-                if (a.B * ptiles >= cus * 8) {
-                    hipLaunchKernelGGL((k_resblock<C, H, PNW, false, true, true>), dim3((unsigned)cus), dim3(PNW * 64), 0, stream, a);
-                    return;
-                }
-            }
-        }
-        if (a.w_bf16) hipLaunchKernelGGL((k_resblock<C, H, NW, false, true>), grid, dim3(NW * 64), 0, stream, a);
-        else hipLaunchKernelGGL((k_resblock<C, H, NW, false, false>), grid, dim3(NW * 64), 0, stream, a);
+        if (p.pers) hipLaunchKernelGGL((k_resblock<128, 64, 6, false, true, true>), grid, block, 0, stream, a);
+        else if (fin && bf) hipLaunchKernelGGL((k_resblock<128, 64, 4, true, true>), grid, block, 0, stream, a);
+        else if (fin) hipLaunchKernelGGL((k_resblock<128, 64, 4, true, false>), grid, block, 0, stream, a);
+        else if (bf) hipLaunchKernelGGL((k_resblock<128, 64, 4, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_resblock<128, 64, 4, false, false>), grid, block, 0, stream, a);
     }
 }
 
 void launch_resblock(const ResArgs& a, hipStream_t stream) {
-    note_launch(a.final_conv ? "k_resblock+final" : "k_resblock");
-    if (a.C == 64) launch_rb<64, 32, 8>(a, stream);    // 128-row tiles, ~50 KB of LDS: three blocks per CU
-    else launch_rb<128, 64, 4>(a, stream);             // 64-row tiles, same footprint
+    launch_resblock_as(a, resblock_plan(a.C, a.final_conv, a.w_bf16, a.B, a.t1 - a.t0, RES_FORM_AUTO, 0, resblock_cus()), stream);
 }
 
 }  // namespace ptts

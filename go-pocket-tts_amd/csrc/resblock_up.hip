@@ -349,18 +349,30 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
 }
 
 // the fused form takes what k_resblock<64, 32, 8, FINAL, bf16, persistent> takes, plus the transposed convolution in front of it
-bool resblock_up_supported(const ResArgs& a) {
+bool resblock_up_shape_supported(const ResArgs& a) {
     if (!(a.fuse_up && a.xin && a.wup && a.final_conv && a.w_bf16 && a.C == 64 && a.H == 32 && a.CI == 128 && a.up_stride == 4)) return false;
-    if (!resblock_supported(a) || a.x_pad < 1 || a.t0 % 4 != 0 || a.x_L * 4 != a.L || !aligned16(a.xin) || a.x_bs % 4 != 0) return false;
-    static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    const int tiles = (a.t1 - a.t0 + 124 - 1) / 124;
-    return a.B * tiles >= cus * 8;                       // enough tiles per block to amortise its weight copies (156 KB)
+    return resblock_supported(a) && a.x_pad >= 1 && a.t0 % 4 == 0 && a.x_L * 4 == a.L && aligned16(a.xin) && a.x_bs % 4 == 0;
+}
+
+// always persistent, 128 KB of LDS: one block per CU; grid 0 (not taken) unless every block gets >= 8 tiles to amortise its weight copies (156 KB)
+ResPlan resblock_up_plan(int B, int rows, int form, int grid, int cus) {
+    ResPlan p;
+    p.nw = 8; p.pers = 1; p.tout = 124; p.tiles = (rows + 124 - 1) / 124;
+    p.grid = form == RES_FORM_PERS ? grid : (form == RES_FORM_AUTO && B * p.tiles >= cus * 8 ? cus : 0);
+    return p;
+}
+
+bool resblock_up_supported(const ResArgs& a) {
+    return resblock_up_shape_supported(a) && resblock_up_plan(a.B, a.t1 - a.t0, RES_FORM_AUTO, 0, resblock_cus()).grid > 0;
+}
+
+void launch_resblock_up_as(const ResArgs& a, const ResPlan& p, hipStream_t stream) {
+    note_launch("k_resblock_up+final");
+    hipLaunchKernelGGL(k_resblock_up, dim3((unsigned)p.grid), dim3(512), 0, stream, a);
 }
 
 void launch_resblock_up(const ResArgs& a, hipStream_t stream) {
-    note_launch("k_resblock_up+final");
-    static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    hipLaunchKernelGGL(k_resblock_up, dim3((unsigned)cus), dim3(512), 0, stream, a);   // 128 KB of LDS: one block per CU
+    launch_resblock_up_as(a, resblock_up_plan(a.B, a.t1 - a.t0, RES_FORM_AUTO, 0, resblock_cus()), stream);
 }
 
 }  // namespace ptts

@@ -157,7 +157,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
-    "ptts_debug_dsp_opts_error",
+    "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
 ]
 
 
@@ -1261,6 +1261,104 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     H.ptts_debug_step_linear.argtypes = [C.POINTER(_StepLinearArgs)]
     _check(H.ptts_debug_step_linear(C.byref(a)))
     return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
+
+
+class _ResblockArgs(C.Structure):   # ptts_resblock_args
+    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "t0", "t1", "C", "H", "pad", "slack", "w_bf16", "final_conv", "form", "grid", "fuse_up", "x_pad", "x_L", "x_slack")] +
+                [(n, _FP) for n in ("u", "w1", "w2", "wf", "b1", "b2", "bf", "xin", "wup", "bup")] +
+                [("rows", C.POINTER(C.c_int32)), ("uo", _FP), ("pcm", _FP), ("row_out", C.c_void_p), ("row_bytes", C.c_int64), ("launched", C.POINTER(C.c_int32))])
+
+
+RES_FORM_AUTO, RES_FORM_TILE, RES_FORM_PERS = 0, 1, 2
+
+
+def debug_resblock(u, w1, w2, *, L=None, pad=2, slack=0, t0=0, t1=None, w_bf16=True, wf=None, b1=None, b2=None, bf=None, rows=None, row_bytes=None,
+                   form=RES_FORM_AUTO, grid=0, xin=None, wup=None, bup=None, x_pad=1, x_slack=0):
+    """ONE launch of a fused SEANet block (csrc/resblock.hip, csrc/resblock_up.hip) on host operands (ptts_debug_resblock, include/ptts_debug.h).
+    u [B, pad + L, C] (None with xin: the fused form makes it from xin [B, x_pad + L / 4, 128], wup [256, 256], bup [64]); w1 [H, 3 C], w2 [C, H]; wf [3 C]
+    asks for the final convolution; rows: [(lim, s16)] per utterance asks for row destinations of row_bytes bytes each; form 0 automatic / 1 one tile per
+    block / 2 `grid` persistent blocks.  Returns a dict: "uo" [B, pad + L + slack, C] or "pcm" [B, L] and "rows" [B, row_bytes] uint8 (whole buffers, 0xff
+    bytes where nothing was stored), "plan": (waves per block, persistent, grid, tiles per utterance, new rows per tile)."""
+    w1, w2 = _f32(w1), _f32(w2)
+    h, c = w1.shape[0], w2.shape[0]
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return C.cast(None, _FP)
+        a = _f32(a)
+        keep.append(a)
+        return _fp(a)
+
+    a = _ResblockArgs()
+    fused = xin is not None
+    if fused:
+        xin = _f32(xin)
+        b, xl = xin.shape[0], xin.shape[1] - int(x_pad)
+        L = 4 * xl if L is None else int(L)
+    else:
+        u = _f32(u)
+        b = u.shape[0]
+        L = u.shape[1] - int(pad) if L is None else int(L)
+        xl = 0
+    a.B, a.L, a.t0, a.t1, a.C, a.H, a.pad, a.slack = b, L, int(t0), L if t1 is None else int(t1), c, h, int(pad), int(slack)
+    a.w_bf16, a.final_conv, a.form, a.grid, a.fuse_up, a.x_pad, a.x_L, a.x_slack = (1 if w_bf16 else 0), (1 if wf is not None else 0), int(form), int(grid), (1 if fused else 0), int(x_pad), xl, int(x_slack)
+    a.u, a.w1, a.w2, a.wf, a.b1, a.b2, a.bf, a.xin, a.wup, a.bup = ptr(None if fused else u), ptr(w1), ptr(w2), ptr(wf), ptr(b1), ptr(b2), ptr(bf), ptr(xin), ptr(wup), ptr(bup)
+    final = wf is not None
+    uo = None if final else np.empty((b, int(pad) + L + int(slack), c), np.float32)
+    pcm = np.empty((b, L), np.float32) if final else None
+    a.uo, a.pcm = ptr(uo), ptr(pcm)
+    ro = None
+    if rows is not None:
+        rt = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(b, 2))
+        keep.append(rt)
+        a.rows = rt.ctypes.data_as(C.POINTER(C.c_int32))
+        a.row_bytes = ((4 * L + 8 * 4 + 15) // 16) * 16 if row_bytes is None else int(row_bytes)
+        ro = np.empty((b, max(int(a.row_bytes), 0)), np.uint8)
+        a.row_out = ro.ctypes.data_as(C.c_void_p)
+    cnt = (C.c_int32 * 5)()
+    a.launched = C.cast(cnt, C.POINTER(C.c_int32))
+    H = hooks()
+    H.ptts_debug_resblock.argtypes = [C.POINTER(_ResblockArgs)]
+    _check(H.ptts_debug_resblock(C.byref(a)))
+    return {"uo": uo, "pcm": pcm, "rows": ro, "plan": tuple(int(v) for v in cnt)}
+
+
+def debug_resblock_plan(c, final_conv, w_bf16, batch, rows, cus, *, fuse_up=False, form=RES_FORM_AUTO, grid=0):
+    """(waves per block, persistent, grid, tiles per utterance, new rows per tile) as resblock_plan / resblock_up_plan choose for `cus` compute units.  No GPU."""
+    out = (C.c_int32 * 5)()
+    H = hooks()
+    H.ptts_debug_resblock_plan.argtypes = [C.c_int32] * 9 + [C.POINTER(C.c_int32)]
+    _check(H.ptts_debug_resblock_plan(int(c), 1 if final_conv else 0, 1 if w_bf16 else 0, 1 if fuse_up else 0, int(batch), int(rows), int(form), int(grid), int(cus), out))
+    return tuple(int(v) for v in out)
+
+
+def debug_seanet_pack(kind, rm, want_lo=True):
+    """The SEANet blocks' weight packers (csrc/model.h) on a matrix: kind 0 frag16 of rm [out, in], 1 the fused transposed convolution's [256, in], 2 the
+    final convolution rm [in].  Returns (hi, lo) uint16 planes (lo None when not asked for).  No GPU."""
+    rm = _f32(rm)
+    out, inn = (16, rm.shape[0]) if kind == 2 else rm.shape
+    hi = np.empty(out * inn, np.uint16)
+    lo = np.empty(out * inn, np.uint16) if (want_lo or kind == 2) else None
+    H = hooks()
+    H.ptts_debug_seanet_pack.argtypes = [C.c_int32, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    _check(H.ptts_debug_seanet_pack(int(kind), _fp(rm), 1 if kind == 2 else out, inn, hi.ctypes.data_as(C.c_void_p), lo.ctypes.data_as(C.c_void_p) if lo is not None else None))
+    return hi, lo
+
+
+def debug_plan_seanet_frags(plan, item):
+    """What the loader packed for a plan (Model.plan): (hi, lo or None, (out, in)) of item 0-2 conv k3, 3-5 conv k1, 6 last transposed convolution, 7 final
+    convolution; None when the loader made no fragment-ordered copy of it.  No GPU."""
+    H = hooks()
+    H.ptts_debug_plan_seanet_frags.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    n, dims = C.c_int64(0), (C.c_int32 * 3)()
+    _check(H.ptts_debug_plan_seanet_frags(plan, int(item), None, None, 0, C.byref(n), dims))
+    if n.value == 0:
+        return None
+    hi = np.empty(n.value, np.uint16)
+    lo = np.empty(n.value, np.uint16) if dims[2] else None
+    _check(H.ptts_debug_plan_seanet_frags(plan, int(item), hi.ctypes.data_as(C.c_void_p), lo.ctypes.data_as(C.c_void_p) if lo is not None else None, n.value, C.byref(n), dims))
+    return hi, lo, (int(dims[0]), int(dims[1]))
 
 
 def last_attention_kernel() -> str:

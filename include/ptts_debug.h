@@ -78,6 +78,41 @@ typedef struct ptts_step_linear_args {
 } ptts_step_linear_args;
 int ptts_debug_step_linear(const ptts_step_linear_args* a);
 
+/* The fused SEANet blocks (csrc/resblock.hip: k_resblock; csrc/resblock_up.hip: k_resblock_up) stand-alone: ONE launch on host operands.
+ *   u [B][pad + L][C]: `pad` history rows (zeros by the kernels' contract) and L rows per utterance; on the device every utterance gets `slack` more rows
+ *   (u_bs = (pad + L + slack) C), filled with NaN.  Rows [t0, t1) are produced: uo [B][pad + L + slack][C] = elu(u + block(u)) (final_conv 0), or
+ *   pcm [B][L] (final_conv 1), or -- rows [B][2] = {lim, s16} given -- utterance b's samples [0, min(lim, L, t1)) in its own 16-byte-aligned destination of
+ *   row_bytes bytes (f32, or int16 by WritePCM16Samples' rule), returned in row_out [B][row_bytes]; pcm then stays untouched.
+ *   Weights, f32 row-major in the checkpoint's GEMM layouts: w1 [H][3 C] (conv k3: [tap][c]), w2 [C][H] (conv k1), wf [3 C] (final conv), b1 [H], b2 [C],
+ *   bf [1] (each optional); w_bf16: rounded to bf16, else hi + lo planes.  They are packed by the loader's own packers (csrc/model.h).
+ *   fuse_up: u is not read; the block's input is the transposed convolution 128 -> 64, stride 4, of xin [B][x_pad + x_L][128] (x_slack NaN rows behind each
+ *   utterance on the device) with wup [4 * 64][2 * 128] (row (phase r, channel): x[t-1] . W[.., r + 4] | x[t] . W[.., r]) and bup [64] (optional).
+ *   form 0: the production choice (resblock_plan / resblock_up_plan, today's thresholds); 1: one tile per block; 2: `grid` persistent blocks.
+ * uo, pcm and row_out are filled with 0xff bytes before the launch and returned whole.  launched [5] receives waves per block, persistent, grid, tiles
+ * per utterance, new rows per tile.  PTTS_EINVAL with a message, before anything is launched, for: whatever resblock_supported / resblock_up_supported
+ * refuse apart from the size threshold, a form the block does not have, and a persistent grid outside [1, B * tiles]. */
+typedef struct ptts_resblock_args {
+    int32_t B, L, t0, t1, C, H, pad, slack, w_bf16, final_conv, form, grid, fuse_up, x_pad, x_L, x_slack;
+    const float *u, *w1, *w2, *wf, *b1, *b2, *bf, *xin, *wup, *bup;
+    const int32_t* rows;
+    float *uo, *pcm;
+    uint8_t* row_out;
+    int64_t row_bytes;
+    int32_t* launched;
+} ptts_resblock_args;
+int ptts_debug_resblock(const ptts_resblock_args* a);
+/* The launch form alone, for `cus` compute units (no GPU): out [5] as `launched` above; grid 0: the form does not exist / the fused kernel is not taken. */
+int ptts_debug_resblock_plan(int32_t C, int32_t final_conv, int32_t w_bf16, int32_t fuse_up, int32_t B, int32_t rows, int32_t form, int32_t grid, int32_t cus,
+                             int32_t* out);
+/* The blocks' weight packers on a caller's matrix (no GPU).  kind 0: rm [out][in] -> fragment-ordered bf16 hi (and lo when given) planes of
+ * out * in entries; 1: the fused transposed convolution's [256][in] operand (rows regrouped first); 2: the final convolution rm [in] as a one-column
+ * matrix, hi and lo planes of 16 * in entries. */
+int ptts_debug_seanet_pack(int32_t kind, const float* rm, int32_t out, int32_t in, uint16_t* hi, uint16_t* lo);
+/* ... and what the model loader packed for a plan (no GPU): item 0-2 the blocks' conv k3, 3-5 their conv k1, 6 the last transposed convolution, 7 the
+ * final convolution.  count receives the entries per plane (0: the loader made no such copy), dims {out, in, has lo plane}; hi / lo (cap entries each)
+ * may be NULL to ask for the sizes only. */
+int ptts_debug_plan_seanet_frags(ptts_plan* p, int32_t item, uint16_t* hi, uint16_t* lo, int64_t cap, int64_t* count, int32_t* dims);
+
 /* name of the kernel the calling thread's last attention launch used ("k_attn_step", "k_attn_window", "k_attn_window<ragged>",
  * "k_attention"): lets a parity test assert that it exercised the kernel it means to */
 const char* ptts_debug_last_attention_kernel(void);
