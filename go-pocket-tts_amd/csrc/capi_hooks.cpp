@@ -499,6 +499,144 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     });
 }
 
+// The many-row GEMMs on host operands: ONE launch of a named kernel.  These kernels clamp addresses instead of bounding their loads, so every element a row's
+// read or store can touch is checked against the caller's buffer sizes here, before anything is uploaded.
+int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: null argument");
+        const ptts_gemm_rows_args& t = *pa;
+        if (!t.A || !t.W || !t.C || t.M <= 0 || t.N <= 0 || t.K <= 0 || t.ldw < t.K || t.a_elems <= 0 || t.c_elems <= 0 || t.epi < EPI_NONE || t.epi > EPI_RESADD_ELU ||
+            (t.aop != AOP_NONE && t.aop != AOP_ELU) || (t.w_bf16 != 0 && t.w_bf16 != 1) || t.a_ld < 1 || t.c_ld < 1 || t.a_rows_per_batch < 0 || t.c_rows_per_batch < 0 ||
+            t.a_rows_per_batch > INT32_MAX || t.c_rows_per_batch > INT32_MAX || t.a_batch_stride < 0 || t.c_batch_stride < 0 || t.a_off < 0 || t.c_off < 0 || t.kslice < 0 ||
+            t.zstride < 0 || t.win_taps < 0 || t.win_c < 0)
+            throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: bad arguments");
+        if (t.kernel < 0 || t.kernel > 5) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: unknown kernel");
+        if ((t.epi >= EPI_RESADD && !t.R) || (t.epi == EPI_GATE_RESADD && (!t.gate || t.ldg < t.N)))
+            throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: operands do not fit the epilogue asked for");
+        const int M = t.M, N = t.N, K = t.K;
+        const bool rope = t.rope_cos || t.rope_sin;
+        if (rope && (!t.rope_cos || !t.rope_sin || t.n_pos < 1 || t.rope_hd < 4 || t.rope_hd % 4 || t.rope_cols < 0 || t.rope_cols > N || t.rope_pos0 < 0 || t.rope_rows_per_seg < 0))
+            throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: bad RoPE arguments");
+        const int planes = t.kslice ? (K + t.kslice - 1) / t.kslice : 1;
+        // what would be ignored in silence: an rgl on another kernel than k_gemm_wres, a cfg on another than k_gemm3 / k_gemm5, a zstride without slices
+        if (t.cfg && t.kernel != 3 && t.kernel != 5) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: cfg is k_gemm3's and k_gemm5's alone");
+        if (t.rgl && t.kernel != 4) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: rgl is k_gemm_wres' alone");
+        if (t.zstride && !t.kslice) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: zstride without kslice");
+        // C's rows, segments and planes must not overlap: two blocks would store to one element (A's rows may: a convolution's windows)
+        const int64_t c_seg = t.c_rows_per_batch ? (std::min<int64_t>(M, t.c_rows_per_batch) - 1) * t.c_ld + N : 0;   // one segment's extent
+        const int64_t c_plane = t.c_rows_per_batch ? ((M - 1) / t.c_rows_per_batch) * t.c_batch_stride + ((M - 1) % t.c_rows_per_batch) * t.c_ld + N : (int64_t)(M - 1) * t.c_ld + N;
+        if (t.c_ld < N || (t.c_rows_per_batch && M > t.c_rows_per_batch && t.c_batch_stride < c_seg) || (planes > 1 && t.zstride < c_plane))
+            throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: rows, segments or planes of C overlap");
+        // the maps against the buffers: the largest element any row's K-wide read (a clamped row is row M - 1) and N-wide store / residual read can touch
+        auto roff = [](int64_t ld, int64_t rpb, int64_t bs, int64_t r) { return rpb ? (r / rpb) * bs + (r % rpb) * ld : r * ld; };
+        for (int64_t m = 0; m < M; m++) {
+            const int64_t ao = t.a_off + roff(t.a_ld, t.a_rows_per_batch, t.a_batch_stride, m);
+            if (ao + K > t.a_elems) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld of A ends at element %lld of %lld", (long long)m, (long long)(ao + K), (long long)t.a_elems));
+            const int64_t co = t.c_off + roff(t.c_ld, t.c_rows_per_batch, t.c_batch_stride, m) + (int64_t)(planes - 1) * t.zstride;
+            if (co + N > t.c_elems) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld of C ends at element %lld of %lld", (long long)m, (long long)(co + N), (long long)t.c_elems));
+            if (rope) {
+                const int64_t pos = t.rope_row_pos ? t.rope_row_pos[m] : (int64_t)t.rope_pos0 + (t.rope_rows_per_seg ? m % t.rope_rows_per_seg : m);
+                if (pos < 0 || pos >= t.n_pos) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld at position %lld, the tables hold %d", (long long)m, (long long)pos, t.n_pos));
+            }
+        }
+        require_device();
+        int dev = 0, cus = 0;
+        PTTS_HIP(hipGetDevice(&dev));
+        PTTS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        const size_t nw = (size_t)N * t.ldw, half = (size_t)(rope ? t.rope_hd / 2 : 0), ntab = (size_t)std::max(t.n_pos, 1) * std::max<size_t>(half, 1);
+        Tmp dA((size_t)t.a_elems * 4), dW(nw * 4), dC((size_t)t.c_elems * 4), dR((size_t)t.c_elems * 4), dB((size_t)N * 4), dAv((size_t)N * 4), dSc((size_t)N * 4),
+            dG((size_t)M * std::max(t.ldg, 1) * 4), dCos(ntab * 4), dSin(ntab * 4), dPos((size_t)M * 4);
+        up(dA.p, t.A, (size_t)t.a_elems * 4);
+        if (t.w_bf16) {
+            std::vector<uint16_t> w16(nw);
+            for (size_t i = 0; i < nw; i++) w16[i] = f32_to_bf16_rne(t.W[i]);
+            up(dW.p, w16.data(), nw * 2);
+        } else up(dW.p, t.W, nw * 4);
+        PTTS_HIP(hipMemset(dC.p, 0xff, (size_t)t.c_elems * 4));
+        GemmArgs g;
+        g.A = dA.as<float>() + t.a_off; g.amap = RowMap{t.a_ld, t.a_rows_per_batch, t.a_batch_stride};
+        g.W = dW.p; g.w_bf16 = t.w_bf16; g.ldw = t.ldw;
+        g.C = dC.as<float>() + t.c_off; g.cmap = RowMap{t.c_ld, t.c_rows_per_batch, t.c_batch_stride};
+        if (t.bias) { up(dB.p, t.bias, (size_t)N * 4); g.bias = dB.as<float>(); }
+        if (t.addvec) { up(dAv.p, t.addvec, (size_t)N * 4); g.addvec = dAv.as<float>(); }
+        if (t.scale) { up(dSc.p, t.scale, (size_t)N * 4); g.scale = dSc.as<float>(); }
+        if (t.gate) { up(dG.p, t.gate, (size_t)M * t.ldg * 4); g.gate = dG.as<float>(); g.ldg = t.ldg; }
+        if (t.R) {   // r_in_c: the in-place residual (R is C: every element read and written by the same lane)
+            up(t.r_in_c ? dC.p : dR.p, t.R, (size_t)t.c_elems * 4);
+            g.R = (t.r_in_c ? dC.as<float>() : dR.as<float>()) + t.c_off;
+        }
+        if (rope) {
+            up(dCos.p, t.rope_cos, ntab * 4); up(dSin.p, t.rope_sin, ntab * 4);
+            g.rope_cos = dCos.as<float>(); g.rope_sin = dSin.as<float>(); g.rope_cols = t.rope_cols; g.rope_hd = t.rope_hd; g.rope_pos0 = t.rope_pos0;
+            g.rope_rows_per_seg = t.rope_rows_per_seg;
+            if (t.rope_row_pos) { up(dPos.p, t.rope_row_pos, (size_t)M * 4); g.rope_row_pos = dPos.as<int32_t>(); }
+        }
+        g.kslice = t.kslice; g.zstride = t.zstride; g.win_taps = t.win_taps; g.win_c = t.win_c;
+        g.alpha = t.alpha; g.aop = t.aop; g.epi = t.epi; g.M = M; g.N = N; g.K = K;
+        // refused before any launch: what the kernel's own predicate refuses, and a forced form its production guard would not allow
+        const bool extra = rope || t.kslice;   // what only k_gemm3 / k_gemm5 implement: another kernel would ignore it in silence
+        int rgl = 0;
+        switch (t.kernel) {
+            case 0:
+                if (extra && !gemm5_supported(g) && !gemm3_supported(g)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: no kernel with RoPE / split-K takes this shape");
+                if (!extra && gemm_wres_supported(g)) rgl = gemm_wres_rgl(g);
+                break;
+            case 1:
+                if (extra || gemm_wres_supported(g) || gemm5_supported(g) || gemm3_supported(g) || gemm2_supported(g))
+                    throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: launch_gemm does not leave this shape to k_gemm");
+                break;
+            case 2:
+                if (extra || !gemm2_supported(g)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: refused by gemm2_supported");
+                break;
+            case 3:
+                if (!gemm3_supported(g)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: refused by gemm3_supported");
+                if (!(t.cfg >= 0 && t.cfg <= 4) && t.cfg != 6) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: unknown k_gemm3 cfg");
+                if (t.cfg == 4 && N < 256) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: k_gemm3<256,8,64> needs N >= 256");
+                break;
+            case 4: {
+                if (!gemm_wres_supported(g)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: refused by gemm_wres_supported");
+                rgl = t.rgl ? t.rgl : gemm_wres_rgl(g);
+                if (rgl < 1 || rgl > gemm_wres_max_rgl(g)) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: rgl %d outside [1, %d]", rgl, gemm_wres_max_rgl(g)));
+                break;
+            }
+            default:
+                if (!gemm5_supported(g)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: refused by gemm5_supported");
+                if (t.cfg < 0 || t.cfg > 4) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: unknown k_gemm5 cfg");
+                if ((t.cfg == 1 || t.cfg == 2) && N % 256) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: a 256-column k_gemm5 form needs N % 256 == 0 (its weight loads are not bounded)");
+                break;
+        }
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        g_launch_census = &census;
+        try {
+            switch (t.kernel) {
+                case 0:
+                    if (rope) { if (!launch_gemm_rope(g, nullptr)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: no RoPE epilogue for this shape"); }
+                    else launch_gemm(g, nullptr);
+                    break;
+                case 1: launch_gemm(g, nullptr); break;
+                case 2: launch_gemm2(g, nullptr); break;
+                case 3: g_gemm3_cfg = t.cfg; launch_gemm3(g, nullptr); g_gemm3_cfg = 0; break;
+                case 4: launch_gemm_wres_as(g, rgl, nullptr); break;
+                default: g_gemm5_cfg = t.cfg; launch_gemm5(g, nullptr); g_gemm5_cfg = 0; break;
+            }
+        } catch (...) { g_launch_census = census_before; g_gemm3_cfg = 0; g_gemm5_cfg = 0; throw; }
+        g_launch_census = census_before;
+        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        PTTS_HIP(hipGetLastError());
+        PTTS_HIP(hipDeviceSynchronize());
+        if (t.launched && t.launched_cap > 0) {
+            std::string s;
+            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
+            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
+            std::memcpy(t.launched, s.data(), n);
+            t.launched[n] = 0;
+        }
+        if (t.info) { t.info[0] = cus; t.info[1] = rgl; }
+        down(t.C, dC.p, (size_t)t.c_elems * 4);
+    });
+}
+
 // ---- the fused SEANet blocks (csrc/resblock.hip, csrc/resblock_up.hip) stand-alone ----
 // the launch form resblock_plan / resblock_up_plan choose (no GPU: `cus` is an argument)
 int ptts_debug_resblock_plan(int32_t C, int32_t final_conv, int32_t w_bf16, int32_t fuse_up, int32_t B, int32_t rows, int32_t form, int32_t grid, int32_t cus, int32_t* out) {

@@ -181,19 +181,35 @@ static int wres_shape(const GemmArgs& a) {   // 1: 256 x 256 tile, 2: 128 column
 }
 bool gemm_wres_supported(const GemmArgs& a) { return wres_shape(a) != 0; }
 
-void launch_gemm_wres(const GemmArgs& a, hipStream_t stream) {
+static int wres_per_xcd() {
     static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    const int per_xcd = std::max(1, cus / 8);
-    note_launch(wres_shape(a) == 1 ? "k_gemm_wres<256,256>" : "k_gemm_wres<128,512>");
+    return std::max(1, cus / 8);
+}
+
+// row groups per XCD: one block per CU at most, so 1 .. CUs / 8 (/ column tiles of the 128 x 512 form)
+int gemm_wres_max_rgl(const GemmArgs& a) {
+    return wres_shape(a) == 1 ? wres_per_xcd() : std::max(1, wres_per_xcd() / ((a.N + 127) / 128));
+}
+
+// the one place that picks the production launch form
+int gemm_wres_rgl(const GemmArgs& a) {
     if (wres_shape(a) == 1) {
         const int npan = (a.M + 31) / 32;
-        const int rgl = std::max(1, std::min(per_xcd, (npan + 8 * WR_NW - 1) / (8 * WR_NW)));   // one block per CU at most
+        return std::max(1, std::min(wres_per_xcd(), (npan + 8 * WR_NW - 1) / (8 * WR_NW)));   // one block per CU at most
+    }
+    return gemm_wres_max_rgl(a);
+}
+
+void launch_gemm_wres_as(const GemmArgs& a, int rgl, hipStream_t stream) {
+    note_launch(wres_shape(a) == 1 ? "k_gemm_wres<256,256>" : "k_gemm_wres<128,512>");
+    if (wres_shape(a) == 1) {
         hipLaunchKernelGGL((k_gemm_wres<256, 256>), dim3((unsigned)(8 * rgl)), dim3(WR_NW * 64), 0, stream, a, 1, rgl);
     } else {
         const int ntiles = (a.N + 127) / 128;
-        const int rgl = std::max(1, per_xcd / ntiles);                                            // row groups per XCD
         hipLaunchKernelGGL((k_gemm_wres<128, 512>), dim3((unsigned)(8 * rgl * ntiles)), dim3(WR_NW * 64), 0, stream, a, ntiles, rgl);
     }
 }
+
+void launch_gemm_wres(const GemmArgs& a, hipStream_t stream) { launch_gemm_wres_as(a, gemm_wres_rgl(a), stream); }
 
 }  // namespace ptts

@@ -66,7 +66,12 @@ constexpr int kSkinnyChunkRows = 256;   // up to this many rows a GEMM on a step
 void launch_gemm(const GemmArgs& a, hipStream_t stream);
 bool launch_gemm_rope(const GemmArgs& a, hipStream_t stream);   // a product with the RoPE epilogue (GemmArgs::rope_cos) on k_gemm3; false: the shape is not taken (the caller rotates in a second launch)
 bool gemm_wres_supported(const GemmArgs& a);   // gemm_wres.hip: K, N <= 256 with the whole weight matrix resident in LDS
-void launch_gemm_wres(const GemmArgs& a, hipStream_t stream);
+void launch_gemm_wres(const GemmArgs& a, hipStream_t stream);   // = launch_gemm_wres_as(a, gemm_wres_rgl(a))
+// its launch form: 8 * rgl (* column tiles) blocks, rgl row groups per XCD, every wave walking the 32-row panels (group, wave) + j * 64 rgl.  gemm_wres_rgl is
+// the only place that chooses for production; another rgl in [1, gemm_wres_max_rgl] is for the kernel's test hook
+int gemm_wres_max_rgl(const GemmArgs& a);   // CUs / 8 (256 x 256), CUs / 8 / column tiles (128 x 512)
+int gemm_wres_rgl(const GemmArgs& a);
+void launch_gemm_wres_as(const GemmArgs& a, int rgl, hipStream_t stream);
 bool gemm2_supported(const GemmArgs& a);
 void launch_gemm2(const GemmArgs& a, hipStream_t stream);
 bool gemm3_supported(const GemmArgs& a);   // direct-to-register activations, 256-row blocks (gemm3.hip)

@@ -158,6 +158,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
+    "ptts_debug_gemm_rows",
 ]
 
 
@@ -1261,6 +1262,75 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     H.ptts_debug_step_linear.argtypes = [C.POINTER(_StepLinearArgs)]
     _check(H.ptts_debug_step_linear(C.byref(a)))
     return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
+
+
+class _GemmRowsArgs(C.Structure):   # ptts_gemm_rows_args
+    _fields_ = ([(n, C.c_int32) for n in ("M", "N", "K", "ldw", "w_bf16", "aop", "epi", "kernel", "cfg", "rgl", "r_in_c", "ldg", "rope_cols", "rope_hd", "rope_pos0",
+                                          "rope_rows_per_seg", "n_pos", "kslice", "win_taps", "win_c")] +
+                [("alpha", C.c_float), ("reserved", C.c_int32)] +
+                [(n, C.c_int64) for n in ("a_elems", "a_ld", "a_rows_per_batch", "a_batch_stride", "a_off", "c_elems", "c_ld", "c_rows_per_batch", "c_batch_stride",
+                                          "c_off", "zstride", "launched_cap")] +
+                [(n, _FP) for n in ("A", "W", "bias", "addvec", "scale", "gate", "R", "rope_cos", "rope_sin")] +
+                [("rope_row_pos", C.POINTER(C.c_int32)), ("C", _FP), ("launched", C.c_char_p), ("info", C.POINTER(C.c_int32))])
+
+
+GEMM_DISPATCH, GEMM_K_GEMM, GEMM_K_GEMM2, GEMM_K_GEMM3, GEMM_K_WRES, GEMM_K_GEMM5 = 0, 1, 2, 3, 4, 5
+
+
+def debug_gemm_rows(a_buf, w, M, *, amap, cmap, c_elems, kernel=0, cfg=0, rgl=0, w_bf16=True, K=None, aop=0, epi=0, alpha=1.0, bias=None, addvec=None, scale=None,
+                    gate=None, residual=None, inplace=False, rope=None, rope_cols=0, rope_hd=64, rope_pos0=0, rope_rows_per_seg=0, rope_row_pos=None, kslice=0,
+                    zstride=0, win_taps=0, win_c=0):
+    """ONE launch of a many-row GEMM kernel on host operands (ptts_debug_gemm_rows, include/ptts_debug.h).  a_buf: A's raw buffer (flat f32); w [N, ldw] (K columns
+    are multiplied: default ldw); amap / cmap = (ld, rows_per_batch, batch_stride, off) in elements; residual: a flat buffer of c_elems floats addressed like C
+    (inplace: the kernel runs with R == C); gate [M, ldg]; rope = (cos, sin) tables [n_pos, rope_hd / 2]; kernel 0 dispatch / 1 k_gemm / 2 k_gemm2 / 3 k_gemm3 /
+    4 k_gemm_wres / 5 k_gemm5.  Returns a dict: "out" (the whole C buffer, 0xff bytes where nothing was stored), "launched" ({kernel: count}), "cus", "rgl"."""
+    a_buf, w = _f32(a_buf).reshape(-1), _f32(w)
+    n, ldw = w.shape
+    keep = []
+
+    def ptr(x):
+        if x is None:
+            return C.cast(None, _FP)
+        x = _f32(x)
+        keep.append(x)
+        return _fp(x)
+
+    a = _GemmRowsArgs()
+    a.M, a.N, a.K, a.ldw, a.w_bf16, a.aop, a.epi = int(M), n, ldw if K is None else int(K), ldw, 1 if w_bf16 else 0, int(aop), int(epi)
+    a.kernel, a.cfg, a.rgl, a.r_in_c = int(kernel), int(cfg), int(rgl), 1 if inplace else 0
+    a.ldg = 0 if gate is None else int(np.asarray(gate).shape[1])
+    a.alpha = float(alpha)
+    a.a_elems, a.c_elems = a_buf.size, int(c_elems)
+    a.a_ld, a.a_rows_per_batch, a.a_batch_stride, a.a_off = (int(v) for v in amap)
+    a.c_ld, a.c_rows_per_batch, a.c_batch_stride, a.c_off = (int(v) for v in cmap)
+    a.A, a.W, a.bias, a.addvec, a.scale, a.gate = ptr(a_buf), ptr(w), ptr(bias), ptr(addvec), ptr(scale), ptr(gate)
+    if residual is not None:
+        residual = _f32(residual).reshape(-1)
+        if residual.size != int(c_elems):
+            raise ValueError("the residual is addressed like C: c_elems floats")
+    a.R = ptr(residual)
+    if rope is not None:
+        cos, sin = _f32(rope[0]), _f32(rope[1])
+        if cos.shape != sin.shape or cos.ndim != 2 or cos.shape[1] * 2 != int(rope_hd):
+            raise ValueError("rope tables are [n_pos, rope_hd / 2]")
+        a.rope_cos, a.rope_sin, a.n_pos = ptr(cos), ptr(sin), cos.shape[0]
+        a.rope_cols, a.rope_hd, a.rope_pos0, a.rope_rows_per_seg = int(rope_cols), int(rope_hd), int(rope_pos0), int(rope_rows_per_seg)
+        if rope_row_pos is not None:
+            rp = np.ascontiguousarray(np.asarray(rope_row_pos, np.int32).reshape(int(M)))
+            keep.append(rp)
+            a.rope_row_pos = rp.ctypes.data_as(C.POINTER(C.c_int32))
+    a.kslice, a.zstride, a.win_taps, a.win_c = int(kslice), int(zstride), int(win_taps), int(win_c)
+    out = np.empty(int(c_elems), np.float32)
+    a.C = ptr(out)
+    name = C.create_string_buffer(512)
+    a.launched, a.launched_cap = C.cast(name, C.c_char_p), 512
+    info = (C.c_int32 * 2)()
+    a.info = C.cast(info, C.POINTER(C.c_int32))
+    H = hooks()
+    H.ptts_debug_gemm_rows.argtypes = [C.POINTER(_GemmRowsArgs)]
+    _check(H.ptts_debug_gemm_rows(C.byref(a)))
+    launched = {k: int(v) for k, v in (item.split("=") for item in name.value.decode().split(";") if item)}
+    return {"out": out, "launched": launched, "cus": int(info[0]), "rgl": int(info[1])}
 
 
 class _ResblockArgs(C.Structure):   # ptts_resblock_args

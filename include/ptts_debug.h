@@ -78,6 +78,39 @@ typedef struct ptts_step_linear_args {
 } ptts_step_linear_args;
 int ptts_debug_step_linear(const ptts_step_linear_args* a);
 
+/* The many-row GEMMs (csrc/kernels.hip k_gemm, gemm2.hip, gemm3.hip, gemm_wres.hip, gemm5.hip) stand-alone: ONE launch of a named kernel on host operands.
+ * C = epi(rope(aop(A) W^T + bias)) with kernels.h' RowMaps on A and C:
+ *   A: a buffer of a_elems floats; row m starts at a_off + (m / a_rows_per_batch) a_batch_stride + (m % a_rows_per_batch) a_ld (a_rows_per_batch 0: a_off + m a_ld)
+ *   and is K wide -- a_ld < K makes the rows overlap (a convolution's windows), a_off leaves history rows in front.
+ *   W [N][ldw] f32 (ldw >= K); w_bf16: rounded to bf16 (nearest even) by the hook.  aop 0 / 1 (ELU on A), epi 0..8 (kernels.h Epi), alpha.
+ *   C: a buffer of c_elems floats addressed the same way (c_off, c_ld, c_rows_per_batch, c_batch_stride), filled with 0xff bytes before the launch and
+ *   returned whole.  R (c_elems floats, addressed like C) is the residual; r_in_c: R is uploaded INTO C and the kernel runs with R == C.
+ *   bias [N], addvec [N], scale [N], gate [M][ldg]: each optional (a missing scale is 1).
+ *   RoPE (interleaved pairs) on the first rope_cols columns: rope_cos / rope_sin [n_pos][rope_hd / 2]; row m sits at rope_row_pos[m] when given, else at
+ *   rope_pos0 + (rope_rows_per_seg ? m % rope_rows_per_seg : m).
+ *   Split-K: kslice > 0: plane z (k in [z kslice, (z + 1) kslice)) goes, as raw sums, to C + z zstride.  win_taps / win_c: GemmArgs' (k_gemm5's k order).
+ *   kernel 0: what launch_gemm (launch_gemm_rope with tables) dispatches; 1 k_gemm (the shape must be one launch_gemm leaves to it); 2 k_gemm2; 3 k_gemm3 with
+ *   cfg 0 (production) / 1 <.,4,64> / 2 <.,4,128> / 3 <.,8,64> / 6 <.,8,128> / 4 <256,8,64>; 4 k_gemm_wres with rgl row groups per XCD (0: production);
+ *   5 k_gemm5 with cfg 0 (production) / 1 <256,8> / 2 <256,4> / 3 <128,8> / 4 <128,4>.
+ * launched (launched_cap bytes) receives the census of the call ("kernel=count;"), info [2] the device's compute units and the rgl used (0: another kernel).
+ * PTTS_EINVAL with a message, before anything is launched, for: what the chosen kernel's *_supported refuses; an unknown kernel or cfg, a 256-column form
+ * with N not a multiple of 256 (k_gemm5 does not bound its weight loads), rgl outside [1, CUs / 8 (/ column tiles)]; RoPE, split-K on a kernel that has none;
+ * what would be ignored: an rgl on another kernel than k_gemm_wres, a cfg on another than k_gemm3 / k_gemm5, a zstride without kslice;
+ * a map whose rows (the K-wide reads, the N-wide stores and residual reads of every plane) leave a_elems / c_elems; a map of C whose rows, segments or planes
+ * overlap (c_ld < N, c_batch_stride below a segment's extent, zstride below a plane's: two blocks would store to one element); a position outside [0, n_pos). */
+typedef struct ptts_gemm_rows_args {
+    int32_t M, N, K, ldw, w_bf16, aop, epi, kernel, cfg, rgl, r_in_c, ldg, rope_cols, rope_hd, rope_pos0, rope_rows_per_seg, n_pos, kslice, win_taps, win_c;
+    float alpha;
+    int32_t reserved;
+    int64_t a_elems, a_ld, a_rows_per_batch, a_batch_stride, a_off, c_elems, c_ld, c_rows_per_batch, c_batch_stride, c_off, zstride, launched_cap;
+    const float *A, *W, *bias, *addvec, *scale, *gate, *R, *rope_cos, *rope_sin;
+    const int32_t* rope_row_pos;
+    float* C;
+    char* launched;
+    int32_t* info;
+} ptts_gemm_rows_args;
+int ptts_debug_gemm_rows(const ptts_gemm_rows_args* a);
+
 /* The fused SEANet blocks (csrc/resblock.hip: k_resblock; csrc/resblock_up.hip: k_resblock_up) stand-alone: ONE launch on host operands.
  *   u [B][pad + L][C]: `pad` history rows (zeros by the kernels' contract) and L rows per utterance; on the device every utterance gets `slack` more rows
  *   (u_bs = (pad + L + slack) C), filled with NaN.  Rows [t0, t1) are produced: uo [B][pad + L + slack][C] = elu(u + block(u)) (final_conv 0), or
