@@ -1142,6 +1142,25 @@ int ptts_compress_rows(ptts_model* h, const ptts_compressor_opts* const* c, cons
     });
 }
 
+// the device form of ptts_limit_apply on host rows: the launches of a request's limiter; a row without one is copied on the host
+int ptts_limit_rows(ptts_model* h, const ptts_limiter_opts* const* l, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+    return guard([&] {
+        Model& m = model_of(h);
+        const RowsCheck check{"limiter"};
+        check.args(rows, !l || !in || !n || !out);
+        std::vector<DspSpec> specs((size_t)rows);
+        for (int i = 0; i < rows; i++) {
+            check.row(i, n[i], !in[i] || !out[i]);
+            if (!l[i]) continue;
+            const std::string e = lim_opts_error(l[i]);
+            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
+            specs[(size_t)i].limit = true;
+            specs[(size_t)i].lim = lim_design(*l[i]);
+        }
+        dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
+    });
+}
+
 // target NULL: measurement only (lufs is required); otherwise out is, and lufs receives what was measured before
 static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
     Model& m = model_of(h);

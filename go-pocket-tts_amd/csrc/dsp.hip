@@ -481,7 +481,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         note_launch("k_eq_apply");
         hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
     }
-    if (p.any_tp) {   // the last stage (true_peak.hip): on what the chain stored
+    if (p.any_tp && !p.tp_later) {   // the last stage (true_peak.hip): on what the chain stored
         launch_tp_peak(rows_dev, n, max_tiles, *p.taps, stream);
         launch_tp_scale(rows_dev, n, max_tiles, stream);
     }

@@ -10,6 +10,7 @@ namespace ptts {
 
 static_assert(sizeof(EqScan) == kDspEqBytes, "kernels.h sizes the DSP ring's tail by it");
 static_assert(sizeof(CmpScan) == kCmpScanBytes, "kernels.h sizes the compressor ring's tail by it");
+static_assert(sizeof(LimScan) == kLimScanBytes, "kernels.h sizes the limiter ring's tail by it");
 
 namespace {
 int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: min((int64)(ms / 1000 * 24000), n)
@@ -61,13 +62,43 @@ void cmp_launch(Model& m, const std::vector<DspJob>& jobs, double*& tiles, hipSt
         at += (size_t)n;
     }
 }
+
+// The limiter's tables (limiter.hip) for the limiter rows of one DSP table, behind that table's last kernel and in front of its true-peak pair:
+// up to kLimMaxDesigns distinct designs a table, which travel behind the rows in the same turn of the ring
+void lim_launch(Model& m, std::vector<LimRow>& rows, const std::vector<const LimScan*>& row_design, hipStream_t s) {
+    constexpr int kRows = RowRing<LimRow>::kRows;
+    std::vector<LimScan> designs;
+    for (size_t at = 0; at < rows.size();) {
+        int n = 0;
+        int64_t max_tiles = 0;
+        designs.clear();
+        for (; n < kRows && at + (size_t)n < rows.size(); n++) {
+            LimRow& r = rows[at + (size_t)n];
+            const LimScan& d = *row_design[at + (size_t)n];
+            size_t k = 0;
+            while (k < designs.size() && std::memcmp(&designs[k], &d, sizeof d) != 0) k++;
+            if (k == designs.size()) {
+                if (designs.size() == (size_t)kLimMaxDesigns) break;   // the next table's
+                designs.push_back(d);
+            }
+            r.design = (int32_t)k;
+            max_tiles = std::max(max_tiles, scan_tiles(r.n));
+        }
+        if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: limiter: too many samples for one launch");
+        const void* designs_dev = nullptr;
+        const LimRow* rows_dev = m.lim_ring.stage(rows.data() + at, n, s, designs.data(), designs.size() * sizeof(LimScan), &designs_dev);
+        launch_limiter(rows_dev, n, (int)max_tiles, static_cast<const LimScan*>(designs_dev), s);
+        m.lim_ring.done(s);
+        at += (size_t)n;
+    }
+}
 }  // namespace
 
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
     if (jobs.empty()) return;
     constexpr int kRows = RowRing<DspRow>::kRows;
-    // scratch: a peak word and a true-peak word per row, then the per-tile states of each compressor row, each DC row and each equaliser row and the block of each loudness row (scan_block.h)
+    // scratch: a peak word and a true-peak word per row, then the per-tile states of each compressor row, each DC row and each equaliser row, the block of each loudness row (scan_block.h) and each limiter row's states and gains (limiter.h)
     size_t tile_doubles = 0;
     for (size_t k = 0; k < jobs.size(); k++) {
         const DspJob& j = jobs[k];
@@ -76,6 +107,7 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         if (j.spec.loud) tile_doubles += loud_doubles(scan_tiles(j.n));
         if (j.spec.eq) tile_doubles += (size_t)scan_tiles(j.n) * 4 * (size_t)j.spec.eq->S;
         if (j.spec.compress && apply) tile_doubles += cmp_state_doubles(scan_tiles(j.n));
+        if (j.spec.limit && apply) tile_doubles += lim_scratch_doubles(j.n);
     }
     const size_t peak_bytes = (2 * jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;   // [jobs] sample peaks, then [jobs] true peaks
     char* scratch = m.work(WORK_DSP_SCRATCH, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
@@ -85,6 +117,7 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
     if (apply) cmp_launch(m, jobs, tiles, s);   // the first stage: what follows measures and rewrites the compressed samples (a measurement alone has no compressor: nothing may be rewritten)
     std::vector<DspRow> rows;
     std::vector<const EqScan*> row_eq;
+    std::vector<const DspSpec*> row_spec;
     rows.reserve(jobs.size());
     for (size_t k = 0; k < jobs.size(); k++) {
         DspJob& j = jobs[k];
@@ -116,16 +149,21 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         }
         rows.push_back(r);
         row_eq.push_back(sp.eq);
+        row_spec.push_back(&sp);
     }
     // a table: up to kRows rows with up to kDspMaxEq distinct equalisers, which travel behind the rows in the same turn of the ring
     std::vector<EqScan> eqs;
     std::vector<const EqScan*> eq_of;
+    std::vector<LimRow> lim_rows;
+    std::vector<const LimScan*> lim_design_of;
     for (size_t at = 0; at < rows.size();) {
         int n = 0;
         int64_t max_tiles = 0;
         DspLaunch p{false, false, false, apply, &scan, &loud_scan()};
         eqs.clear();
         eq_of.clear();
+        lim_rows.clear();
+        lim_design_of.clear();
         for (; n < kRows && at + (size_t)n < rows.size(); n++) {
             DspRow& r = rows[at + (size_t)n];
             if (r.flags & DSP_EQ) {
@@ -146,12 +184,32 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             p.any_loud = p.any_loud || (r.flags & DSP_LOUD);
             p.any_tp = p.any_tp || (r.flags & DSP_TP);
         }
+        if (apply) for (int k = 0; k < n; k++) {   // (a measurement alone has no limiter: nothing may be rewritten)
+            const DspSpec& sp = *row_spec[at + (size_t)k];
+            if (!sp.limit) continue;
+            const DspRow& r = rows[at + (size_t)k];
+            LimRow q{};
+            q.x = r.x; q.n = r.n;
+            q.p_tiles = tiles;
+            q.r = reinterpret_cast<float*>(tiles + scan_state_doubles<1>(scan_tiles(r.n)));
+            tiles += lim_scratch_doubles(r.n);
+            lim_rows.push_back(q);
+            lim_design_of.push_back(&sp.lim);
+        }
+        p.tp_later = !lim_rows.empty();
         p.taps = &tp_taps();
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: dsp: too many samples for one launch");
         const void* eqs_dev = nullptr;
         const DspRow* rows_dev = m.dsp_ring.stage(rows.data() + at, n, s, eqs.data(), eqs.size() * sizeof(EqScan), &eqs_dev);
         p.eqs = static_cast<const EqScan*>(eqs_dev);
         launch_dsp(rows_dev, n, (int)max_tiles, p, s);
+        if (p.tp_later) {   // behind the fades, in front of the ceiling
+            lim_launch(m, lim_rows, lim_design_of, s);
+            if (p.any_tp) {
+                launch_tp_peak(rows_dev, n, (int)max_tiles, *p.taps, s);
+                launch_tp_scale(rows_dev, n, (int)max_tiles, s);
+            }
+        }
         m.dsp_ring.done(s);
         at += (size_t)n;
     }

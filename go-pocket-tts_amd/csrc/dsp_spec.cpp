@@ -19,12 +19,14 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->ceiling = ext.ceiling;
     out->compress = ext.compress;
     out->cmp = ext.cmp;
+    out->limit = ext.limit;
+    out->lim = ext.lim;
     return std::string();
 }
 
 bool dsp_active(const ptts_dsp_opts* o) {
     DspExt ext;
-    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && (ext.true_peak || ext.compress)));
+    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && (ext.true_peak || ext.compress || ext.limit)));
 }
 
 }  // namespace ptts

@@ -12,7 +12,8 @@ struct DspSpec {
     bool true_peak = false; float ceiling = 1.0f;      // measured and held at or under `ceiling` (linear)
     bool loud = false; double target_power = 0.0;      // measured (BS.1770) on the samples as the compressor leaves them; 10^((target LUFS + 0.691) / 10) is what its gain aims at
     bool compress = false; CmpScan cmp{};              // the first stage (compressor.h): everything above is measured and applied behind it
-    bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud; }   // the chain behind the compressor
+    bool limit = false; LimScan lim{};                 // the limiter (limiter.h): behind the fades, in front of the true-peak ceiling
+    bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };
 

@@ -299,6 +299,8 @@ extern std::atomic<int64_t> g_resample_launches;
 // True-peak rows (DSP_TP; true_peak.hip, true_peak.h): k_tp_peak + k_tp_scale behind the table's last kernel, on what the chain stored: the row's
 // true peak (eight-fold oversampled, atomicMax on its own zeroed word) and, where it exceeds the row's ceiling, one gain over the whole row.  A
 // row with the ceiling as its only switch passes through k_dsp_apply untouched.  Tables without such a row launch what they launched before.
+// Limiter rows have no flag here: their kernels run on a table of their own (LimRow below) between this table's last kernel and k_tp_peak; a
+// row with the limiter as its only switch passes through k_dsp_apply untouched, like one with the ceiling alone.
 enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8, DSP_TP = 16 };
 constexpr int kDspMaxEq = 16;
 constexpr size_t kDspEqBytes = 1192;   // sizeof(EqScan)
@@ -327,6 +329,7 @@ struct TpTaps;
 struct DspLaunch {
     bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr;
     bool any_tp = false; const TpTaps* taps = nullptr;
+    bool tp_later = false;   // a limiter row is in the table: launch_dsp leaves the true-peak pair to its caller, who runs the limiter's table first
 };
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
@@ -352,6 +355,26 @@ static_assert(sizeof(CmpRow) == 40, "a turn of the compressor ring holds 256 of 
 struct CmpScan;
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
 void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream);
+
+// A request's look-ahead peak limiter (limiter.hip, limiter.h): behind the fades and in front of the true-peak
+// ceiling, on a table of its own behind the DSP table's last kernel and in front of k_tp_peak.  k_lim_summary + k_lim_carry (the release's state
+// entering each tile, the compressor's (max, times) scan over the look-ahead hold), k_lim_gain (the state entering every run, then the
+// required gain r of every sample as an f32 into scratch) and k_lim_apply (the box mean of r in its fixed order, one product, one store), in
+// place.  No kernel reads a sample that another workgroup of the same launch writes: the first three read x and write scratch only,
+// k_lim_apply reads x in its own tile only.  A table's distinct designs (at most kLimMaxDesigns) travel behind its rows.
+constexpr int kLimMaxDesigns = 16;
+constexpr size_t kLimScanBytes = 64;   // sizeof(LimScan)
+struct LimRow {
+    float* x;              // the row's samples (device), rewritten in place
+    int64_t n;             // samples; nothing at or beyond n is touched
+    double* p_tiles;       // the release's per-tile states, [ceil(n / kDspTile)][2]: E_f, S_f (scan_block.h scan_E<1> / scan_S<1>)
+    float* r;              // the required gain, [n]
+    int32_t design, pad;   // the index of the row's design among the table's
+};
+static_assert(sizeof(LimRow) == 40, "a turn of the limiter ring holds 256 of them");
+struct LimScan;
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
+void launch_limiter(const LimRow* rows_dev, int n, int max_tiles, const LimScan* designs_dev, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

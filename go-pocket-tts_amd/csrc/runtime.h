@@ -103,6 +103,7 @@ struct Model {
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
+    RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were

@@ -14,6 +14,7 @@
 
 #include "compressor.h"
 #include "eq.h"
+#include "limiter.h"
 
 namespace ptts {
 
@@ -55,11 +56,12 @@ std::string tp_ceiling_error(double ceiling_dbtp);
 // c = (float)pow(10, dBTP / 20)
 inline float tp_ceiling(double ceiling_dbtp) { return (float)std::pow(10.0, ceiling_dbtp / 20.0); }
 
-// what a live ptts_dsp_ext says, by value (false: e is NULL or not live, and e is not read): the ceiling, and the compressor that
-// ptts_dsp_ext_set_compressor attached (compressor.cpp), as designed.  Copied out under the registry's mutex, which the setter takes too
-struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; };
+// what a live ptts_dsp_ext says, by value (false: e is NULL or not live, and e is not read): the ceiling, the compressor that
+// ptts_dsp_ext_set_compressor attached (compressor.cpp) and the limiter that ptts_dsp_ext_set_limiter attached (limiter.cpp), both as designed.
+// Copied out under the registry's mutex, which the setters take too
+struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; bool limit = false; LimScan lim{}; };
 bool ext_lookup(const ptts_dsp_ext* e, DspExt* out);
 
 }  // namespace ptts
 
-struct ptts_dsp_ext { ptts::DspExt v; };   // (true_peak.cpp makes and frees it, compressor.cpp sets its compressor)
+struct ptts_dsp_ext { ptts::DspExt v; };   // (true_peak.cpp makes and frees it, compressor.cpp sets its compressor, limiter.cpp its limiter)

@@ -87,6 +87,18 @@ class CompressorOpts(C.Structure):   # ptts_compressor_opts
                          float(attack_ms), float(release_ms), float(makeup_db))
 
 
+class LimiterOpts(C.Structure):   # ptts_limiter_opts
+    """A look-ahead peak limiter's options (ptts_limiter_opts): ceiling_db -60 .. 0, lookahead_ms 0.25 .. 5, release_ms 5 .. 5000, drive_db 0 .. 24.
+    size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32), ("ceiling_db", C.c_double), ("lookahead_ms", C.c_double),
+                ("release_ms", C.c_double), ("drive_db", C.c_double)]
+
+    def __init__(self, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, release_ms: float = 80.0, drive_db: float = 0.0,
+                 size: Optional[int] = None, reserved: int = 0):
+        super().__init__(C.sizeof(LimiterOpts) if size is None else int(size), int(reserved), float(ceiling_db), float(lookahead_ms),
+                         float(release_ms), float(drive_db))
+
+
 class EqSection(C.Structure):   # ptts_eq_section
     _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("freq_hz", C.c_double), ("gain_db", C.c_double), ("q", C.c_double)]
 
@@ -150,6 +162,7 @@ ABI_SYMBOLS = [
     "ptts_eq_design", "ptts_eq_response", "ptts_eq_create", "ptts_eq_free", "ptts_eq_apply", "ptts_eq_rows",
     "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
     "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
+    "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -257,6 +270,9 @@ def lib():
         L.ptts_compress_gain.argtypes = [C.POINTER(CompressorOpts), C.c_double, _DP]
         L.ptts_compress_apply.argtypes = [C.POINTER(CompressorOpts), _FP, C.c_int64]
         L.ptts_compress_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CompressorOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        L.ptts_dsp_ext_set_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterOpts)]
+        L.ptts_limit_apply.argtypes = [C.POINTER(LimiterOpts), _FP, C.c_int64]
+        L.ptts_limit_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(LimiterOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -386,6 +402,9 @@ class RuntimeGenerateConfig:
     # a dynamic range compressor (ptts_dsp_opts.ext, ptts_dsp_ext_set_compressor; None: off): the FIRST stage of the chain, compress_apply of this
     # request's own raw 24 kHz audio; loudness and normalise are measured behind it
     compressor: Optional[CompressorOpts] = None
+    # a look-ahead peak limiter (ptts_dsp_opts.ext, ptts_dsp_ext_set_limiter; None: off): behind the fades and in front of the true-peak ceiling,
+    # limit_apply of what the stages above made of this request's 24 kHz audio
+    limiter: Optional[LimiterOpts] = None
 
 
 def _free_addr(addr: int):
@@ -690,6 +709,16 @@ class Model:
         outs = [np.empty(r.size, np.float32) for r in rows]
         pc = (C.POINTER(CompressorOpts) * max(n, 1))(*[C.pointer(c) if c is not None else None for c in cs])
         _check(lib().ptts_compress_rows(self.h, pc, pp, _ip(ns), n, _row_ptrs(outs)))
+        return outs[0] if single else outs
+
+    def limit_rows(self, x, limiter):
+        """ptts_limit_rows: limit_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
+        limiter: one LimiterOpts for every row, or one per row (None copies that row)."""
+        single, rows, n, pp, ns = _rows_in(x)
+        ls = list(limiter) if isinstance(limiter, (list, tuple)) else [limiter] * n
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        pl = (C.POINTER(LimiterOpts) * max(n, 1))(*[C.pointer(l) if l is not None else None for l in ls])
+        _check(lib().ptts_limit_rows(self.h, pl, pp, _ip(ns), n, _row_ptrs(outs)))
         return outs[0] if single else outs
 
     def true_peak_rows(self, x):
@@ -1618,23 +1647,25 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
     eq = getattr(cfg, "eq", None)
     tp = getattr(cfg, "true_peak_dbtp", None)
     cmp_ = getattr(cfg, "compressor", None)
-    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None or cmp_ is not None):
+    lim = getattr(cfg, "limiter", None)
+    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None or cmp_ is not None or lim is not None):
         return None
     o = DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
     if eq is not None:
         o.eq = eq.h
-    if tp is not None or cmp_ is not None:
-        o._ext = DspExt(true_peak_dbtp=None if tp is None else float(tp), compressor=cmp_)   # (kept by the struct, which the request keeps: the handle lives as long as the call)
+    if tp is not None or cmp_ is not None or lim is not None:
+        o._ext = DspExt(true_peak_dbtp=None if tp is None else float(tp), compressor=cmp_, limiter=lim)   # (kept by the struct, which the request keeps: the handle lives as long as the call)
         o.ext = o._ext.h
     return o
 
 
 class DspExt:
-    """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off) and a compressor
-    (a CompressorOpts; None: off).  With neither the handle switches nothing on.  It belongs to no model; keep it alive while requests that name it
-    are running, and set its compressor before they start."""
+    """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
+    (a CompressorOpts; None: off) and a limiter (a LimiterOpts; None: off).  With none of them the handle switches nothing on.  It belongs to no
+    model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
 
-    def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None):
+    def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
+                 limiter: Optional[LimiterOpts] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -1647,10 +1678,16 @@ class DspExt:
         self.h = h.value
         if compressor is not None:
             self.set_compressor(compressor)
+        if limiter is not None:
+            self.set_limiter(limiter)
 
     def set_compressor(self, compressor: Optional[CompressorOpts]):
         """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
         _check(lib().ptts_dsp_ext_set_compressor(self.h, None if compressor is None else C.byref(compressor)))
+
+    def set_limiter(self, limiter: Optional[LimiterOpts]):
+        """ptts_dsp_ext_set_limiter: attaches the limiter (None: off again).  Not while requests that name the handle are running."""
+        _check(lib().ptts_dsp_ext_set_limiter(self.h, None if limiter is None else C.byref(limiter)))
 
     def free(self):
         if self.h:
@@ -1674,6 +1711,13 @@ def compress_apply(compressor: CompressorOpts, samples) -> np.ndarray:
     """ptts_compress_apply: the compressor over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
     out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
     _check(lib().ptts_compress_apply(C.byref(compressor), _fp(out), out.size))
+    return out
+
+
+def limit_apply(limiter: LimiterOpts, samples) -> np.ndarray:
+    """ptts_limit_apply: the limiter over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
+    out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    _check(lib().ptts_limit_apply(C.byref(limiter), _fp(out), out.size))
     return out
 
 

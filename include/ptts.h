@@ -131,7 +131,7 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * -> fade out -> egress.  The host statement of the result: ptts_loudness_normalize, or ptts_dsp_apply(normalize, dc_block, 0, 0); then
  * ptts_eq_apply; then ptts_dsp_apply(0, 0, fade_in_ms, fade_out_ms); then the egress.  The equaliser gives ptts_eq_apply's bits.  Peak and
  * loudness are measured on the raw decoded audio, in front of the equaliser: a boosting equaliser can push samples past +-1, and the PCM16
- * and G.711 egress clamps them as it always does (f32 leaves as it is) -- unless the request sets a true-peak ceiling.
+ * and G.711 egress clamps them as it always does (f32 leaves as it is) -- unless the request sets a true-peak ceiling or a limiter.
  *
  * The true-peak ceiling (`ext`, a handle of ptts_dsp_ext_create below with true_peak = 1) is the last stage.  The whole order of a request's
  * chain: the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out -> true-peak ceiling -> egress.  The host statement of
@@ -143,7 +143,14 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * The compressor (attached to the `ext` handle by ptts_dsp_ext_set_compressor below) is the FIRST stage, on the request's own raw 24 kHz
  * audio.  The whole order of a request's chain: compressor -> the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out
  * -> true-peak ceiling -> egress.  The host statement of the result: ptts_compress_apply, then everything as above; the device gives
- * ptts_compress_apply's bits.  Peak and loudness are measured on the COMPRESSED audio, so a request still lands on its LUFS target. */
+ * ptts_compress_apply's bits.  Peak and loudness are measured on the COMPRESSED audio, so a request still lands on its LUFS target.
+ *
+ * The limiter (attached to the `ext` handle by ptts_dsp_ext_set_limiter below) sits behind the fades and in front of the true-peak ceiling.  The
+ * whole order of a request's chain: compressor -> the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out -> limiter
+ * -> true-peak ceiling -> egress.  The host statement of the result: everything in front of the limiter as above, then ptts_limit_apply, then
+ * ptts_true_peak_limit if the ceiling is set, then the egress; the device gives ptts_limit_apply's bits.  With a limiter a boosting equaliser
+ * or a makeup gain no longer ends in the egress's hard clip: sample peaks stay at or under its ceiling, and the static ceiling behind it has
+ * only the inter-sample remainder to take off. */
 #if defined(__GNUC__)
 #define PTTS_ANON __extension__
 #else
@@ -392,6 +399,46 @@ int  ptts_dsp_ext_set_compressor(ptts_dsp_ext* e, const ptts_compressor_opts* c)
 int  ptts_compress_gain(const ptts_compressor_opts* c, double level_db, double* gain_db);
 int  ptts_compress_apply(const ptts_compressor_opts* c, float* samples, int64_t n);
 int  ptts_compress_rows(ptts_model* m, const ptts_compressor_opts* const* c, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
+
+/* Look-ahead peak limiter at 24 kHz: float64, no recurrence that is not a scan.  With c = 10^(ceiling_db / 20),
+ * d = 10^(drive_db / 20), L = lrint(lookahead_ms * 24) samples (6 .. 120) and rho = exp(-1 / (release_ms * 24)), per row x[0, n):
+ *     a[i] = |x[i]| d                                  the level (a NaN never wins and reads as 0)
+ *     m[i] = max a[j], j in [i, i + L]                  the look-ahead peak hold (samples at or beyond n read as 0)
+ *     p[i] = max(m[i], rho p[i-1]),  p[-1] = 0          the release
+ *     r[i] = p[i] > c ? (float)(c / p[i]) : 1.0f        the required gain, one IEEE division rounded once to f32;  r[i] = r[0] for i < 0
+ *     g[i] = (r[i] + r[i-1] + ... + r[i-L]) / (L + 1)   the smoothed gain: a float64 sum in exactly that order, times the double 1.0 / (L + 1)
+ *     y[i] = (float)((x[i] d) g[i])
+ * The release is evaluated as a blocked scan on the compressor's grid (runs of 30 samples, tiles of 1920; csrc/limiter.h), and that form is
+ * the definition: host and device run the same functions and give the same bits.  It agrees with the sample-by-sample statement to one f32
+ * step at the row's peak.
+ *   - Every term of g[i] comes from a hold window that contains sample i, so |y[i]| <= c (1 + 2^-22): the ceiling holds for every sample.
+ *   - Where the driven signal has been under the ceiling for long enough (every p in [i - L, i] at or under c), g[i] is 1 (or the double
+ *     just below it), and with drive_db = 0 the sample comes back bit for bit: the limiter engages only where it must.
+ *   - y[i] depends on x[0, i + L] only.
+ *   - It limits SAMPLE peaks at 24 kHz; inter-sample peaks, rate conversion and quantisation come behind it.  The static true-peak ceiling
+ *     may follow it and then has only the inter-sample remainder to take off.
+ * Non-finite samples are not treated specially: a NaN sample comes out as NaN and touches nothing else; an infinite sample holds p at +inf
+ * from L samples in front of it to the end of the row, so the gain falls to 0 in front of it, the sample itself comes out as NaN (inf * 0)
+ * and every later finite sample as a zero (csrc/limiter.h).
+ * ptts_limiter_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_dsp_ext_set_limiter attaches the limiter to a live handle of ptts_dsp_ext_create (l NULL: off again); a handle that is not live is
+ * PTTS_EINVAL and is not read.  Set it before requests name the handle, not while they run.  Refused together with pcm_callback like every
+ * other switch of `ext`.
+ * ptts_limit_apply: the limiter over samples[0, n) in place.  Host.
+ * ptts_limit_rows: the same on rows of host samples on the device, by the kernels a request's limiter runs; shaped like ptts_compress_rows.
+ * l[i] NULL copies row i; in[i] == out[i] is allowed; a bad row is named. */
+typedef struct ptts_limiter_opts {
+    uint32_t size;          /* sizeof(ptts_limiter_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  reserved;      /* 0 */
+    double   ceiling_db;    /* -60 .. 0 (dBFS, sample peak) */
+    double   lookahead_ms;  /* 0.25 .. 5: the delay-free look-ahead and the length of the gain's attack ramp */
+    double   release_ms;    /* 5 .. 5000 */
+    double   drive_db;      /* 0 .. 24: gain in front of the limiter (0: none) */
+} ptts_limiter_opts;
+int  ptts_dsp_ext_set_limiter(ptts_dsp_ext* e, const ptts_limiter_opts* l);
+int  ptts_limit_apply(const ptts_limiter_opts* l, float* samples, int64_t n);
+int  ptts_limit_rows(ptts_model* m, const ptts_limiter_opts* const* l, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
