@@ -1108,56 +1108,54 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
     });
 }
 
-// the device form of ptts_eq_apply on host rows: the launches of a request's `eq`; a row without an equaliser is copied on the host
-int ptts_eq_rows(ptts_model* h, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+// The host-rows entry points with one stage and one option per row (ptts_eq_rows, ptts_compress_rows, ptts_limit_rows): the argument checks
+// under the stage's name, each row's spec from per_row(i, spec) -- which returns the row's refusal, or nothing -- and the round trip.  A row
+// whose spec stays empty is copied on the host
+static int stage_rows(ptts_model* h, const char* what, bool opts_null, const float* const* in, const int64_t* n, int32_t rows, float* const* out,
+                      const std::function<std::string(int, DspSpec&)>& per_row) {
     return guard([&] {
         Model& m = model_of(h);
-        const RowsCheck check{"eq"};
-        check.args(rows, !eq || !in || !n || !out);
+        const RowsCheck check{what};
+        check.args(rows, opts_null || !in || !n || !out);
         std::vector<DspSpec> specs((size_t)rows);
         for (int i = 0; i < rows; i++) {
             check.row(i, n[i], !in[i] || !out[i]);
-            if (eq[i] && !(specs[(size_t)i].eq = eq_lookup(eq[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: eq: row %d: the handle is not a live equaliser of ptts_eq_create", i));
+            const std::string e = per_row(i, specs[(size_t)i]);
+            if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
         }
         dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
+    });
+}
+
+// the device form of ptts_eq_apply on host rows: the launches of a request's `eq`; a row without an equaliser is copied on the host
+int ptts_eq_rows(ptts_model* h, const ptts_eq* const* eq, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+    return stage_rows(h, "eq", !eq, in, n, rows, out, [&](int i, DspSpec& spec) {
+        if (eq[i] && !(spec.eq = eq_lookup(eq[i]))) return strfmt("eq: row %d: the handle is not a live equaliser of ptts_eq_create", i);
+        return std::string();
     });
 }
 
 // the device form of ptts_compress_apply on host rows: the launches of a request's compressor; a row without one is copied on the host
 int ptts_compress_rows(ptts_model* h, const ptts_compressor_opts* const* c, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
-    return guard([&] {
-        Model& m = model_of(h);
-        const RowsCheck check{"compressor"};
-        check.args(rows, !c || !in || !n || !out);
-        std::vector<DspSpec> specs((size_t)rows);
-        for (int i = 0; i < rows; i++) {
-            check.row(i, n[i], !in[i] || !out[i]);
-            if (!c[i]) continue;
-            const std::string e = cmp_opts_error(c[i]);
-            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
-            specs[(size_t)i].compress = true;
-            specs[(size_t)i].cmp = cmp_design(*c[i]);
-        }
-        dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
+    return stage_rows(h, "compressor", !c, in, n, rows, out, [&](int i, DspSpec& spec) {
+        if (!c[i]) return std::string();
+        const std::string e = cmp_opts_error(c[i]);
+        if (!e.empty()) return strfmt("row %d: ", i) + e;
+        spec.compress = true;
+        spec.cmp = cmp_design(*c[i]);
+        return std::string();
     });
 }
 
 // the device form of ptts_limit_apply on host rows: the launches of a request's limiter; a row without one is copied on the host
 int ptts_limit_rows(ptts_model* h, const ptts_limiter_opts* const* l, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
-    return guard([&] {
-        Model& m = model_of(h);
-        const RowsCheck check{"limiter"};
-        check.args(rows, !l || !in || !n || !out);
-        std::vector<DspSpec> specs((size_t)rows);
-        for (int i = 0; i < rows; i++) {
-            check.row(i, n[i], !in[i] || !out[i]);
-            if (!l[i]) continue;
-            const std::string e = lim_opts_error(l[i]);
-            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
-            specs[(size_t)i].limit = true;
-            specs[(size_t)i].lim = lim_design(*l[i]);
-        }
-        dsp_rows_device(m, in, n, rows, specs.data(), true, {out});
+    return stage_rows(h, "limiter", !l, in, n, rows, out, [&](int i, DspSpec& spec) {
+        if (!l[i]) return std::string();
+        const std::string e = lim_opts_error(l[i]);
+        if (!e.empty()) return strfmt("row %d: ", i) + e;
+        spec.limit = true;
+        spec.lim = lim_design(*l[i]);
+        return std::string();
     });
 }
 

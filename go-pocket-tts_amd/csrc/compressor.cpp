@@ -6,40 +6,21 @@
 #include <cmath>
 #include <cstddef>
 
-#include "true_peak.h"
+#include "dsp_ext.h"
+#include "opts_check.h"
 
 namespace ptts {
-
-namespace {
-int fail(const std::string& e) {
-    set_last_error("ptts-hip: " + e);
-    return PTTS_EINVAL;
-}
-
-bool range_error(const char* field, double v, double lo, double hi, std::string& out) {
-    if (std::isfinite(v) && v >= lo && v <= hi) return false;
-    out = strfmt("compressor: %s %g is not a finite value from %g to %g", field, v, lo, hi);
-    return true;
-}
-}  // namespace
 
 std::string cmp_opts_error(const ptts_compressor_opts* c) {
     if (!c) return "compressor: null options";
     constexpr size_t kKnown = sizeof(ptts_compressor_opts);
-    if (c->size < kKnown) return strfmt("compressor: size %u is smaller than the fields up to makeup_db (%zu bytes)", c->size, kKnown);
-    if (c->size > kKnown) {   // a caller newer than this library: whatever it says beyond what is known here must be "off"
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(c);
-        for (size_t i = kKnown; i < c->size; i++)
-            if (b[i]) return strfmt("compressor: size %u: byte %zu is not 0, and this library knows %zu bytes", c->size, i, kKnown);
-    }
+    std::string e = opts_size_error("compressor", c, c->size, kKnown, kKnown, "the fields up to makeup_db");
+    if (!e.empty()) return e;
     if (c->reserved) return strfmt("compressor: reserved is %d, must be 0", c->reserved);
-    std::string e;
-    if (range_error("threshold_db", c->threshold_db, -60.0, 0.0, e)) return e;
-    if (range_error("ratio", c->ratio, 1.0, 100.0, e)) return e;
-    if (range_error("knee_db", c->knee_db, 0.0, 24.0, e)) return e;
-    if (range_error("attack_ms", c->attack_ms, 0.05, 200.0, e)) return e;
-    if (range_error("release_ms", c->release_ms, 5.0, 5000.0, e)) return e;
-    if (range_error("makeup_db", c->makeup_db, -24.0, 24.0, e)) return e;
+    const auto bad = [&e](const char* field, double v, double lo, double hi) { return range_error("compressor", field, v, lo, hi, e); };
+    if (bad("threshold_db", c->threshold_db, -60.0, 0.0) || bad("ratio", c->ratio, 1.0, 100.0) || bad("knee_db", c->knee_db, 0.0, 24.0) ||
+        bad("attack_ms", c->attack_ms, 0.05, 200.0) || bad("release_ms", c->release_ms, 5.0, 5000.0) || bad("makeup_db", c->makeup_db, -24.0, 24.0))
+        return e;
     return std::string();
 }
 

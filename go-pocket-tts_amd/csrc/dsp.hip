@@ -19,7 +19,7 @@
 //                   gains, which k_dsp_apply leaves to k_eq_apply for such a row.  The fold s <- A^30 s + e_l is N independent sums, each in its
 //                   fixed order: lane i < N computes component i (lanes_advance), the other components reach it by v_readlane.  The bits are
 //                   scan_advance's; the serial chain is one sum long, not N.
-//   k_tp_peak, k_tp_scale   true-peak rows (DSP_TP), behind everything above: true_peak.hip.
+// The limiter's kernels (limiter.hip) and the true-peak pair (true_peak.hip) follow these on the same rows; dsp_launch (dsp_device.cpp) has the order.
 // k_dsp_* are the DC block's (DspScan, DSP_DC rows, on the f32 product x * gain wherever it is read), k_loud_* the K-weighting's (LoudScan,
 // DSP_LOUD rows, on the RAW samples: nothing is written to them, k_dsp_apply applies the gain).  Stream order has the peak complete before
 // k_loud_gate and k_dsp_summary start, and the loudness gain before k_dsp_summary.  One wave per workgroup and at most 12.5 KB of LDS: a CU
@@ -29,7 +29,7 @@
 // k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row (k_dsp_apply: and an equaliser row), so a table without
 // one launches the instantiation that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
-#include "scan_block.h"
+#include "dsp_tile.h"
 
 namespace ptts {
 
@@ -93,11 +93,6 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
         if (pk > 0.0f) atomicMax(r.peak, __float_as_uint(pk));
     }
 }
-
-// only a full tile that another one follows hands a state on
-__device__ __forceinline__ bool tile_hands_on(const DspRow& r) { return (int64_t)(blockIdx.x + 1) * kDspTile < r.n; }
-// samples of the lane's run in a tile of cnt
-__device__ __forceinline__ int run_count(int cnt) { return max(0, min(kDspRun, cnt - (int)threadIdx.x * kDspRun)); }
 
 // tile blockIdx.x of the row, which hands a state on: E_f into the row's per-tile states
 template <class Sys>
@@ -172,12 +167,12 @@ __device__ __forceinline__ void scan_enter(const Sys& sc, const float* run, int 
 template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_DC) && tile_hands_on(r)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
+    if ((r.flags & DSP_DC) && tile_hands_on(r.n)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_summary(const DspRow* __restrict__ rows, const LoudScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_LOUD) && tile_hands_on(r)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
+    if ((r.flags & DSP_LOUD) && tile_hands_on(r.n)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restrict__ rows, const DspScan sc) {
@@ -331,7 +326,7 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restri
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes * kEqStates];
     const DspRow& r = rows[blockIdx.y];
-    if (!(r.flags & DSP_EQ) || !tile_hands_on(r)) return;
+    if (!(r.flags & DSP_EQ) || !tile_hands_on(r.n)) return;
     float* tile = reinterpret_cast<float*>(tile4);
     load_tile(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile, kNoGain);
     __syncthreads();
@@ -455,10 +450,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         note_launch("k_loud_gate");
         hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
     }
-    if (!p.apply) {
-        if (p.any_tp) launch_tp_peak(rows_dev, n, max_tiles, *p.taps, stream);   // a measurement alone
-        return;
-    }
+    if (!p.apply) return;   // a measurement alone
     if (p.any_dc) {
         if (max_tiles > 1) {
             note_launch("k_dsp_summary");
@@ -480,10 +472,6 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         hipLaunchKernelGGL(k_eq_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, p.eqs);
         note_launch("k_eq_apply");
         hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
-    }
-    if (p.any_tp && !p.tp_later) {   // the last stage (true_peak.hip): on what the chain stored
-        launch_tp_peak(rows_dev, n, max_tiles, *p.taps, stream);
-        launch_tp_scale(rows_dev, n, max_tiles, stream);
     }
 }
 

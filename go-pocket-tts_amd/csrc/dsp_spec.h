@@ -1,6 +1,7 @@
 // dsp_spec.h -- what one row of the post-processing chain gets, as a plain value: a ptts_dsp_opts with its handles looked
-// up, plus the row's loudness.  dsp_spec.cpp is the only code that reads a ptts_dsp_opts; like eq.cpp it builds with a plain C++ compiler (no HIP header).
+// up, plus the row's loudness; and the scratch such a row's stages need on the device (dsp_scratch).  dsp_spec.cpp is the only code that reads a ptts_dsp_opts; like eq.cpp it builds with a plain C++ compiler (no HIP header).
 #pragma once
+#include "dsp_ext.h"
 #include "true_peak.h"
 
 namespace ptts {
@@ -16,6 +17,34 @@ struct DspSpec {
     bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };
+
+// The scratch plan: the doubles of WORK_DSP_SCRATCH each stage of a row of n samples needs (dsp_device.cpp sizes the buffer by total() and carves
+// it by the fields, and nothing else decides either).  apply false: a measurement alone, which rewrites nothing -- no compressor, equaliser or limiter
+struct DspScratch {
+    size_t cmp = 0;    // the compressor's per-tile states of both recurrences (compressor.h cmp_state_doubles)
+    size_t dc = 0;     // the DC block's per-tile states (scan_block.h scan_state_doubles)
+    size_t loud = 0;   // the loudness block: M, the gain, the K-weighting's per-tile states, the sub-block energies (scan_block.h loud_doubles)
+    size_t eq = 0;     // the equaliser's per-tile states, 2 S doubles each for E_f and S_f
+    size_t lim = 0;    // the limiter's per-tile states, then its gains, one f32 a sample (limiter.h lim_scratch_doubles)
+    size_t total() const { return cmp + dc + loud + eq + lim; }
+    // where each region starts within the row's total(): one behind the other, in the order above
+    size_t cmp_at() const { return 0; }
+    size_t dc_at() const { return cmp; }
+    size_t loud_at() const { return dc_at() + dc; }
+    size_t eq_at() const { return loud_at() + loud; }
+    size_t lim_at() const { return eq_at() + eq; }
+};
+inline DspScratch dsp_scratch(const DspSpec& sp, int64_t n, bool apply) {
+    DspScratch q;
+    if (n <= 0) return q;
+    const int64_t F = scan_tiles(n);
+    if (sp.compress && apply) q.cmp = cmp_state_doubles(F);
+    if (sp.dc_block) q.dc = scan_state_doubles<DspScan::N>(F);
+    if (sp.loud) q.loud = loud_doubles(F);
+    if (sp.eq && apply) q.eq = (size_t)F * 4 * (size_t)sp.eq->S;
+    if (sp.limit && apply) q.lim = lim_scratch_doubles(n);
+    return q;
+}
 
 // o (NULL: nothing) with its handles looked up, into *out.  Empty: fine.  Otherwise the message of the first bad field -- a fade that is negative
 // or not a number, an eq or ext that is not a live handle (looked up by address, never read) -- and *out is not to be used.

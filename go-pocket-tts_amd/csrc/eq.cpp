@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "eq.h"
+#include "opts_check.h"
 
 namespace ptts {
 
@@ -20,17 +21,6 @@ std::mutex g_live_mu;
 std::set<std::pair<const void*, int>>& live() {
     static std::set<std::pair<const void*, int>>* s = new std::set<std::pair<const void*, int>>();   // (never destroyed: handles may be freed while the process exits)
     return *s;
-}
-
-const char* range_error(const char* field, double v, double lo, double hi, int index, std::string& out) {
-    if (std::isfinite(v) && v >= lo && v <= hi) return nullptr;
-    out = strfmt("eq: section %d: %s %g is not a finite value from %g to %g", index, field, v, lo, hi);
-    return field;
-}
-
-int fail(const std::string& e) {
-    set_last_error("ptts-hip: " + e);
-    return PTTS_EINVAL;
 }
 
 std::string sections_error(const ptts_eq_section* s, int32_t n) {
@@ -48,11 +38,12 @@ std::string eq_section_error(const ptts_eq_section& s, int index) {
     if (s.type < PTTS_EQ_LOWPASS || s.type > PTTS_EQ_PEAKING) return strfmt("eq: section %d: type %d is not a PTTS_EQ_* type", index, s.type);
     if (s.reserved) return strfmt("eq: section %d: reserved is %d, must be 0", index, s.reserved);
     std::string e;
-    if (range_error("freq_hz", s.freq_hz, 10.0, 11000.0, index, e)) return e;
-    if (range_error("q", s.q, 0.1, 10.0, index, e)) return e;
+    const std::string stage = strfmt("eq: section %d", index);
+    if (range_error(stage.c_str(), "freq_hz", s.freq_hz, 10.0, 11000.0, e)) return e;
+    if (range_error(stage.c_str(), "q", s.q, 0.1, 10.0, e)) return e;
     const bool pass = s.type == PTTS_EQ_LOWPASS || s.type == PTTS_EQ_HIGHPASS;
     if (pass && !(s.gain_db == 0.0)) return strfmt("eq: section %d: gain_db %g must be 0 for a low-pass or a high-pass", index, s.gain_db);
-    if (range_error("gain_db", s.gain_db, -24.0, 24.0, index, e)) return e;
+    if (range_error(stage.c_str(), "gain_db", s.gain_db, -24.0, 24.0, e)) return e;
     return std::string();
 }
 

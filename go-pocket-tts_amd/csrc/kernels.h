@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "limiter.h"
+
 namespace ptts {
 
 // Rows of a 2-D operand may live in per-utterance segments (channels-last sequences with
@@ -295,7 +297,8 @@ extern std::atomic<int64_t> g_resample_launches;
 // where normalise's gain sits.  Tables without such a row launch the kernels they launched before it existed.
 // Equaliser rows (DSP_EQ): k_eq_summary + k_eq_carry + k_eq_apply behind k_dsp_apply, on what it stored (gain and DC block applied, rounded
 // to f32): the row's own cascade of 1 .. 4 sections (scan_block.h EqScan, 2 .. 8 states per tile), then the fades, which k_dsp_apply leaves to
-// k_eq_apply for such a row.  A table's distinct equalisers (at most kDspMaxEq) travel behind its rows; a row names its own by index.
+// k_eq_apply for such a row.  A table's distinct equalisers (at most kDspMaxEq) travel behind its rows; a row names its own by index (how rows
+// are cut into tables, here and for the compressor and the limiter below: row_tables.h).
 // True-peak rows (DSP_TP; true_peak.hip, true_peak.h): k_tp_peak + k_tp_scale behind the table's last kernel, on what the chain stored: the row's
 // true peak (eight-fold oversampled, atomicMax on its own zeroed word) and, where it exceeds the row's ceiling, one gain over the whole row.  A
 // row with the ceiling as its only switch passes through k_dsp_apply untouched.  Tables without such a row launch what they launched before.
@@ -303,7 +306,8 @@ extern std::atomic<int64_t> g_resample_launches;
 // row with the limiter as its only switch passes through k_dsp_apply untouched, like one with the ceiling alone.
 enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8, DSP_TP = 16 };
 constexpr int kDspMaxEq = 16;
-constexpr size_t kDspEqBytes = 1192;   // sizeof(EqScan)
+constexpr size_t kDspEqBytes = 1192;
+static_assert(sizeof(EqScan) == kDspEqBytes, "the DSP ring's tail (runtime.h) is sized by it");
 struct DspRow {
     float* x;              // the row's samples (device), rewritten in place
     int64_t n;             // samples; nothing at or beyond n is touched
@@ -318,22 +322,17 @@ struct DspRow {
     float ceiling;         // true-peak rows: the linear ceiling c = (float)pow(10, dBTP / 20)
 };
 static_assert(sizeof(DspRow) == 96, "a turn of the DSP ring holds 256 of them");
-struct DspScan;
-struct LoudScan;
-struct EqScan;
 // which flags occur in a table's rows, and the systems' coefficients (loud: needed with any_loud); apply false: the measuring launches only,
 // the samples stay as they are
 // any_eq: eqs is the device copy of the table's equalisers
-// any_tp: the table has a true-peak row (taps: the meter's, true_peak.h); with apply false such a row is measured only
-struct TpTaps;
 struct DspLaunch {
     bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr;
-    bool any_tp = false; const TpTaps* taps = nullptr;
-    bool tp_later = false;   // a limiter row is in the table: launch_dsp leaves the true-peak pair to its caller, who runs the limiter's table first
 };
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
-// launch_dsp's last two (true_peak.hip): the true peak of every DSP_TP row into its word; the gain c / TP over the rows whose word exceeds c
+// the last two of a table with a true-peak row (true_peak.hip; dsp_launch calls them behind launch_dsp's kernels and the limiter's tables, the
+// first alone for a measurement): the true peak of every DSP_TP row into its word; the gain c / TP over the rows whose word exceeds c
+struct TpTaps;
 void launch_tp_peak(const DspRow* rows_dev, int n, int max_tiles, const TpTaps& taps, hipStream_t stream);
 void launch_tp_scale(const DspRow* rows_dev, int n, int max_tiles, hipStream_t stream);
 
@@ -343,7 +342,8 @@ void launch_tp_scale(const DspRow* rows_dev, int n, int max_tiles, hipStream_t s
 // from its entering state) and k_cmp_apply (both states entering every run, the gain curve, one store), in place.  A table's distinct designs
 // (at most kCmpMaxDesigns) travel behind its rows; a row names its own by index.
 constexpr int kCmpMaxDesigns = 16;
-constexpr size_t kCmpScanBytes = 128;   // sizeof(CmpScan)
+constexpr size_t kCmpScanBytes = 128;
+static_assert(sizeof(CmpScan) == kCmpScanBytes, "the compressor ring's tail (runtime.h) is sized by it");
 struct CmpRow {
     float* x;              // the row's samples (device), rewritten in place
     int64_t n;             // samples; nothing at or beyond n is touched
@@ -352,7 +352,6 @@ struct CmpRow {
     int32_t design, pad;   // the index of the row's design among the table's
 };
 static_assert(sizeof(CmpRow) == 40, "a turn of the compressor ring holds 256 of them");
-struct CmpScan;
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
 void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream);
 
@@ -363,7 +362,8 @@ void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpSc
 // place.  No kernel reads a sample that another workgroup of the same launch writes: the first three read x and write scratch only,
 // k_lim_apply reads x in its own tile only.  A table's distinct designs (at most kLimMaxDesigns) travel behind its rows.
 constexpr int kLimMaxDesigns = 16;
-constexpr size_t kLimScanBytes = 64;   // sizeof(LimScan)
+constexpr size_t kLimScanBytes = 64;
+static_assert(sizeof(LimScan) == kLimScanBytes, "the limiter ring's tail (runtime.h) is sized by it");
 struct LimRow {
     float* x;              // the row's samples (device), rewritten in place
     int64_t n;             // samples; nothing at or beyond n is touched
@@ -372,7 +372,6 @@ struct LimRow {
     int32_t design, pad;   // the index of the row's design among the table's
 };
 static_assert(sizeof(LimRow) == 40, "a turn of the limiter ring holds 256 of them");
-struct LimScan;
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
 void launch_limiter(const LimRow* rows_dev, int n, int max_tiles, const LimScan* designs_dev, hipStream_t stream);
 

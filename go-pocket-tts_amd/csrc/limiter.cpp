@@ -7,38 +7,21 @@
 #include <cstddef>
 #include <vector>
 
-#include "true_peak.h"
+#include "dsp_ext.h"
+#include "opts_check.h"
 
 namespace ptts {
-
-namespace {
-int fail(const std::string& e) {
-    set_last_error("ptts-hip: " + e);
-    return PTTS_EINVAL;
-}
-
-bool range_error(const char* field, double v, double lo, double hi, std::string& out) {
-    if (std::isfinite(v) && v >= lo && v <= hi) return false;
-    out = strfmt("limiter: %s %g is not a finite value from %g to %g", field, v, lo, hi);
-    return true;
-}
-}  // namespace
 
 std::string lim_opts_error(const ptts_limiter_opts* l) {
     if (!l) return "limiter: null options";
     constexpr size_t kKnown = sizeof(ptts_limiter_opts);
-    if (l->size < kKnown) return strfmt("limiter: size %u is smaller than the fields up to drive_db (%zu bytes)", l->size, kKnown);
-    if (l->size > kKnown) {   // a caller newer than this library: whatever it says beyond what is known here must be "off"
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(l);
-        for (size_t i = kKnown; i < l->size; i++)
-            if (b[i]) return strfmt("limiter: size %u: byte %zu is not 0, and this library knows %zu bytes", l->size, i, kKnown);
-    }
+    std::string e = opts_size_error("limiter", l, l->size, kKnown, kKnown, "the fields up to drive_db");
+    if (!e.empty()) return e;
     if (l->reserved) return strfmt("limiter: reserved is %d, must be 0", l->reserved);
-    std::string e;
-    if (range_error("ceiling_db", l->ceiling_db, -60.0, 0.0, e)) return e;
-    if (range_error("lookahead_ms", l->lookahead_ms, 0.25, 5.0, e)) return e;
-    if (range_error("release_ms", l->release_ms, 5.0, 5000.0, e)) return e;
-    if (range_error("drive_db", l->drive_db, 0.0, 24.0, e)) return e;
+    const auto bad = [&e](const char* field, double v, double lo, double hi) { return range_error("limiter", field, v, lo, hi, e); };
+    if (bad("ceiling_db", l->ceiling_db, -60.0, 0.0) || bad("lookahead_ms", l->lookahead_ms, 0.25, 5.0) || bad("release_ms", l->release_ms, 5.0, 5000.0) ||
+        bad("drive_db", l->drive_db, 0.0, 24.0))
+        return e;
     return std::string();
 }
 

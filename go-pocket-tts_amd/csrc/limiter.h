@@ -49,7 +49,6 @@ struct LimScan {
     int32_t L, pad;                  // the look-ahead in samples, lrint(lookahead_ms * 24): 6 .. kLimMaxAhead
     double pad2;
 };
-static_assert(sizeof(LimScan) == 64, "kernels.h sizes the limiter ring's tail by it");
 
 constexpr int kLimMaxAhead = 120;   // 5 ms
 

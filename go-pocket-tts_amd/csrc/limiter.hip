@@ -14,6 +14,7 @@
 // the three kernels that read x across a tile's edge write scratch only, and k_lim_apply, the only one that writes x, reads x in its own
 // tile only.  Stream order has each launch complete before the next reads what it wrote.  Nothing at or beyond n is read or written.
 #include "device_util.h"
+#include "dsp_tile.h"
 #include "limiter.h"
 
 namespace ptts {
@@ -22,11 +23,6 @@ namespace {
 
 constexpr int kLimLds = kDspTile + kLimMaxAhead;   // floats: a tile and the longest halo
 
-// only a full tile that another one follows hands a state on
-__device__ __forceinline__ bool lim_hands_on(const LimRow& r) { return (int64_t)(blockIdx.x + 1) * kDspTile < r.n; }
-// samples of the lane's run in a tile of cnt
-__device__ __forceinline__ int lim_run_count(int cnt) { return max(0, min(kDspRun, cnt - (int)threadIdx.x * kDspRun)); }
-
 // the magnitudes of samples [base, base + kDspTile + L) into ax; zero at and beyond n
 __device__ __forceinline__ void lim_load_mag(const LimRow& r, int64_t base, int L, float* ax) {
     const int have = (int)min((int64_t)(kDspTile + L), r.n - base);
@@ -34,24 +30,11 @@ __device__ __forceinline__ void lim_load_mag(const LimRow& r, int64_t base, int 
     for (int q = threadIdx.x; q < kDspTile + L; q += kDspLanes) ax[q] = (q < have) ? lim_mag(src[q]) : 0.0f;
 }
 
-// The release's fold over a tile's runs from state S: e[l] is run l's end state from zero (LDS, [kDspLanes], complete).  Returns the state
-// entering the lane's run; *behind receives the state behind the last run
-__device__ __forceinline__ double lim_enter(const LimScan& d, const double* e, double S, double* behind) {
-    const int l = threadIdx.x;
-    double t = S, mine = S;
-    for (int j = 0; j < kDspLanes; j++) {
-        if (j == l) mine = t;
-        t = cmp_fold_p(d.rho_run, t, e[j]);
-    }
-    *behind = t;
-    return mine;
-}
-
 __global__ __launch_bounds__(kDspLanes) void k_lim_summary(const LimRow* __restrict__ rows, const LimScan* __restrict__ designs) {
     __shared__ float ax[kLimLds];
     __shared__ double e[kDspLanes];
     const LimRow& r = rows[blockIdx.y];
-    if (!lim_hands_on(r)) return;
+    if (!tile_hands_on(r.n)) return;
     const LimScan d = designs[r.design];
     lim_load_mag(r, (int64_t)blockIdx.x * kDspTile, d.L, ax);
     __syncthreads();
@@ -61,31 +44,15 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_summary(const LimRow* __restr
     e[l] = lim_run_p(d, m, kDspRun, 0.0);
     __syncthreads();
     double E;
-    lim_enter(d, e, 0.0, &E);
+    fold_enter_max(d.rho_run, e, 0.0, &E);
     if (l == 0) scan_E<1>(r.p_tiles, blockIdx.x)[0] = E;
 }
 
-// a row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time, by every lane alike (lane 0 stores); the state is carried from
-// one group of 64 to the next
 __global__ __launch_bounds__(kDspLanes) void k_lim_carry(const LimRow* __restrict__ rows, const LimScan* __restrict__ designs) {
     __shared__ double ein[kDspLanes];
     const LimRow& r = rows[blockIdx.x];
     if (r.n <= 0) return;
-    const LimScan d = designs[r.design];
-    const int64_t F = scan_tiles(r.n);
-    const int l = threadIdx.x;
-    double s = 0.0;   // the state entering tile c0 + j
-    for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
-        const int64_t f = c0 + l;
-        if (f < F - 1) ein[l] = scan_E<1>(r.p_tiles, f)[0];
-        __syncthreads();
-        const int m = (int)min((int64_t)kDspLanes, F - c0);
-        for (int j = 0; j < m; j++) {
-            if (l == 0) scan_S<1>(r.p_tiles, c0 + j)[0] = s;
-            if (c0 + j < F - 1) s = cmp_fold_p(d.rho_tile, s, ein[j]);
-        }
-        __syncthreads();
-    }
+    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_lim_gain(const LimRow* __restrict__ rows, const LimScan* __restrict__ designs) {
@@ -98,13 +65,13 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_gain(const LimRow* __restrict
     const LimScan d = designs[r.design];
     lim_load_mag(r, base, d.L, ax);
     __syncthreads();
-    const int l = threadIdx.x, c = lim_run_count(cnt);
+    const int l = threadIdx.x, c = run_count(cnt);
     float m[kDspRun];
     lim_hold(ax + l * kDspRun, d.L, m);
     e[l] = lim_run_p(d, m, c, 0.0);
     __syncthreads();   // (every lane has read its windows: ax may be written)
     double behind;
-    const double tp = lim_enter(d, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
+    const double tp = fold_enter_max(d.rho_run, e, scan_S<1>(r.p_tiles, blockIdx.x)[0], &behind);
     lim_run_r(d, m, c, tp, ax + l * kDspRun);
     __syncthreads();
     float* dst = r.r + base;
@@ -127,7 +94,7 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_apply(const LimRow* __restric
     float* x = r.x + base;
     for (int q = threadIdx.x; q < cnt; q += kDspLanes) tile[q] = x[q];
     __syncthreads();
-    const int l = threadIdx.x, c = lim_run_count(cnt);
+    const int l = threadIdx.x, c = run_count(cnt);
     if (c > 0) {
         const float* mine = rr + l * kDspRun;   // the run's windows: mine[0, L + c)
         bool ones = true;

@@ -45,7 +45,7 @@ enum WorkSlot : size_t {
     WORK_CONVERT_IN = 25,        // device_convert (ptts_resample, ptts_pcm_encode): the packed input rows
     WORK_CONVERT_OUT = 26,       // ... and the packed output rows
     WORK_ENCODER_CLIP = 26,      // mimi_encode_clip: a voice clip at its own rate, in front of k_resample.  Shares WORK_CONVERT_OUT's storage (see above)
-    WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words and per-tile scan states
+    WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words, then what dsp_scratch (dsp_spec.h) plans for each row's stages
     WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin
 };
 

@@ -4,6 +4,8 @@
 #include <cstring>
 #include <new>
 
+#include "dsp_ext.h"
+#include "opts_check.h"
 #include "rate_taps.h"
 #include "true_peak.h"
 
@@ -14,11 +16,6 @@
 namespace ptts {
 
 namespace {
-int fail(const std::string& e) {
-    set_last_error("ptts-hip: " + e);
-    return PTTS_EINVAL;
-}
-
 // TP of the row; one body, compiled twice on x86-64: fmaf as the fused instruction where the processor has it, the C library's fmaf (the
 // same correctly rounded result) where it has not
 __attribute__((always_inline)) inline float measure(const float* x, int64_t n, const TpTaps& t, float* y) {
@@ -94,14 +91,10 @@ int ptts_dsp_ext_create(const ptts_dsp_ext_opts* o, ptts_dsp_ext** out) {
     if (!o || !out) return fail("dsp ext: null argument");
     *out = nullptr;
     constexpr size_t kKnown = sizeof(ptts_dsp_ext_opts), kLeast = offsetof(ptts_dsp_ext_opts, ceiling_dbtp) + sizeof(double);
-    if (o->size < kLeast) return fail(strfmt("dsp ext: size %u is smaller than true_peak and ceiling_dbtp (%zu bytes)", o->size, kLeast));
-    if (o->size > kKnown) {   // a caller newer than this library: whatever it says beyond what is known here must be "off"
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(o);
-        for (size_t i = kKnown; i < o->size; i++)
-            if (b[i]) return fail(strfmt("dsp ext: size %u: byte %zu is not 0, and this library knows %zu bytes", o->size, i, kKnown));
-    }
+    std::string e = opts_size_error("dsp ext", o, o->size, kLeast, kKnown, "true_peak and ceiling_dbtp");
+    if (!e.empty()) return fail(e);
     if (o->true_peak != 0 && o->true_peak != 1) return fail(strfmt("dsp ext: true_peak %d is not 0 or 1", o->true_peak));
-    const std::string e = tp_ceiling_error(o->ceiling_dbtp);
+    e = tp_ceiling_error(o->ceiling_dbtp);
     if (!e.empty()) return fail("dsp ext: " + e);
     ptts_dsp_ext* h = new (std::nothrow) ptts_dsp_ext{};
     if (!h) { set_last_error("ptts-hip: out of host memory"); return PTTS_ENOMEM; }

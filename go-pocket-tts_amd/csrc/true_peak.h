@@ -1,4 +1,4 @@
-// true_peak.h -- the true-peak meter of a request's ceiling (include/ptts.h ptts_true_peak, ptts_dsp_ext), written once
+// true_peak.h -- the true-peak meter of a request's ceiling (include/ptts.h ptts_true_peak; the handle that carries it: dsp_ext.h), written once
 // for the host (true_peak.cpp) and the device (true_peak.hip).  No HIP header: true_peak.cpp builds with a plain C++ compiler.
 //
 // The meter oversamples the 24 kHz row eight times, to the 192 kHz of ITU-R BS.1770-4 Annex 2, with the project's own polyphase design
@@ -11,10 +11,9 @@
 // under-read: a 10 kHz tone reads 0.16 dB low.  Speech from this decoder has little energy there.
 #pragma once
 #include <cmath>
+#include <string>
 
-#include "compressor.h"
-#include "eq.h"
-#include "limiter.h"
+#include "scan_block.h"
 
 namespace ptts {
 
@@ -56,12 +55,4 @@ std::string tp_ceiling_error(double ceiling_dbtp);
 // c = (float)pow(10, dBTP / 20)
 inline float tp_ceiling(double ceiling_dbtp) { return (float)std::pow(10.0, ceiling_dbtp / 20.0); }
 
-// what a live ptts_dsp_ext says, by value (false: e is NULL or not live, and e is not read): the ceiling, the compressor that
-// ptts_dsp_ext_set_compressor attached (compressor.cpp) and the limiter that ptts_dsp_ext_set_limiter attached (limiter.cpp), both as designed.
-// Copied out under the registry's mutex, which the setters take too
-struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; bool limit = false; LimScan lim{}; };
-bool ext_lookup(const ptts_dsp_ext* e, DspExt* out);
-
 }  // namespace ptts
-
-struct ptts_dsp_ext { ptts::DspExt v; };   // (true_peak.cpp makes and frees it, compressor.cpp sets its compressor, limiter.cpp its limiter)

@@ -1,5 +1,5 @@
 // true_peak.hip -- the true-peak ceiling of ragged rows of 24 kHz audio on the device, the last stage of the post-processing chain (kernels.h
-// DspRow, DSP_TP rows; true_peak.h).  launch_dsp (dsp.hip) launches both behind the table's last kernel.
+// DspRow, DSP_TP rows; true_peak.h).  dsp_launch (dsp_device.cpp) launches both behind the table's last kernel, k_tp_peak alone for a measurement.
 //
 //   k_tp_peak    grid (tile, row), kTpThreads = 256 threads.  A tile is kDspTile samples on the row's own grid.  The workgroup stages its tile
 //                with the 26 samples in front and the 27 behind into LDS, zeros outside [0, n); lane l then takes the samples l, l + 256, ... of

@@ -691,35 +691,29 @@ class Model:
         _check(lib().ptts_dsp_rows(self.h, pp, _ip(ns), n, C.byref(o), _row_ptrs(outs)))
         return outs[0] if single else outs
 
+    def _stage_rows(self, entry, x, each, pointer_type, pointer_of):
+        """The host-rows entry points that take one option per row: each is one for every row, or one per row (None copies that row)."""
+        single, rows, n, pp, ns = _rows_in(x)
+        per_row = list(each) if isinstance(each, (list, tuple)) else [each] * n
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        po = (pointer_type * max(n, 1))(*[pointer_of(o) if o is not None else None for o in per_row])
+        _check(entry(self.h, po, pp, _ip(ns), n, _row_ptrs(outs)))
+        return outs[0] if single else outs
+
     def eq_rows(self, x, eq):
         """ptts_eq_rows: Eq.apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).  eq: one Eq for
         every row, or one per row (None copies that row)."""
-        single, rows, n, pp, ns = _rows_in(x)
-        eqs = list(eq) if isinstance(eq, (list, tuple)) else [eq] * n
-        outs = [np.empty(r.size, np.float32) for r in rows]
-        pe = (C.c_void_p * max(n, 1))(*[e.h if e is not None else None for e in eqs])
-        _check(lib().ptts_eq_rows(self.h, pe, pp, _ip(ns), n, _row_ptrs(outs)))
-        return outs[0] if single else outs
+        return self._stage_rows(lib().ptts_eq_rows, x, eq, C.c_void_p, lambda e: e.h)
 
     def compress_rows(self, x, compressor):
         """ptts_compress_rows: compress_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
         compressor: one CompressorOpts for every row, or one per row (None copies that row)."""
-        single, rows, n, pp, ns = _rows_in(x)
-        cs = list(compressor) if isinstance(compressor, (list, tuple)) else [compressor] * n
-        outs = [np.empty(r.size, np.float32) for r in rows]
-        pc = (C.POINTER(CompressorOpts) * max(n, 1))(*[C.pointer(c) if c is not None else None for c in cs])
-        _check(lib().ptts_compress_rows(self.h, pc, pp, _ip(ns), n, _row_ptrs(outs)))
-        return outs[0] if single else outs
+        return self._stage_rows(lib().ptts_compress_rows, x, compressor, C.POINTER(CompressorOpts), C.pointer)
 
     def limit_rows(self, x, limiter):
         """ptts_limit_rows: limit_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
         limiter: one LimiterOpts for every row, or one per row (None copies that row)."""
-        single, rows, n, pp, ns = _rows_in(x)
-        ls = list(limiter) if isinstance(limiter, (list, tuple)) else [limiter] * n
-        outs = [np.empty(r.size, np.float32) for r in rows]
-        pl = (C.POINTER(LimiterOpts) * max(n, 1))(*[C.pointer(l) if l is not None else None for l in ls])
-        _check(lib().ptts_limit_rows(self.h, pl, pp, _ip(ns), n, _row_ptrs(outs)))
-        return outs[0] if single else outs
+        return self._stage_rows(lib().ptts_limit_rows, x, limiter, C.POINTER(LimiterOpts), C.pointer)
 
     def true_peak_rows(self, x):
         """ptts_true_peak_rows: true_peak() of mono f32 rows at 24 kHz (an array, or a list: one launch for all), measured on the device."""
@@ -1707,18 +1701,20 @@ def compress_gain(compressor: CompressorOpts, level_db: float) -> float:
     return float(out.value)
 
 
+def _apply_on_host(entry, opts, samples) -> np.ndarray:
+    out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    _check(entry(C.byref(opts), _fp(out), out.size))
+    return out
+
+
 def compress_apply(compressor: CompressorOpts, samples) -> np.ndarray:
     """ptts_compress_apply: the compressor over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
-    out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
-    _check(lib().ptts_compress_apply(C.byref(compressor), _fp(out), out.size))
-    return out
+    return _apply_on_host(lib().ptts_compress_apply, compressor, samples)
 
 
 def limit_apply(limiter: LimiterOpts, samples) -> np.ndarray:
     """ptts_limit_apply: the limiter over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
-    out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
-    _check(lib().ptts_limit_apply(C.byref(limiter), _fp(out), out.size))
-    return out
+    return _apply_on_host(lib().ptts_limit_apply, limiter, samples)
 
 
 def true_peak(samples) -> float:

@@ -1,5 +1,5 @@
-"""The host-rows entry points of include/ptts.h (ptts_dsp_rows, ptts_eq_rows, ptts_loudness_rows, ptts_loudness_normalize_rows,
-ptts_true_peak_rows; ptts_resample and ptts_pcm_encode beside them) as one round trip: pack, upload, launch, download.  What each of them
+"""The host-rows entry points of include/ptts.h (ptts_dsp_rows, ptts_eq_rows, ptts_compress_rows, ptts_limit_rows, ptts_loudness_rows,
+ptts_loudness_normalize_rows, ptts_true_peak_rows; ptts_resample and ptts_pcm_encode beside them) as one round trip: pack, upload, launch, download.  What each of them
 promises at its edges -- rows that alias their outputs, calls with nothing in them, rows that share a call, tables that fill up, and the
 launches of a call -- through the public ABI and the launch census alone."""
 import ctypes as C
@@ -136,13 +136,71 @@ def test_a_call_larger_than_one_table(pkg, tiny):  # noqa: F811
     rt.launch_counts(True)
     got = gm.eq_rows(rows, which)
     counts = _census(rt.launch_counts(False))
-    assert counts.get("k_eq_apply", 0) >= 2, counts
+    assert counts.get("k_eq_apply", 0) == 17, counts   # greedy: the 17th equaliser starts the next table, so sixteen tables of 16 rows and one of 1
     assert _same(got, [e.apply(r) for r, e in zip(rows, which)])
     for e in eqs:
         e.free()
     rows = [x[i:i + 27].copy() for i in range(257)]
     got = gm.true_peak_rows(rows)
     assert np.array_equal(_u32(got), _u32(np.array([rt.true_peak(r) for r in rows], np.float32)))
+
+
+def _peak_db(rows):
+    return 20.0 * np.log10(min(float(np.abs(r).max()) for r in rows))
+
+
+def test_compress_rows_larger_than_one_table(pkg, tiny):  # noqa: F811
+    """257 rows with 17 distinct compressors: the compressor's own table cuts, at the 257th row and at the 17th design."""
+    _, gm = tiny
+    rt = pkg.runtime
+    cs = [rt.CompressorOpts(threshold_db=-60.0 + i) for i in range(17)]
+    x = E.signal(257 + 30, seed=15)
+    rows = [x[i:i + 30].copy() for i in range(257)]
+    assert _peak_db(rows) > -44.0 + 6.0   # every row's peak lies above every threshold and knee
+    which = [cs[i % 17] for i in range(257)]
+    rt.launch_counts(True)
+    got = gm.compress_rows(rows, which)
+    counts = rt.launch_counts(False)
+    assert {k: v for k, v in counts.items() if k.startswith("k_cmp")} == {"k_cmp_carry_p": 17, "k_cmp_carry_s": 17, "k_cmp_apply": 17}, counts
+    want = [rt.compress_apply(c, r) for r, c in zip(rows, which)]
+    assert _same(got, want)
+    assert not any(np.array_equal(_u32(w), _u32(r)) for w, r in zip(want, rows))
+    assert len({_u32(rt.compress_apply(c, rows[0])).tobytes() for c in cs}) == 17   # (17 designs that differ in what they do)
+
+
+def test_limit_rows_larger_than_one_table(pkg, tiny):  # noqa: F811
+    """257 rows with 17 distinct limiters: the limiter's own table cuts, at the 257th row and at the 17th design."""
+    _, gm = tiny
+    rt = pkg.runtime
+    ls = [rt.LimiterOpts(ceiling_db=-60.0 + i) for i in range(17)]
+    x = E.signal(257 + 30, seed=16)
+    rows = [x[i:i + 30].copy() for i in range(257)]
+    assert _peak_db(rows) > -44.0   # every row's peak lies above every ceiling
+    which = [ls[i % 17] for i in range(257)]
+    rt.launch_counts(True)
+    got = gm.limit_rows(rows, which)
+    counts = rt.launch_counts(False)
+    assert {k: v for k, v in counts.items() if k.startswith("k_lim")} == {"k_lim_carry": 17, "k_lim_gain": 17, "k_lim_apply": 17}, counts
+    want = [rt.limit_apply(l, r) for r, l in zip(rows, which)]
+    assert _same(got, want)
+    assert not any(np.array_equal(_u32(w), _u32(r)) for w, r in zip(want, rows))
+    assert len({_u32(rt.limit_apply(l, rows[0])).tobytes() for l in ls}) == 17   # (17 designs that differ in what they do)
+
+
+def test_a_mixed_call_gives_every_row_its_own_scratch(pkg, tiny):  # noqa: F811
+    """40 rows of four lengths through every stage that takes scratch at once -- a compressor, normalise, DC block, fades, a limiter and a
+    ceiling: the bits of the same rows one per call, so no row's states lie in another row's region."""
+    _, gm = tiny
+    rt = pkg.runtime
+    ext = rt.DspExt(true_peak_dbtp=-9.0, compressor=rt.CompressorOpts(threshold_db=-30.0), limiter=rt.LimiterOpts(ceiling_db=-6.0))
+    o = rt.DspOpts(1, 1, 50.0, 80.0)
+    o.ext = ext.h
+    rows = _rows([1, 1919, 1921, 9601] * 10, seed=17)
+    got = gm.dsp_rows(rows, opts=o)
+    alone = [gm.dsp_rows(r, opts=o) for r in rows]
+    assert _same(got, alone)
+    assert not np.array_equal(_u32(got[3]), _u32(gm.dsp_rows(rows[3], normalize=True, dc_block=True, **FADES)))   # (the ext's stages ran)
+    ext.free()
 
 
 def test_launch_census_of_every_entry_point(pkg, tiny):  # noqa: F811
