@@ -3,6 +3,7 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
@@ -32,7 +33,6 @@ constexpr int ATT_NI = 16;
 // address-space-qualified views: a pointer that arrives through memory is 'generic' to the compiler, which then emits
 // flat_load (LDS-aperture check, both wait counters); these say where the data is.  The constant view of a wave-uniform
 // index turns into a scalar load.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) u32x4* gptr_u4;
 __device__ __forceinline__ uint4 gload16(const char* p) {
     const u32x4 t = *(gptr_u4)p;

@@ -5,29 +5,9 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-union FragW {
-    bf16x8 v;
-    uint4 q;
-    unsigned u[4];
-};
-
-// (a, b) -> packed bf16 hi pair and bf16 lo pair with a = hi + lo to ~2^-17 (round-to-nearest-even)
-__device__ __forceinline__ void split2w(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
 
 // One WAVE owns 32 consecutive query rows of one (utterance, head) and walks the union of their windows (at most
 // 32 + context - 1 keys) in tiles of 32 keys on the matrix cores.  Everything is computed TRANSPOSED so that no operand
@@ -72,16 +52,16 @@ __global__ __launch_bounds__(256) void k_attn_window(AttnArgs a, int qtiles) {
     const RowMap qm{a.q_ld, a.q_rows_per_batch, a.q_batch_stride}, om{a.out_ld, a.o_rows_per_batch, a.o_batch_stride};
     const int row = seg_row0 + r0 + my_q;
 
-    FragW qh[4], ql[4];   // step i: dims 16 i + 8 half .. + 7 of the lane's query, scaled by 1/sqrt(64) (exact)
+    Frag qh[4], ql[4];   // step i: dims 16 i + 8 half .. + 7 of the lane's query, scaled by 1/sqrt(64) (exact)
     {
         const float* qp = a.q + row_off(qm, row) + a.q_col0 + h * 64 + half * 8;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const float4 t0 = *reinterpret_cast<const float4*>(qp + 16 * i), t1 = *reinterpret_cast<const float4*>(qp + 16 * i + 4);
-            split2w(t0.x * 0.125f, t0.y * 0.125f, qh[i].u[0], ql[i].u[0]);
-            split2w(t0.z * 0.125f, t0.w * 0.125f, qh[i].u[1], ql[i].u[1]);
-            split2w(t1.x * 0.125f, t1.y * 0.125f, qh[i].u[2], ql[i].u[2]);
-            split2w(t1.z * 0.125f, t1.w * 0.125f, qh[i].u[3], ql[i].u[3]);
+            split2(t0.x * 0.125f, t0.y * 0.125f, qh[i].u[0], ql[i].u[0]);
+            split2(t0.z * 0.125f, t0.w * 0.125f, qh[i].u[1], ql[i].u[1]);
+            split2(t1.x * 0.125f, t1.y * 0.125f, qh[i].u[2], ql[i].u[2]);
+            split2(t1.z * 0.125f, t1.w * 0.125f, qh[i].u[3], ql[i].u[3]);
         }
     }
     typedef typename std::conditional<KVBF16, unsigned short, float>::type KvT;
@@ -93,7 +73,7 @@ __global__ __launch_bounds__(256) void k_attn_window(AttnArgs a, int qtiles) {
     float m = -INFINITY, l = 0.0f;
 
     for (int kt = j_lo; kt <= p_last; kt += 32) {
-        FragW kh[4], kl[4];
+        Frag kh[4], kl[4];
         {
             const KvT* kp = kb + (int64_t)min(kt + j, p_last) * a.k_row_stride + half * 8;
             if constexpr (KVBF16) {
@@ -107,12 +87,7 @@ __global__ __launch_bounds__(256) void k_attn_window(AttnArgs a, int qtiles) {
                     t[i][1] = *reinterpret_cast<const float4*>(kp + 16 * i + 4);
                 }
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    split2w(t[i][0].x, t[i][0].y, kh[i].u[0], kl[i].u[0]);
-                    split2w(t[i][0].z, t[i][0].w, kh[i].u[1], kl[i].u[1]);
-                    split2w(t[i][1].x, t[i][1].y, kh[i].u[2], kl[i].u[2]);
-                    split2w(t[i][1].z, t[i][1].w, kh[i].u[3], kl[i].u[3]);
-                }
+                for (int i = 0; i < 4; i++) split8(t[i][0], t[i][1], kh[i], kl[i]);
             }
         }
         // values of the tile's 32 keys for dims j and 32 + j, in the key order of the score registers
@@ -161,12 +136,12 @@ __global__ __launch_bounds__(256) void k_attn_window(AttnArgs a, int qtiles) {
         }
 #pragma unroll
         for (int i = 0; i < 2; i++) {
-            FragW ph, pl, vh0, vl0, vh1, vl1;
+            Frag ph, pl, vh0, vl0, vh1, vl1;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                split2w(s[8 * i + 2 * e], s[8 * i + 2 * e + 1], ph.u[e], pl.u[e]);
-                split2w(v0[8 * i + 2 * e], v0[8 * i + 2 * e + 1], vh0.u[e], vl0.u[e]);
-                split2w(v1[8 * i + 2 * e], v1[8 * i + 2 * e + 1], vh1.u[e], vl1.u[e]);
+                split2(s[8 * i + 2 * e], s[8 * i + 2 * e + 1], ph.u[e], pl.u[e]);
+                split2(v0[8 * i + 2 * e], v0[8 * i + 2 * e + 1], vh0.u[e], vl0.u[e]);
+                split2(v1[8 * i + 2 * e], v1[8 * i + 2 * e + 1], vh1.u[e], vl1.u[e]);
             }
             o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh0.v, ph.v, o0, 0, 0, 0);
             if constexpr (!KVBF16) PTTS_LO_MFMA(o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl0.v, ph.v, o0, 0, 0, 0));
@@ -236,16 +211,16 @@ __global__ __launch_bounds__(64 * NW) void k_attn_window_lds(AttnArgs a, int qbl
     const RowMap qm{a.q_ld, a.q_rows_per_batch, a.q_batch_stride}, om{a.out_ld, a.o_rows_per_batch, a.o_batch_stride};
     const int row = seg * seg_rows + (wave_on ? r0 : b0) + my_q;
 
-    FragW qh[4], ql[4];   // step i: dims 16 i + 8 half .. + 7 of the lane's query, scaled by 1/sqrt(64) (exact)
+    Frag qh[4], ql[4];   // step i: dims 16 i + 8 half .. + 7 of the lane's query, scaled by 1/sqrt(64) (exact)
     {
         const float* qp = a.q + row_off(qm, row) + a.q_col0 + h * 64 + half * 8;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const float4 t0 = *reinterpret_cast<const float4*>(qp + 16 * i), t1 = *reinterpret_cast<const float4*>(qp + 16 * i + 4);
-            split2w(t0.x * 0.125f, t0.y * 0.125f, qh[i].u[0], ql[i].u[0]);
-            split2w(t0.z * 0.125f, t0.w * 0.125f, qh[i].u[1], ql[i].u[1]);
-            split2w(t1.x * 0.125f, t1.y * 0.125f, qh[i].u[2], ql[i].u[2]);
-            split2w(t1.z * 0.125f, t1.w * 0.125f, qh[i].u[3], ql[i].u[3]);
+            split2(t0.x * 0.125f, t0.y * 0.125f, qh[i].u[0], ql[i].u[0]);
+            split2(t0.z * 0.125f, t0.w * 0.125f, qh[i].u[1], ql[i].u[1]);
+            split2(t1.x * 0.125f, t1.y * 0.125f, qh[i].u[2], ql[i].u[2]);
+            split2(t1.z * 0.125f, t1.w * 0.125f, qh[i].u[3], ql[i].u[3]);
         }
     }
     const float* kb = (const float*)a.k + (int64_t)seg * a.k_seg_stride + (int64_t)h * a.k_head_stride;
@@ -285,16 +260,16 @@ __global__ __launch_bounds__(64 * NW) void k_attn_window_lds(AttnArgs a, int qbl
             const int k_dst = sk * 128 + ((sc ^ ((sk >> 1) & 7)) << 4);
             const int v_dst = sd * 64 + ((sg ^ aw_vswz(sd)) << 4);
             uint4 hq, lq;
-            split2w(sk0[u].x, sk0[u].y, hq.x, lq.x);
-            split2w(sk0[u].z, sk0[u].w, hq.y, lq.y);
-            split2w(sk1[u].x, sk1[u].y, hq.z, lq.z);
-            split2w(sk1[u].z, sk1[u].w, hq.w, lq.w);
+            split2(sk0[u].x, sk0[u].y, hq.x, lq.x);
+            split2(sk0[u].z, sk0[u].w, hq.y, lq.y);
+            split2(sk1[u].x, sk1[u].y, hq.z, lq.z);
+            split2(sk1[u].z, sk1[u].w, hq.w, lq.w);
             *reinterpret_cast<uint4*>(buf + k_dst) = hq;
             *reinterpret_cast<uint4*>(buf + AW_KB + k_dst) = lq;
-            split2w(sv[u][0], sv[u][1], hq.x, lq.x);
-            split2w(sv[u][2], sv[u][3], hq.y, lq.y);
-            split2w(sv[u][4], sv[u][5], hq.z, lq.z);
-            split2w(sv[u][6], sv[u][7], hq.w, lq.w);
+            split2(sv[u][0], sv[u][1], hq.x, lq.x);
+            split2(sv[u][2], sv[u][3], hq.y, lq.y);
+            split2(sv[u][4], sv[u][5], hq.z, lq.z);
+            split2(sv[u][6], sv[u][7], hq.w, lq.w);
             *reinterpret_cast<uint4*>(buf + 2 * AW_KB + v_dst) = hq;
             *reinterpret_cast<uint4*>(buf + 2 * AW_KB + AW_VB + v_dst) = lq;
         }
@@ -322,7 +297,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_window_lds(AttnArgs a, int qbl
             for (int r = 0; r < 16; r++) s[r] = 0.0f;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                FragW kh, kl;
+                Frag kh, kl;
                 kh.q = *reinterpret_cast<const uint4*>(buf + ka + (((2 * i + half) ^ ksw) << 4));
                 kl.q = *reinterpret_cast<const uint4*>(buf + AW_KB + ka + (((2 * i + half) ^ ksw) << 4));
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh.v, qh[i].v, s, 0, 0, 0);
@@ -357,9 +332,9 @@ __global__ __launch_bounds__(64 * NW) void k_attn_window_lds(AttnArgs a, int qbl
             }
 #pragma unroll
             for (int i = 0; i < 2; i++) {
-                FragW ph, pl, vh0, vl0, vh1, vl1;
+                Frag ph, pl, vh0, vl0, vh1, vl1;
 #pragma unroll
-                for (int e = 0; e < 4; e++) split2w(s[8 * i + 2 * e], s[8 * i + 2 * e + 1], ph.u[e], pl.u[e]);
+                for (int e = 0; e < 4; e++) split2(s[8 * i + 2 * e], s[8 * i + 2 * e + 1], ph.u[e], pl.u[e]);
                 const unsigned char* vt = buf + 2 * AW_KB;
                 vh0.q = *reinterpret_cast<const uint4*>(vt + va0 + (((2 * i + half) ^ vsw0) << 4));
                 vl0.q = *reinterpret_cast<const uint4*>(vt + AW_VB + va0 + (((2 * i + half) ^ vsw0) << 4));

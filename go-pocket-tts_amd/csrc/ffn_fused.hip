@@ -24,30 +24,11 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
 namespace {
-
-typedef __bf16 ff_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ff_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ff_f32x2 __attribute__((ext_vector_type(2)));
-typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
-
-union FfFrag {
-    ff_bf16x8 v;
-    uint4 q;
-    unsigned u[4];
-};
-
-__device__ __forceinline__ void ff_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    ff_f32x2 f = {a, b};
-    ff_bf16x2 h = __builtin_convertvector(f, ff_bf16x2);
-    ff_f32x2 r = f - __builtin_convertvector(h, ff_f32x2);
-    ff_bf16x2 l = __builtin_convertvector(r, ff_bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
 
 // GELU(erf) with erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7 absolute): 1 - (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z = |x| / sqrt 2.  Branch-free,
 // ~16 vector instructions with two transcendentals (v_rcp_f32, v_exp_f32) -- libm's erff is ~40 with a divergent branch, and this kernel evaluates it
@@ -76,24 +57,11 @@ constexpr int FF_W2B = FF_D * FF_CH * 2;  // bytes of a W2 chunk image (32 KB)
 constexpr int FF_IMG = FF_W1B + FF_W2B;   // one chunk's images, contiguous in the arena
 
 // 32 KB global -> LDS by the block's four waves: 32 wave-instructions of 1 KB (lane l: 16 bytes at src + 16 l -> dst + 16 l).
-// Inline assembly on purpose: told about an LDS-DMA write (the builtin), hipcc puts `s_waitcnt vmcnt(0)` in front of the next ds_read of ANY slot --
-// it cannot tell the slots apart -- which is the copy waited for at once instead of an iteration later.  So the copies are invisible to its
-// counters and ordered by hand: every wave waits vmcnt(0) at the one place below where a slot changes hands, in front of the block's barrier.
-// (The compiler's own vmcnt(N) waits stay right: loads return in issue order, so a wait that lets the N youngest VISIBLE loads stay in flight
-// has also seen every older copy land; and no visible load is issued between a copy and that wait.)  m0 carries the LDS address; nothing else
-// in this kernel uses it -- and the compiler keeps nothing in it across statements: m0 is a RESERVED register to LLVM (listing it as a clobber is rejected as
-// "reserved registers on the clobber list"), written right in front of each of the compiler's own uses (s_sendmsg, GWS, v_movrel), none of which these kernels have.
-// One LDS-DMA wave-instruction: lane l's 16 bytes at src_lane -> dst + 16 l.  The wait state between the write of m0 and its use is written out because
-// the compiler's hazard recognizer does not look inside inline assembly (ISA: SALU write of M0 -> LDS "direct" / GDS / sendmsg use needs one).
-__device__ __forceinline__ void ff_dma1k(const char* src_lane, char* dst) {
-    const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(base), "v"(src_lane) : "memory");
-}
 __device__ __forceinline__ void ff_dma32k(const char* src, char* dst, int wave, int lane) {
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         const int idx = i * 4 + wave;
-        ff_dma1k(src + idx * 1024 + lane * 16, dst + idx * 1024);
+        lds_dma1k(src + idx * 1024 + lane * 16, dst + idx * 1024);
     }
 }
 
@@ -101,7 +69,7 @@ __device__ __forceinline__ void ff_dma32k(const char* src, char* dst, int wave, 
 // v_mfma_f32_16x16x32_bf16 for the 16 k steps, bf16 hi + lo (x = hi + lo to 2^-17).  k step s, lane (row, q): k = 32 s + 4 q + (0..3) and
 // 32 s + 16 + 4 q + (0..3) -- the k order the weight images are laid out in (and the order in which a pair of 16x16 accumulator tiles would hand
 // its values over: these kernels can take their rows from a product later).
-__device__ __forceinline__ void ff_rows_layernorm(const float* xrow, const float* ln_w, const float* ln_b, float eps, int q, FfFrag (&xh)[16], FfFrag (&xl)[16]) {
+__device__ __forceinline__ void ff_rows_layernorm(const float* xrow, const float* ln_w, const float* ln_b, float eps, int q, Frag (&xh)[16], Frag (&xl)[16]) {
     float4 v[16][2];
 #pragma unroll
     for (int s = 0; s < 16; s++) {
@@ -138,10 +106,10 @@ __device__ __forceinline__ void ff_rows_layernorm(const float* xrow, const float
             o[h].z = (v[s][h].z - mean) * rstd * g.z + b.z;
             o[h].w = (v[s][h].w - mean) * rstd * g.w + b.w;
         }
-        ff_split2(o[0].x, o[0].y, xh[s].u[0], xl[s].u[0]);
-        ff_split2(o[0].z, o[0].w, xh[s].u[1], xl[s].u[1]);
-        ff_split2(o[1].x, o[1].y, xh[s].u[2], xl[s].u[2]);
-        ff_split2(o[1].z, o[1].w, xh[s].u[3], xl[s].u[3]);
+        split2(o[0].x, o[0].y, xh[s].u[0], xl[s].u[0]);
+        split2(o[0].z, o[0].w, xh[s].u[1], xl[s].u[1]);
+        split2(o[1].x, o[1].y, xh[s].u[2], xl[s].u[2]);
+        split2(o[1].z, o[1].w, xh[s].u[3], xl[s].u[3]);
     }
 }
 
@@ -150,11 +118,11 @@ __device__ __forceinline__ void ff_rows_layernorm(const float* xrow, const float
 // multiplied; piece(s) is other work that rides in step s's shadow.  Each step is fenced (sched_barrier) and its order pinned (sched_group_barrier) --
 // left to itself the scheduler issues read, wait, multiply back to back and piles the vector work up in front of the matrix instructions.
 template <class Piece>
-__device__ __forceinline__ void ff_gemm1(const char* w1, int r16, int q, const FfFrag (&xh)[16], const FfFrag (&xl)[16], ff_f32x4 (&acc)[2], Piece&& piece) {
+__device__ __forceinline__ void ff_gemm1(const char* w1, int r16, int q, const Frag (&xh)[16], const Frag (&xl)[16], f32x4 (&acc)[2], Piece&& piece) {
     const int sw1 = (r16 >> 1) & 7;
-    acc[0] = ff_f32x4{0.f, 0.f, 0.f, 0.f};
-    acc[1] = ff_f32x4{0.f, 0.f, 0.f, 0.f};
-    FfFrag wa[2], wb[2];
+    acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    Frag wa[2], wb[2];
     const char* wl = w1 + r16 * 128;
     wa[0].q = *reinterpret_cast<const uint4*>(wl + ((q ^ sw1) << 4));
     wb[0].q = *reinterpret_cast<const uint4*>(wl + ((q ^ sw1) << 4) + 2048);
@@ -214,12 +182,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int m0 = blockIdx.x * 64 + wave * 16;
     const int row = min(m0 + r16, a.M - 1);
     const float* xrow = a.x + row_off(a.xmap, row);
-    FfFrag xh[FF_KS], xl[FF_KS];
+    Frag xh[FF_KS], xl[FF_KS];
     ff_rows_layernorm(xrow, a.ln_w, a.ln_b, a.eps, q, xh, xl);
 
-    ff_f32x4 acc2[FF_OT];
+    f32x4 acc2[FF_OT];
 #pragma unroll
-    for (int t = 0; t < FF_OT; t++) acc2[t] = ff_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < FF_OT; t++) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // fragment addresses inside a slot.  W1 image: [k pair j (8)][hidden unit h (32)][128 B], the 16-byte chunk (k-step parity sg, lane group q) of
     // row h at position (4 sg + q) ^ ((h >> 1) & 7); W2 image: [output o (512)][64 B], lane group q's chunk at q ^ (3 * ((o >> 3) & 1)).
@@ -227,7 +195,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the first copies has landed
     __syncthreads();                                   // ... and everybody else's
-    ff_f32x4 acc1[2], acc1n[2];
+    f32x4 acc1[2], acc1n[2];
     ff_gemm1(w1s(0), r16, q, xh, xl, acc1, [](int) {});
 
     for (int c = 0; c < nch; c++) {
@@ -247,20 +215,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // (past the last chunk the last one is copied again, into a slot nobody reads any more: no branch inside the fenced steps)
         // this chunk's activation in the shadow of the next chunk's first product: GELU(erf) (tensor_util.go:84-94) on the 8 sums the lane holds (one per
         // two k steps), split into hi + lo (one pair per four steps) -> the second product's B operand
-        FfFrag hh, hl;
+        Frag hh, hl;
         float g[8];
         ff_gemm1(w1s(min(c + 1, nch - 1) & 1), r16, q, xh, xl, acc1n, [&](int s) {   // (past the last chunk: the last slot once more, never used -- no branch around 64 matrix instructions)
             const int i = s >> 1;
             if ((s & 1) == 0) g[i] = ff_gelu(acc1[i >> 2][i & 3]);
-            else if (i & 1) ff_split2(g[i - 1], g[i], hh.u[i >> 1], hl.u[i >> 1]);
+            else if (i & 1) split2(g[i - 1], g[i], hh.u[i >> 1], hl.u[i >> 1]);
             if constexpr (V == 0) {
-                if (s < 8) ff_dma1k(src1 + s * 4096, dst1 + s * 4096);
-                else ff_dma1k(src2 + (s - 8) * 4096, dst2 + (s - 8) * 4096);
+                if (s < 8) lds_dma1k(src1 + s * 4096, dst1 + s * 4096);
+                else lds_dma1k(src2 + (s - 8) * 4096, dst2 + (s - 8) * 4096);
             }
         });
         // second product: Y^T += W2[:, chunk] x H^T, 32 output tiles x (one fragment read, two matrix instructions), fragment t+1 requested before t is multiplied
         const char* w2 = w2s(c & 1) + w2_lane;
-        FfFrag w2f[2];
+        Frag w2f[2];
         w2f[0].q = *reinterpret_cast<const uint4*>(w2);
 #pragma unroll
         for (int t = 0; t < FF_OT; t++) {
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int t = 0; t < 8; t++) {
 #pragma clang fp contract(off)
-                const ff_f32x4 y = acc2[t0 + t];
+                const f32x4 y = acc2[t0 + t];
                 float4 o;
                 o.x = r[t].x + sc[t].x * y[0];
                 o.y = r[t].y + sc[t].y * y[1];
@@ -326,7 +294,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     const int m0 = blockIdx.x * 64 + wave * 16;
     const int row = min(m0 + r16, a.M - 1);
-    FfFrag xh[FF_KS], xl[FF_KS];
+    Frag xh[FF_KS], xl[FF_KS];
     ff_rows_layernorm(a.x + row_off(a.xmap, row), a.ln_w, a.ln_b, a.eps, q, xh, xl);
     // RoPE: the lane's row sits at one position; its output columns 32 c + 16 ht + 4 q + (0..3) are two (even, odd) pairs of a 64-wide head, pair index
     // ((32 (c & 1) + 16 ht + 4 q) >> 1) + (0, 1): eight table entries per lane for the whole kernel
@@ -346,14 +314,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float* const yrow = a.y + row_off(a.ymap, row);
 
     // rotate + store the two tiles of chunk cc (PAR = cc & 1, compile time: it selects the table registers), pieces p = 0 (tile 0), 1 (tile 1)
-    auto store_piece = [&](ff_f32x4 (&acc)[2], int cc, auto par, int ht) {
+    auto store_piece = [&](f32x4 (&acc)[2], int cc, auto par, int ht) {
 #pragma clang fp contract(off)
         constexpr int PAR = decltype(par)::value;
         // (the reads of the sums stay HERE, five k steps and a barrier behind the matrix instruction that wrote them: see the note at the end of ff_gemm1)
         asm volatile("" : "+a"(acc[0]), "+a"(acc[1]));
         const int col = 32 * cc + 16 * ht + 4 * q;
         const bool rot = rope && 32 * cc < a.rope_cols;   // (rope_cols % 64 == 0: a chunk is rotated whole or not at all)
-        const ff_f32x4 v = acc[ht];
+        const f32x4 v = acc[ht];
         const float2 c2 = cs[2 * PAR + ht], s2 = sn[2 * PAR + ht];
         // products and sums rounded one by one, as the reference's x*c - y*s is (rope.go:81-105): contraction is off here
         const float y0 = v[0] * c2.x - v[1] * s2.x, y1 = v[0] * s2.x + v[1] * c2.x;
@@ -364,9 +332,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    ff_f32x4 accA[2], accB[2];
+    f32x4 accA[2], accB[2];
     // iteration c (parity PAR): copy chunk c+2 into the slot chunk c-1 has left, multiply chunk c into `acc`, and in its shadow rotate + store chunk c-1 from `prev`
-    auto iter = [&](int c, auto par, auto first, ff_f32x4 (&acc)[2], ff_f32x4 (&prev)[2]) {
+    auto iter = [&](int c, auto par, auto first, f32x4 (&acc)[2], f32x4 (&prev)[2]) {
         constexpr int PAR = decltype(par)::value;
         constexpr bool FIRST = decltype(first)::value != 0;
         if constexpr (!FIRST) {
@@ -378,7 +346,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const char* const src = img + (size_t)min(c + 2, nch - 1) * FF_W1B + wave * 1024 + lane * 16;
         char* const dst = lds + ((c + 2) % NS) * FF_W1B + wave * 1024;
         ff_gemm1(lds + (c % NS) * FF_W1B, r16, q, xh, xl, acc, [&](int s) {
-            if ((s & 1) == 0) ff_dma1k(src + (s >> 1) * 4096, dst + (s >> 1) * 4096);   // (past the last chunk: the last one again, into a slot nobody reads any more)
+            if ((s & 1) == 0) lds_dma1k(src + (s >> 1) * 4096, dst + (s >> 1) * 4096);   // (past the last chunk: the last one again, into a slot nobody reads any more)
             if constexpr (!FIRST) {
                 if (s == 5) store_piece(prev, c - 1, std::integral_constant<int, 1 - PAR>{}, 0);
                 if (s == 11) store_piece(prev, c - 1, std::integral_constant<int, 1 - PAR>{}, 1);

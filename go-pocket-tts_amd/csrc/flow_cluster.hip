@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
@@ -30,42 +31,22 @@ namespace ptts {
 // of one row (two 16-byte granule stores).
 // Work split inside a workgroup: see the kernel.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 fc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fc_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float fc_f32x2 __attribute__((ext_vector_type(2)));
-typedef float fc_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int FC_C = 512;                   // width of the flow net (host: flow_cluster_supported)
 constexpr int FC_RB = 2048, FC_CMASK = 127;   // LDS image: bytes and 16-byte chunks (- 1) per row (bf16 x 1024: k_skinny's NJ <= 4 image)
 constexpr unsigned FC_SPIN_LIMIT = 1u << 15;  // sweeps of a row before giving up (a pass is >= 0.5 us: >= 16 ms)
 constexpr int FC_FAULT_WORD = 32 * kFlowClusterMaxTiles;   // behind the tiles' tag-base words (32 words apart)
 
-union FcFrag {
-    fc_bf16x8 v;
-    uint4 q;
-};
-
-__device__ __forceinline__ void fc_split2(float a, float b, unsigned& hi, unsigned& lo) {   // (skinny.hip split2)
-    fc_f32x2 f = {a, b};
-    fc_bf16x2 h = __builtin_convertvector(f, fc_bf16x2);
-    fc_f32x2 r = f - __builtin_convertvector(h, fc_f32x2);
-    fc_bf16x2 l = __builtin_convertvector(r, fc_bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
 // wave `wave`'s row of the LDS image from the lane's 2 x 4 values (columns 4 lane .. and 4 (lane + 64) ..)
 __device__ __forceinline__ void fc_stage(unsigned char* Xh, unsigned char* Xl, int wave, int lane, const float4 (&xr)[2]) {
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int k = (lane + 64 * j) * 4;
-        unsigned h01, l01, h23, l23;
-        fc_split2(xr[j].x, xr[j].y, h01, l01);
-        fc_split2(xr[j].z, xr[j].w, h23, l23);
+        uint2 hi, lo;
+        split4(xr[j], hi, lo);
         const int off = wave * FC_RB + ((((k >> 3) ^ wave) & FC_CMASK) << 4) + ((k & 4) << 1);
-        *reinterpret_cast<uint2*>(&Xh[off]) = make_uint2(h01, h23);
-        *reinterpret_cast<uint2*>(&Xl[off]) = make_uint2(l01, l23);
+        *reinterpret_cast<uint2*>(&Xh[off]) = hi;
+        *reinterpret_cast<uint2*>(&Xl[off]) = lo;
     }
 }
 
@@ -77,13 +58,13 @@ __device__ __forceinline__ void fc_stage(unsigned char* Xh, unsigned char* Xl, i
 // against 35.9 without; 0.2 us between passes instead of 0.03: 35.8 against 36.0.
 template <typename RS>
 __device__ __forceinline__ bool fc_sweep(RS rs, int row_off, int lane, unsigned tag, float4 (&xr)[2]) {
-    fc_u32x4 g0 = {0u, 0u, 0u, 0u}, g1 = g0, g2 = g0, g3 = g0;
+    u32x4 g0 = {0u, 0u, 0u, 0u}, g1 = g0, g2 = g0, g3 = g0;
     bool got = true;
     const int voff = row_off + lane * 32;
     const int watch = row_off + ((lane >> 1) * 16 + 6 + 8 * (lane & 1)) * 8;   // producing wave lane >> 1 (16 columns each): its columns 6, 7 / 14, 15
     for (unsigned spins = 0;; spins++) {
         asm volatile("" ::: "memory");   // (the loads are re-issued every pass)
-        const fc_u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rs, watch, 0, 16);   // aux 16: sc1
+        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rs, watch, 0, 16);   // aux 16: sc1
         if (__all(w[1] == tag && w[3] == tag)) {
             asm volatile("" ::: "memory");
             g0 = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 16);
@@ -93,7 +74,7 @@ __device__ __forceinline__ bool fc_sweep(RS rs, int row_off, int lane, unsigned 
             const bool ok = g0[1] == tag && g0[3] == tag && g1[1] == tag && g1[3] == tag && g2[1] == tag && g2[3] == tag && g3[1] == tag && g3[3] == tag;
             if (__all(ok)) break;
         }
-        if (spins > FC_SPIN_LIMIT) { got = false; g0 = g1 = g2 = g3 = fc_u32x4{0u, 0u, 0u, 0u}; break; }
+        if (spins > FC_SPIN_LIMIT) { got = false; g0 = g1 = g2 = g3 = u32x4{0u, 0u, 0u, 0u}; break; }
         __builtin_amdgcn_s_sleep(8);   // ~0.2 us between passes: watching harder is slower (below)
     }
     xr[0] = make_float4(__uint_as_float(g0[0]), __uint_as_float(g0[2]), __uint_as_float(g1[0]), __uint_as_float(g1[2]));
@@ -103,7 +84,7 @@ __device__ __forceinline__ bool fc_sweep(RS rs, int row_off, int lane, unsigned 
 
 template <typename RS>
 __device__ __forceinline__ void fc_publish(RS rs, int voff, unsigned tag, const float (&v)[4]) {
-    const fc_u32x4 a = {__float_as_uint(v[0]), tag, __float_as_uint(v[1]), tag}, b = {__float_as_uint(v[2]), tag, __float_as_uint(v[3]), tag};
+    const u32x4 a = {__float_as_uint(v[0]), tag, __float_as_uint(v[1]), tag}, b = {__float_as_uint(v[2]), tag, __float_as_uint(v[3]), tag};
     __builtin_amdgcn_raw_buffer_store_b128(a, rs, voff, 0, 16);
     __builtin_amdgcn_raw_buffer_store_b128(b, rs, voff + 16, 0, 16);
 }
@@ -156,19 +137,19 @@ __global__ __launch_bounds__(FC_THREADS) void k_flow_cluster(FlowClusterArgs a) 
         auto product = [&](float (&acc)[4]) {
 #pragma unroll
             for (int ss = 0; ss < 4; ss++) {
-                fc_f32x4 acc_h = {0.f, 0.f, 0.f, 0.f}, acc_l = {0.f, 0.f, 0.f, 0.f};
+                f32x4 acc_h = {0.f, 0.f, 0.f, 0.f}, acc_l = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < 4; s++) {
                     // chunk c = 16 ss + 4 q + s of row i16 sits at c ^ i16 (fc_stage): the quarter is an immediate offset of the four per-s addresses
                     const int off = i16 * FC_RB + (((q * 4 + s) ^ i16) << 4) + ss * 256;
-                    FcFrag xh, xl, wv;
+                    Frag xh, xl, wv;
                     xh.q = *reinterpret_cast<const uint4*>(&Xh[off]);
                     xl.q = *reinterpret_cast<const uint4*>(&Xl[off]);
                     wv.q = w[ss * 4 + s];
                     acc_h = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv.v, xh.v, acc_h, 0, 0, 0);
                     acc_l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv.v, xl.v, acc_l, 0, 0, 0);
                 }
-                const fc_f32x4 accv = acc_h + acc_l;
+                const f32x4 accv = acc_h + acc_l;
                 if (ss == 0) { acc[0] = accv[0]; acc[1] = accv[1]; acc[2] = accv[2]; acc[3] = accv[3]; }
                 else { acc[0] += accv[0]; acc[1] += accv[1]; acc[2] += accv[2]; acc[3] += accv[3]; }
             }
@@ -251,29 +232,29 @@ __global__ __launch_bounds__(FC_THREADS) void k_flow_cluster(FlowClusterArgs a) 
                 } else if (!fc_sweep(rs, sweep_off, lane, base + 2 * r, xr)) fault = 1;
                 if (wave == 4) FC_STAMP(32 + 4 * r);
                 // LayerNorm over the row, biased variance (linear.go:295-309) -- k_skinny's prologue (PRO_LN | PRO_AFFINE | PRO_MOD)
-                fc_f32x2 s2 = {0.f, 0.f};
+                f32x2 s2 = {0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < 2; j++) s2 += fc_f32x2{xr[j].x, xr[j].z} + fc_f32x2{xr[j].y, xr[j].w};
+                for (int j = 0; j < 2; j++) s2 += f32x2{xr[j].x, xr[j].z} + f32x2{xr[j].y, xr[j].w};
                 const float rk = __builtin_amdgcn_rcpf((float)FC_C);
                 const float mean = wave_sum_dpp(s2.x + s2.y) * rk;
-                const fc_f32x2 m2 = {mean, mean};
-                fc_f32x2 v2 = {0.f, 0.f};
+                const f32x2 m2 = {mean, mean};
+                f32x2 v2 = {0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
-                    const fc_f32x2 da = fc_f32x2{xr[j].x, xr[j].y} - m2, db = fc_f32x2{xr[j].z, xr[j].w} - m2;
+                    const f32x2 da = f32x2{xr[j].x, xr[j].y} - m2, db = f32x2{xr[j].z, xr[j].w} - m2;
                     v2 += da * da + db * db;
                 }
                 const float inv_std = __builtin_amdgcn_rsqf(wave_sum_dpp(v2.x + v2.y) * rk + a.eps[r]);
-                const fc_f32x2 is2 = {inv_std, inv_std};
+                const f32x2 is2 = {inv_std, inv_std};
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     const float4 lw = j ? lw1 : lw0, lb = j ? lb1 : lb0, lc = j ? lc1 : lc0, lh = j ? lh1 : lh0;
-                    fc_f32x2 oa = (fc_f32x2{xr[j].x, xr[j].y} - m2) * is2, ob = (fc_f32x2{xr[j].z, xr[j].w} - m2) * is2;
-                    oa = oa * fc_f32x2{lw.x, lw.y} + fc_f32x2{lb.x, lb.y};
-                    ob = ob * fc_f32x2{lw.z, lw.w} + fc_f32x2{lb.z, lb.w};
-                    const fc_f32x2 one = {1.0f, 1.0f};
-                    oa = oa * (fc_f32x2{lc.x, lc.y} + one) + fc_f32x2{lh.x, lh.y};
-                    ob = ob * (fc_f32x2{lc.z, lc.w} + one) + fc_f32x2{lh.z, lh.w};
+                    f32x2 oa = (f32x2{xr[j].x, xr[j].y} - m2) * is2, ob = (f32x2{xr[j].z, xr[j].w} - m2) * is2;
+                    oa = oa * f32x2{lw.x, lw.y} + f32x2{lb.x, lb.y};
+                    ob = ob * f32x2{lw.z, lw.w} + f32x2{lb.z, lb.w};
+                    const f32x2 one = {1.0f, 1.0f};
+                    oa = oa * (f32x2{lc.x, lc.y} + one) + f32x2{lh.x, lh.y};
+                    ob = ob * (f32x2{lc.z, lc.w} + one) + f32x2{lh.z, lh.w};
                     xr[j] = make_float4(oa.x, oa.y, ob.x, ob.y);
                 }
                 fc_stage(Xh, Xl, row, lane, xr);

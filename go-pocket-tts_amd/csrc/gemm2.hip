@@ -1,7 +1,6 @@
 // gemm2.hip -- the many-row GEMM behind prefill and the Mimi decoder (every Linear / Conv1d / ConvTranspose1d of
 // mimi.go:719-789 and flow_transformer.go:749-771 at M = hundreds .. millions of rows).
-#include "kernels.h"
-#include "device_util.h"
+#include "gemm_tile.h"
 
 namespace ptts {
 
@@ -15,24 +14,6 @@ namespace ptts {
 // Tile: 128 rows x BN columns (BN = 128 / 64 / 32 picked from N) x 32-deep k tiles, 4 waves, each wave 32 rows x BN.
 // LDS rows are 32 bf16 + 8 pad (80 B): the 16-lane groups of a ds_read_b128 then start 20 dwords apart, which is
 // conflict-free.  Global loads of tile t+1 are issued before the MFMAs of tile t (register prefetch).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void split2g(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-union FragG {
-    bf16x8 v;
-    uint4 q;
-};
 
 constexpr int G2_BM = 128, G2_BK = 32, G2_LD = 40;   // LD in bf16 elements (80-byte rows)
 
@@ -45,14 +26,10 @@ __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned short Wh[BN * G2_LD];
     __shared__ __attribute__((aligned(16))) unsigned short Wl[WBF16 ? 8 : BN * G2_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD-aware tile order: blocks are dealt round-robin to the 8 XCDs (each with a private L2), so block id b runs on
-    // XCD b % 8.  All column tiles of one 128-row panel of A are given ids with the same b % 8 and consecutive b / 8:
-    // the panel is fetched from HBM once into that XCD's L2 instead of once per column tile.  (Speed only.)
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + G2_BM - 1) / G2_BM;
-    const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-    const int pan = (j / ncol) * 8 + xcd;
-    if (pan >= npan) return;
-    const int m0 = pan * G2_BM, n0 = (j % ncol) * BN;
+    const XcdTile xt = xcd_tile(blockIdx.x, ncol);
+    if (xt.pan >= npan) return;   // all column tiles of a row panel on one XCD (gemm_tile.h)
+    const int m0 = xt.pan * G2_BM, n0 = xt.coltile(ncol) * BN;
 
     // A staging: thread owns rows (tid >> 3) + 32 i, float4 column (tid & 7)
     const float* aptr[4];
@@ -113,12 +90,11 @@ __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
         __syncthreads();   // the previous tile's fragment reads are done
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            unsigned h01, l01, h23, l23;
-            split2g(ar[i].x, ar[i].y, h01, l01);
-            split2g(ar[i].z, ar[i].w, h23, l23);
+            uint2 hi, lo;
+            split4(ar[i], hi, lo);
             int off = ((tid >> 3) + 32 * i) * G2_LD + (tid & 7) * 4;
-            *reinterpret_cast<uint2*>(&Ah[off]) = make_uint2(h01, h23);
-            *reinterpret_cast<uint2*>(&Al[off]) = make_uint2(l01, l23);
+            *reinterpret_cast<uint2*>(&Ah[off]) = hi;
+            *reinterpret_cast<uint2*>(&Al[off]) = lo;
         }
 #pragma unroll
         for (int j = 0; j < WCH; j++) {
@@ -126,11 +102,10 @@ __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
             if constexpr (WBF16) {
                 *reinterpret_cast<uint4*>(&Wh[wrow[j] * G2_LD + wk[j]]) = wr[j];
             } else {
-                unsigned h01, l01, h23, l23;
-                split2g(__uint_as_float(wr[j].x), __uint_as_float(wr[j].y), h01, l01);
-                split2g(__uint_as_float(wr[j].z), __uint_as_float(wr[j].w), h23, l23);
-                *reinterpret_cast<uint2*>(&Wh[wrow[j] * G2_LD + wk[j]]) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(&Wl[wrow[j] * G2_LD + wk[j]]) = make_uint2(l01, l23);
+                uint2 hi, lo;
+                split4(as_float4(wr[j]), hi, lo);
+                *reinterpret_cast<uint2*>(&Wh[wrow[j] * G2_LD + wk[j]]) = hi;
+                *reinterpret_cast<uint2*>(&Wl[wrow[j] * G2_LD + wk[j]]) = lo;
             }
         }
         __syncthreads();
@@ -138,17 +113,17 @@ __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
         const int r = lane & 31, kh = (lane >> 5) * 8;
 #pragma unroll
         for (int ks = 0; ks < G2_BK / 16; ks++) {
-            FragG xh, xl;
+            Frag xh, xl;
             xh.q = *reinterpret_cast<const uint4*>(&Ah[(wave * 32 + r) * G2_LD + ks * 16 + kh]);
             xl.q = *reinterpret_cast<const uint4*>(&Al[(wave * 32 + r) * G2_LD + ks * 16 + kh]);
 #pragma unroll
             for (int t = 0; t < NT; t++) {
-                FragG wh;
+                Frag wh;
                 wh.q = *reinterpret_cast<const uint4*>(&Wh[(t * 32 + r) * G2_LD + ks * 16 + kh]);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh.v, wh.v, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl.v, wh.v, acc[t], 0, 0, 0);
                 if constexpr (!WBF16) {
-                    FragG wl;
+                    Frag wl;
                     wl.q = *reinterpret_cast<const uint4*>(&Wl[(t * 32 + r) * G2_LD + ks * 16 + kh]);
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh.v, wl.v, acc[t], 0, 0, 0);
                 }
@@ -156,56 +131,38 @@ __global__ __launch_bounds__(256) void k_gemm2(GemmArgs a) {
         }
     }
 
-    // epilogue: lane holds C[row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)][col = lane&31] of each 32x32 tile.
+    // epilogue (gemm_tile.h): lane holds C[row = acc32_row(reg, lane)][col = lane&31] of each 32x32 tile.
     // The 16 row addresses are computed once (one divide each) and reused by every column tile.
     int64_t rowoff[16];
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
-        int m = m0 + wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        int m = m0 + wave * 32 + acc32_row(reg, lane);
         rowoff[reg] = m < a.M ? row_off(a.cmap, m) : -1;
     }
 #pragma unroll
     for (int t = 0; t < NT; t++) {
         const int n = n0 + t * 32 + (lane & 31);
         if (n >= a.N) continue;
-        const float bias = a.bias ? a.bias[n] : 0.0f;
-        const float addv = a.addvec ? a.addvec[n] : 0.0f;
-        const float scl = a.scale ? a.scale[n] : 1.0f;
+        const EpiCol ec = epi_col(a, n);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             if (rowoff[reg] < 0) continue;
-            float v = acc[t][reg] + bias;
+            const float v = acc[t][reg] + ec.bias;
             const int64_t co = rowoff[reg] + n;
-            switch (a.epi) {
-                case EPI_NONE: break;
-                case EPI_GELU: v = gelu1(v); break;
-                case EPI_SILU: v = silu1(addv + v); break;
-                case EPI_ELU: v = elu1(v); break;
-                case EPI_RESADD: v = a.R[co] + v; break;
-                case EPI_SCALE_RESADD: v = a.R[co] + scl * v; break;
-                case EPI_GATE_RESADD: {
-                    int m = m0 + wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                    v = a.R[co] + a.gate[(int64_t)m * a.ldg + n] * v;
-                    break;
-                }
-                case EPI_AXPY: v = a.R[co] + a.alpha * v; break;
-                case EPI_RESADD_ELU: v = elu1(a.R[co] + v); break;
-            }
-            a.C[co] = v;
+            a.C[co] = epi_scalar(a, ec, v, n, co, [&] { return m0 + wave * 32 + acc32_row(reg, lane); });
         }
     }
 }
 
 bool gemm2_supported(const GemmArgs& a) {
     const int kalign = a.w_bf16 ? 8 : 4;
-    return a.M >= 96 && a.K % kalign == 0 && aligned16(a.A) && a.amap.ld % 4 == 0 && a.amap.batch_stride % 4 == 0 &&
-           a.ldw % kalign == 0 && aligned16(a.W);
+    return a.M >= 96 && a.K % kalign == 0 && gemm_operands_aligned(a, kalign, false);
 }
 
 template <int BN>
 static void launch_bn(const GemmArgs& a, hipStream_t stream) {
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + G2_BM - 1) / G2_BM;
-    dim3 grid((unsigned)(((npan + 7) / 8) * 8 * ncol));
+    dim3 grid(xcd_grid(npan, ncol));
     if (a.w_bf16) hipLaunchKernelGGL((k_gemm2<BN, true>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((k_gemm2<BN, false>), grid, dim3(256), 0, stream, a);
 }

@@ -1,7 +1,6 @@
 // gemm3.hip -- the many-row GEMM of the Mimi decoder and of prefill, second generation (every Linear / Conv1d /
 // ConvTranspose1d of mimi.go:719-789 and flow_transformer.go:749-771 at M = thousands .. millions of rows).
-#include "kernels.h"
-#include "device_util.h"
+#include "gemm_tile.h"
 
 namespace ptts {
 
@@ -19,24 +18,6 @@ namespace ptts {
 //    columns of one row, so bias / residual / store are 16-byte accesses.
 // Block = 8 waves x 32 rows = 256 rows x BN columns (BN = 128 / 64 / 32 by N); per 32 k a wave issues 4 global loads,
 // BN/16 LDS reads and BN/4 (bf16 weights) MFMAs.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split2h(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-union Frag3 {
-    bf16x8 v;
-    uint4 q;
-};
 
 thread_local int g_gemm3_cfg = 0;   // debug knob (ptts_debug_gemm): 0 = default shape
 
@@ -53,12 +34,10 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
     __shared__ __attribute__((aligned(16))) char Ws[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
-    // XCD-aware order (speed only): all column tiles of a 256-row panel run on the XCD that already holds the panel in L2
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + G3_BM - 1) / G3_BM;
-    const int bid = blockIdx.x, xcd = bid & 7, jb = bid >> 3;
-    const int pan = (jb / ncol) * 8 + xcd;
-    if (pan >= npan) return;
-    const int m0 = pan * G3_BM + wave * 32, n0 = (jb % ncol) * BN;
+    const XcdTile xt = xcd_tile(blockIdx.x, ncol);
+    if (xt.pan >= npan) return;   // all column tiles of a row panel on one XCD (gemm_tile.h)
+    const int m0 = xt.pan * G3_BM + wave * 32, n0 = xt.coltile(ncol) * BN;
     // split-K (a.kslice > 0): blockIdx.y owns k in [kz, kz + KL) and writes its raw sums to plane blockIdx.y of C
     const int kz = blockIdx.y * a.kslice;
     const int KL = a.kslice ? min(a.kslice, a.K - kz) : a.K;
@@ -91,12 +70,11 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
             if constexpr (WBF16) {   // 8 k at kk*8: sub-chunk kk>>2, 16-byte slot kk&3
                 *reinterpret_cast<uint4*>(base + (kk >> 2) * HALF + n * 64 + (kk & 3) * 16) = wreg[p];
             } else {                 // 4 k at kk*4: sub-chunk kk>>3, 8-byte slot kk&7
-                unsigned h01, l01, h23, l23;
-                split2h(__uint_as_float(wreg[p].x), __uint_as_float(wreg[p].y), h01, l01);
-                split2h(__uint_as_float(wreg[p].z), __uint_as_float(wreg[p].w), h23, l23);
+                uint2 hi, lo;
+                split4(as_float4(wreg[p]), hi, lo);
                 const int off = (kk >> 3) * HALF + n * 64 + (kk & 7) * 8;
-                *reinterpret_cast<uint2*>(base + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(base + PLANE + off) = make_uint2(l01, l23);
+                *reinterpret_cast<uint2*>(base + off) = hi;
+                *reinterpret_cast<uint2*>(base + PLANE + off) = lo;
             }
         }
     };
@@ -111,13 +89,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
     // activations: a ring of SPC 32-k steps per wave.  The slot of step i is refilled with step i + SPC as soon as step i
     // has been split into fragments, so every wave keeps SPC steps (CH k of its 32 rows) in flight at all times.
     float4 av[SPC][2][2];
-    auto a_load = [&](int i, float4 (&dst)[2][2]) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            dst[t][0] = *reinterpret_cast<const float4*>(aptr[t] + i * 32);
-            dst[t][1] = *reinterpret_cast<const float4*>(aptr[t] + i * 32 + 4);
-        }
-    };
+    auto a_load = [&](int i, float4 (&dst)[2][2]) { a_step_load(aptr, i * 32, dst); };
     w_load(0);
 #pragma unroll
     for (int s = 0; s < SPC; s++)
@@ -130,24 +102,18 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
         for (int s = 0; s < SPC; s++) {
             const int i = c * SPC + s;
             if (i < nsteps) {
-                Frag3 ah[2], al[2];
+                Frag ah[2], al[2];
 #pragma unroll
                 for (int t = 0; t < 2; t++) {
                     float4 x0 = av[s][t][0], x1 = av[s][t][1];
-                    if (a.aop == AOP_ELU) {
-                        x0.x = elu_fast(x0.x); x0.y = elu_fast(x0.y); x0.z = elu_fast(x0.z); x0.w = elu_fast(x0.w);
-                        x1.x = elu_fast(x1.x); x1.y = elu_fast(x1.y); x1.z = elu_fast(x1.z); x1.w = elu_fast(x1.w);
-                    }
-                    split2h(x0.x, x0.y, ah[t].q.x, al[t].q.x);
-                    split2h(x0.z, x0.w, ah[t].q.y, al[t].q.y);
-                    split2h(x1.x, x1.y, ah[t].q.z, al[t].q.z);
-                    split2h(x1.z, x1.w, ah[t].q.w, al[t].q.w);
+                    if (a.aop == AOP_ELU) { elu_fast4(x0); elu_fast4(x1); }
+                    split8(x0, x1, ah[t], al[t]);
                 }
                 if (i + SPC < nsteps) a_load(i + SPC, av[s]);
                 const char* wb = Ws + (c & 1) * STAGE + s * HALF + r16 * 64 + g * 16;
 #pragma unroll
                 for (int n = 0; n < NT; n++) {
-                    Frag3 wh;
+                    Frag wh;
                     wh.q = *reinterpret_cast<const uint4*>(wb + n * 1024);
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
@@ -155,7 +121,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
                         acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, al[t].v, acc[t][n], 0, 0, 0);
                     }
                     if constexpr (!WBF16) {
-                        Frag3 wl;
+                        Frag wl;
                         wl.q = *reinterpret_cast<const uint4*>(wb + PLANE + n * 1024);
 #pragma unroll
                         for (int t = 0; t < 2; t++) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl.v, ah[t].v, acc[t][n], 0, 0, 0);
@@ -236,8 +202,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm3(GemmArgs a) {
 bool gemm3_supported(const GemmArgs& a) {
     const int kalign = a.w_bf16 ? 8 : 4;
     const bool res = a.epi >= EPI_RESADD;
-    return a.M >= 512 && a.K % 32 == 0 && a.N % 4 == 0 && aligned16(a.A) && a.amap.ld % 4 == 0 && a.amap.batch_stride % 4 == 0 &&
-           a.ldw % kalign == 0 && aligned16(a.W) && aligned16(a.C) && a.cmap.ld % 4 == 0 && a.cmap.batch_stride % 4 == 0 &&
+    return a.M >= 512 && a.K % 32 == 0 && a.N % 4 == 0 && gemm_operands_aligned(a, kalign, true) &&
            (!a.bias || aligned16(a.bias)) && (!a.addvec || aligned16(a.addvec)) && (!a.scale || aligned16(a.scale)) &&
            (!res || aligned16(a.R)) && (a.epi != EPI_GATE_RESADD || (aligned16(a.gate) && a.ldg % 4 == 0)) &&
            (!a.rope_cos || (a.rope_hd % 4 == 0 && a.rope_cols % 4 == 0 && a.epi == EPI_NONE)) &&
@@ -247,7 +212,7 @@ bool gemm3_supported(const GemmArgs& a) {
 template <int BN, int NW, int CH>
 static void launch3_cfg(const GemmArgs& a, hipStream_t stream) {
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + NW * 32 - 1) / (NW * 32);
-    dim3 grid((unsigned)(((npan + 7) / 8) * 8 * ncol), (unsigned)(a.kslice ? (a.K + a.kslice - 1) / a.kslice : 1));
+    dim3 grid(xcd_grid(npan, ncol), (unsigned)(a.kslice ? (a.K + a.kslice - 1) / a.kslice : 1));
     if (a.w_bf16) hipLaunchKernelGGL((k_gemm3<BN, true, NW, CH>), grid, dim3(NW * 64), 0, stream, a);
     else hipLaunchKernelGGL((k_gemm3<BN, false, NW, CH>), grid, dim3(NW * 64), 0, stream, a);
 }

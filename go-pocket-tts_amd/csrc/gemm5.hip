@@ -17,37 +17,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
-#include "device_util.h"
+#include "gemm_tile.h"
 
 namespace ptts {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // (a uint4 copied out of global memory is a struct memcpy the optimiser leaves in scratch)
-
-union Frag5 {
-    bf16x8 v;
-    uint4 q;
-};
-
-__device__ __forceinline__ void split5(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-// A weight column's 32 k (64 bytes = four 16-byte chunks) are stored with chunk c at c ^ fw(column).  A ds_read_b128 is served
-// in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: each group holds every fragment column once,
-// columns 4..11 with the neighbouring k group; with this XOR its 16 lanes hit 16 different 16-byte bank slots.
-__device__ __forceinline__ int fw5(int col) { return ((col >> 3) & 1) * 3; }
 
 template <int V> using ic = std::integral_constant<int, V>;
 
@@ -68,12 +42,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     __shared__ __attribute__((aligned(16))) char Ws[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
-    // XCD-aware order (speed only): all column tiles of a row panel run on the XCD that already holds the panel in L2
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + BM - 1) / BM;
-    const int bid = blockIdx.x, xcd = bid & 7, jb = bid >> 3;
-    const int pan = (jb / ncol) * 8 + xcd;
-    if (pan >= npan) return;
-    const int m0 = pan * BM + wave * 32, n0 = (jb % ncol) * BN;
+    const XcdTile xt = xcd_tile(blockIdx.x, ncol);
+    if (xt.pan >= npan) return;   // all column tiles of a row panel on one XCD (gemm_tile.h)
+    const int m0 = xt.pan * BM + wave * 32, n0 = xt.coltile(ncol) * BN;
 
     // split-K (a.kslice > 0, the prompt prefill's linear2): blockIdx.y owns k in [kz, kz + KL) and writes its raw sums to plane blockIdx.y of C
     const int kz = blockIdx.y * a.kslice;
@@ -86,7 +58,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int wn = tid / PPR, wk = tid % PPR;                            // 8 k at wk*8: sub-chunk wk>>2, chunk wk&3
     const char* wsrc = (const char*)a.W + ((int64_t)(n0 + wn) * a.ldw + kz + wk * 8) * 2;
     const int64_t wstep = (int64_t)CPP * a.ldw * 2;
-    const int wdst = (wk >> 2) * HALF + wn * 64 + (((wk & 3) ^ fw5(wn)) << 4);   // CPP % 16 == 0: the swizzle of column wn + CPP p is wn's
+    const int wdst = (wk >> 2) * HALF + wn * 64 + (((wk & 3) ^ frag_swz(wn)) << 4);   // CPP % 16 == 0: the swizzle of column wn + CPP p is wn's
     static_assert(CPP % 16 == 0, "");
     u32x4 wreg[PPT];
     // k offset of the c-th 64-deep chunk.  A causal convolution as a product reads, for output row r, the window rows r-taps+1 .. r (K = taps x C,
@@ -114,47 +86,34 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
     const int nchunks = KL / CH, nsteps = nchunks * SPC;       // K (and a K slice) % CH == 0 (host)
     float4 av[SPC][2][2];
-    auto a_load = [&](int i, float4 (&dst)[2][2]) {
-        const int ko = koff(i / SPC) + (i % SPC) * 32;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            dst[t][0] = *reinterpret_cast<const float4*>(aptr[t] + ko);
-            dst[t][1] = *reinterpret_cast<const float4*>(aptr[t] + ko + 4);
-        }
-    };
+    auto a_load = [&](int i, float4 (&dst)[2][2]) { a_step_load(aptr, koff(i / SPC) + (i % SPC) * 32, dst); };
     w_load(0);
 #pragma unroll
     for (int s = 0; s < SPC; s++) a_load(min(s, nsteps - 1), av[s]);
     w_store(0);
     __syncthreads();
-    const int frag_off = r16 * 64 + ((g ^ fw5(r16)) << 4);
+    const int frag_off = r16 * 64 + ((g ^ frag_swz(r16)) << 4);
     for (int c = 0; c < nchunks; c++) {
         w_load(min(c + 1, nchunks - 1));                       // the last chunk is fetched (and staged) once more: no branch, nobody reads it
 #pragma unroll
         for (int s = 0; s < SPC; s++) {
             const int i = c * SPC + s;
-            Frag5 ah[2], al[2];
+            Frag ah[2], al[2];
 #pragma unroll
             for (int t = 0; t < 2; t++) {
                 float4 x0 = av[s][t][0], x1 = av[s][t][1];
-                if constexpr (ELU_A) {
-                    x0.x = elu_fast(x0.x); x0.y = elu_fast(x0.y); x0.z = elu_fast(x0.z); x0.w = elu_fast(x0.w);
-                    x1.x = elu_fast(x1.x); x1.y = elu_fast(x1.y); x1.z = elu_fast(x1.z); x1.w = elu_fast(x1.w);
-                }
+                if constexpr (ELU_A) { elu_fast4(x0); elu_fast4(x1); }
                 if constexpr (ABL & 4) {
                     ah[t].q = make_uint4(__float_as_uint(x0.x), __float_as_uint(x0.y), __float_as_uint(x0.z), __float_as_uint(x0.w));
                     al[t].q = make_uint4(__float_as_uint(x1.x), __float_as_uint(x1.y), __float_as_uint(x1.z), __float_as_uint(x1.w));
                 } else {
-                    split5(x0.x, x0.y, ah[t].q.x, al[t].q.x);
-                    split5(x0.z, x0.w, ah[t].q.y, al[t].q.y);
-                    split5(x1.x, x1.y, ah[t].q.z, al[t].q.z);
-                    split5(x1.z, x1.w, ah[t].q.w, al[t].q.w);
+                    split8(x0, x1, ah[t], al[t]);
                 }
             }
             if constexpr (!(ABL & 1)) a_load(min(i + SPC, nsteps - 1), av[s]);
             __builtin_amdgcn_sched_barrier(0);                    // the loads stay in front of the products they run under
             const char* wb = Ws + (c & 1) * STAGE + s * HALF + frag_off;
-            Frag5 wh[2];                                            // fragment n + 1 is requested before fragment n is multiplied
+            Frag wh[2];                                            // fragment n + 1 is requested before fragment n is multiplied
             wh[0].q = *reinterpret_cast<const uint4*>(wb);
             if constexpr (!(ABL & 18)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
@@ -162,7 +121,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if constexpr (!(ABL & 2)) {
                     if (n + 1 < NT) wh[(n + 1) & 1].q = *reinterpret_cast<const uint4*>(wb + (n + 1) * 1024);
                 }
-                const Frag5& w = (ABL & 2) ? wh[0] : wh[n & 1];
+                const Frag& w = (ABL & 2) ? wh[0] : wh[n & 1];
                 if constexpr (!(ABL & 16)) {
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
@@ -284,15 +243,15 @@ bool gemm5_supported(const GemmArgs& a) {
     constexpr int min_m = 1024;
     return a.w_bf16 && epi_ok && a.M >= min_m && a.K % 64 == 0 && a.K >= 64 && a.N % 128 == 0 && !a.tail &&
            (!a.kslice || (a.kslice % 64 == 0 && a.K % a.kslice == 0 && a.epi == EPI_NONE && !a.bias && !a.rope_cos && a.zstride % 4 == 0)) &&
-           aligned16(a.A) && a.amap.ld % 4 == 0 && a.amap.batch_stride % 4 == 0 && a.ldw % 8 == 0 && aligned16(a.W) && (int64_t)a.N * a.ldw * 2 >= (int64_t)a.N * 4 &&
-           aligned16(a.C) && a.cmap.ld % 4 == 0 && a.cmap.batch_stride % 4 == 0 && (!a.bias || aligned16(a.bias)) && (!a.scale || aligned16(a.scale)) &&
+           gemm_operands_aligned(a, 8, false) && (int64_t)a.N * a.ldw * 2 >= (int64_t)a.N * 4 && gemm_c_aligned(a) &&   // (the parent's order of these tests)
+           (!a.bias || aligned16(a.bias)) && (!a.scale || aligned16(a.scale)) &&
            (!res || aligned16(a.R)) && (!a.rope_cos || (a.rope_hd == 64 && a.rope_cols % 64 == 0 && a.epi == EPI_NONE));
 }
 
 template <int BN, int NW, int ABL = 0>
 static void launch5_cfg(const GemmArgs& a, hipStream_t stream) {
     const int ncol = (a.N + BN - 1) / BN, npan = (a.M + NW * 32 - 1) / (NW * 32);
-    dim3 grid((unsigned)(((npan + 7) / 8) * 8 * ncol), (unsigned)(a.kslice ? a.K / a.kslice : 1));
+    dim3 grid(xcd_grid(npan, ncol), (unsigned)(a.kslice ? a.K / a.kslice : 1));
     if (a.aop == AOP_ELU) hipLaunchKernelGGL((k_gemm5<BN, NW, true, ABL>), grid, dim3(NW * 64), 0, stream, a);
     else hipLaunchKernelGGL((k_gemm5<BN, NW, false, ABL>), grid, dim3(NW * 64), 0, stream, a);
 }

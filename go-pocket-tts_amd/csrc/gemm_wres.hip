@@ -4,8 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "kernels.h"
-#include "device_util.h"
+#include "gemm_tile.h"
 
 namespace ptts {
 
@@ -20,28 +19,6 @@ namespace ptts {
 // 32-row panels (panel = (block, wave) + j * blocks * 8), keeps a ring of four 32-k steps of its rows in flight ACROSS panel
 // boundaries (the rows are the only thing it ever fetches), multiplies against the resident fragments and stores its 32 x N
 // results.  A wave that waits for memory leaves the matrix core to the other wave of its SIMD.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split2w(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-// chunk c (of the four 16-byte chunks of a column's 32 k) is stored at c ^ fw(column): with it the 16 lanes of each group a
-// ds_read_b128 is served in hit 16 different bank slots (gemm5.hip has the derivation; the plain layout was a 2-way conflict)
-__device__ __forceinline__ int wres_fw(int col) { return ((col >> 3) & 1) * 3; }
-
-union FragW {
-    bf16x8 v;
-    uint4 q;
-};
 
 constexpr int WR_RING = 4, WR_NW = 8;
 
@@ -66,7 +43,7 @@ __global__ __launch_bounds__(WR_NW * 64) void k_gemm_wres(GemmArgs a, int ntiles
             const int n = pc / PPR, kk = pc % PPR;
             uint4 u = make_uint4(0, 0, 0, 0);
             if (n0 + n < a.N && kk * 8 < a.K) u = *reinterpret_cast<const uint4*>((const char*)a.W + ((int64_t)(n0 + n) * a.ldw + kk * 8) * 2);
-            *reinterpret_cast<uint4*>(Wl + (kk >> 2) * (WR_N * 64) + n * 64 + (((kk & 3) ^ wres_fw(n)) << 4)) = u;
+            *reinterpret_cast<uint4*>(Wl + (kk >> 2) * (WR_N * 64) + n * 64 + (((kk & 3) ^ frag_swz(n)) << 4)) = u;
         }
     }
     if (tid < WR_N) Bl[tid] = (a.bias && n0 + tid < a.N) ? a.bias[n0 + tid] : 0.0f;
@@ -92,11 +69,7 @@ __global__ __launch_bounds__(WR_NW * 64) void k_gemm_wres(GemmArgs a, int ntiles
     };
     l_rows();
     auto a_load = [&](float4 (&dst)[2][2]) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            dst[t][0] = *reinterpret_cast<const float4*>(lrow[t] + li * 32);
-            dst[t][1] = *reinterpret_cast<const float4*>(lrow[t] + li * 32 + 4);
-        }
+        a_step_load(lrow, li * 32, dst);
         if (++li == nsteps) { li = 0; lp = min(lp + 1, mine - 1); l_rows(); }   // (past the last panel: its rows again, never used)
     };
 #pragma unroll
@@ -114,19 +87,13 @@ __global__ __launch_bounds__(WR_NW * 64) void k_gemm_wres(GemmArgs a, int ntiles
         for (int r = 0; r < WR_RING; r++) {
             const int q = q0 + r;
             if (q < total) {                          // wave-uniform
-                FragW ah[2], al[2];
+                Frag ah[2], al[2];
 #pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const float4 x0 = av[r][t][0], x1 = av[r][t][1];
-                    split2w(x0.x, x0.y, ah[t].q.x, al[t].q.x);
-                    split2w(x0.z, x0.w, ah[t].q.y, al[t].q.y);
-                    split2w(x1.x, x1.y, ah[t].q.z, al[t].q.z);
-                    split2w(x1.z, x1.w, ah[t].q.w, al[t].q.w);
-                }
+                for (int t = 0; t < 2; t++) split8(av[r][t][0], av[r][t][1], ah[t], al[t]);
                 a_load(av[r]);                            // unconditional (no load behind a branch: the compiler would drain the ring there)
                 __builtin_amdgcn_sched_barrier(0);
-                const unsigned char* wb = Wl + step * (WR_N * 64) + r16 * 64 + ((g ^ wres_fw(r16)) << 4);
-                FragW wh[2];                              // fragment n + 1 is requested before fragment n is multiplied
+                const unsigned char* wb = Wl + step * (WR_N * 64) + r16 * 64 + ((g ^ frag_swz(r16)) << 4);
+                Frag wh[2];                              // fragment n + 1 is requested before fragment n is multiplied (k_gemm5's sweep)
                 wh[0].q = *reinterpret_cast<const uint4*>(wb);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
@@ -170,8 +137,7 @@ __global__ __launch_bounds__(WR_NW * 64) void k_gemm_wres(GemmArgs a, int ntiles
 
 static bool wres_common(const GemmArgs& a) {
     return a.w_bf16 && a.K % 32 == 0 && a.N % 4 == 0 && a.M >= 2048 && a.aop == AOP_NONE && (a.epi == EPI_NONE || a.epi == EPI_ELU || a.epi == EPI_GELU) &&
-           !a.rope_cos && !a.kslice && !a.tail && aligned16(a.A) && a.amap.ld % 4 == 0 && a.amap.batch_stride % 4 == 0 && a.ldw % 8 == 0 &&
-           aligned16(a.W) && aligned16(a.C) && a.cmap.ld % 4 == 0 && a.cmap.batch_stride % 4 == 0;
+           !a.rope_cos && !a.kslice && !a.tail && gemm_operands_aligned(a, 8, true);
 }
 static int wres_shape(const GemmArgs& a) {   // 1: 256 x 256 tile, 2: 128 columns x 512 k, 0: not this kernel's
     if (!wres_common(a)) return 0;

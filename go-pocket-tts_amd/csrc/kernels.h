@@ -74,6 +74,8 @@ void launch_gemm_wres(const GemmArgs& a, hipStream_t stream);   // = launch_gemm
 int gemm_wres_max_rgl(const GemmArgs& a);   // CUs / 8 (256 x 256), CUs / 8 / column tiles (128 x 512)
 int gemm_wres_rgl(const GemmArgs& a);
 void launch_gemm_wres_as(const GemmArgs& a, int rgl, hipStream_t stream);
+// The generations below share their tile steps (XCD tile order, fragment swizzle, activation step, scalar epilogue, operand alignment) through gemm_tile.h,
+// and with every other matrix-core kernel the bf16 hi + lo operand split, the fragment union and the LDS-DMA instruction through mfma_util.h.
 bool gemm2_supported(const GemmArgs& a);
 void launch_gemm2(const GemmArgs& a, hipStream_t stream);
 bool gemm3_supported(const GemmArgs& a);   // direct-to-register activations, 256-row blocks (gemm3.hip)

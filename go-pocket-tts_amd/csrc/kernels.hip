@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "kernels.h"
 #include "device_util.h"
+#include "gemm_tile.h"
 #include "step_open.h"
 
 namespace ptts {
@@ -22,7 +23,6 @@ namespace ptts {
 // k = 8*g + 4*kq + j), which lets each lane fetch its four values per operand with one ds_read_b128.
 // ------------------------------------------------------------------------------------------------
 constexpr int GM = 64, GN = 64, GK = 32, GLD = GK + 4;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <bool WBF16>
 __global__ __launch_bounds__(256) void k_gemm(GemmArgs a, int a_vec, int w_vec) {
@@ -116,30 +116,17 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs a, int a_vec, int w_vec) 
         }
     }
 
-    // epilogue: lane holds C[row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)][col = lane&31] of its 32x32 tile
+    // epilogue (gemm_tile.h): lane holds C[row = acc32_row(reg, lane)][col = lane&31] of its 32x32 tile
     const int n = n0 + wn * 32 + (lane & 31);
     if (n >= a.N) return;
-    const float bias = a.bias ? a.bias[n] : 0.0f;
-    const float addv = a.addvec ? a.addvec[n] : 0.0f;
-    const float scl = a.scale ? a.scale[n] : 1.0f;
+    const EpiCol ec = epi_col(a, n);
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
-        int m = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        int m = m0 + wm * 32 + acc32_row(reg, lane);
         if (m >= a.M) continue;
-        float v = acc[reg] + bias;
+        float v = acc[reg] + ec.bias;
         int64_t co = row_off(a.cmap, m) + n;
-        switch (a.epi) {
-            case EPI_NONE: break;
-            case EPI_GELU: v = gelu1(v); break;
-            case EPI_SILU: v = silu1(addv + v); break;
-            case EPI_ELU: v = elu1(v); break;
-            case EPI_RESADD: v = a.R[co] + v; break;
-            case EPI_SCALE_RESADD: v = a.R[co] + scl * v; break;
-            case EPI_GATE_RESADD: v = a.R[co] + a.gate[(int64_t)m * a.ldg + n] * v; break;
-            case EPI_AXPY: v = a.R[co] + a.alpha * v; break;
-            case EPI_RESADD_ELU: v = elu1(a.R[co] + v); break;
-        }
-        a.C[co] = v;
+        a.C[co] = epi_scalar(a, ec, v, n, co, [&] { return m; });
     }
 }
 
@@ -818,7 +805,6 @@ void launch_conv_final(const float* in, int in_pad_rows, const float* w, const f
     size_t lds = ((size_t)(256 + k - 1) * (c + 1) + (size_t)k * c) * sizeof(float);
     hipLaunchKernelGGL(k_conv_final, dim3((unsigned)(b * tiles)), dim3(256), lds, stream, in, in_pad_rows, w, bias, b, t, t0, t1, c, k, elu_in, out);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // PCM egress: audio.WritePCM16Samples on the device -- halves the bytes that cross PCIe

@@ -5,6 +5,7 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
@@ -22,24 +23,6 @@ namespace ptts {
 // L2-resident; products are computed transposed (weights as the MFMA row operand) so a lane ends up with four
 // consecutive channels of one row.  Numerics are those of k_gemm3 (activations hi + lo, f32 weights hi + lo,
 // f32 accumulation).  The first HALO rows of a tile only feed later rows and are recomputed by the neighbouring tile.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split2r(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-union FragR {
-    bf16x8 v;
-    uint4 q;
-};
 
 // PERS (bf16 weights): a block stays on its CU and walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Every weight
 // fragment of the three products is copied into LDS once per block, so that the ONLY global fetches of a tile are its rows --
@@ -133,8 +116,8 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
             const int c = j * 16 + 4 * g;
             const int rho = i_own + 2;
             unsigned h01, l01, h23, l23;
-            split2r(elu_fast(x[j].x), elu_fast(x[j].y), h01, l01);
-            split2r(elu_fast(x[j].z), elu_fast(x[j].w), h23, l23);
+            split2(elu_fast(x[j].x), elu_fast(x[j].y), h01, l01);
+            split2(elu_fast(x[j].z), elu_fast(x[j].w), h23, l23);
             const int off = rho * ROWB + ((((c >> 3) ^ rho) & CM) << 4) + ((c & 4) << 1);
             *reinterpret_cast<uint2*>(eu_hi + off) = make_uint2(h01, h23);
             *reinterpret_cast<uint2*>(eu_lo + off) = make_uint2(l01, l23);
@@ -162,17 +145,17 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
             const int tap = (s * 32) / C, c0 = (s * 32) % C;
             const int rho = i_lane + tap;             // window row i-2+tap, stored at rho = that + 2
             const int off = rho * ROWB + ((((c0 >> 3) + g) ^ rho) & CM) * 16;
-            FragR xh, xl;
+            Frag xh, xl;
             xh.q = *reinterpret_cast<const uint4*>(eu_hi + off);
             xl.q = *reinterpret_cast<const uint4*>(eu_lo + off);
 #pragma unroll
             for (int n = 0; n < NT; n++) {
-                FragR wh;
+                Frag wh;
                 wh.q = w1[(n * KS + s) * 64];
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xh.v, acc[n], 0, 0, 0);
                 PTTS_LO_MFMA(acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xl.v, acc[n], 0, 0, 0));
                 if constexpr (!WBF16) {
-                    FragR wl;
+                    Frag wl;
                     wl.q = w1l[(n * KS + s) * 64];
                     acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl.v, xh.v, acc[n], 0, 0, 0);
                 }
@@ -183,8 +166,8 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
             const int ch = n * 16 + 4 * g;
             const float4 b = PERS ? *reinterpret_cast<const float4*>(bl1 + ch) : (a.b1 ? *reinterpret_cast<const float4*>(a.b1 + ch) : make_float4(0.f, 0.f, 0.f, 0.f));
             unsigned h01, l01, h23, l23;
-            split2r(elu_fast(acc[n][0] + b.x), elu_fast(acc[n][1] + b.y), h01, l01);
-            split2r(elu_fast(acc[n][2] + b.z), elu_fast(acc[n][3] + b.w), h23, l23);
+            split2(elu_fast(acc[n][0] + b.x), elu_fast(acc[n][1] + b.y), h01, l01);
+            split2(elu_fast(acc[n][2] + b.z), elu_fast(acc[n][3] + b.w), h23, l23);
             const int off = i_lane * HROWB + ((((ch >> 3) ^ i_lane) & HM) << 4) + ((ch & 4) << 1);
             *reinterpret_cast<uint2*>(h_hi + off) = make_uint2(h01, h23);
             *reinterpret_cast<uint2*>(h_lo + off) = make_uint2(l01, l23);
@@ -204,17 +187,17 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
 #pragma unroll
         for (int s = 0; s < KS; s++) {
             const int off = i_lane * HROWB + (((s * 4 + g) ^ i_lane) & HM) * 16;
-            FragR xh, xl;
+            Frag xh, xl;
             xh.q = *reinterpret_cast<const uint4*>(h_hi + off);
             xl.q = *reinterpret_cast<const uint4*>(h_lo + off);
 #pragma unroll
             for (int n = 0; n < NT; n++) {
-                FragR wh;
+                Frag wh;
                 wh.q = w2[(n * KS + s) * 64];
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xh.v, acc[n], 0, 0, 0);
                 PTTS_LO_MFMA(acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xl.v, acc[n], 0, 0, 0));
                 if constexpr (!WBF16) {
-                    FragR wl;
+                    Frag wl;
                     wl.q = w2l[(n * KS + s) * 64];
                     acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl.v, xh.v, acc[n], 0, 0, 0);
                 }
@@ -232,12 +215,11 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
             if constexpr (FINAL) {                    // the sum replaces elu(u) in the planes (dead since stage B's barrier);
                 if (!in_seq) v = make_float4(0.f, 0.f, 0.f, 0.f);   // rows before the utterance are the final conv's zero padding
                 const int rho = i_lane + 2;
-                unsigned h01, l01, h23, l23;
-                split2r(v.x, v.y, h01, l01);
-                split2r(v.z, v.w, h23, l23);
+                uint2 hi, lo;
+                split4(v, hi, lo);
                 const int off = rho * ROWB + ((((ch >> 3) ^ rho) & CM) << 4) + ((ch & 4) << 1);
-                *reinterpret_cast<uint2*>(eu_hi + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(eu_lo + off) = make_uint2(l01, l23);
+                *reinterpret_cast<uint2*>(eu_hi + off) = hi;
+                *reinterpret_cast<uint2*>(eu_lo + off) = lo;
             } else if (store) {
                 *reinterpret_cast<float4*>(orow + ch) = v;
             }
@@ -256,7 +238,7 @@ __global__ __launch_bounds__(NW * 64) void k_resblock(ResArgs a) {
             const int tap = (s * 32) / C, c0 = (s * 32) % C;
             const int rho = i_lane + tap;
             const int off = rho * ROWB + ((((c0 >> 3) + g) ^ rho) & CM) * 16;
-            FragR xh, xl, wh, wl;
+            Frag xh, xl, wh, wl;
             xh.q = *reinterpret_cast<const uint4*>(eu_hi + off);
             xl.q = *reinterpret_cast<const uint4*>(eu_lo + off);
             wh.q = wfh[s * 64];

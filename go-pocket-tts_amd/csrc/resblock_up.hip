@@ -21,31 +21,11 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split2u(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-union FragU {
-    bf16x8 v;
-    uint4 q;
-    u32x4 w;
-};
 
 // f32 u tile [128 rows][64 channels]: 16-byte chunk k of row i sits at chunk k ^ usw(i).  Stage 0 writes rows 4 r + phase (r = lane & 15),
 // stage C reads rows 16 wave + r: with this XOR both hit 16 different chunks per lane group.
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
     int tile = blockIdx.x;
     request_rows(tile);
     // this wave's share of the transposed convolution's weights: column tiles 2 wave, 2 wave + 1, all eight k steps, for good
-    FragU wu[2][8];
+    Frag wu[2][8];
 #pragma unroll
     for (int ct = 0; ct < 2; ct++)
 #pragma unroll
@@ -141,12 +121,11 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 const int r = e / (CI / 4), c = (e % (CI / 4)) * 4;
                 float4 v = x[j];
                 if (tin + r >= a.x_L) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                unsigned h01, l01, h23, l23;
-                split2u(v.x, v.y, h01, l01);
-                split2u(v.z, v.w, h23, l23);
+                uint2 hi, lo;
+                split4(v, hi, lo);
                 const int off = r * XROWB + c * 2;
-                *reinterpret_cast<uint2*>(x_hi + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(x_lo + off) = make_uint2(l01, l23);
+                *reinterpret_cast<uint2*>(x_hi + off) = hi;
+                *reinterpret_cast<uint2*>(x_lo + off) = lo;
             }
         }
         if (tid < 2 * ROWB / 16) {                    // the two rows in front of the tile only feed halo rows: zeros
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 for (int rt = 0; rt < 2; rt++) {
                     const int rho = rt * 16 + r16 + jr;
                     const int off = rho * XROWB + ((c0 >> 3) + g) * 16;
-                    FragU xh, xl;
+                    Frag xh, xl;
                     xh.q = *reinterpret_cast<const uint4*>(x_hi + off);
                     xl.q = *reinterpret_cast<const uint4*>(x_lo + off);
 #pragma unroll
@@ -197,8 +176,8 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                     if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);   // rows before the utterance (zero history) or past its end
                     *reinterpret_cast<float4*>(ut + i * (C * 4) + (((ch >> 2) ^ usw(i)) << 4)) = v;
                     unsigned h01, l01, h23, l23;
-                    split2u(elu_fast(v.x), elu_fast(v.y), h01, l01);
-                    split2u(elu_fast(v.z), elu_fast(v.w), h23, l23);
+                    split2(elu_fast(v.x), elu_fast(v.y), h01, l01);
+                    split2(elu_fast(v.z), elu_fast(v.w), h23, l23);
                     const int off = rho * ROWB + ((((ch >> 3) ^ esw(rho)) & CM) << 4) + ((ch & 4) << 1);
                     *reinterpret_cast<uint2*>(eu_hi + off) = make_uint2(h01, h23);
                     *reinterpret_cast<uint2*>(eu_lo + off) = make_uint2(l01, l23);
@@ -222,12 +201,12 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 const int tap = (s * 32) / C, c0 = (s * 32) % C;
                 const int rho = i_lane + tap;             // window row i-2+tap, stored at rho = that + 2
                 const int off = rho * ROWB + ((((c0 >> 3) + g) ^ esw(rho)) & CM) * 16;
-                FragU xh, xl;
+                Frag xh, xl;
                 xh.q = *reinterpret_cast<const uint4*>(eu_hi + off);
                 xl.q = *reinterpret_cast<const uint4*>(eu_lo + off);
 #pragma unroll
                 for (int n = 0; n < NT; n++) {
-                    FragU wh;
+                    Frag wh;
                     wh.q = w1[(n * KS + s) * 64];
                     acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xh.v, acc[n], 0, 0, 0);
                     PTTS_LO_MFMA(acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xl.v, acc[n], 0, 0, 0));
@@ -238,8 +217,8 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 const int ch = n * 16 + 4 * g;
                 const float4 b = *reinterpret_cast<const float4*>(bl1 + ch);
                 unsigned h01, l01, h23, l23;
-                split2u(elu_fast(acc[n][0] + b.x), elu_fast(acc[n][1] + b.y), h01, l01);
-                split2u(elu_fast(acc[n][2] + b.z), elu_fast(acc[n][3] + b.w), h23, l23);
+                split2(elu_fast(acc[n][0] + b.x), elu_fast(acc[n][1] + b.y), h01, l01);
+                split2(elu_fast(acc[n][2] + b.z), elu_fast(acc[n][3] + b.w), h23, l23);
                 const int off = i_lane * HROWB + ch * 2;
                 *reinterpret_cast<uint2*>(h_hi + off) = make_uint2(h01, h23);
                 *reinterpret_cast<uint2*>(h_lo + off) = make_uint2(l01, l23);
@@ -257,12 +236,12 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
 #pragma unroll
             for (int s = 0; s < KS; s++) {
                 const int off = i_lane * HROWB + (s * 4 + g) * 16;
-                FragU xh, xl;
+                Frag xh, xl;
                 xh.q = *reinterpret_cast<const uint4*>(h_hi + off);
                 xl.q = *reinterpret_cast<const uint4*>(h_lo + off);
 #pragma unroll
                 for (int n = 0; n < NT; n++) {
-                    FragU wh;
+                    Frag wh;
                     wh.q = w2[(n * KS + s) * 64];
                     acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xh.v, acc[n], 0, 0, 0);
                     PTTS_LO_MFMA(acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xl.v, acc[n], 0, 0, 0));
@@ -278,12 +257,11 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 v.z = elu_fast(ur.z + (acc[n][2] + b.z)); v.w = elu_fast(ur.w + (acc[n][3] + b.w));
                 if (!in_seq) v = make_float4(0.f, 0.f, 0.f, 0.f);   // rows before the utterance are the final conv's zero padding
                 const int rho = i_lane + 2;
-                unsigned h01, l01, h23, l23;
-                split2u(v.x, v.y, h01, l01);
-                split2u(v.z, v.w, h23, l23);
+                uint2 hi, lo;
+                split4(v, hi, lo);
                 const int off = rho * ROWB + ((((ch >> 3) ^ esw(rho)) & CM) << 4) + ((ch & 4) << 1);
-                *reinterpret_cast<uint2*>(eu_hi + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(eu_lo + off) = make_uint2(l01, l23);
+                *reinterpret_cast<uint2*>(eu_hi + off) = hi;
+                *reinterpret_cast<uint2*>(eu_lo + off) = lo;
             }
         }
         // ---- D: pcm[row] = bf + sum_{tap, c} sum[row-2+tap][c] * wf[tap*C + c] ----
@@ -298,7 +276,7 @@ __global__ __launch_bounds__(512) void k_resblock_up(ResArgs a) {
                 const int tap = (s * 32) / C, c0 = (s * 32) % C;
                 const int rho = i_lane + tap;
                 const int off = rho * ROWB + ((((c0 >> 3) + g) ^ esw(rho)) & CM) * 16;
-                FragU xh, xl, wh, wl;
+                Frag xh, xl, wh, wl;
                 xh.q = *reinterpret_cast<const uint4*>(eu_hi + off);
                 xl.q = *reinterpret_cast<const uint4*>(eu_lo + off);
                 wh.q = wfh[s * 64];

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 #include "step_open.h"
 
 namespace ptts {
@@ -34,30 +35,10 @@ namespace ptts {
 // Blocks that share a weight tile (the row tiles) are 8-congruent in dispatch order when N/64 is a multiple of 8,
 // i.e. land on one XCD and share its L2 (speed only).
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SK_CHAIN_BX = 3;  // blocks per row tile of a chained last launch: one for fx and the books, two for the halves of x (1024 columns)
 constexpr int SK_KMAX = 1024;   // K slice per block (LDS image: 2 x 16 rows x 2 KB = 64 KB)
 constexpr int SK_KMAX2 = 2048;  // ... for the plain (no fused prologue) split-K launches: NJ = 8, image 2 x 16 rows x 4 KB = 128 KB
-
-// (a, b) -> packed bf16 hi pair and bf16 lo pair with a = hi + lo (round-to-nearest-even, NaN stays NaN)
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    f32x2 r = f - __builtin_convertvector(h, f32x2);
-    bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
-union Frag8 {
-    bf16x8 v;
-    uint4 q;
-    unsigned u[4];
-};
 
 // prologue variants (template parameter PRO)
 constexpr int PRO_LN = 1, PRO_AFFINE = 2, PRO_MOD = 4, PRO_PARTIAL = 8, PRO_ONE = 16;   // PRO_ONE (with PRO_PARTIAL): exactly one plane (the usual case: see below)
@@ -316,12 +297,11 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
         for (int j = 0; j < NJ; j++) {
             const int k = (lane + 64 * j) * 4;
             if (k >= nss * 128) continue;
-            unsigned h01, l01, h23, l23;
-            split2(xr[j].x, xr[j].y, h01, l01);
-            split2(xr[j].z, xr[j].w, h23, l23);
+            uint2 hi, lo;
+            split4(xr[j], hi, lo);
             const int off = wave * RB + ((((k >> 3) ^ wave) & CMASK) << 4) + ((k & 4) << 1);
-            *reinterpret_cast<uint2*>(&Xh[off]) = make_uint2(h01, h23);
-            *reinterpret_cast<uint2*>(&Xl[off]) = make_uint2(l01, l23);
+            *reinterpret_cast<uint2*>(&Xh[off]) = hi;
+            *reinterpret_cast<uint2*>(&Xl[off]) = lo;
         }
     }
     __syncthreads();
@@ -396,14 +376,14 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
         for (int s = 0; s < 4; s++) {
             const int c = (ss_lo + t) * 16 + q * 4 + s;            // logical 16-byte chunk = 8 k
             const int off = i16 * RB + (((c ^ i16) & CMASK) << 4);
-            Frag8 xh, xl;
+            Frag xh, xl;
             xh.q = *reinterpret_cast<const uint4*>(&Xh[off]);
             xl.q = *reinterpret_cast<const uint4*>(&Xl[off]);
             if constexpr (WT == 2) {
                 // 8 offset-binary bytes -> 8 bf16: (float)byte - 128 is an integer in [-127, 127], exact in bf16
                 const uint4 r = w[t][s >> 1];
                 const unsigned d0 = (s & 1) ? r.z : r.x, d1 = (s & 1) ? r.w : r.y;
-                Frag8 wv;
+                Frag wv;
                 f32x2 p;
                 p = f32x2{(float)(d0 & 0xffu), (float)((d0 >> 8) & 0xffu)} - f32x2{128.f, 128.f};
                 { bf16x2 b = __builtin_convertvector(p, bf16x2); wv.u[0] = *reinterpret_cast<unsigned*>(&b); }
@@ -416,12 +396,12 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
                 acc_h = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh.v, wv.v, acc_h, 0, 0, 0);
                 acc_l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl.v, wv.v, acc_l, 0, 0, 0);
             } else if constexpr (WT == 1) {
-                Frag8 wv;
+                Frag wv;
                 wv.q = w[t][s];
                 acc_h = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh.v, wv.v, acc_h, 0, 0, 0);
                 acc_l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl.v, wv.v, acc_l, 0, 0, 0);
             } else {
-                Frag8 wh, wl;
+                Frag wh, wl;
                 const uint4 r0 = w[t][2 * s], r1 = w[t][2 * s + 1];
                 split2(__uint_as_float(r0.x), __uint_as_float(r0.y), wh.u[0], wl.u[0]);
                 split2(__uint_as_float(r0.z), __uint_as_float(r0.w), wh.u[1], wl.u[1]);

@@ -8,43 +8,17 @@
 #pragma once
 
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
-
-typedef __bf16 so_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 so_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float so_f32x2 __attribute__((ext_vector_type(2)));
-typedef float so_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SO_K = 32;            // the latent width this path is built for (host: d.ldim == 32)
 constexpr int SO_PITCH = SO_K * 2;  // bytes per row of a bf16 plane
 
-union SoFrag {
-    so_bf16x8 v;
-    uint4 q;
-    unsigned u[4];
-};
-
-// v -> bf16 hi + bf16 lo with v = hi + lo to ~2^-17 (round to nearest even; a NaN stays a NaN)
-__device__ __forceinline__ void so_split1(float v, unsigned short& hi, unsigned short& lo) {
-    const __bf16 h = (__bf16)v;
-    const __bf16 l = (__bf16)(v - (float)h);
-    hi = __builtin_bit_cast(unsigned short, h);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
-__device__ __forceinline__ void so_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    so_f32x2 f = {a, b};
-    so_bf16x2 h = __builtin_convertvector(f, so_bf16x2);
-    so_f32x2 r = f - __builtin_convertvector(h, so_f32x2);
-    so_bf16x2 l = __builtin_convertvector(r, so_bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
 // element (row, col) of a [16][32] plane pair in LDS
 __device__ __forceinline__ void so_put(unsigned char* ph, unsigned char* pl, int row, int col, float v) {
     unsigned short h, l;
-    so_split1(v, h, l);
+    split1(v, h, l);
     *reinterpret_cast<unsigned short*>(ph + row * SO_PITCH + col * 2) = h;
     *reinterpret_cast<unsigned short*>(pl + row * SO_PITCH + col * 2) = l;
 }
@@ -79,21 +53,21 @@ __device__ __forceinline__ SoW<WBF16> so_load_w(const void* W, const float* bias
 template <bool WBF16>
 __device__ __forceinline__ void so_tile(const unsigned char* ph, const unsigned char* pl, const SoW<WBF16>& w, int n0, float* out, int64_t ld, int m0, int M, int lane) {
     const int j = lane & 15, q = lane >> 4;
-    SoFrag xh, xl;
+    Frag xh, xl;
     xh.q = *reinterpret_cast<const uint4*>(ph + j * SO_PITCH + q * 16);
     xl.q = *reinterpret_cast<const uint4*>(pl + j * SO_PITCH + q * 16);
-    so_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if constexpr (WBF16) {
-        SoFrag wv;
+        Frag wv;
         wv.q = w.a;
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv.v, xh.v, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv.v, xl.v, acc, 0, 0, 0);
     } else {
-        SoFrag wh, wl;
-        so_split2(__uint_as_float(w.a.x), __uint_as_float(w.a.y), wh.u[0], wl.u[0]);
-        so_split2(__uint_as_float(w.a.z), __uint_as_float(w.a.w), wh.u[1], wl.u[1]);
-        so_split2(__uint_as_float(w.b[0].x), __uint_as_float(w.b[0].y), wh.u[2], wl.u[2]);
-        so_split2(__uint_as_float(w.b[0].z), __uint_as_float(w.b[0].w), wh.u[3], wl.u[3]);
+        Frag wh, wl;
+        split2(__uint_as_float(w.a.x), __uint_as_float(w.a.y), wh.u[0], wl.u[0]);
+        split2(__uint_as_float(w.a.z), __uint_as_float(w.a.w), wh.u[1], wl.u[1]);
+        split2(__uint_as_float(w.b[0].x), __uint_as_float(w.b[0].y), wh.u[2], wl.u[2]);
+        split2(__uint_as_float(w.b[0].z), __uint_as_float(w.b[0].w), wh.u[3], wl.u[3]);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xh.v, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh.v, xl.v, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl.v, xh.v, acc, 0, 0, 0);

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "device_util.h"
+#include "mfma_util.h"
 
 namespace ptts {
 
@@ -28,11 +29,6 @@ namespace ptts {
 // columns of one row (16-byte stores).  What differs from the 64-row path is the grouping of the sums over K (one accumulator pair over the whole slice instead of
 // four K parts): rounding order, covered by the same tolerances (tests/test_gpu_wide_batch.py runs every 64-row check at 128 and 256 rows through these kernels).
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 tl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tl_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float tl_f32x2 __attribute__((ext_vector_type(2)));
-typedef float tl_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TL_COLS = 64, TL_KC = 128;                     // a block's columns and the K chunk; its rows are the template parameter ROWS (64, or 32 up to 128 rows:
                                                              // twice the blocks, each taking in two thirds of the bytes -- a 128-row launch has 96..128 blocks of 64 rows)
 constexpr int TL_W = TL_COLS * TL_KC * 2;                    // bytes of the weight pieces of a stage (16 KB)
@@ -47,30 +43,9 @@ template <int ROWS> struct TlShape {
     static constexpr int PIECES = APIECES + WPIECES;
 };
 
-union TlFrag {
-    tl_bf16x8 v;
-    uint4 q;
-};
-
-__device__ __forceinline__ void tl_split2(float a, float b, unsigned& hi, unsigned& lo) {   // (skinny.hip split2)
-    tl_f32x2 f = {a, b};
-    tl_bf16x2 h = __builtin_convertvector(f, tl_bf16x2);
-    tl_f32x2 r = f - __builtin_convertvector(h, tl_f32x2);
-    tl_bf16x2 l = __builtin_convertvector(r, tl_bf16x2);
-    hi = *reinterpret_cast<unsigned*>(&h);
-    lo = *reinterpret_cast<unsigned*>(&l);
-}
-
 // 16-byte chunk swizzle of a row image (row r of a 16-row tile, 16 chunks of 8 k per 128-deep chunk): chunk c sits at c ^ tl_swz(r).  With a 256-byte row pitch the
 // 16 lanes one ds_read_b128 service group holds (two lane groups q of different rows) then hit 16 different 16-byte slots of the 256-byte bank period.
 __device__ __forceinline__ int tl_swz(int r) { return ((r >> 2) & 1) | (r & 2) | ((r & 1) << 3); }
-
-// One LDS-DMA wave-instruction: lane l's 16 bytes at src_lane -> lds_base + 16 l (ffn_fused.hip ff_dma1k: inline assembly so that the compiler's wait counters do
-// not serialise the ring; the wait state between the write of m0 and its use is written out; m0 is reserved to the compiler, which keeps nothing in it across statements)
-__device__ __forceinline__ void tl_dma1k(const char* src_lane, char* dst) {
-    const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(base), "v"(src_lane) : "memory");
-}
 
 template <bool PLANES, int ROWS>
 __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
@@ -104,10 +79,10 @@ __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
     auto issue = [&](int ch) {
         char* st = lds + (ch % TL_NS) * TL_STAGE;
         const int ss = ss0 + ch;
-        tl_dma1k(a_hi + (int64_t)ss * (TL_KC * 2), st + wave * 1024);
-        tl_dma1k(a_lo + (int64_t)ss * (TL_KC * 2), st + TL_PLANE + wave * 1024);
+        lds_dma1k(a_hi + (int64_t)ss * (TL_KC * 2), st + wave * 1024);
+        lds_dma1k(a_lo + (int64_t)ss * (TL_KC * 2), st + TL_PLANE + wave * 1024);
 #pragma unroll
-        for (int i = 0; i < S::WPIECES; i++) tl_dma1k(w_src[i] + (int64_t)ss * 4096, st + 2 * TL_PLANE + (wave + i * S::WAVES) * 1024);
+        for (int i = 0; i < S::WPIECES; i++) lds_dma1k(w_src[i] + (int64_t)ss * 4096, st + 2 * TL_PLANE + (wave + i * S::WAVES) * 1024);
     };
 
     // ---- epilogue operands: requested before the copies (they are older than every copy in the wave's queue, so the counted waits below cover them) ----
@@ -124,7 +99,7 @@ __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
 
 #pragma unroll
     for (int c = 0; c < TL_NS - 1; c++) if (c < nch) issue(c);
-    tl_f32x4 acc_h = {0.f, 0.f, 0.f, 0.f}, acc_l = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc_h = {0.f, 0.f, 0.f, 0.f}, acc_l = {0.f, 0.f, 0.f, 0.f};
     const int x_off = (rt * 16 + i16) * 256, x_swz = tl_swz(i16);
     for (int ch = 0; ch < nch; ch++) {
         // chunk ch has landed: this wave's copies of it (everything but the copies of the chunks issued after it -- up to NS - 2 of them -- is complete), then everybody's
@@ -140,7 +115,7 @@ __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
         const char* st = lds + (ch % TL_NS) * TL_STAGE;
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            TlFrag w, xh, xl;
+            Frag w, xh, xl;
             w.q = *reinterpret_cast<const uint4*>(st + 2 * TL_PLANE + (cg * 4 + s) * 1024 + lane * 16);
             const int off = x_off + (((q * 4 + s) ^ x_swz) << 4);
             xh.q = *reinterpret_cast<const uint4*>(st + off);
@@ -150,7 +125,7 @@ __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
         }
     }
     // D of the swapped product: lane (i16, q) holds row m = its x row, columns n .. n + 3
-    const tl_f32x4 acc = acc_h + acc_l;
+    const f32x4 acc = acc_h + acc_l;
     if (!m_ok || !n_ok) return;
     float v[4] = {acc[0], acc[1], acc[2], acc[3]};
     if (a.splitk > 1) {   // raw sums of the K slice; slice 0 carries residual + bias (k_skinny's convention: the consumer reads plane 0 as its rows and adds the others)
@@ -170,11 +145,10 @@ __global__ __launch_bounds__(ROWS * 16) void k_tall(TallArgs a) {
             break;
     }
     if constexpr (PLANES) {
-        unsigned h01, l01, h23, l23;
-        tl_split2(v[0], v[1], h01, l01);
-        tl_split2(v[2], v[3], h23, l23);
-        *reinterpret_cast<uint2*>(a.ch + (int64_t)m * a.ldp + n) = make_uint2(h01, h23);
-        *reinterpret_cast<uint2*>(a.cl + (int64_t)m * a.ldp + n) = make_uint2(l01, l23);
+        uint2 hi, lo;
+        split4(make_float4(v[0], v[1], v[2], v[3]), hi, lo);
+        *reinterpret_cast<uint2*>(a.ch + (int64_t)m * a.ldp + n) = hi;
+        *reinterpret_cast<uint2*>(a.cl + (int64_t)m * a.ldp + n) = lo;
     } else {
         *reinterpret_cast<float4*>(a.C + (int64_t)m * a.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -245,32 +219,31 @@ __global__ __launch_bounds__(256) void k_rowprep(PrepArgs a) {
             for (int j = 0; j < NJ; j++) *reinterpret_cast<float4*>(a.x_out + (int64_t)m * a.D + (lane + 64 * j) * 4) = xr[j];
         }
     }
-    tl_f32x2 s2 = {0.f, 0.f};
+    f32x2 s2 = {0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < NJ; j++) s2 += tl_f32x2{xr[j].x, xr[j].z} + tl_f32x2{xr[j].y, xr[j].w};
+    for (int j = 0; j < NJ; j++) s2 += f32x2{xr[j].x, xr[j].z} + f32x2{xr[j].y, xr[j].w};
     const float rk = __builtin_amdgcn_rcpf((float)a.D);
     const float mean = wave_sum_dpp(s2.x + s2.y) * rk;
-    const tl_f32x2 m2 = {mean, mean};
-    tl_f32x2 v2 = {0.f, 0.f};
+    const f32x2 m2 = {mean, mean};
+    f32x2 v2 = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
-        const tl_f32x2 da = tl_f32x2{xr[j].x, xr[j].y} - m2, db = tl_f32x2{xr[j].z, xr[j].w} - m2;
+        const f32x2 da = f32x2{xr[j].x, xr[j].y} - m2, db = f32x2{xr[j].z, xr[j].w} - m2;
         v2 += da * da + db * db;
     }
     const float inv_std = __builtin_amdgcn_rsqf(wave_sum_dpp(v2.x + v2.y) * rk + a.eps);
-    const tl_f32x2 is2 = {inv_std, inv_std};
+    const f32x2 is2 = {inv_std, inv_std};
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
-        tl_f32x2 oa = (tl_f32x2{xr[j].x, xr[j].y} - m2) * is2, ob = (tl_f32x2{xr[j].z, xr[j].w} - m2) * is2;
-        oa = oa * tl_f32x2{lw[j].x, lw[j].y} + tl_f32x2{lb[j].x, lb[j].y};
-        ob = ob * tl_f32x2{lw[j].z, lw[j].w} + tl_f32x2{lb[j].z, lb[j].w};
+        f32x2 oa = (f32x2{xr[j].x, xr[j].y} - m2) * is2, ob = (f32x2{xr[j].z, xr[j].w} - m2) * is2;
+        oa = oa * f32x2{lw[j].x, lw[j].y} + f32x2{lb[j].x, lb[j].y};
+        ob = ob * f32x2{lw[j].z, lw[j].w} + f32x2{lb[j].z, lb[j].w};
         const int col = (lane + 64 * j) * 4;
         if (a.y_out) *reinterpret_cast<float4*>(a.y_out + (int64_t)m * a.D + col) = make_float4(oa.x, oa.y, ob.x, ob.y);
-        unsigned h01, l01, h23, l23;
-        tl_split2(oa.x, oa.y, h01, l01);
-        tl_split2(ob.x, ob.y, h23, l23);
-        *reinterpret_cast<uint2*>(a.yh + (int64_t)m * a.ldy + col) = make_uint2(h01, h23);
-        *reinterpret_cast<uint2*>(a.yl + (int64_t)m * a.ldy + col) = make_uint2(l01, l23);
+        uint2 hi, lo;
+        split4(make_float4(oa.x, oa.y, ob.x, ob.y), hi, lo);
+        *reinterpret_cast<uint2*>(a.yh + (int64_t)m * a.ldy + col) = hi;
+        *reinterpret_cast<uint2*>(a.yl + (int64_t)m * a.ldy + col) = lo;
     }
 }
 

@@ -126,7 +126,7 @@ def planes(c):
 
 
 # ------------------------------------------------------------------------------------------------ host logic of the launchers (restated)
-def _al(c, kalign):   # the alignment conditions every *_supported shares
+def _al(c, kalign):   # the alignment conditions every *_supported shares (csrc/gemm_tile.h gemm_operands_aligned)
     a, cm = amap(c), cmap(c)
     return a[0] % 4 == 0 and a[2] % 4 == 0 and a[3] % 4 == 0 and (c["K"] + c["ldw_pad"]) % kalign == 0, cm[0] % 4 == 0 and cm[2] % 4 == 0 and cm[3] % 4 == 0
 
