@@ -1159,6 +1159,33 @@ int ptts_limit_rows(ptts_model* h, const ptts_limiter_opts* const* l, const floa
     });
 }
 
+// the device form of ptts_join on host rows: k_join, as ptts_generate_joined launches it
+int ptts_join_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, float* out) {
+    return guard([&] {
+        Model& m = model_of(h);
+        JoinLens l;
+        std::string e = join_opts_error(opts, &l);
+        int64_t total = 0;
+        if (e.empty()) e = join_plan(n, rows, l, nullptr, nullptr, &total);
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        if (!in || (!out && total > 0)) throw Error(PTTS_EINVAL, "ptts-hip: join: null argument");
+        for (int i = 0; i < rows; i++)
+            if (!in[i] && n[i] > 0) throw Error(PTTS_EINVAL, strfmt("ptts-hip: join: part %d is null", i));
+        join_rows_device(m, in, n, rows, l, out);
+    });
+}
+
+// Service.Synthesize's chunks as one utterance (service.go:107-153), finished on the device: generate_joined (runtime.cpp)
+int ptts_generate_joined(ptts_model* h, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, ptts_result* out, ptts_join_part* parts) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        if (!reqs || !out || n <= 0) throw Error(PTTS_EINVAL, "ptts-hip: no requests");
+        if (!o) throw Error(PTTS_EINVAL, "ptts-hip: join: null options");
+        set_last_error("");
+        generate_joined(*h->m, reqs, n, *o, out, parts);
+    });
+}
+
 // target NULL: measurement only (lufs is required); otherwise out is, and lufs receives what was measured before
 static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
     Model& m = model_of(h);

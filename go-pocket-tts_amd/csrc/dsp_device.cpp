@@ -1,7 +1,7 @@
 // dsp_device.cpp -- the host side of the device post-processing (dsp.hip, compressor.hip, limiter.hip, true_peak.hip):
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
-// them; what a row gets is resolved in dsp_spec.cpp.
+// them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows.
 #include <cmath>
 
 #include "row_tables.h"
@@ -182,6 +182,56 @@ void dsp_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t
         if (o.true_peaks && j.tp_out) PTTS_HIP(hipMemcpyAsync(o.true_peaks + i, j.tp_out, sizeof(float), hipMemcpyDeviceToHost, s));
         if (o.out) buf.download(i, o.out[i], s);
     }
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the join (join.hip; join.h has the rule) ----
+
+void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s) {
+    constexpr int kRows = RowRing<JoinRow>::kRows;
+    for (size_t at = 0; at < rows.size(); at += kRows) {
+        const int n = (int)std::min<size_t>(kRows, rows.size() - at);
+        int64_t tiles = 0;
+        for (int i = 0; i < n; i++) {
+            const JoinRow& r = rows[at + (size_t)i];
+            if (r.gap + r.n > 0) tiles = std::max(tiles, (r.gap + r.n + 3 + kJoinTile - 1) / kJoinTile);
+        }
+        if (tiles == 0) continue;
+        if (tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: join: too many samples for one launch");
+        launch_join(m.join_ring.stage(rows.data() + at, n, s), n, (int)tiles, s);
+        m.join_ring.done(s);
+    }
+}
+
+void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out) {
+    std::vector<int64_t> off((size_t)rows), seam((size_t)rows);
+    int64_t total = 0;
+    const std::string e = join_plan(n, rows, l, off.data(), seam.data(), &total);
+    if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+    if (total == 0) return;
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> bytes((size_t)rows + 1);
+    for (int i = 0; i < rows; i++) bytes[(size_t)i] = (size_t)n[i] * sizeof(float);
+    bytes[(size_t)rows] = (size_t)total * sizeof(float);   // the joined row, behind the parts
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes));
+    std::vector<JoinRow> jr;
+    for (int i = 0; i < rows; i++) {
+        if (n[i] > 0) buf.upload(i, in[i], s);
+        const int64_t k = seam[(size_t)i], k_next = i + 1 < rows ? seam[(size_t)i + 1] : 0;
+        JoinRow r{};
+        r.src = (const float*)buf.row(i);
+        r.prev = k ? (const float*)buf.row(i - 1) + (n[i - 1] - k) : nullptr;
+        r.dst = (float*)buf.row(rows);
+        r.off = off[(size_t)i];
+        r.n = n[i] - k_next;
+        r.k = (int32_t)k;
+        r.gap = i ? (int32_t)l.gap : 0;
+        jr.push_back(r);
+    }
+    join_launch(m, jr, s);
+    buf.download(rows, out, s);
     PTTS_HIP(hipStreamSynchronize(s));
 }
 

@@ -377,6 +377,25 @@ static_assert(sizeof(LimRow) == 40, "a turn of the limiter ring holds 256 of the
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
 void launch_limiter(const LimRow* rows_dev, int n, int max_tiles, const LimScan* designs_dev, hipStream_t stream);
 
+// A text's parts joined into one row (join.hip, k_join; join.h has the rule, join.cpp the host statement): a table of
+// parts, each copied to its offset in the joined row behind its gap of zeros, its first k samples crossfaded with its predecessor's last k.  A
+// row writes [off - gap, off + n): n stops where the successor's seam begins, so the rows' spans tile the joined row and every sample is
+// written once.  prev travels with the row, so a seam is computed by one row even when the predecessor sits in the previous table.
+constexpr int kJoinThreads = 256;
+constexpr int kJoinTile = 4 * kJoinThreads;   // output samples per workgroup (4 consecutive per lane)
+struct JoinRow {
+    const float* src;      // the part's samples (device)
+    const float* prev;     // seam rows (k > 0): the predecessor's last k samples (device); may be dst + off itself, see join.hip
+    float* dst;            // the joined row (device)
+    int64_t off;           // where the part's first sample goes in dst
+    int64_t n;             // the part's samples this row writes: its length minus the seam behind it
+    int32_t k;             // samples of the seam in front of the part (0: none; <= n)
+    int32_t gap;           // zeros in front of the part, dst[off - gap, off) (0 with k > 0)
+};
+static_assert(sizeof(JoinRow) == 48, "a turn of the join ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil((gap + n + 3) / kJoinTile) of a row (three more: the destination's 16-byte grid)
+void launch_join(const JoinRow* rows_dev, int n, int max_tiles, hipStream_t stream);
+
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.
 // final_conv with rows: utterance b's samples [0, lim) go straight to dst (f32, or int16 through WritePCM16Samples' arithmetic) --

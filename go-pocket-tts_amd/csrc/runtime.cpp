@@ -1378,7 +1378,7 @@ const PcmRow* results_alloc(const Model& m, const std::vector<Delivery>& g, PcmR
         if (!u.res || u.filled) continue;
         const int fmt = u.req->pcm_format;
         const bool s16 = fmt == PTTS_PCM_S16;
-        const int64_t ns = egress_length(*u.req, (int64_t)u.nf * spf);
+        const int64_t ns = egress_length(*u.req, u.samples(spf));
         void* p = result_alloc((size_t)std::max<int64_t>(1, ns) * pcm_bytes(fmt));
         set_result_buffer(*u.res, fmt, p);
         if (!p) continue;
@@ -1403,11 +1403,11 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         std::vector<DspJob> jobs;
         for (int64_t i = 0; i < n; i++) {
             const Delivery& u = g[(size_t)i];
-            if (u.res && !u.filled && u.nf > 0 && (u.req->dsp || u.req->loudness) && result_buffer(*u.res, u.req->pcm_format)) {
+            if (u.res && !u.filled && u.samples(spf) > 0 && (u.req->dsp || u.req->loudness) && result_buffer(*u.res, u.req->pcm_format)) {
                 // resolved now, not at admission: a handle freed since the request was checked ends the call with PTTS_EINVAL, nothing is launched
                 // (whether the row has work is asked of the resolved spec; request_postprocesses, which counts an ext unseen, has kept every
                 // such request away from the decoder's direct store, so `stored` is false for a group that holds one)
-                DspJob j{const_cast<float*>(pcm) + i * pcm_stride, (int64_t)u.nf * spf, DspSpec()};
+                DspJob j{const_cast<float*>(pcm) + i * pcm_stride, u.samples(spf), DspSpec()};
                 const std::string e = dsp_resolve(u.req->dsp, &j.spec);
                 if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
                 const double target_lufs = (double)u.req->loudness / 100.0;   // 0.01 LUFS
@@ -1422,7 +1422,7 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
         if (!u.res) continue;
         ptts_result& r = *u.res;
         const int fmt = u.req->pcm_format;
-        r.n_frames = u.nf; r.eos_step = u.eos; r.n_samples = egress_length(*u.req, (int64_t)u.nf * spf);
+        r.n_frames = u.nf; r.eos_step = u.eos; r.n_samples = egress_length(*u.req, u.samples(spf));
         const bool s16 = fmt == PTTS_PCM_S16;
         if (!result_buffer(r, fmt)) { r.status = PTTS_ENOMEM; continue; }
         if (!stored && !u.filled && r.n_samples > 0) {   // all copies are queued back to back: the caller waits once
@@ -1468,7 +1468,7 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
             dst = sb;
             sb += (bytes + 255) & ~(size_t)255;
         }
-        rows.push_back(resample_row(rate_filter(m, kNativeRate, request_rate(*u.req), s), pcm + i * pcm_stride, (int64_t)u.nf * spf, dst, 0, r.n_samples, fmt));
+        rows.push_back(resample_row(rate_filter(m, kNativeRate, request_rate(*u.req), s), pcm + i * pcm_stride, u.samples(spf), dst, 0, r.n_samples, fmt));
     }
     resample_launch(m, rows, s);
     for (size_t k = 0; k < copies.size(); k++)
@@ -1556,6 +1556,20 @@ void enqueue_step(Batch& b, int lsd, bool use_graph, int nsteps) {
 }
 
 namespace {
+// What the groups of one generate_joined call share: the text's joined row on the device (WORK_JOINED, sized for the step budgets before the
+// first group runs), how far it is filled, and the parts' records.  A group's Chunk::deliver joins its rows behind what is there.
+struct JoinSink {
+    JoinLens lens;
+    float* row = nullptr;         // the joined row (device)
+    int64_t cap = 0;              // its samples
+    ptts_join_part* parts;        // [n], by request index
+    int64_t at = 0;               // the joined length so far
+    int64_t n_prev = -1;          // samples of the last part joined (-1: none yet)
+    int64_t frames = 0;
+    int fail = PTTS_OK;           // the code of the first chunk, in text order, that was cancelled or ran past the decoder's reach
+    std::string fail_msg;
+};
+
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
 // alike: copies, decoder launches and host functions queued on the two streams may still read `cancelled`, `stream_ranges` and
 // `stream_host`, so both streams are drained first, then the streaming buffers go back.
@@ -1563,6 +1577,7 @@ struct Chunk {
     Model& m;
     const ptts_request* reqs; const std::vector<int>& idx; ptts_result* res;   // slot i: reqs[idx[i]], answered in res[idx[i]]
     const int lsd;
+    JoinSink* const join;        // generate_joined: the group's rows go into the text's joined row, nothing into res (null)
     const int B = (int)idx.size(), ld = m.d.ldim;
     const int64_t spf = m.d.samples_per_frame;
     const hipStream_t s = m.stream;
@@ -1627,6 +1642,7 @@ struct Chunk {
     }
     void phase(int i, hipStream_t st) { if (hipEvent_t e = phase_event(i)) PTTS_HIP(hipEventRecord(e, st)); }
     void setup(); void decoder_setup(); void ar_loop(); void deliver();   // the phases, in order
+    void deliver_joined(const int32_t* nf, const int32_t* eos);
     void decode_upto(int f1, const PcmRow* rows = nullptr, bool* rows_used = nullptr);
     void emit_upto(int f1, bool last = false);
 };
@@ -1879,6 +1895,7 @@ void Chunk::deliver() {
     PTTS_HIP(hipStreamSynchronize(s));
     if (hp[1 + 2 * B]) flow_cluster_fault(*b);
     const int32_t* nf = hp + 1;
+    if (join) { deliver_joined(nf, hp + 1 + B); return; }
     int Tmax = 0;
     std::vector<Delivery> g((size_t)B);   // row i of the decode: slot i (cancelled and over-long utterances are decoded, not delivered)
     for (int i = 0; i < B; i++) {
@@ -1908,11 +1925,59 @@ void Chunk::deliver() {
     PTTS_HIP(hipStreamSynchronize(s));
     mark("results d2h");
 }
+
+// generate_joined's delivery (behind the fault check: a group that is run again has joined nothing yet): the parts' records; the decode of
+// the whole group into the decoder's buffer; one k_join table that copies the group's rows behind what the text's row holds.  A seam inside
+// the group is computed by the row behind it, which reads its predecessor's tail in the decoder's buffer.  The group's first row has its
+// predecessor in an earlier group, whose buffer is gone: that group stored the tail unfaded, and this row fades it where it lies.
+void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
+    int Tmax = 0;
+    for (int i = 0; i < B; i++) {
+        ptts_join_part& p = join->parts[idx[(size_t)i]];
+        const bool overlong = !cancelled[i] && nf[i] > t_limit;   // ran past the decoder's reach, as in deliver()
+        p.n_frames = nf[i]; p.eos_step = eos[i];
+        p.status = cancelled[i] ? PTTS_ECANCELLED : overlong ? PTTS_EINVAL : PTTS_OK;
+        if (p.status != PTTS_OK && join->fail == PTTS_OK) {
+            join->fail = p.status;
+            join->fail_msg = overlong ? std::string(too_long(nf[i]).what()) : strfmt("generate: context canceled (request %d of the joined call)", idx[(size_t)i]);
+        }
+        Tmax = std::max(Tmax, nf[i]);
+    }
+    if (join->fail != PTTS_OK) return;   // the call fails: nothing of this group is decoded
+    if (m.prof.phases_on) { PTTS_HIP(hipStreamWaitEvent(m.stream2, m.prof.phase[2], 0)); phase(3, m.stream2); }
+    decode_upto(std::min(steps_run, Tmax));
+    phase(4, m.stream2);
+    m.prof.phases = m.prof.phases_on && f_done > 0;
+    PTTS_HIP(hipStreamSynchronize(m.stream2));
+    mark("mimi");
+    const JoinLens& l = join->lens;
+    std::vector<JoinRow> rows;
+    for (int i = 0; i < B; i++) {
+        ptts_join_part& p = join->parts[idx[(size_t)i]];
+        const int64_t n = (int64_t)nf[i] * spf;
+        const float* src = pcm->as<float>() + (size_t)i * T * spf;
+        const bool first = join->n_prev < 0;
+        const int64_t k = first ? 0 : join_seam(l.xfade, join->n_prev, n);
+        const int64_t off = first ? 0 : join->at + l.gap - k;
+        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, (int64_t)nf[i + 1] * spf) : 0;   // (the group's last row stores its tail whole)
+        if (off + n > join->cap) throw Error(PTTS_EINVAL, "ptts-hip: internal: the joined row is smaller than the text");
+        JoinRow r{};
+        r.src = src;
+        r.prev = !k ? nullptr : i ? pcm->as<float>() + (size_t)(i - 1) * T * spf + (join->n_prev - k) : join->row + off;
+        r.dst = join->row;
+        r.off = off; r.n = n - k_next; r.k = (int32_t)k; r.gap = first ? 0 : (int32_t)l.gap;
+        rows.push_back(r);
+        p.offset = off; p.n_samples = n;
+        join->at = off + n; join->n_prev = n; join->frames += nf[i];
+    }
+    join_launch(m, rows, s);   // behind the decode (stream2 has been waited for); the next group's decode waits for s (decode_upto)
+    mark("join");
+}
 }  // namespace
 
-static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector<int>& idx, ptts_result* res, int lsd) {
+static void generate_chunk(Model& m, const ptts_request* reqs, const std::vector<int>& idx, ptts_result* res, int lsd, JoinSink* join = nullptr) {
     UploadScope upload_scope(m.upload, m.stream);
-    Chunk c{m, reqs, idx, res, lsd};
+    Chunk c{m, reqs, idx, res, lsd, join};
     c.setup();
     c.decoder_setup();
     c.ar_loop();
@@ -1951,6 +2016,22 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
     return std::string();
 }
 
+// one group, and once more after a hand-off inside k_flow_cluster timed out somewhere in its AR loop (found when the loop's counters were read
+// back).  The group's inputs are the requests themselves: it runs again on the 2 x depth launches, which compute the same bits (the batch has
+// been switched over: flow_cluster_recover).  Only a group that has already spoken to its caller -- step callbacks, streamed samples -- cannot
+// be re-run.  res null: a group of generate_joined, which has delivered nothing when the fault is found
+static void generate_group(Model& m, const ptts_request* reqs, const std::vector<int>& idx, ptts_result* res, int lsd, JoinSink* join = nullptr) {
+    try {
+        generate_chunk(m, reqs, idx, res, lsd, join);
+    } catch (const FlowClusterFault&) {
+        bool spoke = false;
+        for (int i : idx) spoke |= reqs[i].step_callback != nullptr || reqs[i].pcm_callback != nullptr;
+        if (spoke) throw;
+        if (res) for (int i : idx) { ptts_free_result(&res[i]); std::memset(&res[i], 0, sizeof res[i]); res[i].eos_step = -1; }
+        generate_chunk(m, reqs, idx, res, lsd, join);
+    }
+}
+
 void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res) {
     std::lock_guard<std::mutex> lock(m.mu);
     m.use_device();
@@ -1976,18 +2057,7 @@ void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res) {
         for (size_t o = 0; o < all.size(); o += (size_t)mb) {
             std::vector<int> idx(all.begin() + (long)o, all.begin() + (long)std::min(all.size(), o + (size_t)mb));
             try {
-                try {
-                    generate_chunk(m, reqs, idx, res, kv.first);
-                } catch (const FlowClusterFault&) {
-                    // a hand-off inside k_flow_cluster timed out somewhere in this chunk's AR loop (found when the loop's counters were read back).  The chunk's
-                    // inputs are the requests themselves: run it again on the 2 x depth launches, which compute the same bits (the batch has been switched
-                    // over: flow_cluster_recover).  Only a chunk that has already spoken to its caller -- step callbacks, streamed samples -- cannot be re-run.
-                    bool spoke = false;
-                    for (int i : idx) spoke |= reqs[i].step_callback != nullptr || reqs[i].pcm_callback != nullptr;
-                    if (spoke) throw;
-                    for (int i : idx) { ptts_free_result(&res[i]); std::memset(&res[i], 0, sizeof res[i]); res[i].eos_step = -1; }
-                    generate_chunk(m, reqs, idx, res, kv.first);
-                }
+                generate_group(m, reqs, idx, res, kv.first);
             } catch (const Error& e) {
                 for (int i : idx) { ptts_free_result(&res[i]); res[i].status = e.code; res[i].eos_step = -1; }
                 if (first_err.empty()) first_err = e.what();
@@ -1995,6 +2065,98 @@ void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res) {
         }
     }
     if (!first_err.empty()) set_last_error(first_err);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Joined synthesis: a text's chunks as one utterance (include/ptts.h ptts_generate_joined; join.h)
+// ------------------------------------------------------------------------------------------------
+// the egress and the chain of the join options, as request_error checks a request's: empty, or the message naming the field
+static std::string join_egress_error(const ptts_join_opts& o) {
+    if (o.pcm_format < PTTS_PCM_F32 || o.pcm_format > PTTS_PCM_ALAW)
+        return strfmt("join: pcm_format %d is not PTTS_PCM_F32, PTTS_PCM_S16, PTTS_PCM_ULAW or PTTS_PCM_ALAW", o.pcm_format);
+    if (o.sample_rate != 0) {
+        const std::string e = rate_pair_error(kNativeRate, o.sample_rate);
+        if (!e.empty()) return "join: sample_rate: " + e;
+    }
+    if (o.dsp) {
+        const std::string e = dsp_opts_error(*o.dsp);
+        if (!e.empty()) return "join: " + e;
+    }
+    if (o.loudness) {
+        if (o.loudness < -7000 || o.loudness > -100) return strfmt("join: loudness %d is not 0 (off) or a target from -7000 to -100 (0.01 LUFS)", o.loudness);
+        if (o.dsp && o.dsp->normalize) return "join: loudness cannot be combined with dsp normalize (one gain)";
+    }
+    return std::string();
+}
+
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, ptts_result* out, ptts_join_part* parts) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    const Desc& d = m.d;
+    const int64_t spf = d.samples_per_frame;
+    std::memset(out, 0, sizeof *out);
+    out->eos_step = -1;
+    std::vector<ptts_join_part> own;
+    if (!parts) { own.resize((size_t)std::max(n, 1)); parts = own.data(); }
+    for (int i = 0; i < n; i++) { std::memset(&parts[i], 0, sizeof parts[i]); parts[i].eos_step = -1; }
+    const auto refuse = [&](const std::string& e) { out->status = PTTS_EINVAL; throw Error(PTTS_EINVAL, "ptts-hip: " + e); };
+    // ---- refusals: nothing is launched ----
+    JoinSink sink;
+    sink.parts = parts;
+    std::string e = join_opts_error(&o, &sink.lens);
+    if (e.empty()) e = join_egress_error(o);
+    if (e.empty() && (n < 1 || n > kJoinMaxRows)) e = strfmt("join: %d requests, a text has from 1 to %d parts", n, kJoinMaxRows);
+    if (!e.empty()) refuse(e);
+    const int lsd = reqs[0].lsd_steps <= 0 ? 1 : reqs[0].lsd_steps;
+    const int t_limit = ROPE_SEQ / d.up_stride;
+    int64_t bound = 0;   // the joined length the step budgets allow
+    for (int i = 0; i < n; i++) {
+        const ptts_request& q = reqs[i];
+        e = request_error(d, q);
+        if (!e.empty()) { parts[i].status = PTTS_EINVAL; out->status = PTTS_EINVAL; throw Error(PTTS_EINVAL, e); }
+        const char* f = q.dsp ? "dsp" : q.loudness ? "loudness" : q.sample_rate ? "sample_rate" : q.pcm_format ? "pcm_format" : q.pcm_callback ? "pcm_callback"
+                        : q.want_latents ? "want_latents" : nullptr;
+        if (f) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d sets %s, which belongs in the join options (ptts_join_opts) of a joined call", i, f)); }
+        const int l = q.lsd_steps <= 0 ? 1 : q.lsd_steps;
+        if (l != lsd) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d has lsd_steps %d and request 0 has %d: the groups would leave text order", i, l, lsd)); }
+        bound += (int64_t)std::min(resolve_max_steps(q), t_limit) * spf + (i ? sink.lens.gap : 0);
+    }
+    if (bound >= kJoinMaxSamples) refuse(strfmt("join: the step budgets allow %lld samples, the joined length must stay below 2^31", (long long)bound));
+    ptts_request eg{};   // the chain and the egress of the joined row, as a request states its own: results_deliver serves it like one
+    eg.sample_rate = o.sample_rate; eg.pcm_format = o.pcm_format; eg.dsp = o.dsp; eg.loudness = o.loudness;
+    hipStream_t s = m.stream;
+    try {
+        sink.cap = std::max<int64_t>(bound, 1);
+        sink.row = m.work(WORK_JOINED, (size_t)sink.cap * sizeof(float)).as<float>();
+        // ---- the groups, as generate() cuts them ----
+        const int mb = std::max(1, m.opts.max_batch);
+        for (int o0 = 0; o0 < n && sink.fail == PTTS_OK; o0 += mb) {
+            std::vector<int> idx;
+            for (int i = o0; i < std::min(n, o0 + mb); i++) idx.push_back(i);
+            try {
+                generate_group(m, reqs, idx, nullptr, lsd, &sink);
+            } catch (const Error& err) {
+                for (int i : idx) if (parts[i].status == PTTS_OK) parts[i].status = err.code;
+                throw;
+            }
+        }
+        if (sink.fail != PTTS_OK) throw Error(sink.fail, sink.fail_msg);
+        // ---- the chain, once over the joined audio; the egress of one row ----
+        std::vector<Delivery> g(1);
+        g[0] = Delivery{&eg, out, (int)std::min<int64_t>(sink.frames, INT32_MAX), -1, false};
+        g[0].n24 = sink.at;
+        results_alloc(m, g, nullptr, nullptr, s);
+        results_deliver(m, g, false, sink.row, sink.at, nullptr, 0, s);
+        PTTS_HIP(hipStreamSynchronize(s));
+        if (out->status != PTTS_OK) throw Error(out->status, "ptts-hip: out of host memory");
+    } catch (const Error& err) {
+        (void)hipStreamSynchronize(s);   // nothing queued still writes the buffer that goes back
+        ptts_free_result(out);
+        std::memset(out, 0, sizeof *out);
+        out->eos_step = -1;
+        out->status = err.code;
+        throw;
+    }
 }
 
 }  // namespace ptts

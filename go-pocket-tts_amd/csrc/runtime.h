@@ -10,6 +10,7 @@
 #include "row_ring.h"
 #include "dsp_spec.h"
 #include "host_rows.h"
+#include "join.h"
 
 namespace ptts {
 
@@ -46,7 +47,8 @@ enum WorkSlot : size_t {
     WORK_CONVERT_OUT = 26,       // ... and the packed output rows
     WORK_ENCODER_CLIP = 26,      // mimi_encode_clip: a voice clip at its own rate, in front of k_resample.  Shares WORK_CONVERT_OUT's storage (see above)
     WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words, then what dsp_scratch (dsp_spec.h) plans for each row's stages
-    WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin
+    WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin; join_rows_device: the parts, then the joined row
+    WORK_JOINED = 31,            // generate_joined: the text's joined row, sized before the first group runs and kept until the egress has read it
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -104,6 +106,7 @@ struct Model {
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
+    RowRing<JoinRow> join_ring;     // k_join's (join_launch, runtime.cpp)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
@@ -321,6 +324,8 @@ struct Delivery {
     ptts_result* res = nullptr;   // nullptr: decoded but not delivered (cancelled, failed)
     int nf = 0, eos = -1;
     bool filled = false;          // res already holds a buffer with every sample (streamed): no allocation, no copy
+    int64_t n24 = -1;             // the row's samples at 24 kHz where they are not nf frames' worth (generate_joined's joined row); -1: nf * spf
+    int64_t samples(int64_t spf) const { return n24 >= 0 ? n24 : (int64_t)nf * spf; }
 };
 // before the decode: result buffers into the results (PCM16 or f32), and the device PcmRow table for mimi_range's direct store (host_rows:
 // page-locked, g.size() entries, uploaded on s into dev_rows).  With it the decoder's last kernel stores every utterance's samples straight
@@ -385,6 +390,15 @@ Model* model_share(Model& base);   // another engine over base's weight arena (b
 Model* model_replicate(Model& base, int device);   // the model on another GPU of this process: own arena, copied from base's by hipMemcpyPeer
 void generate(Model& m, const ptts_request* reqs, int n, ptts_result* res);
 std::string request_error(const Desc& d, const ptts_request& q);   // empty: the request is well formed
+// Joined synthesis (join.h has the rule; include/ptts.h ptts_generate_joined): the requests as generate() runs them, in text order; each
+// group's decoded rows go through k_join into one device row for the text (Chunk::deliver, behind the fault check), then one DspJob over that
+// row and the egress of one row into *out.  parts: [n] or null.  Throws for a refusal (nothing launched) and for a failed chunk
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, ptts_result* out, ptts_join_part* parts);
+// k_join over a list of rows on s, one launch per RowRing::kRows rows
+void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
+// ptts_join_rows: the parts packed into one device buffer with the joined row behind them, uploaded, join_launch, the joined row back, one wait.
+// Takes Model::mu.  The lengths are planned (join_plan) and out holds the joined length
+void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
 
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)

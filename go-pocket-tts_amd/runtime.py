@@ -99,6 +99,25 @@ class LimiterOpts(C.Structure):   # ptts_limiter_opts
                          float(release_ms), float(drive_db))
 
 
+class JoinOpts(C.Structure):   # ptts_join_opts
+    """How a text's parts become one utterance (ptts_join_opts): gap_ms of silence between consecutive parts or crossfade_ms of overlap (each
+    0 .. 2000, not both), and -- for Model.generate_joined -- the chain (dsp: a DspOpts; loudness in 0.01 LUFS), run once over the joined audio,
+    and its egress (pcm_format, sample_rate).  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("pcm_format", C.c_int32), ("sample_rate", C.c_int32), ("loudness", C.c_int32), ("dsp", C.POINTER(DspOpts)),
+                ("gap_ms", C.c_double), ("crossfade_ms", C.c_double)]
+
+    def __init__(self, gap_ms: float = 0.0, crossfade_ms: float = 0.0, pcm_format: int = 0, sample_rate: int = 0, loudness: int = 0,
+                 dsp: Optional[DspOpts] = None, size: Optional[int] = None):
+        super().__init__(C.sizeof(JoinOpts) if size is None else int(size), int(pcm_format), int(sample_rate), int(loudness),
+                         C.pointer(dsp) if dsp is not None else None, float(gap_ms), float(crossfade_ms))
+        self._dsp = dsp   # (borrowed by the struct: kept alive with it)
+
+
+class JoinPart(C.Structure):   # ptts_join_part: one chunk of a joined call, offset and n_samples at 24 kHz in the joined audio
+    _fields_ = [("offset", C.c_int64), ("n_samples", C.c_int64), ("n_frames", C.c_int32), ("eos_step", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class EqSection(C.Structure):   # ptts_eq_section
     _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("freq_hz", C.c_double), ("gain_db", C.c_double), ("q", C.c_double)]
 
@@ -163,6 +182,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
     "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
+    "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -273,6 +293,11 @@ def lib():
         L.ptts_dsp_ext_set_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterOpts)]
         L.ptts_limit_apply.argtypes = [C.POINTER(LimiterOpts), _FP, C.c_int64]
         L.ptts_limit_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(LimiterOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        L.ptts_join_length.restype = C.c_int64
+        L.ptts_join_length.argtypes = [_IP, C.c_int32, C.POINTER(JoinOpts), _IP]
+        L.ptts_join.argtypes = [C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
+        L.ptts_join_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
+        L.ptts_generate_joined.argtypes = [C.c_void_p, C.POINTER(_Request), C.c_int32, C.POINTER(JoinOpts), C.POINTER(_Result), C.POINTER(JoinPart)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -433,6 +458,15 @@ class GenerateResult:
     n_frames: int
     eos_step: int
     latents: Optional[np.ndarray] = None
+
+
+@dataclass
+class JoinedResult:
+    """One joined call's result: the whole text's audio in the join options' egress format; n_frames summed over the chunks; parts: a JoinPart per
+    chunk (offset and n_samples at 24 kHz in the joined audio, in front of the egress; n_frames; eos_step; status)."""
+    pcm: np.ndarray
+    n_frames: int
+    parts: list
 
 
 @dataclass
@@ -745,6 +779,14 @@ class Model:
         """Test hook (libptts_hooks.so ptts_debug_loudness_energies): the rows' 480-sample K-weighted energies as the device kernels compute them."""
         return loudness_energies(x, self)
 
+    def join_rows(self, parts, join: Optional[JoinOpts] = None) -> np.ndarray:
+        """ptts_join_rows: join() on the device, by the kernel generate_joined runs: one upload, k_join, one download."""
+        rows, n, pp, ns = _join_in(parts)
+        o = join if join is not None else JoinOpts()
+        out = np.empty(max(join_length(ns[:n], o), 1), np.float32)
+        _check(lib().ptts_join_rows(self.h, pp, _ip(ns), n, C.byref(o), _fp(out)))
+        return out[:join_length(ns[:n], o)]
+
     def pcm_encode(self, x, pcm_format: int) -> np.ndarray:
         """ptts_pcm_encode: the device egress conversion of 24 kHz f32 samples into PCM_F32 / PCM_S16 / PCM_ULAW / PCM_ALAW."""
         x = _f32(x).reshape(-1)
@@ -891,6 +933,37 @@ class Model:
                 for i in range(n):
                     lib().ptts_free_result(C.byref(ress[i]))
         return out
+
+
+    def generate_joined(self, token_lists: Sequence[Sequence[int]], cfgs: Sequence[RuntimeGenerateConfig], join: Optional[JoinOpts] = None) -> JoinedResult:
+        """ptts_generate_joined: the chunks of one text, generated as generate_batch generates them, joined on the device (gap or crossfade), the
+        chain of `join` run once over the joined audio, one egress.  The cfgs carry no post-processing, rate or format of their own.  A failed call
+        raises PttsError with the chunks' records in its `parts`."""
+        n = len(token_lists)
+        reqs = (_Request * max(n, 1))()
+        parts = (JoinPart * max(n, 1))()
+        res = _Result()
+        keep = []
+        for i, (toks, cfg) in enumerate(zip(token_lists, cfgs)):
+            self._fill_request(reqs[i], toks, cfg, keep)
+        o = join if join is not None else JoinOpts()
+        rc = lib().ptts_generate_joined(self.h, reqs, n, C.byref(o), C.byref(res), parts)
+        records = [JoinPart(p.offset, p.n_samples, p.n_frames, p.eos_step, p.status, 0) for p in parts[:n]]
+        try:
+            _check(rc)
+        except PttsError as e:
+            lib().ptts_free_result(C.byref(res))
+            e.parts = records
+            raise
+        fmt = int(o.pcm_format)
+        field = {PCM_F32: "pcm", PCM_S16: "pcm16"}.get(fmt, "pcm8")
+        addr = C.cast(getattr(res, field), C.c_void_p).value
+        if res.n_samples and addr:
+            pcm = np.asarray(_OwnedBuffer(addr, int(res.n_samples), _PCM_DTYPES[fmt]))   # zero-copy, back to the pool on collection
+        else:
+            lib().ptts_free_result(C.byref(res))
+            pcm = np.zeros(0, _PCM_DTYPES[fmt])
+        return JoinedResult(pcm, int(res.n_frames), records)
 
 
 class DeviceVoice:
@@ -1622,6 +1695,34 @@ class Dispatcher:
 
 
 # ---- text front end (internal/text/prepare.go) ---------------------------------------------------------
+def _join_in(parts):
+    """A list of arrays as the parts of a join: (rows, n, their pointer array, their lengths as int64)."""
+    rows = [_f32(r).reshape(-1) for r in parts]
+    return rows, len(rows), _row_ptrs(rows), np.array([r.size for r in rows] or [0], np.int64)
+
+
+def join_length(lengths, join: Optional[JoinOpts] = None, offsets: bool = False):
+    """ptts_join_length: the joined length of parts of these lengths at 24 kHz (offsets: and where each part's first sample lies).  Host."""
+    ns = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    offs = np.zeros(max(ns.size, 1), np.int64)
+    o = join if join is not None else JoinOpts()
+    total = int(lib().ptts_join_length(_ip(ns) if ns.size else None, ns.size, C.byref(o), _ip(offs)))
+    if total < 0:
+        _check(-total)
+    return (total, offs[:ns.size]) if offsets else total
+
+
+def join(parts, join: Optional[JoinOpts] = None) -> np.ndarray:
+    """ptts_join: the parts (mono f32 at 24 kHz, in order) as one utterance, with join.gap_ms of silence or join.crossfade_ms of overlap at the
+    seams.  Host: the statement of what Model.join_rows and Model.generate_joined compute."""
+    rows, n, pp, ns = _join_in(parts)
+    o = join if join is not None else JoinOpts()
+    total = join_length(ns[:n], o)
+    out = np.empty(max(total, 1), np.float32)
+    _check(lib().ptts_join(pp, _ip(ns), n, C.byref(o), _fp(out)))
+    return out[:total]
+
+
 def dsp_apply(samples, normalize: bool = False, dc_block: bool = False, fade_in_ms: float = 0.0, fade_out_ms: float = 0.0) -> np.ndarray:
     """audio.PeakNormalize / DCBlock / FadeIn / FadeOut in the CLI's order (dsp.go:12-78, synth.go:361-390); returns a new array."""
     out = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
@@ -2086,3 +2187,15 @@ class Service:
         """Service.Synthesize (service.go:107-153): the chunks' PCM, concatenated."""
         parts = [r.pcm for _, r in self.synthesize_chunks(text, **voice)]
         return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+
+    def synthesize_joined(self, text: str, join: Optional[JoinOpts] = None, **voice) -> JoinedResult:
+        """Service.Synthesize with the join, the post-processing over the whole text (cmd/pockettts/synth.go:361-390) and the egress on the
+        device, in one call (Model.generate_joined): one result for the text, parts[i] says where chunk i lies in it.  Joined requests do not
+        go through a dispatcher, which deals single requests."""
+        if self.dispatcher is not None:
+            raise PttsError(PTTS_EINVAL, "synthesize_joined: a service with a dispatcher deals single requests; joined calls go to the model")
+        try:
+            chunks = prepare_chunks(text, self.encode, MAX_TOKENS_PER_CHUNK, self.model.info.frame_rate)
+        except PttsError as e:
+            raise PttsError(e.code, f"no tokens produced from input: {e}") from None   # service.go:124-126
+        return self.model.generate_joined([c.token_ids for c in chunks], [self.generate_config(c, **voice) for c in chunks], join)

@@ -124,7 +124,8 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * rounded to f32 where ptts_dsp_apply rounds it.  Normalise and the fades give ptts_dsp_apply's bits; the DC block is the same float64
  * recurrence evaluated as a blocked scan and agrees with it to one f32 step at the row's peak.  It is per request: the reference's CLI
  * runs the chain over a whole text's concatenated chunks (cmd/pockettts/synth.go:361-390); a host that wants that for a multi-chunk
- * text keeps using ptts_dsp_apply, or ptts_dsp_rows, on the concatenation.
+ * text keeps using ptts_dsp_apply, or ptts_dsp_rows, on the concatenation -- or has ptts_generate_joined (below) join the chunks and run the
+ * chain once over the whole text on the device.
  *
  * The equaliser (`eq`, a handle of ptts_eq_create below: a cascade of one to four biquad sections chosen by the caller) sits behind the DC
  * block and in front of the fades.  The whole order of a request's chain: the loudness or normalise gain -> DC block -> equaliser -> fade in
@@ -293,7 +294,7 @@ int  ptts_loudness(const float* samples, int64_t n, double* lufs);
 int  ptts_loudness_normalize(float* samples, int64_t n, double target_lufs, double* measured);
 /* The same on the device, by the kernels a request's `loudness` runs, shaped like ptts_dsp_rows: rows of host samples at 24 kHz (in[i]: n[i]
  * floats, any length >= 0), one launch sequence for all rows.  lufs / measured: [rows] (measured optional); out[i]: n[i] floats, in[i] == out[i]
- * allowed.  A host that wants one loudness over a text's chunks calls these on the concatenation. */
+ * allowed.  A host that wants one loudness over a text's chunks calls these on the concatenation, or ptts_generate_joined with `loudness`. */
 int  ptts_loudness_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double* lufs);
 int  ptts_loudness_normalize_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, double target_lufs, float* const* out,
                                   double* measured);
@@ -439,6 +440,60 @@ typedef struct ptts_limiter_opts {
 int  ptts_dsp_ext_set_limiter(ptts_dsp_ext* e, const ptts_limiter_opts* l);
 int  ptts_limit_apply(const ptts_limiter_opts* l, float* samples, int64_t n);
 int  ptts_limit_rows(ptts_model* m, const ptts_limiter_opts* const* l, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
+
+/* Joined synthesis: a text's chunks as ONE utterance.  The reference's Service.Synthesize appends the chunks' PCM
+ * (internal/tts/service.go:107-153) and its CLI runs the post-processing once over the concatenation (cmd/pockettts/synth.go:361-390); the
+ * request's own `dsp`, `loudness` and egress above work per request.  Here the join, the chain over the whole text and the egress stay on the
+ * device, and one result comes back.
+ *
+ * The join.  Parts x_0 .. x_(R-1) of n_i samples at 24 kHz, in order, R from 1 to 4096, n_i >= 0, the joined length below 2^31.  With
+ *     G = (int64)(gap_ms / 1000 * 24000),   K = (int64)(crossfade_ms / 1000 * 24000)
+ * (the expression of ptts_dsp_apply's fades; each a finite value from 0 to 2000 ms, at most one of the two above 0):
+ *   - gap: G zeros between consecutive parts, none in front of the first part or behind the last;
+ *   - crossfade: at the seam between parts i and i+1, K_i = min(K, n_i / 2, n_(i+1) / 2) (integer divisions: two seams never touch the same
+ *     sample), the last K_i samples of part i overlap the first K_i of part i+1 = b, and for j in [0, K_i)
+ *         out = a[n_i - K_i + j] * ((float)(K_i - 1 - j) / (float)K_i) + b[j] * ((float)j / (float)K_i)
+ *     -- two f32 divisions, two f32 products, one f32 sum, each rounded once, nothing fused: ptts_dsp_apply's fade out of the tail plus its
+ *     fade in of the head;
+ *   - every other sample is copied bit for bit (NaN and infinity pass);
+ *   - offset_0 = 0, offset_(i+1) = offset_i + n_i + G - K_i is where a part's first sample lies; the joined length is offset_(R-1) + n_(R-1).
+ * ptts_join_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field or a broken limit is
+ * PTTS_EINVAL and the error names it.
+ * ptts_join_length: the joined length of parts of n[0 .. rows) samples, or -PTTS_EINVAL; offsets (optional, [rows]) receives the part offsets.
+ *     Only size, gap_ms and crossfade_ms of the options are read.  Host.
+ * ptts_join: the join of in[0 .. rows) into out[0, ptts_join_length): the statement of the result.  Host.
+ * ptts_join_rows: the same on the device, by the kernel ptts_generate_joined runs (k_join), shaped like ptts_dsp_rows: one upload, one launch
+ *     per 256 parts, one download.  It gives ptts_join's bits.
+ *
+ * ptts_generate_joined: the n requests run exactly as ptts_generate runs them (the same admission checks, groups of max_batch, step callbacks
+ * and cancel flags), in text order; every group's decoded audio is joined on the device into one row for the text; after the last group the
+ * chain of `dsp` and `loudness` runs ONCE over the joined audio (every stage as documented for ptts_request.dsp: the host statement is the
+ * host chain on ptts_join of the chunks' audio) and the egress (sample_rate, pcm_format) delivers ONE result: out->n_samples counts samples of
+ * the joined audio at the output rate, out->n_frames is the sum of the chunks' frames, out->eos_step is -1.  parts (optional, [n]) receives
+ * each chunk's offset and length in the joined 24 kHz audio, its frame count, EOS step and status: captions and progress.
+ * PTTS_EINVAL, nothing launched, naming the field: a request with a non-zero dsp, loudness, sample_rate, pcm_format, pcm_callback or
+ * want_latents (these belong in the join options); requests that differ in their resolved lsd_steps (the groups would leave text order); n
+ * outside 1 .. 4096; step budgets that allow 2^31 samples or more; and everything ptts_generate refuses, in its own words.  A chunk that is
+ * cancelled or runs past the decoder's reach fails the whole call with that chunk's code: *out is zeroed and parts[i].status names the chunk
+ * (chunks of later groups have not run: status 0, no frames). */
+typedef struct ptts_join_opts {
+    uint32_t size;          /* sizeof(ptts_join_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  pcm_format;    /* PTTS_PCM_*: the egress of the joined audio */
+    int32_t  sample_rate;   /* 0: 24000; as ptts_request.sample_rate */
+    int32_t  loudness;      /* 0: off; as ptts_request.loudness, over the joined audio */
+    const ptts_dsp_opts* dsp;   /* NULL, or the chain, run ONCE over the joined audio (borrowed for the call) */
+    double   gap_ms;        /* 0 .. 2000: silence between consecutive parts */
+    double   crossfade_ms;  /* 0 .. 2000: overlap of consecutive parts; not together with gap_ms */
+} ptts_join_opts;
+typedef struct ptts_join_part {
+    int64_t offset, n_samples;   /* at 24 kHz, in the joined audio (in front of the egress) */
+    int32_t n_frames, eos_step, status, reserved;
+} ptts_join_part;
+int64_t ptts_join_length(const int64_t* n, int32_t rows, const ptts_join_opts* opts, int64_t* offsets /* optional [rows] */);
+int  ptts_join(const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, float* out);
+int  ptts_join_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, float* out);
+int  ptts_generate_joined(ptts_model* m, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, ptts_result* out,
+                          ptts_join_part* parts /* [n], optional */);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -691,7 +746,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_eq_section, ptts_eq_design, ptts_eq_response, ptts_eq_create, ptts_eq_free, ptts_eq_apply, ptts_eq_rows; ptts_dsp_opts.ext (over
  * reserved[2..3], likewise) with ptts_dsp_ext_opts, ptts_dsp_ext_create, ptts_dsp_ext_free, ptts_true_peak, ptts_true_peak_limit,
  * ptts_true_peak_rows; ptts_compressor_opts with ptts_dsp_ext_set_compressor (the handle is the extension point: no struct grows),
- * ptts_compress_gain, ptts_compress_apply, ptts_compress_rows */
+ * ptts_compress_gain, ptts_compress_apply, ptts_compress_rows; ptts_limiter_opts with ptts_dsp_ext_set_limiter, ptts_limit_apply,
+ * ptts_limit_rows; the new structs ptts_join_opts and ptts_join_part, which change no existing one, with ptts_join_length, ptts_join, ptts_join_rows,
+ * ptts_generate_joined */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
