@@ -14,7 +14,7 @@ namespace ptts {
 //   2. the burst -- every wave requests ALL the K rows and ALL the V rows it owns (up to 16 + 16 wave-instructions of
 //      1 KiB: 8 keys x 128 B in bf16, 4 keys x 256 B in f32) -- is issued BEFORE the step's own q/k/v are touched: the rows
 //      already in the cache do not depend on them.  The loads are unconditional (slots past the end re-read the last
-//      valid row: finite data, zero weight);
+//      valid row: finite data, zero weight; at offset 0 there is no such row and the block leaves early with out = v);
 //   3. while the burst is in flight: q and k of this step are rotated by the RoPE table row at the cache offset
 //      (rope.go:81-105; position = offset BEFORE the append, flow_transformer.go:340-347), k and v are appended to the
 //      cache at that offset and also left in LDS in cache format -- the key slot at the offset takes them from there;
@@ -123,6 +123,12 @@ __global__ __launch_bounds__(256) void k_attn_step(const int32_t* p_seg_len, con
         }
     }
     __syncthreads();
+    if (pos == 0) {   // uniform per block.  The only key is this step's own: weight 1, out = v as the cache now holds it.  Every slot of the burst re-read own
+                      // row 0, which nothing wrote before this step (a reset slot keeps the bytes of its last tenant, NaN padding of a voice state included,
+                      // and 0 * NaN is NaN): none of it may reach the sums.  From offset 1 on the clamp row pos - 1 is a key of this head: finite.
+        if (tid < 64) outp[tid] = KVBF16 ? __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(own_v)[tid] << 16) : reinterpret_cast<const float*>(own_v)[tid];
+        return;
+    }
     const int nk = pos + 1;
     {   // the key slot at the offset takes this step's k, v from LDS (one lane group of one wave; wave-uniform branches)
         const int g_p = pos / KPI, i_p = g_p >> 2, w_p = g_p & 3, kq_p = pos % KPI;
@@ -234,11 +240,15 @@ int attn_step_rounds(int keys, bool kv_bf16) {
     return std::max(1, std::min(ATT_NI, (keys + kpw - 1) / kpw));
 }
 
+int attn_step_launch_rounds(const AttnArgs& a) {
+    const int keys = a.keys_now > 0 ? std::min(a.keys_now, a.max_keys) : a.max_keys;   // unknown: the whole cache
+    return attn_step_rounds(keys, a.kv_bf16 != 0);
+}
+
 void launch_attn_step(const AttnArgs& a, hipStream_t stream) {
     note_launch("k_attn_step");
     dim3 grid(a.heads, a.rows);
-    const int keys = a.keys_now > 0 ? std::min(a.keys_now, a.max_keys) : a.max_keys;   // unknown: the whole cache
-    const int ni = attn_step_rounds(keys, a.kv_bf16 != 0);
+    const int ni = attn_step_launch_rounds(a);
     if (a.kv_bf16) launch_ni<true, 1>(a, ni, grid, stream);
     else launch_ni<false, 1>(a, ni, grid, stream);
 }

@@ -499,6 +499,88 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     });
 }
 
+// The step attention on host operands: ONE launch_attention call with the AttnArgs of the AR step (runtime.cpp step_core).  k_attn_step bounds none of its
+// loads by a buffer size -- cache rows up to seg_len, prefix rows up to pre_len, the RoPE row at seg_len -- so every one of those is checked against the
+// buffers allocated here before anything is uploaded; there is no way to ask for a launch without the checks.
+int ptts_debug_attn_step(const ptts_attn_step_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_attn_step: null argument");
+        const ptts_attn_step_args& t = *pa;
+        if (!t.qkv || !t.cos_t || !t.sin_t || !t.seg_len || !t.active || !t.pre_len || !t.voice_of_row || !t.k || !t.v || !t.out || (t.kv_bf16 != 0 && t.kv_bf16 != 1) ||
+            t.rows < 1 || t.rows > 1024 || t.heads < 1 || t.heads > 64 || t.cap < 1 || t.cap > 4096 || t.layers < 1 || t.layers > 64 || t.keys_now < 0 || t.n_pre < 0 ||
+            t.n_pre > 4)
+            throw Error(PTTS_EINVAL, "ptts_debug_attn_step: bad arguments");
+        const int rows = t.rows, heads = t.heads, cap = t.cap, D = heads * 64, es = t.kv_bf16 ? 2 : 4;
+        if (t.layer < 0 || t.layer >= t.layers) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: layer %d of %d", t.layer, t.layers));
+        if (t.qkv_ld < 3 * (int64_t)D || t.out_ld < D) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: qkv_ld %lld / out_ld %lld below 3 d_model / d_model (%d)", (long long)t.qkv_ld, (long long)t.out_ld, D));
+        for (int i = 0; i < t.n_pre; i++)
+            if (!t.pre_k[i] || !t.pre_v[i] || t.pre_rows[i] < 1 || t.pre_rows[i] > cap) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: prefix buffer %d is null, empty or longer than the cache", i));
+        for (int r = 0; r < rows; r++) {
+            const int pos = t.seg_len[r], pre = t.pre_len[r], vo = t.voice_of_row[r];
+            if (pos < 0 || pos >= cap) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d at offset %d, the cache holds %d", r, pos, cap));
+            if (vo < -1 || vo >= t.n_pre) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d names prefix buffer %d of %d", r, vo, t.n_pre));
+            if (pre < 0 || pre > pos) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d: prefix of %d keys at offset %d", r, pre, pos));
+            if (pre != 0 && (vo < 0 || pre != t.pre_rows[vo])) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d: prefix of %d keys is not the length of the buffer it names", r, pre));
+            if (t.keys_now > 0 && t.active[r] && pos + 1 > t.keys_now) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d at offset %d is beyond keys_now %d", r, pos, t.keys_now));
+        }
+        require_device();
+        const size_t qkv_bytes = (size_t)rows * t.qkv_ld * 4, tab_bytes = (size_t)cap * 32 * 4, out_bytes = (size_t)rows * t.out_ld * 4, kv_bytes = (size_t)rows * heads * cap * 64 * es;
+        Tmp dQ(qkv_bytes), dCos(tab_bytes), dSin(tab_bytes), dLen((size_t)rows * 4), dAct((size_t)rows * 4), dPl((size_t)rows * 4), dPk((size_t)rows * sizeof(void*)),
+            dPv((size_t)rows * sizeof(void*)), dK(kv_bytes), dV(kv_bytes), dO(out_bytes);
+        std::vector<std::unique_ptr<Tmp>> pre;   // [2 i]: keys of buffer i, [2 i + 1]: values
+        for (int i = 0; i < t.n_pre; i++) {
+            const size_t n = (size_t)t.layers * heads * t.pre_rows[i] * 64 * es;
+            pre.emplace_back(new Tmp(n)); up(pre.back()->p, t.pre_k[i], n);
+            pre.emplace_back(new Tmp(n)); up(pre.back()->p, t.pre_v[i], n);
+        }
+        std::vector<const void*> hk((size_t)rows, nullptr), hv((size_t)rows, nullptr);
+        for (int r = 0; r < rows; r++)
+            if (t.voice_of_row[r] >= 0) { hk[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r]]->p; hv[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r] + 1]->p; }
+        up(dQ.p, t.qkv, qkv_bytes); up(dCos.p, t.cos_t, tab_bytes); up(dSin.p, t.sin_t, tab_bytes);
+        up(dLen.p, t.seg_len, (size_t)rows * 4); up(dAct.p, t.active, (size_t)rows * 4); up(dPl.p, t.pre_len, (size_t)rows * 4);
+        up(dPk.p, hk.data(), (size_t)rows * sizeof(void*)); up(dPv.p, hv.data(), (size_t)rows * sizeof(void*));
+        up(dK.p, t.k, kv_bytes); up(dV.p, t.v, kv_bytes);
+        PTTS_HIP(hipMemset(dO.p, 0xff, out_bytes));
+        AttnArgs a;   // as step_core fills them
+        a.k = dK.p; a.v = dV.p; a.kv_bf16 = t.kv_bf16;
+        a.k_seg_stride = (int64_t)heads * cap * 64; a.k_head_stride = (int64_t)cap * 64; a.k_row_stride = 64;
+        a.seg_len = dLen.as<int32_t>(); a.active = dAct.as<int32_t>();
+        a.context = -1;
+        a.out = dO.as<float>(); a.out_ld = t.out_ld;
+        a.rows = rows; a.heads = heads; a.max_keys = cap;
+        a.keys_now = t.keys_now;
+        a.fused_step = 1; a.qkv = dQ.as<float>(); a.qkv_ld = t.qkv_ld; a.d_model = D;
+        a.cos_t = dCos.as<float>(); a.sin_t = dSin.as<float>(); a.cap = cap;
+        a.pre_k = dPk.as<const void*>(); a.pre_v = dPv.as<const void*>(); a.pre_len = dPl.as<int32_t>(); a.layer = t.layer;
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        g_launch_census = &census;
+        try { launch_attention(a, nullptr); } catch (...) { g_launch_census = census_before; throw; }
+        g_launch_census = census_before;
+        if (census_before)   // (a caller's own census sees the launch too: a refusal leaves it empty)
+            for (const auto& kv : census) (*census_before)[kv.first] += kv.second;
+        PTTS_HIP(hipDeviceSynchronize());
+        const bool step = std::string(g_last_attn_kernel) == "k_attn_step";
+        if (t.kernel && t.kernel_cap > 0) {
+            const size_t n = std::min<size_t>(std::strlen(g_last_attn_kernel), (size_t)t.kernel_cap - 1);
+            std::memcpy(t.kernel, g_last_attn_kernel, n);
+            t.kernel[n] = 0;
+        }
+        if (t.info) {
+            int64_t all = 0;
+            for (const auto& kv : census) all += kv.second;
+            t.info[0] = step ? attn_step_launch_rounds(a) : 0;
+            t.info[1] = (int32_t)all; t.info[2] = (int32_t)census["k_attn_step"]; t.info[3] = (int32_t)census["k_attention"];
+        }
+        down(t.out, dO.p, out_bytes); down(t.k, dK.p, kv_bytes); down(t.v, dV.p, kv_bytes);
+    });
+}
+
+int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per_round) {
+    if (keys_per_round) *keys_per_round = attn_step_keys_per_round(kv_bf16 != 0);
+    return attn_step_rounds(keys, kv_bf16 != 0);
+}
+
 // The many-row GEMMs on host operands: ONE launch of a named kernel.  These kernels clamp addresses instead of bounding their loads, so every element a row's
 // read or store can touch is checked against the caller's buffer sizes here, before anything is uploaded.
 int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {

@@ -227,6 +227,7 @@ bool attn_step_supported(const AttnArgs& a);
 void launch_attn_step(const AttnArgs& a, hipStream_t stream);
 int attn_step_keys_per_round(bool kv_bf16);       // keys one load round of the block covers (32 bf16 / 16 f32)
 int attn_step_rounds(int keys, bool kv_bf16);     // rounds launch_attn_step issues for a launch bounded by `keys` (1..16)
+int attn_step_launch_rounds(const AttnArgs& a);   // ... for this launch: bounded by keys_now when the host knows it, by max_keys otherwise
 bool attn_window_supported(const AttnArgs& a);   // Mimi sliding-window attention on the f32 matrix cores
 void launch_attn_window(const AttnArgs& a, hipStream_t stream);
 

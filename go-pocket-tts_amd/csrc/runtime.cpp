@@ -343,6 +343,10 @@ void batch_reset(Batch& b) {
     const int B = b.B;
     launch_fill_i32(b.st.kv_len, 0, B, s);
     b.kv_bound = 0;
+    // the decoder runs every utterance of a batch over the longest one's frames, and its window attention gives the keys of later frames weight zero,
+    // not a skip (attn_window.hip: a 32-query tile spans two frames): frames no step of THIS run writes must hold finite data -- not fresh memory, not
+    // the NaN frames an earlier tenant of the slot may have left -- or 0 * NaN reaches the utterance's last frame
+    PTTS_HIP(hipMemsetAsync(b.latents.p, 0, (size_t)B * b.max_steps * b.m->d.ldim * sizeof(float), s));
     launch_fill_i32(b.st.active, 1, B, s);
     launch_fill_i32(b.st.step, 0, B, s);
     launch_fill_i32(b.st.countdown, -1, B, s);

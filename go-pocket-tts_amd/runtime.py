@@ -191,7 +191,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
-    "ptts_debug_gemm_rows",
+    "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds",
 ]
 
 
@@ -1358,6 +1358,63 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     H.ptts_debug_step_linear.argtypes = [C.POINTER(_StepLinearArgs)]
     _check(H.ptts_debug_step_linear(C.byref(a)))
     return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
+
+
+class _AttnStepArgs(C.Structure):   # ptts_attn_step_args
+    _fields_ = ([(n, C.c_int32) for n in ("kv_bf16", "heads", "rows", "layers", "layer", "cap", "keys_now", "n_pre")] +
+                [(n, C.c_int64) for n in ("qkv_ld", "out_ld", "kernel_cap")] +
+                [(n, _FP) for n in ("qkv", "cos_t", "sin_t")] +
+                [(n, C.POINTER(C.c_int32)) for n in ("seg_len", "active", "pre_len", "voice_of_row")] +
+                [("pre_k", C.c_void_p * 4), ("pre_v", C.c_void_p * 4), ("pre_rows", C.c_int32 * 4), ("k", C.c_void_p), ("v", C.c_void_p), ("out", _FP),
+                 ("kernel", C.c_char_p), ("info", C.POINTER(C.c_int32))])
+
+
+def debug_attn_step(qkv, cos, sin, seg_len, k, v, *, kv_bf16, heads, layers=1, layer=0, keys_now=0, active=None, pre_len=None, voice_of_row=None, pre_k=(),
+                    pre_v=(), out_ld=None):
+    """The step attention (csrc/attn_step.hip) on host operands (ptts_debug_attn_step, include/ptts_debug.h): one launch_attention call with the AR step's
+    arguments.  qkv [rows, qkv_ld]; cos / sin [cap, 32]; k, v [rows, heads, cap, 64] in the cache format (uint16 bf16 bits, or 4-byte elements); pre_k / pre_v:
+    up to 4 prefix buffers [layers, heads, len, 64] in the same format, named per row by voice_of_row (-1: none).  Returns a dict: "out" ([rows, out_ld], NaN
+    where nothing was stored), "k" / "v" (the caches after the launch, the inputs are not modified), "kernel" (launch_attention's choice), "rounds" (load
+    rounds of k_attn_step, 0 for another kernel), "launches", "k_attn_step", "k_attention" (the census of the call)."""
+    qkv, cos, sin = _f32(qkv), _f32(cos), _f32(sin)
+    rows, qkv_ld = qkv.shape
+    cap = cos.shape[0]
+    es = 2 if kv_bf16 else 4
+    i32 = lambda a, fill: np.ascontiguousarray(np.full(rows, fill, np.int32) if a is None else np.asarray(a, np.int32))   # noqa: E731
+    seg_len, active, pre_len, voice_of_row = i32(seg_len, 0), i32(active, 1), i32(pre_len, 0), i32(voice_of_row, -1)
+    k, v = np.array(k, order="C", copy=True), np.array(v, order="C", copy=True)
+    pre_k, pre_v = [np.ascontiguousarray(p) for p in pre_k], [np.ascontiguousarray(p) for p in pre_v]
+    if (cos.shape != (cap, 32) or sin.shape != (cap, 32) or any(a.shape != (rows,) for a in (seg_len, active, pre_len, voice_of_row)) or len(pre_k) != len(pre_v) or
+            len(pre_k) > 4 or any(a.itemsize != es or a.shape != (rows, heads, cap, 64) for a in (k, v)) or
+            any(a.itemsize != es or a.ndim != 4 or a.shape[:2] != (layers, heads) or a.shape[3] != 64 or a.shape != b.shape for a, b in zip(pre_k, pre_v))):
+        raise PttsError(PTTS_EINVAL, "debug_attn_step: operand shapes do not fit (include/ptts_debug.h ptts_attn_step_args)")
+    out_ld = heads * 64 if out_ld is None else int(out_ld)
+    out = np.empty((rows, max(out_ld, 0)), np.float32)
+    name = C.create_string_buffer(64)
+    info = (C.c_int32 * 4)()
+    a = _AttnStepArgs()
+    a.kv_bf16, a.heads, a.rows, a.layers, a.layer, a.cap, a.keys_now, a.n_pre = (1 if kv_bf16 else 0), int(heads), rows, int(layers), int(layer), cap, int(keys_now), len(pre_k)
+    a.qkv_ld, a.out_ld, a.kernel_cap = qkv_ld, out_ld, 64
+    a.qkv, a.cos_t, a.sin_t = _fp(qkv), _fp(cos), _fp(sin)
+    a.seg_len, a.active, a.pre_len, a.voice_of_row = [C.cast(x.ctypes.data, C.POINTER(C.c_int32)) for x in (seg_len, active, pre_len, voice_of_row)]
+    for i, (pk, pv) in enumerate(zip(pre_k, pre_v)):
+        a.pre_k[i], a.pre_v[i], a.pre_rows[i] = pk.ctypes.data, pv.ctypes.data, pk.shape[2]
+    a.k, a.v, a.out = k.ctypes.data, v.ctypes.data, _fp(out)
+    a.kernel = C.cast(name, C.c_char_p)
+    a.info = C.cast(info, C.POINTER(C.c_int32))
+    H = hooks()
+    H.ptts_debug_attn_step.argtypes = [C.POINTER(_AttnStepArgs)]
+    _check(H.ptts_debug_attn_step(C.byref(a)))
+    return {"out": out, "k": k, "v": v, "kernel": name.value.decode(), "rounds": int(info[0]), "launches": int(info[1]), "k_attn_step": int(info[2]),
+            "k_attention": int(info[3])}
+
+
+def attn_step_rounds(keys: int, kv_bf16: bool):
+    """(load rounds of k_attn_step for a launch bounded by `keys`, keys per round): attn_step_rounds / attn_step_keys_per_round of csrc/attn_step.hip.  No GPU."""
+    H = hooks()
+    H.ptts_debug_attn_step_rounds.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    kpr = C.c_int32()
+    return int(H.ptts_debug_attn_step_rounds(int(keys), 1 if kv_bf16 else 0, C.byref(kpr))), int(kpr.value)
 
 
 class _GemmRowsArgs(C.Structure):   # ptts_gemm_rows_args

@@ -78,6 +78,36 @@ typedef struct ptts_step_linear_args {
 } ptts_step_linear_args;
 int ptts_debug_step_linear(const ptts_step_linear_args* a);
 
+/* The step attention (csrc/attn_step.hip: k_attn_step, and k_attention behind it for caches beyond one burst) stand-alone: ONE launch_attention call with
+ * AttnArgs filled as the AR step fills them (runtime.cpp step_core: fused_step, context -1, d_model = heads * 64, max_keys = cap), on host operands.
+ *   qkv [rows][qkv_ld] (q | k | v, d_model each), cos_t / sin_t [cap][32], seg_len / active / pre_len / voice_of_row [rows];
+ *   pre_k / pre_v [n_pre <= 4]: prefix buffers [layers][heads][pre_rows[i]][64] in the cache format (bf16 bits or f32); voice_of_row[r] names the buffer
+ *   row r's prefix pointers are set to (-1: null pointers); the pre_k / pre_v / pre_len device arrays are always passed, as the step passes them;
+ *   k, v [rows][heads][cap][64]: the rows' own caches of `layer` as raw bytes in the cache format, uploaded, and returned whole after the launch;
+ *   out [rows][out_ld]: filled with 0xff bytes before the launch and returned whole.
+ * kernel (kernel_cap bytes) receives the name launch_attention picked; info [4]: the load rounds the launch issues (attn_step_launch_rounds; 0 when another
+ * kernel ran), all noted launches, k_attn_step launches, k_attention launches.
+ * PTTS_EINVAL with a message, before anything is uploaded or launched, unless (these keep every access inside the buffers above):
+ *   0 <= seg_len[r] < cap; pre_len[r] <= seg_len[r]; pre_len[r] is 0 or exactly pre_rows[voice_of_row[r]]; -1 <= voice_of_row[r] < n_pre;
+ *   keys_now == 0 or seg_len[r] + 1 <= keys_now for every active row; qkv_ld >= 3 * heads * 64; out_ld >= heads * 64; 0 <= layer < layers;
+ *   1 <= rows <= 1024, 1 <= heads <= 64, 1 <= cap <= 4096, 1 <= layers <= 64, pre_rows[i] >= 1. */
+typedef struct ptts_attn_step_args {
+    int32_t kv_bf16, heads, rows, layers, layer, cap, keys_now, n_pre;
+    int64_t qkv_ld, out_ld, kernel_cap;
+    const float *qkv, *cos_t, *sin_t;
+    const int32_t *seg_len, *active, *pre_len, *voice_of_row;
+    const void* pre_k[4];
+    const void* pre_v[4];
+    int32_t pre_rows[4];
+    void *k, *v;
+    float* out;
+    char* kernel;
+    int32_t* info;
+} ptts_attn_step_args;
+int ptts_debug_attn_step(const ptts_attn_step_args* a);
+/* attn_step_rounds / attn_step_keys_per_round of csrc/attn_step.hip (no GPU): the load rounds for a launch bounded by `keys`, the keys one round covers. */
+int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per_round);
+
 /* The many-row GEMMs (csrc/kernels.hip k_gemm, gemm2.hip, gemm3.hip, gemm_wres.hip, gemm5.hip) stand-alone: ONE launch of a named kernel on host operands.
  * C = epi(rope(aop(A) W^T + bias)) with kernels.h' RowMaps on A and C:
  *   A: a buffer of a_elems floats; row m starts at a_off + (m / a_rows_per_batch) a_batch_stride + (m % a_rows_per_batch) a_ld (a_rows_per_batch 0: a_off + m a_ld)
