@@ -6,6 +6,7 @@
 
 #include "capi_internal.h"
 #include "eq.h"
+#include "opts_check.h"
 
 using namespace ptts;
 using namespace ptts::capi;
@@ -1097,7 +1098,8 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
         const RowsCheck check{"dsp"};
         check.args(rows, !in || !n || !out);
         DspSpec spec;
-        const std::string e = dsp_resolve(opts, &spec);
+        std::string e = dsp_resolve(opts, &spec);
+        if (e.empty()) e = dsp_trim_refusal(spec);   // the output rows have the input's length
         if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
         for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i] || !out[i]);
         if (!spec.any()) {   // nothing switched on: a copy, no lock, no launch
@@ -1157,6 +1159,41 @@ int ptts_limit_rows(ptts_model* h, const ptts_limiter_opts* const* l, const floa
         spec.lim = lim_design(*l[i]);
         return std::string();
     });
+}
+
+// the device form of ptts_trim_apply on host rows: the launches of a joined call's trim; a row without one is copied on the host
+int ptts_trim_rows(ptts_model* h, const ptts_trim_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info) {
+    return guard([&] {
+        Model& m = model_of(h);
+        const RowsCheck check{"trim"};
+        check.args(rows, !t || !in || !n || !out || !info);
+        std::vector<TrimScan> designs((size_t)rows);
+        std::vector<const TrimScan*> design((size_t)rows, nullptr);
+        for (int i = 0; i < rows; i++) {
+            check.row(i, n[i], !in[i] || !out[i]);
+            if (n[i] >= kTrimMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: trim: row %d has %lld samples, a row must stay below 2^31", i, (long long)n[i]));
+            if (!t[i]) continue;
+            const std::string e = trim_opts_error(t[i]);
+            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
+            designs[(size_t)i] = trim_design(*t[i]);
+            design[(size_t)i] = &designs[(size_t)i];
+        }
+        if (rows > 0) trim_rows_device(m, design.data(), in, n, rows, out, info);
+    });
+}
+
+// the trim of a joined call's parts, attached to the handle (trim.cpp checks and designs it, and stays a file that builds alone)
+int ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t) {
+    DspExt v;   // (the design is made outside the registry's mutex)
+    if (t) {
+        const std::string err = trim_opts_error(t);
+        if (!err.empty()) return fail(err);
+        v.trim = true;
+        v.trm = trim_design(*t);
+    }
+    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.trim = v.trim; e->v.trm = v.trm; }))
+        return fail(strfmt("trim: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
+    return PTTS_OK;
 }
 
 // the device form of ptts_join on host rows: k_join, as ptts_generate_joined launches it

@@ -235,4 +235,69 @@ void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_
     PTTS_HIP(hipStreamSynchronize(s));
 }
 
+// ---- the trim (trim.hip; trim.h has the rule) ----
+
+const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const std::vector<const TrimScan*>& key, hipStream_t s) {
+    size_t tiles = 0;
+    for (const TrimRow& r : rows) tiles += (size_t)scan_tiles(std::max<int64_t>(r.n, 0));
+    const size_t info_bytes = (rows.size() * sizeof(ptts_trim_info) + 255) & ~(size_t)255;
+    char* scratch = m.work(WORK_TRIM_SCRATCH, info_bytes + std::max<size_t>(tiles, 1) * sizeof(TrimTile)).as<char>();
+    ptts_trim_info* info = reinterpret_cast<ptts_trim_info*>(scratch);
+    TrimTile* t = reinterpret_cast<TrimTile*>(scratch + info_bytes);
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (rows[i].n >= kTrimMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: trim: row %zu has %lld samples, a row must stay below 2^31", i, (long long)rows[i].n));
+        rows[i].info = info + i;
+        rows[i].tiles = t;
+        t += scan_tiles(std::max<int64_t>(rows[i].n, 0));
+    }
+    launch_tables(m.trim_ring, rows, key, kTrimMaxDesigns, same_bytes<TrimScan>, &TrimRow::design, "trim", s,
+                  [&](size_t, int k, const TrimRow* rows_dev, int max_tiles, const TrimScan* designs_dev) { launch_trim(rows_dev, k, max_tiles, designs_dev, s); });
+    return info;
+}
+
+void trim_rows_device(Model& m, const TrimScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    // the rows, then their trimmed forms; a row that stays on the host takes no bytes
+    std::vector<size_t> bytes((size_t)rows * 2);
+    std::unique_ptr<bool[]> skip(new bool[(size_t)rows * 2 + 1]);
+    for (int i = 0; i < rows; i++) {
+        const bool sk = !design[i] || n[i] <= 0;
+        skip[(size_t)i] = skip[(size_t)(rows + i)] = sk;
+        bytes[(size_t)i] = bytes[(size_t)(rows + i)] = sk ? 0 : (size_t)n[i] * sizeof(float);
+    }
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
+    std::vector<TrimRow> tr;
+    std::vector<const TrimScan*> key;
+    std::vector<int> row_of;
+    for (int i = 0; i < rows; i++) {
+        info[i] = ptts_trim_info{0, n[i], n[i], 0, 0, 0};
+        if (skip[(size_t)i]) {   // nothing to do on the device: a copy
+            if (n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            continue;
+        }
+        buf.upload(i, in[i], s);
+        TrimRow r{};
+        r.src = (const float*)buf.row(i);
+        r.dst = (float*)buf.row(rows + i);
+        r.n = n[i];
+        tr.push_back(r);
+        key.push_back(design[i]);
+        row_of.push_back(i);
+    }
+    if (tr.empty()) return;
+    const ptts_trim_info* info_dev = trim_launch(m, tr, key, s);
+    std::vector<ptts_trim_info> got(tr.size());
+    PTTS_HIP(hipMemcpyAsync(got.data(), info_dev, got.size() * sizeof(ptts_trim_info), hipMemcpyDeviceToHost, s));
+    PTTS_HIP(hipStreamSynchronize(s));   // the lengths decide what comes back
+    for (size_t k = 0; k < tr.size(); k++) {
+        const int i = row_of[k];
+        if (got[k].n_out < 0 || got[k].n_out > n[i]) throw Error(PTTS_EINVAL, "ptts-hip: internal: a trimmed row is longer than the row");
+        info[i] = got[k];
+        if (got[k].n_out > 0) PTTS_HIP(hipMemcpyAsync(out[i], tr[k].dst, (size_t)got[k].n_out * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
 }  // namespace ptts

@@ -21,6 +21,8 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->cmp = ext.cmp;
     out->limit = ext.limit;
     out->lim = ext.lim;
+    out->trim = ext.trim;
+    out->trm = ext.trm;
     return std::string();
 }
 

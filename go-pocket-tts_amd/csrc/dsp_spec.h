@@ -14,6 +14,7 @@ struct DspSpec {
     bool loud = false; double target_power = 0.0;      // measured (BS.1770) on the samples as the compressor leaves them; 10^((target LUFS + 0.691) / 10) is what its gain aims at
     bool compress = false; CmpScan cmp{};              // the first stage (compressor.h): everything above is measured and applied behind it
     bool limit = false; LimScan lim{};                 // the limiter (limiter.h): behind the fades, in front of the true-peak ceiling
+    bool trim = false; TrimScan trm{};                 // the trim of a joined call's parts (trim.h): no stage of the chain, neither rest() nor any() counts it
     bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };
@@ -50,6 +51,10 @@ inline DspScratch dsp_scratch(const DspSpec& sp, int64_t n, bool apply) {
 // or not a number, an eq or ext that is not a live handle (looked up by address, never read) -- and *out is not to be used.
 std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out);
 inline std::string dsp_opts_error(const ptts_dsp_opts& o) { DspSpec spec; return dsp_resolve(&o, &spec); }
+// Where a row's length is fixed before the decode (a request's own dsp, ptts_dsp_rows) a resolved spec with a trim is refused: the message, or empty
+inline std::string dsp_trim_refusal(const DspSpec& s) {
+    return s.trim ? std::string("dsp: ext: trim changes a row's length; it is served by ptts_generate_joined and ptts_trim_rows") : std::string();
+}
 // whether o switches anything on, without an error: what dsp_resolve's spec says with any(), except that an eq counts unseen (so a dead one is
 // active, and refused where the row is resolved) and an ext that is not live counts for nothing.  One registry look-up at the most: it is
 // asked per request before the decode and per streamed hand-over

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "limiter.h"
+#include "trim.h"
 
 namespace ptts {
 
@@ -396,6 +397,33 @@ struct JoinRow {
 static_assert(sizeof(JoinRow) == 48, "a turn of the join ring holds 256 of them");
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil((gap + n + 3) / kJoinTile) of a row (three more: the destination's 16-byte grid)
 void launch_join(const JoinRow* rows_dev, int n, int max_tiles, hipStream_t stream);
+
+// Silence control of the parts of a joined text (trim.hip, trim.h has the rule, trim.cpp the host statement): in front
+// of k_join, from one buffer into another.  k_trim_mark (every tile: its first and last loud index, what its inner pauses lose), k_trim_carry
+// (one workgroup per row: the loud index in front of and behind every tile, the row's ptts_trim_info, the exclusive prefix of what the tiles
+// keep) and k_trim_store (every tile: what it keeps, at its offset).  A table's distinct designs (at most kTrimMaxDesigns) travel behind its rows.
+constexpr int kTrimMaxDesigns = 16;
+constexpr size_t kTrimScanBytes = 32;
+static_assert(sizeof(TrimScan) == kTrimScanBytes, "the trim ring's tail (runtime.h) is sized by it");
+struct TrimTile {
+    int32_t first, last;     // k_trim_mark: the tile's first and last loud index in the row (kTrimNoneBehind, kTrimNone: no loud sample in the tile)
+    int32_t removed, cuts;   // ... and the samples and the count of the cuts both of whose loud ends lie in the tile
+    int32_t prev, next;      // k_trim_carry: the last loud index in front of the tile and the first one behind it (kTrimNone, kTrimNoneBehind)
+    int32_t off, pad;        // ... and the output samples in front of the tile's
+};
+static_assert(sizeof(TrimTile) == 32, "trim_scratch_bytes counts on it");
+struct TrimRow {
+    const float* src;        // the row's samples (device)
+    float* dst;              // where what stays goes (device), [n]: another buffer than src
+    int64_t n;               // samples, below 2^31; nothing at or beyond n is touched
+    TrimTile* tiles;         // [ceil(n / kDspTile)]
+    ptts_trim_info* info;    // the row's record (device): k_trim_carry writes it, k_trim_store reads it
+    int32_t design, pad;     // the index of the row's design among the table's
+};
+static_assert(sizeof(TrimRow) == 48, "a turn of the trim ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row (0: empty rows only, which still get their record);
+// designs_dev: the table's designs
+void launch_trim(const TrimRow* rows_dev, int n, int max_tiles, const TrimScan* designs_dev, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

@@ -1572,6 +1572,9 @@ struct JoinSink {
     int64_t frames = 0;
     int fail = PTTS_OK;           // the code of the first chunk, in text order, that was cancelled or ran past the decoder's reach
     std::string fail_msg;
+    bool trim = false;            // the join options' ext carries a trim (resolved once, before anything launches): every part goes through
+    TrimScan trm{};               // k_trim_* in front of k_join, and its length is what comes back in `info`
+    ptts_trim_info* info = nullptr;   // page-locked, [max_batch]: a group's records (Model::trim_info)
 };
 
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
@@ -1931,7 +1934,8 @@ void Chunk::deliver() {
 }
 
 // generate_joined's delivery (behind the fault check: a group that is run again has joined nothing yet): the parts' records; the decode of
-// the whole group into the decoder's buffer; one k_join table that copies the group's rows behind what the text's row holds.  A seam inside
+// the whole group into the decoder's buffer; with a trim (trim.h), the rows' trimmed forms and their lengths; one k_join table that copies the
+// group's rows behind what the text's row holds.  A seam inside
 // the group is computed by the row behind it, which reads its predecessor's tail in the decoder's buffer.  The group's first row has its
 // predecessor in an earlier group, whose buffer is gone: that group stored the tail unfaded, and this row fades it where it lies.
 void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
@@ -1955,19 +1959,43 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
     PTTS_HIP(hipStreamSynchronize(m.stream2));
     mark("mimi");
     const JoinLens& l = join->lens;
+    // The parts as the join sees them: the decoder's rows, or, with a trim, what k_trim_* keeps of them in a buffer of the same row stride; the
+    // lengths then come back in one page-locked copy behind the launches, and everything below counts in them
+    const float* part0 = pcm->as<float>();
+    std::vector<int64_t> len((size_t)B);
+    for (int i = 0; i < B; i++) len[(size_t)i] = (int64_t)nf[i] * spf;
+    if (join->trim) {
+        float* const kept = m.work(WORK_TRIMMED, std::max<size_t>((size_t)B * T * spf, 1) * sizeof(float)).as<float>();
+        std::vector<TrimRow> tr((size_t)B);
+        for (int i = 0; i < B; i++) {
+            tr[(size_t)i].src = part0 + (size_t)i * T * spf;
+            tr[(size_t)i].dst = kept + (size_t)i * T * spf;
+            tr[(size_t)i].n = len[(size_t)i];
+        }
+        const ptts_trim_info* info_dev = trim_launch(m, tr, std::vector<const TrimScan*>((size_t)B, &join->trm), s);
+        PTTS_HIP(hipMemcpyAsync(join->info, info_dev, (size_t)B * sizeof(ptts_trim_info), hipMemcpyDeviceToHost, s));
+        PTTS_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < B; i++) {
+            const int64_t n_out = join->info[i].n_out;
+            if (n_out < 0 || n_out > len[(size_t)i]) throw Error(PTTS_EINVAL, "ptts-hip: internal: a trimmed part is longer than the part");
+            len[(size_t)i] = n_out;
+        }
+        part0 = kept;
+        mark("trim");
+    }
     std::vector<JoinRow> rows;
     for (int i = 0; i < B; i++) {
         ptts_join_part& p = join->parts[idx[(size_t)i]];
-        const int64_t n = (int64_t)nf[i] * spf;
-        const float* src = pcm->as<float>() + (size_t)i * T * spf;
+        const int64_t n = len[(size_t)i];
+        const float* src = part0 + (size_t)i * T * spf;
         const bool first = join->n_prev < 0;
         const int64_t k = first ? 0 : join_seam(l.xfade, join->n_prev, n);
         const int64_t off = first ? 0 : join->at + l.gap - k;
-        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, (int64_t)nf[i + 1] * spf) : 0;   // (the group's last row stores its tail whole)
+        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, len[(size_t)i + 1]) : 0;   // (the group's last row stores its tail whole)
         if (off + n > join->cap) throw Error(PTTS_EINVAL, "ptts-hip: internal: the joined row is smaller than the text");
         JoinRow r{};
         r.src = src;
-        r.prev = !k ? nullptr : i ? pcm->as<float>() + (size_t)(i - 1) * T * spf + (join->n_prev - k) : join->row + off;
+        r.prev = !k ? nullptr : i ? part0 + (size_t)(i - 1) * T * spf + (join->n_prev - k) : join->row + off;
         r.dst = join->row;
         r.off = off; r.n = n - k_next; r.k = (int32_t)k; r.gap = first ? 0 : (int32_t)l.gap;
         rows.push_back(r);
@@ -2002,7 +2030,9 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
         if (!e.empty()) return "generate: " + e;
     }
     if (q.dsp) {
-        const std::string e = dsp_opts_error(*q.dsp);
+        DspSpec spec;
+        std::string e = dsp_resolve(q.dsp, &spec);
+        if (e.empty()) e = dsp_trim_refusal(spec);   // a request's result buffers are sized before the decode
         if (!e.empty()) return "generate: " + e;
         if (q.pcm_callback) {   // the peak and the end are not known when samples are handed over; the filter and the fade in are refused with it for now
             const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : q.dsp->eq ? "eq" : q.dsp->ext ? "ext" : nullptr;
@@ -2111,6 +2141,13 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     if (e.empty()) e = join_egress_error(o);
     if (e.empty() && (n < 1 || n > kJoinMaxRows)) e = strfmt("join: %d requests, a text has from 1 to %d parts", n, kJoinMaxRows);
     if (!e.empty()) refuse(e);
+    if (o.dsp) {   // the trim of the parts, resolved once: the chain below never sees it
+        DspSpec spec;
+        e = dsp_resolve(o.dsp, &spec);
+        if (!e.empty()) refuse("join: " + e);
+        sink.trim = spec.trim;
+        sink.trm = spec.trm;
+    }
     const int lsd = reqs[0].lsd_steps <= 0 ? 1 : reqs[0].lsd_steps;
     const int t_limit = ROPE_SEQ / d.up_stride;
     int64_t bound = 0;   // the joined length the step budgets allow
@@ -2134,6 +2171,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         sink.row = m.work(WORK_JOINED, (size_t)sink.cap * sizeof(float)).as<float>();
         // ---- the groups, as generate() cuts them ----
         const int mb = std::max(1, m.opts.max_batch);
+        if (sink.trim) sink.info = static_cast<ptts_trim_info*>(m.trim_info.ensure((size_t)mb * sizeof(ptts_trim_info)));
         for (int o0 = 0; o0 < n && sink.fail == PTTS_OK; o0 += mb) {
             std::vector<int> idx;
             for (int i = o0; i < std::min(n, o0 + mb); i++) idx.push_back(i);

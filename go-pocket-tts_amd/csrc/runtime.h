@@ -38,6 +38,25 @@ struct DevBuf {
 
 struct Batch;
 
+// a page-locked host buffer, grow-only: what a small device->host read-back lands in without a staging copy
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    void* ensure(size_t bytes) {
+        if (bytes <= n && p) return p;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        PTTS_HIP(hipHostMalloc(&p, std::max<size_t>(bytes, 256), hipHostMallocDefault));
+        n = std::max<size_t>(bytes, 256);
+        return p;
+    }
+};
+
 // Model::work's buffers of the egress and of the host-rows entry points, by name (the other slots are still numbers at their call sites).  Every
 // user holds Model::mu from its first use of a buffer until the work that reads it is queued on Model::stream (device_convert even waits for
 // it), so two names for one number never hold data at the same time.
@@ -49,6 +68,8 @@ enum WorkSlot : size_t {
     WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words, then what dsp_scratch (dsp_spec.h) plans for each row's stages
     WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin; join_rows_device: the parts, then the joined row
     WORK_JOINED = 31,            // generate_joined: the text's joined row, sized before the first group runs and kept until the egress has read it
+    WORK_TRIMMED = 32,           // generate_joined with a trim: what k_trim_store keeps of a group's decoded rows, at the decoder buffer's row stride
+    WORK_TRIM_SCRATCH = 33,      // trim_launch: the rows' ptts_trim_info records, then their TrimTile tables
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -107,6 +128,8 @@ struct Model {
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, runtime.cpp)
+    RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (trim_launch, dsp_device.cpp)
+    PinnedBuf trim_info;            // generate_joined with a trim: a group's ptts_trim_info records, [max_batch] (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
@@ -399,6 +422,12 @@ void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
 // ptts_join_rows: the parts packed into one device buffer with the joined row behind them, uploaded, join_launch, the joined row back, one wait.
 // Takes Model::mu.  The lengths are planned (join_plan) and out holds the joined length
 void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
+// The trim of a list of rows on s (trim.hip; trim.h has the rule): rows[i] states src, dst and n, key[i] its design; their scratch (WORK_TRIM_SCRATCH)
+// and their tables are made here, one launch sequence per table.  Returns the device copy of the rows' records, [rows.size()], complete behind the launches
+const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const std::vector<const TrimScan*>& key, hipStream_t s);
+// ptts_trim_rows: the rows packed into one device buffer with their trimmed forms behind them, uploaded, trim_launch, the records back, then what
+// stays of each row.  Takes Model::mu.  design[i] null: the row is copied on the host
+void trim_rows_device(Model& m, const TrimScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info);
 
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)

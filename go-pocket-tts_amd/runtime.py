@@ -99,6 +99,23 @@ class LimiterOpts(C.Structure):   # ptts_limiter_opts
                          float(release_ms), float(drive_db))
 
 
+class TrimOpts(C.Structure):   # ptts_trim_opts
+    """Silence control of a joined call's parts (ptts_trim_opts): edges 0 / 1 (cut the silent head and tail), threshold_db -120 .. 0 (a sample is
+    loud when |x| > 10^(threshold_db / 20)), pad_ms 0 .. 500 (kept around the first and last loud sample), max_pause_ms 0 (pauses untouched) or
+    20 .. 5000 (the longest pause that stays).  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("edges", C.c_int32), ("threshold_db", C.c_double), ("pad_ms", C.c_double), ("max_pause_ms", C.c_double)]
+
+    def __init__(self, edges: int = 1, threshold_db: float = -50.0, pad_ms: float = 30.0, max_pause_ms: float = 0.0, size: Optional[int] = None):
+        super().__init__(C.sizeof(TrimOpts) if size is None else int(size), int(edges), float(threshold_db), float(pad_ms), float(max_pause_ms))
+
+
+class TrimInfo(C.Structure):   # ptts_trim_info: what a trim made of one row
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("n_out", C.c_int64), ("cuts", C.c_int64), ("speech", C.c_int32), ("reserved", C.c_int32)]
+
+    def astuple(self):
+        return (int(self.lo), int(self.hi), int(self.n_out), int(self.cuts), int(self.speech))
+
+
 class JoinOpts(C.Structure):   # ptts_join_opts
     """How a text's parts become one utterance (ptts_join_opts): gap_ms of silence between consecutive parts or crossfade_ms of overlap (each
     0 .. 2000, not both), and -- for Model.generate_joined -- the chain (dsp: a DspOpts; loudness in 0.01 LUFS), run once over the joined audio,
@@ -183,6 +200,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
     "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined",
+    "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -298,6 +316,10 @@ def lib():
         L.ptts_join.argtypes = [C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
         L.ptts_join_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
         L.ptts_generate_joined.argtypes = [C.c_void_p, C.POINTER(_Request), C.c_int32, C.POINTER(JoinOpts), C.POINTER(_Result), C.POINTER(JoinPart)]
+        L.ptts_trim_plan.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, C.POINTER(TrimInfo)]
+        L.ptts_trim_apply.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, _FP, C.POINTER(TrimInfo)]
+        L.ptts_trim_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TrimOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), C.POINTER(TrimInfo)]
+        L.ptts_dsp_ext_set_trim.argtypes = [C.c_void_p, C.POINTER(TrimOpts)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -748,6 +770,20 @@ class Model:
         """ptts_limit_rows: limit_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
         limiter: one LimiterOpts for every row, or one per row (None copies that row)."""
         return self._stage_rows(lib().ptts_limit_rows, x, limiter, C.POINTER(LimiterOpts), C.pointer)
+
+    def trim_rows(self, x, trim):
+        """ptts_trim_rows: trim_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all), by the kernels
+        generate_joined runs.  trim: one TrimOpts for every row, or one per row (None copies that row).  Returns (rows, their TrimInfo records);
+        for a single array (the row, its record)."""
+        single, rows, n, pp, ns = _rows_in(x)
+        per_row = list(trim) if isinstance(trim, (list, tuple)) else [trim] * n
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        po = (C.POINTER(TrimOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_row])
+        infos = (TrimInfo * max(n, 1))()
+        _check(lib().ptts_trim_rows(self.h, po, pp, _ip(ns), n, _row_ptrs(outs), infos))
+        outs = [o[:int(infos[i].n_out)] for i, o in enumerate(outs)]
+        recs = [TrimInfo(v.lo, v.hi, v.n_out, v.cuts, v.speech, 0) for v in infos[:n]]
+        return (outs[0], recs[0]) if single else (outs, recs)
 
     def true_peak_rows(self, x):
         """ptts_true_peak_rows: true_peak() of mono f32 rows at 24 kHz (an array, or a list: one launch for all), measured on the device."""
@@ -1813,11 +1849,12 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
 
 class DspExt:
     """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
-    (a CompressorOpts; None: off) and a limiter (a LimiterOpts; None: off).  With none of them the handle switches nothing on.  It belongs to no
+    (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off).
+    With none of them the handle switches nothing on.  It belongs to no
     model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
 
     def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
-                 limiter: Optional[LimiterOpts] = None):
+                 limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -1832,6 +1869,8 @@ class DspExt:
             self.set_compressor(compressor)
         if limiter is not None:
             self.set_limiter(limiter)
+        if trim is not None:
+            self.set_trim(trim)
 
     def set_compressor(self, compressor: Optional[CompressorOpts]):
         """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
@@ -1840,6 +1879,11 @@ class DspExt:
     def set_limiter(self, limiter: Optional[LimiterOpts]):
         """ptts_dsp_ext_set_limiter: attaches the limiter (None: off again).  Not while requests that name the handle are running."""
         _check(lib().ptts_dsp_ext_set_limiter(self.h, None if limiter is None else C.byref(limiter)))
+
+    def set_trim(self, trim: Optional[TrimOpts]):
+        """ptts_dsp_ext_set_trim: attaches the trim of a joined call's parts (None: off again).  Served by Model.generate_joined, whose JoinOpts.dsp
+        names the handle; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
+        _check(lib().ptts_dsp_ext_set_trim(self.h, None if trim is None else C.byref(trim)))
 
     def free(self):
         if self.h:
@@ -1873,6 +1917,24 @@ def compress_apply(compressor: CompressorOpts, samples) -> np.ndarray:
 def limit_apply(limiter: LimiterOpts, samples) -> np.ndarray:
     """ptts_limit_apply: the limiter over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
     return _apply_on_host(lib().ptts_limit_apply, limiter, samples)
+
+
+def trim_plan(trim: TrimOpts, samples) -> TrimInfo:
+    """ptts_trim_plan: what the trim makes of mono f32 samples at 24 kHz -- lo, hi, n_out, cuts, speech.  Host."""
+    x = _f32(samples).reshape(-1)
+    info = TrimInfo()
+    _check(lib().ptts_trim_plan(C.byref(trim), _fp(x), x.size, C.byref(info)))
+    return info
+
+
+def trim_apply(trim: TrimOpts, samples, in_place: bool = False):
+    """ptts_trim_apply: (the trimmed row as a new array, its TrimInfo).  Host: the statement of what Model.trim_rows and a joined call's trim
+    compute.  in_place: the library writes over its input (out == in)."""
+    x = np.array(samples, dtype=np.float32, copy=True).reshape(-1)
+    out = x if in_place else np.empty(x.size, np.float32)
+    info = TrimInfo()
+    _check(lib().ptts_trim_apply(C.byref(trim), _fp(x), x.size, _fp(out), C.byref(info)))
+    return out[:int(info.n_out)].copy(), info
 
 
 def true_peak(samples) -> float:

@@ -495,6 +495,57 @@ int  ptts_join_rows(ptts_model* m, const float* const* in, const int64_t* n, int
 int  ptts_generate_joined(ptts_model* m, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, ptts_result* out,
                           ptts_join_part* parts /* [n], optional */);
 
+/* Silence control of the parts of a joined text: a part's silent head and tail cut off and its over-long pauses
+ * capped, per part and IN FRONT of the join, so that what a listener hears between two sentences is the join's gap or crossfade and not the
+ * chunks' own lead-in and trailing frames around it; a joined call with one request is the single-utterance form (no lead-in latency).  The
+ * order of a joined call: trim per part -> join -> the chain of `dsp` and `loudness` once -> egress.
+ *
+ * On a row x[0, n) at 24 kHz, n below 2^31, with
+ *     t = (float)pow(10, threshold_db / 20),   H = (int64)(pad_ms / 1000 * 24000),   M = (int64)(max_pause_ms / 1000 * 24000)
+ * a sample is LOUD when fabsf(x) > t (a NaN never is, an infinity is, |x| == t is not), and L is the ascending set of loud indices:
+ *   - no loud sample: the row comes back whole; lo = 0, hi = n, n_out = n, cuts = 0, speech = 0;
+ *   - otherwise speech = 1 and, with `edges`, lo = max(0, L.first - H) and hi = min(n, L.last + 1 + H); without, lo = 0 and hi = n;
+ *   - pauses, when M > 0: consecutive loud indices u < v with q = v - u - 1 > M lose the samples [u + 1 + (M - M / 2), v - M / 2) (integer
+ *     division): the first ceil(M / 2) and the last floor(M / 2) samples of the pause stay; `cuts` counts such pairs;
+ *   - every sample of [lo, hi) that is not removed is output, in order, moved as its 32 bits: n_out = hi - lo - sum(q - M).
+ * Integer comparisons and copies only: the host and the device give the same bits, and no tolerance applies.  The lower bound of 20 ms on
+ * max_pause_ms is one period of a 50 Hz voice: the quiet samples between the peaks of voiced speech are never a pause.
+ * ptts_trim_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it; edges == 0 with max_pause_ms == 0 is refused too ("trim: nothing switched on").
+ * ptts_trim_plan: what the trim makes of x[0, n), into *info; writes nothing else.  Host.
+ * ptts_trim_apply: the trimmed row into out, which holds n floats (the first info->n_out are written; out == in is allowed); info is optional.
+ *     Host: the statement of the result.
+ * ptts_trim_rows: the same on rows of host samples on the device, by the kernels ptts_generate_joined runs (k_trim_mark, k_trim_carry,
+ *     k_trim_store), shaped like ptts_limit_rows: one upload, one launch sequence per 256 rows, one download.  t[i] NULL copies row i (its record
+ *     says lo = 0, hi = n_out = n[i], cuts = 0, speech = 0); n[i] >= 0; in[i] == out[i] is allowed; out[i] holds n[i] floats; info ([rows]) is
+ *     required; a bad row is named.
+ * ptts_dsp_ext_set_trim attaches the trim to a live handle of ptts_dsp_ext_create (t NULL: off again); a handle that is not live is PTTS_EINVAL
+ *     and is not read.  Set it before calls name the handle, not while they run.  It is served where the lengths are decided on the host behind
+ *     the decode: by ptts_generate_joined, whose join options' `dsp` names the handle -- every part is trimmed in front of the join,
+ *     parts[i].offset and parts[i].n_samples count the trimmed audio, parts[i].n_frames and out->n_frames still count decoded frames, and the
+ *     chain of that `dsp` runs over the joined audio as without a trim (the trim is a stage per part, not a stage of the chain).  Everywhere a
+ *     row's length is fixed before the decode it is refused with PTTS_EINVAL, nothing launched ("dsp: ext: trim changes a row's length ..."):
+ *     a ptts_request.dsp whose ext carries a trim (ptts_generate, the dispatcher, the continuous engine, streaming) and ptts_dsp_rows. */
+typedef struct ptts_trim_opts {
+    uint32_t size;           /* sizeof(ptts_trim_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  edges;          /* 0 or 1: trim the row's silent head and tail */
+    double   threshold_db;   /* -120 .. 0 (dBFS): a sample is loud when fabsf(x) > (float)pow(10, threshold_db / 20) */
+    double   pad_ms;         /* 0 .. 500: audio kept in front of the first and behind the last loud sample */
+    double   max_pause_ms;   /* 0: pauses untouched; else 20 .. 5000: the longest pause that stays */
+} ptts_trim_opts;
+typedef struct ptts_trim_info {
+    int64_t lo, hi;          /* the edges: what lies in [lo, hi) and in no cut is output */
+    int64_t n_out;           /* samples of the trimmed row */
+    int64_t cuts;            /* pauses that were shortened */
+    int32_t speech;          /* 1: the row has a loud sample; 0: it came back whole */
+    int32_t reserved;
+} ptts_trim_info;
+int  ptts_trim_plan(const ptts_trim_opts* t, const float* x, int64_t n, ptts_trim_info* info);
+int  ptts_trim_apply(const ptts_trim_opts* t, const float* in, int64_t n, float* out, ptts_trim_info* info /* optional */);
+int  ptts_trim_rows(ptts_model* m, const ptts_trim_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out,
+                    ptts_trim_info* info /* [rows] */);
+int  ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t);
+
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
  * tokens, and derive each chunk's step budget and EOS tail.  The SentencePiece encoder is the caller's. */
@@ -748,7 +799,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_true_peak_rows; ptts_compressor_opts with ptts_dsp_ext_set_compressor (the handle is the extension point: no struct grows),
  * ptts_compress_gain, ptts_compress_apply, ptts_compress_rows; ptts_limiter_opts with ptts_dsp_ext_set_limiter, ptts_limit_apply,
  * ptts_limit_rows; the new structs ptts_join_opts and ptts_join_part, which change no existing one, with ptts_join_length, ptts_join, ptts_join_rows,
- * ptts_generate_joined */
+ * ptts_generate_joined; the new structs ptts_trim_opts and ptts_trim_info, likewise, with ptts_trim_plan, ptts_trim_apply, ptts_trim_rows,
+ * ptts_dsp_ext_set_trim */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
