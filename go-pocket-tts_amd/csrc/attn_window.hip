@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "common.h"
 #include "kernels.h"
 #include "device_util.h"
 #include "mfma_util.h"
@@ -373,22 +374,31 @@ bool attn_window_supported(const AttnArgs& a) {
     return !a.kv_bf16 && a.context > 0 && !a.row_seg && !a.row_pos && a.rows % a.rows_per_seg == 0;
 }
 
-void launch_attn_window(const AttnArgs& a, hipStream_t stream) {
+// the LDS form addresses a segment's rows by 32-bit element offsets, and exists for the dense f32 case only
+bool attn_window_form_supported(const AttnArgs& a, int form) {
+    if (form == AW_FORM_WAVE) return true;
+    return form == AW_FORM_LDS && !a.rag_off && !a.kv_bf16 && (int64_t)(a.pos_base + a.rows_per_seg) * a.k_row_stride < (1ll << 31);
+}
+
+// (measured: Mimi phase of the benchmark batch 12.85 -> 12.50 ms with the shared tiles, 128 queries per block; 64 queries per block -- two waves, 10 tiles
+// of which a wave uses 9 instead of 12 / 9 -- 12.7 ms; profiles/r4_mimi_ab.txt)
+int attn_window_form(const AttnArgs& a) { return attn_window_form_supported(a, AW_FORM_LDS) ? AW_FORM_LDS : AW_FORM_WAVE; }
+
+void launch_attn_window_as(const AttnArgs& a, int form, hipStream_t stream) {
+    if (!attn_window_form_supported(a, form)) throw Error(PTTS_EINVAL, strfmt("ptts-hip: internal: the window attention has no form %d for these operands", form));
     note_launch(a.rag_off ? "k_attn_window<ragged>" : "k_attn_window");
     const int qtiles = (a.rows_per_seg + 31) / 32;   // ragged: rows_per_seg is the longest segment
     const int segs = a.rag_off ? a.rag_segs : a.rows / a.rows_per_seg;
     dim3 grid(a.heads, (unsigned)(segs * ((qtiles + 3) / 4)));
-    if (a.rag_off) {
+    if (form == AW_FORM_LDS) {
+        const int qblocks = (a.rows_per_seg + 127) / 128;
+        hipLaunchKernelGGL(k_attn_window_lds<4>, dim3(a.heads, (unsigned)(segs * qblocks)), dim3(256), 0, stream, a, qblocks);
+    } else if (a.rag_off) {
         if (a.kv_bf16) hipLaunchKernelGGL((k_attn_window<true, true>), grid, dim3(256), 0, stream, a, qtiles);
         else hipLaunchKernelGGL((k_attn_window<false, true>), grid, dim3(256), 0, stream, a, qtiles);
-    } else {
-        // (measured: Mimi phase of the benchmark batch 12.85 -> 12.50 ms with the shared tiles, 128 queries per block; 64 queries per block -- two waves, 10 tiles
-        // of which a wave uses 9 instead of 12 / 9 -- 12.7 ms; profiles/r4_mimi_ab.txt)
-        if ((int64_t)(a.pos_base + a.rows_per_seg) * a.k_row_stride < (1ll << 31)) {
-            const int qblocks = (a.rows_per_seg + 127) / 128;
-            hipLaunchKernelGGL(k_attn_window_lds<4>, dim3(a.heads, (unsigned)(segs * qblocks)), dim3(256), 0, stream, a, qblocks);
-        } else hipLaunchKernelGGL((k_attn_window<false, false>), grid, dim3(256), 0, stream, a, qtiles);
-    }
+    } else hipLaunchKernelGGL((k_attn_window<false, false>), grid, dim3(256), 0, stream, a, qtiles);
 }
+
+void launch_attn_window(const AttnArgs& a, hipStream_t stream) { launch_attn_window_as(a, attn_window_form(a), stream); }
 
 }  // namespace ptts

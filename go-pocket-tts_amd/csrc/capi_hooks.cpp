@@ -581,6 +581,115 @@ int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per
     return attn_step_rounds(keys, kv_bf16 != 0);
 }
 
+// The window attention on host operands: ONE launch with AttnArgs as mimi_range / the encoder (dense) or the prompt prefill (ragged) fill them.  The kernels
+// bound their key loads by positions alone (pos_base + rows, rag_pos0 + segment length), never by a buffer size, so those are checked against the buffers
+// allocated here before anything is uploaded.
+int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: null argument");
+        const ptts_attn_window_args& t = *pa;
+        if (!t.qkv || !t.out || (t.kv_bf16 != 0 && t.kv_bf16 != 1) || (t.ragged != 0 && t.ragged != 1)) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: bad arguments");
+        if (t.form < 0 || t.form > 2) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: unknown form %d", t.form));
+        if (t.heads < 1 || t.heads > 16 || t.segs < 1 || t.segs > 16)
+            throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: %d heads, %d segments: the hook takes 1..16 of each", t.heads, t.segs));
+        const int heads = t.heads, segs = t.segs, D = heads * 64, es = t.kv_bf16 ? 2 : 4;
+        if (t.ld < (t.ragged ? 1 : 3) * (int64_t)D || t.out_ld < D)
+            throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: ld %lld / out_ld %lld below the columns the launch reads / writes (d_model %d)", (long long)t.ld, (long long)t.out_ld, D));
+        if (t.ld > (1 << 16) || t.out_ld > (1 << 16)) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: ld / out_ld above 65536");
+        if (t.ld % 4 || t.out_ld % 4)
+            throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: ld %lld / out_ld %lld: rows must keep 16-byte alignment (attn_window_supported)", (long long)t.ld, (long long)t.out_ld));
+        int rows = 0, longest = 0, max_pos = 0;
+        std::vector<int32_t> row_seg, row_pos;
+        if (t.ragged) {
+            if (!t.k || !t.v || !t.rag_off || !t.rag_pos0) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: ragged operands need k, v, rag_off and rag_pos0");
+            if (t.form == 2) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: form 2 (k_attn_window_lds) takes dense operands only");
+            if (t.cap < 1 || t.cap > 4096 || t.rows < 1 || t.rows > 4096) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: cap %d / rows %d outside 1..4096", t.cap, t.rows));
+            if (t.rag_off[0] != 0 || t.rag_off[segs] != t.rows) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: rag_off runs from %d to %d, not from 0 to rows %d", t.rag_off[0], t.rag_off[segs], t.rows));
+            rows = t.rows;
+            row_seg.resize((size_t)rows); row_pos.resize((size_t)rows);
+            for (int s = 0; s < segs; s++) {
+                const int n = t.rag_off[s + 1] - t.rag_off[s];
+                if (n < 0) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: rag_off decreases at segment %d", s));
+                if (t.rag_pos0[s] < 0 || t.rag_pos0[s] + n > t.cap) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: segment %d: %d rows from position %d, the cache holds %d", s, n, t.rag_pos0[s], t.cap));
+                longest = std::max(longest, n);
+                for (int i = 0; i < n; i++) { row_seg[(size_t)t.rag_off[s] + i] = s; row_pos[(size_t)t.rag_off[s] + i] = t.rag_pos0[s] + i; max_pos = std::max(max_pos, t.rag_pos0[s] + i); }
+            }
+        } else {
+            if (t.kv_bf16) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: the dense layout is f32 (attn_window_supported)");
+            if (t.T1 < 1 || t.T1 > 4096) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: T1 %d outside 1..4096", t.T1));
+            if (t.t0 < 0 || t.CT < 1 || (int64_t)t.t0 + t.CT > t.T1) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: chunk (%d, %d) leaves the %d rows of a segment", t.t0, t.CT, t.T1));
+            if ((int64_t)segs * t.CT > 4096) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: %d rows, the hook takes 4096", segs * t.CT));
+            if (t.context < 1) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: the dense launch needs a window (context %d; attn_window_supported)", t.context));
+            rows = segs * t.CT;
+        }
+        require_device();
+        const size_t q_bytes = (t.ragged ? (size_t)rows : (size_t)segs * t.T1) * t.ld * 4, kv_bytes = t.ragged ? (size_t)segs * heads * t.cap * 64 * es : 16,
+                     out_bytes = (size_t)rows * t.out_ld * 4, meta_n = (size_t)2 * rows + 2 * segs + 1;
+        Tmp dQ(q_bytes), dK(kv_bytes), dV(kv_bytes), dO(out_bytes), dMeta(meta_n * 4);
+        AttnArgs a;
+        a.q_ld = t.ld; a.q_col0 = 0;
+        a.context = t.context;
+        a.out = dO.as<float>(); a.out_ld = t.out_ld;
+        a.rows = rows; a.heads = heads;
+        if (t.ragged) {   // runtime.cpp, the prompt prefill: one upload holds row -> segment, row -> position, the segments' first rows and first positions
+            int32_t* d_slot = dMeta.as<int32_t>();
+            int32_t* d_pos = d_slot + rows;
+            a.q = dQ.as<float>();
+            a.k = dK.p; a.v = dV.p; a.kv_bf16 = t.kv_bf16;
+            a.k_seg_stride = (int64_t)heads * t.cap * 64; a.k_head_stride = (int64_t)t.cap * 64; a.k_row_stride = 64;
+            a.row_seg = d_slot; a.row_pos = d_pos;
+            a.rag_off = d_pos + rows; a.rag_pos0 = d_pos + rows + segs + 1; a.rag_segs = segs; a.rows_per_seg = longest;
+            a.max_keys = max_pos + 1;
+        } else {          // runtime.cpp mimi_range (encoder.cpp: t0 = 0, CT = T1, one segment)
+            float* qkv = dQ.as<float>();
+            a.q = qkv + (size_t)t.t0 * t.ld; a.q_rows_per_batch = t.CT; a.q_batch_stride = (int64_t)t.T1 * t.ld;
+            a.k = qkv + D; a.v = qkv + 2 * D; a.kv_bf16 = 0;
+            a.k_seg_stride = (int64_t)t.T1 * t.ld; a.k_head_stride = 64; a.k_row_stride = t.ld;
+            a.rows_per_seg = t.CT; a.pos_base = t.t0;
+            a.max_keys = std::min(t.T1, t.context);
+        }
+        if (!attn_window_supported(a) || (t.form && !attn_window_form_supported(a, t.form))) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: refused by attn_window_supported");
+        up(dQ.p, t.qkv, q_bytes);
+        if (t.ragged) {
+            std::vector<int32_t> meta(meta_n);
+            std::copy(row_seg.begin(), row_seg.end(), meta.begin());
+            std::copy(row_pos.begin(), row_pos.end(), meta.begin() + rows);
+            std::copy(t.rag_off, t.rag_off + segs + 1, meta.begin() + 2 * rows);
+            std::copy(t.rag_pos0, t.rag_pos0 + segs, meta.begin() + 2 * rows + segs + 1);
+            up(dMeta.p, meta.data(), meta_n * 4);
+            up(dK.p, t.k, kv_bytes); up(dV.p, t.v, kv_bytes);
+        }
+        PTTS_HIP(hipMemset(dO.p, 0xff, out_bytes));
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        g_launch_census = &census;
+        try {
+            if (t.form == 0) launch_attention(a, nullptr);
+            else launch_attn_window_as(a, t.form, nullptr);
+        } catch (...) { g_launch_census = census_before; throw; }
+        g_launch_census = census_before;
+        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        PTTS_HIP(hipGetLastError());
+        PTTS_HIP(hipDeviceSynchronize());
+        if (t.kernel && t.kernel_cap > 0) {
+            const char* name = t.form == 0 ? g_last_attn_kernel
+                             : t.form == 2 ? "k_attn_window_lds<4>"
+                             : !t.ragged ? "k_attn_window<false,false>" : (t.kv_bf16 ? "k_attn_window<true,true>" : "k_attn_window<false,true>");
+            const size_t n = std::min<size_t>(std::strlen(name), (size_t)t.kernel_cap - 1);
+            std::memcpy(t.kernel, name, n);
+            t.kernel[n] = 0;
+        }
+        if (t.launched && t.launched_cap > 0) {
+            std::string s;
+            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
+            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
+            std::memcpy(t.launched, s.data(), n);
+            t.launched[n] = 0;
+        }
+        down(t.out, dO.p, out_bytes);
+    });
+}
+
 // The many-row GEMMs on host operands: ONE launch of a named kernel.  These kernels clamp addresses instead of bounding their loads, so every element a row's
 // read or store can touch is checked against the caller's buffer sizes here, before anything is uploaded.
 int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {

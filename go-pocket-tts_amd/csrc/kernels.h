@@ -230,7 +230,13 @@ int attn_step_keys_per_round(bool kv_bf16);       // keys one load round of the 
 int attn_step_rounds(int keys, bool kv_bf16);     // rounds launch_attn_step issues for a launch bounded by `keys` (1..16)
 int attn_step_launch_rounds(const AttnArgs& a);   // ... for this launch: bounded by keys_now when the host knows it, by max_keys otherwise
 bool attn_window_supported(const AttnArgs& a);   // Mimi sliding-window attention on the f32 matrix cores
-void launch_attn_window(const AttnArgs& a, hipStream_t stream);
+void launch_attn_window(const AttnArgs& a, hipStream_t stream);   // = launch_attn_window_as(a, attn_window_form(a))
+// The kernel forms of attn_window.hip.  WAVE: k_attn_window, every wave fetches its own key tiles (the only form for ragged segments and bf16 caches);
+// LDS: k_attn_window_lds<4>, the key tiles of 128 queries shared through LDS (dense f32 only, 32-bit element offsets inside a segment).
+enum { AW_FORM_WAVE = 1, AW_FORM_LDS = 2 };
+int attn_window_form(const AttnArgs& a);           // the production choice for a launch attn_window_supported takes
+bool attn_window_form_supported(const AttnArgs& a, int form);
+void launch_attn_window_as(const AttnArgs& a, int form, hipStream_t stream);   // (test hook: a form the operands do not allow is PTTS_EINVAL)
 
 // latent [B, T, L] -> x[b, 1+t, :] = Wp * latent + bp  (model.go:252-319), row 0 of each utterance zeroed
 void launch_projector(const float* latent, int64_t lat_bstride, const float* wp, const float* bp, int b, int t, int f0, int f1,

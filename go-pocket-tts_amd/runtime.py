@@ -209,7 +209,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
-    "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds",
+    "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window",
 ]
 
 
@@ -1451,6 +1451,59 @@ def attn_step_rounds(keys: int, kv_bf16: bool):
     H.ptts_debug_attn_step_rounds.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     kpr = C.c_int32()
     return int(H.ptts_debug_attn_step_rounds(int(keys), 1 if kv_bf16 else 0, C.byref(kpr))), int(kpr.value)
+
+
+class _AttnWindowArgs(C.Structure):   # ptts_attn_window_args
+    _fields_ = ([(n, C.c_int32) for n in ("form", "ragged", "kv_bf16", "heads", "segs", "context", "T1", "t0", "CT", "cap", "rows", "reserved")] +
+                [(n, C.c_int64) for n in ("ld", "out_ld", "kernel_cap", "launched_cap")] +
+                [("qkv", _FP), ("k", C.c_void_p), ("v", C.c_void_p), ("rag_off", C.POINTER(C.c_int32)), ("rag_pos0", C.POINTER(C.c_int32)), ("out", _FP),
+                 ("kernel", C.c_char_p), ("launched", C.c_char_p)])
+
+
+ATTN_WINDOW_DISPATCH, ATTN_WINDOW_WAVE, ATTN_WINDOW_LDS = 0, 1, 2
+
+
+def debug_attn_window(qkv, *, heads, context, form=0, t0=0, ct=None, k=None, v=None, rag_off=None, rag_pos0=None, kv_bf16=False, out_ld=None):
+    """The window attention (csrc/attn_window.hip) on host operands (ptts_debug_attn_window, include/ptts_debug.h): one launch.  Dense: qkv [segs, T1, ld] (q | k |
+    v at columns 0, D, 2 D), the chunk (t0, ct) of every segment is launched (ct default: T1 - t0).  Ragged (rag_off given): qkv is the packed query rows
+    [rows, ld], k / v the caches [segs, heads, cap, 64] in the cache format (uint16 bf16 bits, or 4-byte elements), rag_off [segs + 1], rag_pos0 [segs].  form 0:
+    launch_attention's dispatch, 1: k_attn_window, 2: k_attn_window_lds<4>.  Returns a dict: "out" ([rows, out_ld], 0xff bytes where nothing was stored),
+    "kernel" (the dispatch's name, or the instance's), "launched" ({kernel: count})."""
+    qkv = _f32(qkv)
+    ragged = rag_off is not None
+    a = _AttnWindowArgs()
+    keep = [qkv]
+    if ragged:
+        es = 2 if kv_bf16 else 4
+        k, v = np.ascontiguousarray(k), np.ascontiguousarray(v)
+        rag_off, rag_pos0 = np.ascontiguousarray(rag_off, np.int32), np.ascontiguousarray(rag_pos0, np.int32)
+        segs = rag_pos0.shape[0] if rag_pos0.ndim == 1 else -1
+        if (qkv.ndim != 2 or segs < 1 or rag_off.shape != (segs + 1,) or k.ndim != 4 or k.shape != v.shape or k.shape[:2] != (segs, heads) or k.shape[3] != 64 or
+                k.itemsize != es or v.itemsize != es):
+            raise PttsError(PTTS_EINVAL, "debug_attn_window: operand shapes do not fit (include/ptts_debug.h ptts_attn_window_args)")
+        rows, ld = qkv.shape
+        a.cap, a.rows = k.shape[2], rows
+        a.k, a.v = k.ctypes.data, v.ctypes.data
+        a.rag_off, a.rag_pos0 = [C.cast(x.ctypes.data, C.POINTER(C.c_int32)) for x in (rag_off, rag_pos0)]
+        keep += [k, v, rag_off, rag_pos0]
+    else:
+        if qkv.ndim != 3:
+            raise PttsError(PTTS_EINVAL, "debug_attn_window: the dense operand is [segs, T1, ld]")
+        segs, t1, ld = qkv.shape
+        ct = t1 - int(t0) if ct is None else int(ct)
+        a.T1, a.t0, a.CT = t1, int(t0), ct
+        rows = max(segs * ct, 0)
+    out_ld = heads * 64 if out_ld is None else int(out_ld)
+    out = np.empty((rows, max(out_ld, 0)), np.float32)
+    name, launched = C.create_string_buffer(64), C.create_string_buffer(256)
+    a.form, a.ragged, a.kv_bf16, a.heads, a.segs, a.context = int(form), (1 if ragged else 0), (1 if kv_bf16 else 0), int(heads), segs, int(context)
+    a.ld, a.out_ld, a.kernel_cap, a.launched_cap = ld, out_ld, 64, 256
+    a.qkv, a.out = _fp(qkv), _fp(out)
+    a.kernel, a.launched = C.cast(name, C.c_char_p), C.cast(launched, C.c_char_p)
+    H = hooks()
+    H.ptts_debug_attn_window.argtypes = [C.POINTER(_AttnWindowArgs)]
+    _check(H.ptts_debug_attn_window(C.byref(a)))
+    return {"out": out, "kernel": name.value.decode(), "launched": {kv.split("=")[0]: int(kv.split("=")[1]) for kv in launched.value.decode().split(";") if kv}}
 
 
 class _GemmRowsArgs(C.Structure):   # ptts_gemm_rows_args

@@ -108,6 +108,32 @@ int ptts_debug_attn_step(const ptts_attn_step_args* a);
 /* attn_step_rounds / attn_step_keys_per_round of csrc/attn_step.hip (no GPU): the load rounds for a launch bounded by `keys`, the keys one round covers. */
 int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per_round);
 
+/* The window attention (csrc/attn_window.hip: k_attn_window, k_attn_window_lds) stand-alone: ONE launch on host operands, AttnArgs filled as the callers do.
+ * Dense (ragged 0; runtime.cpp mimi_range, encoder.cpp): qkv [segs][T1][ld] f32 holds q | k | v at columns 0, D, 2 D (D = heads * 64).  The chunk (t0, CT) is
+ *   launched: q = qkv + t0 ld with q_rows_per_batch CT and q_batch_stride T1 ld; k / v = qkv + D / 2 D with k_seg_stride T1 ld, k_head_stride 64,
+ *   k_row_stride ld; rows_per_seg CT, pos_base t0, context (> 0), rows = segs CT.
+ * Ragged (ragged 1; runtime.cpp's prompt prefill): qkv is the packed query rows [rows][ld]; k, v are caches [segs][heads][cap][64] as raw bytes (f32, or bf16
+ *   bits with kv_bf16); rag_off [segs + 1] (rag_off[0] = 0, rag_off[segs] = rows), rag_pos0 [segs]; row_seg / row_pos are derived and passed as the prefill
+ *   passes them; rows_per_seg = the longest segment; context: -1 as in production, or a window.
+ * out [rows][out_ld] is filled with 0xff bytes before the launch and returned whole.
+ * form 0: through launch_attention (the dispatch is under test); 1: k_attn_window<false, false>, or the ragged instance of the cache format; 2:
+ * k_attn_window_lds<4> (dense only).  kernel (kernel_cap bytes) receives the name launch_attention picked (form 0) or the instance's; launched (launched_cap
+ * bytes) the census of the call ("kernel=count;").
+ * PTTS_EINVAL with a message, before anything is uploaded or launched, for whatever could take an access outside these buffers: ld < 3 D (ragged: < D) or
+ * out_ld < D; ld or out_ld not a multiple of 4 (the kernels' 16-byte accesses: attn_window_supported); t0 < 0, CT < 1, t0 + CT > T1; a dense context < 1 or a
+ * dense bf16 cache; rag_off not starting at 0, not non-decreasing or not ending at rows; rag_pos0[s] < 0 or rag_pos0[s] + n_s > cap; an unknown form or form 2
+ * on ragged operands; sizes outside 1 <= rows <= 4096, heads <= 16, segs <= 16, cap / T1 <= 4096. */
+typedef struct ptts_attn_window_args {
+    int32_t form, ragged, kv_bf16, heads, segs, context, T1, t0, CT, cap, rows, reserved;
+    int64_t ld, out_ld, kernel_cap, launched_cap;
+    const float* qkv;
+    const void *k, *v;
+    const int32_t *rag_off, *rag_pos0;
+    float* out;
+    char *kernel, *launched;
+} ptts_attn_window_args;
+int ptts_debug_attn_window(const ptts_attn_window_args* a);
+
 /* The many-row GEMMs (csrc/kernels.hip k_gemm, gemm2.hip, gemm3.hip, gemm_wres.hip, gemm5.hip) stand-alone: ONE launch of a named kernel on host operands.
  * C = epi(rope(aop(A) W^T + bias)) with kernels.h' RowMaps on A and C:
  *   A: a buffer of a_elems floats; row m starts at a_off + (m / a_rows_per_batch) a_batch_stride + (m % a_rows_per_batch) a_ld (a_rows_per_batch 0: a_off + m a_ld)
