@@ -44,6 +44,102 @@ int ptts_debug_flow_cluster_inject(ptts_model* h, int32_t block) {
     });
 }
 
+// k_flow_cluster on host operands: a SEQUENCE of launches on one granule buffer and one set of tag words, FlowClusterArgs filled as runtime.cpp step_flow
+// fills them.  The kernel's workgroups spin on each other, so nothing is launched that the batch set-up would not launch: flow_cluster_fits and
+// flow_cluster_supported are asked, inject and stamps stay at their defaults (there is no argument that reaches them).
+int ptts_debug_flow_cluster(const ptts_flow_cluster_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_flow_cluster: null argument");
+        const ptts_flow_cluster_args& t = *pa;
+        constexpr int C = 512, kSlack = 3;
+        constexpr int kMaxRows = kFlowClusterMaxTiles * kFlowClusterRows;
+        if (t.rows < 1 || t.rows > kMaxRows) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: %d rows, the kernel takes 1..%d", t.rows, kMaxRows));
+        if (t.depth < 1 || t.depth > FC_MAX_DEPTH) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: depth %d outside 1..%d", t.depth, FC_MAX_DEPTH));
+        if (t.ldmod % 4 != 0 || t.ldmod < (int64_t)3 * t.depth * C)
+            throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: ldmod %lld: a multiple of 4 and at least 3 depth 512 = %d", (long long)t.ldmod, 3 * t.depth * C));
+        if (t.ldmod > (1 << 16)) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: ldmod %lld above 65536", (long long)t.ldmod));
+        if (t.n_launch < 1 || t.n_launch > 8) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: %d launches, the hook takes 1..8", t.n_launch));
+        if (t.in_place != 0 && t.in_place != 1) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: in_place %d is neither 0 nor 1", t.in_place));
+        if (!t.fx || !t.ada || !t.ln_w || !t.ln_b || !t.b0 || !t.b2 || !t.eps || !t.w0 || !t.w2 || !t.launch_rows || !t.out || !t.state || (!t.in_place && !t.fx_back))
+            throw Error(PTTS_EINVAL, "ptts_debug_flow_cluster: null operand");
+        for (int i = 0; i < t.n_launch; i++)
+            if (t.launch_rows[i] < 1 || t.launch_rows[i] > t.rows)
+                throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: launch %d of %d rows, the operands hold %d", i, t.launch_rows[i], t.rows));
+        if (t.tag_base0 & 1u) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: tag_base0 %u is odd (a launch's base is even: h tags are odd, x tags even)", t.tag_base0));
+        const int rows = t.rows, depth = t.depth, L = t.n_launch;
+        // weights: rounded to bf16 and tiled by the loader's packer (what Lin::wt holds)
+        const size_t wbytes = step_tiled_bytes((size_t)C, (size_t)C, 2);
+        std::vector<uint8_t> wt((size_t)2 * depth * wbytes);
+        for (int r = 0; r < depth; r++) {
+            pack_step_tiled(t.w0 + (size_t)r * C * C, (size_t)C, (size_t)C, true, wt.data() + (size_t)(2 * r) * wbytes);
+            pack_step_tiled(t.w2 + (size_t)r * C * C, (size_t)C, (size_t)C, true, wt.data() + (size_t)(2 * r + 1) * wbytes);
+        }
+        require_device();
+        int device = 0;
+        PTTS_HIP(hipGetDevice(&device));
+        if (!flow_cluster_fits(rows, device)) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: the grid of %d rows is not resident at once on this device (flow_cluster_fits)", rows));
+        const size_t row_bytes = (size_t)C * 4, buf_rows = (size_t)rows + kSlack, fx_bytes = buf_rows * row_bytes, ada_bytes = buf_rows * (size_t)t.ldmod * 4, vec_bytes = (size_t)depth * C * 4;
+        Tmp dW(wt.size()), dAda(ada_bytes), dLw(vec_bytes), dLb(vec_bytes), dB0(vec_bytes), dB2(vec_bytes), dIn((size_t)L * fx_bytes), dOut((size_t)L * fx_bytes),
+            dX(flow_cluster_xbuf_bytes(rows)), dSync(kFlowClusterSyncBytes);
+        up(dW.p, wt.data(), wt.size());
+        PTTS_HIP(hipMemset(dAda.p, 0xff, ada_bytes));   // (NaN slack rows behind `rows`)
+        up(dAda.p, t.ada, (size_t)rows * t.ldmod * 4);
+        up(dLw.p, t.ln_w, vec_bytes); up(dLb.p, t.ln_b, vec_bytes); up(dB0.p, t.b0, vec_bytes); up(dB2.p, t.b2, vec_bytes);
+        // every launch its own copy of the rows it takes: NaN behind them (in place that is what the rows at and beyond launch_rows keep)
+        PTTS_HIP(hipMemset(dIn.p, 0xff, (size_t)L * fx_bytes)); PTTS_HIP(hipMemset(dOut.p, 0xff, (size_t)L * fx_bytes));
+        for (int i = 0; i < L; i++) up(dIn.as<uint8_t>() + (size_t)i * fx_bytes, t.fx, (size_t)t.launch_rows[i] * row_bytes);
+        // the exchange state as runtime.cpp sets it up (zeroes), then the tag words at tag_base0
+        PTTS_HIP(hipMemset(dX.p, 0, flow_cluster_xbuf_bytes(rows))); PTTS_HIP(hipMemset(dSync.p, 0, kFlowClusterSyncBytes));
+        std::vector<uint32_t> sync(kFlowClusterSyncBytes / 4, 0u);
+        for (int tile = 0; tile < kFlowClusterMaxTiles; tile++) sync[(size_t)tile * 32] = t.tag_base0;
+        up(dSync.p, sync.data(), kFlowClusterSyncBytes);
+        auto read_state = [&] {
+            down(sync.data(), dSync.p, kFlowClusterSyncBytes);
+            for (int tile = 0; tile < kFlowClusterMaxTiles; tile++) t.state[tile] = sync[(size_t)tile * 32];
+            t.state[kFlowClusterMaxTiles] = sync[(size_t)32 * kFlowClusterMaxTiles];
+        };
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        int faulted = -1;
+        for (int i = 0; i < L && faulted < 0; i++) {
+            FlowClusterArgs fa;   // as step_flow fills them
+            float* in = dIn.as<float>() + (size_t)i * buf_rows * C;
+            fa.fx_in = in; fa.fx_out = t.in_place ? in : dOut.as<float>() + (size_t)i * buf_rows * C;
+            fa.ada = dAda.as<float>(); fa.ldmod = t.ldmod; fa.rows = t.launch_rows[i]; fa.depth = depth;
+            for (int r = 0; r < depth; r++) {
+                fa.eps[r] = t.eps[r]; fa.ln_w[r] = dLw.as<float>() + (size_t)r * C; fa.ln_b[r] = dLb.as<float>() + (size_t)r * C;
+                fa.w0[r] = dW.as<uint8_t>() + (size_t)(2 * r) * wbytes; fa.b0[r] = dB0.as<float>() + (size_t)r * C;
+                fa.w2[r] = dW.as<uint8_t>() + (size_t)(2 * r + 1) * wbytes; fa.b2[r] = dB2.as<float>() + (size_t)r * C;
+            }
+            fa.xbuf = dX.as<unsigned long long>(); fa.sync = dSync.as<unsigned>();
+            if (!flow_cluster_supported(fa, C)) throw Error(PTTS_EINVAL, "ptts_debug_flow_cluster: refused by flow_cluster_supported");
+            g_launch_census = &census;
+            try { launch_flow_cluster(fa, nullptr); } catch (...) { g_launch_census = census_before; throw; }
+            g_launch_census = census_before;
+            PTTS_HIP(hipGetLastError());
+            PTTS_HIP(hipDeviceSynchronize());
+            uint32_t fault = 0;
+            down(&fault, dSync.as<uint32_t>() + (size_t)32 * kFlowClusterMaxTiles, 4);
+            if (fault) faulted = i;   // (nothing is retried, nothing more is launched on this state)
+        }
+        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launches too
+        if (t.launched && t.launched_cap > 0) {
+            std::string s;
+            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
+            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
+            std::memcpy(t.launched, s.data(), n);
+            t.launched[n] = 0;
+        }
+        read_state();
+        for (int i = 0; i < L; i++) {
+            down(t.out + (size_t)i * rows * C, (t.in_place ? dIn : dOut).as<uint8_t>() + (size_t)i * fx_bytes, (size_t)rows * row_bytes);
+            if (!t.in_place) down(t.fx_back + (size_t)i * rows * C, dIn.as<uint8_t>() + (size_t)i * fx_bytes, (size_t)rows * row_bytes);
+        }
+        if (faulted >= 0)
+            throw Error(PTTS_ENODEVICE, strfmt("ptts_debug_flow_cluster: the in-launch hand-off timed out (k_flow_cluster), launch %d of %d; nothing is retried", faulted, L));
+    });
+}
+
 int64_t ptts_debug_resample_launches(int32_t reset) {
     return reset ? g_resample_launches.exchange(0) : g_resample_launches.load();
 }

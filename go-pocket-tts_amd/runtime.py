@@ -209,7 +209,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
-    "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window",
+    "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window", "ptts_debug_flow_cluster",
 ]
 
 
@@ -1336,6 +1336,60 @@ def debug_tall_linear(x, w, *, bias=None, residual=None, epi=0, splitk=1, ln=Non
                                     _fp(w), _fp(b) if b is not None else nul, _fp(r) if r is not None else nul, 1 if out_planes else 0, _fp(out),
                                     _fp(xo) if xo is not None else nul))
     return (out[0] if s == 1 else out), xo
+
+
+class _FlowClusterArgs(C.Structure):   # ptts_flow_cluster_args
+    _fields_ = ([(n, C.c_int32) for n in ("rows", "depth", "n_launch", "in_place")] + [("tag_base0", C.c_uint32), ("reserved", C.c_int32)] +
+                [(n, C.c_int64) for n in ("ldmod", "launched_cap")] +
+                [(n, _FP) for n in ("fx", "ada", "ln_w", "ln_b", "b0", "b2", "eps", "w0", "w2")] +
+                [("launch_rows", C.POINTER(C.c_int32)), ("out", _FP), ("fx_back", _FP), ("state", C.POINTER(C.c_uint32)), ("launched", C.c_char_p)])
+
+
+FLOW_CLUSTER_TILES, FLOW_CLUSTER_TILE_ROWS = 22, 12
+
+
+def debug_flow_cluster(fx, ada, ln_w, ln_b, w0, b0, w2, b2, eps, *, launch_rows=None, in_place=True, tag_base0=0, null=()):
+    """k_flow_cluster (csrc/flow_cluster.hip) on host operands (ptts_debug_flow_cluster, include/ptts_debug.h): the launches `launch_rows` (default: one of
+    all rows) one after another on one granule buffer and one set of tag words starting at tag_base0.  fx [rows, 512], ada [rows, ldmod], ln_w / ln_b / b0 /
+    b2 [depth, 512], w0 / w2 [depth, 512, 512] f32, eps [depth].  Returns a dict: "out" [n_launch, rows, 512] (0xff bytes where nothing was stored), "fx_back"
+    (out of place: the launches' input copies afterwards, else None), "tags" (the 22 tiles' tag words), "fault" (the fault word), "launched" ({kernel:
+    count}).  A set fault word raises PttsError (PTTS_ENODEVICE) with the same dict as its `partial` attribute.  null: names of ptts_flow_cluster_args
+    pointers to pass as NULL (the refusal tests)."""
+    fx, ada, ln_w, ln_b, w0, b0, w2, b2 = [_f32(a) for a in (fx, ada, ln_w, ln_b, w0, b0, w2, b2)]
+    eps = np.ascontiguousarray(np.atleast_1d(np.asarray(eps, np.float32)))
+    depth = int(eps.shape[0])
+    if (fx.ndim != 2 or fx.shape[1] != 512 or ada.ndim != 2 or ada.shape[0] != fx.shape[0] or eps.ndim != 1 or
+            any(a.shape != (depth, 512) for a in (ln_w, ln_b, b0, b2)) or any(a.shape != (depth, 512, 512) for a in (w0, w2))):
+        raise PttsError(PTTS_EINVAL, "debug_flow_cluster: operand shapes do not fit (include/ptts_debug.h ptts_flow_cluster_args)")
+    rows = fx.shape[0]
+    lr = np.ascontiguousarray([rows] if launch_rows is None else launch_rows, np.int32).reshape(-1)
+    n = int(lr.shape[0])
+    out = np.empty((n, rows, 512), np.float32)
+    back = None if in_place else np.empty((n, rows, 512), np.float32)
+    state = np.zeros(FLOW_CLUSTER_TILES + 1, np.uint32)
+    launched = C.create_string_buffer(256)
+    a = _FlowClusterArgs()
+    a.rows, a.depth, a.n_launch, a.in_place, a.tag_base0 = rows, depth, n, (1 if in_place else 0), int(tag_base0)
+    a.ldmod, a.launched_cap = ada.shape[1], 256
+    a.fx, a.ada, a.ln_w, a.ln_b, a.b0, a.b2, a.eps, a.w0, a.w2 = [_fp(x) for x in (fx, ada, ln_w, ln_b, b0, b2, eps, w0, w2)]
+    a.launch_rows = C.cast(lr.ctypes.data, C.POINTER(C.c_int32))
+    a.out = _fp(out)
+    a.fx_back = _fp(back) if back is not None else C.cast(None, _FP)
+    a.state = C.cast(state.ctypes.data, C.POINTER(C.c_uint32))
+    a.launched = C.cast(launched, C.c_char_p)
+    for name in null:
+        setattr(a, name, C.cast(None, dict(_FlowClusterArgs._fields_)[name]))
+    H = hooks()
+    H.ptts_debug_flow_cluster.argtypes = [C.POINTER(_FlowClusterArgs)]
+    rc = H.ptts_debug_flow_cluster(C.byref(a))
+    res = {"out": out, "fx_back": back, "tags": state[:FLOW_CLUSTER_TILES].copy(), "fault": int(state[FLOW_CLUSTER_TILES]),
+           "launched": {kv.split("=")[0]: int(kv.split("=")[1]) for kv in launched.value.decode().split(";") if kv}}
+    try:
+        _check(rc)
+    except PttsError as e:
+        e.partial = res
+        raise
+    return res
 
 
 class _StepLinearArgs(C.Structure):   # ptts_step_linear_args

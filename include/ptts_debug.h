@@ -232,6 +232,33 @@ int ptts_debug_kweighting(int32_t sample_rate, double out[10]);
  * call is clean.  Nothing in the product sets it. */
 int ptts_debug_flow_cluster_inject(ptts_model* m, int32_t block);
 
+/* k_flow_cluster (csrc/flow_cluster.hip) stand-alone on host operands: a sequence of launches, FlowClusterArgs filled as runtime.cpp step_flow fills them.
+ *   fx [rows][512]; ada [rows][ldmod]: block r's shift | scale | gate at columns 3 r 512; ln_w, ln_b, b0, b2 [depth][512]; eps [depth];
+ *   w0, w2 [depth][512][512] f32 row-major, rounded to bf16 and tiled by the loader's pack_step_tiled.
+ *   launch_rows [n_launch]: the launches run one after another on ONE granule buffer and ONE set of tag words -- both zeroed as the batch set-up zeroes them,
+ *   then all 22 tiles' tag words set to tag_base0.  Launch i runs on its own device copy of fx's first launch_rows[i] rows (0xff bytes behind them);
+ *   in_place 1: fx_out == fx_in (production); 0: a separate output, and fx_back [n_launch][rows][512] receives the input copies after the launches.
+ *   On the device fx, the outputs and ada carry 3 slack rows of 0xff bytes behind `rows`.
+ *   out [n_launch][rows][512]: filled with 0xff bytes before the launches and returned whole; state [23]: the 22 tag words and the fault word after the
+ *   sequence; launched (launched_cap bytes): the census of the call ("kernel=count;").
+ * If a launch leaves the fault word set, nothing more is launched and -- out, state and the census delivered -- the call fails with PTTS_ENODEVICE ("hand-off
+ * timed out"); nothing is retried.  The hook has no way to set FlowClusterArgs::inject or ::stamps.
+ * PTTS_EINVAL with a message, before a device is asked for: rows outside [1, 264]; depth outside [1, 8]; ldmod % 4 != 0, ldmod < 3 depth 512 or ldmod > 65536;
+ * n_launch outside [1, 8]; a launch_rows entry outside [1, rows]; an odd tag_base0 (a launch's base is even: h tags are odd, x tags even); in_place not 0 / 1; a
+ * null operand (fx_back only with in_place 0; launched may be null).  With a device: a grid that is not resident at once (flow_cluster_fits) and whatever
+ * flow_cluster_supported refuses. */
+typedef struct ptts_flow_cluster_args {
+    int32_t rows, depth, n_launch, in_place;
+    uint32_t tag_base0;
+    int32_t reserved;
+    int64_t ldmod, launched_cap;
+    const float *fx, *ada, *ln_w, *ln_b, *b0, *b2, *eps, *w0, *w2;
+    const int32_t* launch_rows;
+    float *out, *fx_back;
+    uint32_t* state;
+    char* launched;
+} ptts_flow_cluster_args;
+int ptts_debug_flow_cluster(const ptts_flow_cluster_args* a);
 
 /* The check every entry point runs on a ptts_dsp_opts, without a model: out (cap bytes, terminated) receives its message, empty when the options are
  * fine; returns the message's length.  No GPU. */
