@@ -1100,6 +1100,7 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
         DspSpec spec;
         std::string e = dsp_resolve(opts, &spec);
         if (e.empty()) e = dsp_trim_refusal(spec);   // the output rows have the input's length
+        if (e.empty()) e = dsp_tempo_refusal(spec);
         if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
         for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i] || !out[i]);
         if (!spec.any()) {   // nothing switched on: a copy, no lock, no launch
@@ -1193,6 +1194,42 @@ int ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t) {
     }
     if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.trim = v.trim; e->v.trm = v.trm; }))
         return fail(strfmt("trim: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
+    return PTTS_OK;
+}
+
+// the device form of ptts_tempo_apply on host rows: the launches of a joined call's tempo; a row without one is copied on the host
+int ptts_tempo_rows(ptts_model* h, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
+    return guard([&] {
+        Model& m = model_of(h);
+        const RowsCheck check{"tempo"};
+        check.args(rows, !t || !in || !n || !out || !n_out);
+        std::vector<TempoScan> designs((size_t)rows);
+        std::vector<const TempoScan*> design((size_t)rows, nullptr);
+        for (int i = 0; i < rows; i++) {
+            check.row(i, n[i], !in[i] || !out[i]);
+            if (n[i] >= kTempoMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d has %lld samples, a row must stay below 2^31 - %d", i, (long long)n[i], kTempoRadius));
+            if (!t[i]) continue;
+            const std::string e = tempo_opts_error(t[i]);
+            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
+            if (n[i] > 0 && in[i] == out[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d: out is in", i));
+            designs[(size_t)i] = tempo_design(*t[i]);
+            design[(size_t)i] = &designs[(size_t)i];
+        }
+        if (rows > 0) tempo_rows_device(m, design.data(), in, n, rows, out, n_out);
+    });
+}
+
+// the tempo of a joined call's parts, attached to the handle (tempo.cpp checks and designs it, and stays a file that builds alone)
+int ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t) {
+    DspExt v;
+    if (t) {
+        const std::string err = tempo_opts_error(t);
+        if (!err.empty()) return fail(err);
+        v.tempo = true;
+        v.tmp = tempo_design(*t);
+    }
+    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.tempo = v.tempo; e->v.tmp = v.tmp; }))
+        return fail(strfmt("tempo: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
     return PTTS_OK;
 }
 

@@ -1,7 +1,8 @@
 // dsp_device.cpp -- the host side of the device post-processing (dsp.hip, compressor.hip, limiter.hip, true_peak.hip):
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
-// them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows.
+// them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the same for
+// the trim (trim.hip) and the tempo (tempo.hip) of a joined call's parts.
 #include <cmath>
 
 #include "row_tables.h"
@@ -297,6 +298,68 @@ void trim_rows_device(Model& m, const TrimScan* const* design, const float* cons
         info[i] = got[k];
         if (got[k].n_out > 0) PTTS_HIP(hipMemcpyAsync(out[i], tr[k].dst, (size_t)got[k].n_out * sizeof(float), hipMemcpyDeviceToHost, s));
     }
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the tempo (tempo.hip; tempo.h has the rule) ----
+
+void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const TempoScan*>& key, hipStream_t s) {
+    size_t hops = 0;
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (rows[i].n >= kTempoMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %zu has %lld samples, a row must stay below 2^31 - %d", i, (long long)rows[i].n, kTempoRadius));
+        rows[i].n_out = tempo_length(rows[i].n, key[i]->speed);
+        hops += (size_t)tempo_hops(rows[i].n_out);
+    }
+    int32_t* p = m.work(WORK_TEMPO_SCRATCH, std::max<size_t>(hops, 1) * sizeof(int32_t)).as<int32_t>();
+    for (TempoRow& r : rows) {
+        r.p = p;
+        p += tempo_hops(r.n_out);
+    }
+    launch_tables(m.tempo_ring, rows, key, kTempoMaxDesigns, same_bytes<TempoScan>, &TempoRow::design, "tempo", s,
+                  [&](size_t first, int k, const TempoRow* rows_dev, int, const TempoScan* designs_dev) {
+        int64_t tiles = 0;   // of the OUTPUT: a slowed row is longer than its input
+        for (int i = 0; i < k; i++) tiles = std::max(tiles, scan_tiles(rows[first + (size_t)i].n_out));
+        if (tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: tempo: too many samples for one launch");
+        launch_tempo(rows_dev, k, (int)tiles, designs_dev, s);
+    });
+}
+
+void tempo_rows_device(Model& m, const TempoScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    // the rows, then their time-scaled forms; a row that stays on the host takes no bytes
+    std::vector<size_t> bytes((size_t)rows * 2);
+    std::unique_ptr<bool[]> skip(new bool[(size_t)rows * 2 + 1]);
+    for (int i = 0; i < rows; i++) {
+        const int64_t len = design[i] ? tempo_length(n[i], design[i]->speed) : std::max<int64_t>(n[i], 0);
+        n_out[i] = len;
+        const bool sk = !design[i] || len <= 0;
+        skip[(size_t)i] = skip[(size_t)(rows + i)] = sk;
+        bytes[(size_t)i] = sk ? 0 : (size_t)n[i] * sizeof(float);
+        bytes[(size_t)(rows + i)] = sk ? 0 : (size_t)len * sizeof(float);
+    }
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
+    std::vector<TempoRow> tr;
+    std::vector<const TempoScan*> key;
+    std::vector<int> row_of;
+    for (int i = 0; i < rows; i++) {
+        if (skip[(size_t)i]) {   // nothing to do on the device: a copy, or an empty row
+            if (!design[i] && n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            continue;
+        }
+        buf.upload(i, in[i], s);
+        TempoRow r{};
+        r.src = (const float*)buf.row(i);
+        r.dst = (float*)buf.row(rows + i);
+        r.n = n[i];
+        tr.push_back(r);
+        key.push_back(design[i]);
+        row_of.push_back(i);
+    }
+    if (tr.empty()) return;
+    tempo_launch(m, tr, key, s);
+    for (int i : row_of) buf.download(rows + i, out[i], s);
     PTTS_HIP(hipStreamSynchronize(s));
 }
 

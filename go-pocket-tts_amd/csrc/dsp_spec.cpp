@@ -23,6 +23,8 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->lim = ext.lim;
     out->trim = ext.trim;
     out->trm = ext.trm;
+    out->tempo = ext.tempo;
+    out->tmp = ext.tmp;
     return std::string();
 }
 

@@ -15,6 +15,7 @@ struct DspSpec {
     bool compress = false; CmpScan cmp{};              // the first stage (compressor.h): everything above is measured and applied behind it
     bool limit = false; LimScan lim{};                 // the limiter (limiter.h): behind the fades, in front of the true-peak ceiling
     bool trim = false; TrimScan trm{};                 // the trim of a joined call's parts (trim.h): no stage of the chain, neither rest() nor any() counts it
+    bool tempo = false; TempoScan tmp{};               // the tempo of a joined call's parts (tempo.h), behind the trim: no stage of the chain either
     bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };
@@ -54,6 +55,10 @@ inline std::string dsp_opts_error(const ptts_dsp_opts& o) { DspSpec spec; return
 // Where a row's length is fixed before the decode (a request's own dsp, ptts_dsp_rows) a resolved spec with a trim is refused: the message, or empty
 inline std::string dsp_trim_refusal(const DspSpec& s) {
     return s.trim ? std::string("dsp: ext: trim changes a row's length; it is served by ptts_generate_joined and ptts_trim_rows") : std::string();
+}
+// ... and one with a tempo, likewise
+inline std::string dsp_tempo_refusal(const DspSpec& s) {
+    return s.tempo ? std::string("dsp: ext: tempo changes a row's length; it is served by ptts_generate_joined and ptts_tempo_rows") : std::string();
 }
 // whether o switches anything on, without an error: what dsp_resolve's spec says with any(), except that an eq counts unseen (so a dead one is
 // active, and refused where the row is resolved) and an ext that is not live counts for nothing.  One registry look-up at the most: it is

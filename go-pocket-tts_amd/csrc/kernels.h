@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "limiter.h"
+#include "tempo.h"
 #include "trim.h"
 
 namespace ptts {
@@ -430,6 +431,25 @@ static_assert(sizeof(TrimRow) == 48, "a turn of the trim ring holds 256 of them"
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row (0: empty rows only, which still get their record);
 // designs_dev: the table's designs
 void launch_trim(const TrimRow* rows_dev, int n, int max_tiles, const TrimScan* designs_dev, hipStream_t stream);
+
+// The speaking rate of the parts of a joined text (tempo.hip, tempo.h has the rule, tempo.cpp the host statement): behind
+// the trim and in front of k_join, from one buffer into another.  k_tempo_plan (one workgroup per row: the hops' read positions, in order) and
+// k_tempo_store (every tile of the OUTPUT: the copy or the blend).  A table's distinct designs (at most kTempoMaxDesigns) travel behind its rows.
+constexpr int kTempoMaxDesigns = 16;
+constexpr size_t kTempoScanBytes = 16;
+static_assert(sizeof(TempoScan) == kTempoScanBytes, "the tempo ring's tail (runtime.h) is sized by it");
+struct TempoRow {
+    const float* src;        // the row's samples (device)
+    float* dst;              // the time-scaled row (device), [n_out]: another buffer than src
+    int64_t n;               // samples, below kTempoMaxSamples; nothing outside [0, n) is read
+    int64_t n_out;           // tempo_length(n, the design's speed): made on the host, the kernels compute no length
+    int32_t* p;              // [tempo_hops(n_out)]: the hops' positions; k_tempo_plan writes them, k_tempo_store reads them
+    int32_t design, pad;     // the index of the row's design among the table's
+};
+static_assert(sizeof(TempoRow) == 48, "a turn of the tempo ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n_out / kDspTile) of a row (0: empty rows only, nothing is launched);
+// designs_dev: the table's designs
+void launch_tempo(const TempoRow* rows_dev, int n, int max_tiles, const TempoScan* designs_dev, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

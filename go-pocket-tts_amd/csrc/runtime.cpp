@@ -1575,6 +1575,8 @@ struct JoinSink {
     bool trim = false;            // the join options' ext carries a trim (resolved once, before anything launches): every part goes through
     TrimScan trm{};               // k_trim_* in front of k_join, and its length is what comes back in `info`
     ptts_trim_info* info = nullptr;   // page-locked, [max_batch]: a group's records (Model::trim_info)
+    bool tempo = false;           // ... and a tempo (tempo.h): every part goes through k_tempo_* behind the trim and in front of k_join, and its
+    TempoScan tmp{};              // length is tempo_length of what the trim left: host arithmetic, nothing comes back
 };
 
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
@@ -1934,7 +1936,8 @@ void Chunk::deliver() {
 }
 
 // generate_joined's delivery (behind the fault check: a group that is run again has joined nothing yet): the parts' records; the decode of
-// the whole group into the decoder's buffer; with a trim (trim.h), the rows' trimmed forms and their lengths; one k_join table that copies the
+// the whole group into the decoder's buffer; with a trim (trim.h), the rows' trimmed forms and their lengths; with a tempo (tempo.h), their
+// time-scaled forms; one k_join table that copies the
 // group's rows behind what the text's row holds.  A seam inside
 // the group is computed by the row behind it, which reads its predecessor's tail in the decoder's buffer.  The group's first row has its
 // predecessor in an earlier group, whose buffer is gone: that group stored the tail unfaded, and this row fades it where it lies.
@@ -1983,11 +1986,28 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
         part0 = kept;
         mark("trim");
     }
+    // ... and with a tempo their time-scaled forms, in a buffer whose row stride holds the longest a decoded row can become
+    int64_t stride = (int64_t)T * spf;
+    if (join->tempo) {
+        const int64_t wide = std::max(stride, tempo_length(stride, join->tmp.speed));
+        float* const scaled = m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide, 1) * sizeof(float)).as<float>();
+        std::vector<TempoRow> tr((size_t)B);
+        for (int i = 0; i < B; i++) {
+            tr[(size_t)i].src = part0 + (size_t)i * (size_t)stride;
+            tr[(size_t)i].dst = scaled + (size_t)i * (size_t)wide;
+            tr[(size_t)i].n = len[(size_t)i];
+        }
+        tempo_launch(m, tr, std::vector<const TempoScan*>((size_t)B, &join->tmp), s);
+        for (int i = 0; i < B; i++) len[(size_t)i] = tr[(size_t)i].n_out;
+        part0 = scaled;
+        stride = wide;
+        mark("tempo");
+    }
     std::vector<JoinRow> rows;
     for (int i = 0; i < B; i++) {
         ptts_join_part& p = join->parts[idx[(size_t)i]];
         const int64_t n = len[(size_t)i];
-        const float* src = part0 + (size_t)i * T * spf;
+        const float* src = part0 + (size_t)i * (size_t)stride;
         const bool first = join->n_prev < 0;
         const int64_t k = first ? 0 : join_seam(l.xfade, join->n_prev, n);
         const int64_t off = first ? 0 : join->at + l.gap - k;
@@ -1995,7 +2015,7 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
         if (off + n > join->cap) throw Error(PTTS_EINVAL, "ptts-hip: internal: the joined row is smaller than the text");
         JoinRow r{};
         r.src = src;
-        r.prev = !k ? nullptr : i ? part0 + (size_t)(i - 1) * T * spf + (join->n_prev - k) : join->row + off;
+        r.prev = !k ? nullptr : i ? part0 + (size_t)(i - 1) * (size_t)stride + (join->n_prev - k) : join->row + off;
         r.dst = join->row;
         r.off = off; r.n = n - k_next; r.k = (int32_t)k; r.gap = first ? 0 : (int32_t)l.gap;
         rows.push_back(r);
@@ -2033,6 +2053,7 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
         DspSpec spec;
         std::string e = dsp_resolve(q.dsp, &spec);
         if (e.empty()) e = dsp_trim_refusal(spec);   // a request's result buffers are sized before the decode
+        if (e.empty()) e = dsp_tempo_refusal(spec);
         if (!e.empty()) return "generate: " + e;
         if (q.pcm_callback) {   // the peak and the end are not known when samples are handed over; the filter and the fade in are refused with it for now
             const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : q.dsp->eq ? "eq" : q.dsp->ext ? "ext" : nullptr;
@@ -2141,12 +2162,14 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     if (e.empty()) e = join_egress_error(o);
     if (e.empty() && (n < 1 || n > kJoinMaxRows)) e = strfmt("join: %d requests, a text has from 1 to %d parts", n, kJoinMaxRows);
     if (!e.empty()) refuse(e);
-    if (o.dsp) {   // the trim of the parts, resolved once: the chain below never sees it
+    if (o.dsp) {   // the trim and the tempo of the parts, resolved once: the chain below never sees them
         DspSpec spec;
         e = dsp_resolve(o.dsp, &spec);
         if (!e.empty()) refuse("join: " + e);
         sink.trim = spec.trim;
         sink.trm = spec.trm;
+        sink.tempo = spec.tempo;
+        sink.tmp = spec.tmp;
     }
     const int lsd = reqs[0].lsd_steps <= 0 ? 1 : reqs[0].lsd_steps;
     const int t_limit = ROPE_SEQ / d.up_stride;
@@ -2160,7 +2183,8 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (f) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d sets %s, which belongs in the join options (ptts_join_opts) of a joined call", i, f)); }
         const int l = q.lsd_steps <= 0 ? 1 : q.lsd_steps;
         if (l != lsd) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d has lsd_steps %d and request 0 has %d: the groups would leave text order", i, l, lsd)); }
-        bound += (int64_t)std::min(resolve_max_steps(q), t_limit) * spf + (i ? sink.lens.gap : 0);
+        const int64_t budget = (int64_t)std::min(resolve_max_steps(q), t_limit) * spf;   // (the trim only shortens; tempo_length is monotone)
+        bound += (sink.tempo ? std::max(budget, tempo_length(budget, sink.tmp.speed)) : budget) + (i ? sink.lens.gap : 0);
     }
     if (bound >= kJoinMaxSamples) refuse(strfmt("join: the step budgets allow %lld samples, the joined length must stay below 2^31", (long long)bound));
     ptts_request eg{};   // the chain and the egress of the joined row, as a request states its own: results_deliver serves it like one

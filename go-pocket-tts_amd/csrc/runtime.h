@@ -70,6 +70,8 @@ enum WorkSlot : size_t {
     WORK_JOINED = 31,            // generate_joined: the text's joined row, sized before the first group runs and kept until the egress has read it
     WORK_TRIMMED = 32,           // generate_joined with a trim: what k_trim_store keeps of a group's decoded rows, at the decoder buffer's row stride
     WORK_TRIM_SCRATCH = 33,      // trim_launch: the rows' ptts_trim_info records, then their TrimTile tables
+    WORK_TEMPO = 34,             // generate_joined with a tempo: a group's time-scaled rows, at the stride of the longest a decoded row can become
+    WORK_TEMPO_SCRATCH = 35,     // tempo_launch: the rows' position tables
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -129,6 +131,7 @@ struct Model {
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, runtime.cpp)
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (trim_launch, dsp_device.cpp)
+    RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (tempo_launch, dsp_device.cpp)
     PinnedBuf trim_info;            // generate_joined with a trim: a group's ptts_trim_info records, [max_batch] (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
@@ -428,6 +431,12 @@ const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const st
 // ptts_trim_rows: the rows packed into one device buffer with their trimmed forms behind them, uploaded, trim_launch, the records back, then what
 // stays of each row.  Takes Model::mu.  design[i] null: the row is copied on the host
 void trim_rows_device(Model& m, const TrimScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info);
+// The tempo of a list of rows on s (tempo.hip; tempo.h has the rule): rows[i] states src, dst and n, key[i] its design; n_out (host arithmetic),
+// the position tables (WORK_TEMPO_SCRATCH) and the row tables are made here, one launch of each kernel per table
+void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const TempoScan*>& key, hipStream_t s);
+// ptts_tempo_rows: the rows packed into one device buffer with their time-scaled forms behind them, uploaded, tempo_launch, the results back, one
+// wait.  Takes Model::mu.  design[i] null: the row is copied on the host.  n_out[i]: what out[i] received
+void tempo_rows_device(Model& m, const TempoScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out);
 
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)

@@ -116,6 +116,15 @@ class TrimInfo(C.Structure):   # ptts_trim_info: what a trim made of one row
         return (int(self.lo), int(self.hi), int(self.n_out), int(self.cuts), int(self.speech))
 
 
+class TempoOpts(C.Structure):   # ptts_tempo_opts
+    """The speaking rate of a joined call's parts (ptts_tempo_opts): speed_permille 500 .. 2000 (1000: unchanged, 1250: a quarter faster and a
+    fifth shorter), the pitch kept.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("speed_permille", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, speed_permille: int = 1000, size: Optional[int] = None, reserved=(0, 0)):
+        super().__init__(C.sizeof(TempoOpts) if size is None else int(size), int(speed_permille), (C.c_int32 * 2)(*[int(v) for v in reserved]))
+
+
 class JoinOpts(C.Structure):   # ptts_join_opts
     """How a text's parts become one utterance (ptts_join_opts): gap_ms of silence between consecutive parts or crossfade_ms of overlap (each
     0 .. 2000, not both), and -- for Model.generate_joined -- the chain (dsp: a DspOpts; loudness in 0.01 LUFS), run once over the joined audio,
@@ -201,6 +210,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
     "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined",
     "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
+    "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -320,6 +330,12 @@ def lib():
         L.ptts_trim_apply.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, _FP, C.POINTER(TrimInfo)]
         L.ptts_trim_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TrimOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), C.POINTER(TrimInfo)]
         L.ptts_dsp_ext_set_trim.argtypes = [C.c_void_p, C.POINTER(TrimOpts)]
+        L.ptts_tempo_length.argtypes = [C.POINTER(TempoOpts), C.c_int64]
+        L.ptts_tempo_length.restype = C.c_int64
+        L.ptts_tempo_plan.argtypes = [C.POINTER(TempoOpts), _FP, C.c_int64, C.POINTER(C.c_int32)]
+        L.ptts_tempo_apply.argtypes = [C.POINTER(TempoOpts), _FP, C.c_int64, _FP]
+        L.ptts_tempo_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TempoOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), _IP]
+        L.ptts_dsp_ext_set_tempo.argtypes = [C.c_void_p, C.POINTER(TempoOpts)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -784,6 +800,19 @@ class Model:
         outs = [o[:int(infos[i].n_out)] for i, o in enumerate(outs)]
         recs = [TrimInfo(v.lo, v.hi, v.n_out, v.cuts, v.speech, 0) for v in infos[:n]]
         return (outs[0], recs[0]) if single else (outs, recs)
+
+    def tempo_rows(self, x, tempo):
+        """ptts_tempo_rows: tempo_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch of each kernel for all), by the
+        kernels generate_joined runs.  tempo: one TempoOpts for every row, or one per row (None copies that row).  Returns the time-scaled rows."""
+        single, rows, n, pp, ns = _rows_in(x)
+        per_row = list(tempo) if isinstance(tempo, (list, tuple)) else [tempo] * n
+        # (sized here, so that options the library refuses reach the library: it names the row)
+        outs = [np.empty(r.size if o is None else r.size * 1000 // min(max(int(o.speed_permille), 500), 2000), np.float32) for r, o in zip(rows, per_row)]
+        po = (C.POINTER(TempoOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_row])
+        lens = np.zeros(max(n, 1), np.int64)
+        _check(lib().ptts_tempo_rows(self.h, po, pp, _ip(ns), n, _row_ptrs(outs), _ip(lens)))
+        outs = [o[:int(lens[i])] for i, o in enumerate(outs)]
+        return outs[0] if single else outs
 
     def true_peak_rows(self, x):
         """ptts_true_peak_rows: true_peak() of mono f32 rows at 24 kHz (an array, or a list: one launch for all), measured on the device."""
@@ -1956,12 +1985,13 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
 
 class DspExt:
     """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
-    (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off).
+    (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off)
+    and their tempo (a TempoOpts; None: off).
     With none of them the handle switches nothing on.  It belongs to no
     model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
 
     def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
-                 limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None):
+                 limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None, tempo: Optional["TempoOpts"] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -1978,6 +2008,8 @@ class DspExt:
             self.set_limiter(limiter)
         if trim is not None:
             self.set_trim(trim)
+        if tempo is not None:
+            self.set_tempo(tempo)
 
     def set_compressor(self, compressor: Optional[CompressorOpts]):
         """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
@@ -1991,6 +2023,11 @@ class DspExt:
         """ptts_dsp_ext_set_trim: attaches the trim of a joined call's parts (None: off again).  Served by Model.generate_joined, whose JoinOpts.dsp
         names the handle; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
         _check(lib().ptts_dsp_ext_set_trim(self.h, None if trim is None else C.byref(trim)))
+
+    def set_tempo(self, tempo: Optional[TempoOpts]):
+        """ptts_dsp_ext_set_tempo: attaches the tempo of a joined call's parts (None: off again).  Served by Model.generate_joined, whose
+        JoinOpts.dsp names the handle, behind the trim; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
+        _check(lib().ptts_dsp_ext_set_tempo(self.h, None if tempo is None else C.byref(tempo)))
 
     def free(self):
         if self.h:
@@ -2042,6 +2079,31 @@ def trim_apply(trim: TrimOpts, samples, in_place: bool = False):
     info = TrimInfo()
     _check(lib().ptts_trim_apply(C.byref(trim), _fp(x), x.size, _fp(out), C.byref(info)))
     return out[:int(info.n_out)].copy(), info
+
+
+def tempo_length(tempo: TempoOpts, n: int) -> int:
+    """ptts_tempo_length: the samples of the time-scaled form of a row of n samples.  Host."""
+    got = int(lib().ptts_tempo_length(C.byref(tempo), int(n)))
+    if got < 0:
+        _check(-got)
+    return got
+
+
+def tempo_plan(tempo: TempoOpts, samples) -> np.ndarray:
+    """ptts_tempo_plan: the read positions of the hops of mono f32 samples at 24 kHz, int32 [ceil(tempo_length / 480)].  Host."""
+    x = _f32(samples).reshape(-1)
+    hops = (tempo_length(tempo, x.size) + 479) // 480
+    p = np.zeros(max(hops, 1), np.int32)
+    _check(lib().ptts_tempo_plan(C.byref(tempo), _fp(x), x.size, p.ctypes.data_as(C.POINTER(C.c_int32))))
+    return p[:hops]
+
+
+def tempo_apply(tempo: TempoOpts, samples) -> np.ndarray:
+    """ptts_tempo_apply: the time-scaled row as a new array.  Host: the statement of what Model.tempo_rows and a joined call's tempo compute."""
+    x = _f32(samples).reshape(-1)
+    out = np.empty(max(tempo_length(tempo, x.size), 1), np.float32)
+    _check(lib().ptts_tempo_apply(C.byref(tempo), _fp(x), x.size, _fp(out)))
+    return out[:tempo_length(tempo, x.size)].copy()
 
 
 def true_peak(samples) -> float:

@@ -546,6 +546,54 @@ int  ptts_trim_rows(ptts_model* m, const ptts_trim_opts* const* t, const float* 
                     ptts_trim_info* info /* [rows] */);
 int  ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t);
 
+/* The speaking rate of the parts of a joined text: a tempo change that keeps the pitch, per part, behind the trim and
+ * IN FRONT of the join.  The order of a joined call: trim per part -> tempo per part -> join -> the chain of `dsp` and `loudness` once ->
+ * egress.  ("tempo", not "rate": a rate is a sample rate in this library.)
+ *
+ * On a row x[0, n) at 24 kHz, n below 2^31 - 240, with s = speed_permille (500 .. 2000; 1000: unchanged, 2000: twice as fast and half as
+ * long), the hop Hs = 480 (20 ms) and the search radius D = 240 (+-10 ms).  Every index is an integer; a sample outside [0, n) reads as 0.0f
+ * and its quantised value as 0.
+ *   - length: n_out = (n * 1000) / s in int64 with integer division, F = ceil(n_out / Hs) hops; n == 0 or n_out == 0 is an empty row;
+ *   - quantised view: q[i] = 0 for a NaN, else (int32)(clamp(x[i], -1, 1) * 32767.0f), truncated towards zero; infinities clamp;
+ *   - positions: p_0 = 0, and for hop k >= 1 with a_k = (k * Hs * s) / 1000 (where the input should be read) and c_k = p_(k-1) + Hs (where
+ *     the previous hop's segment continues):  S(d) = sum over j in [0, Hs) of |q[a_k + d + j] - q[c_k + j]| for d in [-D, D] (it fits an
+ *     int32), d* minimises (S(d), |d|, d > 0) lexicographically -- the least S, then the least |d|, then the negative one -- and
+ *     p_k = a_k + d*.  A position may be negative or run past n;
+ *   - output, m in [0, n_out), k = m / Hs, j = m % Hs:  k == 0 or p_k == c_k (the hop continues its predecessor): out[m] = x[p_k + j], moved
+ *     as its 32 bits; otherwise out[m] = x[c_k + j] * ((float)(Hs - j) / (float)Hs) + x[p_k + j] * ((float)j / (float)Hs): two f32
+ *     divisions, two f32 products and one f32 sum, each rounded once, nothing fused.
+ * Every decision is integer arithmetic: the host and the device choose the same positions and give the same bits, and no tolerance applies.
+ * s == 1000 returns the row bit for bit (d = 0 has S = 0 and the least |d|: every hop continues).  The continuation has S = 0 whenever it lies
+ * inside the search window, so stretches of the input pass through untouched between splices.  The last hop of a slowed row may fade into
+ * the zeros behind n.  Audio above +-1 is clamped in the search only, never in the output.  n stays below 2^31 - 240 so that a position
+ * (at most n + 239) is an int32.
+ * ptts_tempo_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_tempo_length: n_out for a row of n samples, or -PTTS_EINVAL.  Host.
+ * ptts_tempo_plan: the F positions of x[0, n)'s hops into positions (F = ceil(ptts_tempo_length / 480)); for tests and captions.  Host.
+ * ptts_tempo_apply: the time-scaled row into out, which holds ptts_tempo_length floats and is not in.  Host: the statement of the result.
+ * ptts_tempo_rows: the same on rows of host samples on the device, by the kernels ptts_generate_joined runs (k_tempo_plan, k_tempo_store),
+ *     shaped like ptts_trim_rows: one upload, one launch of each kernel per 256 rows, one download.  t[i] NULL copies row i (n_out[i] = n[i]);
+ *     n[i] >= 0; out[i] holds ptts_tempo_length(t[i], n[i]) floats and is not in[i] (with t[i] NULL it holds n[i] and may be); n_out ([rows])
+ *     is required; a bad row is named.
+ * ptts_dsp_ext_set_tempo attaches the tempo to a live handle of ptts_dsp_ext_create (t NULL: off again); a handle that is not live is
+ *     PTTS_EINVAL and is not read.  Set it before calls name the handle, not while they run.  It is served by ptts_generate_joined, whose join
+ *     options' `dsp` names the handle: parts[i].offset and parts[i].n_samples count the time-scaled audio, parts[i].n_frames and out->n_frames
+ *     still count decoded frames, and a text whose step budgets, slowed, allow 2^31 samples or more is refused.  Everywhere a row's length is
+ *     fixed before the decode it is refused with PTTS_EINVAL, nothing launched ("dsp: ext: tempo changes a row's length ..."): a
+ *     ptts_request.dsp whose ext carries a tempo (ptts_generate, the dispatcher, the continuous engine, streaming) and ptts_dsp_rows. */
+typedef struct ptts_tempo_opts {
+    uint32_t size;             /* sizeof(ptts_tempo_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  speed_permille;   /* 500 .. 2000: 1000 leaves the row as it is, 1250 is a quarter faster, 800 a quarter slower */
+    int32_t  reserved[2];      /* 0 */
+} ptts_tempo_opts;
+int64_t ptts_tempo_length(const ptts_tempo_opts* t, int64_t n);
+int  ptts_tempo_plan(const ptts_tempo_opts* t, const float* x, int64_t n, int32_t* positions /* [F] */);
+int  ptts_tempo_apply(const ptts_tempo_opts* t, const float* in, int64_t n, float* out);
+int  ptts_tempo_rows(ptts_model* m, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out,
+                     int64_t* n_out /* [rows] */);
+int  ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t);
+
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
  * tokens, and derive each chunk's step budget and EOS tail.  The SentencePiece encoder is the caller's. */
@@ -800,7 +848,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_compress_gain, ptts_compress_apply, ptts_compress_rows; ptts_limiter_opts with ptts_dsp_ext_set_limiter, ptts_limit_apply,
  * ptts_limit_rows; the new structs ptts_join_opts and ptts_join_part, which change no existing one, with ptts_join_length, ptts_join, ptts_join_rows,
  * ptts_generate_joined; the new structs ptts_trim_opts and ptts_trim_info, likewise, with ptts_trim_plan, ptts_trim_apply, ptts_trim_rows,
- * ptts_dsp_ext_set_trim */
+ * ptts_dsp_ext_set_trim; the new struct ptts_tempo_opts, likewise, with ptts_tempo_length, ptts_tempo_plan, ptts_tempo_apply, ptts_tempo_rows,
+ * ptts_dsp_ext_set_tempo */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
