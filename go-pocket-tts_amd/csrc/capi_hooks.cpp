@@ -1083,6 +1083,109 @@ int ptts_debug_resblock(const ptts_resblock_args* pa) {
     });
 }
 
+// ---- the kernels of csrc/ffn_fused.hip stand-alone ----
+// the loader's image packers on a caller's matrices (no GPU)
+int ptts_debug_mimi_pack(int32_t kind, const float* w1, const float* w2, int32_t n, uint16_t* dst) {
+    return guard([&] {
+        if (!w1 || !dst || n < 32 || n % 32 || kind < 0 || kind > 1 || (kind == 0 && !w2)) throw Error(PTTS_EINVAL, "ptts_debug_mimi_pack: bad arguments");
+        if (kind == 0) pack_ffn_image(w1, w2, n, dst);
+        else pack_w1_image(w1, n, dst);
+    });
+}
+
+// ONE launch of k_mimi_ffn / k_mimi_rowlin on host operands.  Both kernels clamp a block's rows past M to row M - 1 and bound nothing else, so every row of
+// both maps and every table position is checked against the caller's buffers here, before anything is uploaded.
+int ptts_debug_mimi_fused(const ptts_mimi_fused_args* pa) {
+    return guard([&] {
+        if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: null argument");
+        const ptts_mimi_fused_args& t = *pa;
+        if (t.kind < 0 || t.kind > 1) throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: unknown kind %d", t.kind));
+        const bool ffn = t.kind == 0;
+        if (!t.x || !t.ln_w || !t.ln_b || !t.w1 || !t.out || (ffn && !t.w2) || t.M < 1 || t.M > (1 << 20) || t.D < 1 || t.D > 4096 || t.F < 1 || t.F > 8192 ||
+            t.x_elems < 1 || t.x_ld < 1 || t.x_rows_per_batch < 0 || t.x_rows_per_batch > INT32_MAX || t.x_batch_stride < 0 || t.x_off < 0 || t.ls_off < 0 || t.ls_off > 64)
+            throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: bad arguments");
+        if (!ffn && (t.y_elems < 1 || t.y_ld < 1 || t.y_rows_per_batch < 0 || t.y_rows_per_batch > INT32_MAX || t.y_batch_stride < 0 || t.y_off < 0 || t.ls))
+            throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: bad arguments for k_mimi_rowlin");
+        const bool rope = t.rope_cos || t.rope_sin;
+        if (rope && (ffn || !t.rope_cos || !t.rope_sin || t.n_pos < 1 || t.pos0 < 0 || t.rows_per_seg < 0 || t.rope_cols < 0))
+            throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: bad RoPE arguments");
+        const int M = t.M, D = t.D, F = t.F;
+        // the maps against the buffers; rows that are stored to must not overlap (two lanes would store to one element)
+        auto check_map = [&](const char* what, int64_t elems, int64_t ld, int64_t rpb, int64_t bs, int64_t off, int width, bool disjoint) {
+            std::vector<int64_t> start((size_t)M);
+            for (int64_t m = 0; m < M; m++) {
+                const int64_t o = off + (rpb ? (m / rpb) * bs + (m % rpb) * ld : m * ld);
+                if (o < 0 || o + width > elems)
+                    throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: row %lld of %s ends at element %lld of %lld", (long long)m, what, (long long)(o + width), (long long)elems));
+                start[(size_t)m] = o;
+            }
+            if (!disjoint) return;
+            std::sort(start.begin(), start.end());
+            for (size_t i = 1; i < start.size(); i++)
+                if (start[i] - start[i - 1] < width) throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: rows of %s overlap (elements %lld and %lld)", what, (long long)start[i - 1], (long long)start[i]));
+        };
+        check_map("x", t.x_elems, t.x_ld, t.x_rows_per_batch, t.x_batch_stride, t.x_off, D, ffn);
+        if (!ffn) check_map("y", t.y_elems, t.y_ld, t.y_rows_per_batch, t.y_batch_stride, t.y_off, F, true);
+        if (rope)
+            for (int64_t m = 0; m < M; m++) {
+                const int64_t pos = (int64_t)t.pos0 + (t.rows_per_seg ? m % t.rows_per_seg : m);
+                if (pos >= t.n_pos) throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: row %lld at position %lld, the tables hold %d", (long long)m, (long long)pos, t.n_pos));
+            }
+        require_device();
+        const size_t img_entries = ffn ? ffn_image_count(F) : w1_image_count(F), ntab = rope ? (size_t)t.n_pos * 32 : 0;
+        Tmp dX((size_t)t.x_elems * 4), dY(ffn ? 0 : (size_t)t.y_elems * 4), dLw((size_t)D * 4), dLb((size_t)D * 4), dLs(((size_t)D + t.ls_off) * 4), dImg(img_entries * 2),
+            dCos(ntab * 4), dSin(ntab * 4);
+        FfnArgs fa;
+        RowLinArgs ra;
+        if (ffn) {
+            fa.x = dX.as<float>() + t.x_off; fa.xmap = RowMap{t.x_ld, t.x_rows_per_batch, t.x_batch_stride};
+            fa.ln_w = dLw.as<float>(); fa.ln_b = dLb.as<float>(); fa.eps = t.eps;
+            fa.img = dImg.p;
+            if (t.ls) fa.ls = dLs.as<float>() + t.ls_off;
+            fa.M = M; fa.D = D; fa.F = F;
+            if (!mimi_ffn_supported(fa)) throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: refused by mimi_ffn_supported");
+        } else {
+            ra.x = dX.as<float>() + t.x_off; ra.xmap = RowMap{t.x_ld, t.x_rows_per_batch, t.x_batch_stride};
+            ra.ln_w = dLw.as<float>(); ra.ln_b = dLb.as<float>(); ra.eps = t.eps;
+            ra.img = dImg.p;
+            ra.y = dY.as<float>() + t.y_off; ra.ymap = RowMap{t.y_ld, t.y_rows_per_batch, t.y_batch_stride};
+            if (rope) { ra.rope_cos = dCos.as<float>(); ra.rope_sin = dSin.as<float>(); ra.rope_cols = t.rope_cols; ra.rope_pos0 = t.pos0; ra.rope_rows_per_seg = t.rows_per_seg; }
+            ra.M = M; ra.N = F; ra.K = D;
+            if (!mimi_rowlin_supported(ra)) throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: refused by mimi_rowlin_supported");
+        }
+        // (D == 512 from here on: the packers' width)
+        std::vector<uint16_t> img(img_entries);
+        if (ffn) pack_ffn_image(t.w1, t.w2, F, img.data());
+        else pack_w1_image(t.w1, F, img.data());
+        up(dImg.p, img.data(), img_entries * 2);
+        up(dX.p, t.x, (size_t)t.x_elems * 4);
+        up(dLw.p, t.ln_w, (size_t)D * 4); up(dLb.p, t.ln_b, (size_t)D * 4);
+        if (t.ls) up(dLs.as<float>() + t.ls_off, t.ls, (size_t)D * 4);
+        if (rope) { up(dCos.p, t.rope_cos, ntab * 4); up(dSin.p, t.rope_sin, ntab * 4); }
+        if (!ffn) PTTS_HIP(hipMemset(dY.p, 0xff, (size_t)t.y_elems * 4));
+        std::map<std::string, int64_t> census;
+        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        g_launch_census = &census;
+        try {
+            if (ffn) launch_mimi_ffn(fa, nullptr);
+            else launch_mimi_rowlin(ra, nullptr);
+        } catch (...) { g_launch_census = census_before; throw; }
+        g_launch_census = census_before;
+        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        PTTS_HIP(hipGetLastError());
+        PTTS_HIP(hipDeviceSynchronize());
+        if (t.launched && t.launched_cap > 0) {
+            std::string s;
+            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
+            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
+            std::memcpy(t.launched, s.data(), n);
+            t.launched[n] = 0;
+        }
+        if (ffn) down(t.out, dX.p, (size_t)t.x_elems * 4);
+        else down(t.out, dY.p, (size_t)t.y_elems * 4);
+    });
+}
+
 int ptts_mimi_layer_piece(ptts_model* h, int32_t layer, int32_t which, const float* x, int64_t rows, int32_t pos0, int32_t rows_per_seg, float* out) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");

@@ -106,6 +106,55 @@ void pack_final_frag(const float* w, size_t n, uint16_t* hi, uint16_t* lo) {
             }
 }
 
+// linear1 [F][512] and linear2 [512][F] of a Mimi transformer layer as the LDS images of k_mimi_ffn (ffn_fused.hip), bf16: per chunk c of 32 hidden
+// units 64 KB that are copied to LDS as they are --
+//   W1 image (32 KB): [k pair j (8)][hidden unit h (32)][128 B]; the 16-byte piece (k-step parity sg, lane group q) of row h sits at position
+//     (4 sg + q) ^ ((h >> 1) & 7) and holds W1[32c + h][k] for k = 32 (2j + sg) + 4q + (0..3), then 32 (2j + sg) + 16 + 4q + (0..3);
+//   W2 image (32 KB): [output o (512)][64 B]; lane group q's piece at position q ^ (3 ((o >> 3) & 1)) holds W2[o][32c + 4q + (0..3)], then
+//     W2[o][32c + 16 + 4q + (0..3)].
+// The positions make every ds_read_b128 fragment read conflict-free (16 lanes of a service group on 16 different 16-byte bank slots); the k order
+// inside a piece is the order in which a pair of 16x16 accumulator tiles hands its values to the next product.
+// The loader (add_w1_image / add_ffn_image below) and the kernels' test hook (ptts_debug_mimi_fused) pack with these functions.
+// rows [32c, 32c + 32) of a row-major [N][512] matrix as one 32-KB W1-format image
+static void w1_image_chunk(const float* w, int c, uint16_t* i1) {
+    const int D = 512;
+    for (int j = 0; j < 8; j++)
+        for (int h = 0; h < 32; h++)
+            for (int sg = 0; sg < 2; sg++)
+                for (int q = 0; q < 4; q++) {
+                    const int pos = (4 * sg + q) ^ ((h >> 1) & 7), s = 2 * j + sg;
+                    uint16_t* p = i1 + ((size_t)j * 32 + h) * 64 + pos * 8;
+                    for (int e = 0; e < 8; e++) {
+                        const int k = 32 * s + (e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4));
+                        p[e] = f32_to_bf16_rne(w[(size_t)(32 * c + h) * D + k]);
+                    }
+                }
+}
+size_t w1_image_count(int N) { return (size_t)(N / 32) * 16384; }
+size_t ffn_image_count(int F) { return (size_t)(F / 32) * 32768; }
+// a [N][512] matrix as N / 32 consecutive W1-format images (k_mimi_rowlin)
+void pack_w1_image(const float* rm, int N, uint16_t* dst) {
+    for (int c = 0; c < N / 32; c++) w1_image_chunk(rm, c, dst + (size_t)c * 16384);
+}
+// per chunk of 32 hidden units: the W1 image of linear1's rows, then the W2 image of linear2's columns (k_mimi_ffn)
+void pack_ffn_image(const float* w1, const float* w2, int F, uint16_t* dst) {
+    const int D = 512, nch = F / 32;
+    for (int c = 0; c < nch; c++) {
+        uint16_t* i1 = dst + (size_t)c * 32768;          // (uint16 units: 64 KB per chunk)
+        uint16_t* i2 = i1 + 16384;
+        w1_image_chunk(w1, c, i1);
+        for (int o = 0; o < D; o++)
+            for (int q = 0; q < 4; q++) {
+                const int pos = q ^ (3 * ((o >> 3) & 1));
+                uint16_t* p = i2 + (size_t)o * 32 + pos * 8;
+                for (int e = 0; e < 8; e++) {
+                    const int hcol = 32 * c + (e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4));
+                    p[e] = f32_to_bf16_rne(w2[(size_t)o * F + hcol]);
+                }
+            }
+    }
+}
+
 namespace {
 
 struct Walker {
@@ -213,58 +262,19 @@ struct Walker {
         fill_rowmajor(rm.data());
         pack_frag16(rm.data(), (size_t)l.out, (size_t)l.in, reinterpret_cast<uint16_t*>(host + l.wf), bf16w ? nullptr : reinterpret_cast<uint16_t*>(host + l.wf_lo));
     }
-    // linear1 [F][512] and linear2 [512][F] of a Mimi transformer layer as the LDS images of k_mimi_ffn (ffn_fused.hip), bf16: per chunk c of 32 hidden
-    // units 64 KB that are copied to LDS as they are --
-    //   W1 image (32 KB): [k pair j (8)][hidden unit h (32)][128 B]; the 16-byte piece (k-step parity sg, lane group q) of row h sits at position
-    //     (4 sg + q) ^ ((h >> 1) & 7) and holds W1[32c + h][k] for k = 32 (2j + sg) + 4q + (0..3), then 32 (2j + sg) + 16 + 4q + (0..3);
-    //   W2 image (32 KB): [output o (512)][64 B]; lane group q's piece at position q ^ (3 ((o >> 3) & 1)) holds W2[o][32c + 4q + (0..3)], then
-    //     W2[o][32c + 16 + 4q + (0..3)].
-    // The positions make every ds_read_b128 fragment read conflict-free (16 lanes of a service group on 16 different 16-byte bank slots); the k order
-    // inside a piece is the order in which a pair of 16x16 accumulator tiles hands its values to the next product.
-    // rows [32c, 32c + 32) of a row-major [N][512] matrix as one 32-KB W1-format image (above)
-    static void w1_image_chunk(const std::vector<float>& w, int c, uint16_t* i1) {
-        const int D = 512;
-        for (int j = 0; j < 8; j++)
-            for (int h = 0; h < 32; h++)
-                for (int sg = 0; sg < 2; sg++)
-                    for (int q = 0; q < 4; q++) {
-                        const int pos = (4 * sg + q) ^ ((h >> 1) & 7), s = 2 * j + sg;
-                        uint16_t* p = i1 + ((size_t)j * 32 + h) * 64 + pos * 8;
-                        for (int e = 0; e < 8; e++) {
-                            const int k = 32 * s + (e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4));
-                            p[e] = f32_to_bf16_rne(w[(size_t)(32 * c + h) * D + k]);
-                        }
-                    }
-    }
-    // a [N][512] matrix as N / 32 consecutive W1-format images (k_mimi_rowlin)
+    // the LDS weight images of ffn_fused.hip (pack_w1_image / pack_ffn_image above): in_proj for k_mimi_rowlin, linear1 + linear2 for k_mimi_ffn
     size_t add_w1_image(const std::string& wn, int N) {
-        const int nch = N / 32;
-        const size_t off = reserve((size_t)nch * 32768);
+        const size_t off = reserve(w1_image_count(N) * 2);
         if (!host) return off;
         const std::vector<float> w = load(wn);
-        for (int c = 0; c < nch; c++) w1_image_chunk(w, c, reinterpret_cast<uint16_t*>(host + off) + (size_t)c * 16384);
+        pack_w1_image(w.data(), N, reinterpret_cast<uint16_t*>(host + off));
         return off;
     }
     size_t add_ffn_image(const std::string& w1n, const std::string& w2n, int F) {
-        const int D = 512, nch = F / 32;
-        const size_t off = reserve((size_t)nch * 65536);
+        const size_t off = reserve(ffn_image_count(F) * 2);
         if (!host) return off;
         const std::vector<float> w1 = load(w1n), w2 = load(w2n);
-        uint16_t* dst = reinterpret_cast<uint16_t*>(host + off);
-        for (int c = 0; c < nch; c++) {
-            uint16_t* i1 = dst + (size_t)c * 32768;          // (uint16 units: 64 KB per chunk)
-            uint16_t* i2 = i1 + 16384;
-            w1_image_chunk(w1, c, i1);
-            for (int o = 0; o < D; o++)
-                for (int q = 0; q < 4; q++) {
-                    const int pos = q ^ (3 * ((o >> 3) & 1));
-                    uint16_t* p = i2 + (size_t)o * 32 + pos * 8;
-                    for (int e = 0; e < 8; e++) {
-                        const int hcol = 32 * c + (e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4));
-                        p[e] = f32_to_bf16_rne(w2[(size_t)o * F + hcol]);
-                    }
-                }
-        }
+        pack_ffn_image(w1.data(), w2.data(), F, reinterpret_cast<uint16_t*>(host + off));
         return off;
     }
     // the weights of a step linear as the kernels multiply them: the file's values, rounded to bf16 or int8-quantized per the mode

@@ -35,6 +35,13 @@ size_t frag16_count(size_t out, size_t in);
 void pack_frag16(const float* rm, size_t out, size_t in, uint16_t* hi, uint16_t* lo);
 void regroup_convtr_rows(const float* rm, int out, int in, int oc, float* dst);
 void pack_final_frag(const float* w, size_t n, uint16_t* hi, uint16_t* lo);
+// The LDS weight images of ffn_fused.hip (model.cpp; the loader and the kernels' test hook pack with the same code), bf16: a row-major [N][512] matrix as
+// N / 32 W1-format images of 32 KB (k_mimi_rowlin; N % 32 == 0), and linear1 [F][512] + linear2 [512][F] as F / 32 chunks of a W1 image followed by a W2
+// image (k_mimi_ffn; F % 32 == 0).  *_count: the uint16 entries of dst.
+size_t w1_image_count(int N);
+size_t ffn_image_count(int F);
+void pack_w1_image(const float* rm, int N, uint16_t* dst);
+void pack_ffn_image(const float* w1, const float* w2, int F, uint16_t* dst);
 
 struct Norm {  // linear.go:184-189
     size_t w = NONE, b = NONE;

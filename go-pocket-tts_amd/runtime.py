@@ -220,6 +220,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
     "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window", "ptts_debug_flow_cluster",
+    "ptts_debug_mimi_fused", "ptts_debug_mimi_pack",
 ]
 
 
@@ -1656,6 +1657,72 @@ def debug_gemm_rows(a_buf, w, M, *, amap, cmap, c_elems, kernel=0, cfg=0, rgl=0,
     _check(H.ptts_debug_gemm_rows(C.byref(a)))
     launched = {k: int(v) for k, v in (item.split("=") for item in name.value.decode().split(";") if item)}
     return {"out": out, "launched": launched, "cus": int(info[0]), "rgl": int(info[1])}
+
+
+class _MimiFusedArgs(C.Structure):   # ptts_mimi_fused_args
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "M", "D", "F", "n_pos", "rope_cols", "pos0", "rows_per_seg", "ls_off", "reserved")] +
+                [("eps", C.c_float), ("reserved_f", C.c_float)] +
+                [(n, C.c_int64) for n in ("x_elems", "x_ld", "x_rows_per_batch", "x_batch_stride", "x_off", "y_elems", "y_ld", "y_rows_per_batch", "y_batch_stride",
+                                          "y_off", "launched_cap")] +
+                [(n, _FP) for n in ("x", "ln_w", "ln_b", "w1", "w2", "ls", "rope_cos", "rope_sin", "out")] + [("launched", C.c_char_p)])
+
+
+MIMI_FFN, MIMI_ROWLIN = 0, 1
+
+
+def debug_mimi_fused(kind, x_buf, M, *, xmap, ln_w, ln_b, w1, w2=None, eps=1e-5, ls=None, ls_off=0, D=None, F=None, y_elems=0, ymap=(0, 0, 0, 0), rope=None,
+                     rope_cols=0, pos0=0, rows_per_seg=0):
+    """ONE launch of k_mimi_ffn (kind 0) or k_mimi_rowlin (kind 1) on host operands (ptts_debug_mimi_fused, include/ptts_debug.h).  x_buf: x's raw buffer (flat
+    f32); xmap / ymap = (ld, rows_per_batch, batch_stride, off) in elements; w1 [F or N, D], w2 [D, F] f32 row-major (rounded to bf16 by the packers); ls [D] or
+    None; rope = (cos, sin) tables [n_pos, 32].  D / F override the widths taken from w1's shape (for refusals).  Returns a dict: "out" (kind 0: the whole x buffer
+    after the in-place launch; kind 1: the whole y buffer, 0xff bytes where nothing was stored), "launched" ({kernel: count})."""
+    x_buf, w1 = _f32(x_buf).reshape(-1), _f32(w1)
+    keep = []
+
+    def ptr(v):
+        if v is None:
+            return C.cast(None, _FP)
+        v = _f32(v)
+        keep.append(v)
+        return _fp(v)
+
+    a = _MimiFusedArgs()
+    a.kind, a.M, a.D, a.F = int(kind), int(M), int(w1.shape[1] if D is None else D), int(w1.shape[0] if F is None else F)
+    a.eps, a.ls_off = float(eps), int(ls_off)
+    a.x_elems = x_buf.size
+    a.x_ld, a.x_rows_per_batch, a.x_batch_stride, a.x_off = (int(v) for v in xmap)
+    a.y_elems = int(y_elems)
+    a.y_ld, a.y_rows_per_batch, a.y_batch_stride, a.y_off = (int(v) for v in ymap)
+    a.x, a.ln_w, a.ln_b, a.w1, a.w2, a.ls = ptr(x_buf), ptr(ln_w), ptr(ln_b), ptr(w1), ptr(w2), ptr(ls)
+    if rope is not None:
+        cos, sin = (None if t is None else _f32(t) for t in rope)
+        a.rope_cos, a.rope_sin = ptr(cos), ptr(sin)
+        a.n_pos = (cos if cos is not None else sin).shape[0]
+        a.rope_cols, a.pos0, a.rows_per_seg = int(rope_cols), int(pos0), int(rows_per_seg)
+    out = np.empty(x_buf.size if int(kind) == 0 else max(int(y_elems), 1), np.float32)
+    a.out = ptr(out)
+    name = C.create_string_buffer(512)
+    a.launched, a.launched_cap = C.cast(name, C.c_char_p), 512
+    H = hooks()
+    H.ptts_debug_mimi_fused.argtypes = [C.POINTER(_MimiFusedArgs)]
+    _check(H.ptts_debug_mimi_fused(C.byref(a)))
+    launched = {k: int(v) for k, v in (item.split("=") for item in name.value.decode().split(";") if item)}
+    return {"out": out, "launched": launched}
+
+
+def debug_mimi_pack(kind, w1, w2=None):
+    """The weight-image packers of csrc/ffn_fused.hip's kernels (csrc/model.h) on matrices: kind 0 w1 [F, 512] + w2 [512, F] -> uint16 [F / 32, 2, 16384] (per
+    chunk the W1 image, then the W2 image); kind 1 w1 [N, 512] -> uint16 [N / 32, 16384].  No GPU."""
+    w1 = _f32(w1)
+    n = w1.shape[0]
+    if w1.ndim != 2 or w1.shape[1] != 512 or (kind == 0 and (w2 is None or tuple(np.shape(w2)) != (512, n))):
+        raise ValueError("w1 is [n, 512], w2 [512, n]")
+    w2 = None if kind != 0 else _f32(w2)
+    dst = np.empty(n * (1024 if kind == 0 else 512), np.uint16)
+    H = hooks()
+    H.ptts_debug_mimi_pack.argtypes = [C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]
+    _check(H.ptts_debug_mimi_pack(int(kind), _fp(w1), C.cast(None, _FP) if w2 is None else _fp(w2), n, dst.ctypes.data_as(C.c_void_p)))
+    return dst.reshape((n // 32, 2, 16384) if kind == 0 else (n // 32, 16384))
 
 
 class _ResblockArgs(C.Structure):   # ptts_resblock_args

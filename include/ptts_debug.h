@@ -260,6 +260,32 @@ typedef struct ptts_flow_cluster_args {
 } ptts_flow_cluster_args;
 int ptts_debug_flow_cluster(const ptts_flow_cluster_args* a);
 
+/* The two kernels of csrc/ffn_fused.hip stand-alone: ONE launch on host operands.
+ *   kind 0, k_mimi_ffn: x += ls * linear2(gelu(linear1(LayerNorm(x)))) in place; kind 1, k_mimi_rowlin: y = rope(LayerNorm(x) W1^T).
+ *   x: a buffer of x_elems floats; row m starts at x_off + (m / x_rows_per_batch) x_batch_stride + (m % x_rows_per_batch) x_ld (x_rows_per_batch 0:
+ *   x_off + m x_ld) and is D wide.  ln_w, ln_b [D], eps.  w1 [F][D] (kind 1: [N][D], N in the field F), w2 [D][F] (kind 0 only): f32 row-major, rounded to
+ *   bf16 and laid out by the loader's packers (csrc/model.h pack_ffn_image / pack_w1_image).  ls [D] or NULL (kind 0); on the device it starts ls_off
+ *   elements into its allocation (0: aligned as the loader aligns it).
+ *   kind 1: y, a buffer of y_elems floats addressed like x (y_off, y_ld, ...), N wide rows; rope_cos / rope_sin [n_pos][32] or both NULL; the first
+ *   rope_cols columns are rotated (interleaved pairs, 64-wide heads) at position pos0 + (rows_per_seg ? m % rows_per_seg : m).
+ * kind 0 returns the whole x buffer after the launch in `out` (x_elems floats); kind 1 fills y with 0xff bytes before the launch and returns it whole in
+ * `out` (y_elems floats).  launched (launched_cap bytes) receives the census of the call ("kernel=count;").
+ * PTTS_EINVAL with a message, before anything is uploaded or launched, for: a row of either map that leaves its buffer; rows of x (kind 0) or of y that
+ * overlap; a position outside [0, n_pos) (the kernels clamp rows, they do not bound table reads); one table without the other; and whatever
+ * mimi_ffn_supported / mimi_rowlin_supported refuse (D != 512, F % 32, N % 64, ld / batch_stride / off % 4, a misaligned ls, rope_cols % 64 or > N). */
+typedef struct ptts_mimi_fused_args {
+    int32_t kind, M, D, F, n_pos, rope_cols, pos0, rows_per_seg, ls_off, reserved;
+    float eps, reserved_f;
+    int64_t x_elems, x_ld, x_rows_per_batch, x_batch_stride, x_off, y_elems, y_ld, y_rows_per_batch, y_batch_stride, y_off, launched_cap;
+    const float *x, *ln_w, *ln_b, *w1, *w2, *ls, *rope_cos, *rope_sin;
+    float* out;
+    char* launched;
+} ptts_mimi_fused_args;
+int ptts_debug_mimi_fused(const ptts_mimi_fused_args* a);
+/* The packers of those kernels' weight images on a caller's matrices (no GPU).  kind 0: w1 [n][512], w2 [512][n] -> n / 32 chunks of 64 KB (k_mimi_ffn);
+ * kind 1: w1 [n][512] -> n / 32 images of 32 KB (k_mimi_rowlin; w2 unused).  dst: n * 1024 (kind 0) or n * 512 (kind 1) uint16.  n % 32 == 0. */
+int ptts_debug_mimi_pack(int32_t kind, const float* w1, const float* w2, int32_t n, uint16_t* dst);
+
 /* The check every entry point runs on a ptts_dsp_opts, without a model: out (cap bytes, terminated) receives its message, empty when the options are
  * fine; returns the message's length.  No GPU. */
 int64_t ptts_debug_dsp_opts_error(const ptts_dsp_opts* opts, char* out, int64_t cap);
