@@ -6,8 +6,128 @@
 #include "scan_block.h"
 #include "true_peak.h"
 
+#include <memory>
+
+// How to add a kernel hook (ptts_debug_<kernel> on a ptts_<kernel>_args of host operands).  Keep this order: (1) every argument and bound check -- the
+// kernels bound few of their loads, so whatever a launch can touch is checked against the caller's sizes first (check_rows for a RowMap); (2)
+// require_device(); (3) the operands through a Stage: in() uploads (a null host pointer stays a null device pointer), out() allocates a result pre-filled
+// with 0xff bytes, so whatever the kernel does not store comes back as NaN / FILL and the buffer comes back whole; (4) the kernel's own *_supported
+// predicate; (5) the launch inside LaunchScope::run, which counts it in a private census, restores the caller's census also on a throw and merges into it
+// only after the launcher returned; (6) hipGetLastError / hipDeviceSynchronize; (7) down() per result, put_str() for every string result.  A forcing global
+// (g_gemm3_cfg, g_skinny_stamps, ...) is set through Scoped alone.  What is not a plain upload stays written out in the hook: an in-place residual, NaN
+// slack rows, an offset into a buffer.
 using namespace ptts;
 using namespace ptts::capi;
+
+namespace {
+
+// sets a variable for a scope; the old value comes back when the scope is left, by a throw too
+template <class T> class Scoped {
+    T& var_;
+    T old_;
+public:
+    Scoped(T& var, T value) : var_(var), old_(var) { var = value; }
+    ~Scoped() { var_ = old_; }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+};
+
+using Census = std::map<std::string, int64_t>;
+
+std::string census_str(const Census& c) {   // "k=v;" per kernel
+    std::string s;
+    for (const auto& kv : c) s += kv.first + "=" + std::to_string(kv.second) + ";";
+    return s;
+}
+
+// a capped C string result: at most cap - 1 characters and the terminator; nothing for a null buffer or a cap below 1
+void put_str(char* dst, int64_t cap, const std::string& s) {
+    if (!dst || cap <= 0) return;
+    const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1);
+    std::memcpy(dst, s.data(), n);
+    dst[n] = 0;
+}
+
+// the launches of one hook call: run() notes them in a census of its own and, once the launcher has returned, adds them to a census the caller switched on
+// (ptts_debug_launch_counts).  A launcher that throws leaves the caller's census as it was.
+class LaunchScope {
+    Census seen_;
+public:
+    template <class F> void run(F&& launch) {
+        Census now;
+        Census* const callers = g_launch_census;
+        {
+            Scoped<Census*> install(g_launch_census, &now);
+            launch();
+        }
+        for (const auto& kv : now) {
+            seen_[kv.first] += kv.second;
+            if (callers) (*callers)[kv.first] += kv.second;
+        }
+    }
+    int64_t count(const char* kernel) const { const auto it = seen_.find(kernel); return it == seen_.end() ? 0 : it->second; }
+    int64_t total() const { int64_t all = 0; for (const auto& kv : seen_) all += kv.second; return all; }
+    std::string str() const { return census_str(seen_); }
+};
+
+// the device buffers of one hook call, freed when it ends
+class Stage {
+    std::vector<std::unique_ptr<Tmp>> bufs_;
+    void* alloc(size_t bytes) { bufs_.emplace_back(new Tmp(bytes)); return bufs_.back()->p; }
+public:
+    void* in_bytes(const void* host, size_t bytes) {   // (the KV caches: elements of 2 or 4 bytes)
+        if (!host) return nullptr;
+        void* d = alloc(bytes);
+        up(d, host, bytes);
+        return d;
+    }
+    template <class T> T* in(const T* host, size_t count) { return static_cast<T*>(in_bytes(host, count * sizeof(T))); }
+    template <class T = float> T* out(size_t count) {
+        void* d = alloc(count * sizeof(T));
+        if (count) PTTS_HIP(hipMemset(d, 0xff, count * sizeof(T)));
+        return static_cast<T*>(d);
+    }
+};
+
+// a RowMap against its buffer: row m's `width` elements start at off + the map's offset of m and must end inside `elems`; disjoint: no two rows overlap
+// (two lanes would store to one element)
+void check_rows(const char* hook, const char* what, int64_t M, int64_t elems, const RowMap& map, int64_t off, int64_t width, bool disjoint) {
+    std::vector<int64_t> start((size_t)M);
+    for (int64_t m = 0; m < M; m++) {
+        const int64_t o = off + (map.rows_per_batch ? (m / map.rows_per_batch) * map.batch_stride + (m % map.rows_per_batch) * map.ld : m * map.ld);
+        if (o < 0 || o + width > elems)
+            throw Error(PTTS_EINVAL, strfmt("%s: row %lld of %s ends at element %lld of %lld", hook, (long long)m, what, (long long)(o + width), (long long)elems));
+        start[(size_t)m] = o;
+    }
+    if (!disjoint) return;
+    std::sort(start.begin(), start.end());
+    for (size_t i = 1; i < start.size(); i++)
+        if (start[i] - start[i - 1] < width) throw Error(PTTS_EINVAL, strfmt("%s: rows of %s overlap (elements %lld and %lld)", hook, what, (long long)start[i - 1], (long long)start[i]));
+}
+
+// the operands of the two step-linear probes (ptts_debug_time_skinny, ptts_debug_skinny_stamps): 0x3c bytes everywhere
+struct SkinnyProbe {
+    Tmp dA, dW, dWt, dC, dlnw;
+    GemmArgs g;
+    SkinnyFuse fu;
+    SkinnyProbe(int M, int N, int K, int w_bf16, int splitk, int fuse_ln)
+        : dA((size_t)M * K * 4), dW((size_t)N * K * 4), dWt(step_tiled_bytes((size_t)N, (size_t)K, w_bf16 ? 2 : 4)), dC((size_t)M * N * 4 * (splitk > 1 ? splitk : 1)),
+          dlnw((size_t)K * 4) {
+        PTTS_HIP(hipMemset(dA.p, 0x3c, (size_t)M * K * 4));
+        PTTS_HIP(hipMemset(dW.p, 0x3c, (size_t)N * K * (w_bf16 ? 2 : 4)));
+        PTTS_HIP(hipMemset(dlnw.p, 0x3c, (size_t)K * 4));
+        PTTS_HIP(hipMemset(dWt.p, 0x3c, step_tiled_bytes((size_t)N, (size_t)K, w_bf16 ? 2 : 4)));
+        g.A = dA.as<float>(); g.amap = RowMap{K, 0, 0};
+        g.W = dW.p; g.w_bf16 = w_bf16; g.ldw = K; g.Wt = dWt.p;
+        g.C = dC.as<float>(); g.cmap = RowMap{N, 0, 0};
+        g.M = M; g.N = N; g.K = K;
+        if (fuse_ln) { fu.ln = 1; fu.ln_w = dlnw.as<float>(); fu.ln_b = dlnw.as<float>(); }
+        if (!(fuse_ln ? skinny_fuse_supported(g, fu) : skinny_supported(g, splitk))) throw Error(PTTS_EINVAL, "shape not supported");
+    }
+    void launch(int splitk) { launch_skinny(g, fu, splitk, dC.as<float>(), nullptr); }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -78,16 +198,16 @@ int ptts_debug_flow_cluster(const ptts_flow_cluster_args* pa) {
         int device = 0;
         PTTS_HIP(hipGetDevice(&device));
         if (!flow_cluster_fits(rows, device)) throw Error(PTTS_EINVAL, strfmt("ptts_debug_flow_cluster: the grid of %d rows is not resident at once on this device (flow_cluster_fits)", rows));
-        const size_t row_bytes = (size_t)C * 4, buf_rows = (size_t)rows + kSlack, fx_bytes = buf_rows * row_bytes, ada_bytes = buf_rows * (size_t)t.ldmod * 4, vec_bytes = (size_t)depth * C * 4;
-        Tmp dW(wt.size()), dAda(ada_bytes), dLw(vec_bytes), dLb(vec_bytes), dB0(vec_bytes), dB2(vec_bytes), dIn((size_t)L * fx_bytes), dOut((size_t)L * fx_bytes),
-            dX(flow_cluster_xbuf_bytes(rows)), dSync(kFlowClusterSyncBytes);
-        up(dW.p, wt.data(), wt.size());
-        PTTS_HIP(hipMemset(dAda.p, 0xff, ada_bytes));   // (NaN slack rows behind `rows`)
-        up(dAda.p, t.ada, (size_t)rows * t.ldmod * 4);
-        up(dLw.p, t.ln_w, vec_bytes); up(dLb.p, t.ln_b, vec_bytes); up(dB0.p, t.b0, vec_bytes); up(dB2.p, t.b2, vec_bytes);
+        const size_t row_bytes = (size_t)C * 4, buf_rows = (size_t)rows + kSlack, vec =(size_t)depth * C;
+        Stage st;
+        Tmp dX(flow_cluster_xbuf_bytes(rows)), dSync(kFlowClusterSyncBytes);
+        const uint8_t* dW = st.in(wt.data(), wt.size());
+        float* dAda = st.out(buf_rows * (size_t)t.ldmod);   // (NaN slack rows behind `rows`)
+        up(dAda, t.ada, (size_t)rows * t.ldmod * 4);
+        const float *dLw = st.in(t.ln_w, vec), *dLb = st.in(t.ln_b, vec), *dB0 = st.in(t.b0, vec), *dB2 = st.in(t.b2, vec);
         // every launch its own copy of the rows it takes: NaN behind them (in place that is what the rows at and beyond launch_rows keep)
-        PTTS_HIP(hipMemset(dIn.p, 0xff, (size_t)L * fx_bytes)); PTTS_HIP(hipMemset(dOut.p, 0xff, (size_t)L * fx_bytes));
-        for (int i = 0; i < L; i++) up(dIn.as<uint8_t>() + (size_t)i * fx_bytes, t.fx, (size_t)t.launch_rows[i] * row_bytes);
+        float *dIn = st.out((size_t)L * buf_rows * C), *dOut = st.out((size_t)L * buf_rows * C);
+        for (int i = 0; i < L; i++) up(dIn + (size_t)i * buf_rows * C, t.fx, (size_t)t.launch_rows[i] * row_bytes);
         // the exchange state as runtime.cpp sets it up (zeroes), then the tag words at tag_base0
         PTTS_HIP(hipMemset(dX.p, 0, flow_cluster_xbuf_bytes(rows))); PTTS_HIP(hipMemset(dSync.p, 0, kFlowClusterSyncBytes));
         std::vector<uint32_t> sync(kFlowClusterSyncBytes / 4, 0u);
@@ -98,42 +218,34 @@ int ptts_debug_flow_cluster(const ptts_flow_cluster_args* pa) {
             for (int tile = 0; tile < kFlowClusterMaxTiles; tile++) t.state[tile] = sync[(size_t)tile * 32];
             t.state[kFlowClusterMaxTiles] = sync[(size_t)32 * kFlowClusterMaxTiles];
         };
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
+        LaunchScope launches;   // (one scope around the whole sequence: a launch that is refused or throws leaves a caller's census without the earlier ones too)
         int faulted = -1;
-        for (int i = 0; i < L && faulted < 0; i++) {
-            FlowClusterArgs fa;   // as step_flow fills them
-            float* in = dIn.as<float>() + (size_t)i * buf_rows * C;
-            fa.fx_in = in; fa.fx_out = t.in_place ? in : dOut.as<float>() + (size_t)i * buf_rows * C;
-            fa.ada = dAda.as<float>(); fa.ldmod = t.ldmod; fa.rows = t.launch_rows[i]; fa.depth = depth;
-            for (int r = 0; r < depth; r++) {
-                fa.eps[r] = t.eps[r]; fa.ln_w[r] = dLw.as<float>() + (size_t)r * C; fa.ln_b[r] = dLb.as<float>() + (size_t)r * C;
-                fa.w0[r] = dW.as<uint8_t>() + (size_t)(2 * r) * wbytes; fa.b0[r] = dB0.as<float>() + (size_t)r * C;
-                fa.w2[r] = dW.as<uint8_t>() + (size_t)(2 * r + 1) * wbytes; fa.b2[r] = dB2.as<float>() + (size_t)r * C;
+        launches.run([&] {
+            for (int i = 0; i < L && faulted < 0; i++) {
+                FlowClusterArgs fa;   // as step_flow fills them
+                float* in = dIn + (size_t)i * buf_rows * C;
+                fa.fx_in = in; fa.fx_out = t.in_place ? in : dOut + (size_t)i * buf_rows * C;
+                fa.ada = dAda; fa.ldmod = t.ldmod; fa.rows = t.launch_rows[i]; fa.depth = depth;
+                for (int r = 0; r < depth; r++) {
+                    fa.eps[r] = t.eps[r]; fa.ln_w[r] = dLw + (size_t)r * C; fa.ln_b[r] = dLb + (size_t)r * C;
+                    fa.w0[r] = dW + (size_t)(2 * r) * wbytes; fa.b0[r] = dB0 + (size_t)r * C;
+                    fa.w2[r] = dW + (size_t)(2 * r + 1) * wbytes; fa.b2[r] = dB2 + (size_t)r * C;
+                }
+                fa.xbuf = dX.as<unsigned long long>(); fa.sync = dSync.as<unsigned>();
+                if (!flow_cluster_supported(fa, C)) throw Error(PTTS_EINVAL, "ptts_debug_flow_cluster: refused by flow_cluster_supported");
+                launch_flow_cluster(fa, nullptr);
+                PTTS_HIP(hipGetLastError());
+                PTTS_HIP(hipDeviceSynchronize());
+                uint32_t fault = 0;
+                down(&fault, dSync.as<uint32_t>() + (size_t)32 * kFlowClusterMaxTiles, 4);
+                if (fault) faulted = i;   // (nothing is retried, nothing more is launched on this state)
             }
-            fa.xbuf = dX.as<unsigned long long>(); fa.sync = dSync.as<unsigned>();
-            if (!flow_cluster_supported(fa, C)) throw Error(PTTS_EINVAL, "ptts_debug_flow_cluster: refused by flow_cluster_supported");
-            g_launch_census = &census;
-            try { launch_flow_cluster(fa, nullptr); } catch (...) { g_launch_census = census_before; throw; }
-            g_launch_census = census_before;
-            PTTS_HIP(hipGetLastError());
-            PTTS_HIP(hipDeviceSynchronize());
-            uint32_t fault = 0;
-            down(&fault, dSync.as<uint32_t>() + (size_t)32 * kFlowClusterMaxTiles, 4);
-            if (fault) faulted = i;   // (nothing is retried, nothing more is launched on this state)
-        }
-        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launches too
-        if (t.launched && t.launched_cap > 0) {
-            std::string s;
-            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
-            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
-            std::memcpy(t.launched, s.data(), n);
-            t.launched[n] = 0;
-        }
+        });
+        put_str(t.launched, t.launched_cap, launches.str());
         read_state();
         for (int i = 0; i < L; i++) {
-            down(t.out + (size_t)i * rows * C, (t.in_place ? dIn : dOut).as<uint8_t>() + (size_t)i * fx_bytes, (size_t)rows * row_bytes);
-            if (!t.in_place) down(t.fx_back + (size_t)i * rows * C, dIn.as<uint8_t>() + (size_t)i * fx_bytes, (size_t)rows * row_bytes);
+            down(t.out + (size_t)i * rows * C, (t.in_place ? dIn : dOut) + (size_t)i * buf_rows * C, (size_t)rows * row_bytes);
+            if (!t.in_place) down(t.fx_back + (size_t)i * rows * C, dIn + (size_t)i * buf_rows * C, (size_t)rows * row_bytes);
         }
         if (faulted >= 0)
             throw Error(PTTS_ENODEVICE, strfmt("ptts_debug_flow_cluster: the in-launch hand-off timed out (k_flow_cluster), launch %d of %d; nothing is retried", faulted, L));
@@ -180,11 +292,7 @@ int ptts_debug_kweighting(int32_t sample_rate, double out[10]) {
 
 int64_t ptts_debug_dsp_opts_error(const ptts_dsp_opts* opts, char* out, int64_t cap) {
     const std::string s = opts ? dsp_opts_error(*opts) : std::string();
-    if (out && cap > 0) {
-        const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1);
-        std::memcpy(out, s.data(), n);
-        out[n] = 0;
-    }
+    put_str(out, cap, s);
     return (int64_t)s.size();
 }
 
@@ -207,14 +315,9 @@ int ptts_debug_true_peak_oversample(const float* samples, int64_t n, float* y) {
 }
 
 int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap) {
-    static thread_local std::map<std::string, int64_t> census;
-    std::string s;
-    for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
-    if (out && cap > 0) {
-        const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1);
-        std::memcpy(out, s.data(), n);
-        out[n] = 0;
-    }
+    static thread_local Census census;
+    const std::string s = census_str(census);
+    put_str(out, cap, s);
     census.clear();
     g_launch_census = on ? &census : nullptr;
     return (int64_t)s.size();
@@ -224,28 +327,13 @@ int64_t ptts_debug_launch_counts(int32_t on, char* out, int64_t cap) {
 int ptts_debug_time_skinny(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t splitk, int32_t fuse_ln, int32_t iters, float* avg_us) {
     return guard([&] {
         require_device();
-        Tmp dA((size_t)M * K * 4), dW((size_t)N * K * 4), dC((size_t)M * N * 4 * (splitk > 1 ? splitk : 1)), dlnw((size_t)K * 4);
-        PTTS_HIP(hipMemset(dA.p, 0x3c, (size_t)M * K * 4));
-        PTTS_HIP(hipMemset(dW.p, 0x3c, (size_t)N * K * (w_bf16 ? 2 : 4)));
-        PTTS_HIP(hipMemset(dlnw.p, 0x3c, (size_t)K * 4));
-        GemmArgs g;
-        g.A = dA.as<float>(); g.amap = RowMap{K, 0, 0};
-        g.W = dW.p; g.w_bf16 = w_bf16; g.ldw = K;
-        const size_t wt_bytes = (size_t)((N + 15) / 16) * ((K + 127) / 128) * 16 * 128 * (w_bf16 ? 2 : 4);
-        Tmp dWt(wt_bytes);
-        PTTS_HIP(hipMemset(dWt.p, 0x3c, wt_bytes));
-        g.Wt = dWt.p;
-        g.C = dC.as<float>(); g.cmap = RowMap{N, 0, 0};
-        g.M = M; g.N = N; g.K = K;
-        SkinnyFuse fu;
-        if (fuse_ln) { fu.ln = 1; fu.ln_w = dlnw.as<float>(); fu.ln_b = dlnw.as<float>(); }
-        if (!(fuse_ln ? skinny_fuse_supported(g, fu) : skinny_supported(g, splitk))) throw Error(PTTS_EINVAL, "shape not supported");
+        SkinnyProbe p(M, N, K, w_bf16, splitk, fuse_ln);
         hipEvent_t e0, e1;
         PTTS_HIP(hipEventCreate(&e0)); PTTS_HIP(hipEventCreate(&e1));
-        for (int i = 0; i < 5; i++) launch_skinny(g, fu, splitk, dC.as<float>(), nullptr);
+        for (int i = 0; i < 5; i++) p.launch(splitk);
         PTTS_HIP(hipDeviceSynchronize());
         PTTS_HIP(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < iters; i++) launch_skinny(g, fu, splitk, dC.as<float>(), nullptr);
+        for (int i = 0; i < iters; i++) p.launch(splitk);
         PTTS_HIP(hipEventRecord(e1, nullptr));
         PTTS_HIP(hipEventSynchronize(e1));
         float ms = 0;
@@ -260,30 +348,16 @@ int ptts_debug_skinny_stamps(int32_t M, int32_t N, int32_t K, int32_t w_bf16, in
                              int32_t* n_blocks) {
     return guard([&] {
         require_device();
-        Tmp dA((size_t)M * K * 4), dW((size_t)N * K * 4), dC((size_t)M * N * 4 * (splitk > 1 ? splitk : 1)), dlnw((size_t)K * 4);
-        PTTS_HIP(hipMemset(dA.p, 0x3c, (size_t)M * K * 4));
-        PTTS_HIP(hipMemset(dW.p, 0x3c, (size_t)N * K * (w_bf16 ? 2 : 4)));
-        PTTS_HIP(hipMemset(dlnw.p, 0x3c, (size_t)K * 4));
-        GemmArgs g;
-        g.A = dA.as<float>(); g.amap = RowMap{K, 0, 0};
-        g.W = dW.p; g.w_bf16 = w_bf16; g.ldw = K;
-        const size_t wt_bytes = (size_t)((N + 15) / 16) * ((K + 127) / 128) * 16 * 128 * (w_bf16 ? 2 : 4);
-        Tmp dWt(wt_bytes);
-        PTTS_HIP(hipMemset(dWt.p, 0x3c, wt_bytes));
-        g.Wt = dWt.p;
-        g.C = dC.as<float>(); g.cmap = RowMap{N, 0, 0};
-        g.M = M; g.N = N; g.K = K;
-        SkinnyFuse fu;
-        if (fuse_ln) { fu.ln = 1; fu.ln_w = dlnw.as<float>(); fu.ln_b = dlnw.as<float>(); }
-        if (!(fuse_ln ? skinny_fuse_supported(g, fu) : skinny_supported(g, splitk))) throw Error(PTTS_EINVAL, "shape not supported");
+        SkinnyProbe p(M, N, K, w_bf16, splitk, fuse_ln);
         const int blocks = ((N + 15) / 16) * ((M + 15) / 16) * (splitk > 1 ? splitk : 1);   // upper bound: the narrow-block variant has N/16 column blocks
         Tmp dS((size_t)blocks * 8 * 8);
         PTTS_HIP(hipMemset(dS.p, 0, (size_t)blocks * 64));
-        for (int i = 0; i < 3; i++) launch_skinny(g, fu, splitk, dC.as<float>(), nullptr);
+        for (int i = 0; i < 3; i++) p.launch(splitk);
         PTTS_HIP(hipDeviceSynchronize());
-        g_skinny_stamps = reinterpret_cast<unsigned long long*>(dS.p);
-        launch_skinny(g, fu, splitk, dC.as<float>(), nullptr);
-        g_skinny_stamps = nullptr;
+        {
+            Scoped<unsigned long long*> stamped(g_skinny_stamps, dS.as<unsigned long long>());
+            p.launch(splitk);
+        }
         PTTS_HIP(hipDeviceSynchronize());
         *n_blocks = blocks;
         down(out, dS.p, (size_t)std::min(blocks, max_blocks) * 64);
@@ -307,9 +381,10 @@ int ptts_debug_step_stamps(ptts_batch* hb, int32_t lsd_steps, uint64_t* out, int
         PTTS_HIP(hipMemsetAsync(b.cur.p, 0, (size_t)b.B * m.d.ldim * sizeof(float), m.stream));
         SkinnyStampLog lg;
         lg.base = ds.as<unsigned long long>(); lg.cap_blocks = (size_t)cap_blocks;
-        g_skinny_stamp_log = &lg;
-        try { step_core(b, lsd_steps); } catch (...) { g_skinny_stamp_log = nullptr; throw; }
-        g_skinny_stamp_log = nullptr;
+        {
+            Scoped<SkinnyStampLog*> logged(g_skinny_stamp_log, &lg);
+            step_core(b, lsd_steps);
+        }
         for (int i = 0; i < b.B; i++) b.kv_len_host[i] += 1;
         PTTS_HIP(hipMemcpyAsync(b.st.kv_len, b.kv_len_host.data(), (size_t)b.B * sizeof(int32_t), hipMemcpyHostToDevice, m.stream));
         PTTS_HIP(hipStreamSynchronize(m.stream));
@@ -348,7 +423,7 @@ int ptts_debug_gemm(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t var
         up(dA.p, ha.data(), na * 4); up(dB.p, hb.data(), (size_t)N * 4);
         if (w_bf16) {
             std::vector<uint16_t> hw16(nw);
-            for (size_t i = 0; i < nw; i++) { uint32_t u; memcpy(&u, &hw[i], 4); hw16[i] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); }
+            for (size_t i = 0; i < nw; i++) hw16[i] = f32_to_bf16_rne(hw[i]);
             up(dW.p, hw16.data(), nw * 2);
         } else up(dW.p, hw.data(), nw * 4);
         if (inplace) {   // a residual with content: the first nc values of the activations' generator, continued
@@ -381,8 +456,8 @@ int ptts_debug_gemm(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t var
             GemmArgs h = g; h.C = c;
             if (inplace) { PTTS_HIP(hipMemcpyAsync(c, dR.p, nc * 4, hipMemcpyDeviceToDevice, nullptr)); h.R = c; }
             if (v == 40) { if (rope) { if (!launch_gemm_rope(h, nullptr)) throw Error(PTTS_EINVAL, "no RoPE epilogue for this shape"); } else launch_gemm(h, nullptr); }
-            else if (v >= 50) { if (!gemm5_supported(h)) throw Error(PTTS_EINVAL, "shape not supported by k_gemm5"); g_gemm5_cfg = v - 50; launch_gemm5(h, nullptr); g_gemm5_cfg = 0; }
-            else if (v >= 3) { g_gemm3_cfg = v >= 30 ? v - 30 : 0; launch_gemm3(h, nullptr); g_gemm3_cfg = 0; }
+            else if (v >= 50) { if (!gemm5_supported(h)) throw Error(PTTS_EINVAL, "shape not supported by k_gemm5"); Scoped<int> cfg(g_gemm5_cfg, v - 50); launch_gemm5(h, nullptr); }
+            else if (v >= 3) { Scoped<int> cfg(g_gemm3_cfg, v >= 30 ? v - 30 : 0); launch_gemm3(h, nullptr); }
             else { if (!gemm2_supported(h)) throw Error(PTTS_EINVAL, "shape not supported by k_gemm2"); launch_gemm2(h, nullptr); }
         };
         hipEvent_t e0, e1;
@@ -437,44 +512,31 @@ int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t
         if (!x || !W || !out || M <= 0 || N <= 0 || K <= 0 || K % 128) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: bad arguments");
         const size_t mk = (size_t)M * K, mn = (size_t)M * N;
         const int S = std::max(1, (int)splitk);
-        auto bf16 = [](float v) { uint32_t u; memcpy(&u, &v, 4); return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); };
-        auto f32 = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float v; memcpy(&v, &u, 4); return v; };
-        // the weights in the step kernels' fragment order (model.cpp add_tiled): [16-column tile][128-deep super-step][4][64 lanes] x 8 bf16
-        const size_t nt = ((size_t)N + 15) / 16, nss = (size_t)K / 128;
-        std::vector<uint16_t> wt(nt * nss * 4 * 64 * 8);
-        for (size_t t = 0; t < nt; t++)
-            for (size_t ss = 0; ss < nss; ss++)
-                for (int sidx = 0; sidx < 4; sidx++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < 8; j++) {
-                            const size_t n = t * 16 + (size_t)(lane & 15), k = ss * 128 + (size_t)(lane >> 4) * 32 + (size_t)sidx * 8 + j;
-                            wt[((((t * nss + ss) * 4 + sidx) * 64 + lane) * 8 + j)] = n < (size_t)N ? bf16(W[n * K + k]) : 0;
-                        }
-        Tmp dW(wt.size() * 2), dAh(mk * 2), dAl(mk * 2), dOut((size_t)S * mn * 4), dCh(mn * 2), dCl(mn * 2);
-        up(dW.p, wt.data(), wt.size() * 2);
-        Tmp dB((size_t)N * 4), dR(mn * 4), dX(mk * 4), dXo(mk * 4), dP(std::max<size_t>(1, (size_t)std::max(0, (int)psplit)) * mk * 4), dPb((size_t)K * 4), dLw((size_t)K * 4), dLb((size_t)K * 4);
-        if (bias) up(dB.p, bias, (size_t)N * 4);
-        if (R) up(dR.p, R, mn * 4);
+        // the weights in the step kernels' fragment order, rounded to bf16: the loader's packer (K % 128 == 0, so its super-steps are whole)
+        std::vector<uint8_t> wt(step_tiled_bytes((size_t)N, (size_t)K, 2));
+        pack_step_tiled(W, (size_t)N, (size_t)K, true, wt.data());
+        Stage st;
+        Tmp dAh(mk * 2), dAl(mk * 2), dOut((size_t)S * mn * 4), dCh(mn * 2), dCl(mn * 2), dXo(mk * 4);
+        const uint8_t* dW = st.in(wt.data(), wt.size());
+        const float *dB = st.in(bias, (size_t)N), *dR = st.in(R, mn);
         if (ln_w) {   // the rows through k_rowprep: split-K planes + residual -> LayerNorm -> bf16 planes
-            up(dX.p, x, mk * 4); up(dLw.p, ln_w, (size_t)K * 4); up(dLb.p, ln_b, (size_t)K * 4);
             PrepArgs pa;
-            pa.x = dX.as<float>(); pa.ldx = K; pa.ln_w = dLw.as<float>(); pa.ln_b = dLb.as<float>(); pa.eps = eps;
+            pa.x = st.in(x, mk); pa.ldx = K; pa.ln_w = st.in(ln_w, (size_t)K); pa.ln_b = st.in(ln_b, (size_t)K); pa.eps = eps;
             if (planes && psplit > 0) {
-                up(dP.p, planes, (size_t)psplit * mk * 4);
-                pa.partial = dP.as<float>(); pa.psplit = psplit; pa.pstride = (int64_t)mk; pa.x_out = dXo.as<float>();
-                if (pbias) { up(dPb.p, pbias, (size_t)K * 4); pa.pbias = dPb.as<float>(); }
+                pa.partial = st.in(planes, (size_t)psplit * mk); pa.psplit = psplit; pa.pstride = (int64_t)mk; pa.x_out = dXo.as<float>();
+                pa.pbias = st.in(pbias, (size_t)K);
             }
             pa.yh = dAh.as<uint16_t>(); pa.yl = dAl.as<uint16_t>(); pa.ldy = K; pa.M = M; pa.D = K;
             if (!rowprep_supported(pa)) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: rows not taken by k_rowprep");
             launch_rowprep(pa, nullptr);
         } else {      // the rows as they are: split on the host the way the kernels split (hi = bf16(x), lo = bf16(x - hi))
             std::vector<uint16_t> hi(mk), lo(mk);
-            for (size_t i = 0; i < mk; i++) { hi[i] = bf16(x[i]); lo[i] = bf16(x[i] - f32(hi[i])); }
+            for (size_t i = 0; i < mk; i++) { hi[i] = f32_to_bf16_rne(x[i]); lo[i] = f32_to_bf16_rne(x[i] - bf16_to_f32(hi[i])); }
             up(dAh.p, hi.data(), mk * 2); up(dAl.p, lo.data(), mk * 2);
         }
         TallArgs t;
-        t.ah = dAh.as<uint16_t>(); t.al = dAl.as<uint16_t>(); t.lda = K; t.Wt = dW.p; t.bias = bias ? dB.as<float>() : nullptr;
-        t.R = R ? dR.as<float>() : nullptr; t.ldr = N; t.M = M; t.N = N; t.K = K; t.epi = epi;
+        t.ah = dAh.as<uint16_t>(); t.al = dAl.as<uint16_t>(); t.lda = K; t.Wt = dW; t.bias = dB;
+        t.R = dR; t.ldr = N; t.M = M; t.N = N; t.K = K; t.epi = epi;
         if (S > 1) { t.splitk = S; t.partial = dOut.as<float>(); t.zstride = (int64_t)mn; }
         else if (out_planes) { t.ch = dCh.as<uint16_t>(); t.cl = dCl.as<uint16_t>(); t.ldp = N; }
         else { t.C = dOut.as<float>(); t.ldc = N; }
@@ -485,14 +547,13 @@ int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t
         if (S == 1 && out_planes) {
             std::vector<uint16_t> hi(mn), lo(mn);
             down(hi.data(), dCh.p, mn * 2); down(lo.data(), dCl.p, mn * 2);
-            for (size_t i = 0; i < mn; i++) out[i] = f32(hi[i]) + f32(lo[i]);
+            for (size_t i = 0; i < mn; i++) out[i] = bf16_to_f32(hi[i]) + bf16_to_f32(lo[i]);
         } else down(out, dOut.p, (size_t)S * mn * 4);
         if (x_out && ln_w && planes && psplit > 0) down(x_out, dXo.p, mk * 4);
     });
 }
 
-// The step linear (csrc/skinny.hip) on host operands: every operand is uploaded, every output buffer is pre-filled with 0xff bytes (NaN where the
-// kernel stores nothing) and comes back whole.  The weights go through the loader's own packers (model.h).
+// The step linear (csrc/skinny.hip) on host operands.  The weights go through the loader's own packers (model.h).
 int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     return guard([&] {
         if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_step_linear: null argument");
@@ -523,47 +584,39 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
         }
         require_device();
         const int64_t zrows = t.zrows ? t.zrows : M;
-        const size_t c_bytes = (size_t)M * t.ldc * 4, p_bytes = (size_t)S * zrows * N * 4, mod_bytes = (size_t)M * std::max(t.ldmod, 1) * 4;
-        Tmp dX((size_t)M * t.lda * 4), dW(nk * 4), dWt(wt.size()), dWs((size_t)N * 4), dB((size_t)N * 4), dAv((size_t)N * 4), dSc((size_t)N * 4), dR(c_bytes), dG((size_t)M * std::max(t.ldg, 1) * 4),
-            dC(c_bytes), dPart(p_bytes), dTail((size_t)M * 4), dLw((size_t)K * 4), dLb((size_t)K * 4), dSh(mod_bytes), dMs(mod_bytes), dPl((size_t)std::max(t.psplit, 1) * mk * 4), dPb((size_t)K * 4),
-            dXo(mk * 4), dYo(mk * 4);
-        up(dX.p, t.x, (size_t)M * t.lda * 4);
-        if (t.wfmt == 1) up(dW.p, rm16.data(), nk * 2); else up(dW.p, rm.data(), nk * 4);
-        up(dWt.p, wt.data(), wt.size());
-        PTTS_HIP(hipMemset(dC.p, 0xff, c_bytes)); PTTS_HIP(hipMemset(dPart.p, 0xff, p_bytes)); PTTS_HIP(hipMemset(dTail.p, 0xff, (size_t)M * 4));
-        PTTS_HIP(hipMemset(dXo.p, 0xff, mk * 4)); PTTS_HIP(hipMemset(dYo.p, 0xff, mk * 4));
+        const size_t c_elems = (size_t)M * t.ldc, p_elems = (size_t)S * zrows * N, mod_elems = (size_t)M * std::max(t.ldmod, 1);
+        Stage st;
+        float *dC = st.out(c_elems), *dPart = st.out(p_elems), *dTail = st.out((size_t)M), *dXo = st.out(mk), *dYo = st.out(mk);
         GemmArgs g;
-        g.A = dX.as<float>(); g.amap = RowMap{t.lda, 0, 0};
-        g.W = dW.p; g.w_bf16 = t.wfmt == 1; g.ldw = K; g.Wt = dWt.p;
-        if (t.wfmt == 2) { up(dWs.p, wscale.data(), (size_t)N * 4); g.wt_i8 = 1; g.wscale = dWs.as<float>(); }
-        if (t.bias) { up(dB.p, t.bias, (size_t)N * 4); g.bias = dB.as<float>(); }
-        if (t.addvec) { up(dAv.p, t.addvec, (size_t)(t.tail ? N - 1 : N) * 4); g.addvec = dAv.as<float>(); }
-        if (t.scale) { up(dSc.p, t.scale, (size_t)N * 4); g.scale = dSc.as<float>(); }
-        if (t.gate) { up(dG.p, t.gate, (size_t)M * t.ldg * 4); g.gate = dG.as<float>(); g.ldg = t.ldg; }
-        g.C = dC.as<float>(); g.cmap = RowMap{t.ldc, 0, 0};
-        if (t.R) {   // r_in_c: the in-place residual (R is C: every element read and written by the same lane)
-            up(t.r_in_c ? dC.p : dR.p, t.R, c_bytes);
-            g.R = t.r_in_c ? dC.as<float>() : dR.as<float>();
-        }
+        g.A = st.in(t.x, (size_t)M * t.lda); g.amap = RowMap{t.lda, 0, 0};
+        g.W = t.wfmt == 1 ? (const void*)st.in(rm16.data(), nk) : st.in(rm.data(), nk);
+        g.w_bf16 = t.wfmt == 1; g.ldw = K; g.Wt = st.in(wt.data(), wt.size());
+        if (t.wfmt == 2) { g.wt_i8 = 1; g.wscale = st.in(wscale.data(), (size_t)N); }
+        g.bias = st.in(t.bias, (size_t)N);
+        g.addvec = st.in(t.addvec, (size_t)(t.tail ? N - 1 : N));
+        g.scale = st.in(t.scale, (size_t)N);
+        if (t.gate) { g.gate = st.in(t.gate, (size_t)M * t.ldg); g.ldg = t.ldg; }
+        g.C = dC; g.cmap = RowMap{t.ldc, 0, 0};
+        if (t.R && t.r_in_c) {   // the in-place residual (R is C: every element read and written by the same lane)
+            up(dC, t.R, c_elems * 4);
+            g.R = dC;
+        } else g.R = st.in(t.R, c_elems);
         g.alpha = t.alpha; g.epi = t.epi;
-        if (t.tail) g.tail = dTail.as<float>();
+        if (t.tail) g.tail = dTail;
         if (t.zrows) g.zstride = zrows * N;
         g.M = M; g.N = N; g.K = K;
         SkinnyFuse fu;
         if (fused) {
             fu.ln = t.ln; fu.eps = t.eps;
-            if (t.ln_w) { up(dLw.p, t.ln_w, (size_t)K * 4); fu.ln_w = dLw.as<float>(); }
-            if (t.ln_b) { up(dLb.p, t.ln_b, (size_t)K * 4); fu.ln_b = dLb.as<float>(); }
-            if (t.shift) { up(dSh.p, t.shift, mod_bytes); fu.shift = dSh.as<float>(); }
-            if (t.mscale) { up(dMs.p, t.mscale, mod_bytes); fu.scale = dMs.as<float>(); }
+            fu.ln_w = st.in(t.ln_w, (size_t)K); fu.ln_b = st.in(t.ln_b, (size_t)K);
+            fu.shift = st.in(t.shift, mod_elems); fu.scale = st.in(t.mscale, mod_elems);
             fu.ldmod = t.ldmod;
             if (t.planes) {
-                up(dPl.p, t.planes, (size_t)t.psplit * mk * 4);
-                fu.partial = dPl.as<float>(); fu.psplit = t.psplit; fu.pstride = (int64_t)mk;
-                if (t.pbias) { up(dPb.p, t.pbias, (size_t)K * 4); fu.pbias = dPb.as<float>(); }
+                fu.partial = st.in(t.planes, (size_t)t.psplit * mk); fu.psplit = t.psplit; fu.pstride = (int64_t)mk;
+                fu.pbias = st.in(t.pbias, (size_t)K);
             }
-            if (t.pgate) { fu.pgate = dXo.as<float>(); fu.ldpg = 1; }   // (never launched: the step kernel takes no gated pending sum)
-            fu.x_out = dXo.as<float>(); fu.y_out = dYo.as<float>();
+            if (t.pgate) { fu.pgate = dXo; fu.ldpg = 1; }   // (never launched: the step kernel takes no gated pending sum)
+            fu.x_out = dXo; fu.y_out = dYo;
         }
         // refused before any launch: whatever the predicates of the kernel refuse
         if (t.path == 0) {
@@ -573,25 +626,17 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
             c.M = std::min(M, 64);
             if (M > kSkinnyChunkRows || (M > 64 && t.tail) || !skinny_supported(c, 1)) throw Error(PTTS_EINVAL, "ptts_debug_step_linear: launch_gemm would not hand this product to the step kernel");
         }
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
-        g_launch_census = &census;
-        try {
-            if (t.path == 0) launch_skinny(g, fu, S, dPart.as<float>(), nullptr);
+        LaunchScope launches;
+        launches.run([&] {
+            if (t.path == 0) launch_skinny(g, fu, S, dPart, nullptr);
             else launch_gemm(g, nullptr);
-        } catch (...) { g_launch_census = census_before; throw; }
-        g_launch_census = census_before;
+        });
         PTTS_HIP(hipDeviceSynchronize());
-        if (t.launches) {
-            t.launches[0] = (int32_t)census["k_skinny"];
-            int64_t all = 0;
-            for (const auto& kv : census) all += kv.second;
-            t.launches[1] = (int32_t)all;
-        }
-        down(t.C, S > 1 ? dPart.p : dC.p, S > 1 ? p_bytes : c_bytes);
-        if (t.tail_out) down(t.tail_out, dTail.p, (size_t)M * 4);
-        if (t.x_out) down(t.x_out, dXo.p, mk * 4);
-        if (t.y_out) down(t.y_out, dYo.p, mk * 4);
+        if (t.launches) { t.launches[0] = (int32_t)launches.count("k_skinny"); t.launches[1] = (int32_t)launches.total(); }
+        down(t.C, S > 1 ? dPart : dC, (S > 1 ? p_elems : c_elems) * 4);
+        if (t.tail_out) down(t.tail_out, dTail, (size_t)M * 4);
+        if (t.x_out) down(t.x_out, dXo, mk * 4);
+        if (t.y_out) down(t.y_out, dYo, mk * 4);
     });
 }
 
@@ -620,55 +665,40 @@ int ptts_debug_attn_step(const ptts_attn_step_args* pa) {
             if (t.keys_now > 0 && t.active[r] && pos + 1 > t.keys_now) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_step: row %d at offset %d is beyond keys_now %d", r, pos, t.keys_now));
         }
         require_device();
-        const size_t qkv_bytes = (size_t)rows * t.qkv_ld * 4, tab_bytes = (size_t)cap * 32 * 4, out_bytes = (size_t)rows * t.out_ld * 4, kv_bytes = (size_t)rows * heads * cap * 64 * es;
-        Tmp dQ(qkv_bytes), dCos(tab_bytes), dSin(tab_bytes), dLen((size_t)rows * 4), dAct((size_t)rows * 4), dPl((size_t)rows * 4), dPk((size_t)rows * sizeof(void*)),
-            dPv((size_t)rows * sizeof(void*)), dK(kv_bytes), dV(kv_bytes), dO(out_bytes);
-        std::vector<std::unique_ptr<Tmp>> pre;   // [2 i]: keys of buffer i, [2 i + 1]: values
+        const size_t tab = (size_t)cap * 32, out_elems = (size_t)rows * t.out_ld, kv_bytes = (size_t)rows * heads * cap * 64 * es;
+        Stage st;
+        std::vector<const void*> pre;   // [2 i]: keys of buffer i, [2 i + 1]: values
         for (int i = 0; i < t.n_pre; i++) {
             const size_t n = (size_t)t.layers * heads * t.pre_rows[i] * 64 * es;
-            pre.emplace_back(new Tmp(n)); up(pre.back()->p, t.pre_k[i], n);
-            pre.emplace_back(new Tmp(n)); up(pre.back()->p, t.pre_v[i], n);
+            pre.push_back(st.in_bytes(t.pre_k[i], n));
+            pre.push_back(st.in_bytes(t.pre_v[i], n));
         }
         std::vector<const void*> hk((size_t)rows, nullptr), hv((size_t)rows, nullptr);
         for (int r = 0; r < rows; r++)
-            if (t.voice_of_row[r] >= 0) { hk[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r]]->p; hv[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r] + 1]->p; }
-        up(dQ.p, t.qkv, qkv_bytes); up(dCos.p, t.cos_t, tab_bytes); up(dSin.p, t.sin_t, tab_bytes);
-        up(dLen.p, t.seg_len, (size_t)rows * 4); up(dAct.p, t.active, (size_t)rows * 4); up(dPl.p, t.pre_len, (size_t)rows * 4);
-        up(dPk.p, hk.data(), (size_t)rows * sizeof(void*)); up(dPv.p, hv.data(), (size_t)rows * sizeof(void*));
-        up(dK.p, t.k, kv_bytes); up(dV.p, t.v, kv_bytes);
-        PTTS_HIP(hipMemset(dO.p, 0xff, out_bytes));
+            if (t.voice_of_row[r] >= 0) { hk[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r]]; hv[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r] + 1]; }
+        void *dK = st.in_bytes(t.k, kv_bytes), *dV = st.in_bytes(t.v, kv_bytes);
+        float* dO = st.out(out_elems);
         AttnArgs a;   // as step_core fills them
-        a.k = dK.p; a.v = dV.p; a.kv_bf16 = t.kv_bf16;
+        a.k = dK; a.v = dV; a.kv_bf16 = t.kv_bf16;
         a.k_seg_stride = (int64_t)heads * cap * 64; a.k_head_stride = (int64_t)cap * 64; a.k_row_stride = 64;
-        a.seg_len = dLen.as<int32_t>(); a.active = dAct.as<int32_t>();
+        a.seg_len = st.in(t.seg_len, (size_t)rows); a.active = st.in(t.active, (size_t)rows);
         a.context = -1;
-        a.out = dO.as<float>(); a.out_ld = t.out_ld;
+        a.out = dO; a.out_ld = t.out_ld;
         a.rows = rows; a.heads = heads; a.max_keys = cap;
         a.keys_now = t.keys_now;
-        a.fused_step = 1; a.qkv = dQ.as<float>(); a.qkv_ld = t.qkv_ld; a.d_model = D;
-        a.cos_t = dCos.as<float>(); a.sin_t = dSin.as<float>(); a.cap = cap;
-        a.pre_k = dPk.as<const void*>(); a.pre_v = dPv.as<const void*>(); a.pre_len = dPl.as<int32_t>(); a.layer = t.layer;
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
-        g_launch_census = &census;
-        try { launch_attention(a, nullptr); } catch (...) { g_launch_census = census_before; throw; }
-        g_launch_census = census_before;
-        if (census_before)   // (a caller's own census sees the launch too: a refusal leaves it empty)
-            for (const auto& kv : census) (*census_before)[kv.first] += kv.second;
+        a.fused_step = 1; a.qkv = st.in(t.qkv, (size_t)rows * t.qkv_ld); a.qkv_ld = t.qkv_ld; a.d_model = D;
+        a.cos_t = st.in(t.cos_t, tab); a.sin_t = st.in(t.sin_t, tab); a.cap = cap;
+        a.pre_k = st.in(hk.data(), (size_t)rows); a.pre_v = st.in(hv.data(), (size_t)rows); a.pre_len = st.in(t.pre_len, (size_t)rows); a.layer = t.layer;
+        LaunchScope launches;
+        launches.run([&] { launch_attention(a, nullptr); });
         PTTS_HIP(hipDeviceSynchronize());
         const bool step = std::string(g_last_attn_kernel) == "k_attn_step";
-        if (t.kernel && t.kernel_cap > 0) {
-            const size_t n = std::min<size_t>(std::strlen(g_last_attn_kernel), (size_t)t.kernel_cap - 1);
-            std::memcpy(t.kernel, g_last_attn_kernel, n);
-            t.kernel[n] = 0;
-        }
+        put_str(t.kernel, t.kernel_cap, g_last_attn_kernel);
         if (t.info) {
-            int64_t all = 0;
-            for (const auto& kv : census) all += kv.second;
             t.info[0] = step ? attn_step_launch_rounds(a) : 0;
-            t.info[1] = (int32_t)all; t.info[2] = (int32_t)census["k_attn_step"]; t.info[3] = (int32_t)census["k_attention"];
+            t.info[1] = (int32_t)launches.total(); t.info[2] = (int32_t)launches.count("k_attn_step"); t.info[3] = (int32_t)launches.count("k_attention");
         }
-        down(t.out, dO.p, out_bytes); down(t.k, dK.p, kv_bytes); down(t.v, dV.p, kv_bytes);
+        down(t.out, dO, out_elems * 4); down(t.k, dK, kv_bytes); down(t.v, dV, kv_bytes);
     });
 }
 
@@ -719,25 +749,27 @@ int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
             rows = segs * t.CT;
         }
         require_device();
-        const size_t q_bytes = (t.ragged ? (size_t)rows : (size_t)segs * t.T1) * t.ld * 4, kv_bytes = t.ragged ? (size_t)segs * heads * t.cap * 64 * es : 16,
-                     out_bytes = (size_t)rows * t.out_ld * 4, meta_n = (size_t)2 * rows + 2 * segs + 1;
-        Tmp dQ(q_bytes), dK(kv_bytes), dV(kv_bytes), dO(out_bytes), dMeta(meta_n * 4);
+        const size_t q_elems = (t.ragged ? (size_t)rows : (size_t)segs * t.T1) * t.ld, kv_bytes = (size_t)segs * heads * t.cap * 64 * es, out_elems = (size_t)rows * t.out_ld,
+                     meta_n = (size_t)2 * rows + 2 * segs + 1;
+        Stage st;
+        Tmp dMeta(meta_n * 4);
+        float *dQ = st.in(t.qkv, q_elems), *dO = st.out(out_elems);
         AttnArgs a;
         a.q_ld = t.ld; a.q_col0 = 0;
         a.context = t.context;
-        a.out = dO.as<float>(); a.out_ld = t.out_ld;
+        a.out = dO; a.out_ld = t.out_ld;
         a.rows = rows; a.heads = heads;
         if (t.ragged) {   // runtime.cpp, the prompt prefill: one upload holds row -> segment, row -> position, the segments' first rows and first positions
             int32_t* d_slot = dMeta.as<int32_t>();
             int32_t* d_pos = d_slot + rows;
-            a.q = dQ.as<float>();
-            a.k = dK.p; a.v = dV.p; a.kv_bf16 = t.kv_bf16;
+            a.q = dQ;
+            a.k = st.in_bytes(t.k, kv_bytes); a.v = st.in_bytes(t.v, kv_bytes); a.kv_bf16 = t.kv_bf16;
             a.k_seg_stride = (int64_t)heads * t.cap * 64; a.k_head_stride = (int64_t)t.cap * 64; a.k_row_stride = 64;
             a.row_seg = d_slot; a.row_pos = d_pos;
             a.rag_off = d_pos + rows; a.rag_pos0 = d_pos + rows + segs + 1; a.rag_segs = segs; a.rows_per_seg = longest;
             a.max_keys = max_pos + 1;
         } else {          // runtime.cpp mimi_range (encoder.cpp: t0 = 0, CT = T1, one segment)
-            float* qkv = dQ.as<float>();
+            float* qkv = dQ;
             a.q = qkv + (size_t)t.t0 * t.ld; a.q_rows_per_batch = t.CT; a.q_batch_stride = (int64_t)t.T1 * t.ld;
             a.k = qkv + D; a.v = qkv + 2 * D; a.kv_bf16 = 0;
             a.k_seg_stride = (int64_t)t.T1 * t.ld; a.k_head_stride = 64; a.k_row_stride = t.ld;
@@ -745,7 +777,6 @@ int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
             a.max_keys = std::min(t.T1, t.context);
         }
         if (!attn_window_supported(a) || (t.form && !attn_window_form_supported(a, t.form))) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: refused by attn_window_supported");
-        up(dQ.p, t.qkv, q_bytes);
         if (t.ragged) {
             std::vector<int32_t> meta(meta_n);
             std::copy(row_seg.begin(), row_seg.end(), meta.begin());
@@ -753,36 +784,20 @@ int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
             std::copy(t.rag_off, t.rag_off + segs + 1, meta.begin() + 2 * rows);
             std::copy(t.rag_pos0, t.rag_pos0 + segs, meta.begin() + 2 * rows + segs + 1);
             up(dMeta.p, meta.data(), meta_n * 4);
-            up(dK.p, t.k, kv_bytes); up(dV.p, t.v, kv_bytes);
         }
-        PTTS_HIP(hipMemset(dO.p, 0xff, out_bytes));
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
-        g_launch_census = &census;
-        try {
+        LaunchScope launches;
+        launches.run([&] {
             if (t.form == 0) launch_attention(a, nullptr);
             else launch_attn_window_as(a, t.form, nullptr);
-        } catch (...) { g_launch_census = census_before; throw; }
-        g_launch_census = census_before;
-        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        });
         PTTS_HIP(hipGetLastError());
         PTTS_HIP(hipDeviceSynchronize());
-        if (t.kernel && t.kernel_cap > 0) {
-            const char* name = t.form == 0 ? g_last_attn_kernel
-                             : t.form == 2 ? "k_attn_window_lds<4>"
-                             : !t.ragged ? "k_attn_window<false,false>" : (t.kv_bf16 ? "k_attn_window<true,true>" : "k_attn_window<false,true>");
-            const size_t n = std::min<size_t>(std::strlen(name), (size_t)t.kernel_cap - 1);
-            std::memcpy(t.kernel, name, n);
-            t.kernel[n] = 0;
-        }
-        if (t.launched && t.launched_cap > 0) {
-            std::string s;
-            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
-            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
-            std::memcpy(t.launched, s.data(), n);
-            t.launched[n] = 0;
-        }
-        down(t.out, dO.p, out_bytes);
+        put_str(t.kernel, t.kernel_cap,
+                t.form == 0 ? g_last_attn_kernel
+                : t.form == 2 ? "k_attn_window_lds<4>"
+                : !t.ragged ? "k_attn_window<false,false>" : (t.kv_bf16 ? "k_attn_window<true,true>" : "k_attn_window<false,true>"));
+        put_str(t.launched, t.launched_cap, launches.str());
+        down(t.out, dO, out_elems * 4);
     });
 }
 
@@ -815,48 +830,40 @@ int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {
         if (t.c_ld < N || (t.c_rows_per_batch && M > t.c_rows_per_batch && t.c_batch_stride < c_seg) || (planes > 1 && t.zstride < c_plane))
             throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: rows, segments or planes of C overlap");
         // the maps against the buffers: the largest element any row's K-wide read (a clamped row is row M - 1) and N-wide store / residual read can touch
-        auto roff = [](int64_t ld, int64_t rpb, int64_t bs, int64_t r) { return rpb ? (r / rpb) * bs + (r % rpb) * ld : r * ld; };
-        for (int64_t m = 0; m < M; m++) {
-            const int64_t ao = t.a_off + roff(t.a_ld, t.a_rows_per_batch, t.a_batch_stride, m);
-            if (ao + K > t.a_elems) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld of A ends at element %lld of %lld", (long long)m, (long long)(ao + K), (long long)t.a_elems));
-            const int64_t co = t.c_off + roff(t.c_ld, t.c_rows_per_batch, t.c_batch_stride, m) + (int64_t)(planes - 1) * t.zstride;
-            if (co + N > t.c_elems) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld of C ends at element %lld of %lld", (long long)m, (long long)(co + N), (long long)t.c_elems));
-            if (rope) {
+        const RowMap amap{t.a_ld, t.a_rows_per_batch, t.a_batch_stride}, cmap{t.c_ld, t.c_rows_per_batch, t.c_batch_stride};
+        check_rows("ptts_debug_gemm_rows", "A", M, t.a_elems, amap, t.a_off, K, false);
+        check_rows("ptts_debug_gemm_rows", "C", M, t.c_elems, cmap, t.c_off + (int64_t)(planes - 1) * t.zstride, N, false);   // (the last plane's rows)
+        if (rope)
+            for (int64_t m = 0; m < M; m++) {
                 const int64_t pos = t.rope_row_pos ? t.rope_row_pos[m] : (int64_t)t.rope_pos0 + (t.rope_rows_per_seg ? m % t.rope_rows_per_seg : m);
                 if (pos < 0 || pos >= t.n_pos) throw Error(PTTS_EINVAL, strfmt("ptts_debug_gemm_rows: row %lld at position %lld, the tables hold %d", (long long)m, (long long)pos, t.n_pos));
             }
-        }
         require_device();
         int dev = 0, cus = 0;
         PTTS_HIP(hipGetDevice(&dev));
         PTTS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         const size_t nw = (size_t)N * t.ldw, half = (size_t)(rope ? t.rope_hd / 2 : 0), ntab = (size_t)std::max(t.n_pos, 1) * std::max<size_t>(half, 1);
-        Tmp dA((size_t)t.a_elems * 4), dW(nw * 4), dC((size_t)t.c_elems * 4), dR((size_t)t.c_elems * 4), dB((size_t)N * 4), dAv((size_t)N * 4), dSc((size_t)N * 4),
-            dG((size_t)M * std::max(t.ldg, 1) * 4), dCos(ntab * 4), dSin(ntab * 4), dPos((size_t)M * 4);
-        up(dA.p, t.A, (size_t)t.a_elems * 4);
+        Stage st;
+        float* dC = st.out((size_t)t.c_elems);
+        GemmArgs g;
+        g.A = st.in(t.A, (size_t)t.a_elems) + t.a_off; g.amap = amap;
         if (t.w_bf16) {
             std::vector<uint16_t> w16(nw);
             for (size_t i = 0; i < nw; i++) w16[i] = f32_to_bf16_rne(t.W[i]);
-            up(dW.p, w16.data(), nw * 2);
-        } else up(dW.p, t.W, nw * 4);
-        PTTS_HIP(hipMemset(dC.p, 0xff, (size_t)t.c_elems * 4));
-        GemmArgs g;
-        g.A = dA.as<float>() + t.a_off; g.amap = RowMap{t.a_ld, t.a_rows_per_batch, t.a_batch_stride};
-        g.W = dW.p; g.w_bf16 = t.w_bf16; g.ldw = t.ldw;
-        g.C = dC.as<float>() + t.c_off; g.cmap = RowMap{t.c_ld, t.c_rows_per_batch, t.c_batch_stride};
-        if (t.bias) { up(dB.p, t.bias, (size_t)N * 4); g.bias = dB.as<float>(); }
-        if (t.addvec) { up(dAv.p, t.addvec, (size_t)N * 4); g.addvec = dAv.as<float>(); }
-        if (t.scale) { up(dSc.p, t.scale, (size_t)N * 4); g.scale = dSc.as<float>(); }
-        if (t.gate) { up(dG.p, t.gate, (size_t)M * t.ldg * 4); g.gate = dG.as<float>(); g.ldg = t.ldg; }
+            g.W = st.in(w16.data(), nw);
+        } else g.W = st.in(t.W, nw);
+        g.w_bf16 = t.w_bf16; g.ldw = t.ldw;
+        g.C = dC + t.c_off; g.cmap = cmap;
+        g.bias = st.in(t.bias, (size_t)N); g.addvec = st.in(t.addvec, (size_t)N); g.scale = st.in(t.scale, (size_t)N);
+        if (t.gate) { g.gate = st.in(t.gate, (size_t)M * t.ldg); g.ldg = t.ldg; }
         if (t.R) {   // r_in_c: the in-place residual (R is C: every element read and written by the same lane)
-            up(t.r_in_c ? dC.p : dR.p, t.R, (size_t)t.c_elems * 4);
-            g.R = (t.r_in_c ? dC.as<float>() : dR.as<float>()) + t.c_off;
+            if (t.r_in_c) up(dC, t.R, (size_t)t.c_elems * 4);
+            g.R = (t.r_in_c ? dC : st.in(t.R, (size_t)t.c_elems)) + t.c_off;
         }
         if (rope) {
-            up(dCos.p, t.rope_cos, ntab * 4); up(dSin.p, t.rope_sin, ntab * 4);
-            g.rope_cos = dCos.as<float>(); g.rope_sin = dSin.as<float>(); g.rope_cols = t.rope_cols; g.rope_hd = t.rope_hd; g.rope_pos0 = t.rope_pos0;
+            g.rope_cos = st.in(t.rope_cos, ntab); g.rope_sin = st.in(t.rope_sin, ntab); g.rope_cols = t.rope_cols; g.rope_hd = t.rope_hd; g.rope_pos0 = t.rope_pos0;
             g.rope_rows_per_seg = t.rope_rows_per_seg;
-            if (t.rope_row_pos) { up(dPos.p, t.rope_row_pos, (size_t)M * 4); g.rope_row_pos = dPos.as<int32_t>(); }
+            g.rope_row_pos = st.in(t.rope_row_pos, (size_t)M);
         }
         g.kslice = t.kslice; g.zstride = t.zstride; g.win_taps = t.win_taps; g.win_c = t.win_c;
         g.alpha = t.alpha; g.aop = t.aop; g.epi = t.epi; g.M = M; g.N = N; g.K = K;
@@ -892,10 +899,8 @@ int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {
                 if ((t.cfg == 1 || t.cfg == 2) && N % 256) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: a 256-column k_gemm5 form needs N % 256 == 0 (its weight loads are not bounded)");
                 break;
         }
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
-        g_launch_census = &census;
-        try {
+        LaunchScope launches;
+        launches.run([&] {
             switch (t.kernel) {
                 case 0:
                     if (rope) { if (!launch_gemm_rope(g, nullptr)) throw Error(PTTS_EINVAL, "ptts_debug_gemm_rows: no RoPE epilogue for this shape"); }
@@ -903,24 +908,16 @@ int ptts_debug_gemm_rows(const ptts_gemm_rows_args* pa) {
                     break;
                 case 1: launch_gemm(g, nullptr); break;
                 case 2: launch_gemm2(g, nullptr); break;
-                case 3: g_gemm3_cfg = t.cfg; launch_gemm3(g, nullptr); g_gemm3_cfg = 0; break;
+                case 3: { Scoped<int> cfg(g_gemm3_cfg, t.cfg); launch_gemm3(g, nullptr); break; }
                 case 4: launch_gemm_wres_as(g, rgl, nullptr); break;
-                default: g_gemm5_cfg = t.cfg; launch_gemm5(g, nullptr); g_gemm5_cfg = 0; break;
+                default: { Scoped<int> cfg(g_gemm5_cfg, t.cfg); launch_gemm5(g, nullptr); break; }
             }
-        } catch (...) { g_launch_census = census_before; g_gemm3_cfg = 0; g_gemm5_cfg = 0; throw; }
-        g_launch_census = census_before;
-        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        });
         PTTS_HIP(hipGetLastError());
         PTTS_HIP(hipDeviceSynchronize());
-        if (t.launched && t.launched_cap > 0) {
-            std::string s;
-            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
-            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
-            std::memcpy(t.launched, s.data(), n);
-            t.launched[n] = 0;
-        }
+        put_str(t.launched, t.launched_cap, launches.str());
         if (t.info) { t.info[0] = cus; t.info[1] = rgl; }
-        down(t.C, dC.p, (size_t)t.c_elems * 4);
+        down(t.C, dC, (size_t)t.c_elems * 4);
     });
 }
 
@@ -974,8 +971,7 @@ int ptts_debug_plan_seanet_frags(ptts_plan* hp, int32_t item, uint16_t* hi, uint
     });
 }
 
-// ONE launch of k_resblock / k_resblock_up on host operands.  Everything is checked before anything is launched; every output is pre-filled with
-// 0xff bytes and comes back whole; the slack rows of u and xin are NaN.  The weights go through the loader's own packers (model.h).
+// ONE launch of k_resblock / k_resblock_up on host operands.  The slack rows of u and xin are NaN.  The weights go through the loader's own packers (model.h).
 int ptts_debug_resblock(const ptts_resblock_args* pa) {
     return guard([&] {
         if (!pa) throw Error(PTTS_EINVAL, "ptts_debug_resblock: null argument");
@@ -1029,46 +1025,32 @@ int ptts_debug_resblock(const ptts_resblock_args* pa) {
         }
         require_device();
         const int64_t urows = (int64_t)t.pad + L + t.slack, u_bs = urows * C, xrows = up_ ? (int64_t)t.x_pad + t.x_L + t.x_slack : 1, x_bs = xrows * 128;
-        const size_t u_bytes = (size_t)B * u_bs * 4, x_bytes = (size_t)B * x_bs * 4, pcm_bytes = (size_t)B * L * 4, row_bytes = t.rows ? (size_t)B * t.row_bytes : 0;
-        Tmp dU(u_bytes), dUo(u_bytes), dX(x_bytes), dPcm(pcm_bytes), dRows(row_bytes), dPr((size_t)B * sizeof(PcmRow)),
-            dW1(n1 * 2), dW1l(n1 * 2), dW2(n2 * 2), dW2l(n2 * 2), dWf(nf * 2), dWfl(nf * 2), dWu(nu * 2), dB1((size_t)H * 4), dB2((size_t)C * 4), dBf(16), dBu(64 * 4);
-        {   // rows [pad + L] of every utterance as given, NaN in the slack rows behind them
-            std::vector<float> img((size_t)B * u_bs, std::nanf(""));
-            if (t.u) for (int b = 0; b < B; b++) std::memcpy(img.data() + (size_t)b * u_bs, t.u + (size_t)b * (t.pad + L) * C, (size_t)(t.pad + L) * C * 4);
-            up(dU.p, img.data(), u_bytes);
-            if (up_) {
-                std::vector<float> xi((size_t)B * x_bs, std::nanf(""));
-                for (int b = 0; b < B; b++) std::memcpy(xi.data() + (size_t)b * x_bs, t.xin + (size_t)b * (t.x_pad + t.x_L) * 128, (size_t)(t.x_pad + t.x_L) * 128 * 4);
-                up(dX.p, xi.data(), x_bytes);
-            }
-        }
-        PTTS_HIP(hipMemset(dUo.p, 0xff, u_bytes)); PTTS_HIP(hipMemset(dPcm.p, 0xff, pcm_bytes));
-        if (row_bytes) PTTS_HIP(hipMemset(dRows.p, 0xff, row_bytes));
-        up(dW1.p, w1h.data(), n1 * 2); up(dW2.p, w2h.data(), n2 * 2);
-        if (!bf) { up(dW1l.p, w1l.data(), n1 * 2); up(dW2l.p, w2l.data(), n2 * 2); }
+        const size_t u_elems = (size_t)B * u_bs, x_elems = (size_t)B * x_bs, pcm_elems = (size_t)B * L, row_bytes = t.rows ? (size_t)B * t.row_bytes : 0;
+        Stage st;
+        std::vector<float> img(u_elems, std::nanf("")), xi(up_ ? x_elems : 0, std::nanf(""));   // rows [pad + L] of every utterance as given, NaN in the slack rows behind them
+        if (t.u) for (int b = 0; b < B; b++) std::memcpy(img.data() + (size_t)b * u_bs, t.u + (size_t)b * (t.pad + L) * C, (size_t)(t.pad + L) * C * 4);
+        if (up_) for (int b = 0; b < B; b++) std::memcpy(xi.data() + (size_t)b * x_bs, t.xin + (size_t)b * (t.x_pad + t.x_L) * 128, (size_t)(t.x_pad + t.x_L) * 128 * 4);
+        float *dUo = st.out(u_elems), *dPcm = st.out(pcm_elems);
+        uint8_t* dRows = st.out<uint8_t>(row_bytes);
         ResArgs a;
-        a.u = dU.as<float>(); a.u_bs = u_bs; a.pad = t.pad;
-        a.w1 = dW1.p; a.w2 = dW2.p;
-        if (!bf) { a.w1_lo = dW1l.p; a.w2_lo = dW2l.p; }
-        if (t.b1) { up(dB1.p, t.b1, (size_t)H * 4); a.b1 = dB1.as<float>(); }
-        if (t.b2) { up(dB2.p, t.b2, (size_t)C * 4); a.b2 = dB2.as<float>(); }
+        a.u = st.in(img.data(), u_elems); a.u_bs = u_bs; a.pad = t.pad;
+        a.w1 = st.in(w1h.data(), n1); a.w2 = st.in(w2h.data(), n2);
+        if (!bf) { a.w1_lo = st.in(w1l.data(), n1); a.w2_lo = st.in(w2l.data(), n2); }
+        a.b1 = st.in(t.b1, (size_t)H); a.b2 = st.in(t.b2, (size_t)C);
         a.B = B; a.L = L; a.t0 = t.t0; a.t1 = t.t1; a.C = C; a.H = H; a.k1 = 3; a.k2 = 1; a.w_bf16 = bf; a.final_conv = fin;
         if (fin) {
-            up(dWf.p, wfh.data(), nf * 2); up(dWfl.p, wfl.data(), nf * 2);
-            a.kf = 3; a.wf_hi = dWf.p; a.wf_lo = dWfl.p;
-            if (t.bf) { up(dBf.p, t.bf, 4); a.bf = dBf.as<float>(); }
-            a.pcm = dPcm.as<float>(); a.pcm_bs = L;
+            a.kf = 3; a.wf_hi = st.in(wfh.data(), nf); a.wf_lo = st.in(wfl.data(), nf);
+            a.bf = st.in(t.bf, 1);
+            a.pcm = dPcm; a.pcm_bs = L;
             if (t.rows) {
                 std::vector<PcmRow> pr((size_t)B);
-                for (int b = 0; b < B; b++) pr[b] = PcmRow{dRows.as<uint8_t>() + (size_t)b * t.row_bytes, t.rows[2 * b], t.rows[2 * b + 1] != 0};
-                up(dPr.p, pr.data(), (size_t)B * sizeof(PcmRow));
-                a.pcm_rows = dPr.as<PcmRow>();
+                for (int b = 0; b < B; b++) pr[b] = PcmRow{dRows + (size_t)b * t.row_bytes, t.rows[2 * b], t.rows[2 * b + 1] != 0};
+                a.pcm_rows = st.in(pr.data(), (size_t)B);
             }
-        } else a.uo = dUo.as<float>();
+        } else a.uo = dUo;
         if (up_) {
-            up(dWu.p, wuh.data(), nu * 2);
-            a.fuse_up = 1; a.xin = dX.as<float>(); a.x_bs = x_bs; a.x_pad = t.x_pad; a.x_L = t.x_L; a.CI = 128; a.up_stride = 4; a.wup = dWu.p;
-            if (t.bup) { up(dBu.p, t.bup, 64 * 4); a.bup = dBu.as<float>(); }
+            a.fuse_up = 1; a.xin = st.in(xi.data(), x_elems); a.x_bs = x_bs; a.x_pad = t.x_pad; a.x_L = t.x_L; a.CI = 128; a.up_stride = 4; a.wup = st.in(wuh.data(), nu);
+            a.bup = st.in(t.bup, 64);
         }
         // refused before any launch: whatever the kernels' own predicates refuse
         if (!(up_ ? resblock_up_shape_supported(a) : resblock_supported(a))) throw Error(PTTS_EINVAL, "ptts_debug_resblock: refused by resblock_supported / resblock_up_shape_supported");
@@ -1077,9 +1059,9 @@ int ptts_debug_resblock(const ptts_resblock_args* pa) {
         PTTS_HIP(hipGetLastError());
         PTTS_HIP(hipDeviceSynchronize());
         if (t.launched) { t.launched[0] = plan.nw; t.launched[1] = plan.pers; t.launched[2] = plan.grid; t.launched[3] = plan.tiles; t.launched[4] = plan.tout; }
-        if (t.uo) down(t.uo, dUo.p, u_bytes);
-        if (t.pcm) down(t.pcm, dPcm.p, pcm_bytes);
-        if (t.rows) down(t.row_out, dRows.p, row_bytes);
+        if (t.uo) down(t.uo, dUo, u_elems * 4);
+        if (t.pcm) down(t.pcm, dPcm, pcm_elems * 4);
+        if (t.rows) down(t.row_out, dRows, row_bytes);
     });
 }
 
@@ -1111,21 +1093,9 @@ int ptts_debug_mimi_fused(const ptts_mimi_fused_args* pa) {
             throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: bad RoPE arguments");
         const int M = t.M, D = t.D, F = t.F;
         // the maps against the buffers; rows that are stored to must not overlap (two lanes would store to one element)
-        auto check_map = [&](const char* what, int64_t elems, int64_t ld, int64_t rpb, int64_t bs, int64_t off, int width, bool disjoint) {
-            std::vector<int64_t> start((size_t)M);
-            for (int64_t m = 0; m < M; m++) {
-                const int64_t o = off + (rpb ? (m / rpb) * bs + (m % rpb) * ld : m * ld);
-                if (o < 0 || o + width > elems)
-                    throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: row %lld of %s ends at element %lld of %lld", (long long)m, what, (long long)(o + width), (long long)elems));
-                start[(size_t)m] = o;
-            }
-            if (!disjoint) return;
-            std::sort(start.begin(), start.end());
-            for (size_t i = 1; i < start.size(); i++)
-                if (start[i] - start[i - 1] < width) throw Error(PTTS_EINVAL, strfmt("ptts_debug_mimi_fused: rows of %s overlap (elements %lld and %lld)", what, (long long)start[i - 1], (long long)start[i]));
-        };
-        check_map("x", t.x_elems, t.x_ld, t.x_rows_per_batch, t.x_batch_stride, t.x_off, D, ffn);
-        if (!ffn) check_map("y", t.y_elems, t.y_ld, t.y_rows_per_batch, t.y_batch_stride, t.y_off, F, true);
+        const RowMap xmap{t.x_ld, t.x_rows_per_batch, t.x_batch_stride}, ymap{t.y_ld, t.y_rows_per_batch, t.y_batch_stride};
+        check_rows("ptts_debug_mimi_fused", "x", M, t.x_elems, xmap, t.x_off, D, ffn);
+        if (!ffn) check_rows("ptts_debug_mimi_fused", "y", M, t.y_elems, ymap, t.y_off, F, true);
         if (rope)
             for (int64_t m = 0; m < M; m++) {
                 const int64_t pos = (int64_t)t.pos0 + (t.rows_per_seg ? m % t.rows_per_seg : m);
@@ -1133,22 +1103,24 @@ int ptts_debug_mimi_fused(const ptts_mimi_fused_args* pa) {
             }
         require_device();
         const size_t img_entries = ffn ? ffn_image_count(F) : w1_image_count(F), ntab = rope ? (size_t)t.n_pos * 32 : 0;
-        Tmp dX((size_t)t.x_elems * 4), dY(ffn ? 0 : (size_t)t.y_elems * 4), dLw((size_t)D * 4), dLb((size_t)D * 4), dLs(((size_t)D + t.ls_off) * 4), dImg(img_entries * 2),
-            dCos(ntab * 4), dSin(ntab * 4);
+        // (allocated here, uploaded behind the predicates: they are what vouches for the widths the uploads and the packers read)
+        Stage st;
+        Tmp dX((size_t)t.x_elems * 4), dLw((size_t)D * 4), dLb((size_t)D * 4), dLs(((size_t)D + t.ls_off) * 4), dImg(img_entries * 2), dCos(ntab * 4), dSin(ntab * 4);
+        float* dY = ffn ? nullptr : st.out((size_t)t.y_elems);
         FfnArgs fa;
         RowLinArgs ra;
         if (ffn) {
-            fa.x = dX.as<float>() + t.x_off; fa.xmap = RowMap{t.x_ld, t.x_rows_per_batch, t.x_batch_stride};
+            fa.x = dX.as<float>() + t.x_off; fa.xmap = xmap;
             fa.ln_w = dLw.as<float>(); fa.ln_b = dLb.as<float>(); fa.eps = t.eps;
             fa.img = dImg.p;
             if (t.ls) fa.ls = dLs.as<float>() + t.ls_off;
             fa.M = M; fa.D = D; fa.F = F;
             if (!mimi_ffn_supported(fa)) throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: refused by mimi_ffn_supported");
         } else {
-            ra.x = dX.as<float>() + t.x_off; ra.xmap = RowMap{t.x_ld, t.x_rows_per_batch, t.x_batch_stride};
+            ra.x = dX.as<float>() + t.x_off; ra.xmap = xmap;
             ra.ln_w = dLw.as<float>(); ra.ln_b = dLb.as<float>(); ra.eps = t.eps;
             ra.img = dImg.p;
-            ra.y = dY.as<float>() + t.y_off; ra.ymap = RowMap{t.y_ld, t.y_rows_per_batch, t.y_batch_stride};
+            ra.y = dY + t.y_off; ra.ymap = ymap;
             if (rope) { ra.rope_cos = dCos.as<float>(); ra.rope_sin = dSin.as<float>(); ra.rope_cols = t.rope_cols; ra.rope_pos0 = t.pos0; ra.rope_rows_per_seg = t.rows_per_seg; }
             ra.M = M; ra.N = F; ra.K = D;
             if (!mimi_rowlin_supported(ra)) throw Error(PTTS_EINVAL, "ptts_debug_mimi_fused: refused by mimi_rowlin_supported");
@@ -1162,27 +1134,16 @@ int ptts_debug_mimi_fused(const ptts_mimi_fused_args* pa) {
         up(dLw.p, t.ln_w, (size_t)D * 4); up(dLb.p, t.ln_b, (size_t)D * 4);
         if (t.ls) up(dLs.as<float>() + t.ls_off, t.ls, (size_t)D * 4);
         if (rope) { up(dCos.p, t.rope_cos, ntab * 4); up(dSin.p, t.rope_sin, ntab * 4); }
-        if (!ffn) PTTS_HIP(hipMemset(dY.p, 0xff, (size_t)t.y_elems * 4));
-        std::map<std::string, int64_t> census;
-        std::map<std::string, int64_t>* const census_before = g_launch_census;
-        g_launch_census = &census;
-        try {
+        LaunchScope launches;
+        launches.run([&] {
             if (ffn) launch_mimi_ffn(fa, nullptr);
             else launch_mimi_rowlin(ra, nullptr);
-        } catch (...) { g_launch_census = census_before; throw; }
-        g_launch_census = census_before;
-        if (census_before) for (const auto& kv : census) (*census_before)[kv.first] += kv.second;   // a census the caller switched on sees the launch too
+        });
         PTTS_HIP(hipGetLastError());
         PTTS_HIP(hipDeviceSynchronize());
-        if (t.launched && t.launched_cap > 0) {
-            std::string s;
-            for (const auto& kv : census) s += kv.first + "=" + std::to_string(kv.second) + ";";
-            const size_t n = std::min<size_t>(s.size(), (size_t)t.launched_cap - 1);
-            std::memcpy(t.launched, s.data(), n);
-            t.launched[n] = 0;
-        }
+        put_str(t.launched, t.launched_cap, launches.str());
         if (ffn) down(t.out, dX.p, (size_t)t.x_elems * 4);
-        else down(t.out, dY.p, (size_t)t.y_elems * 4);
+        else down(t.out, dY, (size_t)t.y_elems * 4);
     });
 }
 

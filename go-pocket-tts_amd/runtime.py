@@ -30,6 +30,7 @@ _PCM_DTYPES = {PCM_F32: "<f4", PCM_S16: "<i2", PCM_ULAW: "|u1", PCM_ALAW: "|u1"}
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int64)
 _DP = C.POINTER(C.c_double)
+_I32P = C.POINTER(C.c_int32)
 _STEP_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
 _PCM_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 
@@ -368,6 +369,9 @@ def hooks():
         H.ptts_debug_loudness_energies.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_DP)]
         H.ptts_debug_dsp_opts_error.restype = C.c_int64
         H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
+        for name, args in (("flow_cluster", _FlowClusterArgs), ("step_linear", _StepLinearArgs), ("attn_step", _AttnStepArgs), ("attn_window", _AttnWindowArgs),
+                           ("gemm_rows", _GemmRowsArgs), ("mimi_fused", _MimiFusedArgs), ("resblock", _ResblockArgs)):   # the hooks on a struct of host operands
+            getattr(H, "ptts_debug_" + name).argtypes = [C.POINTER(args)]
         _hooks = H
     return _hooks
 
@@ -400,6 +404,32 @@ def _fp(a: Optional[np.ndarray]):
 
 def _ip(a: np.ndarray):
     return C.cast(a.ctypes.data, _IP)
+
+
+class _Keep:
+    """Pointers for the fields of a ctypes struct: None gives a null pointer, anything else is made a contiguous array that stays referenced as long as
+    this object does (the struct itself holds addresses only)."""
+
+    def __init__(self):
+        self.arrays = []
+
+    def _ptr(self, a, dtype, ptr):
+        if a is None:
+            return C.cast(None, ptr)
+        a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
+        self.arrays.append(a)
+        return C.cast(a.ctypes.data, ptr)
+
+    def f32(self, a):
+        return self._ptr(a, np.float32, _FP)
+
+    def i32(self, a):
+        return self._ptr(a, np.int32, _I32P)
+
+
+def _census_dict(buf) -> dict:
+    """{kernel: count} of a census string "k=v;k=v;" in a ctypes buffer."""
+    return {k: int(v) for k, v in (item.split("=") for item in buf.value.decode().split(";") if item)}
 
 
 # ----------------------------------------------------------------------------- reference-shaped types
@@ -1398,22 +1428,18 @@ def debug_flow_cluster(fx, ada, ln_w, ln_b, w0, b0, w2, b2, eps, *, launch_rows=
     back = None if in_place else np.empty((n, rows, 512), np.float32)
     state = np.zeros(FLOW_CLUSTER_TILES + 1, np.uint32)
     launched = C.create_string_buffer(256)
-    a = _FlowClusterArgs()
+    a, keep = _FlowClusterArgs(), _Keep()
     a.rows, a.depth, a.n_launch, a.in_place, a.tag_base0 = rows, depth, n, (1 if in_place else 0), int(tag_base0)
     a.ldmod, a.launched_cap = ada.shape[1], 256
-    a.fx, a.ada, a.ln_w, a.ln_b, a.b0, a.b2, a.eps, a.w0, a.w2 = [_fp(x) for x in (fx, ada, ln_w, ln_b, b0, b2, eps, w0, w2)]
-    a.launch_rows = C.cast(lr.ctypes.data, C.POINTER(C.c_int32))
-    a.out = _fp(out)
-    a.fx_back = _fp(back) if back is not None else C.cast(None, _FP)
+    a.fx, a.ada, a.ln_w, a.ln_b, a.b0, a.b2, a.eps, a.w0, a.w2 = [keep.f32(x) for x in (fx, ada, ln_w, ln_b, b0, b2, eps, w0, w2)]
+    a.launch_rows = keep.i32(lr)
+    a.out, a.fx_back = keep.f32(out), keep.f32(back)
     a.state = C.cast(state.ctypes.data, C.POINTER(C.c_uint32))
     a.launched = C.cast(launched, C.c_char_p)
     for name in null:
         setattr(a, name, C.cast(None, dict(_FlowClusterArgs._fields_)[name]))
-    H = hooks()
-    H.ptts_debug_flow_cluster.argtypes = [C.POINTER(_FlowClusterArgs)]
-    rc = H.ptts_debug_flow_cluster(C.byref(a))
-    res = {"out": out, "fx_back": back, "tags": state[:FLOW_CLUSTER_TILES].copy(), "fault": int(state[FLOW_CLUSTER_TILES]),
-           "launched": {kv.split("=")[0]: int(kv.split("=")[1]) for kv in launched.value.decode().split(";") if kv}}
+    rc = hooks().ptts_debug_flow_cluster(C.byref(a))
+    res = {"out": out, "fx_back": back, "tags": state[:FLOW_CLUSTER_TILES].copy(), "fault": int(state[FLOW_CLUSTER_TILES]), "launched": _census_dict(launched)}
     try:
         _check(rc)
     except PttsError as e:
@@ -1443,16 +1469,8 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     n, k = w.shape
     ldc = n if ldc is None else int(ldc)
     s = max(1, int(splitk))
-    keep = []   # the arrays the struct points into
-
-    def ptr(a):
-        if a is None:
-            return C.cast(None, _FP)
-        a = _f32(a)
-        keep.append(a)
-        return _fp(a)
-
-    a = _StepLinearArgs()
+    a, keep = _StepLinearArgs(), _Keep()
+    ptr = keep.f32
     a.M, a.N, a.K, a.lda, a.ldc, a.wfmt, a.epi, a.splitk, a.tail, a.path = m, n, k, lda, ldc, int(wfmt), int(epi), s, 1 if tail else 0, int(path)
     a.ldg = 0 if gate is None else int(np.asarray(gate).shape[1])
     a.ln = 1 if ln else 0
@@ -1473,10 +1491,8 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     ws = np.empty(n, np.float32) if int(wfmt) == 2 else None
     cnt = (C.c_int32 * 2)()
     a.C, a.tail_out, a.x_out, a.y_out, a.w_eff, a.w_scale = ptr(out), ptr(tl), ptr(xo), ptr(yo), ptr(we), ptr(ws)
-    a.launches = C.cast(cnt, C.POINTER(C.c_int32))
-    H = hooks()
-    H.ptts_debug_step_linear.argtypes = [C.POINTER(_StepLinearArgs)]
-    _check(H.ptts_debug_step_linear(C.byref(a)))
+    a.launches = C.cast(cnt, _I32P)
+    _check(hooks().ptts_debug_step_linear(C.byref(a)))
     return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
 
 
@@ -1512,19 +1528,17 @@ def debug_attn_step(qkv, cos, sin, seg_len, k, v, *, kv_bf16, heads, layers=1, l
     out = np.empty((rows, max(out_ld, 0)), np.float32)
     name = C.create_string_buffer(64)
     info = (C.c_int32 * 4)()
-    a = _AttnStepArgs()
+    a, keep = _AttnStepArgs(), _Keep()
     a.kv_bf16, a.heads, a.rows, a.layers, a.layer, a.cap, a.keys_now, a.n_pre = (1 if kv_bf16 else 0), int(heads), rows, int(layers), int(layer), cap, int(keys_now), len(pre_k)
     a.qkv_ld, a.out_ld, a.kernel_cap = qkv_ld, out_ld, 64
-    a.qkv, a.cos_t, a.sin_t = _fp(qkv), _fp(cos), _fp(sin)
-    a.seg_len, a.active, a.pre_len, a.voice_of_row = [C.cast(x.ctypes.data, C.POINTER(C.c_int32)) for x in (seg_len, active, pre_len, voice_of_row)]
+    a.qkv, a.cos_t, a.sin_t = keep.f32(qkv), keep.f32(cos), keep.f32(sin)
+    a.seg_len, a.active, a.pre_len, a.voice_of_row = [keep.i32(x) for x in (seg_len, active, pre_len, voice_of_row)]
     for i, (pk, pv) in enumerate(zip(pre_k, pre_v)):
         a.pre_k[i], a.pre_v[i], a.pre_rows[i] = pk.ctypes.data, pv.ctypes.data, pk.shape[2]
-    a.k, a.v, a.out = k.ctypes.data, v.ctypes.data, _fp(out)
+    a.k, a.v, a.out = k.ctypes.data, v.ctypes.data, keep.f32(out)
     a.kernel = C.cast(name, C.c_char_p)
-    a.info = C.cast(info, C.POINTER(C.c_int32))
-    H = hooks()
-    H.ptts_debug_attn_step.argtypes = [C.POINTER(_AttnStepArgs)]
-    _check(H.ptts_debug_attn_step(C.byref(a)))
+    a.info = C.cast(info, _I32P)
+    _check(hooks().ptts_debug_attn_step(C.byref(a)))
     return {"out": out, "k": k, "v": v, "kernel": name.value.decode(), "rounds": int(info[0]), "launches": int(info[1]), "k_attn_step": int(info[2]),
             "k_attention": int(info[3])}
 
@@ -1555,8 +1569,7 @@ def debug_attn_window(qkv, *, heads, context, form=0, t0=0, ct=None, k=None, v=N
     "kernel" (the dispatch's name, or the instance's), "launched" ({kernel: count})."""
     qkv = _f32(qkv)
     ragged = rag_off is not None
-    a = _AttnWindowArgs()
-    keep = [qkv]
+    a, keep = _AttnWindowArgs(), _Keep()
     if ragged:
         es = 2 if kv_bf16 else 4
         k, v = np.ascontiguousarray(k), np.ascontiguousarray(v)
@@ -1568,8 +1581,7 @@ def debug_attn_window(qkv, *, heads, context, form=0, t0=0, ct=None, k=None, v=N
         rows, ld = qkv.shape
         a.cap, a.rows = k.shape[2], rows
         a.k, a.v = k.ctypes.data, v.ctypes.data
-        a.rag_off, a.rag_pos0 = [C.cast(x.ctypes.data, C.POINTER(C.c_int32)) for x in (rag_off, rag_pos0)]
-        keep += [k, v, rag_off, rag_pos0]
+        a.rag_off, a.rag_pos0 = keep.i32(rag_off), keep.i32(rag_pos0)
     else:
         if qkv.ndim != 3:
             raise PttsError(PTTS_EINVAL, "debug_attn_window: the dense operand is [segs, T1, ld]")
@@ -1582,12 +1594,10 @@ def debug_attn_window(qkv, *, heads, context, form=0, t0=0, ct=None, k=None, v=N
     name, launched = C.create_string_buffer(64), C.create_string_buffer(256)
     a.form, a.ragged, a.kv_bf16, a.heads, a.segs, a.context = int(form), (1 if ragged else 0), (1 if kv_bf16 else 0), int(heads), segs, int(context)
     a.ld, a.out_ld, a.kernel_cap, a.launched_cap = ld, out_ld, 64, 256
-    a.qkv, a.out = _fp(qkv), _fp(out)
+    a.qkv, a.out = keep.f32(qkv), keep.f32(out)
     a.kernel, a.launched = C.cast(name, C.c_char_p), C.cast(launched, C.c_char_p)
-    H = hooks()
-    H.ptts_debug_attn_window.argtypes = [C.POINTER(_AttnWindowArgs)]
-    _check(H.ptts_debug_attn_window(C.byref(a)))
-    return {"out": out, "kernel": name.value.decode(), "launched": {kv.split("=")[0]: int(kv.split("=")[1]) for kv in launched.value.decode().split(";") if kv}}
+    _check(hooks().ptts_debug_attn_window(C.byref(a)))
+    return {"out": out, "kernel": name.value.decode(), "launched": _census_dict(launched)}
 
 
 class _GemmRowsArgs(C.Structure):   # ptts_gemm_rows_args
@@ -1612,16 +1622,8 @@ def debug_gemm_rows(a_buf, w, M, *, amap, cmap, c_elems, kernel=0, cfg=0, rgl=0,
     4 k_gemm_wres / 5 k_gemm5.  Returns a dict: "out" (the whole C buffer, 0xff bytes where nothing was stored), "launched" ({kernel: count}), "cus", "rgl"."""
     a_buf, w = _f32(a_buf).reshape(-1), _f32(w)
     n, ldw = w.shape
-    keep = []
-
-    def ptr(x):
-        if x is None:
-            return C.cast(None, _FP)
-        x = _f32(x)
-        keep.append(x)
-        return _fp(x)
-
-    a = _GemmRowsArgs()
+    a, keep = _GemmRowsArgs(), _Keep()
+    ptr = keep.f32
     a.M, a.N, a.K, a.ldw, a.w_bf16, a.aop, a.epi = int(M), n, ldw if K is None else int(K), ldw, 1 if w_bf16 else 0, int(aop), int(epi)
     a.kernel, a.cfg, a.rgl, a.r_in_c = int(kernel), int(cfg), int(rgl), 1 if inplace else 0
     a.ldg = 0 if gate is None else int(np.asarray(gate).shape[1])
@@ -1642,21 +1644,16 @@ def debug_gemm_rows(a_buf, w, M, *, amap, cmap, c_elems, kernel=0, cfg=0, rgl=0,
         a.rope_cos, a.rope_sin, a.n_pos = ptr(cos), ptr(sin), cos.shape[0]
         a.rope_cols, a.rope_hd, a.rope_pos0, a.rope_rows_per_seg = int(rope_cols), int(rope_hd), int(rope_pos0), int(rope_rows_per_seg)
         if rope_row_pos is not None:
-            rp = np.ascontiguousarray(np.asarray(rope_row_pos, np.int32).reshape(int(M)))
-            keep.append(rp)
-            a.rope_row_pos = rp.ctypes.data_as(C.POINTER(C.c_int32))
+            a.rope_row_pos = keep.i32(np.asarray(rope_row_pos, np.int32).reshape(int(M)))
     a.kslice, a.zstride, a.win_taps, a.win_c = int(kslice), int(zstride), int(win_taps), int(win_c)
     out = np.empty(int(c_elems), np.float32)
     a.C = ptr(out)
     name = C.create_string_buffer(512)
     a.launched, a.launched_cap = C.cast(name, C.c_char_p), 512
     info = (C.c_int32 * 2)()
-    a.info = C.cast(info, C.POINTER(C.c_int32))
-    H = hooks()
-    H.ptts_debug_gemm_rows.argtypes = [C.POINTER(_GemmRowsArgs)]
-    _check(H.ptts_debug_gemm_rows(C.byref(a)))
-    launched = {k: int(v) for k, v in (item.split("=") for item in name.value.decode().split(";") if item)}
-    return {"out": out, "launched": launched, "cus": int(info[0]), "rgl": int(info[1])}
+    a.info = C.cast(info, _I32P)
+    _check(hooks().ptts_debug_gemm_rows(C.byref(a)))
+    return {"out": out, "launched": _census_dict(name), "cus": int(info[0]), "rgl": int(info[1])}
 
 
 class _MimiFusedArgs(C.Structure):   # ptts_mimi_fused_args
@@ -1677,16 +1674,8 @@ def debug_mimi_fused(kind, x_buf, M, *, xmap, ln_w, ln_b, w1, w2=None, eps=1e-5,
     None; rope = (cos, sin) tables [n_pos, 32].  D / F override the widths taken from w1's shape (for refusals).  Returns a dict: "out" (kind 0: the whole x buffer
     after the in-place launch; kind 1: the whole y buffer, 0xff bytes where nothing was stored), "launched" ({kernel: count})."""
     x_buf, w1 = _f32(x_buf).reshape(-1), _f32(w1)
-    keep = []
-
-    def ptr(v):
-        if v is None:
-            return C.cast(None, _FP)
-        v = _f32(v)
-        keep.append(v)
-        return _fp(v)
-
-    a = _MimiFusedArgs()
+    a, keep = _MimiFusedArgs(), _Keep()
+    ptr = keep.f32
     a.kind, a.M, a.D, a.F = int(kind), int(M), int(w1.shape[1] if D is None else D), int(w1.shape[0] if F is None else F)
     a.eps, a.ls_off = float(eps), int(ls_off)
     a.x_elems = x_buf.size
@@ -1703,11 +1692,8 @@ def debug_mimi_fused(kind, x_buf, M, *, xmap, ln_w, ln_b, w1, w2=None, eps=1e-5,
     a.out = ptr(out)
     name = C.create_string_buffer(512)
     a.launched, a.launched_cap = C.cast(name, C.c_char_p), 512
-    H = hooks()
-    H.ptts_debug_mimi_fused.argtypes = [C.POINTER(_MimiFusedArgs)]
-    _check(H.ptts_debug_mimi_fused(C.byref(a)))
-    launched = {k: int(v) for k, v in (item.split("=") for item in name.value.decode().split(";") if item)}
-    return {"out": out, "launched": launched}
+    _check(hooks().ptts_debug_mimi_fused(C.byref(a)))
+    return {"out": out, "launched": _census_dict(name)}
 
 
 def debug_mimi_pack(kind, w1, w2=None):
@@ -1743,16 +1729,8 @@ def debug_resblock(u, w1, w2, *, L=None, pad=2, slack=0, t0=0, t1=None, w_bf16=T
     bytes where nothing was stored), "plan": (waves per block, persistent, grid, tiles per utterance, new rows per tile)."""
     w1, w2 = _f32(w1), _f32(w2)
     h, c = w1.shape[0], w2.shape[0]
-    keep = []
-
-    def ptr(a):
-        if a is None:
-            return C.cast(None, _FP)
-        a = _f32(a)
-        keep.append(a)
-        return _fp(a)
-
-    a = _ResblockArgs()
+    a, keep = _ResblockArgs(), _Keep()
+    ptr = keep.f32
     fused = xin is not None
     if fused:
         xin = _f32(xin)
@@ -1772,17 +1750,13 @@ def debug_resblock(u, w1, w2, *, L=None, pad=2, slack=0, t0=0, t1=None, w_bf16=T
     a.uo, a.pcm = ptr(uo), ptr(pcm)
     ro = None
     if rows is not None:
-        rt = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(b, 2))
-        keep.append(rt)
-        a.rows = rt.ctypes.data_as(C.POINTER(C.c_int32))
+        a.rows = keep.i32(np.asarray(rows, np.int32).reshape(b, 2))
         a.row_bytes = ((4 * L + 8 * 4 + 15) // 16) * 16 if row_bytes is None else int(row_bytes)
         ro = np.empty((b, max(int(a.row_bytes), 0)), np.uint8)
         a.row_out = ro.ctypes.data_as(C.c_void_p)
     cnt = (C.c_int32 * 5)()
-    a.launched = C.cast(cnt, C.POINTER(C.c_int32))
-    H = hooks()
-    H.ptts_debug_resblock.argtypes = [C.POINTER(_ResblockArgs)]
-    _check(H.ptts_debug_resblock(C.byref(a)))
+    a.launched = C.cast(cnt, _I32P)
+    _check(hooks().ptts_debug_resblock(C.byref(a)))
     return {"uo": uo, "pcm": pcm, "rows": ro, "plan": tuple(int(v) for v in cnt)}
 
 
@@ -1848,7 +1822,7 @@ def launch_counts(on: bool) -> dict:
     """Kernel launches noted on this thread since the previous call ({kernel: count}); switches the census on / off."""
     buf = C.create_string_buffer(4096)
     hooks().ptts_debug_launch_counts(1 if on else 0, buf, 4096)
-    return {k: int(v) for k, v in (item.split("=") for item in buf.value.decode().split(";") if item)}
+    return _census_dict(buf)
 
 
 def op_conv1d_leftpad(x, w, bias=None) -> np.ndarray:

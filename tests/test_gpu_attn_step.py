@@ -41,6 +41,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round
 from _parity import record
 
 F32 = np.float32
@@ -74,12 +75,6 @@ def launch_rounds(keys_now, cap, fmt):
 
 
 # ------------------------------------------------------------------------------------------------ number formats
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
 def to_fmt(a, fmt):
     """f32 values in the cache format's precision."""
     return bf16_round(a) if fmt == "bf16" else np.ascontiguousarray(a, F32)

@@ -52,6 +52,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round, split
 from _parity import record
 
 F32 = np.float32
@@ -64,12 +65,6 @@ FORM_KERNEL = {1: "k_attn_window<false,false>", 2: "k_attn_window_lds<4>"}
 
 
 # ------------------------------------------------------------------------------------------------ number formats
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
 def to_bits(a, fmt):
     u = np.ascontiguousarray(a, F32).view(np.uint32)
     return (u >> 16).astype(np.uint16) if fmt == "bf16" else u.copy()
@@ -344,11 +339,6 @@ def test_flat_cases_feel_every_key():
 
 
 # ------------------------------------------------------------------------------------------------ the kernels' arithmetic in numpy f32 (no GPU)
-def split(x):
-    hi = bf16_round(x)
-    return hi, bf16_round(x - hi)
-
-
 # the key a score register holds: register r of half-wave g is key (r & 3) + 8 (r >> 2) + 4 g of the tile
 KEY_OF = np.array([[(r & 3) + 8 * (r >> 2) + 4 * g for r in range(16)] for g in range(2)])
 

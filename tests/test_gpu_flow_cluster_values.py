@@ -47,6 +47,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round, bits, split
 from _parity import record
 
 F32 = np.float32
@@ -56,12 +57,6 @@ KAPPA = 4.0
 CEIL = 1e-4
 TILE, TILES, MAX_ROWS = 12, 22, 264
 FILL = np.uint32(0xFFFFFFFF)
-
-
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
 
 
 # ------------------------------------------------------------------------------------------------ cases
@@ -161,11 +156,6 @@ def wave_sum(v):
     for _ in range(4):
         v = v[:, 0::2] + v[:, 1::2]
     return (v[:, 0] + v[:, 1]) + (v[:, 2] + v[:, 3])
-
-
-def split(a):
-    hi = bf16_round(a)
-    return hi, bf16_round(a - hi)
 
 
 def emulate_product(a, w):
@@ -330,10 +320,6 @@ def test_refusals_before_any_device(pkg):
 
 # ------------------------------------------------------------------------------------------------ GPU
 gpu = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 def first_difference(a, b):

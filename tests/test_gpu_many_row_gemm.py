@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round, check_bound, elu64, silu64, untouched
 from _parity import record
 
 TOL = 3e-5
@@ -41,12 +42,6 @@ CUS = 256            # compute units plan() assumes for the production rgl (MI35
 
 
 # ------------------------------------------------------------------------------------------------ number formats, functions
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
 try:
     from scipy.special import erf as erf64
 except ImportError:   # pragma: no cover
@@ -56,14 +51,6 @@ except ImportError:   # pragma: no cover
 
 def gelu64(v):
     return 0.5 * v * (1.0 + erf64(v / math.sqrt(2.0)))
-
-
-def silu64(v):
-    return v / (1.0 + np.exp(-v))
-
-
-def elu64(v):
-    return np.where(v > 0, v, np.expm1(np.minimum(v, 0.0)))
 
 
 def elu_fast32(v):
@@ -580,20 +567,8 @@ def test_planted_defects_exceed_the_bound(defect):
 
 # ------------------------------------------------------------------------------------------------ GPU
 gpu = pytest.mark.gpu
-FILL = np.uint32(0xFFFFFFFF)
-
-
-def untouched(a):
-    return bool((np.ascontiguousarray(a).view(np.uint32) == FILL).all())
-
-
 def check(name, got, want, bound):
-    got = np.asarray(got)
-    err = np.abs(got.astype(np.float64) - want)
-    worst = float((err / bound).max()) if err.size else 0.0
-    record(name, float(err.max()) if err.size else 0.0, worst, float(np.abs(want).max()) if err.size else 0.0, (TOL, 0))   # (max_rel slot: error / bound)
-    print(f"{name}: max abs {float(err.max()) if err.size else 0.0:.3e}, error / bound {worst:.3f}")
-    assert np.isfinite(got).all() and worst <= 1.0, (name, float(err.max()), worst)
+    check_bound(name, got, want, bound, TOL)
 
 
 def run(pkg, c, o, **over):

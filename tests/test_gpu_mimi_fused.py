@@ -37,6 +37,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_bits, bf16_round, bits, check_bound, split
 from _parity import record
 
 TOL = 3e-5
@@ -59,16 +60,6 @@ except ImportError:   # pragma: no cover
 
 
 # ------------------------------------------------------------------------------------------------ number formats, functions
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
-def bf16_bits(a):
-    return (bf16_round(a).view(np.uint32) >> 16).astype(np.uint16)
-
-
 def gelu64(v):
     return 0.5 * v * (1.0 + erf64(v / math.sqrt(2.0)))
 
@@ -329,11 +320,6 @@ def reference(c, o):
     return ref_ffn(o) if c["kind"] == FFN else ref_rowlin(c, o)
 
 
-def split(a):
-    hi = bf16_round(a)
-    return hi, bf16_round(a - hi)
-
-
 def product(ah, al, W, lo=True):
     """sum over the 32-deep steps: bf16 x bf16 products are exact, sums in f32, the hi product of a step and then its lo product."""
     acc = np.zeros((ah.shape[0], W.shape[0]), F32)
@@ -500,10 +486,6 @@ gpu = pytest.mark.gpu
 FILL = np.uint32(0xFFFFFFFF)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 def run(pkg, c, o, **over):
     """one launch of case c on operands o; asserts the census: exactly one launch, of the kernel the case names."""
     kw = dict(xmap=o["xmap"], ln_w=o["ln_w"], ln_b=o["ln_b"], w1=o["W1"], eps=EPS)
@@ -530,12 +512,7 @@ def rows_of(c, o, buf):
 
 
 def check(name, got, want, bound):
-    got = np.asarray(got)
-    err = np.abs(got.astype(np.float64) - want)
-    worst = float((err / bound).max())
-    record("mimi_fused " + name, float(err.max()), worst, float(np.abs(want).max()), (TOL, 0))   # (max_rel slot: error / bound)
-    print(f"{name}: max abs {float(err.max()):.3e}, error / bound {worst:.3f}")
-    assert np.isfinite(got).all() and worst <= 1.0, (name, float(err.max()), worst)
+    check_bound("mimi_fused " + name, got, want, bound, TOL)
 
 
 def check_case(pkg, c):

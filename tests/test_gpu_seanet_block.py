@@ -40,6 +40,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_bits, bf16_round, elu64, untouched
 from _parity import record
 
 TOL = 3e-5
@@ -113,20 +114,6 @@ def test_production_thresholds_are_the_stated_ones(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ number formats
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
-def bf16_bits(a):
-    return (bf16_round(a).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def elu64(v):
-    return np.where(v > 0, v, np.expm1(np.minimum(v, 0.0)))
-
-
 def elu32(v):
     """the kernels' form in f32: exp(v) - 1 on (-inf, 0]"""
     v = np.asarray(v, F32)
@@ -562,10 +549,6 @@ def test_loader_and_hook_pack_the_same_bytes(pkg):
 
 # ------------------------------------------------------------------------------------------------ GPU
 gpu = pytest.mark.gpu
-
-
-def untouched(a):
-    return bool((np.ascontiguousarray(a).view(np.uint8) == 0xFF).all())
 
 
 def check(name, got, want, bound):

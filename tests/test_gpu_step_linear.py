@@ -13,7 +13,6 @@ Tolerance: the kernel's arithmetic is exact up to the bf16 hi + lo split of the 
 Lipschitz bound (GELU 1.2, SiLU 1.1: max |silu'| = 1.0998; ELU 1; a per-column scale, gate or alpha multiplies the product's share) and, for a sum over split-K
 planes, times the number of planes.  test_emulation_stays_within_half_the_bound (no GPU) runs a numpy emulation of the kernel's arithmetic -- round-to-nearest-even
 hi / lo split, f32 products and sums per 32-deep matrix step and per K part in the kernel's order -- over every case of this file and holds it to HALF that bound."""
-import math
 import os
 import sys
 import zlib
@@ -22,6 +21,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round, check_bound, elu64, gelu64, silu64, untouched
 from _parity import record
 
 TOL = 3e-5
@@ -82,12 +82,6 @@ def test_pick_split_never_leaves_an_empty_slice():
 
 
 # ------------------------------------------------------------------------------------------------ number formats
-def bf16_round(a):
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F32)
-
-
 def quantize_rows(w):
     """model.cpp quantize_rows in f32: s = max|row| / 127 (1 for a zero row), q = rint(W / s) clamped to +-127, W^ = q s."""
     w = np.ascontiguousarray(w, F32)
@@ -95,22 +89,6 @@ def quantize_rows(w):
     s = np.where(mx > 0, mx / F32(127.0), F32(1.0)).astype(F32)
     q = np.clip(np.rint(w / s[:, None]), -127.0, 127.0).astype(F32)
     return q * s[:, None], q, s
-
-
-def erf64(v):
-    return np.vectorize(math.erf, otypes=[np.float64])(v)
-
-
-def gelu64(v):
-    return 0.5 * v * (1.0 + erf64(v / math.sqrt(2.0)))
-
-
-def silu64(v):
-    return v / (1.0 + np.exp(-v))
-
-
-def elu64(v):
-    return np.where(v > 0, v, np.expm1(np.minimum(v, 0.0)))
 
 
 # ------------------------------------------------------------------------------------------------ cases
@@ -381,20 +359,8 @@ def test_emulation_stays_within_half_the_bound(group):
 
 # ------------------------------------------------------------------------------------------------ GPU
 gpu = pytest.mark.gpu
-FILL = np.uint32(0xFFFFFFFF)
-
-
-def untouched(a):
-    return bool((np.ascontiguousarray(a).view(np.uint32) == FILL).all())
-
-
 def check(name, got, want, bound):
-    got = np.asarray(got)
-    err = np.abs(got.astype(np.float64) - want)
-    worst = float((err / bound).max()) if err.size else 0.0
-    record(name, float(err.max()) if err.size else 0.0, worst, float(np.abs(want).max()) if err.size else 0.0, (TOL, 0))   # (max_rel slot: error / bound)
-    print(f"{name}: max abs {float(err.max()) if err.size else 0.0:.3e}, error / bound {worst:.3f}")
-    assert np.isfinite(got).all() and worst <= 1.0, (name, float(err.max()), worst)
+    check_bound(name, got, want, bound, TOL)
 
 
 def run(pkg, c, o, **over):

@@ -15,16 +15,11 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _kernel_ref import bf16_round
 from _parity import record
 
 pytestmark = pytest.mark.gpu
 TOL = 3e-5
-
-
-def bf16_round(a):
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(np.float32)
 
 
 def layernorm64(x, w, b, eps):
