@@ -1256,7 +1256,27 @@ int ptts_generate_joined(ptts_model* h, const ptts_request* reqs, int32_t n, con
         if (!reqs || !out || n <= 0) throw Error(PTTS_EINVAL, "ptts-hip: no requests");
         if (!o) throw Error(PTTS_EINVAL, "ptts-hip: join: null options");
         set_last_error("");
-        generate_joined(*h->m, reqs, n, *o, out, parts);
+        generate_joined(*h->m, reqs, n, *o, nullptr, out, parts);
+    });
+}
+
+// ... handed over group by group (runtime.cpp JoinStream).  The stream options are checked first: their refusals need no model
+int ptts_generate_joined_streamed(ptts_model* h, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, const ptts_join_stream_opts* so, ptts_result* out,
+                                  ptts_join_part* parts) {
+    return guard([&] {
+        const std::string e = join_stream_opts_error(so);
+        if (!e.empty()) {   // *out and parts as generate_joined leaves them on a refusal
+            if (out) { std::memset(out, 0, sizeof *out); out->eos_step = -1; out->status = PTTS_EINVAL; }
+            for (int i = 0; parts && i < n && n <= kJoinMaxRows; i++) { std::memset(&parts[i], 0, sizeof parts[i]); parts[i].eos_step = -1; }
+            throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        }
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        if (!reqs || !out || n <= 0) throw Error(PTTS_EINVAL, "ptts-hip: no requests");
+        if (!o) throw Error(PTTS_EINVAL, "ptts-hip: join: null options");
+        set_last_error("");
+        ptts_join_stream_opts known{};   // (a newer caller's struct: the bytes this library knows)
+        std::memcpy(&known, so, std::min<size_t>(so->size, sizeof known));
+        generate_joined(*h->m, reqs, n, *o, &known, out, parts);
     });
 }
 

@@ -264,6 +264,36 @@ int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out) {
     });
 }
 
+int ptts_debug_dsp_windows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts, const int64_t* cuts, int32_t n_cuts,
+                           float* const* out) {
+    return guard([&] {
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native: model is not fully initialized");
+        if (rows < 0 || n_cuts < 0 || (rows > 0 && (!in || !n || !out)) || (n_cuts > 0 && !cuts)) throw Error(PTTS_EINVAL, "ptts-hip: dsp: windows: null argument");
+        DspSpec spec;
+        std::string e = dsp_resolve(opts, &spec);
+        if (e.empty()) e = dsp_trim_refusal(spec);
+        if (e.empty()) e = dsp_tempo_refusal(spec);
+        if (e.empty()) e = dsp_window_refusal(spec);   // only the causal stages, as the streamed joined call words it
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        for (int i = 0; i < rows; i++)
+            if (n[i] < 0 || (n[i] > 0 && (!in[i] || !out[i]))) throw Error(PTTS_EINVAL, strfmt("ptts-hip: dsp: windows: row %d is negative or null", i));
+        const int64_t fo = spec.fade_out_ms > 0 ? (int64_t)(spec.fade_out_ms / 1000.0 * (double)kNativeRate) : 0;
+        for (int w = 0; w < n_cuts; w++) {
+            if (cuts[w] <= (w ? cuts[w - 1] : 0) || cuts[w] % kDspTile != 0)
+                throw Error(PTTS_EINVAL, strfmt("ptts-hip: dsp: windows: cut %d (%lld) is not an ascending multiple of %d above 0", w, (long long)cuts[w], kDspTile));
+            for (int i = 0; i < rows; i++)
+                if (cuts[w] < n[i] && cuts[w] > n[i] - fo)
+                    throw Error(PTTS_EINVAL, strfmt("ptts-hip: dsp: windows: cut %d (%lld) lies in the fade out of row %d (%lld samples, the last %lld fade out)", w,
+                                                    (long long)cuts[w], i, (long long)n[i], (long long)fo));
+        }
+        if (!spec.any()) {   // nothing switched on: a copy, no launch
+            for (int i = 0; i < rows; i++) if (n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            return;
+        }
+        dsp_windows_device(*h->m, in, n, rows, spec, cuts, n_cuts, out);
+    });
+}
+
 int ptts_debug_loudness_energies(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, double* const* out) {
     return guard([&] {
         if (rows < 0 || (rows > 0 && (!in || !n || !out))) throw Error(PTTS_EINVAL, "ptts-hip: loudness: null argument");

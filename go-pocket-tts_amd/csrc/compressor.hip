@@ -14,6 +14,8 @@
 // it meets at step l: the order is the host's (compressor.cpp cmp_apply_blocked), and so are the bits.  The stride-30 run access is the 2-way
 // bank pattern k_eq_apply lives with.  Stream order has each launch complete before the next reads what it wrote; the summaries and k_cmp_apply
 // read the raw samples, only k_cmp_apply writes them, every workgroup its own tile.  Nothing at or beyond n is read or written.
+// A launch may cover a window of a row (kernels.h CmpRow::t0, ::open, ::carry; dsp_tile.h): both carries start from the states the window in front
+// left and leave theirs behind an open window's last tile, which the summaries then cover; nothing in front of the window is written.
 #include "device_util.h"
 #include "dsp_tile.h"
 
@@ -37,9 +39,9 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_p(const CmpRow* __res
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
     const CmpRow& r = rows[blockIdx.y];
-    if (!tile_hands_on(r.n)) return;
+    if (!tile_hands_on(r.t0, r.n, r.open)) return;
     float* tile = reinterpret_cast<float*>(tile4);
-    tile_load(r.x + (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
+    tile_load(r.x + (r.t0 + blockIdx.x) * kDspTile, kDspTile, tile);
     __syncthreads();
     const CmpScan d = designs[r.design];
     const int l = threadIdx.x;
@@ -53,17 +55,17 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_p(const CmpRow* __res
 __global__ __launch_bounds__(kDspLanes) void k_cmp_carry_p(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ double ein[kDspLanes];
     const CmpRow& r = rows[blockIdx.x];
-    if (r.n <= 0) return;
-    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein);
+    if (win_tiles(r.t0, r.n) <= 0) return;
+    carry_one<true>(designs[r.design].rho_tile, win_tiles(r.t0, r.n), r.p_tiles, ein, r.carry ? r.carry + kCarryCmpP : nullptr, r.open);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_s(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
     const CmpRow& r = rows[blockIdx.y];
-    if (!tile_hands_on(r.n)) return;
+    if (!tile_hands_on(r.t0, r.n, r.open)) return;
     float* tile = reinterpret_cast<float*>(tile4);
-    tile_load(r.x + (int64_t)blockIdx.x * kDspTile, kDspTile, tile);
+    tile_load(r.x + (r.t0 + blockIdx.x) * kDspTile, kDspTile, tile);
     __syncthreads();
     const CmpScan d = designs[r.design];
     const int l = threadIdx.x;
@@ -83,15 +85,15 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_s(const CmpRow* __res
 __global__ __launch_bounds__(kDspLanes) void k_cmp_carry_s(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ double ein[kDspLanes];
     const CmpRow& r = rows[blockIdx.x];
-    if (r.n <= 0) return;
-    carry_one<false>(designs[r.design].alpha_tile, scan_tiles(r.n), r.s_tiles, ein);
+    if (win_tiles(r.t0, r.n) <= 0) return;
+    carry_one<false>(designs[r.design].alpha_tile, win_tiles(r.t0, r.n), r.s_tiles, ein, r.carry ? r.carry + kCarryCmpS : nullptr, r.open);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_cmp_apply(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
     const CmpRow& r = rows[blockIdx.y];
-    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    const int64_t n = r.n, base = (r.t0 + blockIdx.x) * kDspTile;
     if (base >= n) return;
     float* tile = reinterpret_cast<float*>(tile4);
     const int cnt = (int)min((int64_t)kDspTile, n - base);
@@ -115,16 +117,17 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_apply(const CmpRow* __restric
 
 }  // namespace
 
-void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream) {
+void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream, bool any_open) {
     if (n <= 0 || max_tiles <= 0) return;
-    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)(max_tiles - 1), (unsigned)n), lanes(kDspLanes);
-    if (max_tiles > 1) {
+    const int hands = any_open ? max_tiles : max_tiles - 1;   // (an open window's last tile hands on as well)
+    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)hands, (unsigned)n), lanes(kDspLanes);
+    if (hands > 0) {
         note_launch("k_cmp_summary_p");
         hipLaunchKernelGGL(k_cmp_summary_p, handing, lanes, 0, stream, rows_dev, designs_dev);
     }
     note_launch("k_cmp_carry_p");
     hipLaunchKernelGGL(k_cmp_carry_p, dim3((unsigned)n), lanes, 0, stream, rows_dev, designs_dev);
-    if (max_tiles > 1) {
+    if (hands > 0) {
         note_launch("k_cmp_summary_s");
         hipLaunchKernelGGL(k_cmp_summary_s, handing, lanes, 0, stream, rows_dev, designs_dev);
     }

@@ -26,6 +26,11 @@
 // holds a dozen workgroups, the passes are reads of the rows at HBM rate.  Tiles lie on the row's own grid and every sum has one order: a
 // row's bits are a function of the row alone, and they are the bits of the host instantiations (dsp.cpp, loudness.cpp).  Nothing at or beyond
 // n is read or written.
+// Windows (kernels.h DSP_OPEN, DspRow::t0, ::carry; dsp_tile.h): k_dsp_summary / _carry / _apply and k_eq_summary / _carry / _apply may cover tiles
+// [t0, ceil(n / 1920)) of a row only, with the window's own per-tile states; the carries start from the state the window in front left and an open
+// window leaves the state behind its last tile, whose E_f the summaries then make as well; the fade in counts in the whole row, the fade out is the
+// closing window's.  The fold is lane 0's (the lanes' for the equaliser) in tile order from whatever state it starts with, so the windows of a row
+// give the one-shot bits, and the one-shot chain is the window t0 = 0, carry null, of a closed row: the same code, launches and LDS.
 // k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row (k_dsp_apply: and an equaliser row), so a table without
 // one launches the instantiation that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
@@ -94,14 +99,14 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
     }
 }
 
-// tile blockIdx.x of the row, which hands a state on: E_f into the row's per-tile states
+// tile blockIdx.x of the row's window, which hands a state on: E_f into the window's per-tile states
 template <class Sys>
 __device__ __forceinline__ void scan_summary(const Sys& sc, const DspRow& r, double* states, const Gain g) {
     constexpr int N = Sys::N;
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes][N];
     float* tile = reinterpret_cast<float*>(tile4);
-    load_tile(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile, g);
+    load_tile(r, (r.t0 + blockIdx.x) * kDspTile, kDspTile, tile, g);
     __syncthreads();
     const int l = threadIdx.x;
     double z[N] = {};
@@ -116,28 +121,32 @@ __device__ __forceinline__ void scan_summary(const Sys& sc, const DspRow& r, dou
     }
 }
 
-// a row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time
+// a window of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time.  carry (null: the row starts here, from zero state, and ends
+// here): the state the window in front left, and, behind an open window's last tile, the state it leaves (win_hands: the tiles that hand on)
 template <class Sys>
-__device__ __forceinline__ void scan_carry(const Sys& sc, int64_t F, double* states) {
+__device__ __forceinline__ void scan_carry(const Sys& sc, int64_t F, double* states, double* carry, bool open) {
     constexpr int N = Sys::N;
     __shared__ double ein[kDspLanes][N], sout[kDspLanes][N];
     const int l = threadIdx.x;
+    const int64_t hands = win_hands(F, open);
     double s[N] = {};   // lane 0's: the state entering tile c0 + j
+    if (carry) for (int i = 0; i < N; i++) s[i] = carry[i];
     for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
         const int64_t f = c0 + l;
-        if (f < F - 1) for (int i = 0; i < N; i++) ein[l][i] = scan_E<N>(states, f)[i];
+        if (f < hands) for (int i = 0; i < N; i++) ein[l][i] = scan_E<N>(states, f)[i];
         __syncthreads();
         if (l == 0) {
             const int m = (int)min((int64_t)kDspLanes, F - c0);
             for (int j = 0; j < m; j++) {
                 for (int i = 0; i < N; i++) sout[j][i] = s[i];
-                if (c0 + j < F - 1) scan_advance<N>(sc.a_tile, s, ein[j]);
+                if (c0 + j < hands) scan_advance<N>(sc.a_tile, s, ein[j]);
             }
         }
         __syncthreads();
         if (f < F) for (int i = 0; i < N; i++) scan_S<N>(states, f)[i] = sout[l][i];
         __syncthreads();
     }
+    if (open && l == 0) for (int i = 0; i < N; i++) carry[i] = s[i];
 }
 
 // z <- the state entering the lane's run (c samples at `run`, in LDS) of tile blockIdx.x: every run from zero state, then lane 0's fold in run
@@ -167,25 +176,26 @@ __device__ __forceinline__ void scan_enter(const Sys& sc, const float* run, int 
 template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_DC) && tile_hands_on(r.n)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
+    if ((r.flags & DSP_DC) && tile_hands_on(r.t0, r.n, r.flags & DSP_OPEN)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_summary(const DspRow* __restrict__ rows, const LoudScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_LOUD) && tile_hands_on(r.n)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
+    if ((r.flags & DSP_LOUD) && tile_hands_on(0, r.n, false)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restrict__ rows, const DspScan sc) {
     const DspRow& r = rows[blockIdx.x];
-    if ((r.flags & DSP_DC) && r.n > 0) scan_carry(sc, scan_tiles(r.n), r.tiles);
+    if ((r.flags & DSP_DC) && win_tiles(r.t0, r.n) > 0) scan_carry(sc, win_tiles(r.t0, r.n), r.tiles, r.carry ? r.carry + kCarryDc : nullptr, r.flags & DSP_OPEN);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_carry(const DspRow* __restrict__ rows, const LoudScan sc) {
     const DspRow& r = rows[blockIdx.x];
-    if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud));
+    if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud), nullptr, false);
 }
 
-// tile[0, cnt) -- samples [base, base + cnt) of the row -- times the two fade gains, into the row
+// tile[0, cnt) -- samples [base, base + cnt) of the row -- times the two fade gains, into the row.  base counts in the whole row, and so do the
+// fades: an open window's row has no fade out yet (fade_out 0), the window that closes the row applies it with the row's final n
 __device__ __forceinline__ void store_tile(const DspRow& r, int64_t base, int cnt, const float* tile, int64_t fin, int64_t fade_out) {
     const int64_t n = r.n, fout0 = n - fade_out;
     float* dst = r.x + base;
@@ -212,7 +222,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
     __shared__ float4 tile4[kDspTile / 4];
     float* tile = reinterpret_cast<float*>(tile4);
     const DspRow& r = rows[blockIdx.y];
-    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    const int64_t n = r.n, base = (r.t0 + blockIdx.x) * kDspTile;
     if (base >= n) return;
     const int cnt = (int)min((int64_t)kDspTile, n - base);
     const Gain g = row_gain<LOUD>(r);
@@ -268,18 +278,20 @@ __device__ __forceinline__ void eq_summary(const Sys sc, const DspRow& r, const 
     if (l < N) scan_E<N>(r.eq_tiles, blockIdx.x)[l] = s;
 }
 
-// an equaliser row of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time.  ein: [kDspLanes][N]
+// a window of F >= 1 tiles of an equaliser row: S_f of every tile from the E_f, 64 tiles at a time.  ein: [kDspLanes][N]; carry, open: as
+// scan_carry's
 template <class Sys>
-__device__ __forceinline__ void eq_carry(const Sys sc, int64_t F, double* states, double* ein) {
+__device__ __forceinline__ void eq_carry(const Sys sc, int64_t F, double* states, double* ein, double* carry, bool open) {
     constexpr int N = Sys::N;
     const int l = threadIdx.x, i = min(l, N - 1);
+    const int64_t hands = win_hands(F, open);
     double prow[N];
 #pragma unroll
     for (int m = 0; m < N; m++) prow[m] = sc.a_tile[N * i + m];
-    double s = 0.0;   // component i of the state entering tile c0 + j
+    double s = carry ? carry[i] : 0.0;   // component i of the state entering tile c0 + j
     for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
         const int64_t f = c0 + l;
-        if (f < F - 1) {
+        if (f < hands) {
 #pragma unroll
             for (int k = 0; k < N; k++) ein[l * N + k] = scan_E<N>(states, f)[k];
         }
@@ -287,10 +299,11 @@ __device__ __forceinline__ void eq_carry(const Sys sc, int64_t F, double* states
         const int m = (int)min((int64_t)kDspLanes, F - c0);
         for (int j = 0; j < m; j++) {
             if (l < N) scan_S<N>(states, c0 + j)[l] = s;
-            if (c0 + j < F - 1) s = lanes_advance<N>(prow, s, ein[j * N + i]);
+            if (c0 + j < hands) s = lanes_advance<N>(prow, s, ein[j * N + i]);
         }
         __syncthreads();
     }
+    if (open && l < N) carry[l] = s;
 }
 
 // the lane's run (c samples at `run`, in LDS) of tile blockIdx.x of an equaliser row, filtered in place from its entering state: every run from
@@ -326,9 +339,9 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restri
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes * kEqStates];
     const DspRow& r = rows[blockIdx.y];
-    if (!(r.flags & DSP_EQ) || !tile_hands_on(r.n)) return;
+    if (!(r.flags & DSP_EQ) || !tile_hands_on(r.t0, r.n, r.flags & DSP_OPEN)) return;
     float* tile = reinterpret_cast<float*>(tile4);
-    load_tile(r, (int64_t)blockIdx.x * kDspTile, kDspTile, tile, kNoGain);
+    load_tile(r, (r.t0 + blockIdx.x) * kDspTile, kDspTile, tile, kNoGain);
     __syncthreads();
     const EqScan& q = eqs[r.eq];
     switch (q.S) {
@@ -343,14 +356,16 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restri
 __global__ __launch_bounds__(kDspLanes) void k_eq_carry(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
     __shared__ double ein[kDspLanes * kEqStates];
     const DspRow& r = rows[blockIdx.x];
-    if (!(r.flags & DSP_EQ) || r.n <= 0) return;
+    const int64_t F = win_tiles(r.t0, r.n);
+    if (!(r.flags & DSP_EQ) || F <= 0) return;
     const EqScan& q = eqs[r.eq];
-    const int64_t F = scan_tiles(r.n);
+    double* const carry = r.carry ? r.carry + kCarryEq : nullptr;
+    const bool open = (r.flags & DSP_OPEN) != 0;
     switch (q.S) {
-        case 1: eq_carry(EqSys<1>(q), F, r.eq_tiles, ein); break;
-        case 2: eq_carry(EqSys<2>(q), F, r.eq_tiles, ein); break;
-        case 3: eq_carry(EqSys<3>(q), F, r.eq_tiles, ein); break;
-        case 4: eq_carry(EqSys<4>(q), F, r.eq_tiles, ein); break;
+        case 1: eq_carry(EqSys<1>(q), F, r.eq_tiles, ein, carry, open); break;
+        case 2: eq_carry(EqSys<2>(q), F, r.eq_tiles, ein, carry, open); break;
+        case 3: eq_carry(EqSys<3>(q), F, r.eq_tiles, ein, carry, open); break;
+        case 4: eq_carry(EqSys<4>(q), F, r.eq_tiles, ein, carry, open); break;
         default: break;
     }
 }
@@ -359,7 +374,7 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_apply(const DspRow* __restrict
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double et[kDspLanes * kEqStates];
     const DspRow& r = rows[blockIdx.y];
-    const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
+    const int64_t n = r.n, base = (r.t0 + blockIdx.x) * kDspTile;
     if (!(r.flags & DSP_EQ) || base >= n) return;
     float* tile = reinterpret_cast<float*>(tile4);
     const int cnt = (int)min((int64_t)kDspTile, n - base);
@@ -433,7 +448,8 @@ __global__ __launch_bounds__(kDspLanes) void k_loud_gate(const DspRow* __restric
 
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream) {
     if (n <= 0 || max_tiles <= 0) return;
-    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)(max_tiles - 1), (unsigned)n), lanes(kDspLanes);
+    const int hands = p.any_open ? max_tiles : max_tiles - 1;   // (an open window's last tile hands on as well)
+    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)hands, (unsigned)n), lanes(kDspLanes);
     if (p.any_norm || (p.any_loud && p.apply)) {   // (a measurement alone has no ceiling to keep)
         note_launch("k_dsp_peak");
         hipLaunchKernelGGL(k_dsp_peak, dim3((unsigned)((max_tiles + 3) / 4), (unsigned)n), dim3(kPeakThreads), 0, stream, rows_dev);
@@ -452,7 +468,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
     }
     if (!p.apply) return;   // a measurement alone
     if (p.any_dc) {
-        if (max_tiles > 1) {
+        if (hands > 0) {
             note_launch("k_dsp_summary");
             hipLaunchKernelGGL(p.any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, handing, lanes, 0, stream, rows_dev, *p.scan);
         }
@@ -464,7 +480,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, false> : k_dsp_apply<false, false>), tiles, lanes, 0, stream, rows_dev, *p.scan);
     } else {
         hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, true> : k_dsp_apply<false, true>), tiles, lanes, 0, stream, rows_dev, *p.scan);
-        if (max_tiles > 1) {   // behind k_dsp_apply: the equaliser reads what it stored
+        if (hands > 0) {   // behind k_dsp_apply: the equaliser reads what it stored
             note_launch("k_eq_summary");
             hipLaunchKernelGGL(k_eq_summary, handing, lanes, 0, stream, rows_dev, p.eqs);
         }

@@ -18,6 +18,11 @@ int64_t fade_samples(double ms, int64_t n) {   // dsp_fade_in / dsp_fade_out: mi
     return f >= (double)n ? n : (int64_t)f;
 }
 
+// the tiles a row's launch covers: its window's where the record has one (kernels.h), else the row's
+template <class Row> int64_t row_tiles(const Row& r) { return scan_tiles(r.n); }
+int64_t row_tiles(const DspRow& r) { return win_tiles(r.t0, r.n); }
+int64_t row_tiles(const CmpRow& r) { return win_tiles(r.t0, r.n); }
+
 // The tables of one stage (row_tables.h has the rule): rows, in order, into up to kRows rows with up to max_designs distinct designs a table,
 // which travel behind the rows in the same turn of the ring.  key[i]: row i's design (null: none); index: where a row names its own among its
 // table's.  launch(first, count, rows_dev, max_tiles, designs_dev) runs between the turn's stage() and done().  stage: the name in the refusal
@@ -29,7 +34,7 @@ void launch_tables(RowRing<Row, kTail>& ring, std::vector<Row>& rows, const std:
         int64_t max_tiles = 0;
         for (int k = 0; k < n; k++) {
             rows[first + (size_t)k].*index = at[k];
-            max_tiles = std::max(max_tiles, scan_tiles(rows[first + (size_t)k].n));
+            max_tiles = std::max(max_tiles, row_tiles(rows[first + (size_t)k]));
         }
         if (max_tiles > INT32_MAX) throw Error(PTTS_EINVAL, strfmt("ptts-hip: %s: too many samples for one launch", stage));
         designs.clear();
@@ -48,12 +53,14 @@ bool same_bytes(const Design& a, const Design& b) { return std::memcmp(&a, &b, s
 // The chain's order, all of it: the compressor's tables in front of everything that measures or rewrites a row; then, DSP table by DSP table,
 // launch_dsp's kernels, the limiter's tables for that table's limiter rows (behind the fades, in front of the ceiling) and the true-peak pair
 // on what all of them stored.  A measurement alone (apply false) rewrites nothing: no compressor, no equaliser, no limiter, k_tp_peak alone.
+// A job with a window (DspJob::t0, open, carry; kernels.h has what a window is) takes the same way: its scratch is planned for the window's
+// samples, its fade in counts in the whole row and its fade out waits for the window that closes the row.
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
     static const DspScan scan = dsp_scan_coeffs(kNativeRate);
     if (jobs.empty()) return;
     // scratch: a peak word and a true-peak word per row, then what dsp_scratch (dsp_spec.h) gives each row's stages
     size_t tile_doubles = 0;
-    for (const DspJob& j : jobs) tile_doubles += dsp_scratch(j.spec, j.n, apply).total();
+    for (const DspJob& j : jobs) tile_doubles += dsp_scratch(j.spec, j.n - j.t0 * kDspTile, apply).total();
     const size_t peak_bytes = (2 * jobs.size() * sizeof(uint32_t) + 255) & ~(size_t)255;   // [jobs] sample peaks, then [jobs] true peaks
     char* scratch = m.work(WORK_DSP_SCRATCH, peak_bytes + std::max<size_t>(tile_doubles, 1) * sizeof(double)).as<char>();
     uint32_t* peaks = reinterpret_cast<uint32_t*>(scratch);
@@ -71,25 +78,28 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         const DspSpec& sp = j.spec;
         j.loud_out = nullptr;
         j.tp_out = nullptr;
-        if (j.n <= 0) continue;
-        const DspScratch q = dsp_scratch(sp, j.n, apply);
+        const int64_t wn = j.n - j.t0 * kDspTile;   // the window's samples (a one-shot job: the row's)
+        if (wn <= 0) continue;
+        const DspScratch q = dsp_scratch(sp, wn, apply);
         double* const mine = tiles;   // the row's regions: mine + q.<stage>_at()
         tiles += q.total();
         if (q.cmp) {
             CmpRow r{};
             r.x = j.x; r.n = j.n;
             r.p_tiles = mine + q.cmp_at();
-            r.s_tiles = r.p_tiles + scan_state_doubles<1>(scan_tiles(j.n));
+            r.s_tiles = r.p_tiles + scan_state_doubles<1>(scan_tiles(wn));
+            r.open = j.open ? 1 : 0; r.t0 = j.t0; r.carry = j.carry;
             cmp_rows.push_back(r);
             cmp_key.push_back(&sp.cmp);
         }
         if (!sp.rest()) continue;   // (a compressor alone: no row of the DSP table)
         DspRow r{};
         r.x = j.x; r.n = j.n;
-        r.fade_in = fade_samples(sp.fade_in_ms, j.n);
-        r.fade_out = fade_samples(sp.fade_out_ms, j.n);
+        r.fade_in = fade_samples(sp.fade_in_ms, j.open ? j.n_row : j.n);   // (an open row: the length it will have, or one beyond every fade)
+        r.fade_out = j.open ? 0 : fade_samples(sp.fade_out_ms, j.n);
         r.peak = peaks + k;
-        r.flags = (sp.normalize ? DSP_NORMALIZE : 0) | (sp.dc_block ? DSP_DC : 0) | (sp.loud ? DSP_LOUD : 0);
+        r.flags = (sp.normalize ? DSP_NORMALIZE : 0) | (sp.dc_block ? DSP_DC : 0) | (sp.loud ? DSP_LOUD : 0) | (j.open ? DSP_OPEN : 0);
+        r.t0 = j.t0; r.carry = j.carry;
         if (q.dc) r.tiles = mine + q.dc_at();
         if (q.loud) {
             r.loud = j.loud_out = mine + q.loud_at();
@@ -110,7 +120,11 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         lim_scratch.push_back(mine + q.lim_at());
     }
     launch_tables(m.cmp_ring, cmp_rows, cmp_key, kCmpMaxDesigns, same_bytes<CmpScan>, &CmpRow::design, "compressor", s,
-                  [&](size_t, int n, const CmpRow* rows_dev, int max_tiles, const CmpScan* designs_dev) { launch_compressor(rows_dev, n, max_tiles, designs_dev, s); });
+                  [&](size_t first, int n, const CmpRow* rows_dev, int max_tiles, const CmpScan* designs_dev) {
+        bool any_open = false;
+        for (size_t i = first; i < first + (size_t)n; i++) any_open = any_open || cmp_rows[i].open;
+        launch_compressor(rows_dev, n, max_tiles, designs_dev, s, any_open);
+    });
     std::vector<LimRow> lim_rows;
     std::vector<const LimScan*> lim_rows_key;
     launch_tables(m.dsp_ring, rows, eq_key, kDspMaxEq, [](const EqScan& a, const EqScan& b) { return &a == &b; } /* a handle's identity */, &DspRow::eq, "dsp", s,
@@ -126,6 +140,7 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             p.any_dc = p.any_dc || (r.flags & DSP_DC);
             p.any_loud = p.any_loud || (r.flags & DSP_LOUD);
             p.any_eq = p.any_eq || (r.flags & DSP_EQ);
+            p.any_open = p.any_open || (r.flags & DSP_OPEN);
             any_tp = any_tp || (r.flags & DSP_TP);
             if (!lim_key[i]) continue;
             LimRow q{};
@@ -183,6 +198,41 @@ void dsp_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t
         if (o.true_peaks && j.tp_out) PTTS_HIP(hipMemcpyAsync(o.true_peaks + i, j.tp_out, sizeof(float), hipMemcpyDeviceToHost, s));
         if (o.out) buf.download(i, o.out[i], s);
     }
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
+// ptts_debug_dsp_windows: the rows uploaded whole, then one dsp_launch per window -- [prev, cut) of every row that has samples there, the row
+// open where it goes on behind the cut -- and a last one to every row's end; the rows' carried states lie behind the rows, zeroed once
+void dsp_windows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const DspSpec& spec, const int64_t* cuts, int32_t n_cuts, float* const* out) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> bytes((size_t)rows + 1);
+    std::unique_ptr<bool[]> skip(new bool[(size_t)rows + 2]);
+    for (int i = 0; i < rows; i++) {
+        skip[(size_t)i] = n[i] <= 0;
+        bytes[(size_t)i] = skip[(size_t)i] ? 0 : (size_t)n[i] * sizeof(float);
+    }
+    skip[(size_t)rows] = false;
+    bytes[(size_t)rows] = (size_t)std::max(rows, 1) * kCarryDoubles * sizeof(double);
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
+    double* const carry = reinterpret_cast<double*>(buf.row(rows));
+    PTTS_HIP(hipMemsetAsync(carry, 0, (size_t)std::max(rows, 1) * kCarryDoubles * sizeof(double), s));
+    for (int i = 0; i < rows; i++) if (n[i] > 0) buf.upload(i, in[i], s);
+    int64_t prev = 0;
+    for (int w = 0; w <= n_cuts; w++) {
+        const int64_t cut = w < n_cuts ? cuts[w] : INT64_MAX;
+        std::vector<DspJob> jobs;
+        for (int i = 0; i < rows; i++) {
+            if (n[i] <= prev) continue;   // the row ended in an earlier window, which closed it
+            DspJob j{(float*)buf.row(i), std::min(n[i], cut), spec};
+            j.t0 = prev / kDspTile; j.open = n[i] > cut; j.n_row = n[i]; j.carry = carry + (size_t)i * kCarryDoubles;
+            jobs.push_back(j);
+        }
+        dsp_launch(m, jobs, s);
+        prev = cut;
+    }
+    for (int i = 0; i < rows; i++) if (n[i] > 0) buf.download(i, out[i], s);
     PTTS_HIP(hipStreamSynchronize(s));
 }
 

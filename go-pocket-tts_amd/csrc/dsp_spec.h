@@ -60,6 +60,13 @@ inline std::string dsp_trim_refusal(const DspSpec& s) {
 inline std::string dsp_tempo_refusal(const DspSpec& s) {
     return s.tempo ? std::string("dsp: ext: tempo changes a row's length; it is served by ptts_generate_joined and ptts_tempo_rows") : std::string();
 }
+// Where a row is handed over window after window (a joined call with a pcm_callback, ptts_debug_dsp_windows) only the causal stages run: the
+// compressor, the DC block, the equaliser and the fades.  The message naming the first stage of s that is none, or empty
+inline std::string dsp_window_refusal(const DspSpec& s) {
+    const char* f = s.normalize ? "normalize" : s.loud ? "loudness" : s.true_peak ? "ext: true_peak" : nullptr;
+    if (f) return strfmt("stream: %s needs the whole text; it cannot be combined with pcm_callback", f);
+    return s.limit ? std::string("stream: ext: limiter looks ahead of the samples it hands over; it cannot be combined with pcm_callback yet") : std::string();
+}
 // whether o switches anything on, without an error: what dsp_resolve's spec says with any(), except that an eq counts unseen (so a dead one is
 // active, and refused where the row is resolved) and an ext that is not live counts for nothing.  One registry look-up at the most: it is
 // asked per request before the decode and per streamed hand-over

@@ -7,8 +7,13 @@
 
 namespace ptts {
 
-// only a full tile that another one follows hands a state on (n: the row's samples)
-__device__ __forceinline__ bool tile_hands_on(int64_t n) { return (int64_t)(blockIdx.x + 1) * kDspTile < n; }
+// A launch covers a window of a row: tiles [t0, ceil(n / kDspTile)) of the row's own grid, n the samples up to the window's end; workgroup
+// blockIdx.x is on tile t0 + blockIdx.x and on entry blockIdx.x of the window's per-tile states.  The row is open when more samples will follow
+// behind n (n is then a multiple of kDspTile).  The one-shot chain is the window t0 = 0 of a closed row.
+// only a full tile that another one follows hands a state on: in a closed row every tile but the last, in an open one the last as well
+__device__ __forceinline__ bool tile_hands_on(int64_t t0, int64_t n, bool open) { return (t0 + blockIdx.x + 1) * kDspTile < n + (open ? 1 : 0); }
+// of a window's F tiles, those that hand a state on (the first ones)
+__device__ __forceinline__ int64_t win_hands(int64_t F, bool open) { return open ? F : F - 1; }
 // samples of the lane's run in a tile of cnt
 __device__ __forceinline__ int run_count(int cnt) { return max(0, min(kDspRun, cnt - (int)threadIdx.x * kDspRun)); }
 
@@ -42,27 +47,30 @@ __device__ __forceinline__ double fold_enter_max(double rho_run, const double* e
     return mine;
 }
 
-// A row of F >= 1 tiles with one state: S_f of every tile from the E_f (scan_E<1>, scan_S<1>), 64 tiles at a time, by every lane alike (lane 0
+// A window of F >= 1 tiles with one state: S_f of every tile from the E_f (scan_E<1>, scan_S<1>), 64 tiles at a time, by every lane alike (lane 0
 // stores); the state is carried from one group of 64 to the next.  Max: S_(f+1) = max(a_tile S_f, E_f), else a_tile S_f + E_f
-// (scan_advance<1>).  ein: LDS, [kDspLanes]
+// (scan_advance<1>).  ein: LDS, [kDspLanes].  carry (null: the row starts here from state 0 and ends here): the state the window in front left;
+// an open window leaves the state behind its last tile there
 template <bool Max>
-__device__ __forceinline__ void carry_one(double a_tile, int64_t F, double* states, double* ein) {
+__device__ __forceinline__ void carry_one(double a_tile, int64_t F, double* states, double* ein, double* carry, bool open) {
     const int l = threadIdx.x;
-    double s[1] = {0.0};   // the state entering tile c0 + j
+    const int64_t hands = win_hands(F, open);
+    double s[1] = {carry ? *carry : 0.0};   // the state entering tile c0 + j
     for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
         const int64_t f = c0 + l;
-        if (f < F - 1) ein[l] = scan_E<1>(states, f)[0];
+        if (f < hands) ein[l] = scan_E<1>(states, f)[0];
         __syncthreads();
         const int m = (int)min((int64_t)kDspLanes, F - c0);
         for (int j = 0; j < m; j++) {
             if (l == 0) scan_S<1>(states, c0 + j)[0] = s[0];
-            if (c0 + j < F - 1) {
+            if (c0 + j < hands) {
                 if (Max) s[0] = cmp_fold_p(a_tile, s[0], ein[j]);
                 else scan_advance<1>(&a_tile, s, ein + j);
             }
         }
         __syncthreads();
     }
+    if (open && l == 0) *carry = s[0];
 }
 
 }  // namespace ptts

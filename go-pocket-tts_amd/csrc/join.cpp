@@ -33,6 +33,20 @@ std::string join_opts_error(const ptts_join_opts* o, JoinLens* out) {
     return std::string();
 }
 
+std::string join_stream_opts_error(const ptts_join_stream_opts* so) {
+    if (!so) return "join: stream: null options";
+    constexpr size_t kKnown = sizeof(ptts_join_stream_opts);
+    std::string e = opts_size_error("join: stream", so, so->size, kKnown, kKnown, "the fields up to pcm_user");
+    if (!e.empty()) return e;
+    if (so->first_group < 0) return strfmt("join: stream: first_group %d is negative (0: max_batch, else the parts of the first group)", so->first_group);
+    return std::string();
+}
+
+int64_t join_stream_hold(const ptts_join_opts& o, const JoinLens& l) {
+    const int64_t fo = o.dsp && o.dsp->fade_out_ms > 0.0 ? ms_samples(o.dsp->fade_out_ms) : 0;
+    return std::max(l.xfade, fo);
+}
+
 std::string join_plan(const int64_t* n, int32_t rows, const JoinLens& l, int64_t* offsets, int64_t* seams, int64_t* total) {
     if (rows < 1 || rows > kJoinMaxRows) return strfmt("join: rows %d is not from 1 to %d", rows, kJoinMaxRows);
     if (!n) return "join: null lengths";
@@ -84,6 +98,14 @@ int64_t ptts_join_length(const int64_t* n, int32_t rows, const ptts_join_opts* o
     if (e.empty()) e = join_plan(n, rows, l, offsets, nullptr, &total);
     if (!e.empty()) return -(int64_t)fail(e);
     return total;
+}
+
+int64_t ptts_join_stream_ready(const ptts_join_opts* o, int64_t joined) {
+    JoinLens l;
+    std::string e = join_opts_error(o, &l);
+    if (e.empty() && joined < 0) e = strfmt("join: stream: joined %lld is negative", (long long)joined);
+    if (!e.empty()) return -(int64_t)fail(e);
+    return join_stream_ready(joined, join_stream_hold(*o, l));
 }
 
 int ptts_join(const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, float* out) {

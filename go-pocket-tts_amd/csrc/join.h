@@ -26,6 +26,15 @@ struct JoinLens { int64_t gap = 0, xfade = 0; };
 // to check (runtime.cpp join_egress_error)
 std::string join_opts_error(const ptts_join_opts* o, JoinLens* out);
 
+// Streamed joined synthesis (include/ptts.h ptts_join_stream_opts).  Empty: so is well formed as far as the host can tell (there, its size by the
+// rules of ptts_dsp_ext_opts, first_group not negative; the upper end is the model's max_batch, the device call's to check)
+std::string join_stream_opts_error(const ptts_join_stream_opts* so);
+// what a hand-over holds back behind the joined length: max(K, Fo), the crossfade and the fade out of o.dsp (a plain read, no handle is looked up)
+int64_t join_stream_hold(const ptts_join_opts& o, const JoinLens& l);
+// the samples that are final once `joined` have been joined and more parts follow: on the grid of the chain's scans (1920: kDspTile)
+constexpr int64_t kJoinStreamGrid = 1920;
+inline int64_t join_stream_ready(int64_t joined, int64_t hold) { return std::max<int64_t>(0, joined - hold) / kJoinStreamGrid * kJoinStreamGrid; }
+
 // samples of the seam between a part of na samples and its successor of nb: two seams never touch the same sample
 inline int64_t join_seam(int64_t xfade, int64_t na, int64_t nb) { return std::min(xfade, std::min(na / 2, nb / 2)); }
 

@@ -315,7 +315,15 @@ extern std::atomic<int64_t> g_resample_launches;
 // row with the ceiling as its only switch passes through k_dsp_apply untouched.  Tables without such a row launch what they launched before.
 // Limiter rows have no flag here: their kernels run on a table of their own (LimRow below) between this table's last kernel and k_tp_peak; a
 // row with the limiter as its only switch passes through k_dsp_apply untouched, like one with the ceiling alone.
-enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8, DSP_TP = 16 };
+// Windows (a streamed joined call, ptts_debug_dsp_windows): a launch of the causal stages -- the compressor, the DC block, the equaliser, the
+// fades -- may cover tiles [t0, ceil(n / kDspTile)) of a row only, n the samples up to the window's end, with the per-tile states of the window
+// alone in scratch.  DSP_OPEN (CmpRow::open): more samples follow behind n, which is then a multiple of kDspTile; the window's last tile hands a
+// state on like the others, the state behind it is left in `carry` and no fade out is applied (the window that closes the row applies it, with
+// the row's final n).  The next window starts from `carry`.  The fold S_(f+1) = A^1920 S_f + E_f is the same sequence of operations wherever
+// the row is cut, so the windows give the bits of the one-shot chain, which is the window t0 = 0, carry null, of a closed row.  The carried
+// states of one row: kCarryDoubles doubles, zero in front of the row's first window.
+enum DspFlags : int32_t { DSP_NORMALIZE = 1, DSP_DC = 2, DSP_LOUD = 4, DSP_EQ = 8, DSP_TP = 16, DSP_OPEN = 32 };
+constexpr int kCarryDc = 0, kCarryEq = 2, kCarryCmpP = 10, kCarryCmpS = 11, kCarryDoubles = 12;   // DspScan::N, then 2 kEqMaxSections, then the compressor's two
 constexpr int kDspMaxEq = 16;
 constexpr size_t kDspEqBytes = 1192;
 static_assert(sizeof(EqScan) == kDspEqBytes, "the DSP ring's tail (runtime.h) is sized by it");
@@ -331,15 +339,18 @@ struct DspRow {
     double* eq_tiles;      // equaliser rows: the cascade's per-tile states, 2 S doubles each for E_f and S_f
     uint32_t* tp;          // true-peak rows: one word, zero before k_tp_peak, then the row's true peak as its uint32 image
     float ceiling;         // true-peak rows: the linear ceiling c = (float)pow(10, dBTP / 20)
+    int64_t t0;            // the window's first tile (0: the row from its start); tiles, eq_tiles hold the window's tiles, entry 0 is tile t0's
+    double* carry;         // the row's carried states, [kCarryDoubles] (null: a one-shot row, started from zero state and closed)
 };
-static_assert(sizeof(DspRow) == 96, "a turn of the DSP ring holds 256 of them");
+static_assert(sizeof(DspRow) == 112, "a turn of the DSP ring holds 256 of them");
 // which flags occur in a table's rows, and the systems' coefficients (loud: needed with any_loud); apply false: the measuring launches only,
 // the samples stay as they are
 // any_eq: eqs is the device copy of the table's equalisers
 struct DspLaunch {
     bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr;
+    bool any_open = false;   // a row is open: the summaries cover every tile of the longest window
 };
-// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row
+// rows_dev: device copy of the n rows; max_tiles: the most tiles a row's window has (a one-shot row: ceil(n / kDspTile))
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
 // the last two of a table with a true-peak row (true_peak.hip; dsp_launch calls them behind launch_dsp's kernels and the limiter's tables, the
 // first alone for a measurement): the true peak of every DSP_TP row into its word; the gain c / TP over the rows whose word exceeds c
@@ -360,11 +371,13 @@ struct CmpRow {
     int64_t n;             // samples; nothing at or beyond n is touched
     double* p_tiles;       // the detector's per-tile states, [ceil(n / kDspTile)][2]: E_f, S_f (scan_block.h scan_E<1> / scan_S<1>)
     double* s_tiles;       // the smoothing's, likewise
-    int32_t design, pad;   // the index of the row's design among the table's
+    int32_t design, open;  // the index of the row's design among the table's; open: as DSP_OPEN
+    int64_t t0;            // the window's first tile, as DspRow::t0: p_tiles and s_tiles hold the window's tiles
+    double* carry;         // as DspRow::carry (kCarryCmpP, kCarryCmpS are this stage's)
 };
-static_assert(sizeof(CmpRow) == 40, "a turn of the compressor ring holds 256 of them");
-// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
-void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream);
+static_assert(sizeof(CmpRow) == 56, "a turn of the compressor ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the most tiles a row's window has; designs_dev: the table's designs; any_open: a row is open
+void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream, bool any_open = false);
 
 // A request's look-ahead peak limiter (limiter.hip, limiter.h): behind the fades and in front of the true-peak
 // ceiling, on a table of its own behind the DSP table's last kernel and in front of k_tp_peak.  k_lim_summary + k_lim_carry (the release's state

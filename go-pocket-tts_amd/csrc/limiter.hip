@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_summary(const LimRow* __restr
     __shared__ float ax[kLimLds];
     __shared__ double e[kDspLanes];
     const LimRow& r = rows[blockIdx.y];
-    if (!tile_hands_on(r.n)) return;
+    if (!tile_hands_on(0, r.n, false)) return;
     const LimScan d = designs[r.design];
     lim_load_mag(r, (int64_t)blockIdx.x * kDspTile, d.L, ax);
     __syncthreads();
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_carry(const LimRow* __restric
     __shared__ double ein[kDspLanes];
     const LimRow& r = rows[blockIdx.x];
     if (r.n <= 0) return;
-    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein);
+    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein, nullptr, false);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_lim_gain(const LimRow* __restrict__ rows, const LimScan* __restrict__ designs) {

@@ -2144,7 +2144,90 @@ static std::string join_egress_error(const ptts_join_opts& o) {
     return std::string();
 }
 
-void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, ptts_result* out, ptts_join_part* parts) {
+namespace {
+// A streamed joined call (include/ptts.h ptts_generate_joined_streamed): what its hand-overs share.  Behind each group's k_join the chain runs over
+// the window [done, P) of the joined row with the carried states (dsp_launch's windowed jobs), the egress converts or copies the outputs
+// [sent, o) into the buffer the result will own, and a host function on stream2 -- where a slow callback holds up a decode at the most, never
+// the next group's steps -- announces them.
+struct JoinStream {
+    Model& m;
+    const ptts_join_stream_opts& so;
+    const ptts_request& eg;          // the join options' chain and egress, as a request states its own
+    DspSpec spec;                    // the chain, resolved before anything launched
+    int64_t hold = 0, fade_in = 0;   // max(K, Fo); the fade in's samples, not clamped
+    void* host = nullptr;            // the result's buffer, allocated for the step budgets' bound
+    char* stage = nullptr;           // where the egress stores when it cannot store into `host` itself (device, indexed like `host`)
+    double* carry = nullptr;         // the chain's carried states (device, [kCarryDoubles])
+    int64_t done = 0, sent = 0;      // 24 kHz samples the chain has finished; outputs handed over
+    hipEvent_t ev = nullptr;
+    struct HandOver { const JoinStream* js; int64_t off, count; };
+    std::vector<std::unique_ptr<HandOver>> handed;   // read by the host functions: kept until both streams are drained
+
+    JoinStream(Model& m_, const ptts_join_stream_opts& so_, const ptts_request& eg_) : m(m_), so(so_), eg(eg_) {}
+    ~JoinStream() {
+        (void)hipStreamSynchronize(m.stream);
+        (void)hipStreamSynchronize(m.stream2);
+        if (ev) (void)hipEventDestroy(ev);
+        result_free(host);
+    }
+    void setup(const ptts_join_opts& o, const JoinLens& lens, int64_t bound, hipStream_t s) {
+        hold = join_stream_hold(o, lens);
+        fade_in = spec.fade_in_ms > 0 ? (int64_t)(spec.fade_in_ms / 1000.0 * (double)kNativeRate) : 0;
+        const size_t bytes = (size_t)std::max<int64_t>(1, egress_length(eg, bound)) * pcm_bytes(eg.pcm_format);
+        host = result_alloc(bytes);
+        if (!host) throw Error(PTTS_ENOMEM, "ptts-hip: out of host memory");
+        // k_resample stores into page-locked memory itself; f32 at 24 kHz without a chain is copied out of the joined row
+        if (request_converts(eg) ? !result_is_pinned(host) : eg.pcm_format == PTTS_PCM_S16) stage = m.work(WORK_JOIN_STAGE, bytes).as<char>();
+        carry = m.work(WORK_JOIN_CARRY, kCarryDoubles * sizeof(double)).as<double>();
+        PTTS_HIP(hipMemsetAsync(carry, 0, kCarryDoubles * sizeof(double), s));
+        PTTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    // behind a group's k_join: `at` samples are joined; last: no part follows
+    void window(float* row, int64_t at, bool last, hipStream_t s) {
+        int64_t P = last ? at : std::max(done, join_stream_ready(at, hold));
+        if (!last && at < fade_in) P = done;   // the fade in is clamped by the final length: not known to exceed it yet
+        if (P > done || last) {
+            if (spec.any()) {
+                std::vector<DspJob> jobs(1, DspJob{row, P, spec});
+                jobs[0].t0 = done / kDspTile; jobs[0].open = !last; jobs[0].carry = carry;
+                dsp_launch(m, jobs, s);
+            }
+            done = P;
+        }
+        // the egress of what is final: outputs [sent, o1)
+        const int fmt = eg.pcm_format;
+        const size_t esz = pcm_bytes(fmt);
+        const bool conv = request_converts(eg);
+        const RateFilter* f = conv ? rate_filter(m, kNativeRate, request_rate(eg), s) : nullptr;
+        const int64_t o1 = last ? egress_length(eg, at) : std::max(sent, resample_ready(f, done));
+        if (o1 <= sent) return;
+        const char* from = nullptr;   // (null: the launch stored into `host` itself)
+        if (conv) {
+            std::vector<ResampleRow> rows(1, resample_row(f, row, done, stage ? (void*)stage : host, sent, o1, fmt));
+            resample_launch(m, rows, s);
+            from = stage;
+        } else if (fmt == PTTS_PCM_S16) {
+            launch_pcm16(row + sent, reinterpret_cast<int16_t*>(stage) + sent, o1 - sent, s);
+            from = stage;
+        } else {
+            from = reinterpret_cast<const char*>(row);
+        }
+        hipStream_t s2 = m.stream2;
+        PTTS_HIP(hipEventRecord(ev, s));
+        PTTS_HIP(hipStreamWaitEvent(s2, ev, 0));
+        if (from) PTTS_HIP(hipMemcpyAsync((char*)host + (size_t)sent * esz, from + (size_t)sent * esz, (size_t)(o1 - sent) * esz, hipMemcpyDeviceToHost, s2));
+        handed.emplace_back(new HandOver{this, sent, o1 - sent});
+        PTTS_HIP(hipLaunchHostFunc(s2, [](void* p) {
+            const HandOver& h = *static_cast<const HandOver*>(p);
+            const JoinStream& js = *h.js;
+            js.so.pcm_callback(js.so.pcm_user, h.off, h.count, (const char*)js.host + (size_t)h.off * pcm_bytes(js.eg.pcm_format));
+        }, handed.back().get()));
+        sent = o1;
+    }
+};
+}  // namespace
+
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts) {
     std::lock_guard<std::mutex> lock(m.mu);
     m.use_device();
     const Desc& d = m.d;
@@ -2161,15 +2244,24 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     std::string e = join_opts_error(&o, &sink.lens);
     if (e.empty()) e = join_egress_error(o);
     if (e.empty() && (n < 1 || n > kJoinMaxRows)) e = strfmt("join: %d requests, a text has from 1 to %d parts", n, kJoinMaxRows);
+    const int mb = std::max(1, m.opts.max_batch);
+    if (e.empty() && so && (so->first_group < 0 || so->first_group > mb))
+        e = strfmt("join: stream: first_group %d is not 0 (max_batch) or from 1 to max_batch (%d)", so->first_group, mb);
     if (!e.empty()) refuse(e);
+    const bool streamed = so && so->pcm_callback;
+    DspSpec spec;
     if (o.dsp) {   // the trim and the tempo of the parts, resolved once: the chain below never sees them
-        DspSpec spec;
         e = dsp_resolve(o.dsp, &spec);
         if (!e.empty()) refuse("join: " + e);
         sink.trim = spec.trim;
         sink.trm = spec.trm;
         sink.tempo = spec.tempo;
         sink.tmp = spec.tmp;
+    }
+    if (streamed) {   // window after window only the causal stages run
+        if (o.loudness) dsp_spec_loudness(spec, nullptr);
+        e = dsp_window_refusal(spec);
+        if (!e.empty()) refuse("join: " + e);
     }
     const int lsd = reqs[0].lsd_steps <= 0 ? 1 : reqs[0].lsd_steps;
     const int t_limit = ROPE_SEQ / d.up_stride;
@@ -2190,23 +2282,40 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     ptts_request eg{};   // the chain and the egress of the joined row, as a request states its own: results_deliver serves it like one
     eg.sample_rate = o.sample_rate; eg.pcm_format = o.pcm_format; eg.dsp = o.dsp; eg.loudness = o.loudness;
     hipStream_t s = m.stream;
+    std::unique_ptr<JoinStream> js;   // (its destructor drains both streams before the hand-overs' records and the buffer go)
     try {
         sink.cap = std::max<int64_t>(bound, 1);
         sink.row = m.work(WORK_JOINED, (size_t)sink.cap * sizeof(float)).as<float>();
-        // ---- the groups, as generate() cuts them ----
-        const int mb = std::max(1, m.opts.max_batch);
+        if (streamed) {
+            js.reset(new JoinStream(m, *so, eg));
+            js->spec = spec;
+            js->setup(o, sink.lens, bound, s);
+        }
+        // ---- the groups, as generate() cuts them; a streamed call's first group may be smaller ----
         if (sink.trim) sink.info = static_cast<ptts_trim_info*>(m.trim_info.ensure((size_t)mb * sizeof(ptts_trim_info)));
-        for (int o0 = 0; o0 < n && sink.fail == PTTS_OK; o0 += mb) {
+        for (int o0 = 0, size = so && so->first_group ? so->first_group : mb; o0 < n && sink.fail == PTTS_OK; o0 += size, size = mb) {
             std::vector<int> idx;
-            for (int i = o0; i < std::min(n, o0 + mb); i++) idx.push_back(i);
+            for (int i = o0; i < std::min(n, o0 + size); i++) idx.push_back(i);
             try {
                 generate_group(m, reqs, idx, nullptr, lsd, &sink);
             } catch (const Error& err) {
                 for (int i : idx) if (parts[i].status == PTTS_OK) parts[i].status = err.code;
                 throw;
             }
+            // the group's hand-over, queued behind its k_join and in front of the next group's prefill; nothing waits for it here
+            if (js && sink.fail == PTTS_OK) js->window(sink.row, sink.at, o0 + size >= n, s);
         }
         if (sink.fail != PTTS_OK) throw Error(sink.fail, sink.fail_msg);
+        if (js) {   // every sample has been handed over from the buffer the result now owns
+            PTTS_HIP(hipStreamSynchronize(s));
+            PTTS_HIP(hipStreamSynchronize(m.stream2));
+            out->n_frames = (int)std::min<int64_t>(sink.frames, INT32_MAX); out->eos_step = -1;
+            out->n_samples = egress_length(eg, sink.at);
+            set_result_buffer(*out, eg.pcm_format, js->host);
+            js->host = nullptr;
+            out->status = PTTS_OK;
+            return;
+        }
         // ---- the chain, once over the joined audio; the egress of one row ----
         std::vector<Delivery> g(1);
         g[0] = Delivery{&eg, out, (int)std::min<int64_t>(sink.frames, INT32_MAX), -1, false};
@@ -2217,6 +2326,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (out->status != PTTS_OK) throw Error(out->status, "ptts-hip: out of host memory");
     } catch (const Error& err) {
         (void)hipStreamSynchronize(s);   // nothing queued still writes the buffer that goes back
+        js.reset();                      // (a streamed call: both streams drained, then its buffer freed)
         ptts_free_result(out);
         std::memset(out, 0, sizeof *out);
         out->eos_step = -1;

@@ -72,6 +72,8 @@ enum WorkSlot : size_t {
     WORK_TRIM_SCRATCH = 33,      // trim_launch: the rows' ptts_trim_info records, then their TrimTile tables
     WORK_TEMPO = 34,             // generate_joined with a tempo: a group's time-scaled rows, at the stride of the longest a decoded row can become
     WORK_TEMPO_SCRATCH = 35,     // tempo_launch: the rows' position tables
+    WORK_JOIN_CARRY = 36,        // a streamed joined call: the chain's carried states between its windows (kernels.h kCarryDoubles)
+    WORK_JOIN_STAGE = 37,        // ... and its egress where that cannot store into the result's buffer itself, indexed like that buffer
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -391,7 +393,13 @@ inline void dsp_spec_loudness(DspSpec& spec, const double* target_lufs) { spec.l
 // one row of the chain: x, n samples at 24 kHz on the device, rewritten in place as spec says.  dsp_launch sets loud_out to a loudness row's two
 // device words (the mean square M as a double, then the f32 gain) and tp_out to a true-peak row's (the true peak's uint32 image); both are valid
 // until the model's next DSP launch
-struct DspJob { float* x; int64_t n; DspSpec spec; double* loud_out = nullptr; uint32_t* tp_out = nullptr; };
+struct DspJob {
+    float* x; int64_t n; DspSpec spec; double* loud_out = nullptr; uint32_t* tp_out = nullptr;
+    // a window of the row (kernels.h; only the causal stages: dsp_window_refusal): the launches cover tiles [t0, ceil(n / 1920)), n the samples up
+    // to the window's end; open: more samples follow behind n (a multiple of 1920), n_row is then the length the fade in is clamped by; carry:
+    // the row's carried states on the device, [kCarryDoubles], zero in front of its first window (null: a one-shot row)
+    int64_t t0 = 0; bool open = false; int64_t n_row = INT64_MAX; double* carry = nullptr;
+};
 // the launches for a table of rows on s.  apply false: loudness and true-peak rows are measured only, no sample is rewritten
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply = true);
 // the chain on host rows, one round trip: rows packed into one device buffer and uploaded, dsp_launch, the outputs read back, one wait.  Takes
@@ -400,6 +408,10 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply =
 // [4 ceil(n / 1920)] sub-block energies as the device computed them; true_peaks [rows] (0: none)
 struct DspRowsOut { float* const* out = nullptr; double* M = nullptr; std::vector<double>* sub = nullptr; float* true_peaks = nullptr; };
 void dsp_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const DspSpec* per_row, bool apply, const DspRowsOut& o);
+// ptts_debug_dsp_windows: spec's causal stages over rows of host samples, window after window by the launches a streamed joined call runs: window
+// w is [cuts[w - 1], cuts[w]) of every row that has samples there (cuts: ascending multiples of 1920, checked by the caller), behind the last cut
+// one more to each row's end; a row is open in a window when it goes on behind it.  The carried states stay on the device.  Takes Model::mu
+void dsp_windows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const DspSpec& spec, const int64_t* cuts, int32_t n_cuts, float* const* out);
 inline size_t pcm_bytes(int fmt) { return fmt == PTTS_PCM_F32 ? 4 : fmt == PTTS_PCM_S16 ? 2 : 1; }
 inline void* result_buffer(const ptts_result& r, int fmt) {
     return fmt == PTTS_PCM_F32 ? (void*)r.pcm : fmt == PTTS_PCM_S16 ? (void*)r.pcm16 : (void*)r.pcm8;
@@ -419,7 +431,9 @@ std::string request_error(const Desc& d, const ptts_request& q);   // empty: the
 // Joined synthesis (join.h has the rule; include/ptts.h ptts_generate_joined): the requests as generate() runs them, in text order; each
 // group's decoded rows go through k_join into one device row for the text (Chunk::deliver, behind the fault check), then one DspJob over that
 // row and the egress of one row into *out.  parts: [n] or null.  Throws for a refusal (nothing launched) and for a failed chunk
-void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, ptts_result* out, ptts_join_part* parts);
+// so (include/ptts.h ptts_generate_joined_streamed; null: ptts_generate_joined): the first group's size, and with a pcm_callback the chain runs
+// window after window behind each group's k_join (DspJob's windows) and the audio that is final is handed over from a host function
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts);
 // k_join over a list of rows on s, one launch per RowRing::kRows rows
 void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
 // ptts_join_rows: the parts packed into one device buffer with the joined row behind them, uploaded, join_launch, the joined row back, one wait.

@@ -167,6 +167,8 @@ PTTS_HD inline void eq_dispatch(const EqScan& e, F&& f) {
 
 // A row's per-tile states in scratch: [F = ceil(n / kDspTile)][2 N] doubles, E_f (N) then S_f (N)
 PTTS_HD inline int64_t scan_tiles(int64_t n) { return (n + kDspTile - 1) / kDspTile; }
+// ... and of a window of it: the tiles from t0 to the end of the first n samples (kernels.h has what a window is)
+PTTS_HD inline int64_t win_tiles(int64_t t0, int64_t n) { return scan_tiles(n) - t0; }
 template <int N> PTTS_HD inline size_t scan_state_doubles(int64_t F) { return (size_t)F * 2 * N; }
 template <int N> PTTS_HD inline double* scan_E(double* states, int64_t f) { return states + f * 2 * N; }
 template <int N> PTTS_HD inline double* scan_S(double* states, int64_t f) { return states + f * 2 * N + N; }

@@ -140,6 +140,18 @@ class JoinOpts(C.Structure):   # ptts_join_opts
         self._dsp = dsp   # (borrowed by the struct: kept alive with it)
 
 
+class JoinStreamOpts(C.Structure):   # ptts_join_stream_opts
+    """How a joined call hands its audio over (ptts_join_stream_opts): first_group parts in the first group (0: max_batch) and the callback of the
+    hand-overs, a _PCM_CB or None.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("first_group", C.c_int32), ("pcm_callback", _PCM_CB), ("pcm_user", C.c_void_p)]
+
+    def __init__(self, first_group: int = 0, pcm_callback=None, size: Optional[int] = None):
+        super().__init__(C.sizeof(JoinStreamOpts) if size is None else int(size), int(first_group))
+        if pcm_callback is not None:
+            self.pcm_callback = pcm_callback
+        self._cb = pcm_callback   # (borrowed by the struct: kept alive with it)
+
+
 class JoinPart(C.Structure):   # ptts_join_part: one chunk of a joined call, offset and n_samples at 24 kHz in the joined audio
     _fields_ = [("offset", C.c_int64), ("n_samples", C.c_int64), ("n_frames", C.c_int32), ("eos_step", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -209,7 +221,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
     "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
-    "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined",
+    "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined", "ptts_generate_joined_streamed", "ptts_join_stream_ready",
     "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
     "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
     ]
@@ -221,7 +233,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
     "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window", "ptts_debug_flow_cluster",
-    "ptts_debug_mimi_fused", "ptts_debug_mimi_pack",
+    "ptts_debug_mimi_fused", "ptts_debug_mimi_pack", "ptts_debug_dsp_windows",
 ]
 
 
@@ -328,6 +340,10 @@ def lib():
         L.ptts_join.argtypes = [C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
         L.ptts_join_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
         L.ptts_generate_joined.argtypes = [C.c_void_p, C.POINTER(_Request), C.c_int32, C.POINTER(JoinOpts), C.POINTER(_Result), C.POINTER(JoinPart)]
+        L.ptts_generate_joined_streamed.argtypes = [C.c_void_p, C.POINTER(_Request), C.c_int32, C.POINTER(JoinOpts), C.POINTER(JoinStreamOpts), C.POINTER(_Result),
+                                                    C.POINTER(JoinPart)]
+        L.ptts_join_stream_ready.restype = C.c_int64
+        L.ptts_join_stream_ready.argtypes = [C.POINTER(JoinOpts), C.c_int64]
         L.ptts_trim_plan.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, C.POINTER(TrimInfo)]
         L.ptts_trim_apply.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, _FP, C.POINTER(TrimInfo)]
         L.ptts_trim_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TrimOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), C.POINTER(TrimInfo)]
@@ -367,6 +383,7 @@ def hooks():
         H.ptts_mimi_layer_piece.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _FP, C.c_int64, C.c_int32, C.c_int32, _FP]
         H.ptts_debug_flow_cluster_inject.argtypes = [C.c_void_p, C.c_int32]
         H.ptts_debug_loudness_energies.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_DP)]
+        H.ptts_debug_dsp_windows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), _IP, C.c_int32, C.POINTER(_FP)]
         H.ptts_debug_dsp_opts_error.restype = C.c_int64
         H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
         for name, args in (("flow_cluster", _FlowClusterArgs), ("step_linear", _StepLinearArgs), ("attn_step", _AttnStepArgs), ("attn_window", _AttnWindowArgs),
@@ -875,6 +892,16 @@ class Model:
         """Test hook (libptts_hooks.so ptts_debug_loudness_energies): the rows' 480-sample K-weighted energies as the device kernels compute them."""
         return loudness_energies(x, self)
 
+    def dsp_windows(self, x, cuts, opts: Optional[DspOpts] = None):
+        """ptts_debug_dsp_windows (libptts_hooks.so): the causal chain of opts over rows of 24 kHz samples in windows cut at `cuts` (ascending multiples
+        of 1920), state carried on the device, by the launches a streamed joined call runs.  The bits of dsp_rows."""
+        single, rows, n, pp, ns = _rows_in(x)
+        outs = [np.empty(r.size, np.float32) for r in rows]
+        cs = np.ascontiguousarray(cuts, np.int64).reshape(-1)
+        _check(hooks().ptts_debug_dsp_windows(self.h, pp, _ip(ns), n, C.byref(opts) if opts is not None else None,
+                                              _ip(cs) if cs.size else None, int(cs.size), _row_ptrs(outs)))
+        return outs[0] if single else outs
+
     def join_rows(self, parts, join: Optional[JoinOpts] = None) -> np.ndarray:
         """ptts_join_rows: join() on the device, by the kernel generate_joined runs: one upload, k_join, one download."""
         rows, n, pp, ns = _join_in(parts)
@@ -1031,10 +1058,13 @@ class Model:
         return out
 
 
-    def generate_joined(self, token_lists: Sequence[Sequence[int]], cfgs: Sequence[RuntimeGenerateConfig], join: Optional[JoinOpts] = None) -> JoinedResult:
+    def generate_joined(self, token_lists: Sequence[Sequence[int]], cfgs: Sequence[RuntimeGenerateConfig], join: Optional[JoinOpts] = None,
+                        pcm_callback=None, first_group: Optional[int] = None, stream: Optional[JoinStreamOpts] = None) -> JoinedResult:
         """ptts_generate_joined: the chunks of one text, generated as generate_batch generates them, joined on the device (gap or crossfade), the
         chain of `join` run once over the joined audio, one egress.  The cfgs carry no post-processing, rate or format of their own.  A failed call
-        raises PttsError with the chunks' records in its `parts`."""
+        raises PttsError with the chunks' records in its `parts`.
+        pcm_callback(offset, samples), first_group or stream (a JoinStreamOpts as it is) make it ptts_generate_joined_streamed: the audio is handed
+        over group by group, from a library thread, while the later groups run; offsets count samples of the egress, `samples` is a copy in its format."""
         n = len(token_lists)
         reqs = (_Request * max(n, 1))()
         parts = (JoinPart * max(n, 1))()
@@ -1043,7 +1073,16 @@ class Model:
         for i, (toks, cfg) in enumerate(zip(token_lists, cfgs)):
             self._fill_request(reqs[i], toks, cfg, keep)
         o = join if join is not None else JoinOpts()
-        rc = lib().ptts_generate_joined(self.h, reqs, n, C.byref(o), C.byref(res), parts)
+        if stream is None and (pcm_callback is not None or first_group is not None):
+            cb = None
+            if pcm_callback is not None:
+                dt = np.dtype(_PCM_DTYPES.get(int(o.pcm_format), "<f4"))
+                cb = _PCM_CB(lambda _u, off, cnt, ptr: pcm_callback(int(off), np.frombuffer(C.string_at(ptr, int(cnt) * dt.itemsize), dtype=dt)))
+            stream = JoinStreamOpts(first_group or 0, cb)
+        if stream is not None:
+            rc = lib().ptts_generate_joined_streamed(self.h, reqs, n, C.byref(o), C.byref(stream), C.byref(res), parts)
+        else:
+            rc = lib().ptts_generate_joined(self.h, reqs, n, C.byref(o), C.byref(res), parts)
         records = [JoinPart(p.offset, p.n_samples, p.n_frames, p.eos_step, p.status, 0) for p in parts[:n]]
         try:
             _check(rc)
@@ -1982,6 +2021,20 @@ def join_length(lengths, join: Optional[JoinOpts] = None, offsets: bool = False)
     return (total, offs[:ns.size]) if offsets else total
 
 
+def dsp_windows(model, x, cuts, opts: Optional[DspOpts] = None):
+    """Model.dsp_windows: the causal chain over rows in windows with carried state (the hook ptts_debug_dsp_windows)."""
+    return model.dsp_windows(x, cuts, opts)
+
+
+def join_stream_ready(join: Optional[JoinOpts], joined: int) -> int:
+    """ptts_join_stream_ready: the samples of the joined 24 kHz audio that are final once `joined` have been joined and more parts follow.  No GPU."""
+    o = join if join is not None else JoinOpts()
+    rc = int(lib().ptts_join_stream_ready(C.byref(o), int(joined)))
+    if rc < 0:
+        _check(-rc)
+    return rc
+
+
 def join(parts, join: Optional[JoinOpts] = None) -> np.ndarray:
     """ptts_join: the parts (mono f32 at 24 kHz, in order) as one utterance, with join.gap_ms of silence or join.crossfade_ms of overlap at the
     seams.  Host: the statement of what Model.join_rows and Model.generate_joined compute."""
@@ -2517,14 +2570,18 @@ class Service:
         parts = [r.pcm for _, r in self.synthesize_chunks(text, **voice)]
         return np.concatenate(parts) if parts else np.zeros(0, np.float32)
 
-    def synthesize_joined(self, text: str, join: Optional[JoinOpts] = None, **voice) -> JoinedResult:
+    def synthesize_joined(self, text: str, join: Optional[JoinOpts] = None, pcm_callback=None, first_group: int = 0, **voice) -> JoinedResult:
         """Service.Synthesize with the join, the post-processing over the whole text (cmd/pockettts/synth.go:361-390) and the egress on the
         device, in one call (Model.generate_joined): one result for the text, parts[i] says where chunk i lies in it.  Joined requests do not
-        go through a dispatcher, which deals single requests."""
+        go through a dispatcher, which deals single requests.  pcm_callback(offset, samples): the audio is handed over group by group while the later
+        groups run (Model.generate_joined), first_group parts in the first group (0: max_batch) for sooner first audio."""
         if self.dispatcher is not None:
             raise PttsError(PTTS_EINVAL, "synthesize_joined: a service with a dispatcher deals single requests; joined calls go to the model")
         try:
             chunks = prepare_chunks(text, self.encode, MAX_TOKENS_PER_CHUNK, self.model.info.frame_rate)
         except PttsError as e:
             raise PttsError(e.code, f"no tokens produced from input: {e}") from None   # service.go:124-126
-        return self.model.generate_joined([c.token_ids for c in chunks], [self.generate_config(c, **voice) for c in chunks], join)
+        cfgs = [self.generate_config(c, **voice) for c in chunks]
+        if pcm_callback is None and not first_group:
+            return self.model.generate_joined([c.token_ids for c in chunks], cfgs, join)
+        return self.model.generate_joined([c.token_ids for c in chunks], cfgs, join, pcm_callback=pcm_callback, first_group=first_group)

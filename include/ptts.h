@@ -495,6 +495,47 @@ int  ptts_join_rows(ptts_model* m, const float* const* in, const int64_t* n, int
 int  ptts_generate_joined(ptts_model* m, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, ptts_result* out,
                           ptts_join_part* parts /* [n], optional */);
 
+/* Streamed joined synthesis: ptts_generate_joined that hands a text's audio over group by group, so a long text is heard after its first
+ * group and not after its last.  A joined call with one request is the single-utterance form.
+ *   Groups.  The first group holds parts [0, g0), g0 = first_group ? first_group : max_batch; the following groups hold max_batch parts each,
+ *     in text order.  Each group runs exactly as ptts_generate_joined runs its groups: the decode after the loop, the trim and the tempo per
+ *     part, k_join.
+ *   The result.  With first_group == 0, *out and parts equal those of ptts_generate_joined(m, reqs, n, o, ...) in every byte, callback or not.
+ *     With another first_group they are the host statement (the host chain on ptts_join of the chunks' audio) on the chunks' audio as
+ *     ptts_generate calls over the same groups give it.
+ *   Hand-overs.  A_g: the joined length at 24 kHz after group g; K = (int64)(crossfade_ms / 1000 * 24000), Fo = (int64)(fade_out_ms / 1000 *
+ *     24000), neither clamped by a length.  Behind a group that is not the last
+ *         P_g = max(P_(g-1), floor(max(0, A_g - max(K, Fo)) / 1920) * 1920)          (P_(-1) = 0; ptts_join_stream_ready(o, A_g) is the floor term)
+ *     and behind the last group P = A.  Held back are the tail the next group's seam fades where it lies ([A_g - k, A_g), k <= K) and whatever
+ *     the fade out could reach, which needs the final length; the floor keeps every cut on the grid of the chain's blocked scans (1920
+ *     samples, one decoder frame).  While A_g is still below the fade in's length nothing is handed over either (that fade is clamped by the
+ *     final length): P_g = P_(g-1).  Window g is [P_(g-1), P_g) of the 24 kHz audio: the chain runs over it with the state the window in front
+ *     left, and gives the bits of the chain run once.  At 24 kHz in f32 or PCM16 the hand-over is that range; at another rate or in G.711 it is
+ *     the outputs [o_(g-1), o_g), o_g the outputs whose filter support lies inside the first P_g samples, as for a streamed request, and
+ *     behind the last group all of them.  pcm_callback(pcm_user, offset, count, samples): offset and count in output samples; a window with
+ *     nothing new makes no call; the hand-overs tile [0, out->n_samples) in order, each sample once.  `samples` points into the buffer *out
+ *     will own, allocated up front for what the step budgets allow.  Callbacks come from a library thread, as a streamed request's, and must
+ *     not call into the library.  A group's hand-over is queued before the next group's prefill is issued; the host does not wait for it.
+ *   The chain of a call with a callback: compressor, DC block, equaliser, fade in, fade out, in the documented order; around them the parts'
+ *     trim and tempo, gap or crossfade, every pcm_format and sample_rate.  PTTS_EINVAL, nothing launched, naming the field: normalize,
+ *     loudness and the true-peak ceiling (they need the whole text) and the limiter (its look-ahead is left for a later change), e.g.
+ *     "join: stream: loudness needs the whole text; it cannot be combined with pcm_callback".  With pcm_callback NULL nothing is refused beyond
+ *     what ptts_generate_joined refuses, and nothing is handed over early: the call differs from it by first_group alone.
+ *   Failure.  A chunk that is cancelled or runs past the decoder's reach fails the call as it fails ptts_generate_joined: *out is zeroed, its
+ *     buffer freed, parts[i].status names the chunk.  Audio handed over before is the true beginning of the text; the pointers of those
+ *     hand-overs die when the call returns.
+ *   Also PTTS_EINVAL, naming the field: so NULL, a bad size (the rules of ptts_dsp_ext_opts.size), a first_group outside 0 .. max_batch.
+ * ptts_join_stream_ready: the samples of the joined 24 kHz audio that are final once `joined` of them have been joined and more parts follow:
+ *     floor(max(0, joined - max(K, Fo)) / 1920) * 1920, Fo of o->dsp (NULL: 0).  -PTTS_EINVAL for bad options or a negative `joined`.  Host. */
+typedef struct ptts_join_stream_opts {
+    uint32_t size;            /* sizeof(ptts_join_stream_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  first_group;     /* 0: max_batch; else 1 .. max_batch: parts in the FIRST group (first audio sooner); later groups hold max_batch */
+    ptts_pcm_callback pcm_callback; void* pcm_user;   /* NULL: nothing is handed over early */
+} ptts_join_stream_opts;     /* 24 bytes */
+int  ptts_generate_joined_streamed(ptts_model* m, const ptts_request* reqs, int32_t n, const ptts_join_opts* o,
+                                   const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts /* [n], optional */);
+int64_t ptts_join_stream_ready(const ptts_join_opts* o, int64_t joined);
+
 /* Silence control of the parts of a joined text: a part's silent head and tail cut off and its over-long pauses
  * capped, per part and IN FRONT of the join, so that what a listener hears between two sentences is the join's gap or crossfade and not the
  * chunks' own lead-in and trailing frames around it; a joined call with one request is the single-utterance form (no lead-in latency).  The
@@ -849,7 +890,7 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_limit_rows; the new structs ptts_join_opts and ptts_join_part, which change no existing one, with ptts_join_length, ptts_join, ptts_join_rows,
  * ptts_generate_joined; the new structs ptts_trim_opts and ptts_trim_info, likewise, with ptts_trim_plan, ptts_trim_apply, ptts_trim_rows,
  * ptts_dsp_ext_set_trim; the new struct ptts_tempo_opts, likewise, with ptts_tempo_length, ptts_tempo_plan, ptts_tempo_apply, ptts_tempo_rows,
- * ptts_dsp_ext_set_tempo */
+ * ptts_dsp_ext_set_tempo; the new struct ptts_join_stream_opts, likewise, with ptts_generate_joined_streamed, ptts_join_stream_ready */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of

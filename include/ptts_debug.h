@@ -219,6 +219,15 @@ int64_t ptts_debug_resample_launches(int32_t reset);
  * functions the kernels call: n samples at 24 kHz, in -> out (in == out allowed).  No GPU. */
 int ptts_debug_dsp_blocked_host(const float* in, int64_t n, float* out);
 
+/* The causal chain over rows of host samples in windows, by the launches a streamed joined call runs (ptts_generate_joined_streamed): window j
+ * covers [cuts[j-1], cuts[j]) of every row that reaches it (cuts: ascending multiples of 1920 above 0; behind the last cut one more window to each
+ * row's end); a row is open in a window when it has samples behind the window's end.  State is carried between windows on the device.  out[i]:
+ * n[i] floats (out[i] == in[i] allowed): the bits of ptts_dsp_rows on the same rows and options.  PTTS_EINVAL for a stage that is not causal
+ * (normalize, the true-peak ceiling, the limiter: as the streamed call words it), a cut off the grid, and a cut c < n[i] with c > n[i] - Fo,
+ * Fo = (int64)(fade_out_ms / 1000 * 24000) (it would deliver part of row i's fade out), naming row and cut. */
+int ptts_debug_dsp_windows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, const ptts_dsp_opts* opts,
+                           const int64_t* cuts, int32_t n_cuts, float* const* out);
+
 /* Loudness (ptts_loudness; csrc/scan_block.h): the energies of the rows' whole 480-sample sub-blocks -- out[i] receives n[i] / 480 doubles, the
  * sums of squares of the K-weighted samples -- as the device kernels of a request's `loudness` compute them (m != NULL), or by the host
  * instantiation of the functions those kernels call (m == NULL, no GPU).  Twenty of them in order, over 9600, are one 400 ms block. */
