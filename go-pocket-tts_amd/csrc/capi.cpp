@@ -1249,7 +1249,7 @@ int ptts_join_rows(ptts_model* h, const float* const* in, const int64_t* n, int3
     });
 }
 
-// Service.Synthesize's chunks as one utterance (service.go:107-153), finished on the device: generate_joined (runtime.cpp)
+// Service.Synthesize's chunks as one utterance (service.go:107-153), finished on the device: generate_joined (generate.cpp)
 int ptts_generate_joined(ptts_model* h, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, ptts_result* out, ptts_join_part* parts) {
     return guard([&] {
         if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
@@ -1260,7 +1260,7 @@ int ptts_generate_joined(ptts_model* h, const ptts_request* reqs, int32_t n, con
     });
 }
 
-// ... handed over group by group (runtime.cpp JoinStream).  The stream options are checked first: their refusals need no model
+// ... handed over group by group (generate.cpp JoinStream).  The stream options are checked first: their refusals need no model
 int ptts_generate_joined_streamed(ptts_model* h, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, const ptts_join_stream_opts* so, ptts_result* out,
                                   ptts_join_part* parts) {
     return guard([&] {

@@ -2,6 +2,7 @@
 // libptts_hooks.so, which depends on libptts_hip.so and is loaded by the tests, tools/ and bench.py's measurement passes only.  The library a host of the
 // reference links therefore exports no fault injection, no micro-benchmarks and no launch census.
 #include "capi_internal.h"
+#include "launch_args.h"
 #include "../../include/ptts_debug.h"
 #include "scan_block.h"
 #include "true_peak.h"
@@ -164,7 +165,7 @@ int ptts_debug_flow_cluster_inject(ptts_model* h, int32_t block) {
     });
 }
 
-// k_flow_cluster on host operands: a SEQUENCE of launches on one granule buffer and one set of tag words, FlowClusterArgs filled as runtime.cpp step_flow
+// k_flow_cluster on host operands: a SEQUENCE of launches on one granule buffer and one set of tag words, FlowClusterArgs filled as step.cpp step_flow
 // fills them.  The kernel's workgroups spin on each other, so nothing is launched that the batch set-up would not launch: flow_cluster_fits and
 // flow_cluster_supported are asked, inject and stamps stay at their defaults (there is no argument that reaches them).
 int ptts_debug_flow_cluster(const ptts_flow_cluster_args* pa) {
@@ -208,7 +209,7 @@ int ptts_debug_flow_cluster(const ptts_flow_cluster_args* pa) {
         // every launch its own copy of the rows it takes: NaN behind them (in place that is what the rows at and beyond launch_rows keep)
         float *dIn = st.out((size_t)L * buf_rows * C), *dOut = st.out((size_t)L * buf_rows * C);
         for (int i = 0; i < L; i++) up(dIn + (size_t)i * buf_rows * C, t.fx, (size_t)t.launch_rows[i] * row_bytes);
-        // the exchange state as runtime.cpp sets it up (zeroes), then the tag words at tag_base0
+        // the exchange state as batch.cpp sets it up (zeroes), then the tag words at tag_base0
         PTTS_HIP(hipMemset(dX.p, 0, flow_cluster_xbuf_bytes(rows))); PTTS_HIP(hipMemset(dSync.p, 0, kFlowClusterSyncBytes));
         std::vector<uint32_t> sync(kFlowClusterSyncBytes / 4, 0u);
         for (int tile = 0; tile < kFlowClusterMaxTiles; tile++) sync[(size_t)tile * 32] = t.tag_base0;
@@ -553,8 +554,8 @@ int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t
             PrepArgs pa;
             pa.x = st.in(x, mk); pa.ldx = K; pa.ln_w = st.in(ln_w, (size_t)K); pa.ln_b = st.in(ln_b, (size_t)K); pa.eps = eps;
             if (planes && psplit > 0) {
-                pa.partial = st.in(planes, (size_t)psplit * mk); pa.psplit = psplit; pa.pstride = (int64_t)mk; pa.x_out = dXo.as<float>();
-                pa.pbias = st.in(pbias, (size_t)K);
+                pa.pend = PendingSum{st.in(planes, (size_t)psplit * mk), psplit, (int64_t)mk, st.in(pbias, (size_t)K)};
+                pa.x_out = dXo.as<float>();
             }
             pa.yh = dAh.as<uint16_t>(); pa.yl = dAl.as<uint16_t>(); pa.ldy = K; pa.M = M; pa.D = K;
             if (!rowprep_supported(pa)) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: rows not taken by k_rowprep");
@@ -641,10 +642,7 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
             fu.ln_w = st.in(t.ln_w, (size_t)K); fu.ln_b = st.in(t.ln_b, (size_t)K);
             fu.shift = st.in(t.shift, mod_elems); fu.scale = st.in(t.mscale, mod_elems);
             fu.ldmod = t.ldmod;
-            if (t.planes) {
-                fu.partial = st.in(t.planes, (size_t)t.psplit * mk); fu.psplit = t.psplit; fu.pstride = (int64_t)mk;
-                fu.pbias = st.in(t.pbias, (size_t)K);
-            }
+            if (t.planes) fu.pend = PendingSum{st.in(t.planes, (size_t)t.psplit * mk), t.psplit, (int64_t)mk, st.in(t.pbias, (size_t)K)};
             if (t.pgate) { fu.pgate = dXo; fu.ldpg = 1; }   // (never launched: the step kernel takes no gated pending sum)
             fu.x_out = dXo; fu.y_out = dYo;
         }
@@ -670,7 +668,7 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     });
 }
 
-// The step attention on host operands: ONE launch_attention call with the AttnArgs of the AR step (runtime.cpp step_core).  k_attn_step bounds none of its
+// The step attention on host operands: ONE launch_attention call with the AttnArgs of the AR step, from the function step.cpp step_core builds them with (launch_args.h attn_step_args).  k_attn_step bounds none of its
 // loads by a buffer size -- cache rows up to seg_len, prefix rows up to pre_len, the RoPE row at seg_len -- so every one of those is checked against the
 // buffers allocated here before anything is uploaded; there is no way to ask for a launch without the checks.
 int ptts_debug_attn_step(const ptts_attn_step_args* pa) {
@@ -708,17 +706,9 @@ int ptts_debug_attn_step(const ptts_attn_step_args* pa) {
             if (t.voice_of_row[r] >= 0) { hk[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r]]; hv[(size_t)r] = pre[(size_t)2 * t.voice_of_row[r] + 1]; }
         void *dK = st.in_bytes(t.k, kv_bytes), *dV = st.in_bytes(t.v, kv_bytes);
         float* dO = st.out(out_elems);
-        AttnArgs a;   // as step_core fills them
-        a.k = dK; a.v = dV; a.kv_bf16 = t.kv_bf16;
-        a.k_seg_stride = (int64_t)heads * cap * 64; a.k_head_stride = (int64_t)cap * 64; a.k_row_stride = 64;
-        a.seg_len = st.in(t.seg_len, (size_t)rows); a.active = st.in(t.active, (size_t)rows);
-        a.context = -1;
-        a.out = dO; a.out_ld = t.out_ld;
-        a.rows = rows; a.heads = heads; a.max_keys = cap;
-        a.keys_now = t.keys_now;
-        a.fused_step = 1; a.qkv = st.in(t.qkv, (size_t)rows * t.qkv_ld); a.qkv_ld = t.qkv_ld; a.d_model = D;
-        a.cos_t = st.in(t.cos_t, tab); a.sin_t = st.in(t.sin_t, tab); a.cap = cap;
-        a.pre_k = st.in(hk.data(), (size_t)rows); a.pre_v = st.in(hv.data(), (size_t)rows); a.pre_len = st.in(t.pre_len, (size_t)rows); a.layer = t.layer;
+        const StepAttnRows ar{st.in(t.qkv, (size_t)rows * t.qkv_ld), t.qkv_ld, D, st.in(t.cos_t, tab), st.in(t.sin_t, tab), st.in(t.seg_len, (size_t)rows),
+                              st.in(t.active, (size_t)rows), st.in(hk.data(), (size_t)rows), st.in(hv.data(), (size_t)rows), st.in(t.pre_len, (size_t)rows), rows};
+        const AttnArgs a = attn_step_args(KvLayer{dK, dV, t.kv_bf16, heads, cap, 64}, ar, t.layer, t.keys_now, dO, t.out_ld);   // step_core's launch form
         LaunchScope launches;
         launches.run([&] { launch_attention(a, nullptr); });
         PTTS_HIP(hipDeviceSynchronize());
@@ -737,7 +727,7 @@ int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per
     return attn_step_rounds(keys, kv_bf16 != 0);
 }
 
-// The window attention on host operands: ONE launch with AttnArgs as mimi_range / the encoder (dense) or the prompt prefill (ragged) fill them.  The kernels
+// The window attention on host operands: ONE launch with the AttnArgs of mimi_range / the encoder (dense) or of the prompt prefill (ragged), from the functions those build them with (launch_args.h).  The kernels
 // bound their key loads by positions alone (pos_base + rows, rag_pos0 + segment length), never by a buffer size, so those are checked against the buffers
 // allocated here before anything is uploaded.
 int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
@@ -754,22 +744,20 @@ int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
         if (t.ld > (1 << 16) || t.out_ld > (1 << 16)) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: ld / out_ld above 65536");
         if (t.ld % 4 || t.out_ld % 4)
             throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: ld %lld / out_ld %lld: rows must keep 16-byte alignment (attn_window_supported)", (long long)t.ld, (long long)t.out_ld));
-        int rows = 0, longest = 0, max_pos = 0;
-        std::vector<int32_t> row_seg, row_pos;
+        int rows = 0;
+        RaggedMeta meta;
         if (t.ragged) {
             if (!t.k || !t.v || !t.rag_off || !t.rag_pos0) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: ragged operands need k, v, rag_off and rag_pos0");
             if (t.form == 2) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: form 2 (k_attn_window_lds) takes dense operands only");
             if (t.cap < 1 || t.cap > 4096 || t.rows < 1 || t.rows > 4096) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: cap %d / rows %d outside 1..4096", t.cap, t.rows));
             if (t.rag_off[0] != 0 || t.rag_off[segs] != t.rows) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: rag_off runs from %d to %d, not from 0 to rows %d", t.rag_off[0], t.rag_off[segs], t.rows));
             rows = t.rows;
-            row_seg.resize((size_t)rows); row_pos.resize((size_t)rows);
             for (int s = 0; s < segs; s++) {
                 const int n = t.rag_off[s + 1] - t.rag_off[s];
                 if (n < 0) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: rag_off decreases at segment %d", s));
                 if (t.rag_pos0[s] < 0 || t.rag_pos0[s] + n > t.cap) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: segment %d: %d rows from position %d, the cache holds %d", s, n, t.rag_pos0[s], t.cap));
-                longest = std::max(longest, n);
-                for (int i = 0; i < n; i++) { row_seg[(size_t)t.rag_off[s] + i] = s; row_pos[(size_t)t.rag_off[s] + i] = t.rag_pos0[s] + i; max_pos = std::max(max_pos, t.rag_pos0[s] + i); }
             }
+            meta = ragged_meta(t.rag_off, t.rag_pos0, segs);   // batch_prompt's one-upload table
         } else {
             if (t.kv_bf16) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: the dense layout is f32 (attn_window_supported)");
             if (t.T1 < 1 || t.T1 > 4096) throw Error(PTTS_EINVAL, strfmt("ptts_debug_attn_window: T1 %d outside 1..4096", t.T1));
@@ -780,41 +768,16 @@ int ptts_debug_attn_window(const ptts_attn_window_args* pa) {
         }
         require_device();
         const size_t q_elems = (t.ragged ? (size_t)rows : (size_t)segs * t.T1) * t.ld, kv_bytes = (size_t)segs * heads * t.cap * 64 * es, out_elems = (size_t)rows * t.out_ld,
-                     meta_n = (size_t)2 * rows + 2 * segs + 1;
+                     meta_bytes = std::max<size_t>(meta.table.size(), 1) * 4;
         Stage st;
-        Tmp dMeta(meta_n * 4);
+        Tmp dMeta(meta_bytes);
         float *dQ = st.in(t.qkv, q_elems), *dO = st.out(out_elems);
-        AttnArgs a;
-        a.q_ld = t.ld; a.q_col0 = 0;
-        a.context = t.context;
-        a.out = dO; a.out_ld = t.out_ld;
-        a.rows = rows; a.heads = heads;
-        if (t.ragged) {   // runtime.cpp, the prompt prefill: one upload holds row -> segment, row -> position, the segments' first rows and first positions
-            int32_t* d_slot = dMeta.as<int32_t>();
-            int32_t* d_pos = d_slot + rows;
-            a.q = dQ;
-            a.k = st.in_bytes(t.k, kv_bytes); a.v = st.in_bytes(t.v, kv_bytes); a.kv_bf16 = t.kv_bf16;
-            a.k_seg_stride = (int64_t)heads * t.cap * 64; a.k_head_stride = (int64_t)t.cap * 64; a.k_row_stride = 64;
-            a.row_seg = d_slot; a.row_pos = d_pos;
-            a.rag_off = d_pos + rows; a.rag_pos0 = d_pos + rows + segs + 1; a.rag_segs = segs; a.rows_per_seg = longest;
-            a.max_keys = max_pos + 1;
-        } else {          // runtime.cpp mimi_range (encoder.cpp: t0 = 0, CT = T1, one segment)
-            float* qkv = dQ;
-            a.q = qkv + (size_t)t.t0 * t.ld; a.q_rows_per_batch = t.CT; a.q_batch_stride = (int64_t)t.T1 * t.ld;
-            a.k = qkv + D; a.v = qkv + 2 * D; a.kv_bf16 = 0;
-            a.k_seg_stride = (int64_t)t.T1 * t.ld; a.k_head_stride = 64; a.k_row_stride = t.ld;
-            a.rows_per_seg = t.CT; a.pos_base = t.t0;
-            a.max_keys = std::min(t.T1, t.context);
-        }
+        // the engine's own launch forms: batch_prompt's (ragged), mimi_range's (dense; encoder.cpp: t0 = 0, CT = T1, one segment)
+        const AttnArgs a = t.ragged ? attn_ragged_args(KvLayer{st.in_bytes(t.k, kv_bytes), st.in_bytes(t.v, kv_bytes), t.kv_bf16, heads, t.cap, 64}, meta, dMeta.as<int32_t>(), dQ,
+                                                       t.ld, t.context, dO, t.out_ld)
+                                    : attn_dense_args(dQ, t.ld, D, segs, t.T1, t.t0, t.CT, heads, 64, t.context, dO, t.out_ld);
         if (!attn_window_supported(a) || (t.form && !attn_window_form_supported(a, t.form))) throw Error(PTTS_EINVAL, "ptts_debug_attn_window: refused by attn_window_supported");
-        if (t.ragged) {
-            std::vector<int32_t> meta(meta_n);
-            std::copy(row_seg.begin(), row_seg.end(), meta.begin());
-            std::copy(row_pos.begin(), row_pos.end(), meta.begin() + rows);
-            std::copy(t.rag_off, t.rag_off + segs + 1, meta.begin() + 2 * rows);
-            std::copy(t.rag_pos0, t.rag_pos0 + segs, meta.begin() + 2 * rows + segs + 1);
-            up(dMeta.p, meta.data(), meta_n * 4);
-        }
+        if (t.ragged) up(dMeta.p, meta.table.data(), meta.table.size() * 4);
         LaunchScope launches;
         launches.run([&] {
             if (t.form == 0) launch_attention(a, nullptr);

@@ -270,7 +270,7 @@ bool cont_accepts(const ContEngine& e, const ptts_request& r) {
     const int ms = resolve_max_steps(r);
     const int tp = (int)r.n_tokens + (r.voice_embedding ? (int)r.voice_frames : 0);
     const int off = r.voice ? reinterpret_cast<const Voice*>(r.voice)->offset : (r.voice_caches ? (int)r.voice_offsets[0] : 0);
-    return ms <= e.max_steps && off + tp + ms <= e.cap && ms <= ROPE_SEQ / e.m.d.up_stride;
+    return ms <= e.max_steps && off + tp + ms <= e.cap && ms <= mimi_frame_limit(e.m.d);
 }
 
 // n waiting requests move into free slots (n <= cont_free_slots): voice state, prompt prefill, bookkeeping, noise rows

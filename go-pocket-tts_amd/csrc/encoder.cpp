@@ -8,7 +8,7 @@
 //   -> transformer (the decoder transformer's layer, positions from 0 per clip) -> downsample conv (stride k/2, no bias) = the raw latent
 // Every convolution is causal with zero history (k - s zero rows in front of a stride-s conv), and a clip is padded with zeros to a whole number of
 // frames.  Channels-last activations; a stride-s convolution is a product whose A rows are the overlapping windows s * Cin apart (RowMap::ld).
-#include "runtime.h"
+#include "launch_args.h"
 
 #include <algorithm>
 #include <cstring>
@@ -16,8 +16,6 @@
 namespace ptts {
 
 namespace {
-
-RowMap flat(int64_t ld) { return RowMap{ld, 0, 0}; }
 
 GemmArgs conv_gemm(const Model& m, const float* A, int64_t lda, const Lin& l, float* C, int64_t ldc, int M) {
     GemmArgs g;
@@ -204,15 +202,7 @@ int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* l
     for (int l = 0; l < e.layers; l++) {
         const auto& L = e.ml[l];
         mimi_layer_qkv(m, L, x, xm, (int)T, w.qkv, qm, 0, (int)T, w.n1, s);
-        AttnArgs a;
-        a.q = w.qkv; a.q_ld = 3 * C; a.q_col0 = 0; a.q_rows_per_batch = T; a.q_batch_stride = T * 3 * C;
-        a.k = w.qkv + C; a.v = w.qkv + 2 * C; a.kv_bf16 = 0;
-        a.k_seg_stride = T * 3 * C; a.k_head_stride = d.mimi_hd; a.k_row_stride = 3 * C;
-        a.rows_per_seg = (int)T; a.pos_base = 0;
-        a.context = d.mimi_ctx;
-        a.out = w.attn; a.out_ld = C;
-        a.rows = (int)T; a.heads = d.mimi_heads; a.hd = d.mimi_hd; a.max_keys = (int)std::min<int64_t>(T, d.mimi_ctx);
-        launch_attention(a, s);
+        launch_attention(attn_dense_args(w.qkv, 3 * C, C, 1, (int)T, 0, (int)T, d.mimi_heads, d.mimi_hd, d.mimi_ctx, w.attn, C), s);   // one segment, one chunk
         GemmArgs go = conv_gemm(m, w.attn, C, L.out_proj, x, C, (int)T);
         go.amap = flat(C); go.cmap = xm;
         go.R = x; go.epi = L.ls1 != NONE ? EPI_SCALE_RESADD : EPI_RESADD; go.scale = m.at<float>(L.ls1);

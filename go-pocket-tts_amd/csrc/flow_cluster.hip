@@ -12,7 +12,7 @@ namespace ptts {
 // ------------------------------------------------------------------------------------------------
 // flowResBlock.Forward x depth (flow_net.go:116-172):  h = silu(mlp0(modulate(LayerNorm(x), shift, scale)));  x += gate * mlp2(h)
 //
-// As launches (runtime.cpp step_core) these are 2 x depth dependent k_skinny launches of 4-5.6 us each for 0.5 MB of weights apiece: launch
+// As launches (step.cpp step_core) these are 2 x depth dependent k_skinny launches of 4-5.6 us each for 0.5 MB of weights apiece: launch
 // boundary, a cold argument block, a cold weight round trip and the store drain every time.  Here the chain stays inside one launch:
 //   * a 12-row tile of the batch belongs to EIGHT workgroups; workgroup cb owns output columns [64 cb, 64 cb + 64) of every linear -- its weight
 //     fragments are requested one linear ahead (they depend on nothing) and wait in registers;

@@ -23,7 +23,7 @@ struct JoinLens { int64_t gap = 0, xfade = 0; };
 
 // empty: o is well formed as far as the join goes (the size rules of ptts_dsp_ext_opts, gap_ms and crossfade_ms finite values from 0 to 2000,
 // not both above 0), and *out has the two lengths; otherwise the message, naming the field.  The egress fields and `dsp` are the device call's
-// to check (runtime.cpp join_egress_error)
+// to check (generate.cpp join_egress_error)
 std::string join_opts_error(const ptts_join_opts* o, JoinLens* out);
 
 // Streamed joined synthesis (include/ptts.h ptts_join_stream_opts).  Empty: so is well formed as far as the host can tell (there, its size by the

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -92,10 +93,13 @@ extern thread_local int g_gemm5_cfg;
 // The optional prologue (SkinnyFuse; needs K == row width <= 1024, splitk == 1) folds the preceding residual update
 // and LayerNorm into the activation staging.
 struct StepFinish;   // defined with StepState below
+// A deferred "rows += sum of split-K planes + bias": `splitk` planes of raw sums, pstride elements apart, added in plane order by the prologue of the rows'
+// next consumer (k_skinny, k_rowprep, k_layernorm_reg).  It sits inside those kernels' by-value arguments: a static_assert behind each pins where it lies.
+struct PendingSum { const float* partial = nullptr; int splitk = 0; int64_t pstride = 0; const float* bias = nullptr; };
 struct SkinnyFuse {
-    // x[row] += pgate[row] * (sum_z partial[z][row] + pbias)   (partial: [psplit][M][K])
-    const float* partial = nullptr; int psplit = 0; int64_t pstride = 0;
-    const float* pbias = nullptr; const float* pgate = nullptr; int64_t ldpg = 0;
+    // x[row] += pgate[row] * (sum_z pend.partial[z][row] + pend.bias)   (partial: [splitk][M][K])
+    PendingSum pend;
+    const float* pgate = nullptr; int64_t ldpg = 0;
     float* x_out = nullptr;          // the updated rows, written once (dense [M, K]); must not alias A
     int ln = 0;                      // 1: LayerNorm the rows before the product
     const float* ln_w = nullptr; const float* ln_b = nullptr; float eps = 1e-5f;
@@ -110,6 +114,7 @@ struct SkinnyFuse {
     int chain = 0;
     const float* chain_noise = nullptr; int64_t chain_noise_stride = 0;   // [B][max_steps][ldim] or null (zeros)
 };
+static_assert(sizeof(SkinnyFuse) == 152 && offsetof(SkinnyFuse, pgate) == 32, "k_skinny takes it by value: the layout stays");
 bool skinny_supported(const GemmArgs& a, int splitk);
 bool skinny_fuse_supported(const GemmArgs& a, const SkinnyFuse& f);
 void launch_skinny(const GemmArgs& a, const SkinnyFuse& fu, int splitk, float* partial, hipStream_t stream);
@@ -125,15 +130,16 @@ extern thread_local SkinnyStampLog* g_skinny_stamp_log;
 extern thread_local hipEvent_t g_skinny_ev[2];   // when set, launch_skinny times the dispatch with them (hipExtLaunchKernel)
 
 // The AR step's big linears at 128+ rows (tall.hip): row preparation once per row, then a 64 x 64-tile product whose operands both stream through LDS.
-struct PrepArgs {   // x' = x + (sum of psplit planes, in order) + pbias -> x_out; LayerNorm(x') -> bf16 hi / lo planes [M][ldy] (and f32 rows to y_out)
+struct PrepArgs {   // x' = x + pend (the planes in order, then the bias) -> x_out; LayerNorm(x') -> bf16 hi / lo planes [M][ldy] (and f32 rows to y_out)
     const float* x = nullptr; int64_t ldx = 0;
-    const float* partial = nullptr; int psplit = 0; int64_t pstride = 0; const float* pbias = nullptr;   // planes [psplit][M][D]
-    float* x_out = nullptr;                                                                            // dense [M][D]; written only with `partial`
+    PendingSum pend;                 // planes [splitk][M][D]
+    float* x_out = nullptr;          // dense [M][D]; written only with pend.partial
     const float* ln_w = nullptr; const float* ln_b = nullptr; float eps = 1e-5f;
     uint16_t* yh = nullptr; uint16_t* yl = nullptr; int64_t ldy = 0;
     float* y_out = nullptr;
     int M = 0, D = 0;
 };
+static_assert(sizeof(PrepArgs) == 120 && offsetof(PrepArgs, x_out) == 48, "k_rowprep takes it by value: the layout stays");
 bool rowprep_supported(const PrepArgs& a);
 void launch_rowprep(const PrepArgs& a, hipStream_t stream);
 struct TallArgs {   // C[M,N] = epi(A[M,K] * W[N,K]^T + bias), A = ah + al (bf16 planes), W the fragment-ordered bf16 copy (Linear::wt)
@@ -158,11 +164,12 @@ struct LnArgs {
     float* y = nullptr; int64_t ldy = 0;   // y == null: reduction prologue only
     int rows = 0, d = 0;
     // optional fused split-K reduction + residual update, applied before the normalisation (flat rows, d % 4 == 0):
-    //   x[row] += pgate[row] * pscale * (sum_z partial[z][row] + pbias)       (x is updated in place)
-    const float* partial = nullptr; int splitk = 0; int64_t pstride = 0;
-    const float* pbias = nullptr; const float* pgate = nullptr; int64_t ldpg = 0;
+    //   x[row] += pgate[row] * pscale * (sum_z pend.partial[z][row] + pend.bias)       (x is updated in place)
+    PendingSum pend;
+    const float* pgate = nullptr; int64_t ldpg = 0;
     const float* pscale = nullptr;
 };
+static_assert(sizeof(LnArgs) == 160 && offsetof(LnArgs, pgate) == 136, "k_layernorm takes it by value: the layout stays");
 void launch_layernorm(const LnArgs& a, hipStream_t stream);
 // Bessel-variance "RMS" norm of the timestep embedder (tensor_util.go:273-326), in place
 void launch_rmsnorm_alpha(float* x, const float* alpha, float eps, int rows, int d, hipStream_t stream);

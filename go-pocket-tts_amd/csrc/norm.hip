@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_layernorm(LnArgs a) {
 }
 
 // d % 4 == 0 and d <= 1024: the row lives in registers (one 16-byte load per 4 values).  Optional prologue
-//   x[row] += gate * scale * (sum_z partial[z][row] + pbias)
+//   x[row] += gate * scale * (sum_z pend.partial[z][row] + pend.bias)
 // folds the split-K reduction and the residual update of the preceding linear into this launch; the partials
 // are added in a fixed order, so results are bitwise reproducible.
 __global__ __launch_bounds__(256) void k_layernorm_reg(LnArgs a) {
@@ -50,18 +50,18 @@ __global__ __launch_bounds__(256) void k_layernorm_reg(LnArgs a) {
         v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (f < nv) {
             v[j] = reinterpret_cast<const float4*>(xw)[f];
-            if (a.partial) {
+            if (a.pend.partial) {
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                for (int z0 = 0; z0 < a.splitk; z0 += 8) {   // 8 independent loads in flight, then a fixed-order sum
+                for (int z0 = 0; z0 < a.pend.splitk; z0 += 8) {   // 8 independent loads in flight, then a fixed-order sum
                     float4 p[8];
 #pragma unroll
                     for (int u = 0; u < 8; u++)
-                        p[u] = z0 + u < a.splitk ? reinterpret_cast<const float4*>(a.partial + (int64_t)(z0 + u) * a.pstride + (int64_t)row * a.d)[f]
+                        p[u] = z0 + u < a.pend.splitk ? reinterpret_cast<const float4*>(a.pend.partial + (int64_t)(z0 + u) * a.pend.pstride + (int64_t)row * a.d)[f]
                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                     for (int u = 0; u < 8; u++) { acc.x += p[u].x; acc.y += p[u].y; acc.z += p[u].z; acc.w += p[u].w; }
                 }
-                if (a.pbias) { float4 b = reinterpret_cast<const float4*>(a.pbias)[f]; acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w; }
+                if (a.pend.bias) { float4 b = reinterpret_cast<const float4*>(a.pend.bias)[f]; acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w; }
                 if (a.pgate) { float4 g = reinterpret_cast<const float4*>(a.pgate + (int64_t)row * a.ldpg)[f]; acc.x *= g.x; acc.y *= g.y; acc.z *= g.z; acc.w *= g.w; }
                 if (a.pscale) { float4 g = reinterpret_cast<const float4*>(a.pscale)[f]; acc.x *= g.x; acc.y *= g.y; acc.z *= g.z; acc.w *= g.w; }
                 v[j].x += acc.x; v[j].y += acc.y; v[j].z += acc.z; v[j].w += acc.w;
@@ -111,7 +111,7 @@ void launch_layernorm(const LnArgs& a, hipStream_t stream) {
                (!a.y || aligned16(a.y)) && (!a.shift || (a.ldmod % 4 == 0 && aligned16(a.shift) && aligned16(a.scale))) &&
                (!a.w || aligned16(a.w)) && (!a.b || aligned16(a.b));
     if (reg) hipLaunchKernelGGL(k_layernorm_reg, dim3((a.rows + 3) / 4), dim3(256), 0, stream, a);
-    else if (a.partial) throw Error(PTTS_EINVAL, "ptts-hip: internal: the fused split-K reduction needs rows of d % 4 == 0, d <= 1024, 16-byte aligned");   // register kernel only
+    else if (a.pend.partial) throw Error(PTTS_EINVAL, "ptts-hip: internal: the fused split-K reduction needs rows of d % 4 == 0, d <= 1024, 16-byte aligned");   // register kernel only
     else hipLaunchKernelGGL(k_layernorm, dim3((a.rows + 3) / 4), dim3(256), 0, stream, a);
 }
 

@@ -131,7 +131,7 @@ struct Model {
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
-    RowRing<JoinRow> join_ring;     // k_join's (join_launch, runtime.cpp)
+    RowRing<JoinRow> join_ring;     // k_join's (join_launch, dsp_device.cpp)
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (trim_launch, dsp_device.cpp)
     RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (tempo_launch, dsp_device.cpp)
     PinnedBuf trim_info;            // generate_joined with a trim: a group's ptts_trim_info records, [max_batch] (read under Model::mu, behind a stream wait)
@@ -236,6 +236,7 @@ struct Batch {
     DevBuf fin_dev;          // StepFinish: what the step's last launch needs for the bookkeeping it carries
 
     ~Batch();
+    void drop_graphs();      // the captured step graphs go (and what their columns were captured with): the next replay captures again
     size_t kv_elem() const { return m->opts.kv == PTTS_KV_BF16 ? 2 : 4; }
     void* kc(int layer) const { return (char*)kcache.p + (size_t)layer * B * m->d.heads * cap * m->d.hd * kv_elem(); }
     void* vc(int layer) const { return (char*)vcache.p + (size_t)layer * B * m->d.heads * cap * m->d.hd * kv_elem(); }
@@ -333,7 +334,14 @@ struct UploadScope { UploadScope(UploadArena& a, hipStream_t s); UploadScope(Upl
 void h2d(void* dst, const void* src, size_t bytes, hipStream_t s);
 void d2h(void* dst, const void* src, size_t bytes, hipStream_t s);
 int resolve_max_steps(const ptts_request& r);                                   // runtime_native_safetensors.go:61-67
+inline int request_lsd(const ptts_request& r) { return r.lsd_steps <= 0 ? 1 : r.lsd_steps; }   // the Euler steps of the request's LSD decode
+// the frames of one utterance the decoder reaches: its RoPE table ends at ROPE_SEQ positions (mimi.go:498)
+inline int mimi_frame_limit(const Desc& d) { return ROPE_SEQ / d.up_stride; }
 void enqueue_step(Batch& b, int lsd, bool use_graph, int nsteps = 1);           // nsteps > 1 only with use_graph
+// the K slices the step's split linear runs a [M][K] x [N][K]^T product in (1: whole); the short prompt's linear2 (batch.cpp) asks as well
+int pick_split(int M, int N, int K, bool w_bf16 = false);
+// the two ldim-wide linears at the head of a step, as the opening kernels take them; false: shapes they do not take (step_core then runs them as step linears)
+bool open_linears(Batch& b, StepOpenLinears& lin);
 void mimi_zero_history(Model& m, MimiWs& w, hipStream_t s);
 // Request staging and result delivery, one copy for generate() (every slot of its batch) and the continuous batch (its newcomers /
 // each group of finished utterances).  The callers keep their own bookkeeping: batch_reset or the slots' host state, the step

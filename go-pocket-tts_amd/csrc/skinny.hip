@@ -55,7 +55,7 @@ constexpr int PRO_LN = 1, PRO_AFFINE = 2, PRO_MOD = 4, PRO_PARTIAL = 8, PRO_ONE 
 template <int WT, bool STAMP, int PRO, int NJ, int CG, bool FIN = false, bool CHAIN = false>
 __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* p_a, int p_lda, int p_ms, int p_n, int p_k, const float* p_part, const float* p_lnw,
                                                  const float* p_lnb, GemmArgs a, SkinnyFuse fu, float* partial, unsigned long long* stamps) {
-    // The nine leading scalars -- copies of a.Wt, a.A, a.amap.ld, a.M | split << 16, a.N, a.K, fu.partial, fu.ln_w, fu.ln_b: 14 dwords, all
+    // The nine leading scalars -- copies of a.Wt, a.A, a.amap.ld, a.M | split << 16, a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b: 14 dwords, all
     // the user SGPRs a kernel can have preloaded (-amdgpu-kernarg-preload-count) -- arrive in registers with the dispatch, so every
     // request on the critical path of the launch leaves before the first scalar-cache round trip for the argument block has
     // returned (that block is cold on every dispatch: ~0.5-1 us).
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
     if (row_ok) {
 #pragma unroll
         for (int j = 0; j < NJ; j++) xr[j] = *reinterpret_cast<const float4*>(p_a + mrow * p_lda + k_begin + kc[j]);
-        if constexpr ((PRO & PRO_PARTIAL) != 0) {   // the first plane of the pending split-K sum (dense [psplit][M][K]: K is the row width here)
+        if constexpr ((PRO & PRO_PARTIAL) != 0) {   // the first plane of the pending split-K sum (dense [splitk][M][K]: K is the row width here)
 #pragma unroll
             for (int j = 0; j < NJ; j++) ps[j] = *reinterpret_cast<const float4*>(p_part + mrow * p_k + kc[j]);
         }
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
         // for fields it never touches (the copies of Wt / A / lda / M / N / K arrive as leading arguments).
         asm volatile("" ::"s"(a.bias), "s"(a.addvec), "s"(a.C), "s"(a.cmap.ld), "s"(a.R), "s"(a.scale), "s"(a.gate), "s"(a.ldg), "s"(a.alpha),
                      "s"(a.tail), "s"(a.epi), "s"(partial));
-        if constexpr ((PRO & PRO_PARTIAL) != 0) asm volatile("" ::"s"(fu.psplit), "s"(fu.pstride), "s"(fu.pbias), "s"(fu.x_out));
+        if constexpr ((PRO & PRO_PARTIAL) != 0) asm volatile("" ::"s"(fu.pend.splitk), "s"(fu.pend.pstride), "s"(fu.pend.bias), "s"(fu.x_out));
         if constexpr ((PRO & PRO_LN) != 0) asm volatile("" ::"s"(fu.eps), "s"(fu.y_out));
         if constexpr ((PRO & PRO_MOD) != 0) asm volatile("" ::"s"(fu.shift), "s"(fu.scale), "s"(fu.ldmod));
         if constexpr (FIN) asm volatile("" ::"s"(fu.fin));
@@ -207,20 +207,20 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
             }
         };
         if constexpr ((PRO & PRO_PARTIAL) != 0) {   // rows += sum_z partial[z] (+ bias); the planes are added in a fixed order
-            // (the AR step hands over [x + (sums_0 + bias)] as the rows and the sums of the other K slices as planes: runtime.cpp step_core)
+            // (the AR step hands over [x + (sums_0 + bias)] as the rows and the sums of the other K slices as planes: step.cpp step_core)
             const float* pp = p_part + mrow * p_k;
             if constexpr ((PRO & PRO_ONE) == 0) {
-                for (int z0 = 1; z0 < fu.psplit; z0 += 3) {   // three more slices per round trip
+                for (int z0 = 1; z0 < fu.pend.splitk; z0 += 3) {   // three more slices per round trip
                     float4 p[3][NJ];
 #pragma unroll
                     for (int u = 0; u < 3; u++) {
-                        const int zz = min(z0 + u, fu.psplit - 1);
+                        const int zz = min(z0 + u, fu.pend.splitk - 1);
 #pragma unroll
-                        for (int j = 0; j < NJ; j++) p[u][j] = *reinterpret_cast<const float4*>(pp + (int64_t)zz * fu.pstride + kc[j]);
+                        for (int j = 0; j < NJ; j++) p[u][j] = *reinterpret_cast<const float4*>(pp + (int64_t)zz * fu.pend.pstride + kc[j]);
                     }
 #pragma unroll
                     for (int u = 0; u < 3; u++) {
-                        if (z0 + u < fu.psplit) {
+                        if (z0 + u < fu.pend.splitk) {
 #pragma unroll
                             for (int j = 0; j < NJ; j++) { ps[j].x += p[u][j].x; ps[j].y += p[u][j].y; ps[j].z += p[u][j].z; ps[j].w += p[u][j].w; }
                         }
@@ -228,10 +228,10 @@ __global__ __launch_bounds__(1024) void k_skinny(const void* p_wt, const float* 
                 }
             }
             load_params();   // after the partials: the register file (128 per lane at 16 waves) does not hold both sets in flight
-            if (fu.pbias) {
+            if (fu.pend.bias) {
 #pragma unroll
                 for (int j = 0; j < NJ; j++) {
-                    const float4 p = *reinterpret_cast<const float4*>(fu.pbias + kc[j]);
+                    const float4 p = *reinterpret_cast<const float4*>(fu.pend.bias + kc[j]);
                     ps[j].x += p.x; ps[j].y += p.y; ps[j].z += p.z; ps[j].w += p.w;
                 }
             }
@@ -569,9 +569,9 @@ bool skinny_supported(const GemmArgs& a, int splitk) {
 bool skinny_fuse_supported(const GemmArgs& a, const SkinnyFuse& f) {
     // the fused prologue needs whole rows in one block: K is the row width, one K slice, dense rows
     return skinny_supported(a, 1) && a.K <= SK_KMAX && a.amap.ld == a.K && a.K % 4 == 0 && (!f.scale || f.ldmod % 4 == 0) &&
-           !f.pgate && (!f.ln_w == !f.ln_b) && (!f.scale == !f.shift) && (!f.partial || f.psplit >= 1) && (f.ln || !(f.ln_w || f.scale)) &&
-           (!(f.partial && f.ln) || f.ln_w) &&   // a pending sum in front of a LayerNorm: instantiated with the affine only (launch_w)
-           (!f.fin || (a.N <= 64 && a.K <= 512 && f.ln && f.scale && !f.ln_w && !f.partial)) &&   // fin: instantiated for the flow net's final layer only
+           !f.pgate && (!f.ln_w == !f.ln_b) && (!f.scale == !f.shift) && (!f.pend.partial || f.pend.splitk >= 1) && (f.ln || !(f.ln_w || f.scale)) &&
+           (!(f.pend.partial && f.ln) || f.ln_w) &&   // a pending sum in front of a LayerNorm: instantiated with the affine only (launch_w)
+           (!f.fin || (a.N <= 64 && a.K <= 512 && f.ln && f.scale && !f.ln_w && !f.pend.partial)) &&   // fin: instantiated for the flow net's final layer only
            (!f.chain || (f.fin && a.N == SO_K && a.epi == EPI_AXPY && !a.tail && f.chain_noise_stride % 2 == 0));   // chain: the frame is the whole row of C (ldim == 32)
 }
 
@@ -587,16 +587,16 @@ static void launch_cg(const GemmArgs& a, const SkinnyFuse& fu, int splitk, float
             grid.x = SK_CHAIN_BX;
             if (g_skinny_ev[0])
                 hipExtLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true, true>), grid, dim3(1024), 0, stream, g_skinny_ev[0], g_skinny_ev[1], 0, a.Wt, a.A, (int)a.amap.ld,
-                                      a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
-            else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true, true>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial,
+                                      a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
+            else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true, true>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial,
                                     (unsigned long long*)nullptr);
             return;
         }
         if (fu.fin) {   // the flow net's final layer with the step's bookkeeping in its epilogue (one column block: grid.x == 1)
             if (g_skinny_ev[0])
                 hipExtLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true>), grid, dim3(1024), 0, stream, g_skinny_ev[0], g_skinny_ev[1], 0, a.Wt, a.A, (int)a.amap.ld,
-                                      a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
-            else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial,
+                                      a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
+            else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG, true>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial,
                                     (unsigned long long*)nullptr);
             return;
         }
@@ -604,18 +604,18 @@ static void launch_cg(const GemmArgs& a, const SkinnyFuse& fu, int splitk, float
     if (SkinnyStampLog* lg = g_skinny_stamp_log) {
         const size_t blocks = (size_t)grid.x * grid.y * grid.z;
         if (lg->used_blocks + blocks <= lg->cap_blocks) {
-            hipLaunchKernelGGL((k_skinny<WBF16, true, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial,
+            hipLaunchKernelGGL((k_skinny<WBF16, true, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial,
                                lg->base + 8 * lg->used_blocks);
             lg->used_blocks += blocks;
             lg->desc.push_back(SkinnyStampLog::Desc{a.M, a.N, a.K, PRO, NJ, CG, (int32_t)blocks, splitk});
             return;
         }
     }
-    if (g_skinny_stamps) hipLaunchKernelGGL((k_skinny<WBF16, true, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial, g_skinny_stamps);
+    if (g_skinny_stamps) hipLaunchKernelGGL((k_skinny<WBF16, true, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial, g_skinny_stamps);
     else if (g_skinny_ev[0])   // hipExtLaunchKernel stamps the dispatch itself: the same interval rocprofv3 reports for the kernel
         hipExtLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG>), grid, dim3(1024), 0, stream, g_skinny_ev[0], g_skinny_ev[1], 0, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N,
-                              a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
+                              a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
+    else hipLaunchKernelGGL((k_skinny<WBF16, false, PRO, NJ, CG>), grid, dim3(1024), 0, stream, a.Wt, a.A, (int)a.amap.ld, a.M | (splitk << 16), a.N, a.K, fu.pend.partial, fu.ln_w, fu.ln_b, a, fu, partial, (unsigned long long*)nullptr);
 }
 
 template <int WBF16, int PRO, int NJ>
@@ -640,12 +640,12 @@ static void launch_pro(const GemmArgs& a, const SkinnyFuse& fu, int splitk, floa
 
 template <int WBF16>
 static void launch_w(const GemmArgs& a, const SkinnyFuse& fu, int splitk, float* partial, dim3 grid, hipStream_t stream) {
-    const int pro = (fu.ln ? PRO_LN : 0) | ((fu.ln && fu.ln_w) ? PRO_AFFINE : 0) | ((fu.ln && fu.scale) ? PRO_MOD : 0) | (fu.partial ? PRO_PARTIAL : 0);
+    const int pro = (fu.ln ? PRO_LN : 0) | ((fu.ln && fu.ln_w) ? PRO_AFFINE : 0) | ((fu.ln && fu.scale) ? PRO_MOD : 0) | (fu.pend.partial ? PRO_PARTIAL : 0);
     switch (pro) {
         case 0: launch_pro<WBF16, 0>(a, fu, splitk, partial, grid, stream); break;
         case PRO_LN | PRO_AFFINE: launch_pro<WBF16, PRO_LN | PRO_AFFINE>(a, fu, splitk, partial, grid, stream); break;
         case PRO_LN | PRO_AFFINE | PRO_PARTIAL:
-            if (fu.psplit == 1) launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_PARTIAL | PRO_ONE>(a, fu, splitk, partial, grid, stream);
+            if (fu.pend.splitk == 1) launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_PARTIAL | PRO_ONE>(a, fu, splitk, partial, grid, stream);
             else launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_PARTIAL>(a, fu, splitk, partial, grid, stream);
             break;
         case PRO_LN | PRO_AFFINE | PRO_MOD: launch_pro<WBF16, PRO_LN | PRO_AFFINE | PRO_MOD>(a, fu, splitk, partial, grid, stream); break;

@@ -180,7 +180,7 @@ void launch_tall(const TallArgs& a, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_rowprep: one wave per row.  x' = x + (sum of `psplit` planes, in order) + pbias -> x_out; LayerNorm(x') (affine) -> bf16 hi / lo planes (+ the f32 rows to y_out).
+// k_rowprep: one wave per row.  x' = x + (sum of pend's planes, in order) + its bias -> x_out; LayerNorm(x') (affine) -> bf16 hi / lo planes (+ the f32 rows to y_out).
 // The arithmetic is k_skinny's fused prologue (PRO_LN | PRO_AFFINE | PRO_PARTIAL), instruction for instruction: a row normalises to the same bits on either path.
 // ------------------------------------------------------------------------------------------------
 template <int NJ>
@@ -194,21 +194,21 @@ __global__ __launch_bounds__(256) void k_rowprep(PrepArgs a) {
     float4 lw[NJ], lb[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; j++) { lw[j] = *reinterpret_cast<const float4*>(a.ln_w + (lane + 64 * j) * 4); lb[j] = *reinterpret_cast<const float4*>(a.ln_b + (lane + 64 * j) * 4); }
-    if (a.partial) {
+    if (a.pend.partial) {
         float4 ps[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; j++) ps[j] = *reinterpret_cast<const float4*>(a.partial + (int64_t)m * a.D + (lane + 64 * j) * 4);
-        for (int zz = 1; zz < a.psplit; zz++) {
+        for (int j = 0; j < NJ; j++) ps[j] = *reinterpret_cast<const float4*>(a.pend.partial + (int64_t)m * a.D + (lane + 64 * j) * 4);
+        for (int zz = 1; zz < a.pend.splitk; zz++) {
 #pragma unroll
             for (int j = 0; j < NJ; j++) {
-                const float4 p = *reinterpret_cast<const float4*>(a.partial + (int64_t)zz * a.pstride + (int64_t)m * a.D + (lane + 64 * j) * 4);
+                const float4 p = *reinterpret_cast<const float4*>(a.pend.partial + (int64_t)zz * a.pend.pstride + (int64_t)m * a.D + (lane + 64 * j) * 4);
                 ps[j].x += p.x; ps[j].y += p.y; ps[j].z += p.z; ps[j].w += p.w;
             }
         }
-        if (a.pbias) {
+        if (a.pend.bias) {
 #pragma unroll
             for (int j = 0; j < NJ; j++) {
-                const float4 p = *reinterpret_cast<const float4*>(a.pbias + (lane + 64 * j) * 4);
+                const float4 p = *reinterpret_cast<const float4*>(a.pend.bias + (lane + 64 * j) * 4);
                 ps[j].x += p.x; ps[j].y += p.y; ps[j].z += p.z; ps[j].w += p.w;
             }
         }
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void k_rowprep(PrepArgs a) {
 bool rowprep_supported(const PrepArgs& a) {
     return a.x && a.ln_w && a.ln_b && a.yh && a.yl && a.M > 0 && (a.D == 512 || a.D == 1024) && a.ldx % 4 == 0 && a.ldy % 4 == 0 && aligned16(a.x) && aligned16(a.ln_w) &&
            aligned16(a.ln_b) && (reinterpret_cast<uintptr_t>(a.yh) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.yl) & 7) == 0 &&
-           (!a.partial || (a.psplit >= 1 && aligned16(a.partial) && a.pstride % 4 == 0)) && (!a.pbias || aligned16(a.pbias)) && (!a.x_out || aligned16(a.x_out)) &&
+           (!a.pend.partial || (a.pend.splitk >= 1 && aligned16(a.pend.partial) && a.pend.pstride % 4 == 0)) && (!a.pend.bias || aligned16(a.pend.bias)) && (!a.x_out || aligned16(a.x_out)) &&
            (!a.y_out || aligned16(a.y_out));
 }
 

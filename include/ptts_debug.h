@@ -79,7 +79,7 @@ typedef struct ptts_step_linear_args {
 int ptts_debug_step_linear(const ptts_step_linear_args* a);
 
 /* The step attention (csrc/attn_step.hip: k_attn_step, and k_attention behind it for caches beyond one burst) stand-alone: ONE launch_attention call with
- * AttnArgs filled as the AR step fills them (runtime.cpp step_core: fused_step, context -1, d_model = heads * 64, max_keys = cap), on host operands.
+ * AttnArgs filled as the AR step fills them (step.cpp step_core: fused_step, context -1, d_model = heads * 64, max_keys = cap), on host operands.
  *   qkv [rows][qkv_ld] (q | k | v, d_model each), cos_t / sin_t [cap][32], seg_len / active / pre_len / voice_of_row [rows];
  *   pre_k / pre_v [n_pre <= 4]: prefix buffers [layers][heads][pre_rows[i]][64] in the cache format (bf16 bits or f32); voice_of_row[r] names the buffer
  *   row r's prefix pointers are set to (-1: null pointers); the pre_k / pre_v / pre_len device arrays are always passed, as the step passes them;
@@ -109,10 +109,10 @@ int ptts_debug_attn_step(const ptts_attn_step_args* a);
 int ptts_debug_attn_step_rounds(int32_t keys, int32_t kv_bf16, int32_t* keys_per_round);
 
 /* The window attention (csrc/attn_window.hip: k_attn_window, k_attn_window_lds) stand-alone: ONE launch on host operands, AttnArgs filled as the callers do.
- * Dense (ragged 0; runtime.cpp mimi_range, encoder.cpp): qkv [segs][T1][ld] f32 holds q | k | v at columns 0, D, 2 D (D = heads * 64).  The chunk (t0, CT) is
+ * Dense (ragged 0; mimi_decode.cpp mimi_range, encoder.cpp): qkv [segs][T1][ld] f32 holds q | k | v at columns 0, D, 2 D (D = heads * 64).  The chunk (t0, CT) is
  *   launched: q = qkv + t0 ld with q_rows_per_batch CT and q_batch_stride T1 ld; k / v = qkv + D / 2 D with k_seg_stride T1 ld, k_head_stride 64,
  *   k_row_stride ld; rows_per_seg CT, pos_base t0, context (> 0), rows = segs CT.
- * Ragged (ragged 1; runtime.cpp's prompt prefill): qkv is the packed query rows [rows][ld]; k, v are caches [segs][heads][cap][64] as raw bytes (f32, or bf16
+ * Ragged (ragged 1; batch.cpp's prompt prefill): qkv is the packed query rows [rows][ld]; k, v are caches [segs][heads][cap][64] as raw bytes (f32, or bf16
  *   bits with kv_bf16); rag_off [segs + 1] (rag_off[0] = 0, rag_off[segs] = rows), rag_pos0 [segs]; row_seg / row_pos are derived and passed as the prefill
  *   passes them; rows_per_seg = the longest segment; context: -1 as in production, or a window.
  * out [rows][out_ld] is filled with 0xff bytes before the launch and returned whole.
@@ -241,7 +241,7 @@ int ptts_debug_kweighting(int32_t sample_rate, double out[10]);
  * call is clean.  Nothing in the product sets it. */
 int ptts_debug_flow_cluster_inject(ptts_model* m, int32_t block);
 
-/* k_flow_cluster (csrc/flow_cluster.hip) stand-alone on host operands: a sequence of launches, FlowClusterArgs filled as runtime.cpp step_flow fills them.
+/* k_flow_cluster (csrc/flow_cluster.hip) stand-alone on host operands: a sequence of launches, FlowClusterArgs filled as step.cpp step_flow fills them.
  *   fx [rows][512]; ada [rows][ldmod]: block r's shift | scale | gate at columns 3 r 512; ln_w, ln_b, b0, b2 [depth][512]; eps [depth];
  *   w0, w2 [depth][512][512] f32 row-major, rounded to bf16 and tiled by the loader's pack_step_tiled.
  *   launch_rows [n_launch]: the launches run one after another on ONE granule buffer and ONE set of tag words -- both zeroed as the batch set-up zeroes them,

@@ -2,7 +2,7 @@
 numpy on the same operands -- every instantiation (KV format x load rounds NI = 1..16), every slot this step's own key can take, every prefix boundary.
 
 What it replaces: StreamingMultiheadAttention's one-token step (attention.go:402-484): RoPE of q and k at the cache offset (rope.go:81-105), append of k and v,
-softmax(q K^T / 8) V over the keys 0..offset.  The hook (ptts_debug_attn_step) fills AttnArgs as the step does (runtime.cpp step_core), calls launch_attention --
+softmax(q K^T / 8) V over the keys 0..offset.  The hook (ptts_debug_attn_step) fills AttnArgs as the step does (step.cpp step_core), calls launch_attention --
 so the dispatch is under test too -- and returns the output (pre-filled with 0xff bytes) and both caches whole.  It refuses, before anything is uploaded, every
 operand that could make the kernel leave the hook's buffers (test_refusals_before_any_launch).
 

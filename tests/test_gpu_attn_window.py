@@ -4,10 +4,10 @@ the test controls -- every launch form, with the strides, heads, segments and po
 What it replaces: mimiTransformerLayer.selfAttention (mimi.go:365-441: softmax(q K^T / 8) V over the keys p - context + 1 .. p of the query's own utterance and
 head) for the Mimi decoder and encoder, and the prompt prefill's attention over a slot's cache rows 0 .. p (flow_transformer.go:749-771).  The hook
 (ptts_debug_attn_window) fills AttnArgs as the callers do:
-  dense  (runtime.cpp mimi_range, encoder.cpp): ONE buffer [segs][T1][ld] holds q | k | v at columns 0, D, 2 D; a chunk (t0, CT) of every segment is launched with
+  dense  (mimi_decode.cpp mimi_range, encoder.cpp): ONE buffer [segs][T1][ld] holds q | k | v at columns 0, D, 2 D; a chunk (t0, CT) of every segment is launched with
          pos_base = t0, k_row_stride = q_ld = ld, k_head_stride = 64 -- form 0 through launch_attention (today k_attn_window_lds<4>), 1 k_attn_window<false, false>
          (dispatched in production only beyond 2^31 elements per segment: reachable through this hook alone), 2 k_attn_window_lds<4>;
-  ragged (runtime.cpp, the prompt prefill): packed query rows, caches [segs][heads][cap][64] in f32 or bf16, rag_off / rag_pos0 -- form 0, k_attn_window<., true>.
+  ragged (batch.cpp, the prompt prefill): packed query rows, caches [segs][heads][cap][64] in f32 or bf16, rag_off / rag_pos0 -- form 0, k_attn_window<., true>.
 Geometry: 2 heads and 2 segments (dense), 3 heads and 1-5 segments (ragged), ld = 3 D + 4, out_ld = D + 4: every stride differs from every other.
 
 Reference: f64, per row the keys max(0, p - ctx + 1) .. p of its own segment and head; a bf16 cache is decoded exactly (no cache-format term in the tolerance).

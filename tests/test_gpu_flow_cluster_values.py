@@ -4,7 +4,7 @@ What it replaces: flowResBlock.Forward x depth (flow_net.go:116-172); one block,
     y   = (LN(x) ln_w + ln_b) (1 + scale) + shift          LN: biased variance over the 512 columns, the block's own eps (linear.go:295-309)
     h   = silu(y W0^T + b0)
     out = x + gate (h W2^T + b2)
-The hook (ptts_debug_flow_cluster) fills FlowClusterArgs as runtime.cpp step_flow does and runs a SEQUENCE of launches on one granule buffer and one set of
+The hook (ptts_debug_flow_cluster) fills FlowClusterArgs as step.cpp step_flow does and runs a SEQUENCE of launches on one granule buffer and one set of
 tag words; on the device fx, the outputs and ada carry NaN slack rows, every output is 0xff before the launch and comes back whole.
 
 Inputs (operands()), unless a case says otherwise: x ~ 1.5 N + 0.2; ln_w ~ 1 + 0.1 N, ln_b ~ 0.1 N; shift, scale, gate ~ 0.5 N per row and block; weights

@@ -1,4 +1,4 @@
-"""Joined synthesis on the GPU (go-pocket-tts_amd/csrc/join.hip, runtime.cpp generate_joined; include/ptts.h ptts_generate_joined; DESIGN.md
+"""Joined synthesis on the GPU (go-pocket-tts_amd/csrc/join.hip, generate.cpp generate_joined; include/ptts.h ptts_generate_joined; DESIGN.md
 section 8, N3): k_join gives ptts_join's bits for every shape and alignment; a joined call is the join of the same requests' audio from one
 ptts_generate call, within a group and across groups; the chain runs once over the whole text and gives the host chain's result on the joined
 audio; the egress is the egress of one row; refusals launch nothing; a cancelled chunk fails the call and is named."""

@@ -1,4 +1,4 @@
-"""Streamed joined synthesis on the GPU (runtime.cpp generate_joined, JoinStream; include/ptts.h ptts_generate_joined_streamed; DESIGN.md section 8,
+"""Streamed joined synthesis on the GPU (generate.cpp generate_joined, JoinStream; include/ptts.h ptts_generate_joined_streamed; DESIGN.md section 8,
 N3): a joined call that hands its audio over group by group gives the bytes of the call that does not, for every chain it may carry, every join
 and every egress; the hand-overs tile the result in order and their boundaries are the documented P_g; a smaller first group is the host
 statement on the chunks of the same groups; without a callback the call launches what ptts_generate_joined launches; what needs the whole text

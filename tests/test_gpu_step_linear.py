@@ -53,7 +53,7 @@ def plan(M, N, K, S, wfmt):
 
 
 def pick_split(M, N, K, w_bf16):
-    """runtime.cpp pick_split."""
+    """step.cpp pick_split."""
     if K <= 1024:
         return 1
     if w_bf16 and M > 32 and K >= 4096 and K % 2048 == 0 and ((N + 31) // 32) * ((M + 15) // 16) * (K // 2048) >= 200:

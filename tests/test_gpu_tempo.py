@@ -1,4 +1,4 @@
-"""The speaking rate on the GPU (go-pocket-tts_amd/csrc/tempo.hip, runtime.cpp generate_joined; include/ptts.h ptts_tempo_opts; DESIGN.md
+"""The speaking rate on the GPU (go-pocket-tts_amd/csrc/tempo.hip, generate.cpp generate_joined; include/ptts.h ptts_tempo_opts; DESIGN.md
 section 8, N3): ptts_tempo_rows gives ptts_tempo_apply's bits on the crafted rows, speeds mixed in one call, across the 256-row table boundary;
 a joined call with a tempo is the host chain trim -> tempo -> join -> chain -> egress of the same requests' audio from one generate_batch call,
 bit for bit, within a group and across groups; one launch of each kernel per group and none without a tempo; refusals launch nothing.

@@ -1,4 +1,4 @@
-"""Silence control on the GPU (go-pocket-tts_amd/csrc/trim.hip, runtime.cpp generate_joined; include/ptts.h ptts_trim_opts; DESIGN.md section
+"""Silence control on the GPU (go-pocket-tts_amd/csrc/trim.hip, generate.cpp generate_joined; include/ptts.h ptts_trim_opts; DESIGN.md section
 8, N3): ptts_trim_rows gives ptts_trim_apply's samples and records bit for bit on the crafted rows; a joined call with a trim is the host join
 of the host trim of the same requests' audio from one generate_batch call, within a group and across groups; the chain reads the trimmed,
 joined audio; one launch of each kernel per group and none without a trim; refusals launch nothing; one request is the trimmed utterance.

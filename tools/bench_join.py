@@ -1,4 +1,4 @@
-"""Joined synthesis (join.hip k_join, runtime.cpp generate_joined) against the route a host had before it, for the same
+"""Joined synthesis (join.hip k_join, generate.cpp generate_joined) against the route a host had before it, for the same
 bytes: one text of 12 chunks of 10 s, full-size synthetic checkpoint, bf16, graph step, one device voice; loudness -16 LUFS, a limiter at -6 dBFS,
 8 kHz mu-law.  Route A: generate_batch of the chunks, the concatenation on the host, ptts_loudness_normalize_rows and ptts_dsp_rows (the limiter) on
 it, ptts_resample, ptts_pcm_encode -- four round trips of the text over PCIe behind the first.  Route B: one generate_joined call.  Every call

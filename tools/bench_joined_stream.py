@@ -1,4 +1,4 @@
-"""Streamed joined synthesis (runtime.cpp generate_joined, JoinStream; include/ptts.h ptts_generate_joined_streamed): the
+"""Streamed joined synthesis (generate.cpp generate_joined, JoinStream; include/ptts.h ptts_generate_joined_streamed): the
 time to first audio and the total time of one text of three full groups (3 x max_batch chunks), full-size synthetic checkpoint, bf16, graph
 step, one device voice, the header's telephony chain -- compressor, DC block, a 300-3400 Hz equaliser, fades, 8 kHz mu-law.  Per call: the wall
 time from the call's start until the first pcm_callback returns, and until the call returns, for first_group 0 (max_batch), 4 and 1; and the

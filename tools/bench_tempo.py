@@ -1,4 +1,4 @@
-"""The speaking rate of a joined call's parts (tempo.hip k_tempo_plan / k_tempo_store, runtime.cpp generate_joined),
+"""The speaking rate of a joined call's parts (tempo.hip k_tempo_plan / k_tempo_store, generate.cpp generate_joined),
 full-size synthetic checkpoint, bf16, graph step, one device voice.  Legs, run interleaved in one process, whole-call wall clock, median of
 --runs rounds after --warmup: (a) / (b) ptts_tempo_rows on 64 x 10 s host rows (the results of one plain batch, each scaled to a peak of 0.9)
 at speed 800 and 1250 -- upload, the two kernels, the time-scaled rows back; (c) one generate_joined call of a text of 12 chunks of 10 s without a

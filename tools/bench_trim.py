@@ -1,4 +1,4 @@
-"""Silence control of a joined call's parts (trim.hip k_trim_mark / k_trim_carry / k_trim_store, runtime.cpp generate_joined; DESIGN.md section 8
+"""Silence control of a joined call's parts (trim.hip k_trim_mark / k_trim_carry / k_trim_store, generate.cpp generate_joined; DESIGN.md section 8
 N3), full-size synthetic checkpoint, bf16, graph step, one device voice.  Legs, run interleaved in one process, whole-call wall clock, median of
 --runs rounds after --warmup: (a) ptts_trim_rows on 64 x 10 s host rows (the results of one plain batch, each scaled to a peak of 0.9; upload,
 the three kernels, the records back, the kept samples back); (b) ptts_limit_rows on the same rows -- the same kind of round trip with four
