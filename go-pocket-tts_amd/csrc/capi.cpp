@@ -1101,6 +1101,7 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
         std::string e = dsp_resolve(opts, &spec);
         if (e.empty()) e = dsp_trim_refusal(spec);   // the output rows have the input's length
         if (e.empty()) e = dsp_tempo_refusal(spec);
+        if (e.empty()) e = dsp_pitch_refusal(spec);
         if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
         for (int i = 0; i < rows; i++) check.row(i, n[i], !in[i] || !out[i]);
         if (!spec.any()) {   // nothing switched on: a copy, no lock, no launch
@@ -1230,6 +1231,61 @@ int ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t) {
     }
     if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.tempo = v.tempo; e->v.tmp = v.tmp; }))
         return fail(strfmt("tempo: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
+    return PTTS_OK;
+}
+
+// the device form of ptts_pitch_apply on host rows: the launches of a joined call's pitch and of the tempo behind it; a row with neither is copied on
+// the host.  p[i] null: the tempo alone, as ptts_tempo_rows
+int ptts_pitch_rows(ptts_model* h, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows,
+                    float* const* out, int64_t* n_out) {
+    return guard([&] {
+        Model& m = model_of(h);
+        const RowsCheck check{"pitch"};
+        check.args(rows, !p || !t || !in || !n || !out || !n_out);
+        std::vector<PitchScan> pitches((size_t)rows);
+        std::vector<TempoScan> tempos((size_t)rows);
+        std::vector<PitchStage> stage((size_t)rows, PitchStage{nullptr, nullptr});
+        for (int i = 0; i < rows; i++) {
+            check.row(i, n[i], !in[i] || !out[i]);
+            const auto refuse = [&](const std::string& e) { throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e); };
+            std::string e = p[i] ? pitch_opts_error(p[i]) : std::string();
+            if (e.empty() && t[i]) e = tempo_opts_error(t[i]);
+            if (!e.empty()) refuse(e);
+            int32_t speed = t[i] ? t[i]->speed_permille : 1000;
+            bool tempo = t[i] != nullptr;
+            if (p[i]) {   // the pair resolves to the effective speed, and the tempo at 1000 is the identity
+                e = pitch_speed_error(p[i]->pitch_permille, speed, &speed);
+                if (e.empty()) e = pitch_length_error(n[i], p[i]->pitch_permille, speed);
+                if (!e.empty()) refuse(e);
+                tempo = speed != 1000;
+                if (p[i]->pitch_permille != 1000) {
+                    pitches[(size_t)i] = pitch_design(*p[i]);
+                    stage[(size_t)i].pitch = &pitches[(size_t)i];
+                }
+            } else if (n[i] >= kTempoMaxSamples) {
+                refuse(strfmt("tempo: %lld samples, a row must stay below 2^31 - %d", (long long)n[i], kTempoRadius));
+            }
+            if (tempo) {
+                tempos[(size_t)i].speed = speed;
+                stage[(size_t)i].tempo = &tempos[(size_t)i];
+            }
+            if (n[i] > 0 && in[i] == out[i] && (stage[(size_t)i].pitch || stage[(size_t)i].tempo)) refuse("pitch: out is in");
+        }
+        if (rows > 0) pitch_rows_device(m, stage.data(), in, n, rows, out, n_out);
+    });
+}
+
+// the pitch of a joined call's parts, attached to the handle (pitch.cpp checks and designs it, and stays a file that builds without HIP)
+int ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p) {
+    DspExt v;
+    if (p) {
+        const std::string err = pitch_opts_error(p);
+        if (!err.empty()) return fail(err);
+        v.pitch = true;
+        v.pit = pitch_design(*p);
+    }
+    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.pitch = v.pitch; e->v.pit = v.pit; }))
+        return fail(strfmt("pitch: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
     return PTTS_OK;
 }
 

@@ -274,6 +274,7 @@ int ptts_debug_dsp_windows(ptts_model* h, const float* const* in, const int64_t*
         std::string e = dsp_resolve(opts, &spec);
         if (e.empty()) e = dsp_trim_refusal(spec);
         if (e.empty()) e = dsp_tempo_refusal(spec);
+        if (e.empty()) e = dsp_pitch_refusal(spec);
         if (e.empty()) e = dsp_window_refusal(spec);   // only the causal stages, as the streamed joined call words it
         if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
         for (int i = 0; i < rows; i++)

@@ -2,7 +2,7 @@
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
 // them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the same for
-// the trim (trim.hip) and the tempo (tempo.hip) of a joined call's parts.
+// the trim (trim.hip), the tempo (tempo.hip) and the pitch (pitch.hip, with its one table image per model) of a joined call's parts.
 #include <cmath>
 
 #include "row_tables.h"
@@ -410,6 +410,121 @@ void tempo_rows_device(Model& m, const TempoScan* const* design, const float* co
     if (tr.empty()) return;
     tempo_launch(m, tr, key, s);
     for (int i : row_of) buf.download(rows + i, out[i], s);
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the pitch (pitch.hip; pitch.h has the rule) ----
+
+PitchImage::~PitchImage() {
+    if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
+    if (staged) (void)hipHostFree(staged);
+}
+
+namespace {
+// the table's image on the device: one per model whatever the pitches.  First use: made from pitch.cpp's table and queued on s from page-locked
+// memory, nothing waits on the host; launches on s follow it, another stream waits for `ready` (as rate_filter, resample.cpp)
+const float* pitch_image(Model& m, hipStream_t s) {
+    if (m.pitch_image) {
+        if (m.pitch_image->up != s) PTTS_HIP(hipStreamWaitEvent(s, m.pitch_image->ready, 0));
+        return m.pitch_image->image.as<float>();
+    }
+    std::unique_ptr<PitchImage> f(new PitchImage());
+    constexpr size_t kBytes = (size_t)kPitchImage * 2 * sizeof(float);
+    PTTS_HIP(hipHostMalloc((void**)&f->staged, kBytes, hipHostMallocDefault));
+    std::memset(f->staged, 0, kBytes);
+    const float* const h = pitch_table_h();
+    const float* const hd = pitch_table_hd();
+    for (int q = 0; q < kPitchEntries; q++) {
+        f->staged[2 * (size_t)pitch_image_at(q)] = h[q];
+        f->staged[2 * (size_t)pitch_image_at(q) + 1] = hd[q];
+    }
+    f->image.ensure(kBytes);
+    PTTS_HIP(hipMemcpyAsync(f->image.p, f->staged, kBytes, hipMemcpyHostToDevice, s));
+    PTTS_HIP(hipEventCreateWithFlags(&f->ready, hipEventDisableTiming));
+    PTTS_HIP(hipEventRecord(f->ready, s));
+    f->up = s;
+    m.pitch_image = std::move(f);
+    return m.pitch_image->image.as<float>();
+}
+}  // namespace
+
+void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const PitchScan*>& key, hipStream_t s) {
+    for (size_t i = 0; i < rows.size(); i++) {
+        rows[i].n_out = pitch_resample_length(rows[i].n, key[i]->p);
+        if (rows[i].n < 0 || rows[i].n_out >= kTempoMaxSamples)
+            throw Error(PTTS_EINVAL, strfmt("ptts-hip: pitch: row %zu has %lld samples and %lld resampled, a row must stay below 2^31 - %d", i, (long long)rows[i].n,
+                                            (long long)rows[i].n_out, kTempoRadius));
+    }
+    const float* const image = pitch_image(m, s);
+    launch_tables(m.pitch_ring, rows, key, kPitchMaxDesigns, same_bytes<PitchScan>, &PitchRow::design, "pitch", s,
+                  [&](size_t first, int k, const PitchRow* rows_dev, int, const PitchScan* designs_dev) {
+        int64_t tiles = 0;   // of the OUTPUT
+        for (int i = 0; i < k; i++) tiles = std::max(tiles, (rows[first + (size_t)i].n_out + kPitchTile - 1) / kPitchTile);
+        launch_pitch(rows_dev, k, (int)tiles, designs_dev, image, s);
+    });
+}
+
+void pitch_rows_device(Model& m, const PitchStage* stage, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    // the rows, then their resampled forms, then their time-scaled forms; a row takes bytes only for the steps it has
+    const size_t R = (size_t)rows;
+    std::vector<size_t> bytes(R * 3, 0);
+    std::unique_ptr<bool[]> skip(new bool[R * 3 + 1]);
+    std::vector<int64_t> n_r(R);
+    for (size_t i = 0; i < R; i++) {
+        const PitchStage& st = stage[i];
+        n_r[i] = st.pitch ? pitch_resample_length(n[i], st.pitch->p) : std::max<int64_t>(n[i], 0);
+        n_out[i] = st.tempo ? tempo_length(n_r[i], st.tempo->speed) : n_r[i];
+        const bool on = (st.pitch || st.tempo) && n_out[i] > 0;
+        skip[i] = !on;
+        skip[R + i] = !(on && st.pitch);
+        skip[2 * R + i] = !(on && st.tempo);
+        if (!skip[i]) bytes[i] = (size_t)n[i] * sizeof(float);
+        if (!skip[R + i]) bytes[R + i] = (size_t)n_r[i] * sizeof(float);
+        if (!skip[2 * R + i]) bytes[2 * R + i] = (size_t)n_out[i] * sizeof(float);
+    }
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
+    std::vector<PitchRow> pr;
+    std::vector<const PitchScan*> pkey;
+    std::vector<TempoRow> tr;
+    std::vector<const TempoScan*> tkey;
+    std::vector<std::pair<int, int>> back;   // (the packed row that holds the result, the caller's row)
+    for (int i = 0; i < rows; i++) {
+        const PitchStage& st = stage[i];
+        if (skip[(size_t)i]) {   // nothing to do on the device: a copy, or an empty result
+            if (!st.pitch && !st.tempo && n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            continue;
+        }
+        buf.upload(i, in[i], s);
+        const float* z = (const float*)buf.row(i);
+        int at = i;
+        if (st.pitch) {
+            PitchRow r{};
+            r.src = z;
+            r.dst = (float*)buf.row(rows + i);
+            r.n = n[i];
+            pr.push_back(r);
+            pkey.push_back(st.pitch);
+            z = r.dst;
+            at = rows + i;
+        }
+        if (st.tempo) {
+            TempoRow r{};
+            r.src = z;
+            r.dst = (float*)buf.row(2 * rows + i);
+            r.n = n_r[(size_t)i];
+            tr.push_back(r);
+            tkey.push_back(st.tempo);
+            at = 2 * rows + i;
+        }
+        back.emplace_back(at, i);
+    }
+    if (back.empty()) return;
+    if (!pr.empty()) pitch_launch(m, pr, pkey, s);
+    if (!tr.empty()) tempo_launch(m, tr, tkey, s);
+    for (const auto& b : back) buf.download(b.first, out[b.second], s);
     PTTS_HIP(hipStreamSynchronize(s));
 }
 

@@ -25,6 +25,8 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->trm = ext.trm;
     out->tempo = ext.tempo;
     out->tmp = ext.tmp;
+    out->pitch = ext.pitch;
+    out->pit = ext.pit;
     return std::string();
 }
 

@@ -16,6 +16,7 @@ struct DspSpec {
     bool limit = false; LimScan lim{};                 // the limiter (limiter.h): behind the fades, in front of the true-peak ceiling
     bool trim = false; TrimScan trm{};                 // the trim of a joined call's parts (trim.h): no stage of the chain, neither rest() nor any() counts it
     bool tempo = false; TempoScan tmp{};               // the tempo of a joined call's parts (tempo.h), behind the trim: no stage of the chain either
+    bool pitch = false; PitchScan pit{};               // the pitch of a joined call's parts (pitch.h), between the trim and the tempo: no stage of the chain either
     bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };
@@ -66,6 +67,10 @@ inline std::string dsp_window_refusal(const DspSpec& s) {
     const char* f = s.normalize ? "normalize" : s.loud ? "loudness" : s.true_peak ? "ext: true_peak" : nullptr;
     if (f) return strfmt("stream: %s needs the whole text; it cannot be combined with pcm_callback", f);
     return s.limit ? std::string("stream: ext: limiter looks ahead of the samples it hands over; it cannot be combined with pcm_callback yet") : std::string();
+}
+// ... and one with a pitch, likewise
+inline std::string dsp_pitch_refusal(const DspSpec& s) {
+    return s.pitch ? std::string("dsp: ext: pitch changes a row's length; it is served by ptts_generate_joined and ptts_pitch_rows") : std::string();
 }
 // whether o switches anything on, without an error: what dsp_resolve's spec says with any(), except that an eq counts unseen (so a dead one is
 // active, and refused where the row is resolved) and an ext that is not live counts for nothing.  One registry look-up at the most: it is

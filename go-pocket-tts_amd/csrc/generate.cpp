@@ -218,6 +218,8 @@ struct JoinSink {
     ptts_trim_info* info = nullptr;   // page-locked, [max_batch]: a group's records (Model::trim_info)
     bool tempo = false;           // ... and a tempo (tempo.h): every part goes through k_tempo_* behind the trim and in front of k_join, and its
     TempoScan tmp{};              // length is tempo_length of what the trim left: host arithmetic, nothing comes back
+    bool pitch = false;           // ... and a pitch other than 1000 (pitch.h): every part goes through k_pitch_resample between the two.  The pair
+    PitchScan pit{};              // (speed, pitch) was resolved to the effective speed beforehand: `tmp` carries it, and `tempo` is off at 1000
 };
 
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
@@ -588,7 +590,7 @@ void Chunk::deliver() {
 
 // generate_joined's delivery (behind the fault check: a group that is run again has joined nothing yet): the parts' records; the decode of
 // the whole group into the decoder's buffer; with a trim (trim.h), the rows' trimmed forms and their lengths; with a tempo (tempo.h), their
-// time-scaled forms; one k_join table that copies the
+// time-scaled forms, and with a pitch (pitch.h) their resampled forms in front of that; one k_join table that copies the
 // group's rows behind what the text's row holds.  A seam inside
 // the group is computed by the row behind it, which reads its predecessor's tail in the decoder's buffer.  The group's first row has its
 // predecessor in an earlier group, whose buffer is gone: that group stored the tail unfaded, and this row fades it where it lies.
@@ -631,8 +633,24 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
         part0 = kept;
         mark("trim");
     }
-    // ... and with a tempo their time-scaled forms, in a buffer whose row stride holds the longest a decoded row can become
+    // ... with a pitch their resampled forms, in a buffer whose row stride holds the longest a decoded row can become
     int64_t stride = (int64_t)T * spf;
+    if (join->pitch) {
+        const int64_t wide = std::max(stride, pitch_resample_length(stride, join->pit.p));
+        float* const shifted = m.work(WORK_PITCH, std::max<size_t>((size_t)B * (size_t)wide, 1) * sizeof(float)).as<float>();
+        std::vector<PitchRow> pr((size_t)B);
+        for (int i = 0; i < B; i++) {
+            pr[(size_t)i].src = part0 + (size_t)i * (size_t)stride;
+            pr[(size_t)i].dst = shifted + (size_t)i * (size_t)wide;
+            pr[(size_t)i].n = len[(size_t)i];
+        }
+        pitch_launch(m, pr, std::vector<const PitchScan*>((size_t)B, &join->pit), s);
+        for (int i = 0; i < B; i++) len[(size_t)i] = pr[(size_t)i].n_out;
+        part0 = shifted;
+        stride = wide;
+        mark("pitch");
+    }
+    // ... and with a tempo their time-scaled forms, likewise
     if (join->tempo) {
         const int64_t wide = std::max(stride, tempo_length(stride, join->tmp.speed));
         float* const scaled = m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide, 1) * sizeof(float)).as<float>();
@@ -699,6 +717,7 @@ std::string request_error(const Desc& d, const ptts_request& q) {   // the argum
         std::string e = dsp_resolve(q.dsp, &spec);
         if (e.empty()) e = dsp_trim_refusal(spec);   // a request's result buffers are sized before the decode
         if (e.empty()) e = dsp_tempo_refusal(spec);
+        if (e.empty()) e = dsp_pitch_refusal(spec);
         if (!e.empty()) return "generate: " + e;
         if (q.pcm_callback) {   // the peak and the end are not known when samples are handed over; the filter and the fade in are refused with it for now
             const char* f = q.dsp->normalize ? "normalize" : q.dsp->fade_out_ms > 0 ? "fade_out_ms" : q.dsp->dc_block ? "dc_block" : q.dsp->fade_in_ms > 0 ? "fade_in_ms" : q.dsp->eq ? "eq" : q.dsp->ext ? "ext" : nullptr;
@@ -901,6 +920,15 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         sink.trm = spec.trm;
         sink.tempo = spec.tempo;
         sink.tmp = spec.tmp;
+        if (spec.pitch) {   // the pair (speed, pitch) becomes the tempo's effective speed; either step may be the identity, and then it is not run
+            int32_t E = 0;
+            e = pitch_speed_error(spec.pit.p, spec.tempo ? spec.tmp.speed : 1000, &E);
+            if (!e.empty()) refuse("join: " + e);
+            sink.pitch = spec.pit.p != 1000;
+            sink.pit = spec.pit;
+            sink.tempo = E != 1000;
+            sink.tmp.speed = E;
+        }
     }
     if (streamed) {   // window after window only the causal stages run
         if (o.loudness) dsp_spec_loudness(spec, nullptr);
@@ -918,8 +946,11 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (f) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d sets %s, which belongs in the join options (ptts_join_opts) of a joined call", i, f)); }
         const int l = request_lsd(q);
         if (l != lsd) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d has lsd_steps %d and request 0 has %d: the groups would leave text order", i, l, lsd)); }
-        const int64_t budget = (int64_t)std::min(resolve_max_steps(q), mimi_frame_limit(d)) * spf;   // (the trim only shortens; tempo_length is monotone)
-        bound += (sink.tempo ? std::max(budget, tempo_length(budget, sink.tmp.speed)) : budget) + (i ? sink.lens.gap : 0);
+        // (the trim only shortens; pitch_resample_length and tempo_length are monotone)
+        const int64_t budget = (int64_t)std::min(resolve_max_steps(q), mimi_frame_limit(d)) * spf;
+        const int64_t shifted = sink.pitch ? pitch_resample_length(budget, sink.pit.p) : budget;
+        const int64_t scaled = sink.tempo ? tempo_length(shifted, sink.tmp.speed) : shifted;
+        bound += std::max(budget, std::max(shifted, scaled)) + (i ? sink.lens.gap : 0);
     }
     if (bound >= kJoinMaxSamples) refuse(strfmt("join: the step budgets allow %lld samples, the joined length must stay below 2^31", (long long)bound));
     ptts_request eg{};   // the chain and the egress of the joined row, as a request states its own: results_deliver serves it like one

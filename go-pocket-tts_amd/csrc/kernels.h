@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "limiter.h"
+#include "pitch.h"
 #include "tempo.h"
 #include "trim.h"
 
@@ -470,6 +471,30 @@ static_assert(sizeof(TempoRow) == 48, "a turn of the tempo ring holds 256 of the
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil(n_out / kDspTile) of a row (0: empty rows only, nothing is launched);
 // designs_dev: the table's designs
 void launch_tempo(const TempoRow* rows_dev, int n, int max_tiles, const TempoScan* designs_dev, hipStream_t stream);
+
+// The pitch of the parts of a joined text, its resampling step (pitch.hip, pitch.h has the rule, pitch.cpp the host statement; DESIGN.md section 8,
+// N3): behind the trim and in front of the tempo, from one buffer into another.  k_pitch_resample, every tile of kPitchTile OUTPUT samples.  A
+// table's distinct designs (at most kPitchMaxDesigns: p may differ from row to row) travel behind its rows.
+constexpr int kPitchMaxDesigns = 16;
+constexpr size_t kPitchScanBytes = 16;
+static_assert(sizeof(PitchScan) == kPitchScanBytes, "the pitch ring's tail (runtime.h) is sized by it");
+constexpr int kPitchThreads = 512;
+constexpr int kPitchTile = 1024;                        // outputs a workgroup
+constexpr int kPitchWindow = 2 * kPitchTile + 110;      // the floats of a tile's input window, at the most (p = 2000)
+// The prototype table as the kernel reads it: entry q = {h[q], hd[q]} at pair pitch_image_at(q), one unused pair behind every 32 (pitch.hip has why)
+PTTS_HD inline int pitch_image_at(int q) { return q + (q >> 5); }
+constexpr int kPitchImage = (kPitchEntries + (kPitchEntries >> 5) + 1) & ~1;   // pairs of floats
+struct PitchRow {
+    const float* src;        // the row's samples (device)
+    float* dst;              // the resampled row (device), [n_out]: another buffer than src
+    int64_t n;               // samples; nothing outside [0, n) is read
+    int64_t n_out;           // pitch_resample_length(n, the design's p), below kTempoMaxSamples: made on the host
+    int32_t design, pad;     // the index of the row's design among the table's
+};
+static_assert(sizeof(PitchRow) == 40, "a turn of the pitch ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n_out / kPitchTile) of a row (0: empty rows only, nothing is launched);
+// designs_dev: the table's designs; image_dev: the table's image, [kPitchImage][2]
+void launch_pitch(const PitchRow* rows_dev, int n, int max_tiles, const PitchScan* designs_dev, const float* image_dev, hipStream_t stream);
 
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.

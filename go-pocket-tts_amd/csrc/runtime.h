@@ -74,6 +74,7 @@ enum WorkSlot : size_t {
     WORK_TEMPO_SCRATCH = 35,     // tempo_launch: the rows' position tables
     WORK_JOIN_CARRY = 36,        // a streamed joined call: the chain's carried states between its windows (kernels.h kCarryDoubles)
     WORK_JOIN_STAGE = 37,        // ... and its egress where that cannot store into the result's buffer itself, indexed like that buffer
+    WORK_PITCH = 38,             // generate_joined with a pitch: a group's resampled rows, at the stride of the longest a decoded row can become
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -95,6 +96,18 @@ struct RateFilter {
     RateFilter(const RateFilter&) = delete;
     RateFilter& operator=(const RateFilter&) = delete;
     ~RateFilter();
+};
+// k_pitch_resample's prototype table (pitch.h) as the kernel reads it (kernels.h pitch_image_at): ONE per model whatever the pitches, made and
+// uploaded on first use like a RateFilter's taps (pitch_image, dsp_device.cpp)
+struct PitchImage {
+    float* staged = nullptr;      // page-locked host copy the upload reads
+    DevBuf image;                 // [kPitchImage][2]
+    hipEvent_t ready = nullptr;   // recorded behind the upload on `up`; a launch on another stream waits for it
+    hipStream_t up = nullptr;
+    PitchImage() = default;
+    PitchImage(const PitchImage&) = delete;
+    PitchImage& operator=(const PitchImage&) = delete;
+    ~PitchImage();
 };
 struct Prof {   // bench.py measurement hook (ptts_profile_*)
     bool on = false;
@@ -134,6 +147,8 @@ struct Model {
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, dsp_device.cpp)
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (trim_launch, dsp_device.cpp)
     RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (tempo_launch, dsp_device.cpp)
+    RowRing<PitchRow, kPitchMaxDesigns * kPitchScanBytes> pitch_ring;   // k_pitch_resample's, likewise (pitch_launch, dsp_device.cpp)
+    std::unique_ptr<PitchImage> pitch_image;   // ... and its table, from the first call that names a pitch on
     PinnedBuf trim_info;            // generate_joined with a trim: a group's ptts_trim_info records, [max_batch] (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
@@ -459,6 +474,15 @@ void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const
 // ptts_tempo_rows: the rows packed into one device buffer with their time-scaled forms behind them, uploaded, tempo_launch, the results back, one
 // wait.  Takes Model::mu.  design[i] null: the row is copied on the host.  n_out[i]: what out[i] received
 void tempo_rows_device(Model& m, const TempoScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out);
+// The resampling step of the pitch of a list of rows on s (pitch.hip; pitch.h has the rule): rows[i] states src, dst and n, key[i] its design (p is
+// not 1000); n_out (host arithmetic), the table's image (first use: made and uploaded) and the row tables are made here, one launch per table
+void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const PitchScan*>& key, hipStream_t s);
+// One row of ptts_pitch_rows, resolved: the pitch (null, or p == 1000: no resample) and the tempo it is followed by (null: none; with a pitch it
+// carries the effective speed E and is null at E == 1000)
+struct PitchStage { const PitchScan* pitch; const TempoScan* tempo; };
+// ptts_pitch_rows: the rows packed into one device buffer with their resampled and their final forms behind them, uploaded, pitch_launch,
+// tempo_launch, the results back, one wait.  Takes Model::mu.  A row with neither step is copied on the host.  n_out[i]: what out[i] received
+void pitch_rows_device(Model& m, const PitchStage* stage, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out);
 
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)

@@ -126,6 +126,15 @@ class TempoOpts(C.Structure):   # ptts_tempo_opts
         super().__init__(C.sizeof(TempoOpts) if size is None else int(size), int(speed_permille), (C.c_int32 * 2)(*[int(v) for v in reserved]))
 
 
+class PitchOpts(C.Structure):   # ptts_pitch_opts
+    """The pitch of a joined call's parts (ptts_pitch_opts): pitch_permille 500 .. 2000 (1000: unchanged, 1100: 10 % higher, 2000: an octave up) at
+    the same duration; formants move with it.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("pitch_permille", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, pitch_permille: int = 1000, size: Optional[int] = None, reserved=(0, 0)):
+        super().__init__(C.sizeof(PitchOpts) if size is None else int(size), int(pitch_permille), (C.c_int32 * 2)(*[int(v) for v in reserved]))
+
+
 class JoinOpts(C.Structure):   # ptts_join_opts
     """How a text's parts become one utterance (ptts_join_opts): gap_ms of silence between consecutive parts or crossfade_ms of overlap (each
     0 .. 2000, not both), and -- for Model.generate_joined -- the chain (dsp: a DspOpts; loudness in 0.01 LUFS), run once over the joined audio,
@@ -224,6 +233,8 @@ ABI_SYMBOLS = [
     "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined", "ptts_generate_joined_streamed", "ptts_join_stream_ready",
     "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
     "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
+    "ptts_pitch_speed", "ptts_pitch_resample_length", "ptts_pitch_resample", "ptts_pitch_length", "ptts_pitch_apply", "ptts_pitch_table",
+    "ptts_pitch_rows", "ptts_dsp_ext_set_pitch",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -354,6 +365,18 @@ def lib():
         L.ptts_tempo_apply.argtypes = [C.POINTER(TempoOpts), _FP, C.c_int64, _FP]
         L.ptts_tempo_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TempoOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), _IP]
         L.ptts_dsp_ext_set_tempo.argtypes = [C.c_void_p, C.POINTER(TempoOpts)]
+        L.ptts_pitch_speed.argtypes = [C.POINTER(PitchOpts), C.POINTER(TempoOpts)]
+        L.ptts_pitch_speed.restype = C.c_int32
+        L.ptts_pitch_resample_length.argtypes = [C.POINTER(PitchOpts), C.c_int64]
+        L.ptts_pitch_resample_length.restype = C.c_int64
+        L.ptts_pitch_resample.argtypes = [C.POINTER(PitchOpts), _FP, C.c_int64, _FP]
+        L.ptts_pitch_length.argtypes = [C.POINTER(PitchOpts), C.POINTER(TempoOpts), C.c_int64]
+        L.ptts_pitch_length.restype = C.c_int64
+        L.ptts_pitch_apply.argtypes = [C.POINTER(PitchOpts), C.POINTER(TempoOpts), _FP, C.c_int64, _FP]
+        L.ptts_pitch_table.argtypes = [C.POINTER(_FP), C.POINTER(_FP), C.POINTER(C.c_int32)]
+        L.ptts_pitch_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(PitchOpts)), C.POINTER(C.POINTER(TempoOpts)), C.POINTER(_FP), _IP, C.c_int32,
+                                      C.POINTER(_FP), _IP]
+        L.ptts_dsp_ext_set_pitch.argtypes = [C.c_void_p, C.POINTER(PitchOpts)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -860,6 +883,29 @@ class Model:
         lens = np.zeros(max(n, 1), np.int64)
         _check(lib().ptts_tempo_rows(self.h, po, pp, _ip(ns), n, _row_ptrs(outs), _ip(lens)))
         outs = [o[:int(lens[i])] for i, o in enumerate(outs)]
+        return outs[0] if single else outs
+
+    def pitch_rows(self, x, pitch, tempo=None):
+        """ptts_pitch_rows: pitch_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all), by the kernels
+        generate_joined runs.  pitch, tempo: one PitchOpts / TempoOpts for every row, or one per row (a row with a pitch of None gets its tempo
+        alone, with both None it is copied).  Returns the shifted rows."""
+        single, rows, n, pp, ns = _rows_in(x)
+        per_p = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * n
+        per_t = list(tempo) if isinstance(tempo, (list, tuple)) else [tempo] * n
+        # (a row whose length the library refuses is sized 1, so that the options reach the library: it names the row, and writes nothing)
+        L = lib()
+        outs = []
+        for r, p, t in zip(rows, per_p, per_t):
+            if p is not None:
+                size = int(L.ptts_pitch_length(C.byref(p), None if t is None else C.byref(t), r.size))
+            else:
+                size = r.size if t is None else r.size * 1000 // min(max(int(t.speed_permille), 500), 2000)
+            outs.append(np.empty(max(size, 1), np.float32))
+        pa = (C.POINTER(PitchOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_p])
+        ta = (C.POINTER(TempoOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_t])
+        lens = np.zeros(max(n, 1), np.int64)
+        _check(lib().ptts_pitch_rows(self.h, pa, ta, pp, _ip(ns), n, _row_ptrs(outs), _ip(lens)))
+        outs = [o[:int(lens[i])].copy() for i, o in enumerate(outs)]
         return outs[0] if single else outs
 
     def true_peak_rows(self, x):
@@ -2080,12 +2126,13 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
 class DspExt:
     """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
     (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off)
-    and their tempo (a TempoOpts; None: off).
+    and their tempo (a TempoOpts; None: off) and pitch (a PitchOpts; None: off).
     With none of them the handle switches nothing on.  It belongs to no
     model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
 
     def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
-                 limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None, tempo: Optional["TempoOpts"] = None):
+                 limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None, tempo: Optional["TempoOpts"] = None,
+                 pitch: Optional["PitchOpts"] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -2104,6 +2151,8 @@ class DspExt:
             self.set_trim(trim)
         if tempo is not None:
             self.set_tempo(tempo)
+        if pitch is not None:
+            self.set_pitch(pitch)
 
     def set_compressor(self, compressor: Optional[CompressorOpts]):
         """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
@@ -2122,6 +2171,11 @@ class DspExt:
         """ptts_dsp_ext_set_tempo: attaches the tempo of a joined call's parts (None: off again).  Served by Model.generate_joined, whose
         JoinOpts.dsp names the handle, behind the trim; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
         _check(lib().ptts_dsp_ext_set_tempo(self.h, None if tempo is None else C.byref(tempo)))
+
+    def set_pitch(self, pitch: Optional[PitchOpts]):
+        """ptts_dsp_ext_set_pitch: attaches the pitch of a joined call's parts (None: off again).  Served by Model.generate_joined, whose
+        JoinOpts.dsp names the handle, between the trim and the tempo; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
+        _check(lib().ptts_dsp_ext_set_pitch(self.h, None if pitch is None else C.byref(pitch)))
 
     def free(self):
         if self.h:
@@ -2173,6 +2227,52 @@ def trim_apply(trim: TrimOpts, samples, in_place: bool = False):
     info = TrimInfo()
     _check(lib().ptts_trim_apply(C.byref(trim), _fp(x), x.size, _fp(out), C.byref(info)))
     return out[:int(info.n_out)].copy(), info
+
+
+def _neg(got: int) -> int:   # a host function's length or speed, or -code
+    if got < 0:
+        _check(-got)
+    return got
+
+
+def pitch_speed(pitch: PitchOpts, tempo: Optional[TempoOpts] = None) -> int:
+    """ptts_pitch_speed: the speed the tempo runs at behind the resample, (1000 * s + p / 2) / p.  Host."""
+    return _neg(int(lib().ptts_pitch_speed(C.byref(pitch), None if tempo is None else C.byref(tempo))))
+
+
+def pitch_resample_length(pitch: PitchOpts, n: int) -> int:
+    """ptts_pitch_resample_length: the samples of the resampled form of a row of n samples.  Host."""
+    return _neg(int(lib().ptts_pitch_resample_length(C.byref(pitch), int(n))))
+
+
+def pitch_length(pitch: PitchOpts, tempo: Optional[TempoOpts], n: int) -> int:
+    """ptts_pitch_length: the samples of the shifted form of a row of n samples.  Host."""
+    return _neg(int(lib().ptts_pitch_length(C.byref(pitch), None if tempo is None else C.byref(tempo), int(n))))
+
+
+def pitch_resample(pitch: PitchOpts, samples) -> np.ndarray:
+    """ptts_pitch_resample: the resampling step alone, as a new array.  Host: the statement of what k_pitch_resample computes."""
+    x = _f32(samples).reshape(-1)
+    n_r = pitch_resample_length(pitch, x.size)
+    out = np.empty(max(n_r, 1), np.float32)
+    _check(lib().ptts_pitch_resample(C.byref(pitch), _fp(x), x.size, _fp(out)))
+    return out[:n_r].copy()
+
+
+def pitch_apply(pitch: PitchOpts, tempo: Optional[TempoOpts], samples) -> np.ndarray:
+    """ptts_pitch_apply: the shifted row as a new array.  Host: the statement of what Model.pitch_rows and a joined call's pitch compute."""
+    x = _f32(samples).reshape(-1)
+    n_f = pitch_length(pitch, tempo, x.size)
+    out = np.empty(max(n_f, 1), np.float32)
+    _check(lib().ptts_pitch_apply(C.byref(pitch), None if tempo is None else C.byref(tempo), _fp(x), x.size, _fp(out)))
+    return out[:n_f].copy()
+
+
+def pitch_table():
+    """ptts_pitch_table: the prototype table of the resample, (h, hd) as f32 arrays of 6828 entries each.  Host."""
+    h, hd, k = _FP(), _FP(), C.c_int32(0)
+    _check(lib().ptts_pitch_table(C.byref(h), C.byref(hd), C.byref(k)))
+    return np.ctypeslib.as_array(h, (k.value,)).copy(), np.ctypeslib.as_array(hd, (k.value,)).copy()
 
 
 def tempo_length(tempo: TempoOpts, n: int) -> int:

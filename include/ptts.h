@@ -635,6 +635,69 @@ int  ptts_tempo_rows(ptts_model* m, const ptts_tempo_opts* const* t, const float
                      int64_t* n_out /* [rows] */);
 int  ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t);
 
+/* The pitch of the parts of a joined text: per part, behind the trim and in front of the tempo.  The order of a joined
+ * call: trim per part -> pitch resample per part -> tempo at the effective speed per part -> join -> the chain of `dsp` and `loudness` once ->
+ * egress.  A pitch change at constant duration is a resampling by the pitch ratio and a tempo change that takes the length back.  FORMANTS MOVE
+ * WITH THE PITCH: every frequency of the part is scaled, so a large shift changes the voice's character, not only its height.
+ *
+ * On a part x[0, n) at 24 kHz with p = pitch_permille (500 .. 2000; 1000: unchanged, 1100: 10 % higher, SSML's "+10%"; 2000: an octave up) and
+ * s the tempo's speed_permille (1000 when there is no tempo) the stage is two steps.  Every index is an integer.
+ *   - resample: z = x read at step p / 1000, so frequencies scale by p / 1000; its length is n_r = (n * 1000 + p - 1) / p (0 for n == 0).
+ *     p == 1000: z is x, nothing is computed.
+ *   - tempo at the effective speed E = (1000 * s + p / 2) / p, integer division: the tempo's statement above runs on z with speed E, unchanged.
+ *     E outside 500 .. 2000 is PTTS_EINVAL, and the error names both fields and both values (at s == 1000 every p is served; at s == 500 p may
+ *     run up to 1001, at s == 2000 from 1000 up).  E == 1000 is the identity and nothing is computed.  The final length is
+ *     ptts_tempo_length at E of n_r.  For parts of one second and more it differs from (n * 1000) / s by at most 0.1 % of it (shorter parts are
+ *     bound by the rounding of the lengths).  Resampling first keeps the tempo's hops at 20 ms of the FINAL audio whatever p is.
+ * The resample is band-limited interpolation from one prototype table with linearly interpolated coefficients, so that any p is served without
+ * a filter design of its own.  R = 256 table steps per input sample, fc = 0.45, W = 80 / 3 samples, Kaiser beta 8.6:
+ *   - table: h[q] = (float)(2 fc sinc(2 fc q / R) I0(beta sqrt(1 - (q / (R W))^2)) / I0(beta)) where 3 q < 80 R, and 0 beyond; computed in
+ *     float64 and rounded once; 6828 entries.  hd[q] = h[q + 1] - h[q], one f32 subtraction of the rounded entries (h[6828] counts as 0).
+ *   - per row: D = max(1000, p) (above 1000 the filter widens, against aliasing) and g = (float)(1000.0 / D).
+ *   - output j in [0, n_r), with c = j * p in int64, sums over the inputs i with 3 |c - 1000 i| < 80 D in ascending i:  a = |c - 1000 i|,
+ *     q = (a * R) / D, r = (a * R) % D, frac = (float)r / (float)D (one IEEE f32 division), coef = fmaf(hd[q], frac, h[q]),
+ *     acc = fmaf(x[i], coef, acc), starting from 0.0f; x outside [0, n) reads as 0.0f.  Then out[j] = acc * g, one f32 product.
+ * Nothing else is rounded and nothing is contracted that the statement does not contract: the host and the device give the same bits.  A NaN
+ * or an infinity reaches every output whose support holds it; which NaN bits come out is the processor's choice and not fixed.  Rows whose
+ * resampled or final length would reach 2^31 - 240 are refused.
+ * ptts_pitch_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_pitch_speed: E for the pair, or -PTTS_EINVAL; t NULL means s = 1000.  Host.
+ * ptts_pitch_resample_length: n_r for a row of n samples, or -PTTS_EINVAL.  Host.
+ * ptts_pitch_resample: the resample alone into out, which holds ptts_pitch_resample_length floats and is not in.  Host: the statement of
+ *     k_pitch_resample.
+ * ptts_pitch_length: the final length of a row of n samples, or -PTTS_EINVAL.  Host.
+ * ptts_pitch_apply: the whole stage into out, which holds ptts_pitch_length floats and is not in: ptts_tempo_apply at E over
+ *     ptts_pitch_resample, by definition.  p == 1000 without a tempo returns the row bit for bit.  Host: the statement of the result.
+ * ptts_pitch_table: the prototype table: *h and *hd point at `*entries` (6828) floats each, owned by the library.  Any argument may be NULL.  Host.
+ * ptts_pitch_rows: the whole stage on rows of host samples on the device, by the kernels ptts_generate_joined runs (k_pitch_resample, then
+ *     k_tempo_plan and k_tempo_store), shaped like ptts_tempo_rows: one upload, one launch sequence per 256 rows, one download.  p[i] NULL
+ *     means the tempo t[i] alone, as ptts_tempo_rows; both NULL copies row i (n_out[i] = n[i]).  n[i] >= 0; out[i] holds
+ *     ptts_pitch_length(p[i], t[i], n[i]) floats and is not in[i] (with both NULL it holds n[i] and may be); the arrays p and t and n_out
+ *     ([rows]) are required; a bad row is named.
+ * ptts_dsp_ext_set_pitch attaches the pitch to a live handle of ptts_dsp_ext_create (p NULL: off again); a handle that is not live is
+ *     PTTS_EINVAL and is not read.  Set it before calls name the handle, not while they run.  It is served by ptts_generate_joined and
+ *     ptts_generate_joined_streamed, whose join options' `dsp` names the handle: the pair (s, p) is resolved to E once, before anything
+ *     launches; parts[i].offset and parts[i].n_samples count the final audio, parts[i].n_frames and out->n_frames still count decoded
+ *     frames; the bound on the joined length takes, per part, the largest of its step budget, its resampled length and its final length, and a
+ *     text that could reach 2^31 samples is refused.  Without a pitch nothing of this is allocated, uploaded or launched.  Everywhere a row's
+ *     length is fixed before the decode it is refused with PTTS_EINVAL, nothing launched ("dsp: ext: pitch changes a row's length ..."): a
+ *     ptts_request.dsp whose ext carries a pitch (ptts_generate, the dispatcher, the continuous engine, streaming) and ptts_dsp_rows. */
+typedef struct ptts_pitch_opts {
+    uint32_t size;             /* sizeof(ptts_pitch_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  pitch_permille;   /* 500 .. 2000: 1000 leaves the row as it is, 1100 is 10 % higher, 2000 an octave up; formants move with it */
+    int32_t  reserved[2];      /* 0 */
+} ptts_pitch_opts;
+int32_t ptts_pitch_speed(const ptts_pitch_opts* p, const ptts_tempo_opts* t);
+int64_t ptts_pitch_resample_length(const ptts_pitch_opts* p, int64_t n);
+int  ptts_pitch_resample(const ptts_pitch_opts* p, const float* in, int64_t n, float* out);
+int64_t ptts_pitch_length(const ptts_pitch_opts* p, const ptts_tempo_opts* t, int64_t n);
+int  ptts_pitch_apply(const ptts_pitch_opts* p, const ptts_tempo_opts* t, const float* in, int64_t n, float* out);
+int  ptts_pitch_table(const float** h, const float** hd, int32_t* entries);
+int  ptts_pitch_rows(ptts_model* m, const ptts_pitch_opts* const* p /* [rows] */, const ptts_tempo_opts* const* t /* [rows] */,
+                     const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out /* [rows] */);
+int  ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p);
+
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
  * tokens, and derive each chunk's step budget and EOS tail.  The SentencePiece encoder is the caller's. */
@@ -890,7 +953,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_limit_rows; the new structs ptts_join_opts and ptts_join_part, which change no existing one, with ptts_join_length, ptts_join, ptts_join_rows,
  * ptts_generate_joined; the new structs ptts_trim_opts and ptts_trim_info, likewise, with ptts_trim_plan, ptts_trim_apply, ptts_trim_rows,
  * ptts_dsp_ext_set_trim; the new struct ptts_tempo_opts, likewise, with ptts_tempo_length, ptts_tempo_plan, ptts_tempo_apply, ptts_tempo_rows,
- * ptts_dsp_ext_set_tempo; the new struct ptts_join_stream_opts, likewise, with ptts_generate_joined_streamed, ptts_join_stream_ready */
+ * ptts_dsp_ext_set_tempo; the new struct ptts_join_stream_opts, likewise, with ptts_generate_joined_streamed, ptts_join_stream_ready;
+ * the new struct ptts_pitch_opts, likewise, with ptts_pitch_speed, ptts_pitch_resample_length, ptts_pitch_resample, ptts_pitch_length,
+ * ptts_pitch_apply, ptts_pitch_table, ptts_pitch_rows, ptts_dsp_ext_set_pitch */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
