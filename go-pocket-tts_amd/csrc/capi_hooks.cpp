@@ -669,6 +669,137 @@ int ptts_debug_step_linear(const ptts_step_linear_args* pa) {
     });
 }
 
+// The opening and the closing of an AR step on host operands: ONE launcher call per op (include/ptts_debug.h).  None of these kernels bounds a load or a
+// store by a buffer size -- the latent row at `step`, the noise row at `step` or `step + 1`, the rows of the two 32-deep linears -- so every counter is
+// checked against the buffers allocated here before anything is uploaded.
+int ptts_debug_step_edge(const ptts_step_edge_args* pa) {
+    return guard([&] {
+        const char* const me = "ptts_debug_step_edge";
+        if (!pa) throw Error(PTTS_EINVAL, strfmt("%s: null argument", me));
+        const ptts_step_edge_args& t = *pa;
+        const int op = t.op;
+        if (op < PTTS_STEP_EDGE_BEGIN || op > PTTS_STEP_EDGE_FIN_CHAIN) throw Error(PTTS_EINVAL, strfmt("%s: unknown op %d", me, op));
+        const bool begin = op == PTTS_STEP_EDGE_BEGIN || op == PTTS_STEP_EDGE_BEGIN_LIN, fin = op == PTTS_STEP_EDGE_FIN || op == PTTS_STEP_EDGE_FIN_CHAIN;
+        const bool chain = op == PTTS_STEP_EDGE_FIN_CHAIN, lins = op == PTTS_STEP_EDGE_BEGIN_LIN || chain;
+        if (t.ldim < 4 || t.ldim > 64 || t.ldim % 4 != 0) throw Error(PTTS_EINVAL, strfmt("%s: ldim %d: a multiple of 4 up to 64", me, t.ldim));
+        if (t.B < 1 || t.B > kStepMaxRows || t.rows < t.B || t.rows > 2 * kStepMaxRows) throw Error(PTTS_EINVAL, strfmt("%s: %d rows launched of %d held: 1..%d, held >= launched", me, t.B, t.rows, kStepMaxRows));
+        if (t.S < 1 || t.S > 4096) throw Error(PTTS_EINVAL, strfmt("%s: %d frames per row outside 1..4096", me, t.S));
+        const int B = t.B, rows = t.rows, ld = t.ldim;
+        const int64_t need = (int64_t)t.S * ld;
+        if (t.lat_stride < need || t.lat_stride > 4 * need + 64) throw Error(PTTS_EINVAL, strfmt("%s: lat_stride %lld below S ldim = %lld (or beyond 4 times that)", me, (long long)t.lat_stride, (long long)need));
+        if (t.noise && (t.noise_stride < need || t.noise_stride > 4 * need + 64))
+            throw Error(PTTS_EINVAL, strfmt("%s: noise_stride %lld below S ldim = %lld (or beyond 4 times that)", me, (long long)t.noise_stride, (long long)need));
+        if (!t.kv_len || !t.active || !t.step || !t.countdown || !t.n_frames || !t.eos_step || !t.max_steps || !t.frames_after_eos || !t.broke || !t.n_active ||
+            !t.eos_threshold || !t.latents || !t.bos || !t.in32 || !t.x0 || (!begin && !t.eos_logit) || (op == PTTS_STEP_EDGE_FINISH && !t.frame) ||
+            (lins && (!t.w_in || !t.w_pj || !t.x || !t.fx)) || (fin && (!t.fx_in || !t.W || !t.shift || !t.mscale || !t.cur)))
+            throw Error(PTTS_EINVAL, strfmt("%s: null operand", me));
+        for (int r = 0; r < B; r++) {
+            if (t.step[r] < 0 || t.step[r] > t.max_steps[r] || t.max_steps[r] > t.S)
+                throw Error(PTTS_EINVAL, strfmt("%s: row %d: step %d, max_steps %d, %d frames held: 0 <= step <= max_steps <= S", me, r, t.step[r], t.max_steps[r], t.S));
+            if (t.active[r] && t.step[r] >= t.max_steps[r]) throw Error(PTTS_EINVAL, strfmt("%s: row %d is active at step %d of %d", me, r, t.step[r], t.max_steps[r]));
+        }
+        if (lins && (t.d_in < 1 || t.d_in > 4096 || t.d_pj < 1 || t.d_pj > 4096 || (t.lin_bf16 != 0 && t.lin_bf16 != 1)))
+            throw Error(PTTS_EINVAL, strfmt("%s: linears of %d and %d rows (1..4096 each), lin_bf16 %d", me, t.d_in, t.d_pj, t.lin_bf16));
+        if (fin) {
+            if (t.N != ld) throw Error(PTTS_EINVAL, strfmt("%s: N %d is not ldim %d (the frame is the whole row of C)", me, t.N, ld));
+            if (t.K < 8 || t.K > 4096 || t.ldmod < t.K || t.ldmod > (1 << 16) || t.wfmt < 0 || t.wfmt > 2 || t.epi < EPI_NONE || t.epi > EPI_RESADD_ELU)
+                throw Error(PTTS_EINVAL, strfmt("%s: K %d, ldmod %d, wfmt %d, epi %d do not fit", me, t.K, t.ldmod, t.wfmt, t.epi));
+            if (chain && (t.lat_stride % 2 != 0 || t.lin_bf16 != (t.wfmt != 0 ? 1 : 0)))
+                throw Error(PTTS_EINVAL, strfmt("%s: chained: lat_stride %lld must be even, the 32-deep linears bf16 exactly when the step weights are not f32", me, (long long)t.lat_stride));
+        }
+        const int N = t.N, K = t.K, d_in = lins ? t.d_in : 0, d_pj = lins ? t.d_pj : 0;
+        const size_t nk = fin ? (size_t)N * K : 0, les = t.lin_bf16 ? 2 : 4;
+        // the final linear: the loader's packers
+        std::vector<float> rm, wscale;
+        std::vector<uint8_t> wt;
+        std::vector<uint16_t> rm16;
+        if (fin) {
+            rm.assign(t.W, t.W + nk);
+            wt.resize(step_tiled_bytes((size_t)N, (size_t)K, t.wfmt == 2 ? 1 : (t.wfmt == 1 ? 2 : 4)));
+            if (t.wfmt == 2) {
+                std::vector<int8_t> q;
+                quantize_rows(rm, (size_t)N, (size_t)K, wscale, q);   // rm -> W^
+                pack_step_tiled_i8(q.data(), (size_t)N, (size_t)K, wt.data());
+                if (t.w_eff) std::memcpy(t.w_eff, rm.data(), nk * 4);
+                if (t.w_scale) std::memcpy(t.w_scale, wscale.data(), (size_t)N * 4);
+            } else {
+                pack_step_tiled(rm.data(), (size_t)N, (size_t)K, t.wfmt == 1, wt.data());
+                if (t.wfmt == 1) { rm16.resize(nk); for (size_t i = 0; i < nk; i++) rm16[i] = f32_to_bf16_rne(rm[i]); }
+            }
+        }
+        require_device();
+        Stage st;
+        const size_t R = (size_t)rows;
+        // the state as the batch set-up lays it out: nine int32 arrays and n_active in one allocation, the thresholds in another
+        std::vector<int32_t> hs(9 * R + 1);
+        int32_t* const harr[9] = {t.kv_len, t.active, t.step, t.countdown, t.n_frames, t.eos_step, t.max_steps, t.frames_after_eos, t.broke};
+        for (int i = 0; i < 9; i++) std::memcpy(hs.data() + (size_t)i * R, harr[i], R * 4);
+        hs[9 * R] = t.n_active[0];
+        int32_t* const ds = st.out<int32_t>(hs.size());
+        up(ds, hs.data(), hs.size() * 4);
+        float* const dthr = st.out(R);
+        up(dthr, t.eos_threshold, R * 4);
+        StepState s;
+        s.kv_len = ds; s.active = ds + R; s.step = ds + 2 * R; s.countdown = ds + 3 * R; s.n_frames = ds + 4 * R; s.eos_step = ds + 5 * R;
+        s.max_steps = ds + 6 * R; s.frames_after_eos = ds + 7 * R; s.broke = ds + 8 * R; s.n_active = ds + 9 * R; s.eos_threshold = dthr;
+        float* const dLat = st.out(R * (size_t)t.lat_stride);
+        up(dLat, t.latents, R * (size_t)t.lat_stride * 4);
+        const float* const dNoise = st.in(t.noise, R * (size_t)t.noise_stride);
+        const float* const dBos = st.in(t.bos, (size_t)ld);
+        const float* const dLogit = st.in(t.eos_logit, R);
+        float *dIn32 = st.out(R * ld), *dX0 = st.out(R * ld), *dX = st.out(R * (size_t)d_in), *dFx = st.out(R * (size_t)d_pj);
+        StepOpenLinears lin;
+        if (lins) {
+            lin.w_in = st.in_bytes(t.w_in, (size_t)d_in * ld * les); lin.b_in = st.in(t.b_in, (size_t)d_in); lin.d_in = d_in; lin.x = dX;
+            lin.w_pj = st.in_bytes(t.w_pj, (size_t)d_pj * ld * les); lin.b_pj = st.in(t.b_pj, (size_t)d_pj); lin.d_pj = d_pj; lin.fx = dFx;
+            lin.w_bf16 = t.lin_bf16;
+        }
+        if (chain && !step_open_mfma_ok(lin, ld)) throw Error(PTTS_EINVAL, strfmt("%s: chained: the 32-deep linears are not taken by the matrix-core opening (step_open_mfma_ok)", me));
+        const float* dFrame = op == PTTS_STEP_EDGE_FINISH ? st.in(t.frame, R * ld) : nullptr;
+        GemmArgs g;
+        SkinnyFuse fu;
+        float* dCur = nullptr;
+        if (fin) {
+            dCur = st.out(R * N);
+            up(dCur, t.cur, R * N * 4);
+            g.A = st.in(t.fx_in, R * K); g.amap = RowMap{K, 0, 0};
+            g.W = t.wfmt == 1 ? (const void*)st.in(rm16.data(), nk) : st.in(rm.data(), nk);
+            g.w_bf16 = t.wfmt == 1; g.ldw = K; g.Wt = st.in(wt.data(), wt.size());
+            if (t.wfmt == 2) { g.wt_i8 = 1; g.wscale = st.in(wscale.data(), (size_t)N); }
+            g.bias = st.in(t.bias, (size_t)N);
+            g.C = dCur; g.cmap = RowMap{N, 0, 0}; g.R = dCur;   // step_flow: current += flow / steps, in place
+            g.alpha = t.alpha; g.epi = t.epi;
+            g.M = B; g.N = N; g.K = K;
+            // the record in device memory, as the batch set-up fills it: a chained step opens the next one in the OTHER copies of fx / cur
+            StepFinish sf{s, dLogit, dLat, t.lat_stride, (int32_t)ld, StepChain{}};
+            if (chain) sf.ch = StepChain{lin.w_in, lin.b_in, lin.x, lin.d_in, lin.w_pj, lin.b_pj, dFx, lin.d_pj, dBos, dX0, lin.w_bf16, 1};
+            fu.ln = 1; fu.eps = t.eps;   // flowFinalLayer: LayerNorm without affine, then the modulation
+            fu.shift = st.in(t.shift, R * (size_t)t.ldmod); fu.scale = st.in(t.mscale, R * (size_t)t.ldmod); fu.ldmod = t.ldmod;
+            fu.fin = st.in(&sf, 1);
+            if (chain) { fu.chain = 1; fu.chain_noise = dNoise; fu.chain_noise_stride = dNoise ? t.noise_stride : need; }
+            if (!skinny_fuse_supported(g, fu)) throw Error(PTTS_EINVAL, strfmt("%s: not taken by the step kernel (skinny_fuse_supported)", me));
+        }
+        LaunchScope launches;
+        launches.run([&] {
+            if (begin) launch_step_begin(s, dLat, t.lat_stride, dBos, dNoise, dNoise ? t.noise_stride : need, ld, B, dIn32, dX0, lins ? &lin : nullptr, nullptr);
+            else if (op == PTTS_STEP_EDGE_FINISH) launch_step_finish(s, dFrame, dLogit, ld, B, dLat, t.lat_stride, nullptr);
+            else launch_skinny(g, fu, 1, nullptr, nullptr);
+        });
+        PTTS_HIP(hipGetLastError());
+        PTTS_HIP(hipDeviceSynchronize());
+        put_str(t.launched, t.launched_cap, launches.str());
+        down(hs.data(), ds, hs.size() * 4);
+        for (int i = 0; i < 9; i++) std::memcpy(harr[i], hs.data() + (size_t)i * R, R * 4);
+        t.n_active[0] = hs[9 * R];
+        down(t.eos_threshold, dthr, R * 4);
+        down(t.latents, dLat, R * (size_t)t.lat_stride * 4);
+        down(t.in32, dIn32, R * ld * 4); down(t.x0, dX0, R * ld * 4);
+        if (t.x) down(t.x, dX, R * (size_t)d_in * 4);
+        if (t.fx) down(t.fx, dFx, R * (size_t)d_pj * 4);
+        if (fin) down(t.cur, dCur, R * N * 4);
+    });
+}
+
 // The step attention on host operands: ONE launch_attention call with the AttnArgs of the AR step, from the function step.cpp step_core builds them with (launch_args.h attn_step_args).  k_attn_step bounds none of its
 // loads by a buffer size -- cache rows up to seg_len, prefix rows up to pre_len, the RoPE row at seg_len -- so every one of those is checked against the
 // buffers allocated here before anything is uploaded; there is no way to ask for a launch without the checks.

@@ -973,6 +973,7 @@ void launch_step_begin(const StepState& s, const float* latents, int64_t lat_str
     const int cols = lin ? lin->d_in + lin->d_pj : 0;
     dim3 grid(lin ? (cols + 255) / 256 : 1, b);
     const void* w_in = lin ? lin->w_in : nullptr;
+    note_launch("k_step_begin");
     if (lin && lin->w_bf16)
         hipLaunchKernelGGL(k_step_begin<true>, grid, dim3(256), 0, stream, s, latents, lat_stride, bos, noise, noise_stride, ldim, in32, x0, w_in,
                            lin->b_in, lin->d_in, lin->x, lin->w_pj, lin->b_pj, lin->d_pj, lin->fx);
@@ -1053,6 +1054,7 @@ __global__ void k_step_finish(StepState s, const float* frame, const float* eos_
 }
 void launch_step_finish(const StepState& s, const float* frame, const float* eos_logit, int ldim, int b, float* latents,
                         int64_t lat_stride, hipStream_t stream) {
+    note_launch("k_step_finish");
     hipLaunchKernelGGL(k_step_finish, dim3(b), dim3(64), 0, stream, s, frame, eos_logit, ldim, b, latents, lat_stride);
 }
 

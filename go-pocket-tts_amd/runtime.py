@@ -244,7 +244,7 @@ HOOK_SYMBOLS = [
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
     "ptts_debug_gemm_rows", "ptts_debug_attn_step", "ptts_debug_attn_step_rounds", "ptts_debug_attn_window", "ptts_debug_flow_cluster",
-    "ptts_debug_mimi_fused", "ptts_debug_mimi_pack", "ptts_debug_dsp_windows",
+    "ptts_debug_mimi_fused", "ptts_debug_mimi_pack", "ptts_debug_dsp_windows", "ptts_debug_step_edge",
 ]
 
 
@@ -409,7 +409,7 @@ def hooks():
         H.ptts_debug_dsp_windows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(DspOpts), _IP, C.c_int32, C.POINTER(_FP)]
         H.ptts_debug_dsp_opts_error.restype = C.c_int64
         H.ptts_debug_dsp_opts_error.argtypes = [C.POINTER(DspOpts), C.c_char_p, C.c_int64]
-        for name, args in (("flow_cluster", _FlowClusterArgs), ("step_linear", _StepLinearArgs), ("attn_step", _AttnStepArgs), ("attn_window", _AttnWindowArgs),
+        for name, args in (("flow_cluster", _FlowClusterArgs), ("step_linear", _StepLinearArgs), ("step_edge", _StepEdgeArgs), ("attn_step", _AttnStepArgs), ("attn_window", _AttnWindowArgs),
                            ("gemm_rows", _GemmRowsArgs), ("mimi_fused", _MimiFusedArgs), ("resblock", _ResblockArgs)):   # the hooks on a struct of host operands
             getattr(H, "ptts_debug_" + name).argtypes = [C.POINTER(args)]
         _hooks = H
@@ -1579,6 +1579,79 @@ def debug_step_linear(x, w, *, wfmt=0, bias=None, addvec=None, residual=None, in
     a.launches = C.cast(cnt, _I32P)
     _check(hooks().ptts_debug_step_linear(C.byref(a)))
     return {"out": out, "tail": tl if tail else None, "x_out": xo, "y_out": yo, "w_eff": we, "w_scale": ws, "k_skinny": int(cnt[0]), "launches": int(cnt[1])}
+
+
+STEP_EDGE_OPS = {"begin": 0, "begin_lin": 1, "finish": 2, "fin": 3, "fin_chain": 4}   # PTTS_STEP_EDGE_*
+STEP_STATE_I32 = ("kv_len", "active", "step", "countdown", "n_frames", "eos_step", "max_steps", "frames_after_eos", "broke")   # kernels.h StepState, [rows] each
+
+
+class _StepEdgeArgs(C.Structure):   # ptts_step_edge_args
+    _fields_ = ([(n, C.c_int32) for n in ("op", "B", "rows", "S", "ldim", "d_in", "d_pj", "lin_bf16", "N", "K", "wfmt", "epi", "ldmod", "reserved")] +
+                [("alpha", C.c_float), ("eps", C.c_float)] +
+                [(n, C.c_int64) for n in ("lat_stride", "noise_stride", "launched_cap")] +
+                [(n, _I32P) for n in STEP_STATE_I32 + ("n_active",)] +
+                [(n, _FP) for n in ("eos_threshold", "latents", "noise", "bos", "eos_logit", "frame")] +
+                [("w_in", C.c_void_p), ("w_pj", C.c_void_p)] +
+                [(n, _FP) for n in ("b_in", "b_pj", "fx_in", "W", "bias", "shift", "mscale", "cur", "in32", "x0", "x", "fx", "w_eff", "w_scale")] +
+                [("launched", C.c_char_p)])
+
+
+def debug_step_edge(op, state, latents, bos, *, B=None, S=None, noise=None, eos_logit=None, frame=None, lin=None, final=None, null=()):
+    """The opening and closing of an AR step on host operands (ptts_debug_step_edge, include/ptts_debug.h): ONE launcher call.  op: a key of STEP_EDGE_OPS.
+    state: {name: [rows] int32 for name in STEP_STATE_I32, "eos_threshold": [rows] f32, "n_active": int}; latents [rows, lat_stride] (S frames of ldim =
+    len(bos) per row: default lat_stride // ldim); noise [rows, noise_stride] or None; B rows are launched (default: all).  lin = dict(w_in [d_in, ldim],
+    w_pj [d_pj, ldim], b_in, b_pj): f32 arrays, or uint16 arrays of bf16 bits.  final = dict(fx [rows, K], W [N, K], bias, shift, mscale [rows, ldmod],
+    cur [rows, N], wfmt, alpha, eps, epi).  Nothing passed in is modified.  Returns a dict: "state" (as above, after the launch), "latents", "cur" (whole,
+    after the launch), "in32", "x0", "x", "fx" (whole; 0xff bytes where nothing was stored), "w_eff" / "w_scale" (int8), "launched" ({kernel: count}).
+    null: names of ptts_step_edge_args pointers to pass as NULL (the refusal tests)."""
+    bos = _f32(bos)
+    ldim = int(bos.shape[0])
+    lat = np.array(latents, np.float32, order="C")
+    rows = int(lat.shape[0])
+    st_i = {n: np.array(state[n], np.int32, order="C").reshape(rows) for n in STEP_STATE_I32}
+    thr = np.array(state["eos_threshold"], np.float32, order="C").reshape(rows)
+    n_act = np.array([int(state["n_active"])], np.int32)
+    a, keep = _StepEdgeArgs(), _Keep()
+    a.op, a.B, a.rows, a.ldim = STEP_EDGE_OPS[op], rows if B is None else int(B), rows, ldim
+    a.S = lat.shape[1] // max(ldim, 1) if S is None else int(S)
+    a.lat_stride, a.launched_cap = lat.shape[1], 256
+    for n in STEP_STATE_I32:
+        setattr(a, n, keep.i32(st_i[n]))
+    a.n_active, a.eos_threshold, a.latents, a.bos = keep.i32(n_act), keep.f32(thr), keep.f32(lat), keep.f32(bos)
+    if noise is not None:
+        noise = _f32(noise)
+        a.noise_stride = noise.shape[1]
+    a.noise, a.eos_logit, a.frame = keep.f32(noise), keep.f32(eos_logit), keep.f32(frame)
+    d_in = d_pj = 0
+    if lin is not None:
+        ws = [np.ascontiguousarray(lin[k]) for k in ("w_in", "w_pj")]
+        a.lin_bf16 = 1 if ws[0].dtype == np.uint16 else 0
+        ws = [w if w.dtype == np.uint16 else _f32(w) for w in ws]
+        keep.arrays += ws
+        d_in, d_pj = int(ws[0].shape[0]), int(ws[1].shape[0])
+        a.d_in, a.d_pj, a.w_in, a.w_pj = d_in, d_pj, ws[0].ctypes.data, ws[1].ctypes.data
+        a.b_in, a.b_pj = keep.f32(lin.get("b_in")), keep.f32(lin.get("b_pj"))
+    cur = we = wsc = None
+    if final is not None:
+        W = _f32(final["W"])
+        a.N, a.K, a.wfmt, a.epi = int(W.shape[0]), int(W.shape[1]), int(final.get("wfmt", 0)), int(final.get("epi", 7))
+        a.alpha, a.eps = float(final.get("alpha", 1.0)), float(final.get("eps", 1e-6))
+        a.ldmod = int(np.asarray(final["shift"]).shape[1])
+        cur = np.array(final["cur"], np.float32, order="C")
+        if a.wfmt == 2:
+            we, wsc = np.empty(W.shape, np.float32), np.empty(W.shape[0], np.float32)
+        a.fx_in, a.W, a.bias, a.shift, a.mscale = keep.f32(final["fx"]), keep.f32(W), keep.f32(final.get("bias")), keep.f32(final["shift"]), keep.f32(final["mscale"])
+        a.cur, a.w_eff, a.w_scale = keep.f32(cur), keep.f32(we), keep.f32(wsc)
+    in32, x0 = np.empty((rows, ldim), np.float32), np.empty((rows, ldim), np.float32)
+    x, fx = (np.empty((rows, d_in), np.float32), np.empty((rows, d_pj), np.float32)) if lin is not None else (None, None)
+    a.in32, a.x0, a.x, a.fx = keep.f32(in32), keep.f32(x0), keep.f32(x), keep.f32(fx)
+    launched = C.create_string_buffer(256)
+    a.launched = C.cast(launched, C.c_char_p)
+    for name in null:
+        setattr(a, name, C.cast(None, dict(_StepEdgeArgs._fields_)[name]))
+    _check(hooks().ptts_debug_step_edge(C.byref(a)))
+    out_state = dict(st_i, eos_threshold=thr, n_active=int(n_act[0]))
+    return {"state": out_state, "latents": lat, "cur": cur, "in32": in32, "x0": x0, "x": x, "fx": fx, "w_eff": we, "w_scale": wsc, "launched": _census_dict(launched)}
 
 
 class _AttnStepArgs(C.Structure):   # ptts_attn_step_args

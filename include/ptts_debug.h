@@ -78,6 +78,53 @@ typedef struct ptts_step_linear_args {
 } ptts_step_linear_args;
 int ptts_debug_step_linear(const ptts_step_linear_args* a);
 
+/* The code that opens and closes an AR step, stand-alone on host operands: ONE launcher call, built as step.cpp / batch.cpp build it.
+ *   op PTTS_STEP_EDGE_BEGIN      launch_step_begin without the two 32-deep linears (k_step_begin)
+ *      PTTS_STEP_EDGE_BEGIN_LIN  launch_step_begin with them: the launcher picks k_step_begin_mm (step_open_mfma_ok, even strides) or k_step_begin
+ *      PTTS_STEP_EDGE_FINISH     launch_step_finish on `frame` (k_step_finish)
+ *      PTTS_STEP_EDGE_FIN        launch_skinny with SkinnyFuse::fin: the flow net's final layer with the bookkeeping in its epilogue
+ *      PTTS_STEP_EDGE_FIN_CHAIN  ... and SkinnyFuse::chain: the launch opens the next step as well
+ *   Every per-row buffer and every state array holds `rows` >= B rows; the launch is told of B.  Rows behind B are there to be found unchanged.
+ *   State, read and written back in place: kv_len, active, step, countdown, n_frames, eos_step, max_steps, frames_after_eos, broke [rows], eos_threshold
+ *   [rows], n_active [1] (kernels.h StepState).
+ *   latents [rows][lat_stride] (lat_stride >= S ldim; S frames per row), read and written back in place; noise [rows][noise_stride] or NULL (zeros);
+ *   bos [ldim]; eos_logit [rows]; frame [rows][ldim] (FINISH).
+ *   The 32-deep linears: w_in [d_in][ldim], w_pj [d_pj][ldim] row-major, f32 or -- lin_bf16 -- bf16 bits; b_in [d_in], b_pj [d_pj] or NULL.
+ *   FIN / FIN_CHAIN: fx_in [rows][K]; W [N][K] f32 with bias [N] or NULL, packed by the loader's packers as wfmt says (0 f32, 1 bf16, 2 int8: w_eff [N][K]
+ *   and w_scale [N] receive W^ and the row scales); shift, mscale [rows][ldmod]; LayerNorm without affine at eps; epilogue epi with alpha;
+ *   cur [rows][N] is the residual AND the output (R == C, as step_flow passes it), read and written back in place.  N == ldim.
+ *   FIN_CHAIN builds the StepFinish + StepChain record in device memory as the batch set-up does: the next step's x0 and fx are the OTHER copies (Batch::cur2,
+ *   fx2), here the results x0 and fx -- a chained launch's blocks read cur and fx_in while one of them writes the next opening, so the two never alias.
+ * Results, filled with 0xff bytes before the launch and returned whole: in32 [rows][ldim], x0 [rows][ldim], x [rows][d_in], fx [rows][d_pj] (NULL or unused
+ * when the op has no linears).  launched (launched_cap bytes): the census of the call ("kernel=count;").
+ * PTTS_EINVAL with a message, before anything is launched -- no call can take an access outside these buffers:
+ *   an unknown op; ldim > 64 or ldim % 4 != 0; B outside [1, 256] or rows < B; S < 1; lat_stride < S ldim (noise_stride likewise with noise);
+ *   a row below B without 0 <= step <= max_steps <= S, or active with step == max_steps; a null operand of the op;
+ *   with linears: d_in or d_pj outside [1, 4096];  FIN / FIN_CHAIN: N != ldim, ldmod < K, wfmt outside 0..2, whatever skinny_fuse_supported refuses;
+ *   FIN_CHAIN: whatever step_open_mfma_ok refuses, an odd lat_stride, lin_bf16 != (wfmt != 0) (the chained form takes the linears' type from the step
+ *   kernel's weight type). */
+#define PTTS_STEP_EDGE_BEGIN 0
+#define PTTS_STEP_EDGE_BEGIN_LIN 1
+#define PTTS_STEP_EDGE_FINISH 2
+#define PTTS_STEP_EDGE_FIN 3
+#define PTTS_STEP_EDGE_FIN_CHAIN 4
+typedef struct ptts_step_edge_args {
+    int32_t op, B, rows, S, ldim, d_in, d_pj, lin_bf16, N, K, wfmt, epi, ldmod, reserved;
+    float alpha, eps;
+    int64_t lat_stride, noise_stride, launched_cap;
+    int32_t *kv_len, *active, *step, *countdown, *n_frames, *eos_step, *max_steps, *frames_after_eos, *broke, *n_active;
+    float* eos_threshold;
+    float* latents;
+    const float *noise, *bos, *eos_logit, *frame;
+    const void *w_in, *w_pj;
+    const float *b_in, *b_pj;
+    const float *fx_in, *W, *bias, *shift, *mscale;
+    float* cur;
+    float *in32, *x0, *x, *fx, *w_eff, *w_scale;
+    char* launched;
+} ptts_step_edge_args;
+int ptts_debug_step_edge(const ptts_step_edge_args* a);
+
 /* The step attention (csrc/attn_step.hip: k_attn_step, and k_attention behind it for caches beyond one burst) stand-alone: ONE launch_attention call with
  * AttnArgs filled as the AR step fills them (step.cpp step_core: fused_step, context -1, d_model = heads * 64, max_keys = cap), on host operands.
  *   qkv [rows][qkv_ld] (q | k | v, d_model each), cos_t / sin_t [cap][32], seg_len / active / pre_len / voice_of_row [rows];
