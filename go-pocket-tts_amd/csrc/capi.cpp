@@ -1163,131 +1163,91 @@ int ptts_limit_rows(ptts_model* h, const ptts_limiter_opts* const* l, const floa
     });
 }
 
-// the device form of ptts_trim_apply on host rows: the launches of a joined call's trim; a row without one is copied on the host
-int ptts_trim_rows(ptts_model* h, const ptts_trim_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info) {
+// The host-rows entry points of a joined call's part stages (ptts_trim_rows, ptts_tempo_rows, ptts_pitch_rows): the argument checks under the entry
+// point's name, each row's stages from per_row(i, stages) -- which throws the row's refusal -- and the one round trip (part_rows_device).  A
+// row whose stages stay empty is copied on the host.  designs: the caller's vectors of designs, sized here to one a row before the first row is
+// looked at, so that what per_row points a row's stages to stays where it is
+extern "C++" {
+template <class... Design>
+static int part_rows(ptts_model* h, const char* what, bool args_null, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out,
+                     ptts_trim_info* info, const std::function<void(int, PartStages&)>& per_row, std::vector<Design>&... designs) {
     return guard([&] {
         Model& m = model_of(h);
-        const RowsCheck check{"trim"};
-        check.args(rows, !t || !in || !n || !out || !info);
-        std::vector<TrimScan> designs((size_t)rows);
-        std::vector<const TrimScan*> design((size_t)rows, nullptr);
+        const RowsCheck check{what};
+        check.args(rows, args_null || !in || !n || !out);
+        std::vector<PartStages> stages((size_t)rows);
+        (designs.resize((size_t)rows), ...);
         for (int i = 0; i < rows; i++) {
             check.row(i, n[i], !in[i] || !out[i]);
-            if (n[i] >= kTrimMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: trim: row %d has %lld samples, a row must stay below 2^31", i, (long long)n[i]));
-            if (!t[i]) continue;
-            const std::string e = trim_opts_error(t[i]);
-            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
-            designs[(size_t)i] = trim_design(*t[i]);
-            design[(size_t)i] = &designs[(size_t)i];
+            per_row(i, stages[(size_t)i]);
         }
-        if (rows > 0) trim_rows_device(m, design.data(), in, n, rows, out, info);
+        if (rows > 0) part_rows_device(m, stages.data(), in, n, rows, out, n_out, info);
     });
+}
+}  // extern "C++"
+// such a row's refusal (e empty: none), as a stage's *_opts_error or a length check words it, behind the row's number
+static void row_refuse(int i, const std::string& e) {
+    if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
+}
+
+// the device form of ptts_trim_apply on host rows: the launches of a joined call's trim; a row without one is copied on the host
+int ptts_trim_rows(ptts_model* h, const ptts_trim_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info) {
+    std::vector<TrimScan> designs;
+    return part_rows(h, "trim", !t || !info, in, n, rows, out, nullptr, info, [&](int i, PartStages& st) {
+        if (n[i] >= kTrimMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: trim: row %d has %lld samples, a row must stay below 2^31", i, (long long)n[i]));
+        if (!t[i]) return;
+        row_refuse(i, trim_opts_error(t[i]));
+        designs[(size_t)i] = trim_design(*t[i]);
+        st.trim = &designs[(size_t)i];
+    }, designs);
 }
 
 // the trim of a joined call's parts, attached to the handle (trim.cpp checks and designs it, and stays a file that builds alone)
-int ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t) {
-    DspExt v;   // (the design is made outside the registry's mutex)
-    if (t) {
-        const std::string err = trim_opts_error(t);
-        if (!err.empty()) return fail(err);
-        v.trim = true;
-        v.trm = trim_design(*t);
-    }
-    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.trim = v.trim; e->v.trm = v.trm; }))
-        return fail(strfmt("trim: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
-    return PTTS_OK;
-}
+int ptts_dsp_ext_set_trim(ptts_dsp_ext* e, const ptts_trim_opts* t) { return ext_set(e, "trim", t, trim_opts_error, trim_design, &DspExt::trim, &DspExt::trm); }
 
 // the device form of ptts_tempo_apply on host rows: the launches of a joined call's tempo; a row without one is copied on the host
 int ptts_tempo_rows(ptts_model* h, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
-    return guard([&] {
-        Model& m = model_of(h);
-        const RowsCheck check{"tempo"};
-        check.args(rows, !t || !in || !n || !out || !n_out);
-        std::vector<TempoScan> designs((size_t)rows);
-        std::vector<const TempoScan*> design((size_t)rows, nullptr);
-        for (int i = 0; i < rows; i++) {
-            check.row(i, n[i], !in[i] || !out[i]);
-            if (n[i] >= kTempoMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d has %lld samples, a row must stay below 2^31 - %d", i, (long long)n[i], kTempoRadius));
-            if (!t[i]) continue;
-            const std::string e = tempo_opts_error(t[i]);
-            if (!e.empty()) throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e);
-            if (n[i] > 0 && in[i] == out[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d: out is in", i));
-            designs[(size_t)i] = tempo_design(*t[i]);
-            design[(size_t)i] = &designs[(size_t)i];
-        }
-        if (rows > 0) tempo_rows_device(m, design.data(), in, n, rows, out, n_out);
-    });
+    std::vector<TempoScan> designs;
+    return part_rows(h, "tempo", !t || !n_out, in, n, rows, out, n_out, nullptr, [&](int i, PartStages& st) {
+        if (n[i] >= kTempoMaxSamples) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d has %lld samples, a row must stay below 2^31 - %d", i, (long long)n[i], kTempoRadius));
+        if (!t[i]) return;
+        row_refuse(i, tempo_opts_error(t[i]));
+        if (n[i] > 0 && in[i] == out[i]) throw Error(PTTS_EINVAL, strfmt("ptts-hip: tempo: row %d: out is in", i));
+        designs[(size_t)i] = tempo_design(*t[i]);
+        st.tempo = &designs[(size_t)i];
+    }, designs);
 }
 
 // the tempo of a joined call's parts, attached to the handle (tempo.cpp checks and designs it, and stays a file that builds alone)
-int ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t) {
-    DspExt v;
-    if (t) {
-        const std::string err = tempo_opts_error(t);
-        if (!err.empty()) return fail(err);
-        v.tempo = true;
-        v.tmp = tempo_design(*t);
-    }
-    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.tempo = v.tempo; e->v.tmp = v.tmp; }))
-        return fail(strfmt("tempo: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
-    return PTTS_OK;
-}
+int ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t) { return ext_set(e, "tempo", t, tempo_opts_error, tempo_design, &DspExt::tempo, &DspExt::tmp); }
 
 // the device form of ptts_pitch_apply on host rows: the launches of a joined call's pitch and of the tempo behind it; a row with neither is copied on
 // the host.  p[i] null: the tempo alone, as ptts_tempo_rows
 int ptts_pitch_rows(ptts_model* h, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows,
                     float* const* out, int64_t* n_out) {
-    return guard([&] {
-        Model& m = model_of(h);
-        const RowsCheck check{"pitch"};
-        check.args(rows, !p || !t || !in || !n || !out || !n_out);
-        std::vector<PitchScan> pitches((size_t)rows);
-        std::vector<TempoScan> tempos((size_t)rows);
-        std::vector<PitchStage> stage((size_t)rows, PitchStage{nullptr, nullptr});
-        for (int i = 0; i < rows; i++) {
-            check.row(i, n[i], !in[i] || !out[i]);
-            const auto refuse = [&](const std::string& e) { throw Error(PTTS_EINVAL, strfmt("ptts-hip: row %d: ", i) + e); };
-            std::string e = p[i] ? pitch_opts_error(p[i]) : std::string();
-            if (e.empty() && t[i]) e = tempo_opts_error(t[i]);
-            if (!e.empty()) refuse(e);
-            int32_t speed = t[i] ? t[i]->speed_permille : 1000;
-            bool tempo = t[i] != nullptr;
-            if (p[i]) {   // the pair resolves to the effective speed, and the tempo at 1000 is the identity
-                e = pitch_speed_error(p[i]->pitch_permille, speed, &speed);
-                if (e.empty()) e = pitch_length_error(n[i], p[i]->pitch_permille, speed);
-                if (!e.empty()) refuse(e);
-                tempo = speed != 1000;
-                if (p[i]->pitch_permille != 1000) {
-                    pitches[(size_t)i] = pitch_design(*p[i]);
-                    stage[(size_t)i].pitch = &pitches[(size_t)i];
-                }
-            } else if (n[i] >= kTempoMaxSamples) {
-                refuse(strfmt("tempo: %lld samples, a row must stay below 2^31 - %d", (long long)n[i], kTempoRadius));
-            }
-            if (tempo) {
-                tempos[(size_t)i].speed = speed;
-                stage[(size_t)i].tempo = &tempos[(size_t)i];
-            }
-            if (n[i] > 0 && in[i] == out[i] && (stage[(size_t)i].pitch || stage[(size_t)i].tempo)) refuse("pitch: out is in");
+    std::vector<PitchScan> pitches;
+    std::vector<TempoScan> tempos;
+    return part_rows(h, "pitch", !p || !t || !n_out, in, n, rows, out, n_out, nullptr, [&](int i, PartStages& st) {
+        if (p[i]) row_refuse(i, pitch_opts_error(p[i]));
+        if (t[i]) row_refuse(i, tempo_opts_error(t[i]));
+        PitchSteps run{t[i] ? t[i]->speed_permille : 1000, false, t[i] != nullptr};
+        if (p[i]) {   // the pair resolves to the effective speed, and the tempo at 1000 is the identity
+            std::string e = pitch_steps(p[i]->pitch_permille, run.E, &run);
+            if (e.empty()) e = pitch_length_error(n[i], p[i]->pitch_permille, run.E);
+            row_refuse(i, e);
+            if (run.resample) pitches[(size_t)i] = pitch_design(*p[i]);
+        } else if (n[i] >= kTempoMaxSamples) {
+            row_refuse(i, strfmt("tempo: %lld samples, a row must stay below 2^31 - %d", (long long)n[i], kTempoRadius));
         }
-        if (rows > 0) pitch_rows_device(m, stage.data(), in, n, rows, out, n_out);
-    });
+        tempos[(size_t)i].speed = run.E;
+        st.pitch = run.resample ? &pitches[(size_t)i] : nullptr;
+        st.tempo = run.tempo ? &tempos[(size_t)i] : nullptr;
+        if (n[i] > 0 && in[i] == out[i] && (st.pitch || st.tempo)) row_refuse(i, "pitch: out is in");
+    }, pitches, tempos);
 }
 
 // the pitch of a joined call's parts, attached to the handle (pitch.cpp checks and designs it, and stays a file that builds without HIP)
-int ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p) {
-    DspExt v;
-    if (p) {
-        const std::string err = pitch_opts_error(p);
-        if (!err.empty()) return fail(err);
-        v.pitch = true;
-        v.pit = pitch_design(*p);
-    }
-    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.pitch = v.pitch; e->v.pit = v.pit; }))
-        return fail(strfmt("pitch: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
-    return PTTS_OK;
-}
+int ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p) { return ext_set(e, "pitch", p, pitch_opts_error, pitch_design, &DspExt::pitch, &DspExt::pit); }
 
 // the device form of ptts_join on host rows: k_join, as ptts_generate_joined launches it
 int ptts_join_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, float* out) {

@@ -78,16 +78,7 @@ using namespace ptts;
 extern "C" {
 
 int ptts_dsp_ext_set_compressor(ptts_dsp_ext* e, const ptts_compressor_opts* c) {
-    DspExt v;   // (the design is made outside the registry's mutex)
-    if (c) {
-        const std::string err = cmp_opts_error(c);
-        if (!err.empty()) return fail(err);
-        v.compress = true;
-        v.cmp = cmp_design(*c);
-    }
-    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.compress = v.compress; e->v.cmp = v.cmp; }))
-        return fail(strfmt("compressor: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
-    return PTTS_OK;
+    return ext_set(e, "compressor", c, cmp_opts_error, cmp_design, &DspExt::compress, &DspExt::cmp);
 }
 
 int ptts_compress_gain(const ptts_compressor_opts* c, double level_db, double* gain_db) {

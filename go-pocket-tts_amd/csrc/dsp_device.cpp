@@ -1,8 +1,9 @@
 // dsp_device.cpp -- the host side of the device post-processing (dsp.hip, compressor.hip, limiter.hip, true_peak.hip):
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
-// them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the same for
-// the trim (trim.hip), the tempo (tempo.hip) and the pitch (pitch.hip, with its one table image per model) of a joined call's parts.
+// them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the part
+// stages of a joined call -- the trim (trim.hip), the pitch (pitch.hip, with its one table image per model) and the tempo (tempo.hip): their table
+// builders, the one chain that runs them in that order (parts_launch) and the one round trip of host rows through it (part_rows_device).
 #include <cmath>
 
 #include "row_tables.h"
@@ -286,8 +287,16 @@ void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_
     PTTS_HIP(hipStreamSynchronize(s));
 }
 
-// ---- the trim (trim.hip; trim.h has the rule) ----
+// ---- the part stages of a joined call: the trim (trim.hip; trim.h), the pitch (pitch.hip; pitch.h), the tempo (tempo.hip; tempo.h) ----
 
+PitchImage::~PitchImage() {
+    if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
+    if (staged) (void)hipHostFree(staged);
+}
+
+namespace {
+// The trim's tables: rows[i] states src, dst and n, key[i] its design; their scratch (WORK_TRIM_SCRATCH) and their tables are made here, one launch
+// sequence per table.  Returns the device copy of the rows' records, [rows.size()], complete behind the launches
 const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const std::vector<const TrimScan*>& key, hipStream_t s) {
     size_t tiles = 0;
     for (const TrimRow& r : rows) tiles += (size_t)scan_tiles(std::max<int64_t>(r.n, 0));
@@ -306,53 +315,8 @@ const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const st
     return info;
 }
 
-void trim_rows_device(Model& m, const TrimScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info) {
-    std::lock_guard<std::mutex> lock(m.mu);
-    m.use_device();
-    hipStream_t s = m.stream;
-    // the rows, then their trimmed forms; a row that stays on the host takes no bytes
-    std::vector<size_t> bytes((size_t)rows * 2);
-    std::unique_ptr<bool[]> skip(new bool[(size_t)rows * 2 + 1]);
-    for (int i = 0; i < rows; i++) {
-        const bool sk = !design[i] || n[i] <= 0;
-        skip[(size_t)i] = skip[(size_t)(rows + i)] = sk;
-        bytes[(size_t)i] = bytes[(size_t)(rows + i)] = sk ? 0 : (size_t)n[i] * sizeof(float);
-    }
-    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
-    std::vector<TrimRow> tr;
-    std::vector<const TrimScan*> key;
-    std::vector<int> row_of;
-    for (int i = 0; i < rows; i++) {
-        info[i] = ptts_trim_info{0, n[i], n[i], 0, 0, 0};
-        if (skip[(size_t)i]) {   // nothing to do on the device: a copy
-            if (n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
-            continue;
-        }
-        buf.upload(i, in[i], s);
-        TrimRow r{};
-        r.src = (const float*)buf.row(i);
-        r.dst = (float*)buf.row(rows + i);
-        r.n = n[i];
-        tr.push_back(r);
-        key.push_back(design[i]);
-        row_of.push_back(i);
-    }
-    if (tr.empty()) return;
-    const ptts_trim_info* info_dev = trim_launch(m, tr, key, s);
-    std::vector<ptts_trim_info> got(tr.size());
-    PTTS_HIP(hipMemcpyAsync(got.data(), info_dev, got.size() * sizeof(ptts_trim_info), hipMemcpyDeviceToHost, s));
-    PTTS_HIP(hipStreamSynchronize(s));   // the lengths decide what comes back
-    for (size_t k = 0; k < tr.size(); k++) {
-        const int i = row_of[k];
-        if (got[k].n_out < 0 || got[k].n_out > n[i]) throw Error(PTTS_EINVAL, "ptts-hip: internal: a trimmed row is longer than the row");
-        info[i] = got[k];
-        if (got[k].n_out > 0) PTTS_HIP(hipMemcpyAsync(out[i], tr[k].dst, (size_t)got[k].n_out * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    PTTS_HIP(hipStreamSynchronize(s));
-}
-
-// ---- the tempo (tempo.hip; tempo.h has the rule) ----
-
+// The tempo's tables: rows[i] states src, dst and n, key[i] its design; n_out (host arithmetic), the position tables (WORK_TEMPO_SCRATCH) and the row
+// tables are made here, one launch of each kernel per table
 void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const TempoScan*>& key, hipStream_t s) {
     size_t hops = 0;
     for (size_t i = 0; i < rows.size(); i++) {
@@ -374,54 +338,7 @@ void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const
     });
 }
 
-void tempo_rows_device(Model& m, const TempoScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
-    std::lock_guard<std::mutex> lock(m.mu);
-    m.use_device();
-    hipStream_t s = m.stream;
-    // the rows, then their time-scaled forms; a row that stays on the host takes no bytes
-    std::vector<size_t> bytes((size_t)rows * 2);
-    std::unique_ptr<bool[]> skip(new bool[(size_t)rows * 2 + 1]);
-    for (int i = 0; i < rows; i++) {
-        const int64_t len = design[i] ? tempo_length(n[i], design[i]->speed) : std::max<int64_t>(n[i], 0);
-        n_out[i] = len;
-        const bool sk = !design[i] || len <= 0;
-        skip[(size_t)i] = skip[(size_t)(rows + i)] = sk;
-        bytes[(size_t)i] = sk ? 0 : (size_t)n[i] * sizeof(float);
-        bytes[(size_t)(rows + i)] = sk ? 0 : (size_t)len * sizeof(float);
-    }
-    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
-    std::vector<TempoRow> tr;
-    std::vector<const TempoScan*> key;
-    std::vector<int> row_of;
-    for (int i = 0; i < rows; i++) {
-        if (skip[(size_t)i]) {   // nothing to do on the device: a copy, or an empty row
-            if (!design[i] && n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
-            continue;
-        }
-        buf.upload(i, in[i], s);
-        TempoRow r{};
-        r.src = (const float*)buf.row(i);
-        r.dst = (float*)buf.row(rows + i);
-        r.n = n[i];
-        tr.push_back(r);
-        key.push_back(design[i]);
-        row_of.push_back(i);
-    }
-    if (tr.empty()) return;
-    tempo_launch(m, tr, key, s);
-    for (int i : row_of) buf.download(rows + i, out[i], s);
-    PTTS_HIP(hipStreamSynchronize(s));
-}
-
-// ---- the pitch (pitch.hip; pitch.h has the rule) ----
-
-PitchImage::~PitchImage() {
-    if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
-    if (staged) (void)hipHostFree(staged);
-}
-
-namespace {
-// the table's image on the device: one per model whatever the pitches.  First use: made from pitch.cpp's table and queued on s from page-locked
+// the pitch table's image on the device: one per model whatever the pitches.  First use: made from pitch.cpp's table and queued on s from page-locked
 // memory, nothing waits on the host; launches on s follow it, another stream waits for `ready` (as rate_filter, resample.cpp)
 const float* pitch_image(Model& m, hipStream_t s) {
     if (m.pitch_image) {
@@ -446,8 +363,9 @@ const float* pitch_image(Model& m, hipStream_t s) {
     m.pitch_image = std::move(f);
     return m.pitch_image->image.as<float>();
 }
-}  // namespace
 
+// The tables of the pitch's resampling step: rows[i] states src, dst and n, key[i] its design (p is not 1000); n_out (host arithmetic), the table's
+// image (first use: made and uploaded) and the row tables are made here, one launch per table
 void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const PitchScan*>& key, hipStream_t s) {
     for (size_t i = 0; i < rows.size(); i++) {
         rows[i].n_out = pitch_resample_length(rows[i].n, key[i]->p);
@@ -464,67 +382,117 @@ void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const
     });
 }
 
-void pitch_rows_device(Model& m, const PitchStage* stage, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
+// one stage of parts_launch behind the trim: the rows that have it, each reading where its predecessor left the row (PartRow::out, n_out) and
+// writing its own destination, through the stage's table builder; then every such row stands at what the stage made.  False: no row has the stage
+template <class Row, class Design, class Launch>
+bool part_stage(std::vector<PartRow>& rows, const Design* PartStages::*which, float* PartRow::*dst, Launch&& launch) {
+    std::vector<Row> t;
+    std::vector<const Design*> key;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (!(rows[i].st.*which)) continue;
+        Row r{};
+        r.src = rows[i].out; r.dst = rows[i].*dst; r.n = rows[i].n_out;
+        t.push_back(r);
+        key.push_back(rows[i].st.*which);
+        at.push_back(i);
+    }
+    if (t.empty()) return false;
+    launch(t, key);
+    for (size_t k = 0; k < t.size(); k++) {
+        rows[at[k]].out = t[k].dst;
+        rows[at[k]].n_out = t[k].n_out;
+    }
+    return true;
+}
+}  // namespace
+
+void parts_launch(Model& m, std::vector<PartRow>& rows, hipStream_t s, const std::function<void(const char*)>& phase, const char* unit) {
+    std::vector<TrimRow> tr;
+    std::vector<const TrimScan*> key;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < rows.size(); i++) {
+        PartRow& r = rows[i];
+        r.out = r.src; r.n_out = r.n;
+        if (!r.st.trim) continue;
+        TrimRow t{};
+        t.src = r.src; t.dst = r.trimmed; t.n = r.n;
+        tr.push_back(t);
+        key.push_back(r.st.trim);
+        at.push_back(i);
+    }
+    if (!tr.empty()) {
+        const ptts_trim_info* info_dev = trim_launch(m, tr, key, s);
+        ptts_trim_info* const got = static_cast<ptts_trim_info*>(m.trim_info.ensure(tr.size() * sizeof(ptts_trim_info)));
+        PTTS_HIP(hipMemcpyAsync(got, info_dev, tr.size() * sizeof(ptts_trim_info), hipMemcpyDeviceToHost, s));
+        PTTS_HIP(hipStreamSynchronize(s));   // the lengths decide what the later stages read and what comes back
+        for (size_t k = 0; k < tr.size(); k++) {
+            PartRow& r = rows[at[k]];
+            if (got[k].n_out < 0 || got[k].n_out > r.n) throw Error(PTTS_EINVAL, strfmt("ptts-hip: internal: a trimmed %s is longer than the %s", unit, unit));
+            r.info = got[k];
+            r.out = r.trimmed; r.n_out = got[k].n_out;
+        }
+        if (phase) phase("trim");
+    }
+    if (part_stage<PitchRow>(rows, &PartStages::pitch, &PartRow::shifted, [&](std::vector<PitchRow>& t, const std::vector<const PitchScan*>& k) { pitch_launch(m, t, k, s); }) && phase)
+        phase("pitch");
+    if (part_stage<TempoRow>(rows, &PartStages::tempo, &PartRow::scaled, [&](std::vector<TempoRow>& t, const std::vector<const TempoScan*>& k) { tempo_launch(m, t, k, s); }) && phase)
+        phase("tempo");
+}
+
+void part_rows_device(Model& m, const PartStages* per_row, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out,
+                      ptts_trim_info* info) {
     std::lock_guard<std::mutex> lock(m.mu);
     m.use_device();
     hipStream_t s = m.stream;
-    // the rows, then their resampled forms, then their time-scaled forms; a row takes bytes only for the steps it has
+    // the rows, then their trimmed, their resampled and their time-scaled forms; a row takes bytes only for the steps it has, and none where it
+    // stays on the host
     const size_t R = (size_t)rows;
-    std::vector<size_t> bytes(R * 3, 0);
-    std::unique_ptr<bool[]> skip(new bool[R * 3 + 1]);
-    std::vector<int64_t> n_r(R);
+    std::vector<size_t> bytes(R * 4, 0);
+    std::unique_ptr<bool[]> skip(new bool[R * 4 + 1]);
     for (size_t i = 0; i < R; i++) {
-        const PitchStage& st = stage[i];
-        n_r[i] = st.pitch ? pitch_resample_length(n[i], st.pitch->p) : std::max<int64_t>(n[i], 0);
-        n_out[i] = st.tempo ? tempo_length(n_r[i], st.tempo->speed) : n_r[i];
-        const bool on = (st.pitch || st.tempo) && n_out[i] > 0;
+        const PartStages& st = per_row[i];
+        // the longest each form can be: the trim only shortens, and the two length functions are monotone
+        const int64_t n_t = std::max<int64_t>(n[i], 0);
+        const int64_t n_r = st.pitch ? pitch_resample_length(n_t, st.pitch->p) : n_t;
+        const int64_t n_f = st.tempo ? tempo_length(n_r, st.tempo->speed) : n_r;
+        if (n_out) n_out[i] = n_f;
+        if (info) info[i] = ptts_trim_info{0, n[i], n[i], 0, 0, 0};
+        const bool on = (st.trim || st.pitch || st.tempo) && n_f > 0;
         skip[i] = !on;
-        skip[R + i] = !(on && st.pitch);
-        skip[2 * R + i] = !(on && st.tempo);
+        skip[R + i] = !(on && st.trim);
+        skip[2 * R + i] = !(on && st.pitch);
+        skip[3 * R + i] = !(on && st.tempo);
         if (!skip[i]) bytes[i] = (size_t)n[i] * sizeof(float);
-        if (!skip[R + i]) bytes[R + i] = (size_t)n_r[i] * sizeof(float);
-        if (!skip[2 * R + i]) bytes[2 * R + i] = (size_t)n_out[i] * sizeof(float);
+        if (!skip[R + i]) bytes[R + i] = (size_t)n_t * sizeof(float);
+        if (!skip[2 * R + i]) bytes[2 * R + i] = (size_t)n_r * sizeof(float);
+        if (!skip[3 * R + i]) bytes[3 * R + i] = (size_t)n_f * sizeof(float);
     }
     PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes), skip.get());
-    std::vector<PitchRow> pr;
-    std::vector<const PitchScan*> pkey;
-    std::vector<TempoRow> tr;
-    std::vector<const TempoScan*> tkey;
-    std::vector<std::pair<int, int>> back;   // (the packed row that holds the result, the caller's row)
+    std::vector<PartRow> pr;
+    std::vector<int> row_of;
     for (int i = 0; i < rows; i++) {
-        const PitchStage& st = stage[i];
+        const PartStages& st = per_row[i];
         if (skip[(size_t)i]) {   // nothing to do on the device: a copy, or an empty result
-            if (!st.pitch && !st.tempo && n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
+            if (!st.trim && !st.pitch && !st.tempo && n[i] > 0 && out[i] != in[i]) std::memmove(out[i], in[i], (size_t)n[i] * sizeof(float));
             continue;
         }
         buf.upload(i, in[i], s);
-        const float* z = (const float*)buf.row(i);
-        int at = i;
-        if (st.pitch) {
-            PitchRow r{};
-            r.src = z;
-            r.dst = (float*)buf.row(rows + i);
-            r.n = n[i];
-            pr.push_back(r);
-            pkey.push_back(st.pitch);
-            z = r.dst;
-            at = rows + i;
-        }
-        if (st.tempo) {
-            TempoRow r{};
-            r.src = z;
-            r.dst = (float*)buf.row(2 * rows + i);
-            r.n = n_r[(size_t)i];
-            tr.push_back(r);
-            tkey.push_back(st.tempo);
-            at = 2 * rows + i;
-        }
-        back.emplace_back(at, i);
+        PartRow r{(const float*)buf.row(i), n[i], st};
+        if (st.trim) r.trimmed = (float*)buf.row(rows + i);
+        if (st.pitch) r.shifted = (float*)buf.row(2 * rows + i);
+        if (st.tempo) r.scaled = (float*)buf.row(3 * rows + i);
+        pr.push_back(r);
+        row_of.push_back(i);
     }
-    if (back.empty()) return;
-    if (!pr.empty()) pitch_launch(m, pr, pkey, s);
-    if (!tr.empty()) tempo_launch(m, tr, tkey, s);
-    for (const auto& b : back) buf.download(b.first, out[b.second], s);
+    if (pr.empty()) return;
+    parts_launch(m, pr, s);
+    for (size_t k = 0; k < pr.size(); k++) {
+        const int i = row_of[k];
+        if (n_out) n_out[i] = pr[k].n_out;
+        if (info && pr[k].st.trim) info[i] = pr[k].info;
+        if (pr[k].n_out > 0) PTTS_HIP(hipMemcpyAsync(out[i], pr[k].out, (size_t)pr[k].n_out * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
     PTTS_HIP(hipStreamSynchronize(s));
 }
 

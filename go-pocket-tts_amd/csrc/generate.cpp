@@ -213,13 +213,13 @@ struct JoinSink {
     int64_t frames = 0;
     int fail = PTTS_OK;           // the code of the first chunk, in text order, that was cancelled or ran past the decoder's reach
     std::string fail_msg;
-    bool trim = false;            // the join options' ext carries a trim (resolved once, before anything launches): every part goes through
-    TrimScan trm{};               // k_trim_* in front of k_join, and its length is what comes back in `info`
-    ptts_trim_info* info = nullptr;   // page-locked, [max_batch]: a group's records (Model::trim_info)
-    bool tempo = false;           // ... and a tempo (tempo.h): every part goes through k_tempo_* behind the trim and in front of k_join, and its
-    TempoScan tmp{};              // length is tempo_length of what the trim left: host arithmetic, nothing comes back
-    bool pitch = false;           // ... and a pitch other than 1000 (pitch.h): every part goes through k_pitch_resample between the two.  The pair
-    PitchScan pit{};              // (speed, pitch) was resolved to the effective speed beforehand: `tmp` carries it, and `tempo` is off at 1000
+    // What the join options' ext asks for every part in front of k_join, resolved once, before anything launches (runtime.h PartStages; parts_launch
+    // runs it): a trim, whose length comes back from the device; a pitch other than 1000; a tempo -- behind a pitch the pair (speed, pitch) was
+    // resolved beforehand (pitch.h pitch_steps), `tmp` carries the effective speed and the step is off at 1000.  The designs the stages point to:
+    PartStages stages;
+    TrimScan trm{};
+    PitchScan pit{};
+    TempoScan tmp{};
 };
 
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
@@ -609,76 +609,37 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
     if (join->fail != PTTS_OK) return;   // the call fails: nothing of this group is decoded
     decode_rest(std::min(steps_run, Tmax));
     const JoinLens& l = join->lens;
-    // The parts as the join sees them: the decoder's rows, or, with a trim, what k_trim_* keeps of them in a buffer of the same row stride; the
-    // lengths then come back in one page-locked copy behind the launches, and everything below counts in them
-    const float* part0 = pcm->as<float>();
-    std::vector<int64_t> len((size_t)B);
-    for (int i = 0; i < B; i++) len[(size_t)i] = (int64_t)nf[i] * spf;
-    if (join->trim) {
-        float* const kept = m.work(WORK_TRIMMED, std::max<size_t>((size_t)B * T * spf, 1) * sizeof(float)).as<float>();
-        std::vector<TrimRow> tr((size_t)B);
-        for (int i = 0; i < B; i++) {
-            tr[(size_t)i].src = part0 + (size_t)i * T * spf;
-            tr[(size_t)i].dst = kept + (size_t)i * T * spf;
-            tr[(size_t)i].n = len[(size_t)i];
-        }
-        const ptts_trim_info* info_dev = trim_launch(m, tr, std::vector<const TrimScan*>((size_t)B, &join->trm), s);
-        PTTS_HIP(hipMemcpyAsync(join->info, info_dev, (size_t)B * sizeof(ptts_trim_info), hipMemcpyDeviceToHost, s));
-        PTTS_HIP(hipStreamSynchronize(s));
-        for (int i = 0; i < B; i++) {
-            const int64_t n_out = join->info[i].n_out;
-            if (n_out < 0 || n_out > len[(size_t)i]) throw Error(PTTS_EINVAL, "ptts-hip: internal: a trimmed part is longer than the part");
-            len[(size_t)i] = n_out;
-        }
-        part0 = kept;
-        mark("trim");
+    // The parts as the join sees them: the decoder's rows through the part stages (parts_launch: the trim, the pitch, the tempo, each where the call
+    // has it).  What the trim keeps lies in a buffer of the decoder buffer's row stride; the resampled and the time-scaled forms in buffers whose
+    // row stride holds the longest a decoded row can become.  Everything below counts in the lengths that come back
+    const PartStages& st = join->stages;
+    const size_t decoded = (size_t)T * spf;
+    float* const kept = st.trim ? m.work(WORK_TRIMMED, std::max<size_t>((size_t)B * decoded, 1) * sizeof(float)).as<float>() : nullptr;
+    const int64_t wide_p = st.pitch ? std::max<int64_t>(decoded, pitch_resample_length(decoded, st.pitch->p)) : (int64_t)decoded;
+    float* const shifted = st.pitch ? m.work(WORK_PITCH, std::max<size_t>((size_t)B * (size_t)wide_p, 1) * sizeof(float)).as<float>() : nullptr;
+    const int64_t wide_t = st.tempo ? std::max(wide_p, tempo_length(wide_p, st.tempo->speed)) : wide_p;
+    float* const scaled = st.tempo ? m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide_t, 1) * sizeof(float)).as<float>() : nullptr;
+    std::vector<PartRow> part((size_t)B);
+    for (int i = 0; i < B; i++) {
+        PartRow& r = part[(size_t)i];
+        r.src = pcm->as<float>() + (size_t)i * decoded; r.n = (int64_t)nf[i] * spf; r.st = st;
+        if (kept) r.trimmed = kept + (size_t)i * decoded;
+        if (shifted) r.shifted = shifted + (size_t)i * (size_t)wide_p;
+        if (scaled) r.scaled = scaled + (size_t)i * (size_t)wide_t;
     }
-    // ... with a pitch their resampled forms, in a buffer whose row stride holds the longest a decoded row can become
-    int64_t stride = (int64_t)T * spf;
-    if (join->pitch) {
-        const int64_t wide = std::max(stride, pitch_resample_length(stride, join->pit.p));
-        float* const shifted = m.work(WORK_PITCH, std::max<size_t>((size_t)B * (size_t)wide, 1) * sizeof(float)).as<float>();
-        std::vector<PitchRow> pr((size_t)B);
-        for (int i = 0; i < B; i++) {
-            pr[(size_t)i].src = part0 + (size_t)i * (size_t)stride;
-            pr[(size_t)i].dst = shifted + (size_t)i * (size_t)wide;
-            pr[(size_t)i].n = len[(size_t)i];
-        }
-        pitch_launch(m, pr, std::vector<const PitchScan*>((size_t)B, &join->pit), s);
-        for (int i = 0; i < B; i++) len[(size_t)i] = pr[(size_t)i].n_out;
-        part0 = shifted;
-        stride = wide;
-        mark("pitch");
-    }
-    // ... and with a tempo their time-scaled forms, likewise
-    if (join->tempo) {
-        const int64_t wide = std::max(stride, tempo_length(stride, join->tmp.speed));
-        float* const scaled = m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide, 1) * sizeof(float)).as<float>();
-        std::vector<TempoRow> tr((size_t)B);
-        for (int i = 0; i < B; i++) {
-            tr[(size_t)i].src = part0 + (size_t)i * (size_t)stride;
-            tr[(size_t)i].dst = scaled + (size_t)i * (size_t)wide;
-            tr[(size_t)i].n = len[(size_t)i];
-        }
-        tempo_launch(m, tr, std::vector<const TempoScan*>((size_t)B, &join->tmp), s);
-        for (int i = 0; i < B; i++) len[(size_t)i] = tr[(size_t)i].n_out;
-        part0 = scaled;
-        stride = wide;
-        mark("tempo");
-    }
+    parts_launch(m, part, s, [&](const char* what) { mark(what); }, "part");
     std::vector<JoinRow> rows;
     for (int i = 0; i < B; i++) {
         ptts_join_part& p = join->parts[idx[(size_t)i]];
-        const int64_t n = len[(size_t)i];
-        const float* src = part0 + (size_t)i * (size_t)stride;
+        const int64_t n = part[(size_t)i].n_out;
         const bool first = join->n_prev < 0;
         const int64_t k = first ? 0 : join_seam(l.xfade, join->n_prev, n);
         const int64_t off = first ? 0 : join->at + l.gap - k;
-        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, len[(size_t)i + 1]) : 0;   // (the group's last row stores its tail whole)
+        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, part[(size_t)i + 1].n_out) : 0;   // (the group's last row stores its tail whole)
         if (off + n > join->cap) throw Error(PTTS_EINVAL, "ptts-hip: internal: the joined row is smaller than the text");
         JoinRow r{};
-        r.src = src;
-        r.prev = !k ? nullptr : i ? part0 + (size_t)(i - 1) * (size_t)stride + (join->n_prev - k) : join->row + off;
+        r.src = part[(size_t)i].out;
+        r.prev = !k ? nullptr : i ? part[(size_t)i - 1].out + (join->n_prev - k) : join->row + off;
         r.dst = join->row;
         r.off = off; r.n = n - k_next; r.k = (int32_t)k; r.gap = first ? 0 : (int32_t)l.gap;
         rows.push_back(r);
@@ -916,19 +877,16 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     if (o.dsp) {   // the trim and the tempo of the parts, resolved once: the chain below never sees them
         e = dsp_resolve(o.dsp, &spec);
         if (!e.empty()) refuse("join: " + e);
-        sink.trim = spec.trim;
         sink.trm = spec.trm;
-        sink.tempo = spec.tempo;
+        sink.pit = spec.pit;
         sink.tmp = spec.tmp;
+        PitchSteps run{sink.tmp.speed, false, spec.tempo};
         if (spec.pitch) {   // the pair (speed, pitch) becomes the tempo's effective speed; either step may be the identity, and then it is not run
-            int32_t E = 0;
-            e = pitch_speed_error(spec.pit.p, spec.tempo ? spec.tmp.speed : 1000, &E);
+            e = pitch_steps(spec.pit.p, spec.tempo ? spec.tmp.speed : 1000, &run);
             if (!e.empty()) refuse("join: " + e);
-            sink.pitch = spec.pit.p != 1000;
-            sink.pit = spec.pit;
-            sink.tempo = E != 1000;
-            sink.tmp.speed = E;
+            sink.tmp.speed = run.E;
         }
+        sink.stages = PartStages{spec.trim ? &sink.trm : nullptr, run.resample ? &sink.pit : nullptr, run.tempo ? &sink.tmp : nullptr};
     }
     if (streamed) {   // window after window only the causal stages run
         if (o.loudness) dsp_spec_loudness(spec, nullptr);
@@ -948,8 +906,8 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (l != lsd) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d has lsd_steps %d and request 0 has %d: the groups would leave text order", i, l, lsd)); }
         // (the trim only shortens; pitch_resample_length and tempo_length are monotone)
         const int64_t budget = (int64_t)std::min(resolve_max_steps(q), mimi_frame_limit(d)) * spf;
-        const int64_t shifted = sink.pitch ? pitch_resample_length(budget, sink.pit.p) : budget;
-        const int64_t scaled = sink.tempo ? tempo_length(shifted, sink.tmp.speed) : shifted;
+        const int64_t shifted = sink.stages.pitch ? pitch_resample_length(budget, sink.pit.p) : budget;
+        const int64_t scaled = sink.stages.tempo ? tempo_length(shifted, sink.tmp.speed) : shifted;
         bound += std::max(budget, std::max(shifted, scaled)) + (i ? sink.lens.gap : 0);
     }
     if (bound >= kJoinMaxSamples) refuse(strfmt("join: the step budgets allow %lld samples, the joined length must stay below 2^31", (long long)bound));
@@ -966,7 +924,6 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
             js->setup(o, sink.lens, bound, s);
         }
         // ---- the groups, as generate() cuts them; a streamed call's first group may be smaller ----
-        if (sink.trim) sink.info = static_cast<ptts_trim_info*>(m.trim_info.ensure((size_t)mb * sizeof(ptts_trim_info)));
         for (int o0 = 0, size = so && so->first_group ? so->first_group : mb; o0 < n && sink.fail == PTTS_OK; o0 += size, size = mb) {
             std::vector<int> idx;
             for (int i = o0; i < std::min(n, o0 + size); i++) idx.push_back(i);

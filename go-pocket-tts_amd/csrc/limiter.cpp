@@ -73,16 +73,7 @@ using namespace ptts;
 extern "C" {
 
 int ptts_dsp_ext_set_limiter(ptts_dsp_ext* e, const ptts_limiter_opts* l) {
-    DspExt v;   // (the design is made outside the registry's mutex)
-    if (l) {
-        const std::string err = lim_opts_error(l);
-        if (!err.empty()) return fail(err);
-        v.limit = true;
-        v.lim = lim_design(*l);
-    }
-    if (!handle_with(e, HANDLE_DSP_EXT, [&] { e->v.limit = v.limit; e->v.lim = v.lim; }))
-        return fail(strfmt("limiter: ext %p is not a live handle of ptts_dsp_ext_create", (const void*)e));
-    return PTTS_OK;
+    return ext_set(e, "limiter", l, lim_opts_error, lim_design, &DspExt::limit, &DspExt::lim);
 }
 
 int ptts_limit_apply(const ptts_limiter_opts* l, float* samples, int64_t n) {

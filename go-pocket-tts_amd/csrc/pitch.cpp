@@ -1,7 +1,7 @@
 // pitch.cpp -- the pitch of one part of a joined text, on the host (include/ptts.h ptts_pitch_opts, ptts_pitch_speed, ptts_pitch_resample_length,
 // ptts_pitch_resample, ptts_pitch_length, ptts_pitch_apply, ptts_pitch_table; pitch.h has the rule): the checks of the caller's options, the
 // prototype table and the statement of the result, which k_pitch_resample (pitch.hip) gives bit for bit and the tempo (tempo.cpp) finishes.
-// ptts_dsp_ext_set_pitch is with the handle's other setters (capi.cpp).
+// ptts_dsp_ext_set_pitch is in capi.cpp, with the handle's trim and tempo setters (dsp_ext.h has the one setter they all call).
 // No HIP header: the file builds with a plain C++ compiler, with tempo.cpp alone (tests/test_pitch_cpu.py does, with sanitizers).
 //
 // A tap is two fused multiply-adds, written as such; the output's gain is one f32 product.  Nothing else here may be contracted.
@@ -32,11 +32,13 @@ std::string pitch_opts_error(const ptts_pitch_opts* p) {
     return std::string();
 }
 
-std::string pitch_speed_error(int32_t p, int32_t s, int32_t* E) {
+std::string pitch_steps(int32_t p, int32_t s, PitchSteps* st) {
     const int32_t e = pitch_speed(s, p);
-    if (E) *E = e;
+    *st = PitchSteps{e, false, false};
     if (e < 500 || e > 2000)
         return strfmt("pitch: speed_permille %d with pitch_permille %d needs the tempo at %d, which is not from 500 to 2000", s, p, e);
+    st->resample = p != 1000;
+    st->tempo = e != 1000;
     return std::string();
 }
 
@@ -110,15 +112,14 @@ void pitch_resample_host(const PitchScan& d, const float* x, int64_t n, float* o
 using namespace ptts;
 
 namespace {
-// the options of one call, checked: the design, the tempo's speed s (1000 without one) and the effective speed E
-struct Stage { PitchScan d; int32_t s, E; };
+// the options of one call, checked: the design and what the pair resolves to (pitch_steps), the tempo's speed being 1000 without one
+struct Stage { PitchScan d; PitchSteps run; };
 std::string stage_of(const ptts_pitch_opts* p, const ptts_tempo_opts* t, Stage* st) {
     std::string e = pitch_opts_error(p);
     if (e.empty() && t) e = tempo_opts_error(t);
     if (!e.empty()) return e;
     st->d = pitch_design(*p);
-    st->s = t ? t->speed_permille : 1000;
-    return pitch_speed_error(st->d.p, st->s, &st->E);
+    return pitch_steps(st->d.p, t ? t->speed_permille : 1000, &st->run);
 }
 }  // namespace
 
@@ -128,7 +129,7 @@ int32_t ptts_pitch_speed(const ptts_pitch_opts* p, const ptts_tempo_opts* t) {
     Stage st;
     const std::string err = stage_of(p, t, &st);
     if (!err.empty()) return -(int32_t)fail(err);
-    return st.E;
+    return st.run.E;
 }
 
 int64_t ptts_pitch_resample_length(const ptts_pitch_opts* p, int64_t n) {
@@ -156,34 +157,34 @@ int ptts_pitch_resample(const ptts_pitch_opts* p, const float* in, int64_t n, fl
 int64_t ptts_pitch_length(const ptts_pitch_opts* p, const ptts_tempo_opts* t, int64_t n) {
     Stage st;
     std::string err = stage_of(p, t, &st);
-    if (err.empty()) err = pitch_length_error(n, st.d.p, st.E);
+    if (err.empty()) err = pitch_length_error(n, st.d.p, st.run.E);
     if (!err.empty()) return -(int64_t)fail(err);
-    return tempo_length(pitch_resample_length(n, st.d.p), st.E);
+    return tempo_length(pitch_resample_length(n, st.d.p), st.run.E);
 }
 
 int ptts_pitch_apply(const ptts_pitch_opts* p, const ptts_tempo_opts* t, const float* in, int64_t n, float* out) {
     Stage st;
     std::string err = stage_of(p, t, &st);
-    if (err.empty()) err = pitch_length_error(n, st.d.p, st.E);
+    if (err.empty()) err = pitch_length_error(n, st.d.p, st.run.E);
     if (!err.empty()) return fail(err);
-    const int64_t n_r = pitch_resample_length(n, st.d.p), n_f = tempo_length(n_r, st.E);
+    const int64_t n_r = pitch_resample_length(n, st.d.p), n_f = tempo_length(n_r, st.run.E);
     if ((n > 0 && !in) || (n_f > 0 && !out)) return fail("pitch: null argument");
     if (n > 0 && in == out) return fail("pitch: out is in (an output reads the inputs around where it writes)");
     // ptts_tempo_apply at E over ptts_pitch_resample; either step may be the identity
     std::vector<float> z;
     const float* zr = in;
-    if (st.d.p != 1000) {
-        if (st.E == 1000) { pitch_resample_host(st.d, in, n, out); return PTTS_OK; }
+    if (st.run.resample) {
+        if (!st.run.tempo) { pitch_resample_host(st.d, in, n, out); return PTTS_OK; }
         z.resize((size_t)std::max<int64_t>(n_r, 1));
         pitch_resample_host(st.d, in, n, z.data());
         zr = z.data();
     }
-    if (st.E == 1000) {
+    if (!st.run.tempo) {
         if (n > 0) std::memcpy(out, in, (size_t)n * sizeof(float));
         return PTTS_OK;
     }
     TempoScan td{};
-    td.speed = st.E;
+    td.speed = st.run.E;
     tempo_apply_host(td, zr, n_r, out);
     return PTTS_OK;
 }

@@ -53,8 +53,12 @@ PTTS_HD inline int64_t pitch_last(int64_t c, int32_t D) { return pitch_floor_div
 // empty: the caller's options are well formed (the size rules of ptts_dsp_ext_opts, pitch_permille in its range, reserved 0); otherwise the
 // message, naming the field
 std::string pitch_opts_error(const ptts_pitch_opts* p);
-// empty: the pair resolves to an effective speed from 500 to 2000 (*E receives it); otherwise the message, naming both fields and both values
-std::string pitch_speed_error(int32_t p, int32_t s, int32_t* E);
+// The pair (pitch p, speed s) of one row, both in permille (1000: none), resolved to the steps that run -- the one place that states the rule:
+// the resample unless p is 1000, the tempo at the effective speed E unless E is 1000
+struct PitchSteps { int32_t E; bool resample, tempo; };
+// empty: the pair resolves to an effective speed from 500 to 2000 (*st says what runs); otherwise the message, naming both fields and both
+// values, and *st holds E alone
+std::string pitch_steps(int32_t p, int32_t s, PitchSteps* st);
 // empty: a row of n samples keeps its resampled and its final length below kTempoMaxSamples
 std::string pitch_length_error(int64_t n, int32_t p, int32_t E);
 // the design of well-formed options

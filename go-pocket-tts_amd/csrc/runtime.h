@@ -66,15 +66,15 @@ enum WorkSlot : size_t {
     WORK_CONVERT_OUT = 26,       // ... and the packed output rows
     WORK_ENCODER_CLIP = 26,      // mimi_encode_clip: a voice clip at its own rate, in front of k_resample.  Shares WORK_CONVERT_OUT's storage (see above)
     WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words, then what dsp_scratch (dsp_spec.h) plans for each row's stages
-    WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin; join_rows_device: the parts, then the joined row
+    WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin; join_rows_device: the parts, then the joined row; part_rows_device: the rows, then their forms
     WORK_JOINED = 31,            // generate_joined: the text's joined row, sized before the first group runs and kept until the egress has read it
-    WORK_TRIMMED = 32,           // generate_joined with a trim: what k_trim_store keeps of a group's decoded rows, at the decoder buffer's row stride
-    WORK_TRIM_SCRATCH = 33,      // trim_launch: the rows' ptts_trim_info records, then their TrimTile tables
-    WORK_TEMPO = 34,             // generate_joined with a tempo: a group's time-scaled rows, at the stride of the longest a decoded row can become
-    WORK_TEMPO_SCRATCH = 35,     // tempo_launch: the rows' position tables
+    WORK_TRIMMED = 32,           // generate_joined with a trim: PartRow::trimmed of a group's rows, what k_trim_store keeps of the decoded rows, at the decoder buffer's row stride
+    WORK_TRIM_SCRATCH = 33,      // parts_launch, the trim: the rows' ptts_trim_info records, then their TrimTile tables
+    WORK_TEMPO = 34,             // generate_joined with a tempo: PartRow::scaled of a group's rows, at the stride of the longest a decoded row can become
+    WORK_TEMPO_SCRATCH = 35,     // parts_launch, the tempo: the rows' position tables
     WORK_JOIN_CARRY = 36,        // a streamed joined call: the chain's carried states between its windows (kernels.h kCarryDoubles)
     WORK_JOIN_STAGE = 37,        // ... and its egress where that cannot store into the result's buffer itself, indexed like that buffer
-    WORK_PITCH = 38,             // generate_joined with a pitch: a group's resampled rows, at the stride of the longest a decoded row can become
+    WORK_PITCH = 38,             // generate_joined with a pitch: PartRow::shifted of a group's rows, at the stride of the longest a decoded row can become
 };
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
@@ -145,11 +145,11 @@ struct Model {
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, dsp_device.cpp)
-    RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (trim_launch, dsp_device.cpp)
-    RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (tempo_launch, dsp_device.cpp)
-    RowRing<PitchRow, kPitchMaxDesigns * kPitchScanBytes> pitch_ring;   // k_pitch_resample's, likewise (pitch_launch, dsp_device.cpp)
+    RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (parts_launch, dsp_device.cpp)
+    RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (parts_launch, dsp_device.cpp)
+    RowRing<PitchRow, kPitchMaxDesigns * kPitchScanBytes> pitch_ring;   // k_pitch_resample's, likewise (parts_launch, dsp_device.cpp)
     std::unique_ptr<PitchImage> pitch_image;   // ... and its table, from the first call that names a pitch on
-    PinnedBuf trim_info;            // generate_joined with a trim: a group's ptts_trim_info records, [max_batch] (read under Model::mu, behind a stream wait)
+    PinnedBuf trim_info;            // parts_launch: the ptts_trim_info records of its rows with a trim, grown to their count (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
     // k_flow_cluster's bounded hand-offs gave up (a tile's workgroups were not running together: a masked or shared device): the steps concerned were
@@ -462,27 +462,30 @@ void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
 // ptts_join_rows: the parts packed into one device buffer with the joined row behind them, uploaded, join_launch, the joined row back, one wait.
 // Takes Model::mu.  The lengths are planned (join_plan) and out holds the joined length
 void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
-// The trim of a list of rows on s (trim.hip; trim.h has the rule): rows[i] states src, dst and n, key[i] its design; their scratch (WORK_TRIM_SCRATCH)
-// and their tables are made here, one launch sequence per table.  Returns the device copy of the rows' records, [rows.size()], complete behind the launches
-const ptts_trim_info* trim_launch(Model& m, std::vector<TrimRow>& rows, const std::vector<const TrimScan*>& key, hipStream_t s);
-// ptts_trim_rows: the rows packed into one device buffer with their trimmed forms behind them, uploaded, trim_launch, the records back, then what
-// stays of each row.  Takes Model::mu.  design[i] null: the row is copied on the host
-void trim_rows_device(Model& m, const TrimScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, ptts_trim_info* info);
-// The tempo of a list of rows on s (tempo.hip; tempo.h has the rule): rows[i] states src, dst and n, key[i] its design; n_out (host arithmetic),
-// the position tables (WORK_TEMPO_SCRATCH) and the row tables are made here, one launch of each kernel per table
-void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const TempoScan*>& key, hipStream_t s);
-// ptts_tempo_rows: the rows packed into one device buffer with their time-scaled forms behind them, uploaded, tempo_launch, the results back, one
-// wait.  Takes Model::mu.  design[i] null: the row is copied on the host.  n_out[i]: what out[i] received
-void tempo_rows_device(Model& m, const TempoScan* const* design, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out);
-// The resampling step of the pitch of a list of rows on s (pitch.hip; pitch.h has the rule): rows[i] states src, dst and n, key[i] its design (p is
-// not 1000); n_out (host arithmetic), the table's image (first use: made and uploaded) and the row tables are made here, one launch per table
-void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const PitchScan*>& key, hipStream_t s);
-// One row of ptts_pitch_rows, resolved: the pitch (null, or p == 1000: no resample) and the tempo it is followed by (null: none; with a pitch it
-// carries the effective speed E and is null at E == 1000)
-struct PitchStage { const PitchScan* pitch; const TempoScan* tempo; };
-// ptts_pitch_rows: the rows packed into one device buffer with their resampled and their final forms behind them, uploaded, pitch_launch,
-// tempo_launch, the results back, one wait.  Takes Model::mu.  A row with neither step is copied on the host.  n_out[i]: what out[i] received
-void pitch_rows_device(Model& m, const PitchStage* stage, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out);
+// What one part of a joined text gets in front of the join (and one row of ptts_trim_rows, ptts_tempo_rows, ptts_pitch_rows), resolved: the trim,
+// then the resampling step of the pitch (p is not 1000), then the tempo (behind a pitch it carries the effective speed E, pitch.h pitch_steps).
+// Null: the step is not run
+struct PartStages { const TrimScan* trim = nullptr; const PitchScan* pitch = nullptr; const TempoScan* tempo = nullptr; };
+// One row of parts_launch.  The caller states src, n and st, and a device destination for each step the row has, sized for the bound that step's
+// own length function gives for the longest the row can be in front of it (trimmed: n; shifted: pitch_resample_length; scaled: tempo_length).
+// parts_launch states where the row's final form lies (src itself without a step), its length, and its trim record (without a trim: untouched)
+struct PartRow {
+    const float* src; int64_t n; PartStages st;
+    float* trimmed = nullptr; float* shifted = nullptr; float* scaled = nullptr;
+    const float* out = nullptr; int64_t n_out = 0; ptts_trim_info info{};
+};
+// The one chain of the part stages on device rows, on s, in this order: the trim's launches (trim.hip; trim.h has the rule) for the rows with a trim,
+// their records back in one copy into page-locked memory (Model::trim_info) behind one stream wait -- the lengths decide everything behind them --
+// then k_pitch_resample (pitch.hip; pitch.h) for the rows with a pitch and the tempo's launches (tempo.hip; tempo.h) for the rows with a tempo.
+// Each stage's scratch and row tables are made here, one launch sequence per table.  phase (optional) is called with "trim", "pitch" and "tempo"
+// behind the launches of a stage that ran; unit: what the caller's rows are called in the internal check of the records.  The caller holds Model::mu
+void parts_launch(Model& m, std::vector<PartRow>& rows, hipStream_t s, const std::function<void(const char*)>& phase = nullptr, const char* unit = "row");
+// ptts_trim_rows, ptts_tempo_rows and ptts_pitch_rows, one round trip: the rows packed into one device buffer with the forms each row's steps need
+// behind them, uploaded, parts_launch, each row's final form back, one wait behind the copies.  Takes Model::mu.  A row with no step is copied on
+// the host; one whose result is empty is left alone.  n_out [rows] (optional): what out[i] received; info [rows] (optional): the trim records,
+// preset to "nothing cut"
+void part_rows_device(Model& m, const PartStages* per_row, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out,
+                      ptts_trim_info* info);
 
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)

@@ -438,6 +438,11 @@ def _rows_in(x):
     return single, rows, len(rows), _row_ptrs(rows), np.array([r.size for r in rows] or [0], np.int64)
 
 
+def _tempo_size(r, t):
+    """The floats of row r's output at the tempo t (None: a copy), with the speed clamped into the range the library takes."""
+    return r.size if t is None else r.size * 1000 // min(max(int(t.speed_permille), 500), 2000)
+
+
 def _fp(a: Optional[np.ndarray]):
     return C.cast(a.ctypes.data, _FP) if a is not None else None   # (ndarray.ctypes.data_as is three times slower; 64 requests per call)
 
@@ -862,50 +867,40 @@ class Model:
         """ptts_trim_rows: trim_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all), by the kernels
         generate_joined runs.  trim: one TrimOpts for every row, or one per row (None copies that row).  Returns (rows, their TrimInfo records);
         for a single array (the row, its record)."""
-        single, rows, n, pp, ns = _rows_in(x)
-        per_row = list(trim) if isinstance(trim, (list, tuple)) else [trim] * n
-        outs = [np.empty(r.size, np.float32) for r in rows]
-        po = (C.POINTER(TrimOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_row])
-        infos = (TrimInfo * max(n, 1))()
-        _check(lib().ptts_trim_rows(self.h, po, pp, _ip(ns), n, _row_ptrs(outs), infos))
-        outs = [o[:int(infos[i].n_out)] for i, o in enumerate(outs)]
-        recs = [TrimInfo(v.lo, v.hi, v.n_out, v.cuts, v.speech, 0) for v in infos[:n]]
+        single, outs, infos = self._part_rows(lib().ptts_trim_rows, x, [(trim, TrimOpts)], lambda r, o: r.size, TrimInfo, lambda v: v.n_out)
+        recs = [TrimInfo(v.lo, v.hi, v.n_out, v.cuts, v.speech, 0) for v in infos[:len(outs)]]
         return (outs[0], recs[0]) if single else (outs, recs)
+
+    def _part_rows(self, entry, x, each, size_of, back=C.c_int64, n_out=int):
+        """The host-rows entry points of a joined call's part stages (trim, tempo, pitch).  each: per option array the entry point takes, (the options
+        -- one for every row, or one per row -- and their struct); size_of(row, its options...): the floats the row's output holds; back: what the
+        entry point reports per row behind the outputs, n_out(one of them) the row's length.  Returns (single, the outputs cut to length, the reports)."""
+        single, rows, n, pp, ns = _rows_in(x)
+        per = [list(o) if isinstance(o, (list, tuple)) else [o] * n for o, _ in each]
+        outs = [np.empty(size_of(*ro), np.float32) for ro in zip(rows, *per)]
+        po = [(C.POINTER(t) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in col]) for col, (_, t) in zip(per, each)]
+        got = (back * max(n, 1))()
+        _check(entry(self.h, *po, pp, _ip(ns), n, _row_ptrs(outs), got))
+        return single, [o[:n_out(got[i])] for i, o in enumerate(outs)], got
 
     def tempo_rows(self, x, tempo):
         """ptts_tempo_rows: tempo_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch of each kernel for all), by the
         kernels generate_joined runs.  tempo: one TempoOpts for every row, or one per row (None copies that row).  Returns the time-scaled rows."""
-        single, rows, n, pp, ns = _rows_in(x)
-        per_row = list(tempo) if isinstance(tempo, (list, tuple)) else [tempo] * n
         # (sized here, so that options the library refuses reach the library: it names the row)
-        outs = [np.empty(r.size if o is None else r.size * 1000 // min(max(int(o.speed_permille), 500), 2000), np.float32) for r, o in zip(rows, per_row)]
-        po = (C.POINTER(TempoOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_row])
-        lens = np.zeros(max(n, 1), np.int64)
-        _check(lib().ptts_tempo_rows(self.h, po, pp, _ip(ns), n, _row_ptrs(outs), _ip(lens)))
-        outs = [o[:int(lens[i])] for i, o in enumerate(outs)]
+        single, outs, _ = self._part_rows(lib().ptts_tempo_rows, x, [(tempo, TempoOpts)], _tempo_size)
         return outs[0] if single else outs
 
     def pitch_rows(self, x, pitch, tempo=None):
         """ptts_pitch_rows: pitch_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all), by the kernels
         generate_joined runs.  pitch, tempo: one PitchOpts / TempoOpts for every row, or one per row (a row with a pitch of None gets its tempo
         alone, with both None it is copied).  Returns the shifted rows."""
-        single, rows, n, pp, ns = _rows_in(x)
-        per_p = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * n
-        per_t = list(tempo) if isinstance(tempo, (list, tuple)) else [tempo] * n
-        # (a row whose length the library refuses is sized 1, so that the options reach the library: it names the row, and writes nothing)
         L = lib()
-        outs = []
-        for r, p, t in zip(rows, per_p, per_t):
-            if p is not None:
-                size = int(L.ptts_pitch_length(C.byref(p), None if t is None else C.byref(t), r.size))
-            else:
-                size = r.size if t is None else r.size * 1000 // min(max(int(t.speed_permille), 500), 2000)
-            outs.append(np.empty(max(size, 1), np.float32))
-        pa = (C.POINTER(PitchOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_p])
-        ta = (C.POINTER(TempoOpts) * max(n, 1))(*[C.pointer(o) if o is not None else None for o in per_t])
-        lens = np.zeros(max(n, 1), np.int64)
-        _check(lib().ptts_pitch_rows(self.h, pa, ta, pp, _ip(ns), n, _row_ptrs(outs), _ip(lens)))
-        outs = [o[:int(lens[i])].copy() for i, o in enumerate(outs)]
+
+        def size(r, p, t):
+            # (a row whose length the library refuses is sized 1, so that the options reach the library: it names the row, and writes nothing)
+            return max(_tempo_size(r, t) if p is None else int(L.ptts_pitch_length(C.byref(p), None if t is None else C.byref(t), r.size)), 1)
+        single, outs, _ = self._part_rows(L.ptts_pitch_rows, x, [(pitch, PitchOpts), (tempo, TempoOpts)], size)
+        outs = [o.copy() for o in outs]
         return outs[0] if single else outs
 
     def true_peak_rows(self, x):

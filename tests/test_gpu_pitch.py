@@ -6,6 +6,7 @@ too; one k_pitch_resample launch per group, none without a pitch or at 1000; ref
 
 The tiny checkpoint's audio peaks near 3.0, above the tempo search's clamp and above the highest threshold a trim may name: its last
 convolution is scaled by 2^-6 here, as test_gpu_tempo.py does."""
+import ctypes as C
 import math
 import re
 
@@ -345,3 +346,182 @@ def test_refusals_launch_nothing(pkg, tiny):
     d._ext.set_pitch(None)
     assert np.array_equal(_u32(gm.dsp_rows(x, opts=d)), _u32(x))
     assert gm.generate_joined(_toks(2), [_cfg(pkg, 2), _cfg(pkg, 2)]).n_frames == 4
+
+
+def test_tempo_rows_and_pitch_rows_without_a_pitch_are_one_path(pkg, tiny):
+    """One row list through ptts_tempo_rows and through ptts_pitch_rows with every pitch null: the same bits from the same launches.  Lengths
+    around one hop (480) and one DSP tile (1920), and nothing.  17 speeds on the first 17 rows, so that the first table ends at its design limit
+    of 16; 15 of them on the rows behind, enough of them non-empty that the second table ends at its 256 rows and a third runs (rows of no
+    samples, and rows whose result is empty, never reach the device: 400 host rows for it)."""
+    _, gm = tiny
+    rt = pkg.runtime
+    lens = (1921, 0, 1, 479, 480, 481, 1919, 1920)
+    speeds = [500, 2000, 1000] + [560 + 97 * k for k in range(14)]
+    assert len(set(speeds)) == 17 and all(500 <= s <= 2000 for s in speeds)
+    rows = [R.noise(lens[i % 8], 3000 + i) for i in range(400)]
+    to = [rt.TempoOpts(speeds[i] if i < 17 else speeds[i % 15]) for i in range(400)]
+    assert {r.size for r in rows} == set(lens) and len({t.speed_permille for t in to}) == 17
+    # the tables the rule cuts (row_tables.h): rows in order, a new table at 256 rows or at a 17th distinct design
+    tables, n_rows, designs, by_rows, by_designs = 1, 0, set(), 0, 0
+    for x, t in zip(rows, to):
+        if R.tempo_length(x.size, t.speed_permille) <= 0:
+            continue
+        full, many = n_rows == 256, len(designs | {t.speed_permille}) > 16
+        if full or many:
+            tables, n_rows, designs = tables + 1, 0, set()
+            by_rows, by_designs = by_rows + full, by_designs + (many and not full)
+        n_rows, designs = n_rows + 1, designs | {t.speed_permille}
+    assert (tables, by_rows, by_designs) == (3, 1, 1)
+    rt.launch_counts(True)
+    a = gm.tempo_rows(rows, to)
+    counts_a = rt.launch_counts(False)
+    rt.launch_counts(True)
+    b = gm.pitch_rows(rows, None, to)
+    counts_b = rt.launch_counts(False)
+    assert counts_a == counts_b and [counts_a.get(k) for k in TEMPO_KERNELS] == [tables, tables], (counts_a, counts_b)
+    for i, (x, t, u, v) in enumerate(zip(rows, to, a, b)):
+        assert u.size == v.size == R.tempo_length(x.size, t.speed_permille) and np.array_equal(_u32(u), _u32(v)), (i, x.size, t.speed_permille)
+    for i in (2, 7, 399):                                                  # and what both give is the host statement (a row at speed 1000 among them)
+        assert np.array_equal(_u32(a[i]), _u32(rt.tempo_apply(to[i], rows[i]))), i
+    assert to[2].speed_permille == 1000 and rows[7].size == 1920 and rows[399].size == 1920
+
+
+def _refusal(pkg, call):
+    rt = pkg.runtime
+    rt.launch_counts(True)
+    with pytest.raises(pkg.PttsError) as ei:
+        call()
+    assert ei.value.code == rt.PTTS_EINVAL and not rt.launch_counts(False)
+    return str(ei.value)
+
+
+def test_refusal_texts_of_the_tempo_and_pitch_rows(pkg, tiny):
+    """Every refusal site of ptts_tempo_rows and ptts_pitch_rows, byte for byte as the entry points worded them before they shared one path.  The
+    lengths of 2^31 and around are refused before any row is read: the rows behind them hold one sample."""
+    _, gm = tiny
+    rt = pkg.runtime
+    L = rt.lib()
+    x = R.tone(2000, 200.0)
+    one = np.zeros(1, np.float32)
+    t8, p11 = rt.TempoOpts(800), rt.PitchOpts(1100)
+
+    def tempo(t, rows, n=None, outs=None, null=None):
+        pp = rt._row_ptrs(rows)
+        po = (C.POINTER(rt.TempoOpts) * len(t))(*[None if o is None else C.pointer(o) for o in t])
+        outs = rt._row_ptrs(outs if outs is not None else [np.empty(2 * r.size + 1, np.float32) for r in rows])
+        ns = np.array([r.size for r in rows] if n is None else n, np.int64)
+        got = np.zeros(len(rows), np.int64)
+        args = dict(t=po, rows=pp, n=rt._ip(ns), out=outs, n_out=rt._ip(got))
+        if null:
+            args[null] = None
+        rt._check(L.ptts_tempo_rows(gm.h, args["t"], args["rows"], args["n"], len(rows), args["out"], args["n_out"]))
+
+    def pitch(p, t, rows, n=None, outs=None, null=None):
+        pp = rt._row_ptrs(rows)
+        pa = (C.POINTER(rt.PitchOpts) * len(p))(*[None if o is None else C.pointer(o) for o in p])
+        ta = (C.POINTER(rt.TempoOpts) * len(t))(*[None if o is None else C.pointer(o) for o in t])
+        outs = rt._row_ptrs(outs if outs is not None else [np.empty(4 * r.size + 1, np.float32) for r in rows])
+        ns = np.array([r.size for r in rows] if n is None else n, np.int64)
+        got = np.zeros(len(rows), np.int64)
+        args = dict(p=pa, t=ta, rows=pp, n=rt._ip(ns), out=outs, n_out=rt._ip(got))
+        if null:
+            args[null] = None
+        rt._check(L.ptts_pitch_rows(gm.h, args["p"], args["t"], args["rows"], args["n"], len(rows), args["out"], args["n_out"]))
+
+    for null in ("t", "rows", "n", "out", "n_out"):
+        assert _refusal(pkg, lambda: tempo([t8], [x], null=null)) == "ptts-hip: tempo: null argument"
+    for null in ("p", "t", "rows", "n", "out", "n_out"):
+        assert _refusal(pkg, lambda: pitch([p11], [None], [x], null=null)) == "ptts-hip: pitch: null argument"
+    assert _refusal(pkg, lambda: tempo([t8, t8], [x, x], n=[x.size, -1])) == "ptts-hip: tempo: row 1 is negative or null"
+    assert _refusal(pkg, lambda: pitch([p11, p11], [None, None], [x, x], n=[x.size, -1])) == "ptts-hip: pitch: row 1 is negative or null"
+    assert _refusal(pkg, lambda: tempo([t8, rt.TempoOpts(2001)], [x, x])) == "ptts-hip: row 1: tempo: speed_permille 2001 is not from 500 to 2000 (1000: unchanged)"
+    assert _refusal(pkg, lambda: pitch([p11, rt.PitchOpts(499)], [None, None], [x, x])) == "ptts-hip: row 1: pitch: pitch_permille 499 is not from 500 to 2000 (1000: unchanged)"
+    assert _refusal(pkg, lambda: pitch([None, None], [t8, rt.TempoOpts(2001)], [x, x])) == "ptts-hip: row 1: tempo: speed_permille 2001 is not from 500 to 2000 (1000: unchanged)"
+    assert _refusal(pkg, lambda: tempo([None, t8], [x, x], outs=[x.copy(), x])) == "ptts-hip: tempo: row 1: out is in"
+    assert _refusal(pkg, lambda: pitch([None, p11], [None, None], [x, x], outs=[x.copy(), x])) == "ptts-hip: row 1: pitch: out is in"
+    assert _refusal(pkg, lambda: pitch([None, None], [None, t8], [x, x], outs=[x.copy(), x])) == "ptts-hip: row 1: pitch: out is in"
+    assert (_refusal(pkg, lambda: pitch([p11, rt.PitchOpts(2000)], [None, rt.TempoOpts(500)], [x, x]))
+            == "ptts-hip: row 1: pitch: speed_permille 500 with pitch_permille 2000 needs the tempo at 250, which is not from 500 to 2000")
+    assert (_refusal(pkg, lambda: pitch([p11, rt.PitchOpts(500)], [None, rt.TempoOpts(1500)], [x, x]))
+            == "ptts-hip: row 1: pitch: speed_permille 1500 with pitch_permille 500 needs the tempo at 3000, which is not from 500 to 2000")
+    # the lengths, refused before a row is read
+    big = (1 << 31) - 240
+    assert _refusal(pkg, lambda: tempo([None, t8], [one, one], n=[1, big], outs=[one.copy(), one.copy()])) == f"ptts-hip: tempo: row 1 has {big} samples, a row must stay below 2^31 - 240"
+    assert _refusal(pkg, lambda: pitch([None, None], [None, t8], [one, one], n=[1, big], outs=[one.copy(), one.copy()])) == f"ptts-hip: row 1: tempo: {big} samples, a row must stay below 2^31 - 240"
+    assert (_refusal(pkg, lambda: pitch([None, rt.PitchOpts(500)], [None, None], [one, one], n=[1, 1 << 30], outs=[one.copy(), one.copy()]))
+            == f"ptts-hip: row 1: pitch: n {1 << 30} at pitch_permille 500 has the resampled length {1 << 31}, a row must stay below 2^31 - 240")
+    assert (_refusal(pkg, lambda: pitch([None, rt.PitchOpts(1000)], [None, rt.TempoOpts(500)], [one, one], n=[1, 1 << 30], outs=[one.copy(), one.copy()]))
+            == f"ptts-hip: row 1: pitch: n {1 << 30} at pitch_permille 1000 and the tempo at 500 has the final length {1 << 31}, a row must stay below 2^31 - 240")
+    assert (_refusal(pkg, lambda: pitch([None, p11], [None, None], [one, one], n=[1, 1 << 33], outs=[one.copy(), one.copy()]))
+            == f"ptts-hip: row 1: pitch: n {1 << 33} is not from 0 to where its lengths stay below 2^31 - 240")
+    # the model serves on
+    assert np.array_equal(_u32(gm.pitch_rows(x, None, t8)), _u32(rt.tempo_apply(t8, x)))
+
+
+def test_a_dead_handle_is_refused_under_the_setters_name(pkg):
+    rt = pkg.runtime
+    ext = rt.DspExt()
+    h = ext.h
+    ext.free()
+    assert ext.h is None
+    ext.h = h                                                              # (the registry knows the handle is gone: it is not read)
+    try:
+        for stage, call in (("compressor", lambda: ext.set_compressor(rt.CompressorOpts())), ("limiter", lambda: ext.set_limiter(rt.LimiterOpts())),
+                            ("trim", lambda: ext.set_trim(rt.TrimOpts())), ("tempo", lambda: ext.set_tempo(rt.TempoOpts(800))),
+                            ("pitch", lambda: ext.set_pitch(rt.PitchOpts(1100))), ("trim", lambda: ext.set_trim(None))):
+            with pytest.raises(pkg.PttsError) as ei:
+                call()
+            assert ei.value.code == rt.PTTS_EINVAL and str(ei.value) == f"ptts-hip: {stage}: ext {h:#x} is not a live handle of ptts_dsp_ext_create"
+    finally:
+        ext.h = None
+    # a live handle refuses bad options by the stage's own check, and keeps what it had
+    live = rt.DspExt(tempo=rt.TempoOpts(800))
+    with pytest.raises(pkg.PttsError) as ei:
+        live.set_tempo(rt.TempoOpts(2001))
+    assert str(ei.value) == "ptts-hip: tempo: speed_permille 2001 is not from 500 to 2000 (1000: unchanged)"
+
+
+_TRACE_CHILD = """
+import sys
+import ptts_amd
+pkg = ptts_amd.load()
+rt = pkg.runtime
+gm = pkg.Model.open(sys.argv[1], device=0, max_batch=2)
+gm.profile_enable(2)
+d = rt.DspOpts(0, 0, 0.0, 0.0)
+ext = rt.DspExt(trim=rt.TrimOpts(edges=1, threshold_db=float(sys.argv[2]), pad_ms=5.0, max_pause_ms=20.0), tempo=rt.TempoOpts(800), pitch=rt.PitchOpts(1100))
+d.ext = ext.h
+cfgs = [pkg.RuntimeGenerateConfig(eos_threshold=float("inf"), max_steps=s, temperature=0.0) for s in (2, 4, 3)]
+res = gm.generate_joined([[3 + i % 40, 7, 11 + i % 40] for i in range(3)], cfgs, rt.JoinOpts(dsp=d))
+ph = gm.profile_read()
+gm.profile_enable(0)
+print("frames", res.n_frames, "parts", [p.n_samples for p in res.parts], "profile", sorted(k for k in ph if k.endswith("_ms")))
+gm.close()
+"""
+
+
+def test_the_phases_of_a_joined_call(pkg, tiny, chunks, tmp_path):
+    """A joined call with a trim, pitch 1100 and speed 800, measured (profile_enable(2)) and traced, names its part stages as before: per group
+    `trim`, `pitch`, `tempo` and `join`, in that order, each behind its launches.  ptts_profile_read's record has fixed times (the timed launches' total; prefill, AR
+    loop, decoder) and no named phases; the names are those of the call's host trace (PTTS_TRACE=1, read once per process: hence the child)."""
+    import os
+    import subprocess
+    import sys
+    cfg, gm = tiny
+    rt = pkg.runtime
+    synth = pkg.synth
+    tensors = synth.make_checkpoint(cfg, seed=1234)
+    for k in ("mimi.decoder.model.11.conv.weight", "mimi.decoder.model.11.conv.bias"):
+        tensors[k] = (tensors[k] * np.float32(2.0 ** -6)).astype(np.float32)
+    path = str(tmp_path / "tiny_quiet.safetensors")
+    synth.write_safetensors(path, tensors)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, "-c", _TRACE_CHILD, path, repr(_trim_db(chunks))], capture_output=True, text=True, cwd=root, timeout=120,
+                         env=dict(os.environ, PTTS_TRACE="1"))
+    assert run.returncode == 0, run.stderr
+    marks = re.findall(r"^\[ptts\] (.+?)\s+[0-9.]+ ms$", run.stderr, re.M)
+    print("phases:", marks)
+    trim = rt.TrimOpts(edges=1, threshold_db=_trim_db(chunks), pad_ms=5.0, max_pause_ms=20.0)
+    want = [rt.pitch_apply(rt.PitchOpts(1100), rt.TempoOpts(800), rt.trim_apply(trim, p)[0]).size for p in chunks]
+    assert f"frames {sum(STEPS)} parts {want} profile ['ar_loop_ms', 'mimi_ms', 'prefill_ms', 'total_ms']" in run.stdout, run.stdout
+    assert [m for m in marks if m in ("trim", "pitch", "tempo", "join")] == ["trim", "pitch", "tempo", "join"] * 2, marks   # two groups

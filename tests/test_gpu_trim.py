@@ -213,3 +213,62 @@ def test_one_request_is_the_trimmed_utterance(pkg, tiny):
     got = gm.generate_joined(_toks(1), [_cfg(pkg, STEPS3[0])], rt.JoinOpts(dsp=_with_trim(rt, trim)))
     assert np.array_equal(_u32(got.pcm), _u32(want)) and got.n_frames == STEPS3[0]
     assert got.parts[0].offset == 0 and got.parts[0].n_samples == info.n_out
+
+
+def test_every_record_of_trim_rows_is_trim_plans(pkg, tiny):
+    """Every TrimInfo field ptts_trim_rows reports is ptts_trim_plan's for the same row: rows the trim shortens at the edges and at a pause, a row
+    it leaves whole (all loud; quiet throughout, which counts as no speech), the row whose n_out is 0 (the trim keeps a sample wherever there is
+    speech, so it is the row of no samples) and rows without a trim, whose record is the preset one."""
+    _, gm = tiny
+    rt = pkg.runtime
+    o = rt.TrimOpts(edges=1, threshold_db=R.THR_DB, pad_ms=2.0, max_pause_ms=20.0)
+    loud = np.full(1921, 0.5, np.float32)
+    rows = [R.row(2 * R.T + 9, [700, R.T + 900]), R.quiet(1919), loud, R.row(481, [0, 480]), np.zeros(0, np.float32), R.quiet(1920), R.row(1921, [1920]), loud]
+    opts = [o, o, o, o, o, None, o, None]
+    got, recs = gm.trim_rows(rows, opts)
+    seen = set()
+    for i, (x, t, g, rec) in enumerate(zip(rows, opts, got, recs)):
+        if t is None:
+            assert (rec.lo, rec.hi, rec.n_out, rec.cuts, rec.speech, rec.reserved) == (0, x.size, x.size, 0, 0, 0) and np.array_equal(_u32(g), _u32(x)), i
+            continue
+        want = rt.trim_plan(t, x)
+        assert (rec.lo, rec.hi, rec.n_out, rec.cuts, rec.speech, rec.reserved) == (want.lo, want.hi, want.n_out, want.cuts, want.speech, 0), (i, rec.astuple(), want.astuple())
+        assert g.size == want.n_out == R.plan(x, edges=1, threshold_db=R.THR_DB, pad_ms=2.0, max_pause_ms=20.0)[1][2], i
+        seen.add("empty" if want.n_out == 0 else "whole" if want.n_out == x.size else "cut" if want.cuts else "edges")
+    assert seen == {"empty", "whole", "cut", "edges"} and recs[4].n_out == 0 and (recs[1].n_out, recs[1].speech) == (1919, 0), seen
+
+
+def test_refusal_texts_of_trim_rows(pkg, tiny):
+    """Every refusal site of ptts_trim_rows, byte for byte.  A length of 2^31 is refused before any row is read: the row behind it holds one sample."""
+    _, gm = tiny
+    rt = pkg.runtime
+    x = R.row(2000, [700])
+    o = rt.TrimOpts(edges=1, threshold_db=R.THR_DB)
+
+    def trim(t, rows, n=None, null=None):
+        pp = rt._row_ptrs(rows)
+        po = (C.POINTER(rt.TrimOpts) * len(t))(*[None if v is None else C.pointer(v) for v in t])
+        outs = rt._row_ptrs([np.empty(max(r.size, 1), np.float32) for r in rows])
+        ns = np.array([r.size for r in rows] if n is None else n, np.int64)
+        args = dict(t=po, rows=pp, n=rt._ip(ns), out=outs, info=(rt.TrimInfo * len(rows))())
+        if null:
+            args[null] = None
+        rt._check(rt.lib().ptts_trim_rows(gm.h, args["t"], args["rows"], args["n"], len(rows), args["out"], args["info"]))
+
+    def refusal(call):
+        rt.launch_counts(True)
+        with pytest.raises(pkg.PttsError) as ei:
+            call()
+        assert ei.value.code == rt.PTTS_EINVAL and not rt.launch_counts(False)
+        return str(ei.value)
+
+    for null in ("t", "rows", "n", "out", "info"):
+        assert refusal(lambda: trim([o], [x], null=null)) == "ptts-hip: trim: null argument"
+    assert refusal(lambda: trim([o, o], [x, x], n=[x.size, -1])) == "ptts-hip: trim: row 1 is negative or null"
+    assert refusal(lambda: trim([o, rt.TrimOpts(pad_ms=-1.0)], [x, x])) == "ptts-hip: row 1: trim: pad_ms -1 is not a finite value from 0 to 500"
+    assert refusal(lambda: trim([o, rt.TrimOpts(edges=0)], [x, x])) == "ptts-hip: row 1: trim: nothing switched on (edges is 0 and max_pause_ms is 0)"
+    one = np.zeros(1, np.float32)
+    for t in (o, None):                                                    # (a row without a trim is held to the length as well)
+        assert refusal(lambda: trim([None, t], [one, one], n=[1, 1 << 31])) == f"ptts-hip: trim: row 1 has {1 << 31} samples, a row must stay below 2^31"
+    got, rec = gm.trim_rows(x, o)                                          # the model serves on
+    assert rec.astuple() == rt.trim_plan(o, x).astuple() and got.size == rec.n_out
