@@ -170,7 +170,7 @@ Voice* voice_create(Model& m, const float* const* caches, const int64_t* steps, 
     v->v.ensure(std::max<size_t>(lb * d.n_layers, 256));
     for (int l = 0; l < d.n_layers; l++) {
         size_t n = (size_t)2 * steps[l] * d.heads * d.hd;
-        DevBuf& raw = m.work(1, n * sizeof(float));
+        DevBuf& raw = m.work(WORK_VOICE_RAW, n * sizeof(float));
         h2d(raw.p, caches[l], n * sizeof(float), m.stream);
         launch_voice_scatter(raw.as<float>(), (int)steps[l], d.heads, d.hd, v->offset, 0, (char*)v->k.p + lb * l, (char*)v->v.p + lb * l,
                              m.opts.kv == PTTS_KV_BF16, v->offset, m.stream);
@@ -191,7 +191,7 @@ void batch_apply_voice(Batch& b, const Voice& v, const std::vector<int32_t>& slo
     const Desc& d = m.d;
     if (!voice_usable_by(v, m)) throw Error(PTTS_EINVAL, "ptts-hip: voice belongs to another model");
     if (v.offset > b.cap) throw Error(PTTS_EINVAL, "ptts-hip: voice state longer than the KV capacity");
-    DevBuf& ds = m.work(10, slots.size() * sizeof(int32_t));
+    DevBuf& ds = m.work(WORK_VOICE_SLOTS, slots.size() * sizeof(int32_t));
     h2d(ds.p, slots.data(), slots.size() * sizeof(int32_t), io);
     const size_t lb = v.layer_bytes();
     for (int l = 0; l < d.n_layers; l++)
@@ -217,7 +217,7 @@ void batch_set_voice(Batch& b, int slot, const float* const* caches, const int64
     check_voice(d, caches, steps, offsets, b.cap);
     for (int l = 0; l < d.n_layers; l++) {
         size_t n = (size_t)2 * steps[l] * d.heads * d.hd;
-        DevBuf& raw = m.work(1, n * sizeof(float));
+        DevBuf& raw = m.work(WORK_VOICE_RAW, n * sizeof(float));
         h2d(raw.p, caches[l], n * sizeof(float), io);
         launch_voice_scatter(raw.as<float>(), (int)steps[l], d.heads, d.hd, (int)offsets[l], slot, b.kc(l), b.vc(l),
                              m.opts.kv == PTTS_KV_BF16, b.cap, io);
@@ -254,11 +254,11 @@ void batch_prompt(Batch& b, const float* rows_dev, const int64_t* row_offsets) {
     const size_t f = sizeof(float);
     // one upload: row -> slot, row -> position, and per slot the first row / first position (the ragged-segment view of the same)
     const RaggedMeta meta = ragged_meta(off.data(), b.kv_len_host.data(), B);
-    int32_t* d_meta = m.work(2, meta.table.size() * sizeof(int32_t)).as<int32_t>();
+    int32_t* d_meta = m.work(WORK_PROMPT_META, meta.table.size() * sizeof(int32_t)).as<int32_t>();
     const int32_t* d_slot = meta.row_seg(d_meta);
     const int32_t* d_pos = meta.row_pos(d_meta);
     h2d(d_meta, meta.table.data(), meta.table.size() * sizeof(int32_t), s);
-    DevBuf& wsb = m.work(3, ((size_t)R * (size_t)(D + D + 3 * D + D + d.ffn)) * f);
+    DevBuf& wsb = m.work(WORK_PROMPT_ACT, ((size_t)R * (size_t)(D + D + 3 * D + D + d.ffn)) * f);
     float* px = wsb.as<float>();
     float* pxn = px + (size_t)R * D;
     float* pqkv = pxn + (size_t)R * D;
@@ -303,7 +303,7 @@ void batch_prompt(Batch& b, const float* rows_dev, const int64_t* row_offsets) {
         GemmArgs g2c = g2;
         g2c.M = std::min(R, 64);
         if (S > 1 && skinny_supported(g2c, S)) {   // (64-row chunks of the split step kernel; the planes of all chunks form one [S][R][D] operand)
-            DevBuf& pb = m.work(9, (size_t)S * R * D * f);
+            DevBuf& pb = m.work(WORK_PREFILL_PLANES, (size_t)S * R * D * f);
             for (int r0 = 0; r0 < R; r0 += 64) {
                 g2c = g2;
                 g2c.M = std::min(64, R - r0);
@@ -319,7 +319,7 @@ void batch_prompt(Batch& b, const float* rows_dev, const int64_t* row_offsets) {
             gs.bias = nullptr; gs.kslice = 1024; gs.zstride = (int64_t)R * D;
             const int Sg = (d.ffn + gs.kslice - 1) / gs.kslice;
             if (R < 16384 && Sg > 1 && Sg <= 8) {
-                DevBuf& pb = m.work(9, (size_t)Sg * R * D * f);
+                DevBuf& pb = m.work(WORK_PREFILL_PLANES, (size_t)Sg * R * D * f);
                 gs.C = pb.as<float>(); gs.cmap = flat(D);
                 if (gemm5_supported(gs) || gemm3_supported(gs)) {
                     if (gemm5_supported(gs)) launch_gemm5(gs, s);   // (bf16 weights from 1024 rows; the same k order within a slice: the same planes)

@@ -1,5 +1,6 @@
-// capi_internal.h -- what the two extern "C" translation units share: capi.cpp (the product ABI, include/ptts.h) and capi_hooks.cpp (the test and
-// measurement hooks of include/ptts_debug.h, built into libptts_hooks.so only -- libptts_hip.so does not contain them).
+// capi_internal.h -- what the extern "C" translation units share: capi.cpp, capi_rows.cpp and capi_ops.cpp (the product ABI, include/ptts.h, by area) and
+// capi_hooks.cpp (the test and measurement hooks of include/ptts_debug.h, built into libptts_hooks.so only -- libptts_hip.so does not contain them).
+// These files check arguments, word the refusals, take the model's lock (Locked) and forward; the device work is the engine's (runtime.h, staged.cpp).
 #pragma once
 
 #include <cmath>
@@ -49,6 +50,12 @@ inline void require_device() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(PTTS_ENODEVICE, "ptts-hip: no HIP device available (this library has no CPU fallback)");
 }
+
+// the model's lock and its device for the rest of an entry point: where the engine function behind it says "the caller holds Model::mu"
+struct Locked {
+    std::lock_guard<std::mutex> lock;
+    explicit Locked(Model& m) : lock(m.mu) { m.use_device(); }
+};
 
 // scratch for the op-level entry points: device 0, default stream, synchronous copies
 struct Tmp {

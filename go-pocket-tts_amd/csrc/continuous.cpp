@@ -250,9 +250,9 @@ ContEngine* cont_create(Model& m, int slots, int kv_cap, int max_steps) {
     // the decoder's workspaces at their largest, so that a later, bigger group of finished utterances never reallocates a buffer an
     // earlier group's kernels are still using
     { MimiWs w; mimi_setup(m, w, 1, kFramesPerDecode + kFramesPerDecode / 8); }
-    m.work(7, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.samples_per_frame * sizeof(float));
-    m.work(8, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.samples_per_frame * sizeof(int16_t));
-    m.work(13, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.ldim * sizeof(float));
+    m.work(WORK_CONT_PCM, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.samples_per_frame * sizeof(float));
+    m.work(WORK_EGRESS_S16, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.samples_per_frame * sizeof(int16_t));
+    m.work(WORK_CONT_RESERVE, (size_t)(kFramesPerDecode + kFramesPerDecode / 8) * m.d.ldim * sizeof(float));
     static const int env_graph = [] { const char* g = getenv("PTTS_GRAPH"); return g ? atoi(g) : -1; }();
     e->use_graph = env_graph >= 0 ? env_graph != 0 : m.opts.use_graph != 0;
     PTTS_HIP(hipStreamSynchronize(m.stream));
@@ -434,7 +434,7 @@ static void start_decode(ContEngine& e, std::vector<ContEngine::Staged>& fin) {
         MimiWs mw;
         mimi_setup(m, mw, nb, T);
         mimi_zero_history(m, mw, s2);
-        DevBuf& pcm = m.work(7, (size_t)nb * T * spf * sizeof(float));
+        DevBuf& pcm = m.work(WORK_CONT_PCM, (size_t)nb * T * spf * sizeof(float));
         // the result buffers first: through a PcmRow table of its own (kLat x 2 B entries, rewritten no sooner than kLat decode starts later) the decoder's
         // last kernel stores the samples into them itself (results_alloc) -- no PCM copy per utterance on the decoder's stream, no conversion launch
         std::vector<Delivery> g((size_t)nb);
@@ -518,7 +518,7 @@ static void take_snapshot(ContEngine& e, ContEngine::Snap& sn, std::vector<void*
         const int turn = e.arena_turn;
         e.arena_turn ^= 1;
         UploadScope upload_scope(e.arenas[turn], e.arena_free[turn]);
-        DevBuf& dr = m.work(15, (size_t)B * sizeof(int32_t));
+        DevBuf& dr = m.work(WORK_CONT_RETIRE, (size_t)B * sizeof(int32_t));
         h2d(dr.p, retire.data(), retire.size() * sizeof(int32_t), m.stream);
         launch_slot_retire(b.st, dr.as<int32_t>(), (int)retire.size(), m.stream);
         PTTS_HIP(hipEventRecord(e.arena_free[turn], m.stream));

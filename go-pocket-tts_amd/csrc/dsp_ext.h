@@ -1,5 +1,5 @@
 // dsp_ext.h -- the handle behind ptts_dsp_opts.ext (include/ptts.h ptts_dsp_ext): what true_peak.cpp (which makes and
-// frees it), compressor.cpp and limiter.cpp (which set its compressor and its limiter), capi.cpp (which sets its trim, its tempo and its pitch) and
+// frees it), compressor.cpp and limiter.cpp (which set its compressor and its limiter), capi_rows.cpp (which sets its trim, its tempo and its pitch) and
 // dsp_spec.cpp (which reads it) share, and the one setter behind the five ptts_dsp_ext_set_*.  No HIP header.
 #pragma once
 #include "compressor.h"
@@ -30,7 +30,7 @@ namespace ptts {
 
 // Every ptts_dsp_ext_set_<stage>: the options checked by the stage's *_opts_error (null options: the stage off), the design made outside the
 // registry's mutex, then the flag and the design stored under it; a handle that is not live is refused under the stage's name.  The callers are
-// compressor.cpp and limiter.cpp for their own stage, and capi.cpp for the trim, the tempo and the pitch, whose files build alone without the registry
+// compressor.cpp and limiter.cpp for their own stage, and capi_rows.cpp for the trim, the tempo and the pitch, whose files build alone without the registry
 template <class Opts, class Design>
 int ext_set(ptts_dsp_ext* e, const char* stage, const Opts* o, std::string (*opts_error)(const Opts*), Design (*design)(const Opts&), bool DspExt::*on,
             Design DspExt::*d) {

@@ -154,7 +154,7 @@ int64_t mimi_encode_clip(Model& m, const float* pcm, int64_t n_samples, float* l
     hipStream_t s = m.stream;
     const int C = d.mimi_dim;
     EncWs w = enc_layout(d, frames, nullptr);
-    DevBuf& wsb = m.work(16, w.floats * sizeof(float));
+    DevBuf& wsb = m.work(WORK_ENCODER, w.floats * sizeof(float));
     w = enc_layout(d, frames, wsb.as<float>());
     float* const* st = stages;
     // zero history in front of every buffer, zero samples after the clip's end
@@ -233,8 +233,8 @@ void mimi_encode(Model& m, const float* const* pcm, const int64_t* n_samples, in
         throw Error(PTTS_EINVAL, strfmt("voice encode: a clip of %lld frames exceeds the %lld frames one clip may have", (long long)longest,
                                         (long long)mimi_encode_max_frames(d)));
     // the workspace once, for the longest clip (layouts grow with the frame count)
-    m.work(16, enc_layout(d, longest, nullptr).floats * sizeof(float));
-    DevBuf& lat = m.work(17, (size_t)longest * d.mimi_dim * sizeof(float));
+    m.work(WORK_ENCODER, enc_layout(d, longest, nullptr).floats * sizeof(float));
+    DevBuf& lat = m.work(WORK_ENCODER_LATENTS, (size_t)longest * d.mimi_dim * sizeof(float));
     for (int i = 0; i < n_clips; i++) {
         const int64_t f = mimi_encode_clip(m, pcm[i], n_samples[i], lat.as<float>(), stages, rates ? rates[i] : kNativeRate);
         PTTS_HIP(hipMemcpyAsync(latent_out[i], lat.p, (size_t)f * d.mimi_dim * sizeof(float), hipMemcpyDeviceToHost, m.stream));

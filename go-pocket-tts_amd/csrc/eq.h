@@ -1,4 +1,4 @@
-// eq.h -- what eq.cpp (the host side of a request's equaliser, no HIP header) shares with the device side (dsp_device.cpp, capi.cpp, generate.cpp).
+// eq.h -- what eq.cpp (the host side of a request's equaliser, no HIP header) shares with the device side (dsp_device.cpp, capi_rows.cpp, generate.cpp).
 #pragma once
 #include <string>
 #include <type_traits>

@@ -28,8 +28,8 @@ void stage_prompt(Batch& b, const std::vector<SlotReq>& list, hipStream_t s, hip
         ids.insert(ids.end(), q.req->tokens, q.req->tokens + q.req->n_tokens);
     }
     for (int sl = 0; sl < b.B; sl++) row_off[(size_t)sl + 1] += row_off[(size_t)sl];
-    DevBuf& rows = m.work(5, (size_t)row_off[(size_t)b.B] * D * sizeof(float));
-    DevBuf& dids = m.work(6, ids.size() * sizeof(int64_t));
+    DevBuf& rows = m.work(WORK_PROMPT_ROWS, (size_t)row_off[(size_t)b.B] * D * sizeof(float));
+    DevBuf& dids = m.work(WORK_PROMPT_IDS, ids.size() * sizeof(int64_t));
     h2d(dids.p, ids.data(), ids.size() * sizeof(int64_t), s);
     // token rows of consecutive requests are contiguous unless a voice embedding sits between them: one gather per such run
     // (a batch without voice embeddings is ONE launch instead of one per request)
@@ -79,7 +79,7 @@ void stage_noise(Batch& b, const std::vector<SlotReq>& list, hipStream_t s) {
         }
     }
     if (draw_rows == 0) return;
-    DevBuf& sb = m.work(12, spec.size() * sizeof(NoiseSpec));
+    DevBuf& sb = m.work(WORK_NOISE_SPECS, spec.size() * sizeof(NoiseSpec));
     h2d(sb.p, spec.data(), spec.size() * sizeof(NoiseSpec), s);
     launch_noise_fill(sb.as<NoiseSpec>(), b.B, draw_rows, noise, slot_rows, ld, s);
 }
@@ -144,7 +144,7 @@ void results_deliver(Model& m, const std::vector<Delivery>& g, bool stored, cons
             if (request_converts(*u.req)) conv.push_back(i);
             else {
                 if (s16 && !pcm16) {
-                    DevBuf& buf = m.work(8, (size_t)(n * pcm_stride) * sizeof(int16_t));
+                    DevBuf& buf = m.work(WORK_EGRESS_S16, (size_t)(n * pcm_stride) * sizeof(int16_t));
                     launch_pcm16(pcm, buf.as<int16_t>(), n * pcm_stride, s);
                     pcm16 = buf.as<int16_t>();
                 }
@@ -348,7 +348,7 @@ void Chunk::setup() {
 // decoded as soon as step f1-1 has finished.
 void Chunk::decoder_setup() {
     T = std::min(ms_max, t_limit);
-    pcm = &m.work(7, (size_t)B * T * spf * sizeof(float));
+    pcm = &m.work(WORK_PCM, (size_t)B * T * spf * sizeof(float));
     const char* env_chunk = getenv("PTTS_MIMI_CHUNK");
     chunk = env_chunk && atoi(env_chunk) > 0 ? atoi(env_chunk) : 1 << 30;   // default: decode after the loop (measured: overlapping
                                                                             // slows the AR launches by as much as it hides)
@@ -368,8 +368,8 @@ void Chunk::decoder_setup() {
             any_conv |= conv;
             if (conv) stage_row = std::max(stage_row, (bytes + 255) & ~(size_t)255);
         }
-        if (any_s16) stream_s16 = &m.work(8, (size_t)B * T * spf * sizeof(int16_t));
-        if (stage_row) stream_stage = m.work(28, stage_row * (size_t)B).as<char>();
+        if (any_s16) stream_s16 = &m.work(WORK_STREAM_S16, (size_t)B * T * spf * sizeof(int16_t));
+        if (stage_row) stream_stage = m.work(WORK_STREAM_STAGE, stage_row * (size_t)B).as<char>();
     }
     // Decoder workspace (~2.7 MB of f32 activations per latent frame and utterance).  A batch of more than kMimiGroup utterances that is decoded in one go after the
     // loop (the default) goes through the decoder group after group in the SAME buffers (stream order keeps them apart); a batch whose frame ranges are decoded under
@@ -482,7 +482,7 @@ void Chunk::emit_upto(int f1, bool last) {
     if (any_conv) {
         // one snapshot of (active, n_frames) for this range's k_resample rows AND its host function, so that both agree on which utterances
         // have ended.  The AR loop goes on meanwhile: active is copied first, so an utterance seen inactive comes with its final frame count
-        DevBuf& snap = m.work(27, (size_t)2 * B * sizeof(int32_t));
+        DevBuf& snap = m.work(WORK_STREAM_SNAP, (size_t)2 * B * sizeof(int32_t));
         int32_t* sa = snap.as<int32_t>();
         int32_t* sn = sa + B;
         PTTS_HIP(hipMemcpyAsync(sa, b->st.active, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s2));
@@ -575,7 +575,7 @@ void Chunk::deliver() {
     }
     // Whole batch decoded in one go (the default): the decoder's last kernel stores the samples into the result buffers itself
     const bool try_direct = !streaming && f_done == 0;
-    const PcmRow* rows = results_alloc(m, g, try_direct ? b->rows_pinned : nullptr, try_direct ? m.work(11, (size_t)B * sizeof(PcmRow)).as<PcmRow>() : nullptr, s);
+    const PcmRow* rows = results_alloc(m, g, try_direct ? b->rows_pinned : nullptr, try_direct ? m.work(WORK_PCM_ROWS, (size_t)B * sizeof(PcmRow)).as<PcmRow>() : nullptr, s);
     bool stored = false;
     decode_rest(std::min(steps_run, Tmax), rows, &stored);
     for (int i = 0; i < B; i++) {   // streamed: the buffer already holds every sample that was announced

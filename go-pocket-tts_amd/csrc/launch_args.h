@@ -23,6 +23,13 @@ inline GemmArgs mk(const Model& m, const float* A, RowMap am, const Lin& l, floa
     g.M = M; g.N = l.out; g.K = l.in;
     return g;
 }
+// mk without the step's fragment-ordered copy.  launch_gemm sends an M <= 64 product WITH Wt to k_skinny; the callers of this one stay on the many-row
+// kernels whatever M is: the staged flow direction (the independent check of the step's flow part) and the speaker projection (staged.cpp)
+inline GemmArgs mk_rows(const Model& m, const float* A, RowMap am, const Lin& l, float* C, RowMap cm, int M) {
+    GemmArgs g = mk(m, A, am, l, C, cm, M);
+    g.Wt = nullptr;
+    return g;
+}
 inline LnArgs mkln(const Model& m, const float* x, RowMap xm, const Norm& n, float* y, int64_t ldy, int rows) {
     LnArgs a;
     a.x = x; a.xmap = xm;

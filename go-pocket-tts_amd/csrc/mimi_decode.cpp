@@ -28,7 +28,7 @@ void mimi_setup(Model& m, MimiWs& w, int B, int T) {
     for (int j = 0; j < 4; j++) n_c[j] = (size_t)B * (w.Ps[j] + w.Ls[j]) * d.sea_ch[j];
     for (int j = 0; j < 3; j++) n_h[j] = (size_t)B * ((d.rb_k2[j] - 1) + w.Ls[j + 1]) * d.sea_hidden[j];
     size_t total = n_xp + n_up + n_n1 + n_qkv * d.mimi_layers + n_n1 + n_ff + n_c[0] + 2 * (n_c[1] + n_c[2] + n_c[3]) + n_h[0] + n_h[1] + n_h[2];
-    DevBuf& wsb = m.work(4, total * sizeof(float));
+    DevBuf& wsb = m.work(WORK_DECODER, total * sizeof(float));
     float* p = wsb.as<float>();
     w.xp = p; p += n_xp;
     w.up = p; p += n_up;

@@ -1,7 +1,7 @@
 // pitch.cpp -- the pitch of one part of a joined text, on the host (include/ptts.h ptts_pitch_opts, ptts_pitch_speed, ptts_pitch_resample_length,
 // ptts_pitch_resample, ptts_pitch_length, ptts_pitch_apply, ptts_pitch_table; pitch.h has the rule): the checks of the caller's options, the
 // prototype table and the statement of the result, which k_pitch_resample (pitch.hip) gives bit for bit and the tempo (tempo.cpp) finishes.
-// ptts_dsp_ext_set_pitch is in capi.cpp, with the handle's trim and tempo setters (dsp_ext.h has the one setter they all call).
+// ptts_dsp_ext_set_pitch is in capi_rows.cpp, with the handle's trim and tempo setters (dsp_ext.h has the one setter they all call).
 // No HIP header: the file builds with a plain C++ compiler, with tempo.cpp alone (tests/test_pitch_cpu.py does, with sanitizers).
 //
 // A tap is two fused multiply-adds, written as such; the output's gain is one f32 product.  Nothing else here may be contracted.

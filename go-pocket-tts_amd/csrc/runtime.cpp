@@ -62,7 +62,7 @@ Model::~Model() {
 
     cached_batch.reset();
     tcomb.clear();
-    ws.clear();
+    for (DevBuf& w : ws) w.release();
     if (own_arena && arena) (void)hipFree(arena);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -154,10 +154,35 @@ Model* model_replicate(Model& base, int device) {
     return m.release();
 }
 
+// the measurement pass's figures since ptts_profile_enable or the last read (bench.py), and the counters back to zero.  The caller holds m.mu
+void profile_read(Model& m, ptts_profile* out) {
+    PTTS_HIP(hipStreamSynchronize(m.stream));
+    std::memset(out, 0, sizeof *out);
+    double ms = 0;
+    for (size_t i = 0; i + 1 < m.prof.used; i += 2) {
+        float t = 0;
+        PTTS_HIP(hipEventElapsedTime(&t, m.prof.ev[i], m.prof.ev[i + 1]));
+        ms += t;
+    }
+    out->launches = m.prof.launches;
+    out->total_ms = ms;
+    out->algorithmic_bytes = m.prof.bytes;
+    out->weight_bytes = m.prof.wbytes;
+    if (m.prof.phases) {
+        PTTS_HIP(hipStreamSynchronize(m.stream2));
+        float t = 0;
+        PTTS_HIP(hipEventElapsedTime(&t, m.prof.phase[0], m.prof.phase[1])); out->prefill_ms = t;
+        PTTS_HIP(hipEventElapsedTime(&t, m.prof.phase[1], m.prof.phase[2])); out->ar_loop_ms = t;
+        PTTS_HIP(hipEventElapsedTime(&t, m.prof.phase[3], m.prof.phase[4])); out->mimi_ms = t;
+    }
+    snprintf(out->kernel, sizeof out->kernel, "%s", "k_skinny");
+    m.prof.used = 0; m.prof.bytes = 0; m.prof.wbytes = 0; m.prof.launches = 0; m.prof.phases = false;
+}
+
 // timestep embedder (flow_net.go:42-83) for one (s, t) pair, then 0.5*(e_s + e_t) (flow_net.go:320-335)
 void Model::compute_tcomb(float sv, float tv, float* dst) {
     const int C = d.flow_dim, nf = d.nfreq;
-    DevBuf& wsb = work(0, (size_t)(2 * nf + 3 * C) * sizeof(float));
+    DevBuf& wsb = work(WORK_TCOMB, (size_t)(2 * nf + 3 * C) * sizeof(float));
     float* feat = wsb.as<float>();
     float* h = feat + 2 * nf;
     float* e[2] = {h + C, h + 2 * C};

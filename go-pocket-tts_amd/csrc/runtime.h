@@ -1,9 +1,10 @@
-// runtime.h -- host-side engine above the kernels: device model, batch of FlowLM states,
-// prefill, AR step (hipGraph), Mimi decode, GenerateAudio loop.
+// runtime.h -- host-side engine above the kernels: device model and its table of work buffers (WorkSlot), batch of FlowLM states, prefill, AR step
+// (hipGraph), Mimi decode and encode, GenerateAudio loop, the continuous batch, the device side of the staged entry points (staged.cpp).
 #pragma once
 
 #include <atomic>
 #include <functional>
+#include <type_traits>
 
 #include "kernels.h"
 #include "model.h"
@@ -57,14 +58,56 @@ struct PinnedBuf {
     }
 };
 
-// Model::work's buffers of the egress and of the host-rows entry points, by name (the other slots are still numbers at their call sites).  Every
-// user holds Model::mu from its first use of a buffer until the work that reads it is queued on Model::stream (device_convert even waits for
-// it), so two names for one number never hold data at the same time.
+// Model::work's buffers, every one by name: the table of what lives in Model::ws.  Every user holds Model::mu from its first use of a buffer until
+// the work that reads it is queued on a stream of the model (the staged entry points and staged_convert even wait for it), so two names for one
+// number never hold data at the same time.  Behind each name: who holds the buffer, and until when.  Where one number has several names, the
+// comment of the later names says why they never meet the earlier ones.  A holder that asks for more than the buffer has goes through
+// DevBuf::ensure's hipFree, which waits for the device: a buffer never moves under queued work.
 enum WorkSlot : size_t {
+    WORK_TCOMB = 0,              // Model::compute_tcomb: the timestep features, hidden row and the two embeddings; until its launches are queued on Model::stream (tcomb_for waits for them)
+    WORK_VOICE_RAW = 1,          // voice_create, batch_set_voice: one layer of a host voice cache in front of its scatter; until the stream wait that follows each layer
+    WORK_PROMPT_META = 2,        // batch_prompt: the ragged table (row -> slot | position | offsets); until the prefill is queued on its stream (the model's, or the batch's io_stream)
+    WORK_PROMPT_ACT = 3,         // batch_prompt: the prefill's activations (x | xn | qkv | attn | ff); likewise
+    WORK_DECODER = 4,            // mimi_setup: the decoder's activations of one group.  A Chunk holds it from decoder_setup to decode_rest's wait for stream2; the staged decode
+                                 // until its stream wait; the continuous engine (which keeps Model::mu while busy) from one start_decode to the next: its serial decodes run on
+                                 // Model::stream and its concurrent ones on ContEngine::dec, and a decode waits for lat_free[lprev], recorded behind the previous decode whichever
+                                 // stream that ran on.  cont_create sizes it for the largest sub-group, so no decode reallocates it under another
+    WORK_PROMPT_ROWS = 5,        // stage_prompt: the packed prompt rows (gathered text rows, voice embeddings); until batch_prompt has copied them, in stream order
+    WORK_TEXT_ROWS = 5,          // staged_text_embeddings: the gathered rows; until its stream wait.  Under Model::mu from first use to that wait, as every staged_* holder: never beside another
+    WORK_PROMPT_UPLOAD = 5,      // staged_prompt: the caller's rows in front of batch_prompt; until its stream wait
+    WORK_PROMPT_IDS = 6,         // stage_prompt: the batch's token ids; until the gathers are queued
+    WORK_TEXT_IDS = 6,           // staged_text_embeddings: the ids; until its stream wait
+    WORK_PCM = 7,                // Chunk (generate, generate_joined): the decoded rows [B][T * spf]; from decoder_setup until the results are read, the last wait of the chunk (under Model::mu throughout)
+    WORK_CONT_PCM = 7,           // the continuous engine: one sub-group's decoded rows, sized in cont_create for the largest; sub-groups follow each other in stream order on one stream, decodes
+                                 // are ordered by lat_free[lprev] as WORK_DECODER's.  The engine holds Model::mu while busy, so no Chunk runs beside it
+    WORK_STREAM_S16 = 8,         // Chunk::stream_s16: the PCM16 image of streamed rows, sized [B][T * spf] in decoder_setup; read by emit_upto's copies on stream2, which decode_rest drains
+    WORK_EGRESS_S16 = 8,         // results_deliver: the PCM16 image of a group's rows; until the caller's wait behind the copies.  In a Chunk that also streams, the size is the same
+                                 // [B][T * spf] int16 as WORK_STREAM_S16's (n = B, pcm_stride = T * spf), so this ensure never outgrows that one, and it runs behind decode_rest's wait
+                                 // for stream2: the streamed copies are done.  In the continuous engine cont_create sizes it for the largest sub-group, ordered as WORK_CONT_PCM
+    WORK_DECODE_IO = 8,          // staged_decode: latents | pcm | mimi latent | transformer rows of one call; until its stream wait
+    WORK_SPEAKER_IO = 8,         // staged_speaker_project: latents | embedding; until its stream wait
+    WORK_NOISE_ROWS = 8,         // staged_noise_rows: the drawn rows; until its stream wait
+    WORK_PREFILL_PLANES = 9,     // batch_prompt: linear2's split-K planes [S][R][D]; from the launch that writes them to the next layer's LayerNorm launch, which adds them (stream order)
+    WORK_FLOW_DIRECTION = 9,     // staged_flow_direction: its whole workspace; until its stream wait.  It runs no prefill, and every caller of batch_prompt keeps Model::mu until its
+                                 // prefill has run (a Chunk and the continuous engine until their results are out; voice_build and staged_prompt until their stream wait)
+    WORK_VOICE_SLOTS = 10,       // batch_apply_voice: the slots a device voice is applied to; until the launches are queued on the batch's stream
+    WORK_PCM_ROWS = 11,          // Chunk::deliver: the PcmRow table of the decoder's direct store; until decode_rest's wait for stream2
+    WORK_NOISE_SPECS = 12,       // stage_noise: the batch's NoiseSpec per slot; until launch_noise_fill is queued
+    WORK_NOISE_ROWS_SPEC = 12,   // staged_noise_rows: its one NoiseSpec; until its stream wait
+    WORK_CONT_RESERVE = 13,      // cont_create sizes it (a decode's worth of latents); nothing reads it since ContEngine::lat took the gathered frames.  Kept: the footprint is unchanged
+    WORK_CONT_RETIRE = 15,       // take_snapshot: the slots that retire; until launch_slot_retire is queued on Model::stream
+    WORK_ENCODER = 16,           // mimi_encode_clip: the encoder's activations of one clip; until the caller's stream wait behind the clip
+    WORK_ENCODER_LATENTS = 17,   // mimi_encode: one clip's latents; until the stream wait behind each clip's copy out
+    WORK_EMBEDDING_IO = 17,      // voice_embedding_device: a clip's latents and their projection; until its stream wait.  It calls mimi_encode_clip, not mimi_encode
+    WORK_VOICE_BUILD_ROWS = 18,  // voice_build: the embeddings packed as prompt rows; until the stream wait behind each group
+    WORK_VOICE_EXPORT = 19,      // voice_export: the layers in the reference's layout; until the read-back (d2h waits)
+    WORK_VOICE_BUILD_TABLE = 20, // voice_build: the VoiceDst table of launch_voice_extract; until the stream wait behind each group
     WORK_EGRESS_PAGEABLE = 24,   // results_deliver: converted rows whose result buffer is pageable, copied out from here
-    WORK_CONVERT_IN = 25,        // device_convert (ptts_resample, ptts_pcm_encode): the packed input rows
+    WORK_CONVERT_IN = 25,        // staged_convert (ptts_resample, ptts_pcm_encode): the packed input rows; until its stream wait
     WORK_CONVERT_OUT = 26,       // ... and the packed output rows
     WORK_ENCODER_CLIP = 26,      // mimi_encode_clip: a voice clip at its own rate, in front of k_resample.  Shares WORK_CONVERT_OUT's storage (see above)
+    WORK_STREAM_SNAP = 27,       // Chunk::emit_upto: a hand-over's snapshot of (active, n_frames) for its k_resample rows; ranges follow each other on stream2, which decode_rest drains
+    WORK_STREAM_STAGE = 28,      // Chunk::stream_stage: the converted rows of streamed requests, one row of stage_row bytes per slot; from decoder_setup until decode_rest drains stream2
     WORK_DSP_SCRATCH = 29,       // dsp_launch: peak words, then what dsp_scratch (dsp_spec.h) plans for each row's stages
     WORK_HOST_ROWS = 30,         // dsp_rows_device: the packed rows of ptts_dsp_rows and its kin; join_rows_device: the parts, then the joined row; part_rows_device: the rows, then their forms
     WORK_JOINED = 31,            // generate_joined: the text's joined row, sized before the first group runs and kept until the egress has read it
@@ -76,6 +119,7 @@ enum WorkSlot : size_t {
     WORK_JOIN_STAGE = 37,        // ... and its egress where that cannot store into the result's buffer itself, indexed like that buffer
     WORK_PITCH = 38,             // generate_joined with a pitch: PartRow::shifted of a group's rows, at the stride of the longest a decoded row can become
 };
+constexpr size_t kWorkSlots = 39;   // one past the largest value above (14 and 21-23 have no holder and stay empty DevBufs)
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
 constexpr int kNativeRate = 24000;            // the decoder's rate: requests at 0 / 24000 in f32 or PCM16 are delivered as before, without k_resample
@@ -137,7 +181,7 @@ struct Model {
     std::vector<hipEvent_t> events;
     std::mutex mu;
     std::map<int, std::unique_ptr<DevBuf>> tcomb;  // lsd_steps -> [n][flow_dim]: 0.5*(embed_s(i/n) + embed_t((i+1)/n))
-    std::vector<std::unique_ptr<DevBuf>> ws;       // grow-only workspaces (Mimi decode, prefill)
+    DevBuf ws[kWorkSlots];                         // grow-only workspaces, one per WorkSlot value (work() below)
     std::unique_ptr<Batch> cached_batch;
     Prof prof;
     std::map<std::pair<int, int>, std::unique_ptr<RateFilter>> rate_filters;   // (input rate, output rate) -> k_resample's taps (resample.cpp)
@@ -160,11 +204,12 @@ struct Model {
     ~Model();
     template <class T> const T* at(size_t off) const { return off == NONE ? nullptr : reinterpret_cast<const T*>(arena + off); }
     UploadArena upload;
-    DevBuf& work(size_t i, size_t bytes) {
-        while (ws.size() <= i) ws.emplace_back(new DevBuf());
-        ws[i]->ensure(bytes);
-        return *ws[i];
+    // by name only: an integer does not convert to a WorkSlot, so a call with a bare number does not compile
+    DevBuf& work(WorkSlot slot, size_t bytes) {
+        ws[slot].ensure(bytes);
+        return ws[slot];
     }
+    static_assert(!std::is_convertible<int, WorkSlot>::value && !std::is_convertible<size_t, WorkSlot>::value, "Model::work takes a WorkSlot name, never a number");
     void use_device() const { PTTS_HIP(hipSetDevice(device)); }
     // seeds of requests that name none (noise_seed == 0): a splitmix64 stream seeded with the clock when the model is opened
     // (the reference seeds its generator the same way, runtime_native_safetensors.go:27-32); never 0
@@ -283,6 +328,7 @@ std::vector<std::unique_ptr<Voice>> voice_build(Model& m, const float* const* em
 // the exact inverse of what launch_voice_scatter reads (a bf16 cache widened exactly).  The caller holds v.m->mu.
 void voice_export(const Voice& v, int layer0, int n_layers, float* out);
 void voice_read_state(const Voice& v, int layer, float* out);
+std::vector<uint8_t> voice_state_bytes(const Voice& v);   // the whole voice as a model-state file's bytes (voice_export + voice_state_file).  The caller holds v.m->mu
 
 // buffers of one Mimi decode (all channels-last, spanning the whole utterance so that frame ranges can be decoded in order)
 struct MimiWs {
@@ -323,6 +369,7 @@ int64_t mimi_encode_samples(int64_t n_samples, int rate);   // the 24 kHz sample
 void require_encoder(const Desc& d);
 void mimi_encode_stage_shapes(const Desc& d, int64_t n_samples, int64_t* shapes /* [kEncStages][2] (rows, channels) */);   // PTTS_EFORMAT naming the missing tensor on a checkpoint without encoder weights
 Model* model_open(Plan* plan, void* device_arena, int fill);
+void profile_read(Model& m, ptts_profile* out);   // ptts_profile_read behind its lock: the figures of the measurement pass, counters reset (runtime.cpp)
 Batch* batch_new(Model& m, int n_slots, int cap, int max_steps);
 void batch_reset(Batch& b);
 void batch_set_voice(Batch& b, int slot, const float* const* caches, const int64_t* steps, const int64_t* offsets);
@@ -487,6 +534,27 @@ void parts_launch(Model& m, std::vector<PartRow>& rows, hipStream_t s, const std
 void part_rows_device(Model& m, const PartStages* per_row, const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out,
                       ptts_trim_info* info);
 
+// ---- the staged entry points' device side (staged.cpp): the pipeline's pieces one call at a time, behind include/ptts.h's ptts_text_embeddings,
+// ptts_batch_prompt / _step / _read_kv, ptts_decode_latents, ptts_noise_rows, ptts_flow_direction, ptts_speaker_project, ptts_resample / ptts_pcm_encode
+// and the voice entry points.  One convention: the CALLER holds Model::mu and has selected the device (the extern "C" function, behind its argument
+// checks); each function runs on Model::stream, takes host operands and results unless it says otherwise, and returns with the stream drained ----
+void staged_text_embeddings(Model& m, const int64_t* ids, int64_t n, float* out);   // n > 0 ids, checked -> out [n][d_model]
+void staged_prompt(Batch& b, const float* emb, const int64_t* row_offsets);         // the rows uploaded, then batch_prompt
+// one AR step: NaN rows of frames_in replaced by BOS, noise (null: zeros) as x0, step_core; a k_flow_cluster hand-off that gave up is recovered here
+// (flow_cluster_recover, the flow part again from the saved x0: the same bits); kv_len + 1; the optional outputs back
+void staged_step(Batch& b, const float* frames_in, int lsd_steps, const float* noise, float* frames_out, float* eos_logits, float* last_hidden);
+void staged_read_kv(const Batch& b, int slot, int layer, float* k, float* v);       // a slot's keys and values of one layer as f32 [H][kv_len][hd]
+// LatentToMimi + MimiDecode of [n_utt][frames][ldim]; pcm, mimi_latent, transformer_out (the decoder transformer's rows, staged parity checks) optional
+void staged_decode(Model& m, const float* latents, int n_utt, int frames, float* pcm, float* mimi_latent, float* transformer_out);
+void staged_noise_rows(Model& m, uint64_t seed, float temperature, int rows, float* out);   // stage_noise's draw for one seed: [rows][ldim]
+void staged_flow_direction(Model& m, const float* c, float sv, float tv, const float* x, int n, float* out);   // flowNet.Forward on n rows, many-row kernels only
+// n host rows -> n host rows through one device buffer each way (PackedRows), one k_resample launch per RowRing::kRows rows; f null: format only
+void staged_convert(Model& m, const float* const* in, const int64_t* n_in, int32_t n, const RateFilter* f, const int64_t* n_out, int fmt, void* const* out);
+// the speaker projection, THE one place that builds it: device latents [frames][speaker_proj.in] -> device rows [frames][d_model], queued, no wait
+void speaker_project_device(Model& m, const float* lat, int64_t frames, float* out);
+void staged_speaker_project(Model& m, const float* latent, int64_t frames, float* out);     // ... on host latents
+// one clip -> its voice embedding in out (host, [ceil(n24 / hop)][d_model]): mimi_encode_clip, then the projection where the encoder left the latents; the frame count
+int64_t voice_embedding_device(Model& m, const float* pcm, int64_t n_samples, float* out, int rate = kNativeRate);
 
 // text front end (text.cpp; internal/text/prepare.go, chunk.go)
 struct TextChunk {

@@ -1,6 +1,6 @@
 // tempo.cpp -- the speaking rate of one part of a joined text, on the host (include/ptts.h ptts_tempo_opts, ptts_tempo_length, ptts_tempo_plan,
 // ptts_tempo_apply; tempo.h has the rule): the checks of the caller's options and the statement of the result, which k_tempo_plan and
-// k_tempo_store (tempo.hip) give bit for bit.  ptts_dsp_ext_set_tempo is with the handle's other setters (capi.cpp).
+// k_tempo_store (tempo.hip) give bit for bit.  ptts_dsp_ext_set_tempo is with the handle's other setters (capi_rows.cpp).
 // No HIP header: the file builds with a plain C++ compiler, alone (tests/test_tempo_cpu.py does, with sanitizers).
 //
 // The blend of a splice is two f32 divisions, two f32 products and one f32 sum, each rounded once.  Nothing here may be contracted into a fused

@@ -30,7 +30,7 @@ std::vector<std::unique_ptr<Voice>> voice_build(Model& m, const float* const* em
             row_off[(size_t)i + 1] = row_off[(size_t)i] + frames[g0 + i];
         }
         std::unique_ptr<Batch> b(batch_new(m, B, cap, 1));
-        DevBuf& rows = m.work(18, (size_t)row_off[(size_t)B] * d.d_model * sizeof(float));
+        DevBuf& rows = m.work(WORK_VOICE_BUILD_ROWS, (size_t)row_off[(size_t)B] * d.d_model * sizeof(float));
         for (int i = 0; i < B; i++)
             PTTS_HIP(hipMemcpyAsync(rows.as<float>() + row_off[(size_t)i] * d.d_model, emb[g0 + i], (size_t)frames[g0 + i] * d.d_model * sizeof(float),
                                     hipMemcpyHostToDevice, m.stream));
@@ -47,7 +47,7 @@ std::vector<std::unique_ptr<Voice>> voice_build(Model& m, const float* const* em
             tab[(size_t)i] = VoiceDst{v->k.p, v->v.p, v->offset, i};
             out.push_back(std::move(v));
         }
-        DevBuf& dt = m.work(20, tab.size() * sizeof(VoiceDst));
+        DevBuf& dt = m.work(WORK_VOICE_BUILD_TABLE, tab.size() * sizeof(VoiceDst));
         PTTS_HIP(hipMemcpyAsync(dt.p, tab.data(), tab.size() * sizeof(VoiceDst), hipMemcpyHostToDevice, m.stream));
         launch_voice_extract(b->kcache.p, b->vcache.p, B, b->cap, d.heads, d.hd, (int)es, d.n_layers, dt.as<VoiceDst>(), B, cap, m.stream);
         PTTS_HIP(hipStreamSynchronize(m.stream));   // (the batch and the host table go out of scope)
@@ -64,12 +64,22 @@ void voice_export(const Voice& v, int layer0, int n_layers, float* out) {
     const size_t n = (size_t)n_layers * 2 * v.offset * d.heads * d.hd;
     if (n == 0) return;
     const size_t lb = v.layer_bytes();
-    DevBuf& o = m.work(19, n * sizeof(float));
+    DevBuf& o = m.work(WORK_VOICE_EXPORT, n * sizeof(float));
     launch_voice_export((const char*)v.k.p + lb * layer0, (const char*)v.v.p + lb * layer0, v.offset, d.heads, d.hd, n_layers,
                         m.opts.kv == PTTS_KV_BF16, o.as<float>(), m.stream);
     d2h(out, o.p, n * sizeof(float), m.stream);
 }
 
 void voice_read_state(const Voice& v, int layer, float* out) { voice_export(v, layer, 1, out); }
+
+std::vector<uint8_t> voice_state_bytes(const Voice& v) {
+    const Desc& d = v.m->d;
+    const size_t per = (size_t)2 * v.offset * d.heads * d.hd;
+    std::vector<float> all(per * d.n_layers);
+    voice_export(v, 0, d.n_layers, all.data());
+    std::vector<const float*> caches((size_t)d.n_layers);
+    for (int l = 0; l < d.n_layers; l++) caches[(size_t)l] = all.data() + per * l;
+    return voice_state_file(caches.data(), v.offset, d.n_layers, d.heads, d.hd);
+}
 
 }  // namespace ptts
