@@ -181,11 +181,13 @@ int ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t) { return e
 
 // the device form of ptts_pitch_apply on host rows: the launches of a joined call's pitch and of the tempo behind it; a row with neither is copied on
 // the host.  p[i] null: the tempo alone, as ptts_tempo_rows
-int ptts_pitch_rows(ptts_model* h, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows,
-                    float* const* out, int64_t* n_out) {
+// f null: ptts_pitch_rows.  Otherwise ptts_formant_rows: row i keeps its formants where f[i] says so and the row has a resampling step
+static int pitch_rows(ptts_model* h, const char* what, const ptts_formant_opts* const* f, bool args_null, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t,
+                      const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
     std::vector<PitchScan> pitches;
     std::vector<TempoScan> tempos;
-    return part_rows(h, "pitch", !p || !t || !n_out, in, n, rows, out, n_out, nullptr, [&](int i, PartStages& st) {
+    return part_rows(h, what, args_null || !p || !t || !n_out, in, n, rows, out, n_out, nullptr, [&](int i, PartStages& st) {
+        if (f && f[i]) row_refuse(i, formant_opts_error(f[i]));
         if (p[i]) row_refuse(i, pitch_opts_error(p[i]));
         if (t[i]) row_refuse(i, tempo_opts_error(t[i]));
         PitchSteps run{t[i] ? t[i]->speed_permille : 1000, false, t[i] != nullptr};
@@ -201,8 +203,26 @@ int ptts_pitch_rows(ptts_model* h, const ptts_pitch_opts* const* p, const ptts_t
         st.pitch = run.resample ? &pitches[(size_t)i] : nullptr;
         st.tempo = run.tempo ? &tempos[(size_t)i] : nullptr;
         if (n[i] > 0 && in[i] == out[i] && (st.pitch || st.tempo)) row_refuse(i, "pitch: out is in");
+        if (f && f[i] && f[i]->keep && st.pitch) {
+            row_refuse(i, formant_pitch_error(st.pitch->p));
+            st.formant = true;
+        }
     }, pitches, tempos);
 }
+
+int ptts_pitch_rows(ptts_model* h, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t, const float* const* in, const int64_t* n, int32_t rows,
+                    float* const* out, int64_t* n_out) {
+    return pitch_rows(h, "pitch", nullptr, false, p, t, in, n, rows, out, n_out);
+}
+
+// the device form of ptts_formant_apply on host rows: ptts_pitch_rows, and for the rows with the option the formant kernels around the resample
+int ptts_formant_rows(ptts_model* h, const ptts_formant_opts* const* f, const ptts_pitch_opts* const* p, const ptts_tempo_opts* const* t, const float* const* in,
+                      const int64_t* n, int32_t rows, float* const* out, int64_t* n_out) {
+    return pitch_rows(h, "formant", f, !f, p, t, in, n, rows, out, n_out);
+}
+
+// the option of a joined call's parts, attached to the handle (formant.cpp checks it, and stays a file that builds without HIP)
+int ptts_dsp_ext_set_formant(ptts_dsp_ext* e, const ptts_formant_opts* f) { return ext_set(e, "formant", f, formant_opts_error, formant_design, &DspExt::formant, &DspExt::fmt); }
 
 // the pitch of a joined call's parts, attached to the handle (pitch.cpp checks and designs it, and stays a file that builds without HIP)
 int ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p) { return ext_set(e, "pitch", p, pitch_opts_error, pitch_design, &DspExt::pitch, &DspExt::pit); }

@@ -2,8 +2,9 @@
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
 // them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the part
-// stages of a joined call -- the trim (trim.hip), the pitch (pitch.hip, with its one table image per model) and the tempo (tempo.hip): their table
-// builders, the one chain that runs them in that order (parts_launch) and the one round trip of host rows through it (part_rows_device).
+// stages of a joined call -- the trim (trim.hip), the pitch (pitch.hip, with its one table image per model; formant.hip around it for the rows
+// that keep their formants) and the tempo (tempo.hip): their table builders, the one chain that runs them in that order (parts_launch) and the
+// one round trip of host rows through it (part_rows_device).
 #include <cmath>
 
 #include "row_tables.h"
@@ -289,7 +290,7 @@ void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_
 
 // ---- the part stages of a joined call: the trim (trim.hip; trim.h), the pitch (pitch.hip; pitch.h), the tempo (tempo.hip; tempo.h) ----
 
-PitchImage::~PitchImage() {
+UploadedTable::~UploadedTable() {
     if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
     if (staged) (void)hipHostFree(staged);
 }
@@ -338,30 +339,45 @@ void tempo_launch(Model& m, std::vector<TempoRow>& rows, const std::vector<const
     });
 }
 
-// the pitch table's image on the device: one per model whatever the pitches.  First use: made from pitch.cpp's table and queued on s from page-locked
-// memory, nothing waits on the host; launches on s follow it, another stream waits for `ready` (as rate_filter, resample.cpp)
-const float* pitch_image(Model& m, hipStream_t s) {
-    if (m.pitch_image) {
-        if (m.pitch_image->up != s) PTTS_HIP(hipStreamWaitEvent(s, m.pitch_image->ready, 0));
-        return m.pitch_image->image.as<float>();
+// A table that one model uploads once, on first use (runtime.h UploadedTable): `bytes` filled by fill(staged) in page-locked memory and queued on s, nothing
+// waits on the host; launches on s follow it, another stream waits for `ready` (as rate_filter, resample.cpp)
+template <class Fill>
+const void* upload_once(std::unique_ptr<UploadedTable>& slot, size_t bytes, hipStream_t s, Fill&& fill) {
+    if (slot) {
+        if (slot->up != s) PTTS_HIP(hipStreamWaitEvent(s, slot->ready, 0));
+        return slot->image.p;
     }
-    std::unique_ptr<PitchImage> f(new PitchImage());
-    constexpr size_t kBytes = (size_t)kPitchImage * 2 * sizeof(float);
-    PTTS_HIP(hipHostMalloc((void**)&f->staged, kBytes, hipHostMallocDefault));
-    std::memset(f->staged, 0, kBytes);
-    const float* const h = pitch_table_h();
-    const float* const hd = pitch_table_hd();
-    for (int q = 0; q < kPitchEntries; q++) {
-        f->staged[2 * (size_t)pitch_image_at(q)] = h[q];
-        f->staged[2 * (size_t)pitch_image_at(q) + 1] = hd[q];
-    }
-    f->image.ensure(kBytes);
-    PTTS_HIP(hipMemcpyAsync(f->image.p, f->staged, kBytes, hipMemcpyHostToDevice, s));
+    std::unique_ptr<UploadedTable> f(new UploadedTable());
+    PTTS_HIP(hipHostMalloc(&f->staged, bytes, hipHostMallocDefault));
+    std::memset(f->staged, 0, bytes);
+    fill(f->staged);
+    f->image.ensure(bytes);
+    PTTS_HIP(hipMemcpyAsync(f->image.p, f->staged, bytes, hipMemcpyHostToDevice, s));
     PTTS_HIP(hipEventCreateWithFlags(&f->ready, hipEventDisableTiming));
     PTTS_HIP(hipEventRecord(f->ready, s));
     f->up = s;
-    m.pitch_image = std::move(f);
-    return m.pitch_image->image.as<float>();
+    slot = std::move(f);
+    return slot->image.p;
+}
+
+// the pitch table's image on the device: one per model whatever the pitches, made from pitch.cpp's table
+const float* pitch_image(Model& m, hipStream_t s) {
+    return static_cast<const float*>(upload_once(m.pitch_image, (size_t)kPitchImage * 2 * sizeof(float), s, [](void* to) {
+        float* const staged = static_cast<float*>(to);
+        const float* const h = pitch_table_h();
+        const float* const hd = pitch_table_hd();
+        for (int q = 0; q < kPitchEntries; q++) {
+            staged[2 * (size_t)pitch_image_at(q)] = h[q];
+            staged[2 * (size_t)pitch_image_at(q) + 1] = hd[q];
+        }
+    }));
+}
+
+// formant.cpp's float64 tables on the device, as they are: one copy per model
+const double* formant_tables_device(Model& m, hipStream_t s) {
+    return static_cast<const double*>(upload_once(m.formant_tables, (size_t)kFormantTableDoubles * sizeof(double), s, [](void* staged) {
+        std::memcpy(staged, formant_tables(), (size_t)kFormantTableDoubles * sizeof(double));
+    }));
 }
 
 // The tables of the pitch's resampling step: rows[i] states src, dst and n, key[i] its design (p is not 1000); n_out (host arithmetic), the table's
@@ -380,6 +396,71 @@ void pitch_launch(Model& m, std::vector<PitchRow>& rows, const std::vector<const
         for (int i = 0; i < k; i++) tiles = std::max(tiles, (rows[first + (size_t)i].n_out + kPitchTile - 1) / kPitchTile);
         launch_pitch(rows_dev, k, (int)tiles, designs_dev, image, s);
     });
+}
+
+// The formant kernels' tables: 256 rows a turn, launch(rows_dev, count, first) between the turn's stage() and done()
+template <class Launch>
+void formant_tables_launch(Model& m, const std::vector<FormantRow>& fr, hipStream_t s, Launch&& launch) {
+    constexpr size_t kRows = RowRing<FormantRow>::kRows;
+    for (size_t at = 0; at < fr.size(); at += kRows) {
+        const int n = (int)std::min(kRows, fr.size() - at);
+        launch(m.formant_ring.stage(fr.data() + at, n, s), n, at);
+        m.formant_ring.done(s);
+    }
+}
+
+// The pitch step of parts_launch: t and key are its rows with a pitch as part_stage made them (src: where the row stands; dst: PartRow::shifted), in the
+// order of `rows`.  Rows that keep their formants (PartStages::formant) get their frames' coefficients and their residual first (k_formant_analyse,
+// k_formant_whiten, one launch of each per table of such rows); k_pitch_resample then reads the residual and writes the resampled residual, in the one
+// launch per table that serves every row with a pitch; k_formant_shape puts the envelopes back, into PartRow::shifted.  The three work buffers are
+// made only when a row has the option: without one this is pitch_launch, and nothing else
+void pitch_stage_launch(Model& m, const std::vector<PartRow>& rows, std::vector<PitchRow>& t, const std::vector<const PitchScan*>& key, hipStream_t s) {
+    std::vector<FormantRow> fr;
+    std::vector<size_t> at;   // where in t
+    size_t k = 0, frames = 0, samples = 0, shifted = 0;
+    for (const PartRow& r : rows) {
+        if (!r.st.pitch) continue;
+        const size_t mine = k++;
+        if (!r.st.formant || t[mine].n <= 0) continue;
+        FormantRow f{};
+        f.n = t[mine].n;
+        f.n_r = pitch_resample_length(f.n, key[mine]->p);
+        f.K = (int32_t)formant_frames(f.n);
+        f.p = key[mine]->p;
+        if (f.n >= kTempoMaxSamples || f.n_r >= kTempoMaxSamples || f.p < kFormantMinPitch || f.p > kFormantMaxPitch)
+            throw Error(PTTS_EINVAL, "ptts-hip: internal: a row that keeps its formants is outside what the option serves");
+        frames += (size_t)f.K; samples += (size_t)f.n; shifted += (size_t)f.n_r;
+        fr.push_back(f);
+        at.push_back(mine);
+    }
+    if (fr.empty()) { pitch_launch(m, t, key, s); return; }
+    float* coeffs = m.work(WORK_FORMANT_COEFFS, frames * kFormantOrder * sizeof(float)).as<float>();
+    float* e = m.work(WORK_FORMANT_RESIDUAL, samples * sizeof(float)).as<float>();
+    float* er = m.work(WORK_FORMANT_SHIFTED, shifted * sizeof(float)).as<float>();
+    for (size_t i = 0; i < fr.size(); i++) {
+        FormantRow& f = fr[i];
+        PitchRow& p = t[at[i]];
+        f.x = p.src; f.e = e; f.er = er; f.out = p.dst; f.coeffs = coeffs;
+        p.src = e; p.dst = er;   // the resample runs on the residual
+        coeffs += (size_t)f.K * kFormantOrder; e += f.n; er += f.n_r;
+    }
+    const double* const tables = formant_tables_device(m, s);
+    formant_tables_launch(m, fr, s, [&](const FormantRow* dev, int n, size_t first) {
+        int64_t K = 0, tiles = 0;
+        for (int i = 0; i < n; i++) {
+            K = std::max<int64_t>(K, fr[first + (size_t)i].K);
+            tiles = std::max(tiles, (fr[first + (size_t)i].n + kFormantHop / 2 + kFormantHop - 1) / kFormantHop);
+        }
+        launch_formant_analyse(dev, n, K, tables, s);
+        launch_formant_whiten(dev, n, tiles, s);
+    });
+    pitch_launch(m, t, key, s);
+    formant_tables_launch(m, fr, s, [&](const FormantRow* dev, int n, size_t first) {
+        int64_t tiles = 0;
+        for (int i = 0; i < n; i++) tiles = std::max(tiles, (fr[first + (size_t)i].n_r + kFormantHop - 1) / kFormantHop);
+        launch_formant_shape(dev, n, tiles, s);
+    });
+    for (size_t i = 0; i < fr.size(); i++) t[at[i]].dst = fr[i].out;   // where the row stands behind the step
 }
 
 // one stage of parts_launch behind the trim: the rows that have it, each reading where its predecessor left the row (PartRow::out, n_out) and
@@ -434,7 +515,7 @@ void parts_launch(Model& m, std::vector<PartRow>& rows, hipStream_t s, const std
         }
         if (phase) phase("trim");
     }
-    if (part_stage<PitchRow>(rows, &PartStages::pitch, &PartRow::shifted, [&](std::vector<PitchRow>& t, const std::vector<const PitchScan*>& k) { pitch_launch(m, t, k, s); }) && phase)
+    if (part_stage<PitchRow>(rows, &PartStages::pitch, &PartRow::shifted, [&](std::vector<PitchRow>& t, const std::vector<const PitchScan*>& k) { pitch_stage_launch(m, rows, t, k, s); }) && phase)
         phase("pitch");
     if (part_stage<TempoRow>(rows, &PartStages::tempo, &PartRow::scaled, [&](std::vector<TempoRow>& t, const std::vector<const TempoScan*>& k) { tempo_launch(m, t, k, s); }) && phase)
         phase("tempo");

@@ -1,9 +1,10 @@
 // dsp_ext.h -- the handle behind ptts_dsp_opts.ext (include/ptts.h ptts_dsp_ext): what true_peak.cpp (which makes and
-// frees it), compressor.cpp and limiter.cpp (which set its compressor and its limiter), capi_rows.cpp (which sets its trim, its tempo and its pitch) and
-// dsp_spec.cpp (which reads it) share, and the one setter behind the five ptts_dsp_ext_set_*.  No HIP header.
+// frees it), compressor.cpp and limiter.cpp (which set its compressor and its limiter), capi_rows.cpp (which sets its trim, its tempo, its pitch and its formant option) and
+// dsp_spec.cpp (which reads it) share, and the one setter behind the six ptts_dsp_ext_set_*.  No HIP header.
 #pragma once
 #include "compressor.h"
 #include "eq.h"
+#include "formant.h"
 #include "limiter.h"
 #include "opts_check.h"
 #include "pitch.h"
@@ -18,8 +19,9 @@ namespace ptts {
 // front of the join, and whatever fixes a row's length before the decode refuses it (dsp_spec.h dsp_trim_refusal).
 // The tempo that ptts_dsp_ext_set_tempo attached (tempo.h: the speed) is served and refused like the trim, behind it (dsp_spec.h dsp_tempo_refusal).
 // The pitch that ptts_dsp_ext_set_pitch attached (pitch.h: p, D, g) likewise, between the trim and the tempo (dsp_spec.h dsp_pitch_refusal).
+// The option that ptts_dsp_ext_set_formant attached (formant.h: keep) goes with the pitch: it changes how the resampling step runs, nothing else.
 // Copied out under the registry's mutex, which the setters take too
-struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; bool limit = false; LimScan lim{}; bool trim = false; TrimScan trm{}; bool tempo = false; TempoScan tmp{}; bool pitch = false; PitchScan pit{}; };
+struct DspExt { bool true_peak = false; float ceiling = 1.0f; bool compress = false; CmpScan cmp{}; bool limit = false; LimScan lim{}; bool trim = false; TrimScan trm{}; bool tempo = false; TempoScan tmp{}; bool pitch = false; PitchScan pit{}; bool formant = false; FormantScan fmt{}; };
 bool ext_lookup(const ptts_dsp_ext* e, DspExt* out);
 
 }  // namespace ptts

@@ -27,6 +27,7 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->tmp = ext.tmp;
     out->pitch = ext.pitch;
     out->pit = ext.pit;
+    out->formant = ext.formant && ext.fmt.keep != 0;
     return std::string();
 }
 

@@ -17,6 +17,7 @@ struct DspSpec {
     bool trim = false; TrimScan trm{};                 // the trim of a joined call's parts (trim.h): no stage of the chain, neither rest() nor any() counts it
     bool tempo = false; TempoScan tmp{};               // the tempo of a joined call's parts (tempo.h), behind the trim: no stage of the chain either
     bool pitch = false; PitchScan pit{};               // the pitch of a joined call's parts (pitch.h), between the trim and the tempo: no stage of the chain either
+    bool formant = false;                              // keep the formants around that pitch (formant.h): set with keep == 1 alone; without a pitch it says nothing
     bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
     bool any() const { return compress || rest(); }
 };

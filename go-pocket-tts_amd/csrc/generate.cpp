@@ -214,7 +214,7 @@ struct JoinSink {
     int fail = PTTS_OK;           // the code of the first chunk, in text order, that was cancelled or ran past the decoder's reach
     std::string fail_msg;
     // What the join options' ext asks for every part in front of k_join, resolved once, before anything launches (runtime.h PartStages; parts_launch
-    // runs it): a trim, whose length comes back from the device; a pitch other than 1000; a tempo -- behind a pitch the pair (speed, pitch) was
+    // runs it): a trim, whose length comes back from the device; a pitch other than 1000 (with the formants kept, where the handle says so); a tempo -- behind a pitch the pair (speed, pitch) was
     // resolved beforehand (pitch.h pitch_steps), `tmp` carries the effective speed and the step is off at 1000.  The designs the stages point to:
     PartStages stages;
     TrimScan trm{};
@@ -887,6 +887,11 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
             sink.tmp.speed = run.E;
         }
         sink.stages = PartStages{spec.trim ? &sink.trm : nullptr, run.resample ? &sink.pit : nullptr, run.tempo ? &sink.tmp : nullptr};
+        if (spec.formant && run.resample) {   // keep the formants around that resample: the pair (option, pitch) is resolved here too
+            e = formant_pitch_error(spec.pit.p);
+            if (!e.empty()) refuse("join: " + e);
+            sink.stages.formant = true;
+        }
     }
     if (streamed) {   // window after window only the causal stages run
         if (o.loudness) dsp_spec_loudness(spec, nullptr);

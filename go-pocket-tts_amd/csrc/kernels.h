@@ -496,6 +496,29 @@ static_assert(sizeof(PitchRow) == 40, "a turn of the pitch ring holds 256 of the
 // designs_dev: the table's designs; image_dev: the table's image, [kPitchImage][2]
 void launch_pitch(const PitchRow* rows_dev, int n, int max_tiles, const PitchScan* designs_dev, const float* image_dev, hipStream_t stream);
 
+// "Keep the formants" around the pitch's resampling step (formant.hip, formant.h has the rule, formant.cpp the host statement; DESIGN.md section 8,
+// N3), for the rows that have the option: k_formant_analyse (every frame of the row) and k_formant_whiten (every tile of 240 samples around a frame
+// boundary) in front of k_pitch_resample, which then reads the residual e and writes er; k_formant_shape (16 output tiles a wave) behind it.
+constexpr int kFormantAnalyseThreads = 256;   // four waves, a frame each
+constexpr int kFormantWhitenThreads = 256;    // 240 samples a workgroup
+constexpr int kFormantShapeTiles = 16;        // output tiles a wave: kFormantSlots lanes each
+struct FormantRow {
+    const float* x;          // the part (device), [n]
+    float* e;                // its residual, [n]: another buffer
+    const float* er;         // the resampled residual, [n_r]
+    float* out;              // the shaped row, [n_r]: another buffer than er
+    float* coeffs;           // [K][24]: a32[1 .. 24] of every frame
+    int64_t n, n_r;          // n_r = pitch_resample_length(n, p), made on the host
+    int32_t K, p;            // formant_frames(n), at least 1; pitch_permille, 800 .. 1500
+};
+static_assert(sizeof(FormantRow) == 64, "a turn of the formant ring holds 256 of them");
+// rows_dev: device copy of the n rows (every one with n > 0); max_frames: the largest K of a row; tables_dev: formant_tables() on the device
+void launch_formant_analyse(const FormantRow* rows_dev, int n, int64_t max_frames, const double* tables_dev, hipStream_t stream);
+// max_tiles: the largest (n + 119) / 240 + 1 of a row
+void launch_formant_whiten(const FormantRow* rows_dev, int n, int64_t max_tiles, hipStream_t stream);
+// max_tiles: the largest ceil(n_r / 240) of a row
+void launch_formant_shape(const FormantRow* rows_dev, int n, int64_t max_tiles, hipStream_t stream);
+
 // One SEANet residual block (+ optionally the final conv) as a single launch, resblock.hip.  u / uo: channels-last
 // [B][pad + L][C] with `pad` zero history rows per utterance; rows [t0, t1) of every utterance are produced.
 // final_conv with rows: utterance b's samples [0, lim) go straight to dst (f32, or int16 through WritePCM16Samples' arithmetic) --

@@ -118,8 +118,11 @@ enum WorkSlot : size_t {
     WORK_JOIN_CARRY = 36,        // a streamed joined call: the chain's carried states between its windows (kernels.h kCarryDoubles)
     WORK_JOIN_STAGE = 37,        // ... and its egress where that cannot store into the result's buffer itself, indexed like that buffer
     WORK_PITCH = 38,             // generate_joined with a pitch: PartRow::shifted of a group's rows, at the stride of the longest a decoded row can become
+    WORK_FORMANT_COEFFS = 39,    // parts_launch, rows that keep their formants: the frames' coefficients, [K][24] a row, one row behind the other
+    WORK_FORMANT_RESIDUAL = 40,  // ... their residuals, what k_pitch_resample reads for them
+    WORK_FORMANT_SHIFTED = 41,   // ... and their resampled residuals, what k_formant_shape reads
 };
-constexpr size_t kWorkSlots = 39;   // one past the largest value above (14 and 21-23 have no holder and stay empty DevBufs)
+constexpr size_t kWorkSlots = 42;   // one past the largest value above (14 and 21-23 have no holder and stay empty DevBufs)
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
 constexpr int kNativeRate = 24000;            // the decoder's rate: requests at 0 / 24000 in f32 or PCM16 are delivered as before, without k_resample
@@ -141,17 +144,18 @@ struct RateFilter {
     RateFilter& operator=(const RateFilter&) = delete;
     ~RateFilter();
 };
-// k_pitch_resample's prototype table (pitch.h) as the kernel reads it (kernels.h pitch_image_at): ONE per model whatever the pitches, made and
-// uploaded on first use like a RateFilter's taps (pitch_image, dsp_device.cpp)
-struct PitchImage {
-    float* staged = nullptr;      // page-locked host copy the upload reads
-    DevBuf image;                 // [kPitchImage][2]
+// A table that a model makes once and keeps on the device, made and uploaded on first use like a RateFilter's taps (upload_once, dsp_device.cpp):
+// k_pitch_resample's prototype table (pitch.h) as the kernel reads it (kernels.h pitch_image_at: [kPitchImage][2] floats, ONE per model whatever
+// the pitches) and the formant kernels' float64 tables (formant.h formant_tables)
+struct UploadedTable {
+    void* staged = nullptr;       // page-locked host copy the upload reads
+    DevBuf image;                 // the device copy
     hipEvent_t ready = nullptr;   // recorded behind the upload on `up`; a launch on another stream waits for it
     hipStream_t up = nullptr;
-    PitchImage() = default;
-    PitchImage(const PitchImage&) = delete;
-    PitchImage& operator=(const PitchImage&) = delete;
-    ~PitchImage();
+    UploadedTable() = default;
+    UploadedTable(const UploadedTable&) = delete;
+    UploadedTable& operator=(const UploadedTable&) = delete;
+    ~UploadedTable();
 };
 struct Prof {   // bench.py measurement hook (ptts_profile_*)
     bool on = false;
@@ -192,7 +196,9 @@ struct Model {
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (parts_launch, dsp_device.cpp)
     RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (parts_launch, dsp_device.cpp)
     RowRing<PitchRow, kPitchMaxDesigns * kPitchScanBytes> pitch_ring;   // k_pitch_resample's, likewise (parts_launch, dsp_device.cpp)
-    std::unique_ptr<PitchImage> pitch_image;   // ... and its table, from the first call that names a pitch on
+    std::unique_ptr<UploadedTable> pitch_image;   // ... and its table, from the first call that names a pitch on
+    RowRing<FormantRow> formant_ring;          // the formant kernels' (parts_launch, dsp_device.cpp)
+    std::unique_ptr<UploadedTable> formant_tables;   // ... and their float64 tables (formant.h formant_tables), uploaded the same way on first use
     PinnedBuf trim_info;            // parts_launch: the ptts_trim_info records of its rows with a trim, grown to their count (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
@@ -511,8 +517,8 @@ void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
 void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
 // What one part of a joined text gets in front of the join (and one row of ptts_trim_rows, ptts_tempo_rows, ptts_pitch_rows), resolved: the trim,
 // then the resampling step of the pitch (p is not 1000), then the tempo (behind a pitch it carries the effective speed E, pitch.h pitch_steps).
-// Null: the step is not run
-struct PartStages { const TrimScan* trim = nullptr; const PitchScan* pitch = nullptr; const TempoScan* tempo = nullptr; };
+// Null: the step is not run.  formant (with a pitch alone): the resampling step runs on the row's residual, between k_formant_whiten and k_formant_shape
+struct PartStages { const TrimScan* trim = nullptr; const PitchScan* pitch = nullptr; const TempoScan* tempo = nullptr; bool formant = false; };
 // One row of parts_launch.  The caller states src, n and st, and a device destination for each step the row has, sized for the bound that step's
 // own length function gives for the longest the row can be in front of it (trimmed: n; shifted: pitch_resample_length; scaled: tempo_length).
 // parts_launch states where the row's final form lies (src itself without a step), its length, and its trim record (without a trim: untouched)
@@ -523,7 +529,8 @@ struct PartRow {
 };
 // The one chain of the part stages on device rows, on s, in this order: the trim's launches (trim.hip; trim.h has the rule) for the rows with a trim,
 // their records back in one copy into page-locked memory (Model::trim_info) behind one stream wait -- the lengths decide everything behind them --
-// then k_pitch_resample (pitch.hip; pitch.h) for the rows with a pitch and the tempo's launches (tempo.hip; tempo.h) for the rows with a tempo.
+// then k_pitch_resample (pitch.hip; pitch.h) for the rows with a pitch -- for those that keep their formants (formant.hip; formant.h) on the residual,
+// between k_formant_analyse and k_formant_whiten in front and k_formant_shape behind, in work buffers made here -- and the tempo's launches (tempo.hip; tempo.h) for the rows with a tempo.
 // Each stage's scratch and row tables are made here, one launch sequence per table.  phase (optional) is called with "trim", "pitch" and "tempo"
 // behind the launches of a stage that ran; unit: what the caller's rows are called in the internal check of the records.  The caller holds Model::mu
 void parts_launch(Model& m, std::vector<PartRow>& rows, hipStream_t s, const std::function<void(const char*)>& phase = nullptr, const char* unit = "row");

@@ -126,6 +126,15 @@ class TempoOpts(C.Structure):   # ptts_tempo_opts
         super().__init__(C.sizeof(TempoOpts) if size is None else int(size), int(speed_permille), (C.c_int32 * 2)(*[int(v) for v in reserved]))
 
 
+class FormantOpts(C.Structure):   # ptts_formant_opts
+    """Keep the formants around the pitch of a joined call's parts (ptts_formant_opts): keep 1 holds the spectral envelope where it was while the
+    pitch moves (served for a pitch from 800 to 1500), keep 0 lets it move with the pitch.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("keep", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, keep: int = 1, size: Optional[int] = None, reserved=(0, 0)):
+        super().__init__(C.sizeof(FormantOpts) if size is None else int(size), int(keep), (C.c_int32 * 2)(*[int(v) for v in reserved]))
+
+
 class PitchOpts(C.Structure):   # ptts_pitch_opts
     """The pitch of a joined call's parts (ptts_pitch_opts): pitch_permille 500 .. 2000 (1000: unchanged, 1100: 10 % higher, 2000: an octave up) at
     the same duration; formants move with it.  size: sizeof as the caller compiled it (None: this mirror's)."""
@@ -235,6 +244,8 @@ ABI_SYMBOLS = [
     "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
     "ptts_pitch_speed", "ptts_pitch_resample_length", "ptts_pitch_resample", "ptts_pitch_length", "ptts_pitch_apply", "ptts_pitch_table",
     "ptts_pitch_rows", "ptts_dsp_ext_set_pitch",
+    "ptts_formant_frames", "ptts_formant_analyse", "ptts_formant_whiten", "ptts_formant_shape", "ptts_formant_apply", "ptts_formant_rows",
+    "ptts_dsp_ext_set_formant",
     ]
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
@@ -377,6 +388,15 @@ def lib():
         L.ptts_pitch_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(PitchOpts)), C.POINTER(C.POINTER(TempoOpts)), C.POINTER(_FP), _IP, C.c_int32,
                                       C.POINTER(_FP), _IP]
         L.ptts_dsp_ext_set_pitch.argtypes = [C.c_void_p, C.POINTER(PitchOpts)]
+        L.ptts_formant_frames.argtypes = [C.c_int64]
+        L.ptts_formant_frames.restype = C.c_int32
+        L.ptts_formant_analyse.argtypes = [_FP, C.c_int64, _FP]
+        L.ptts_formant_whiten.argtypes = [_FP, _FP, C.c_int64, _FP]
+        L.ptts_formant_shape.argtypes = [_FP, C.c_int64, C.c_int32, _FP, C.c_int64, _FP]
+        L.ptts_formant_apply.argtypes = [C.POINTER(FormantOpts), C.POINTER(PitchOpts), C.POINTER(TempoOpts), _FP, C.c_int64, _FP]
+        L.ptts_formant_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(FormantOpts)), C.POINTER(C.POINTER(PitchOpts)), C.POINTER(C.POINTER(TempoOpts)),
+                                        C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), _IP]
+        L.ptts_dsp_ext_set_formant.argtypes = [C.c_void_p, C.POINTER(FormantOpts)]
         L.ptts_loudness_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, _DP]
         L.ptts_loudness_normalize_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.c_double, C.POINTER(_FP), _DP]
         L.ptts_mimi_encode_rates.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_FP)]
@@ -900,6 +920,17 @@ class Model:
             # (a row whose length the library refuses is sized 1, so that the options reach the library: it names the row, and writes nothing)
             return max(_tempo_size(r, t) if p is None else int(L.ptts_pitch_length(C.byref(p), None if t is None else C.byref(t), r.size)), 1)
         single, outs, _ = self._part_rows(L.ptts_pitch_rows, x, [(pitch, PitchOpts), (tempo, TempoOpts)], size)
+        outs = [o.copy() for o in outs]
+        return outs[0] if single else outs
+
+    def formant_rows(self, x, formant, pitch, tempo=None):
+        """ptts_formant_rows: formant_apply on the device, on mono f32 rows at 24 kHz, by the kernels generate_joined runs.  formant, pitch, tempo: one
+        FormantOpts / PitchOpts / TempoOpts for every row, or one per row (a row with a formant of None is exactly pitch_rows' row).  Returns the rows."""
+        L = lib()
+
+        def size(r, f, p, t):
+            return max(_tempo_size(r, t) if p is None else int(L.ptts_pitch_length(C.byref(p), None if t is None else C.byref(t), r.size)), 1)
+        single, outs, _ = self._part_rows(L.ptts_formant_rows, x, [(formant, FormantOpts), (pitch, PitchOpts), (tempo, TempoOpts)], size)
         outs = [o.copy() for o in outs]
         return outs[0] if single else outs
 
@@ -2194,13 +2225,13 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
 class DspExt:
     """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
     (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off)
-    and their tempo (a TempoOpts; None: off) and pitch (a PitchOpts; None: off).
+    and their tempo (a TempoOpts; None: off) and pitch (a PitchOpts; None: off), with the formants kept (a FormantOpts; None: they move with the pitch).
     With none of them the handle switches nothing on.  It belongs to no
     model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
 
     def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
                  limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None, tempo: Optional["TempoOpts"] = None,
-                 pitch: Optional["PitchOpts"] = None):
+                 pitch: Optional["PitchOpts"] = None, formant: Optional["FormantOpts"] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -2221,6 +2252,8 @@ class DspExt:
             self.set_tempo(tempo)
         if pitch is not None:
             self.set_pitch(pitch)
+        if formant is not None:
+            self.set_formant(formant)
 
     def set_compressor(self, compressor: Optional[CompressorOpts]):
         """ptts_dsp_ext_set_compressor: attaches the compressor (None: off again).  Not while requests that name the handle are running."""
@@ -2244,6 +2277,11 @@ class DspExt:
         """ptts_dsp_ext_set_pitch: attaches the pitch of a joined call's parts (None: off again).  Served by Model.generate_joined, whose
         JoinOpts.dsp names the handle, between the trim and the tempo; a request's own dsp and Model.dsp_rows refuse a handle that carries one."""
         _check(lib().ptts_dsp_ext_set_pitch(self.h, None if pitch is None else C.byref(pitch)))
+
+    def set_formant(self, formant: Optional[FormantOpts]):
+        """ptts_dsp_ext_set_formant: keeps the formants around the handle's pitch (None: off again).  Served where the pitch is; without a pitch, or
+        at 1000, it switches nothing on."""
+        _check(lib().ptts_dsp_ext_set_formant(self.h, None if formant is None else C.byref(formant)))
 
     def free(self):
         if self.h:
@@ -2333,6 +2371,49 @@ def pitch_apply(pitch: PitchOpts, tempo: Optional[TempoOpts], samples) -> np.nda
     n_f = pitch_length(pitch, tempo, x.size)
     out = np.empty(max(n_f, 1), np.float32)
     _check(lib().ptts_pitch_apply(C.byref(pitch), None if tempo is None else C.byref(tempo), _fp(x), x.size, _fp(out)))
+    return out[:n_f].copy()
+
+
+def formant_frames(n: int) -> int:
+    """ptts_formant_frames: the frames K = ceil(n / 240) of a row of n samples.  Host."""
+    return _neg(int(lib().ptts_formant_frames(int(n))))
+
+
+def formant_analyse(samples) -> np.ndarray:
+    """ptts_formant_analyse: the row's coefficients a32[1 .. 24] per frame, [K, 24] f32.  Host: the statement of k_formant_analyse."""
+    x = _f32(samples).reshape(-1)
+    out = np.zeros((max(formant_frames(x.size), 1), 24), np.float32)
+    _check(lib().ptts_formant_analyse(_fp(x), x.size, _fp(out)))
+    return out[:formant_frames(x.size)].copy()
+
+
+def formant_whiten(coeffs, samples) -> np.ndarray:
+    """ptts_formant_whiten: the row's residual under the coefficients [K, 24].  Host: the statement of k_formant_whiten."""
+    x = _f32(samples).reshape(-1)
+    c = np.ascontiguousarray(coeffs, np.float32)
+    assert c.size == formant_frames(x.size) * 24
+    out = np.empty(max(x.size, 1), np.float32)
+    _check(lib().ptts_formant_whiten(_fp(c), _fp(x), x.size, _fp(out)))
+    return out[:x.size].copy()
+
+
+def formant_shape(coeffs, n: int, pitch_permille: int, residual) -> np.ndarray:
+    """ptts_formant_shape: the envelopes of the part of n samples put back on its resampled residual.  Host: the statement of k_formant_shape."""
+    e = _f32(residual).reshape(-1)
+    c = np.ascontiguousarray(coeffs, np.float32)
+    assert c.size == formant_frames(n) * 24
+    out = np.empty(max(e.size, 1), np.float32)
+    _check(lib().ptts_formant_shape(_fp(c), int(n), int(pitch_permille), _fp(e), e.size, _fp(out)))
+    return out[:e.size].copy()
+
+
+def formant_apply(formant: FormantOpts, pitch: PitchOpts, tempo: Optional[TempoOpts], samples) -> np.ndarray:
+    """ptts_formant_apply: the shifted row with its formants kept, as a new array.  Host: the statement of what Model.formant_rows and a joined call
+    with the option compute."""
+    x = _f32(samples).reshape(-1)
+    n_f = pitch_length(pitch, tempo, x.size)
+    out = np.empty(max(n_f, 1), np.float32)
+    _check(lib().ptts_formant_apply(C.byref(formant), C.byref(pitch), None if tempo is None else C.byref(tempo), _fp(x), x.size, _fp(out)))
     return out[:n_f].copy()
 
 

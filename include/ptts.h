@@ -638,7 +638,8 @@ int  ptts_dsp_ext_set_tempo(ptts_dsp_ext* e, const ptts_tempo_opts* t);
 /* The pitch of the parts of a joined text: per part, behind the trim and in front of the tempo.  The order of a joined
  * call: trim per part -> pitch resample per part -> tempo at the effective speed per part -> join -> the chain of `dsp` and `loudness` once ->
  * egress.  A pitch change at constant duration is a resampling by the pitch ratio and a tempo change that takes the length back.  FORMANTS MOVE
- * WITH THE PITCH: every frequency of the part is scaled, so a large shift changes the voice's character, not only its height.
+ * WITH THE PITCH: every frequency of the part is scaled, so a large shift changes the voice's character, not only its height -- unless the
+ * handle also carries the option of ptts_formant_opts, below, which keeps them in place.
  *
  * On a part x[0, n) at 24 kHz with p = pitch_permille (500 .. 2000; 1000: unchanged, 1100: 10 % higher, SSML's "+10%"; 2000: an octave up) and
  * s the tempo's speed_permille (1000 when there is no tempo) the stage is two steps.  Every index is an integer.
@@ -697,6 +698,69 @@ int  ptts_pitch_table(const float** h, const float** hd, int32_t* entries);
 int  ptts_pitch_rows(ptts_model* m, const ptts_pitch_opts* const* p /* [rows] */, const ptts_tempo_opts* const* t /* [rows] */,
                      const float* const* in, const int64_t* n, int32_t rows, float* const* out, int64_t* n_out /* [rows] */);
 int  ptts_dsp_ext_set_pitch(ptts_dsp_ext* e, const ptts_pitch_opts* p);
+
+/* Keep the formants: the pitch of a part without its vocal-tract resonances moving with it.  The part's spectral
+ * envelope is estimated by linear prediction, the part is flattened (whitened) with it, only the flat residual goes through the pitch's resampler,
+ * and the original envelope is put back on the resampled residual; the tempo follows as it does without the option.  The order of a joined call
+ * with it: trim per part -> [whiten -> the pitch's resample of the residual -> shape] -> tempo at the effective speed E -> join -> chain ->
+ * egress.  The bracket replaces the bare resample; every length stays: ptts_pitch_resample_length, ptts_pitch_speed and ptts_pitch_length hold.
+ *
+ * Constants: hop 240, window 720, order 24, warm-up 720 samples; bandwidth expansion 0.99; lag window 60 Hz; white-noise factor 1.0001.  On a
+ * part x[0, n) at 24 kHz with the pitch p; samples outside a row read as 0.0f:
+ *   - frames: K = ceil(n / 240); frame f looks at x[240 f - 240 + j], j in [0, 720): its centre is 240 f + 120.
+ *   - analysis, float64, per frame: v[j] = (double)x * w[j], w[j] = 0.5 - 0.5 cos(2 pi (j + 0.5) / 720).  r[l], l = 0 .. 24, is one fma chain from
+ *     0.0 over ascending j = l .. 719 of v[j] * v[j - l].  r[0] not finite or not > 0: the frame is the identity (a[1 .. 24] = 0).  Otherwise
+ *     r[l] *= exp(-0.5 (2 pi 60 l / 24000)^2) and r[0] *= 1.0001.  Levinson-Durbin, stage i = 1 .. 24, E = r[0] at the start: acc = r[i], then over
+ *     ascending j = 1 .. i - 1 acc = fma(a[j], r[i - j], acc); k = -acc / E; the new a[j] = a[j] + k * a[i - j] for j below i (a product, then a
+ *     sum) and a[i] = k; E = E * (1 - k * k), nothing contracted.  A k that is not finite or has |k| >= 1, or an E that is not > 0, makes the frame
+ *     the identity.  a32[k] = (float)(a[k] * 0.99^k).  The three tables (w, the lag window, 0.99^k) are made once in float64.  K x 24 floats a part.
+ *   - the pair of a source time tau: b = tau - 120, f0 = floor(b / 240), rho = b - 240 f0, fa = clamp(f0, 0, K - 1), fb = clamp(f0 + 1, 0, K - 1),
+ *     u = (float)rho / 240.0f (one IEEE f32 division); mix(A, B) = A * (1.0f - u) + B * u: one difference, two products, one sum, each rounded
+ *     once, nothing fused.
+ *   - whiten: E_f[i] is one f32 chain: acc = x[i], then for k = 1 .. 24 ascending acc = fmaf(a32_f[k], x[i - k], acc); e[i] = mix(E_fa[i], E_fb[i])
+ *     with tau = i, for i in [0, n).
+ *   - resample: e' = ptts_pitch_resample of e at p, unchanged: n_r samples.
+ *   - shape: output j lies in tile t = j / 240, which starts its recursions at m0 = 240 t - 720.  For a frame f, Y[m] for m >= m0 is one f32 chain:
+ *     acc = e'[m] (0.0f outside [0, n_r)), then for k = 1 .. 24 ascending acc = fmaf(-a32_f[k], Y[m - k], acc), with Y[m] = 0 for m < m0.
+ *     out[j] = mix(Y_fa[j], Y_fb[j]) with tau = (j * p) / 1000 in int64.  A tile needs at most four frames (p = 1500).
+ *   - tempo: the tempo's statement at E on out, unchanged.
+ * The recursive filter is bounded on purpose: every tile of 240 outputs restarts from zero state 720 samples earlier, so tiles are independent.
+ * The host and the device run the same chains in the same order and give the same bits (outside NaNs, whose bits are the processor's).
+ *   - A NaN at sample i makes identity frames of the three frames whose windows hold it.  It reaches the residual samples i .. i + 24, and outputs
+ *     no further than 720 + 240 samples plus the resampler's support behind its image; nothing else of the row is touched.
+ *   - Peaks may grow: there is no gain control here; the chain's limiter and ceiling follow.
+ *   - Below p = 1000 the residual is band-limited to p / 1000 of the band, as the plain pitch is.
+ * The option is served for p from 800 to 1500; outside it is PTTS_EINVAL, and the error names both fields and both values (at p = 667 a float64
+ * prototype of this statement no longer kept the envelope nearer to its place than it moved).  p == 1000, or no pitch at all, means nothing is
+ * computed and the part comes back as without the option.
+ * ptts_formant_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_formant_frames: K for a row of n samples, or -PTTS_EINVAL.  Host.
+ * ptts_formant_analyse: the K x 24 coefficients a32[1 .. 24] of x[0, n).  Host: the statement of k_formant_analyse.
+ * ptts_formant_whiten: e[0, n) from the coefficients and x; e is not x.  Host: the statement of k_formant_whiten.
+ * ptts_formant_shape: out[0, n_r) from the coefficients of the part of n samples, p and the resampled residual e_r[0, n_r); out is not e_r.  Host:
+ *     the statement of k_formant_shape.
+ * ptts_formant_apply: the whole stage into out, which holds ptts_pitch_length(p, t, n) floats and is not in.  keep == 0 or p == 1000: exactly
+ *     ptts_pitch_apply.  Host: the statement of the result.
+ * ptts_formant_rows: the whole stage on rows of host samples on the device, shaped like ptts_pitch_rows.  f[i] NULL (or keep 0): row i exactly
+ *     as ptts_pitch_rows.  The arrays f, p, t and n_out ([rows]) are required; a bad row is named.
+ * ptts_dsp_ext_set_formant attaches the option to a live handle of ptts_dsp_ext_create (f NULL: off again); a handle that is not live is
+ *     PTTS_EINVAL and is not read.  It is served where the pitch is: ptts_generate_joined and ptts_generate_joined_streamed resolve the pair
+ *     (option, pitch) before anything launches.  Without the option nothing of this is allocated, uploaded or launched. */
+typedef struct ptts_formant_opts {
+    uint32_t size;             /* sizeof(ptts_formant_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  keep;             /* 0: formants move with the pitch; 1: they stay */
+    int32_t  reserved[2];      /* 0 */
+} ptts_formant_opts;
+int32_t ptts_formant_frames(int64_t n);
+int  ptts_formant_analyse(const float* x, int64_t n, float* coeffs /* [K][24] */);
+int  ptts_formant_whiten(const float* coeffs, const float* x, int64_t n, float* e);
+int  ptts_formant_shape(const float* coeffs, int64_t n, int32_t pitch_permille, const float* e_r, int64_t n_r, float* out);
+int  ptts_formant_apply(const ptts_formant_opts* f, const ptts_pitch_opts* p, const ptts_tempo_opts* t, const float* in, int64_t n, float* out);
+int  ptts_formant_rows(ptts_model* m, const ptts_formant_opts* const* f /* [rows] */, const ptts_pitch_opts* const* p /* [rows] */,
+                       const ptts_tempo_opts* const* t /* [rows] */, const float* const* in, const int64_t* n, int32_t rows, float* const* out,
+                       int64_t* n_out /* [rows] */);
+int  ptts_dsp_ext_set_formant(ptts_dsp_ext* e, const ptts_formant_opts* f);
 
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
@@ -955,7 +1019,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_dsp_ext_set_trim; the new struct ptts_tempo_opts, likewise, with ptts_tempo_length, ptts_tempo_plan, ptts_tempo_apply, ptts_tempo_rows,
  * ptts_dsp_ext_set_tempo; the new struct ptts_join_stream_opts, likewise, with ptts_generate_joined_streamed, ptts_join_stream_ready;
  * the new struct ptts_pitch_opts, likewise, with ptts_pitch_speed, ptts_pitch_resample_length, ptts_pitch_resample, ptts_pitch_length,
- * ptts_pitch_apply, ptts_pitch_table, ptts_pitch_rows, ptts_dsp_ext_set_pitch */
+ * ptts_pitch_apply, ptts_pitch_table, ptts_pitch_rows, ptts_dsp_ext_set_pitch;
+ * the new struct ptts_formant_opts, likewise, with ptts_formant_frames, ptts_formant_analyse, ptts_formant_whiten, ptts_formant_shape,
+ * ptts_formant_apply, ptts_formant_rows, ptts_dsp_ext_set_formant */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
