@@ -70,7 +70,7 @@ int ptts_dsp_rows(ptts_model* h, const float* const* in, const int64_t* n, int32
     });
 }
 
-// The host-rows entry points with one stage and one option per row (ptts_eq_rows, ptts_compress_rows, ptts_limit_rows): the argument checks
+// The host-rows entry points with one stage and one option per row (ptts_eq_rows, ptts_compress_rows, ptts_deess_rows, ptts_limit_rows): the argument checks
 // under the stage's name, each row's spec from per_row(i, spec) -- which returns the row's refusal, or nothing -- and the round trip.  A row
 // whose spec stays empty is copied on the host
 static int stage_rows(ptts_model* h, const char* what, bool opts_null, const float* const* in, const int64_t* n, int32_t rows, float* const* out,
@@ -105,6 +105,18 @@ int ptts_compress_rows(ptts_model* h, const ptts_compressor_opts* const* c, cons
         if (!e.empty()) return strfmt("row %d: ", i) + e;
         spec.compress = true;
         spec.cmp = cmp_design(*c[i]);
+        return std::string();
+    });
+}
+
+// the device form of ptts_deess_apply on host rows: the launches of a request's de-esser; a row without one is copied on the host
+int ptts_deess_rows(ptts_model* h, const ptts_deesser_opts* const* d, const float* const* in, const int64_t* n, int32_t rows, float* const* out) {
+    return stage_rows(h, "deesser", !d, in, n, rows, out, [&](int i, DspSpec& spec) {
+        if (!d[i]) return std::string();
+        const std::string e = de_opts_error(d[i]);
+        if (!e.empty()) return strfmt("row %d: ", i) + e;
+        spec.deess = true;
+        spec.des = de_design(*d[i]);
         return std::string();
     });
 }

@@ -94,25 +94,39 @@ PTTS_HD inline double cmp_exp2(double v) {
     return q * cmp_double((uint64_t)(k + 1023) << 52);
 }
 
-// the linear gain at level s (s >= 0 or +inf, never a NaN): the static curve and the makeup gain
-PTTS_HD inline double cmp_gain(const CmpScan& d, double s) {
+// the static curve in dB at a level s above the knee's lower edge (s > s_lo, +inf included, never a NaN), without the makeup gain (deesser.h
+// holds it against its floor)
+PTTS_HD inline double cmp_curve_db(const CmpScan& d, double s) {
 #pragma clang fp contract(off)
-    if (!(s > d.s_lo)) return d.g_lo;
     const double over = kCmpDbPerLog2 * cmp_log2(s) - d.thr_db, two = 2.0 * over;
     double g_db;
     if (two > d.knee_db) g_db = d.slope * over;
     else if (two < -d.knee_db) g_db = 0.0;
     else { const double h = over + 0.5 * d.knee_db; g_db = d.knee_q * (h * h); }
-    return cmp_exp2((g_db + d.makeup_db) * kCmpLog2PerDb);
+    return g_db;
+}
+// the linear gain at level s (s >= 0 or +inf, never a NaN): the static curve and the makeup gain
+PTTS_HD inline double cmp_gain(const CmpScan& d, double s) {
+#pragma clang fp contract(off)
+    if (!(s > d.s_lo)) return d.g_lo;
+    return cmp_exp2((cmp_curve_db(d, s) + d.makeup_db) * kCmpLog2PerDb);
+}
+
+// one sample of each recurrence: the detector from p at the level a = |x| (a NaN never wins), the smoothing from s at the detector's new state
+PTTS_HD inline double cmp_step_p(const CmpScan& d, double a, double p) {
+#pragma clang fp contract(off)
+    const double r = d.rho * p;
+    return (a > r) ? a : r;
+}
+PTTS_HD inline double cmp_step_s(const CmpScan& d, double p, double s) {
+#pragma clang fp contract(off)
+    return d.alpha * s + d.beta * p;
 }
 
 // the detector over `count` samples from state p: the state behind them
 PTTS_HD inline double cmp_run_p(const CmpScan& d, const float* x, int count, double p) {
 #pragma clang fp contract(off)
-    for (int i = 0; i < count; i++) {
-        const double a = __builtin_fabs((double)x[i]), r = d.rho * p;
-        p = (a > r) ? a : r;
-    }
+    for (int i = 0; i < count; i++) p = cmp_step_p(d, __builtin_fabs((double)x[i]), p);
     return p;
 }
 // t_(l+1) = max(pw t_l, e_l), S_(f+1) = max(pw S_f, E_f): e is never a NaN
@@ -125,9 +139,8 @@ PTTS_HD inline double cmp_fold_p(double pw, double t, double e) {
 PTTS_HD inline double cmp_run_s(const CmpScan& d, const float* x, int count, double p, double s) {
 #pragma clang fp contract(off)
     for (int i = 0; i < count; i++) {
-        const double a = __builtin_fabs((double)x[i]), r = d.rho * p;
-        p = (a > r) ? a : r;
-        s = d.alpha * s + d.beta * p;
+        p = cmp_step_p(d, __builtin_fabs((double)x[i]), p);
+        s = cmp_step_s(d, p, s);
     }
     return s;
 }
@@ -136,9 +149,8 @@ PTTS_HD inline void cmp_run_y(const CmpScan& d, const float* x, int count, doubl
 #pragma clang fp contract(off)
     for (int i = 0; i < count; i++) {
         const double xi = (double)x[i];
-        const double a = __builtin_fabs(xi), r = d.rho * p;
-        p = (a > r) ? a : r;
-        s = d.alpha * s + d.beta * p;
+        p = cmp_step_p(d, __builtin_fabs(xi), p);
+        s = cmp_step_s(d, p, s);
         y[i] = (float)(xi * cmp_gain(d, s));
     }
 }

@@ -23,18 +23,6 @@ namespace ptts {
 
 namespace {
 
-// the smoothing's fold over a tile's runs from state S, as dsp_tile.h's fold_enter_max is the detector's: scan_advance<1>, t <- alpha^30 t + e_l
-__device__ __forceinline__ double cmp_enter_s(const CmpScan& d, const double* e, double S, double* behind) {
-    const int l = threadIdx.x;
-    double t[1] = {S}, mine = S;
-    for (int j = 0; j < kDspLanes; j++) {
-        if (j == l) mine = t[0];
-        scan_advance<1>(&d.alpha_run, t, e + j);
-    }
-    *behind = t[0];
-    return mine;
-}
-
 __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_p(const CmpRow* __restrict__ rows, const CmpScan* __restrict__ designs) {
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes];
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_summary_s(const CmpRow* __res
     e[l] = cmp_run_s(d, run, kDspRun, tp, 0.0);
     __syncthreads();
     double E;
-    cmp_enter_s(d, e, 0.0, &E);
+    fold_enter_sum(d.alpha_run, e, 0.0, &E);
     if (l == 0) scan_E<1>(r.s_tiles, blockIdx.x)[0] = E;
 }
 
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(kDspLanes) void k_cmp_apply(const CmpRow* __restric
     __syncthreads();
     e[l] = cmp_run_s(d, run, c, tp, 0.0);
     __syncthreads();
-    const double ts = cmp_enter_s(d, e, scan_S<1>(r.s_tiles, blockIdx.x)[0], &behind);
+    const double ts = fold_enter_sum(d.alpha_run, e, scan_S<1>(r.s_tiles, blockIdx.x)[0], &behind);
     cmp_run_y(d, run, c, tp, ts, run);
     __syncthreads();
     tile_store(r.x + base, cnt, tile);

@@ -1,4 +1,4 @@
-// dsp_device.cpp -- the host side of the device post-processing (dsp.hip, compressor.hip, limiter.hip, true_peak.hip):
+// dsp_device.cpp -- the host side of the device post-processing (dsp.hip, compressor.hip, deesser.hip, limiter.hip, true_peak.hip):
 // the order of the chain's stages, their row tables (cut by row_tables.h's rule) and scratch (planned by dsp_spec.h's dsp_scratch), their
 // launches, and the round trip of host rows through them.  The coefficients come from dsp.cpp (dsp_scan_coeffs), made as dsp_dc_block makes
 // them; what a row gets is resolved in dsp_spec.cpp.  At the end: the tables of k_join (join.hip) and the round trip of ptts_join_rows, then the part
@@ -49,12 +49,12 @@ void launch_tables(RowRing<Row, kTail>& ring, std::vector<Row>& rows, const std:
 }
 
 template <class Design>
-bool same_bytes(const Design& a, const Design& b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // a design by value: compressors, limiters
+bool same_bytes(const Design& a, const Design& b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // a design by value: compressors, de-essers, limiters
 }  // namespace
 
-// The chain's order, all of it: the compressor's tables in front of everything that measures or rewrites a row; then, DSP table by DSP table,
+// The chain's order, all of it: the compressor's tables, then the de-esser's, in front of everything that measures or rewrites a row; then, DSP table by DSP table,
 // launch_dsp's kernels, the limiter's tables for that table's limiter rows (behind the fades, in front of the ceiling) and the true-peak pair
-// on what all of them stored.  A measurement alone (apply false) rewrites nothing: no compressor, no equaliser, no limiter, k_tp_peak alone.
+// on what all of them stored.  A measurement alone (apply false) rewrites nothing: no compressor, no de-esser, no equaliser, no limiter, k_tp_peak alone.
 // A job with a window (DspJob::t0, open, carry; kernels.h has what a window is) takes the same way: its scratch is planned for the window's
 // samples, its fade in counts in the whole row and its fade out waits for the window that closes the row.
 void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) {
@@ -70,6 +70,8 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
     PTTS_HIP(hipMemsetAsync(peaks, 0, peak_bytes, s));
     std::vector<CmpRow> cmp_rows;
     std::vector<const CmpScan*> cmp_key;
+    std::vector<DeRow> de_rows;
+    std::vector<const DeScan*> de_key;
     std::vector<DspRow> rows;
     std::vector<const EqScan*> eq_key;       // per DSP row: its equaliser, where it is applied
     std::vector<const LimScan*> lim_key;     // per DSP row: its limiter, where it is applied
@@ -94,7 +96,18 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
             cmp_rows.push_back(r);
             cmp_key.push_back(&sp.cmp);
         }
-        if (!sp.rest()) continue;   // (a compressor alone: no row of the DSP table)
+        if (q.de) {
+            if (j.t0 || j.open || j.carry) throw Error(PTTS_EINVAL, "ptts-hip: internal: the de-esser is not served window after window (dsp_window_refusal)");
+            const int64_t F = scan_tiles(wn);
+            DeRow r{};
+            r.x = j.x; r.n = j.n;
+            r.b_tiles = mine + q.de_at();
+            r.p_tiles = r.b_tiles + scan_state_doubles<2>(F);
+            r.s_tiles = r.p_tiles + scan_state_doubles<1>(F);
+            de_rows.push_back(r);
+            de_key.push_back(&sp.des);
+        }
+        if (!sp.rest()) continue;   // (a compressor or a de-esser alone: no row of the DSP table)
         DspRow r{};
         r.x = j.x; r.n = j.n;
         r.fade_in = fade_samples(sp.fade_in_ms, j.open ? j.n_row : j.n);   // (an open row: the length it will have, or one beyond every fade)
@@ -127,6 +140,8 @@ void dsp_launch(Model& m, std::vector<DspJob>& jobs, hipStream_t s, bool apply) 
         for (size_t i = first; i < first + (size_t)n; i++) any_open = any_open || cmp_rows[i].open;
         launch_compressor(rows_dev, n, max_tiles, designs_dev, s, any_open);
     });
+    launch_tables(m.de_ring, de_rows, de_key, kDeMaxDesigns, same_bytes<DeScan>, &DeRow::design, "deesser", s,
+                  [&](size_t, int n, const DeRow* rows_dev, int max_tiles, const DeScan* designs_dev) { launch_deesser(rows_dev, n, max_tiles, designs_dev, s); });
     std::vector<LimRow> lim_rows;
     std::vector<const LimScan*> lim_rows_key;
     launch_tables(m.dsp_ring, rows, eq_key, kDspMaxEq, [](const EqScan& a, const EqScan& b) { return &a == &b; } /* a handle's identity */, &DspRow::eq, "dsp", s,

@@ -19,6 +19,8 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
     out->ceiling = ext.ceiling;
     out->compress = ext.compress;
     out->cmp = ext.cmp;
+    out->deess = ext.deess;
+    out->des = ext.des;
     out->limit = ext.limit;
     out->lim = ext.lim;
     out->trim = ext.trim;
@@ -33,7 +35,7 @@ std::string dsp_resolve(const ptts_dsp_opts* o, DspSpec* out) {
 
 bool dsp_active(const ptts_dsp_opts* o) {
     DspExt ext;
-    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && (ext.true_peak || ext.compress || ext.limit)));
+    return o && (o->normalize || o->dc_block || o->fade_in_ms > 0 || o->fade_out_ms > 0 || o->eq || (o->ext && ext_lookup(o->ext, &ext) && (ext.true_peak || ext.compress || ext.deess || ext.limit)));
 }
 
 }  // namespace ptts

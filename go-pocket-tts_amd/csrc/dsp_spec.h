@@ -13,13 +13,14 @@ struct DspSpec {
     bool true_peak = false; float ceiling = 1.0f;      // measured and held at or under `ceiling` (linear)
     bool loud = false; double target_power = 0.0;      // measured (BS.1770) on the samples as the compressor leaves them; 10^((target LUFS + 0.691) / 10) is what its gain aims at
     bool compress = false; CmpScan cmp{};              // the first stage (compressor.h): everything above is measured and applied behind it
+    bool deess = false; DeScan des{};                  // the de-esser (deesser.h): directly behind the compressor; "behind it" above means behind the pair
     bool limit = false; LimScan lim{};                 // the limiter (limiter.h): behind the fades, in front of the true-peak ceiling
     bool trim = false; TrimScan trm{};                 // the trim of a joined call's parts (trim.h): no stage of the chain, neither rest() nor any() counts it
     bool tempo = false; TempoScan tmp{};               // the tempo of a joined call's parts (tempo.h), behind the trim: no stage of the chain either
     bool pitch = false; PitchScan pit{};               // the pitch of a joined call's parts (pitch.h), between the trim and the tempo: no stage of the chain either
     bool formant = false;                              // keep the formants around that pitch (formant.h): set with keep == 1 alone; without a pitch it says nothing
-    bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor
-    bool any() const { return compress || rest(); }
+    bool rest() const { return normalize || dc_block || fade_in_ms > 0 || fade_out_ms > 0 || eq || true_peak || loud || limit; }   // the chain behind the compressor and the de-esser
+    bool any() const { return compress || deess || rest(); }
 };
 
 // The scratch plan: the doubles of WORK_DSP_SCRATCH each stage of a row of n samples needs (dsp_device.cpp sizes the buffer by total() and carves
@@ -30,13 +31,15 @@ struct DspScratch {
     size_t loud = 0;   // the loudness block: M, the gain, the K-weighting's per-tile states, the sub-block energies (scan_block.h loud_doubles)
     size_t eq = 0;     // the equaliser's per-tile states, 2 S doubles each for E_f and S_f
     size_t lim = 0;    // the limiter's per-tile states, then its gains, one f32 a sample (limiter.h lim_scratch_doubles)
-    size_t total() const { return cmp + dc + loud + eq + lim; }
+    size_t de = 0;     // the de-esser's per-tile states: the side chain's, the detector's, the smoothing's (deesser.h de_state_doubles)
+    size_t total() const { return cmp + dc + loud + eq + lim + de; }
     // where each region starts within the row's total(): one behind the other, in the order above
     size_t cmp_at() const { return 0; }
     size_t dc_at() const { return cmp; }
     size_t loud_at() const { return dc_at() + dc; }
     size_t eq_at() const { return loud_at() + loud; }
     size_t lim_at() const { return eq_at() + eq; }
+    size_t de_at() const { return lim_at() + lim; }
 };
 inline DspScratch dsp_scratch(const DspSpec& sp, int64_t n, bool apply) {
     DspScratch q;
@@ -47,6 +50,7 @@ inline DspScratch dsp_scratch(const DspSpec& sp, int64_t n, bool apply) {
     if (sp.loud) q.loud = loud_doubles(F);
     if (sp.eq && apply) q.eq = (size_t)F * 4 * (size_t)sp.eq->S;
     if (sp.limit && apply) q.lim = lim_scratch_doubles(n);
+    if (sp.deess && apply) q.de = de_state_doubles(F);
     return q;
 }
 
@@ -63,11 +67,13 @@ inline std::string dsp_tempo_refusal(const DspSpec& s) {
     return s.tempo ? std::string("dsp: ext: tempo changes a row's length; it is served by ptts_generate_joined and ptts_tempo_rows") : std::string();
 }
 // Where a row is handed over window after window (a joined call with a pcm_callback, ptts_debug_dsp_windows) only the causal stages run: the
-// compressor, the DC block, the equaliser and the fades.  The message naming the first stage of s that is none, or empty
+// compressor, the DC block, the equaliser and the fades.  The message naming the first stage of s that is none, or empty.  The de-esser is causal
+// too, but its states are not carried from window to window yet: it is refused last, in words of its own
 inline std::string dsp_window_refusal(const DspSpec& s) {
     const char* f = s.normalize ? "normalize" : s.loud ? "loudness" : s.true_peak ? "ext: true_peak" : nullptr;
     if (f) return strfmt("stream: %s needs the whole text; it cannot be combined with pcm_callback", f);
-    return s.limit ? std::string("stream: ext: limiter looks ahead of the samples it hands over; it cannot be combined with pcm_callback yet") : std::string();
+    if (s.limit) return std::string("stream: ext: limiter looks ahead of the samples it hands over; it cannot be combined with pcm_callback yet");
+    return s.deess ? std::string("stream: ext: deesser is not carried from window to window yet; it cannot be combined with pcm_callback yet") : std::string();
 }
 // ... and one with a pitch, likewise
 inline std::string dsp_pitch_refusal(const DspSpec& s) {

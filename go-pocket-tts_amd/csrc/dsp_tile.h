@@ -1,4 +1,4 @@
-// dsp_tile.h -- what the post-processing kernels share on the device (dsp.hip, compressor.hip, limiter.hip; scan_block.h has the grid and the
+// dsp_tile.h -- what the post-processing kernels share on the device (dsp.hip, compressor.hip, deesser.hip, limiter.hip; scan_block.h has the grid and the
 // host-and-device arithmetic): one wave per workgroup, workgroup blockIdx.x on tile blockIdx.x of its row, lane l on
 // run l of the tile.  Device code only.
 #pragma once
@@ -44,6 +44,19 @@ __device__ __forceinline__ double fold_enter_max(double rho_run, const double* e
         t = cmp_fold_p(rho_run, t, e[j]);
     }
     *behind = t;
+    return mine;
+}
+
+// The linear fold with one state (scan_advance<1>, t <- alpha^30 t + e_l) over a tile's runs from state S, shaped like fold_enter_max: the
+// attack smoothing's, in compressor.hip and deesser.hip
+__device__ __forceinline__ double fold_enter_sum(double alpha_run, const double* e, double S, double* behind) {
+    const int l = threadIdx.x;
+    double t[1] = {S}, mine = S;
+    for (int j = 0; j < kDspLanes; j++) {
+        if (j == l) mine = t[0];
+        scan_advance<1>(&alpha_run, t, e + j);
+    }
+    *behind = t[0];
     return mine;
 }
 

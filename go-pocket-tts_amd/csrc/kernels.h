@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "deesser.h"
 #include "limiter.h"
 #include "pitch.h"
 #include "tempo.h"
@@ -386,6 +387,28 @@ struct CmpRow {
 static_assert(sizeof(CmpRow) == 56, "a turn of the compressor ring holds 256 of them");
 // rows_dev: device copy of the n rows; max_tiles: the most tiles a row's window has; designs_dev: the table's designs; any_open: a row is open
 void launch_compressor(const CmpRow* rows_dev, int n, int max_tiles, const CmpScan* designs_dev, hipStream_t stream, bool any_open = false);
+
+// A request's de-esser (deesser.hip, deesser.h): directly behind the compressor's tables and in front of launch_dsp's,
+// on a table of its own.  A scan of three levels, each needing the one in front at every tile's start: k_de_summary_b + k_de_carry_b (the side
+// chain's two biquad states entering each tile: the equaliser's linear scan for one section), k_de_summary_p + k_de_carry_p (the detector's, the
+// compressor's (max, times) scan on the band, which every tile makes again from the section's entering state), k_de_summary_s + k_de_carry_s
+// (the smoothing's, likewise) and k_de_apply (all three again, the curve held at the floor, the band's gain, one store), in place.  The band is
+// never stored beside the row.  A table's distinct designs (at most kDeMaxDesigns) travel behind its rows; a row names its own by index.  No
+// windows: the stage is refused where a row is handed over window after window (dsp_spec.h dsp_window_refusal).
+constexpr int kDeMaxDesigns = 16;
+constexpr size_t kDeScanBytes = 256;
+static_assert(sizeof(DeScan) == kDeScanBytes, "the de-esser ring's tail (runtime.h) is sized by it");
+struct DeRow {
+    float* x;              // the row's samples (device), rewritten in place
+    int64_t n;             // samples; nothing at or beyond n is touched
+    double* b_tiles;       // the section's per-tile states, [ceil(n / kDspTile)][4]: E_f, S_f, two each (scan_block.h scan_E<2> / scan_S<2>)
+    double* p_tiles;       // the detector's, [ceil(n / kDspTile)][2] (scan_E<1> / scan_S<1>)
+    double* s_tiles;       // the smoothing's, likewise
+    int32_t design, pad;   // the index of the row's design among the table's
+};
+static_assert(sizeof(DeRow) == 48, "a turn of the de-esser ring holds 256 of them");
+// rows_dev: device copy of the n rows; max_tiles: the largest ceil(n / kDspTile) of a row; designs_dev: the table's designs
+void launch_deesser(const DeRow* rows_dev, int n, int max_tiles, const DeScan* designs_dev, hipStream_t stream);
 
 // A request's look-ahead peak limiter (limiter.hip, limiter.h): behind the fades and in front of the true-peak
 // ceiling, on a table of its own behind the DSP table's last kernel and in front of k_tp_peak.  k_lim_summary + k_lim_carry (the release's state

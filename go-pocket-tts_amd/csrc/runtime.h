@@ -192,6 +192,7 @@ struct Model {
     RowRing<ResampleRow> rs_ring;   // k_resample's row tables (resample.cpp)
     RowRing<CmpRow, kCmpMaxDesigns * kCmpScanBytes> cmp_ring;   // the compressor kernels', a table's designs behind its rows (dsp_device.cpp)
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
+    RowRing<DeRow, kDeMaxDesigns * kDeScanBytes> de_ring;       // the de-esser kernels', likewise
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, dsp_device.cpp)
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (parts_launch, dsp_device.cpp)
     RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (parts_launch, dsp_device.cpp)

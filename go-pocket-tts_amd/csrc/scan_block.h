@@ -135,6 +135,7 @@ struct EqSys {
     const DspBiquad* c;
     const double *a_run, *a_tile;
     PTTS_HD explicit EqSys(const EqScan& e) : c(e.c), a_run(e.a_run), a_tile(e.a_tile) {}
+    PTTS_HD EqSys(const DspBiquad* c_, const double* a_run_, const double* a_tile_) : c(c_), a_run(a_run_), a_tile(a_tile_) {}   // (deesser.h: a design that holds one section)
     PTTS_HD void run(const float* x, int count, double* z, float* y = nullptr) const {
 #pragma clang fp contract(off)
         double w[N];

@@ -100,6 +100,19 @@ class LimiterOpts(C.Structure):   # ptts_limiter_opts
                          float(release_ms), float(drive_db))
 
 
+class DeesserOpts(C.Structure):   # ptts_deesser_opts
+    """A de-esser's options (ptts_deesser_opts): freq_hz 2000 .. 10000 and q 0.3 .. 4 of the side chain's high-pass, then the compressor's detector on
+    that band -- threshold_db -60 .. 0, ratio 1 .. 100, knee_db 0 .. 24, attack_ms 0.05 .. 200, release_ms 5 .. 5000 -- and max_reduction_db 0 .. 40,
+    the most the band is turned down by.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32), ("freq_hz", C.c_double), ("q", C.c_double), ("threshold_db", C.c_double),
+                ("ratio", C.c_double), ("knee_db", C.c_double), ("attack_ms", C.c_double), ("release_ms", C.c_double), ("max_reduction_db", C.c_double)]
+
+    def __init__(self, freq_hz: float = 5000.0, q: float = 0.7071, threshold_db: float = -30.0, ratio: float = 4.0, knee_db: float = 6.0,
+                 attack_ms: float = 1.0, release_ms: float = 60.0, max_reduction_db: float = 12.0, size: Optional[int] = None, reserved: int = 0):
+        super().__init__(C.sizeof(DeesserOpts) if size is None else int(size), int(reserved), float(freq_hz), float(q), float(threshold_db),
+                         float(ratio), float(knee_db), float(attack_ms), float(release_ms), float(max_reduction_db))
+
+
 class TrimOpts(C.Structure):   # ptts_trim_opts
     """Silence control of a joined call's parts (ptts_trim_opts): edges 0 / 1 (cut the silent head and tail), threshold_db -120 .. 0 (a sample is
     loud when |x| > 10^(threshold_db / 20)), pad_ms 0 .. 500 (kept around the first and last loud sample), max_pause_ms 0 (pauses untouched) or
@@ -239,6 +252,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_create", "ptts_dsp_ext_free", "ptts_true_peak", "ptts_true_peak_limit", "ptts_true_peak_rows",
     "ptts_dsp_ext_set_compressor", "ptts_compress_gain", "ptts_compress_apply", "ptts_compress_rows",
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
+    "ptts_dsp_ext_set_deesser", "ptts_deess_apply", "ptts_deess_band", "ptts_deess_rows",
     "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined", "ptts_generate_joined_streamed", "ptts_join_stream_ready",
     "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
     "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
@@ -357,6 +371,10 @@ def lib():
         L.ptts_dsp_ext_set_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterOpts)]
         L.ptts_limit_apply.argtypes = [C.POINTER(LimiterOpts), _FP, C.c_int64]
         L.ptts_limit_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(LimiterOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
+        L.ptts_dsp_ext_set_deesser.argtypes = [C.c_void_p, C.POINTER(DeesserOpts)]
+        L.ptts_deess_apply.argtypes = [C.POINTER(DeesserOpts), _FP, C.c_int64]
+        L.ptts_deess_band.argtypes = [C.POINTER(DeesserOpts), _FP, C.c_int64, _FP]
+        L.ptts_deess_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DeesserOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP)]
         L.ptts_join_length.restype = C.c_int64
         L.ptts_join_length.argtypes = [_IP, C.c_int32, C.POINTER(JoinOpts), _IP]
         L.ptts_join.argtypes = [C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), _FP]
@@ -564,6 +582,9 @@ class RuntimeGenerateConfig:
     # a look-ahead peak limiter (ptts_dsp_opts.ext, ptts_dsp_ext_set_limiter; None: off): behind the fades and in front of the true-peak ceiling,
     # limit_apply of what the stages above made of this request's 24 kHz audio
     limiter: Optional[LimiterOpts] = None
+    # a de-esser (ptts_dsp_opts.ext, ptts_dsp_ext_set_deesser; None: off): directly behind the compressor and in front of everything else,
+    # deess_apply of what the compressor made of this request's 24 kHz audio
+    deesser: Optional[DeesserOpts] = None
 
 
 def _free_addr(addr: int):
@@ -882,6 +903,11 @@ class Model:
         """ptts_limit_rows: limit_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
         limiter: one LimiterOpts for every row, or one per row (None copies that row)."""
         return self._stage_rows(lib().ptts_limit_rows, x, limiter, C.POINTER(LimiterOpts), C.pointer)
+
+    def deess_rows(self, x, deesser):
+        """ptts_deess_rows: deess_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all).
+        deesser: one DeesserOpts for every row, or one per row (None copies that row)."""
+        return self._stage_rows(lib().ptts_deess_rows, x, deesser, C.POINTER(DeesserOpts), C.pointer)
 
     def trim_rows(self, x, trim):
         """ptts_trim_rows: trim_apply on the device, on mono f32 rows at 24 kHz (an array, or a list: one launch sequence for all), by the kernels
@@ -2211,27 +2237,28 @@ def _dsp_opts(cfg) -> Optional[DspOpts]:
     tp = getattr(cfg, "true_peak_dbtp", None)
     cmp_ = getattr(cfg, "compressor", None)
     lim = getattr(cfg, "limiter", None)
-    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None or cmp_ is not None or lim is not None):
+    des = getattr(cfg, "deesser", None)
+    if not (nz or dc or fi != 0.0 or fo != 0.0 or eq is not None or tp is not None or cmp_ is not None or lim is not None or des is not None):
         return None
     o = DspOpts(1 if nz else 0, 1 if dc else 0, fi, fo)
     if eq is not None:
         o.eq = eq.h
-    if tp is not None or cmp_ is not None or lim is not None:
-        o._ext = DspExt(true_peak_dbtp=None if tp is None else float(tp), compressor=cmp_, limiter=lim)   # (kept by the struct, which the request keeps: the handle lives as long as the call)
+    if tp is not None or cmp_ is not None or lim is not None or des is not None:
+        o._ext = DspExt(true_peak_dbtp=None if tp is None else float(tp), compressor=cmp_, limiter=lim, deesser=des)   # (kept by the struct, which the request keeps: the handle lives as long as the call)
         o.ext = o._ext.h
     return o
 
 
 class DspExt:
     """Further per-request options behind ptts_dsp_opts.ext (ptts_dsp_ext): a true-peak ceiling in dBTP (-60 .. 0; None: off), a compressor
-    (a CompressorOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off)
+    (a CompressorOpts; None: off), a de-esser (a DeesserOpts; None: off), a limiter (a LimiterOpts; None: off) and, for joined calls alone, a trim of the parts (a TrimOpts; None: off)
     and their tempo (a TempoOpts; None: off) and pitch (a PitchOpts; None: off), with the formants kept (a FormantOpts; None: they move with the pitch).
     With none of them the handle switches nothing on.  It belongs to no
-    model; keep it alive while requests that name it are running, and set its compressor and limiter before they start."""
+    model; keep it alive while requests that name it are running, and set its compressor, de-esser and limiter before they start."""
 
     def __init__(self, true_peak_dbtp: Optional[float] = None, opts: Optional[DspExtOpts] = None, compressor: Optional[CompressorOpts] = None,
                  limiter: Optional[LimiterOpts] = None, trim: Optional["TrimOpts"] = None, tempo: Optional["TempoOpts"] = None,
-                 pitch: Optional["PitchOpts"] = None, formant: Optional["FormantOpts"] = None):
+                 pitch: Optional["PitchOpts"] = None, formant: Optional["FormantOpts"] = None, deesser: Optional[DeesserOpts] = None):
         o = opts if opts is not None else DspExtOpts(C.sizeof(DspExtOpts), 0 if true_peak_dbtp is None else 1,
                                                      0.0 if true_peak_dbtp is None else float(true_peak_dbtp))
         L = lib()
@@ -2246,6 +2273,8 @@ class DspExt:
             self.set_compressor(compressor)
         if limiter is not None:
             self.set_limiter(limiter)
+        if deesser is not None:
+            self.set_deesser(deesser)
         if trim is not None:
             self.set_trim(trim)
         if tempo is not None:
@@ -2262,6 +2291,10 @@ class DspExt:
     def set_limiter(self, limiter: Optional[LimiterOpts]):
         """ptts_dsp_ext_set_limiter: attaches the limiter (None: off again).  Not while requests that name the handle are running."""
         _check(lib().ptts_dsp_ext_set_limiter(self.h, None if limiter is None else C.byref(limiter)))
+
+    def set_deesser(self, deesser: Optional[DeesserOpts]):
+        """ptts_dsp_ext_set_deesser: attaches the de-esser (None: off again).  Not while requests that name the handle are running."""
+        _check(lib().ptts_dsp_ext_set_deesser(self.h, None if deesser is None else C.byref(deesser)))
 
     def set_trim(self, trim: Optional[TrimOpts]):
         """ptts_dsp_ext_set_trim: attaches the trim of a joined call's parts (None: off again).  Served by Model.generate_joined, whose JoinOpts.dsp
@@ -2315,6 +2348,20 @@ def compress_apply(compressor: CompressorOpts, samples) -> np.ndarray:
 def limit_apply(limiter: LimiterOpts, samples) -> np.ndarray:
     """ptts_limit_apply: the limiter over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
     return _apply_on_host(lib().ptts_limit_apply, limiter, samples)
+
+
+def deess_apply(deesser: DeesserOpts, samples) -> np.ndarray:
+    """ptts_deess_apply: the de-esser over mono f32 samples at 24 kHz, on the host, in the device kernels' blocked form; returns a new array."""
+    return _apply_on_host(lib().ptts_deess_apply, deesser, samples)
+
+
+def deess_band(deesser: DeesserOpts, samples) -> np.ndarray:
+    """ptts_deess_band: the de-esser's side chain alone -- its high-pass section over mono f32 samples at 24 kHz, Eq.apply of that one section --
+    on the host; returns a new array."""
+    x = _f32(samples).reshape(-1)
+    out = np.empty(x.size, np.float32)
+    _check(lib().ptts_deess_band(C.byref(deesser), _fp(x), x.size, _fp(out)))
+    return out
 
 
 def trim_plan(trim: TrimOpts, samples) -> TrimInfo:

@@ -151,7 +151,12 @@ typedef void (*ptts_pcm_callback)(void* user, int64_t sample_offset, int64_t n_s
  * -> true-peak ceiling -> egress.  The host statement of the result: everything in front of the limiter as above, then ptts_limit_apply, then
  * ptts_true_peak_limit if the ceiling is set, then the egress; the device gives ptts_limit_apply's bits.  With a limiter a boosting equaliser
  * or a makeup gain no longer ends in the egress's hard clip: sample peaks stay at or under its ceiling, and the static ceiling behind it has
- * only the inter-sample remainder to take off. */
+ * only the inter-sample remainder to take off.
+ *
+ * The de-esser (attached to the `ext` handle by ptts_dsp_ext_set_deesser below) runs directly behind the compressor: what is said above of the
+ * compressor -- everything else is measured and applied behind it -- holds for the pair.  The whole order of a request's chain: compressor ->
+ * de-esser -> the loudness or normalise gain -> DC block -> equaliser -> fade in -> fade out -> limiter -> true-peak ceiling -> egress.  The
+ * host statement of the result: ptts_compress_apply, then ptts_deess_apply, then everything as above; the device gives ptts_deess_apply's bits. */
 #if defined(__GNUC__)
 #define PTTS_ANON __extension__
 #else
@@ -373,7 +378,8 @@ int  ptts_true_peak_rows(ptts_model* m, const float* const* in, const int64_t* n
  * 0 where 2 (L - T) < -W, (1 / R - 1)(L - T) where 2 (L - T) > W, (1 / R - 1)(L - T + W / 2)^2 / (2 W) between.  Both recurrences are evaluated
  * as blocked scans on a fixed grid (runs of 30 samples, tiles of 1920; csrc/compressor.h), and that form is the definition: host and device run
  * the same function and give the same bits.  It agrees with the sample-by-sample statement (libm's log10 and pow) to one f32 step at the
- * row's peak.  No look-ahead, no side-chain filter, not a limiter: a transient shorter than the attack passes.
+ * row's peak.  No look-ahead, no side-chain filter (the de-esser below is this detector behind one), not a limiter: a transient shorter than
+ * the attack passes.
  * Non-finite samples are not treated specially: a NaN sample comes out as NaN and touches nothing else; an infinite sample holds the level
  * at +inf for the rest of the row, which a ratio above 1 thereby silences (csrc/compressor.h).
  * ptts_compressor_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
@@ -400,6 +406,52 @@ int  ptts_dsp_ext_set_compressor(ptts_dsp_ext* e, const ptts_compressor_opts* c)
 int  ptts_compress_gain(const ptts_compressor_opts* c, double level_db, double* gain_db);
 int  ptts_compress_apply(const ptts_compressor_opts* c, float* samples, int64_t n);
 int  ptts_compress_rows(ptts_model* m, const ptts_compressor_opts* const* c, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
+
+/* De-esser at 24 kHz: the compressor's detector behind a side-chain filter, its gain applied to that band alone.
+ * Float64.  Per sample, from zero state:
+ *     b = (float) HP(x)     one PTTS_EQ_HIGHPASS section at (freq_hz, q) as ptts_eq_design designs it: b is ptts_eq_apply of that section on x
+ *     p = max(|b|, rho p),  s = alpha s + (1 - alpha) p       the compressor's two recurrences on the BAND's level (a NaN never wins)
+ *     G = max(curve(20 log10 s), -max_reduction_db)            the compressor's soft-knee curve with makeup 0, held at the floor
+ *     y = x  where G is exactly 0 (the sample's 32 bits);  elsewhere  y = (float)(x + (g - 1) b),  20 log10 g = G
+ * Only the band is turned down, and never by more than max_reduction_db; where the band's level stays under the knee the row comes back bit
+ * for bit (so does every row at ratio 1).  The three recurrences are evaluated as blocked scans on the compressor's grid (runs of 30 samples,
+ * tiles of 1920; csrc/deesser.h), through the equaliser's and the compressor's own functions and the library's own log2 and exp2, and that form
+ * is the definition: host and device run the same functions and give the same bits.  It agrees with the sample-by-sample statement (libm's
+ * log10 and pow) to one f32 step at the row's peak.  One band, minimum phase; no split into complementary bands, no wide-band mode.
+ * Non-finite samples are not treated specially: a NaN sample poisons what the biquad's state carries -- the band is NaN from that sample to
+ * the end of the row, so y is NaN there wherever G is not 0 and x bit for bit wherever it is (the level, which a NaN never enters, decays) --
+ * and an infinite one does too: the level stands at +inf for the rest of the row, G at the floor, and every sample from there on comes out
+ * non-finite (csrc/deesser.h).  Samples in front of either are untouched.  Host and device agree on which samples are NaN and on every
+ * other sample's bits; a NaN's sign and payload are the processor's.
+ * Place in a request's chain: directly behind the compressor and in front of everything else -- compressor -> de-esser -> the loudness or
+ * normalise gain -> DC block -> equaliser -> fade in -> fade out -> limiter -> true-peak ceiling -> egress.  Peak and loudness are measured on
+ * the de-essed audio.  The host statement of the result: ptts_compress_apply, ptts_deess_apply, then everything as above.  A joined call runs
+ * it once over the joined audio, like the rest of the chain.
+ * ptts_deesser_opts is size-versioned by the rules of ptts_dsp_ext_opts.size (every field below is required).  A bad field is PTTS_EINVAL and the
+ * error names it.
+ * ptts_dsp_ext_set_deesser attaches the de-esser to a live handle of ptts_dsp_ext_create (d NULL: off again); a handle that is not live is
+ * PTTS_EINVAL and is not read.  Set it before requests name the handle, not while they run.  Refused together with pcm_callback like every
+ * other switch of `ext`; a streamed joined call with a callback refuses it by name (its states are not carried from window to window yet).
+ * ptts_deess_apply: the de-esser over samples[0, n) in place.  Host.
+ * ptts_deess_band: band[0, n) receives b alone (band may be in).  Host.
+ * ptts_deess_rows: ptts_deess_apply on rows of host samples on the device, by the kernels a request's de-esser runs; shaped like
+ * ptts_limit_rows.  d[i] NULL copies row i; in[i] == out[i] is allowed; a bad row is named. */
+typedef struct ptts_deesser_opts {
+    uint32_t size;            /* sizeof(ptts_deesser_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  reserved;        /* 0 */
+    double   freq_hz;         /* 2000 .. 10000: corner of the side chain's high-pass */
+    double   q;               /* 0.3 .. 4 */
+    double   threshold_db;    /* -60 .. 0 (dBFS of the BAND's detector level) */
+    double   ratio;           /* 1 .. 100 (1: the curve does nothing) */
+    double   knee_db;         /* 0 .. 24 (0: hard knee) */
+    double   attack_ms;       /* 0.05 .. 200 */
+    double   release_ms;      /* 5 .. 5000 */
+    double   max_reduction_db;/* 0 .. 40: the band is never turned down by more */
+} ptts_deesser_opts;
+int  ptts_dsp_ext_set_deesser(ptts_dsp_ext* e, const ptts_deesser_opts* d);
+int  ptts_deess_apply(const ptts_deesser_opts* d, float* samples, int64_t n);
+int  ptts_deess_band(const ptts_deesser_opts* d, const float* in, int64_t n, float* band);
+int  ptts_deess_rows(ptts_model* m, const ptts_deesser_opts* const* d, const float* const* in, const int64_t* n, int32_t rows, float* const* out);
 
 /* Look-ahead peak limiter at 24 kHz: float64, no recurrence that is not a scan.  With c = 10^(ceiling_db / 20),
  * d = 10^(drive_db / 20), L = lrint(lookahead_ms * 24) samples (6 .. 120) and rho = exp(-1 / (release_ms * 24)), per row x[0, n):
@@ -1021,7 +1073,8 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * the new struct ptts_pitch_opts, likewise, with ptts_pitch_speed, ptts_pitch_resample_length, ptts_pitch_resample, ptts_pitch_length,
  * ptts_pitch_apply, ptts_pitch_table, ptts_pitch_rows, ptts_dsp_ext_set_pitch;
  * the new struct ptts_formant_opts, likewise, with ptts_formant_frames, ptts_formant_analyse, ptts_formant_whiten, ptts_formant_shape,
- * ptts_formant_apply, ptts_formant_rows, ptts_dsp_ext_set_formant */
+ * ptts_formant_apply, ptts_formant_rows, ptts_dsp_ext_set_formant;
+ * the new struct ptts_deesser_opts, likewise, with ptts_dsp_ext_set_deesser, ptts_deess_apply, ptts_deess_band, ptts_deess_rows */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
