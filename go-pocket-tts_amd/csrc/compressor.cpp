@@ -43,31 +43,12 @@ CmpScan cmp_design(const ptts_compressor_opts& c) {
 }
 
 void cmp_apply_blocked(const CmpScan& d, float* x, int64_t n) {
-    double Sp = 0.0, Ss = 0.0;
+    double Sp = 0.0, Ss = 0.0, tp[kDspLanes], ts[kDspLanes];
     for (int64_t base = 0; base < n; base += kDspTile) {
         const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
-        const auto count = [cnt](int l) { return std::max(0, std::min(kDspRun, cnt - l * kDspRun)); };
         float* tile = x + base;
-        double tp[kDspLanes], ts[kDspLanes];
-        double t = Sp, Ep = 0.0;
-        for (int l = 0; l < kDspLanes; l++) {
-            const double e = cmp_run_p(d, tile + l * kDspRun, count(l), 0.0);
-            tp[l] = t;
-            t = cmp_fold_p(d.rho_run, t, e);
-            Ep = cmp_fold_p(d.rho_run, Ep, e);
-        }
-        double u[1] = {Ss}, Es[1] = {0.0};
-        for (int l = 0; l < kDspLanes; l++) {
-            const double e[1] = {cmp_run_s(d, tile + l * kDspRun, count(l), tp[l], 0.0)};
-            ts[l] = u[0];
-            scan_advance<1>(&d.alpha_run, u, e);
-            scan_advance<1>(&d.alpha_run, Es, e);
-        }
-        for (int l = 0; l < kDspLanes; l++) cmp_run_y(d, tile + l * kDspRun, count(l), tp[l], ts[l], tile + l * kDspRun);
-        Sp = cmp_fold_p(d.rho_tile, Sp, Ep);
-        double S1[1] = {Ss};
-        scan_advance<1>(&d.alpha_tile, S1, Es);
-        Ss = S1[0];
+        cmp_tile_states(d, tile, cnt, Sp, Ss, tp, ts);
+        for (int l = 0; l < kDspLanes; l++) cmp_run_y(d, tile + l * kDspRun, scan_run_count(cnt, l), tp[l], ts[l], tile + l * kDspRun);
     }
 }
 

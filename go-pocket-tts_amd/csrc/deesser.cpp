@@ -51,44 +51,14 @@ void de_band_blocked(const DeScan& d, const float* x, int64_t n, float* band) {
 void de_apply_blocked(const DeScan& d, float* x, int64_t n) {
     const EqSys<1> sys = de_band(d);
     const CmpScan& c = d.det;
-    double Sb[2] = {0.0, 0.0}, Sp = 0.0, Ss = 0.0;
+    double Sb[2] = {0.0, 0.0}, Sp = 0.0, Ss = 0.0, tp[kDspLanes], ts[kDspLanes];
     float band[kDspTile];
     for (int64_t base = 0; base < n; base += kDspTile) {
         const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
-        const auto count = [cnt](int l) { return std::max(0, std::min(kDspRun, cnt - l * kDspRun)); };
         float* tile = x + base;
-        // the band of the tile: scan_walk's steps for this tile
-        double eb[kDspLanes][2] = {};
-        for (int l = 0; l < kDspLanes; l++) sys.run(tile + l * kDspRun, count(l), eb[l]);
-        double Eb[2] = {0.0, 0.0}, tb[2] = {Sb[0], Sb[1]};
-        for (int l = 0; l < kDspLanes; l++) {
-            double z[2] = {tb[0], tb[1]};
-            sys.run(tile + l * kDspRun, count(l), z, band + l * kDspRun);
-            scan_advance<2>(sys.a_run, tb, eb[l]);
-            scan_advance<2>(sys.a_run, Eb, eb[l]);
-        }
-        // the detector and the smoothing on the band: cmp_apply_blocked's steps for this tile
-        double tp[kDspLanes], ts[kDspLanes];
-        double t = Sp, Ep = 0.0;
-        for (int l = 0; l < kDspLanes; l++) {
-            const double e = cmp_run_p(c, band + l * kDspRun, count(l), 0.0);
-            tp[l] = t;
-            t = cmp_fold_p(c.rho_run, t, e);
-            Ep = cmp_fold_p(c.rho_run, Ep, e);
-        }
-        double u[1] = {Ss}, Es[1] = {0.0};
-        for (int l = 0; l < kDspLanes; l++) {
-            const double e[1] = {cmp_run_s(c, band + l * kDspRun, count(l), tp[l], 0.0)};
-            ts[l] = u[0];
-            scan_advance<1>(&c.alpha_run, u, e);
-            scan_advance<1>(&c.alpha_run, Es, e);
-        }
-        for (int l = 0; l < kDspLanes; l++) de_run_y(d, tile + l * kDspRun, band + l * kDspRun, count(l), tp[l], ts[l]);
-        scan_advance<2>(sys.a_tile, Sb, Eb);
-        Sp = cmp_fold_p(c.rho_tile, Sp, Ep);
-        double S1[1] = {Ss};
-        scan_advance<1>(&c.alpha_tile, S1, Es);
-        Ss = S1[0];
+        scan_tile(sys, tile, cnt, Sb, [&](int off, int count, double* z) { sys.run(tile + off, count, z, band + off); });   // the band of the tile
+        cmp_tile_states(c, band, cnt, Sp, Ss, tp, ts);                                                                      // the detector on it
+        for (int l = 0; l < kDspLanes; l++) de_run_y(d, tile + l * kDspRun, band + l * kDspRun, scan_run_count(cnt, l), tp[l], ts[l]);
     }
 }
 

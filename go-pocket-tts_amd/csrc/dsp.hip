@@ -4,21 +4,21 @@
 //
 //   k_dsp_peak      normalise and loudness rows: max |x| of the row.  A max is order-independent and non-negative floats order like their bit
 //                   patterns, so the workgroups' atomicMax on the uint32 image gives the host's peak whatever the schedule.  NaNs never win.
-//   k_*_summary     one workgroup per full tile that another tile follows; lane l runs run l from zero state, lane 0 folds the 64 end states
-//                   in run order into E_f (scan_summary).
-//   k_*_carry       one workgroup per row; S_0 = 0, S_(f+1) = A^1920 S_f + E_f in tile order (scan_carry).
+//   k_*_summary     one workgroup per full tile that another tile follows: the tile into LDS, E_f from it (dsp_tile.h scan_summary; the DC block's
+//                   fold is lane 0's, dc_summary below).
+//   k_*_carry       one workgroup per row: S_f of every tile in tile order (dsp_tile.h scan_carry).
 //   k_dsp_apply     every tile: gain (an IEEE f32 division, one f32 product per sample), the runs' recurrence from their entering states
-//                   (scan_enter: t_0 = S_f, t_(l+1) = A^30 t_l + e_l in run order), the rounding to f32, the two fade gains as two f32
-//                   products, one store.
+//                   (dc_enter below: dsp_tile.h's scan_enter with lane 0's fold), the rounding to f32, the two fade gains as two f32 products,
+//                   one store.
 //   k_loud_energy   every tile: the runs' entering states, each run's sum of squared outputs in sample order, and the tile's four sub-block
 //                   energies (16 run sums each, in run order) as doubles.
 //   k_loud_gate     one workgroup per row: block energies (20 sub-blocks in order, over 9600; lanes take a block each), the absolute and the
 //                   relative gate and the means in block order by lane 0, M and the f32 gain min((float)sqrt(T / M), 1 / peak).
 //   k_eq_summary, k_eq_carry, k_eq_apply   equaliser rows (DSP_EQ), behind k_dsp_apply on what it stored: the same three steps for the row's own
-//                   cascade (EqSys<S>, N = 2 S states, the coefficients read from the table's equalisers behind its rows), then the two fade
-//                   gains, which k_dsp_apply leaves to k_eq_apply for such a row.  The fold s <- A^30 s + e_l is N independent sums, each in its
-//                   fixed order: lane i < N computes component i (lanes_advance), the other components reach it by v_readlane.  The bits are
-//                   scan_advance's; the serial chain is one sum long, not N.
+//                   cascade (EqSys<S>, N = 2 S states, the coefficients read from the table's equalisers behind its rows; eq_dispatch picks
+//                   the instantiation), then the two fade gains, which k_dsp_apply leaves to k_eq_apply for such a row.
+// The scan itself -- the runs from zero state, the fold in run order, the carry in tile order -- is dsp_tile.h's for the three systems (but for
+// dc_summary and dc_enter, which say why); the kernels here load and store tiles, own the LDS and apply gains, fades and energies.
 // The limiter's kernels (limiter.hip) and the true-peak pair (true_peak.hip) follow these on the same rows; dsp_launch (dsp_device.cpp) has the order.
 // k_dsp_* are the DC block's (DspScan, DSP_DC rows, on the f32 product x * gain wherever it is read), k_loud_* the K-weighting's (LoudScan,
 // DSP_LOUD rows, on the RAW samples: nothing is written to them, k_dsp_apply applies the gain).  Stream order has the peak complete before
@@ -29,8 +29,8 @@
 // Windows (kernels.h DSP_OPEN, DspRow::t0, ::carry; dsp_tile.h): k_dsp_summary / _carry / _apply and k_eq_summary / _carry / _apply may cover tiles
 // [t0, ceil(n / 1920)) of a row only, with the window's own per-tile states; the carries start from the state the window in front left and an open
 // window leaves the state behind its last tile, whose E_f the summaries then make as well; the fade in counts in the whole row, the fade out is the
-// closing window's.  The fold is lane 0's (the lanes' for the equaliser) in tile order from whatever state it starts with, so the windows of a row
-// give the one-shot bits, and the one-shot chain is the window t0 = 0, carry null, of a closed row: the same code, launches and LDS.
+// closing window's.  The fold runs in tile order from whatever state it starts with, so the windows of a row give the one-shot bits, and the
+// one-shot chain is the window t0 = 0, carry null, of a closed row: the same code, launches and LDS.
 // k_dsp_summary and k_dsp_apply are templates on whether the table has a loudness row (k_dsp_apply: and an equaliser row), so a table without
 // one launches the instantiation that does not know the flag: the code it ran before the flag existed.
 #include "device_util.h"
@@ -99,10 +99,13 @@ __global__ __launch_bounds__(kPeakThreads) void k_dsp_peak(const DspRow* __restr
     }
 }
 
+// The DC block's own summary and enter: dsp_tile.h's scan_summary and scan_enter with the fold left to lane 0, its t_l scattered through a second
+// LDS array, and the LDS their own.  Both shared forms measured slower in k_dsp_summary and k_dsp_apply (profiles/dsp_scan_refactor.json: 4 % split,
+// 8 % whole), and so did this form on LDS passed in by pointer (3 %: the fold is then not unrolled), so these two kernels keep the code they had;
+// the carry is the shared one.  The bits are scan_advance's either way.
 // tile blockIdx.x of the row's window, which hands a state on: E_f into the window's per-tile states
-template <class Sys>
-__device__ __forceinline__ void scan_summary(const Sys& sc, const DspRow& r, double* states, const Gain g) {
-    constexpr int N = Sys::N;
+__device__ __forceinline__ void dc_summary(const DspScan& sc, const DspRow& r, double* states, const Gain g) {
+    constexpr int N = DspScan::N;
     __shared__ float4 tile4[kDspTile / 4];
     __shared__ double e[kDspLanes][N];
     float* tile = reinterpret_cast<float*>(tile4);
@@ -120,40 +123,9 @@ __device__ __forceinline__ void scan_summary(const Sys& sc, const DspRow& r, dou
         for (int i = 0; i < N; i++) E[i] = s[i];
     }
 }
-
-// a window of F >= 1 tiles: S_f of every tile from the E_f, 64 tiles at a time.  carry (null: the row starts here, from zero state, and ends
-// here): the state the window in front left, and, behind an open window's last tile, the state it leaves (win_hands: the tiles that hand on)
-template <class Sys>
-__device__ __forceinline__ void scan_carry(const Sys& sc, int64_t F, double* states, double* carry, bool open) {
-    constexpr int N = Sys::N;
-    __shared__ double ein[kDspLanes][N], sout[kDspLanes][N];
-    const int l = threadIdx.x;
-    const int64_t hands = win_hands(F, open);
-    double s[N] = {};   // lane 0's: the state entering tile c0 + j
-    if (carry) for (int i = 0; i < N; i++) s[i] = carry[i];
-    for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
-        const int64_t f = c0 + l;
-        if (f < hands) for (int i = 0; i < N; i++) ein[l][i] = scan_E<N>(states, f)[i];
-        __syncthreads();
-        if (l == 0) {
-            const int m = (int)min((int64_t)kDspLanes, F - c0);
-            for (int j = 0; j < m; j++) {
-                for (int i = 0; i < N; i++) sout[j][i] = s[i];
-                if (c0 + j < hands) scan_advance<N>(sc.a_tile, s, ein[j]);
-            }
-        }
-        __syncthreads();
-        if (f < F) for (int i = 0; i < N; i++) scan_S<N>(states, f)[i] = sout[l][i];
-        __syncthreads();
-    }
-    if (open && l == 0) for (int i = 0; i < N; i++) carry[i] = s[i];
-}
-
-// z <- the state entering the lane's run (c samples at `run`, in LDS) of tile blockIdx.x: every run from zero state, then lane 0's fold in run
-// order from S_f.  (Behind a run that is not full no run follows: its t is not read.)
-template <class Sys>
-__device__ __forceinline__ void scan_enter(const Sys& sc, const float* run, int c, double* states, double* z) {
-    constexpr int N = Sys::N;
+// z <- the state entering the lane's run (c samples at `run`, in LDS) of tile blockIdx.x
+__device__ __forceinline__ void dc_enter(const DspScan& sc, const float* run, int c, double* states, double* z) {
+    constexpr int N = DspScan::N;
     __shared__ double e[kDspLanes][N], t[kDspLanes][N];
     const int l = threadIdx.x;
     for (int i = 0; i < N; i++) z[i] = 0.0;
@@ -173,25 +145,37 @@ __device__ __forceinline__ void scan_enter(const Sys& sc, const float* run, int 
     for (int i = 0; i < N; i++) z[i] = t[l][i];
 }
 
+// the same for the K-weighting, on the shared scan
+__device__ __forceinline__ void loud_summary(const LoudScan& sc, const DspRow& r, double* states) {
+    __shared__ float4 tile4[kDspTile / 4];
+    __shared__ double e[kDspLanes * LoudScan::N];
+    float* tile = reinterpret_cast<float*>(tile4);
+    load_tile(r, blockIdx.x * (int64_t)kDspTile, kDspTile, tile, kNoGain);
+    __syncthreads();
+    scan_summary(sc, tile, e, scan_E<LoudScan::N>(states, blockIdx.x));
+}
+
 template <bool LOUD>
 __global__ __launch_bounds__(kDspLanes) void k_dsp_summary(const DspRow* __restrict__ rows, const DspScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_DC) && tile_hands_on(r.t0, r.n, r.flags & DSP_OPEN)) scan_summary(sc, r, r.tiles, row_gain<LOUD>(r));
+    if ((r.flags & DSP_DC) && tile_hands_on(r.t0, r.n, r.flags & DSP_OPEN)) dc_summary(sc, r, r.tiles, row_gain<LOUD>(r));
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_summary(const DspRow* __restrict__ rows, const LoudScan sc) {
     const DspRow& r = rows[blockIdx.y];
-    if ((r.flags & DSP_LOUD) && tile_hands_on(0, r.n, false)) scan_summary(sc, r, loud_states(r.loud), kNoGain);
+    if ((r.flags & DSP_LOUD) && tile_hands_on(0, r.n, false)) loud_summary(sc, r, loud_states(r.loud));
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_dsp_carry(const DspRow* __restrict__ rows, const DspScan sc) {
+    __shared__ double ein[kDspLanes * DspScan::N];
     const DspRow& r = rows[blockIdx.x];
-    if ((r.flags & DSP_DC) && win_tiles(r.t0, r.n) > 0) scan_carry(sc, win_tiles(r.t0, r.n), r.tiles, r.carry ? r.carry + kCarryDc : nullptr, r.flags & DSP_OPEN);
+    if ((r.flags & DSP_DC) && win_tiles(r.t0, r.n) > 0) scan_carry(sc, win_tiles(r.t0, r.n), r.tiles, ein, r.carry ? r.carry + kCarryDc : nullptr, r.flags & DSP_OPEN);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_carry(const DspRow* __restrict__ rows, const LoudScan sc) {
+    __shared__ double ein[kDspLanes * LoudScan::N];
     const DspRow& r = rows[blockIdx.x];
-    if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud), nullptr, false);
+    if ((r.flags & DSP_LOUD) && r.n > 0) scan_carry(sc, scan_tiles(r.n), loud_states(r.loud), ein, nullptr, false);
 }
 
 // tile[0, cnt) -- samples [base, base + cnt) of the row -- times the two fade gains, into the row.  base counts in the whole row, and so do the
@@ -236,7 +220,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
         float* run = tile + threadIdx.x * kDspRun;
         const int c = run_count(cnt);
         double z[DspScan::N];
-        scan_enter(sc, run, c, r.tiles, z);
+        dc_enter(sc, run, c, r.tiles, z);
         sc.run(run, c, z, run);
         __syncthreads();
     }
@@ -245,95 +229,7 @@ __global__ __launch_bounds__(kDspLanes) void k_dsp_apply(const DspRow* __restric
 
 // ---- equaliser rows ----
 
-__device__ __forceinline__ double lane_bcast(double v, int lane) {   // lane's v in every lane (lane: the same in all of them)
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
-// scan_advance, a component per lane: s <- P s + e with s_i, e_i and row i of P in lane i (i < N; the lanes behind repeat lane N - 1).  Sum i is
-// scan_advance's sum i, product by product.  All 64 lanes call it together.
-template <int N>
-__device__ __forceinline__ double lanes_advance(const double (&prow)[N], double si, double ei) {
-#pragma clang fp contract(off)
-    double v = prow[0] * lane_bcast(si, 0);
-#pragma unroll
-    for (int m = 1; m < N; m++) v = v + prow[m] * lane_bcast(si, m);
-    return v + ei;
-}
-
-// tile blockIdx.x of an equaliser row, which hands a state on (the tile is in LDS): E_f into the row's per-tile states.  e: [kDspLanes][N]
-template <class Sys>
-__device__ __forceinline__ void eq_summary(const Sys sc, const DspRow& r, const float* tile, double* e) {
-    constexpr int N = Sys::N;
-    const int l = threadIdx.x, i = min(l, N - 1);
-    double z[N] = {};
-    sc.run(tile + l * kDspRun, kDspRun, z);
-#pragma unroll
-    for (int k = 0; k < N; k++) e[l * N + k] = z[k];
-    __syncthreads();
-    double prow[N];
-#pragma unroll
-    for (int m = 0; m < N; m++) prow[m] = sc.a_run[N * i + m];
-    double s = 0.0;
-    for (int j = 0; j < kDspLanes; j++) s = lanes_advance<N>(prow, s, e[j * N + i]);
-    if (l < N) scan_E<N>(r.eq_tiles, blockIdx.x)[l] = s;
-}
-
-// a window of F >= 1 tiles of an equaliser row: S_f of every tile from the E_f, 64 tiles at a time.  ein: [kDspLanes][N]; carry, open: as
-// scan_carry's
-template <class Sys>
-__device__ __forceinline__ void eq_carry(const Sys sc, int64_t F, double* states, double* ein, double* carry, bool open) {
-    constexpr int N = Sys::N;
-    const int l = threadIdx.x, i = min(l, N - 1);
-    const int64_t hands = win_hands(F, open);
-    double prow[N];
-#pragma unroll
-    for (int m = 0; m < N; m++) prow[m] = sc.a_tile[N * i + m];
-    double s = carry ? carry[i] : 0.0;   // component i of the state entering tile c0 + j
-    for (int64_t c0 = 0; c0 < F; c0 += kDspLanes) {
-        const int64_t f = c0 + l;
-        if (f < hands) {
-#pragma unroll
-            for (int k = 0; k < N; k++) ein[l * N + k] = scan_E<N>(states, f)[k];
-        }
-        __syncthreads();
-        const int m = (int)min((int64_t)kDspLanes, F - c0);
-        for (int j = 0; j < m; j++) {
-            if (l < N) scan_S<N>(states, c0 + j)[l] = s;
-            if (c0 + j < hands) s = lanes_advance<N>(prow, s, ein[j * N + i]);
-        }
-        __syncthreads();
-    }
-    if (open && l < N) carry[l] = s;
-}
-
-// the lane's run (c samples at `run`, in LDS) of tile blockIdx.x of an equaliser row, filtered in place from its entering state: every run from
-// zero state, the fold in run order from S_f (t_l takes e_l's place in et: [kDspLanes][N]), the run again
-template <class Sys>
-__device__ __forceinline__ void eq_filter(const Sys sc, const DspRow& r, float* run, int c, double* et) {
-    constexpr int N = Sys::N;
-    const int l = threadIdx.x, i = min(l, N - 1);
-    double z[N] = {};
-    sc.run(run, c, z);
-#pragma unroll
-    for (int k = 0; k < N; k++) et[l * N + k] = z[k];
-    __syncthreads();
-    double prow[N];
-#pragma unroll
-    for (int m = 0; m < N; m++) prow[m] = sc.a_run[N * i + m];
-    double s = scan_S<N>(r.eq_tiles, blockIdx.x)[i];
-    for (int j = 0; j < kDspLanes; j++) {
-        double ej = 0.0;
-        if (l < N) { ej = et[j * N + l]; et[j * N + l] = s; }
-        s = lanes_advance<N>(prow, s, ej);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) z[k] = et[l * N + k];
-    sc.run(run, c, z, run);
-    __syncthreads();
-}
-
-constexpr int kEqStates = 2 * kEqMaxSections;
+constexpr int kEqStates = 2 * kEqMaxSections;   // the kernels' LDS is sized for the longest cascade; a row's own N = 2 S packs at its front
 
 __global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
     __shared__ float4 tile4[kDspTile / 4];
@@ -343,14 +239,7 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_summary(const DspRow* __restri
     float* tile = reinterpret_cast<float*>(tile4);
     load_tile(r, (r.t0 + blockIdx.x) * kDspTile, kDspTile, tile, kNoGain);
     __syncthreads();
-    const EqScan& q = eqs[r.eq];
-    switch (q.S) {
-        case 1: eq_summary(EqSys<1>(q), r, tile, e); break;
-        case 2: eq_summary(EqSys<2>(q), r, tile, e); break;
-        case 3: eq_summary(EqSys<3>(q), r, tile, e); break;
-        case 4: eq_summary(EqSys<4>(q), r, tile, e); break;
-        default: break;
-    }
+    eq_dispatch(eqs[r.eq], [&](auto sys) { scan_summary(sys, tile, e, scan_E<decltype(sys)::N>(r.eq_tiles, blockIdx.x)); });
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_eq_carry(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
@@ -358,16 +247,8 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_carry(const DspRow* __restrict
     const DspRow& r = rows[blockIdx.x];
     const int64_t F = win_tiles(r.t0, r.n);
     if (!(r.flags & DSP_EQ) || F <= 0) return;
-    const EqScan& q = eqs[r.eq];
     double* const carry = r.carry ? r.carry + kCarryEq : nullptr;
-    const bool open = (r.flags & DSP_OPEN) != 0;
-    switch (q.S) {
-        case 1: eq_carry(EqSys<1>(q), F, r.eq_tiles, ein, carry, open); break;
-        case 2: eq_carry(EqSys<2>(q), F, r.eq_tiles, ein, carry, open); break;
-        case 3: eq_carry(EqSys<3>(q), F, r.eq_tiles, ein, carry, open); break;
-        case 4: eq_carry(EqSys<4>(q), F, r.eq_tiles, ein, carry, open); break;
-        default: break;
-    }
+    eq_dispatch(eqs[r.eq], [&](auto sys) { scan_carry(sys, F, r.eq_tiles, ein, carry, (r.flags & DSP_OPEN) != 0); });
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_eq_apply(const DspRow* __restrict__ rows, const EqScan* __restrict__ eqs) {
@@ -382,20 +263,18 @@ __global__ __launch_bounds__(kDspLanes) void k_eq_apply(const DspRow* __restrict
     __syncthreads();
     float* run = tile + threadIdx.x * kDspRun;
     const int c = run_count(cnt);
-    const EqScan& q = eqs[r.eq];
-    switch (q.S) {
-        case 1: eq_filter(EqSys<1>(q), r, run, c, et); break;
-        case 2: eq_filter(EqSys<2>(q), r, run, c, et); break;
-        case 3: eq_filter(EqSys<3>(q), r, run, c, et); break;
-        case 4: eq_filter(EqSys<4>(q), r, run, c, et); break;
-        default: break;
-    }
+    eq_dispatch(eqs[r.eq], [&](auto sys) {   // the lane's run, filtered in place from its entering state
+        double z[decltype(sys)::N];
+        scan_enter(sys, run, c, scan_S<decltype(sys)::N>(r.eq_tiles, blockIdx.x), et, z);
+        sys.run(run, c, z, run);
+    });
+    __syncthreads();
     store_tile(r, base, cnt, tile, r.fade_in, r.fade_out);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_loud_energy(const DspRow* __restrict__ rows, const LoudScan sc) {
     __shared__ float4 tile4[kDspTile / 4];
-    __shared__ double q[kDspLanes];
+    __shared__ double q[kDspLanes], et[kDspLanes * LoudScan::N];
     float* tile = reinterpret_cast<float*>(tile4);
     const DspRow& r = rows[blockIdx.y];
     const int64_t n = r.n, base = (int64_t)blockIdx.x * kDspTile;
@@ -405,7 +284,7 @@ __global__ __launch_bounds__(kDspLanes) void k_loud_energy(const DspRow* __restr
     __syncthreads();
     const int l = threadIdx.x, c = run_count(cnt);
     double z[LoudScan::N];
-    scan_enter(sc, tile + l * kDspRun, c, loud_states(r.loud), z);
+    scan_enter(sc, tile + l * kDspRun, c, scan_S<LoudScan::N>(loud_states(r.loud), blockIdx.x), et, z);
     q[l] = sc.run(tile + l * kDspRun, c, z);
     __syncthreads();
     // (a sub-block the row ends in holds the sum over the samples that are there; no whole 400 ms block contains it, so the gate never reads it)
@@ -467,25 +346,13 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
     }
     if (!p.apply) return;   // a measurement alone
-    if (p.any_dc) {
-        if (hands > 0) {
-            note_launch("k_dsp_summary");
-            hipLaunchKernelGGL(p.any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, handing, lanes, 0, stream, rows_dev, *p.scan);
-        }
-        note_launch("k_dsp_carry");
-        hipLaunchKernelGGL(k_dsp_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.scan);
-    }
+    if (p.any_dc) launch_scan_pair("k_dsp_summary", p.any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, "k_dsp_carry", k_dsp_carry, hands, n, stream, rows_dev, *p.scan);
     note_launch("k_dsp_apply");
     if (!p.any_eq) {
         hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, false> : k_dsp_apply<false, false>), tiles, lanes, 0, stream, rows_dev, *p.scan);
     } else {
         hipLaunchKernelGGL((p.any_loud ? k_dsp_apply<true, true> : k_dsp_apply<false, true>), tiles, lanes, 0, stream, rows_dev, *p.scan);
-        if (hands > 0) {   // behind k_dsp_apply: the equaliser reads what it stored
-            note_launch("k_eq_summary");
-            hipLaunchKernelGGL(k_eq_summary, handing, lanes, 0, stream, rows_dev, p.eqs);
-        }
-        note_launch("k_eq_carry");
-        hipLaunchKernelGGL(k_eq_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, p.eqs);
+        launch_scan_pair("k_eq_summary", k_eq_summary, "k_eq_carry", k_eq_carry, hands, n, stream, rows_dev, p.eqs);   // behind k_dsp_apply: the equaliser reads what it stored
         note_launch("k_eq_apply");
         hipLaunchKernelGGL(k_eq_apply, tiles, lanes, 0, stream, rows_dev, p.eqs);
     }

@@ -1,6 +1,6 @@
 // limiter.hip -- a request's look-ahead peak limiter on ragged rows of 24 kHz audio, in place, behind the DSP kernels and in front of k_tp_peak
-// (kernels.h LimRow; limiter.h).  Four launches, shaped like compressor.hip's: one wave per workgroup, lane l owns run
-// l of its tile.
+// (kernels.h LimRow; limiter.h).  Four launches: one wave per workgroup, lane l owns run l of its tile; the
+// release is the compressor's (max, times) scan, whose fold, carry and launch pair are dsp_tile.h's (fold_enter_max, carry_max, launch_scan_pair).
 //
 //   k_lim_summary   one workgroup per full tile that another tile follows: the tile's magnitudes with L samples of halo AHEAD in LDS (8 KB),
 //                   every run's hold (lim_hold) and its release end state from p = 0, folded in run order with max (cmp_fold_p) into E_f.
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_carry(const LimRow* __restric
     __shared__ double ein[kDspLanes];
     const LimRow& r = rows[blockIdx.x];
     if (r.n <= 0) return;
-    carry_one<true>(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein, nullptr, false);
+    carry_max(designs[r.design].rho_tile, scan_tiles(r.n), r.p_tiles, ein, nullptr, false);
 }
 
 __global__ __launch_bounds__(kDspLanes) void k_lim_gain(const LimRow* __restrict__ rows, const LimScan* __restrict__ designs) {
@@ -115,13 +115,8 @@ __global__ __launch_bounds__(kDspLanes) void k_lim_apply(const LimRow* __restric
 
 void launch_limiter(const LimRow* rows_dev, int n, int max_tiles, const LimScan* designs_dev, hipStream_t stream) {
     if (n <= 0 || max_tiles <= 0) return;
-    const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)(max_tiles - 1), (unsigned)n), lanes(kDspLanes);
-    if (max_tiles > 1) {
-        note_launch("k_lim_summary");
-        hipLaunchKernelGGL(k_lim_summary, handing, lanes, 0, stream, rows_dev, designs_dev);
-    }
-    note_launch("k_lim_carry");
-    hipLaunchKernelGGL(k_lim_carry, dim3((unsigned)n), lanes, 0, stream, rows_dev, designs_dev);
+    const dim3 tiles((unsigned)max_tiles, (unsigned)n), lanes(kDspLanes);
+    launch_scan_pair("k_lim_summary", k_lim_summary, "k_lim_carry", k_lim_carry, max_tiles - 1, n, stream, rows_dev, designs_dev);
     note_launch("k_lim_gain");
     hipLaunchKernelGGL(k_lim_gain, tiles, lanes, 0, stream, rows_dev, designs_dev);
     note_launch("k_lim_apply");

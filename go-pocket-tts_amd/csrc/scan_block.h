@@ -174,28 +174,34 @@ template <int N> PTTS_HD inline size_t scan_state_doubles(int64_t F) { return (s
 template <int N> PTTS_HD inline double* scan_E(double* states, int64_t f) { return states + f * 2 * N; }
 template <int N> PTTS_HD inline double* scan_S(double* states, int64_t f) { return states + f * 2 * N + N; }
 
-// The host form: the tiles of x[0, n) in order and in each the runs from zero state, the fold giving each run's entering state and E_f, and
-// each_run(i0, count, z) for every run -- samples [i0, i0 + count), z its entering state (the callback's own arithmetic wants its own pragma)
+// samples of run l in a tile of cnt
+PTTS_HD inline int scan_run_count(int cnt, int l) { const int c = cnt - l * kDspRun; return c < 0 ? 0 : (c < kDspRun ? c : kDspRun); }
+
+// The host form, a tile of it: x[0, cnt) entered in state S, which is left at the state behind the tile -- the runs from zero state, the fold
+// giving each run's entering state and E_f, and each_run(off, count, z) for every run -- samples [off, off + count) of the tile, z its entering
+// state (the callback's own arithmetic wants its own pragma)
+template <class Sys, class F>
+inline void scan_tile(const Sys& sc, const float* x, int cnt, double* S, F&& each_run) {
+    constexpr int N = Sys::N;
+    double e[kDspLanes][N] = {};
+    for (int l = 0; l < kDspLanes; l++) sc.run(x + l * kDspRun, scan_run_count(cnt, l), e[l]);
+    double E[N] = {}, t[N];
+    for (int i = 0; i < N; i++) t[i] = S[i];
+    for (int l = 0; l < kDspLanes; l++) {
+        double z[N];
+        for (int i = 0; i < N; i++) z[i] = t[i];
+        each_run(l * kDspRun, scan_run_count(cnt, l), z);
+        scan_advance<N>(sc.a_run, t, e[l]);
+        scan_advance<N>(sc.a_run, E, e[l]);
+    }
+    scan_advance<N>(sc.a_tile, S, E);
+}
+// ... and the tiles of x[0, n) in order from zero state: each_run(i0, count, z) with i0 counting in the row
 template <class Sys, class F>
 inline void scan_walk(const Sys& sc, const float* x, int64_t n, F&& each_run) {
-    constexpr int N = Sys::N;
-    double S[N] = {};
-    for (int64_t base = 0; base < n; base += kDspTile) {
-        const int cnt = (int)std::min<int64_t>(kDspTile, n - base);
-        const auto count = [cnt](int l) { return std::max(0, std::min(kDspRun, cnt - l * kDspRun)); };
-        double e[kDspLanes][N] = {};
-        for (int l = 0; l < kDspLanes; l++) sc.run(x + base + l * kDspRun, count(l), e[l]);
-        double E[N] = {}, t[N];
-        for (int i = 0; i < N; i++) t[i] = S[i];
-        for (int l = 0; l < kDspLanes; l++) {
-            double z[N];
-            for (int i = 0; i < N; i++) z[i] = t[i];
-            each_run(base + l * kDspRun, count(l), z);
-            scan_advance<N>(sc.a_run, t, e[l]);
-            scan_advance<N>(sc.a_run, E, e[l]);
-        }
-        scan_advance<N>(sc.a_tile, S, E);
-    }
+    double S[Sys::N] = {};
+    for (int64_t base = 0; base < n; base += kDspTile)
+        scan_tile(sc, x + base, (int)std::min<int64_t>(kDspTile, n - base), S, [&](int off, int count, double* z) { each_run(base + off, count, z); });
 }
 
 // ---- loudness only: energies, gates and the gain ----
