@@ -816,4 +816,25 @@ int ptts_generate_joined_streamed(ptts_model* h, const ptts_request* reqs, int32
     });
 }
 
+// ... with one ptts_part_opts per part (generate.cpp JoinSink's per-part stages, seams and volumes).  so NULL: not streamed
+int ptts_generate_joined_parts(ptts_model* h, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, const ptts_part_opts* po, const ptts_join_stream_opts* so,
+                               ptts_result* out, ptts_join_part* parts, float* gains) {
+    return guard([&] {
+        const std::string e = so ? join_stream_opts_error(so) : std::string();
+        if (!e.empty() || !po) {   // *out and parts as generate_joined leaves them on a refusal
+            if (out) { std::memset(out, 0, sizeof *out); out->eos_step = -1; out->status = PTTS_EINVAL; }
+            for (int i = 0; parts && i < n && n <= kJoinMaxRows; i++) { std::memset(&parts[i], 0, sizeof parts[i]); parts[i].eos_step = -1; }
+            throw Error(PTTS_EINVAL, "ptts-hip: " + (e.empty() ? std::string("join: parts: null list") : e));
+        }
+        if (!h || !h->m) throw Error(PTTS_EINVAL, "native-safetensors runtime unavailable");
+        if (!reqs || !out || n <= 0) throw Error(PTTS_EINVAL, "ptts-hip: no requests");
+        if (!o) throw Error(PTTS_EINVAL, "ptts-hip: join: null options");
+        set_last_error("");
+        ptts_join_stream_opts known{};   // (a newer caller's struct: the bytes this library knows)
+        if (so) std::memcpy(&known, so, std::min<size_t>(so->size, sizeof known));
+        const JoinPartsList list{po, gains};
+        generate_joined(*h->m, reqs, n, *o, so ? &known : nullptr, out, parts, &list);
+    });
+}
+
 }  // extern "C"

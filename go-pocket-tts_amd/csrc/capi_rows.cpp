@@ -255,6 +255,32 @@ int ptts_join_rows(ptts_model* h, const float* const* in, const int64_t* n, int3
     });
 }
 
+// the statement of volume plus join (join.cpp join_parts_run), with the level's gain as ptts_loudness_normalize measures it
+int ptts_join_parts(const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* o, const ptts_part_opts* po, float* out, float* gains) {
+    return join_parts_run(in, n, rows, o, po, out, gains,
+                          [](const float* x, int64_t len, double target_lufs) { return loud_measure_gain(x, len, loud_target_power(target_lufs), nullptr); });
+}
+
+// the device form of ptts_join_parts on host rows: the loudness rows' measuring kernels for the levels, then k_join_gain (k_join for a table without a gain)
+int ptts_join_parts_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* opts, const ptts_part_opts* po, float* out,
+                         float* gains) {
+    return guard([&] {
+        Model& m = model_of(h);
+        JoinLens l;
+        JoinSeams seams;
+        std::vector<PartVolume> vol;
+        std::string e = join_opts_error(opts, &l);
+        if (e.empty()) e = join_parts_error(po, rows, l, &seams, &vol);
+        int64_t total = 0;
+        if (e.empty()) e = join_parts_plan(n, rows, seams, nullptr, nullptr, &total);
+        if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+        if (!in || (!out && total > 0)) throw Error(PTTS_EINVAL, "ptts-hip: join: null argument");
+        for (int i = 0; i < rows; i++)
+            if (!in[i] && n[i] > 0) throw Error(PTTS_EINVAL, strfmt("ptts-hip: join: part %d is null", i));
+        join_parts_rows_device(m, in, n, rows, seams, vol, out, gains);
+    });
+}
+
 // target NULL: measurement only (lufs is required); otherwise out is, and lufs receives what was measured before
 static void loudness_rows(ptts_model* h, const float* const* in, const int64_t* n, int32_t rows, const double* target, float* const* out, double* lufs) {
     Model& m = model_of(h);

@@ -329,7 +329,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
     if (n <= 0 || max_tiles <= 0) return;
     const int hands = p.any_open ? max_tiles : max_tiles - 1;   // (an open window's last tile hands on as well)
     const dim3 tiles((unsigned)max_tiles, (unsigned)n), handing((unsigned)hands, (unsigned)n), lanes(kDspLanes);
-    if (p.any_norm || (p.any_loud && p.apply)) {   // (a measurement alone has no ceiling to keep)
+    if (p.any_norm || (p.any_loud && (p.apply || p.gain_only))) {   // (a measurement alone has no ceiling to keep)
         note_launch("k_dsp_peak");
         hipLaunchKernelGGL(k_dsp_peak, dim3((unsigned)((max_tiles + 3) / 4), (unsigned)n), dim3(kPeakThreads), 0, stream, rows_dev);
     }
@@ -345,7 +345,7 @@ void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p
         note_launch("k_loud_gate");
         hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)n), lanes, 0, stream, rows_dev, *p.loud);
     }
-    if (!p.apply) return;   // a measurement alone
+    if (!p.apply || p.gain_only) return;   // a measurement alone, or the gain left in its word for another kernel to apply
     if (p.any_dc) launch_scan_pair("k_dsp_summary", p.any_loud ? k_dsp_summary<true> : k_dsp_summary<false>, "k_dsp_carry", k_dsp_carry, hands, n, stream, rows_dev, *p.scan);
     note_launch("k_dsp_apply");
     if (!p.any_eq) {

@@ -303,6 +303,150 @@ void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_
     PTTS_HIP(hipStreamSynchronize(s));
 }
 
+// ---- per-part options (include/ptts.h ptts_part_opts): the level's measuring launches, the gain form of the join ----
+
+void level_launch(Model& m, const std::vector<const float*>& x, const std::vector<int64_t>& n, const std::vector<double>& target, std::vector<const float*>& words,
+                  hipStream_t s) {
+    const size_t R = x.size();
+    words.assign(R, nullptr);
+    size_t doubles = 0, live = 0;
+    for (size_t i = 0; i < R; i++)
+        if (n[i] > 0) { doubles += loud_doubles(scan_tiles(n[i])); live++; }
+    if (!live) return;
+    const size_t peak_bytes = (live * sizeof(uint32_t) + 255) & ~(size_t)255;
+    char* scratch = m.work(WORK_PART_LEVEL, peak_bytes + doubles * sizeof(double)).as<char>();
+    uint32_t* peaks = reinterpret_cast<uint32_t*>(scratch);
+    double* loud = reinterpret_cast<double*>(scratch + peak_bytes);
+    PTTS_HIP(hipMemsetAsync(peaks, 0, peak_bytes, s));
+    std::vector<DspRow> rows;
+    for (size_t i = 0; i < R; i++) {
+        if (n[i] <= 0) continue;   // (an empty part: nothing passes the gates, its gain is 1)
+        DspRow r{};
+        r.x = const_cast<float*>(x[i]); r.n = n[i];   // the measuring kernels write nothing to x
+        r.peak = peaks + rows.size();
+        r.flags = DSP_LOUD;
+        r.loud = loud;
+        r.target = target[i];
+        words[i] = reinterpret_cast<const float*>(loud + 1);
+        loud += loud_doubles(scan_tiles(n[i]));
+        rows.push_back(r);
+    }
+    constexpr size_t kRows = RowRing<DspRow, kDspMaxEq * kDspEqBytes>::kRows;
+    static const DspScan scan = dsp_scan_coeffs(kNativeRate);
+    for (size_t at = 0; at < rows.size(); at += kRows) {
+        const int k = (int)std::min(kRows, rows.size() - at);
+        int64_t tiles = 0;
+        for (int i = 0; i < k; i++) tiles = std::max(tiles, scan_tiles(rows[at + (size_t)i].n));
+        if (tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: join: parts: level: too many samples for one launch");
+        DspLaunch p{false, false, true, false, &scan, &loud_scan()};
+        p.gain_only = true;
+        launch_dsp(m.dsp_ring.stage(rows.data() + at, k, s), k, (int)tiles, p, s);
+        m.dsp_ring.done(s);
+    }
+}
+
+void join_gain_launch(Model& m, const std::vector<JoinGainRow>& rows, hipStream_t s) {
+    constexpr int kRows = RowRing<JoinGainRow>::kRows;
+    std::vector<JoinRow> plain;
+    for (size_t at = 0; at < rows.size(); at += kRows) {
+        const int n = (int)std::min<size_t>(kRows, rows.size() - at);
+        int64_t tiles = 0;
+        bool any = false;
+        for (int i = 0; i < n; i++) {
+            const JoinRow& r = rows[at + (size_t)i].r;
+            any = any || rows[at + (size_t)i].flags != 0;
+            if (r.gap + r.n > 0) tiles = std::max(tiles, (r.gap + r.n + 3 + kJoinTile - 1) / kJoinTile);
+        }
+        if (tiles == 0) continue;
+        if (tiles > INT32_MAX) throw Error(PTTS_EINVAL, "ptts-hip: join: too many samples for one launch");
+        if (!any) {   // a table without a gain: k_join, as join_launch launches it
+            plain.clear();
+            for (int i = 0; i < n; i++) plain.push_back(rows[at + (size_t)i].r);
+            launch_join(m.join_ring.stage(plain.data(), n, s), n, (int)tiles, s);
+            m.join_ring.done(s);
+            continue;
+        }
+        launch_join_gain(m.join_gain_ring.stage(rows.data() + at, n, s), n, (int)tiles, s);
+        m.join_gain_ring.done(s);
+    }
+}
+
+// the flags and the gains of row r from the part's volume and, for a seam whose tail lies in the predecessor's own buffer, the predecessor's
+static void join_row_gains(JoinGainRow& r, const PartGain& mine, const PartGain* prev) {
+    if (mine.fixed) { r.flags |= JOIN_GAIN_IMM; r.g = mine.g; }
+    else if (mine.word) { r.flags |= JOIN_GAIN_WORD; r.gw = mine.word; }
+    if (!prev || r.r.k <= 0) return;
+    if (prev->fixed) { r.flags |= JOIN_PREV_IMM; r.g_prev = prev->g; }
+    else if (prev->word) { r.flags |= JOIN_PREV_WORD; r.gw_prev = prev->word; }
+}
+
+JoinGainRow join_gain_row(const JoinRow& r, const PartGain& mine, const PartGain* prev) {
+    JoinGainRow g{};
+    g.r = r; g.g = 1.0f; g.g_prev = 1.0f;
+    join_row_gains(g, mine, prev);
+    return g;
+}
+
+// the parts' volumes on device rows: the fixed gains as they are, the levels' words from one level_launch over the rows that have one
+std::vector<PartGain> part_gains_launch(Model& m, const std::vector<const float*>& x, const std::vector<int64_t>& n, const std::vector<PartVolume>& vol, hipStream_t s) {
+    std::vector<PartGain> g(vol.size());
+    std::vector<const float*> lx, words;
+    std::vector<int64_t> ln;
+    std::vector<double> lt;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < vol.size(); i++) {
+        if (vol[i].fixed) { g[i].fixed = true; g[i].g = vol[i].g; }
+        else if (vol[i].level) { lx.push_back(x[i]); ln.push_back(n[i]); lt.push_back(loud_target_power(vol[i].target_lufs)); at.push_back(i); }
+    }
+    if (!lx.empty()) {
+        level_launch(m, lx, ln, lt, words, s);
+        for (size_t k = 0; k < at.size(); k++) g[at[k]].word = words[k];
+    }
+    return g;
+}
+
+void join_parts_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinSeams& seams, const std::vector<PartVolume>& vol, float* out,
+                            float* gains) {
+    std::vector<int64_t> off((size_t)rows), seam((size_t)rows);
+    int64_t total = 0;
+    const std::string e = join_parts_plan(n, rows, seams, off.data(), seam.data(), &total);
+    if (!e.empty()) throw Error(PTTS_EINVAL, "ptts-hip: " + e);
+    for (int i = 0; gains && i < rows; i++) gains[i] = vol[(size_t)i].fixed ? vol[(size_t)i].g : 1.0f;
+    if (total == 0) return;
+    std::lock_guard<std::mutex> lock(m.mu);
+    m.use_device();
+    hipStream_t s = m.stream;
+    std::vector<size_t> bytes((size_t)rows + 1);
+    for (int i = 0; i < rows; i++) bytes[(size_t)i] = (size_t)n[i] * sizeof(float);
+    bytes[(size_t)rows] = (size_t)total * sizeof(float);   // the joined row, behind the parts
+    PackedRows buf(m, WORK_HOST_ROWS, std::move(bytes));
+    std::vector<const float*> x((size_t)rows);
+    std::vector<int64_t> len(n, n + rows);
+    for (int i = 0; i < rows; i++) {
+        if (n[i] > 0) buf.upload(i, in[i], s);
+        x[(size_t)i] = (const float*)buf.row(i);
+    }
+    const std::vector<PartGain> pg = part_gains_launch(m, x, len, vol, s);
+    std::vector<JoinGainRow> jr;
+    for (int i = 0; i < rows; i++) {
+        const int64_t k = seam[(size_t)i], k_next = i + 1 < rows ? seam[(size_t)i + 1] : 0;
+        JoinRow r{};
+        r.src = x[(size_t)i];
+        r.prev = k ? x[(size_t)i - 1] + (n[i - 1] - k) : nullptr;
+        r.dst = (float*)buf.row(rows);
+        r.off = off[(size_t)i];
+        r.n = n[i] - k_next;
+        r.k = (int32_t)k;
+        r.gap = i ? (int32_t)seams.lens[(size_t)i - 1].gap : 0;
+        jr.push_back(join_gain_row(r, pg[(size_t)i], i ? &pg[(size_t)i - 1] : nullptr));
+    }
+    join_gain_launch(m, jr, s);
+    buf.download(rows, out, s);
+    for (int i = 0; gains && i < rows; i++)
+        if (pg[(size_t)i].word) PTTS_HIP(hipMemcpyAsync(gains + i, pg[(size_t)i].word, sizeof(float), hipMemcpyDeviceToHost, s));
+    PTTS_HIP(hipStreamSynchronize(s));
+}
+
 // ---- the part stages of a joined call: the trim (trim.hip; trim.h), the pitch (pitch.hip; pitch.h), the tempo (tempo.hip; tempo.h) ----
 
 UploadedTable::~UploadedTable() {

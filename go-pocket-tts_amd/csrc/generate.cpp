@@ -204,7 +204,8 @@ namespace {
 // What the groups of one generate_joined call share: the text's joined row on the device (WORK_JOINED, sized for the step budgets before the
 // first group runs), how far it is filled, and the parts' records.  A group's Chunk::deliver joins its rows behind what is there.
 struct JoinSink {
-    JoinLens lens;
+    JoinLens lens;                // the pair of the join options
+    std::vector<JoinLens> seam;   // [n], by request index: the seam BEHIND part i (a call without a list: `lens` everywhere)
     float* row = nullptr;         // the joined row (device)
     int64_t cap = 0;              // its samples
     ptts_join_part* parts;        // [n], by request index
@@ -215,11 +216,17 @@ struct JoinSink {
     std::string fail_msg;
     // What the join options' ext asks for every part in front of k_join, resolved once, before anything launches (runtime.h PartStages; parts_launch
     // runs it): a trim, whose length comes back from the device; a pitch other than 1000 (with the formants kept, where the handle says so); a tempo -- behind a pitch the pair (speed, pitch) was
-    // resolved beforehand (pitch.h pitch_steps), `tmp` carries the effective speed and the step is off at 1000.  The designs the stages point to:
-    PartStages stages;
-    TrimScan trm{};
-    PitchScan pit{};
-    TempoScan tmp{};
+    // resolved beforehand (pitch.h pitch_steps), `tmp` carries the effective speed and the step is off at 1000.  One PartStages per part, by request
+    // index: a call without a list (include/ptts.h ptts_part_opts) fills them uniformly from the handle.  The designs the stages point to ([n], or [1]
+    // where every part shares them):
+    std::vector<PartStages> stages;
+    std::vector<TrimScan> trm;
+    std::vector<PitchScan> pit;
+    std::vector<TempoScan> tmp;
+    // a list's volumes ([n]; empty: a call without a list, whose groups go to join_launch as they always did) and where the gains go ([n], pinned;
+    // null: a call without a list)
+    std::vector<PartVolume> vol;
+    float* gains = nullptr;
 };
 
 // One generate_chunk call: its requests and what its phases share.  The destructor is the clean-up of the normal path and of a throw
@@ -608,34 +615,56 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
     }
     if (join->fail != PTTS_OK) return;   // the call fails: nothing of this group is decoded
     decode_rest(std::min(steps_run, Tmax));
-    const JoinLens& l = join->lens;
-    // The parts as the join sees them: the decoder's rows through the part stages (parts_launch: the trim, the pitch, the tempo, each where the call
+    // The parts as the join sees them: the decoder's rows through the part stages (parts_launch: the trim, the pitch, the tempo, each where the part
     // has it).  What the trim keeps lies in a buffer of the decoder buffer's row stride; the resampled and the time-scaled forms in buffers whose
-    // row stride holds the longest a decoded row can become.  Everything below counts in the lengths that come back
-    const PartStages& st = join->stages;
+    // row stride holds the longest a decoded row of the group's widest part can become.  Everything below counts in the lengths that come back
     const size_t decoded = (size_t)T * spf;
-    float* const kept = st.trim ? m.work(WORK_TRIMMED, std::max<size_t>((size_t)B * decoded, 1) * sizeof(float)).as<float>() : nullptr;
-    const int64_t wide_p = st.pitch ? std::max<int64_t>(decoded, pitch_resample_length(decoded, st.pitch->p)) : (int64_t)decoded;
-    float* const shifted = st.pitch ? m.work(WORK_PITCH, std::max<size_t>((size_t)B * (size_t)wide_p, 1) * sizeof(float)).as<float>() : nullptr;
-    const int64_t wide_t = st.tempo ? std::max(wide_p, tempo_length(wide_p, st.tempo->speed)) : wide_p;
-    float* const scaled = st.tempo ? m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide_t, 1) * sizeof(float)).as<float>() : nullptr;
+    bool any_trim = false, any_pitch = false, any_tempo = false;
+    int64_t wide_p = (int64_t)decoded, wide_t = (int64_t)decoded;
+    for (int i = 0; i < B; i++) {
+        const PartStages& st = join->stages[(size_t)idx[(size_t)i]];
+        any_trim |= st.trim != nullptr; any_pitch |= st.pitch != nullptr; any_tempo |= st.tempo != nullptr;
+        const int64_t mine_p = st.pitch ? std::max<int64_t>(decoded, pitch_resample_length(decoded, st.pitch->p)) : (int64_t)decoded;
+        const int64_t mine_t = st.tempo ? std::max(mine_p, tempo_length(mine_p, st.tempo->speed)) : mine_p;
+        wide_p = std::max(wide_p, mine_p);
+        wide_t = std::max(wide_t, mine_t);
+    }
+    float* const kept = any_trim ? m.work(WORK_TRIMMED, std::max<size_t>((size_t)B * decoded, 1) * sizeof(float)).as<float>() : nullptr;
+    float* const shifted = any_pitch ? m.work(WORK_PITCH, std::max<size_t>((size_t)B * (size_t)wide_p, 1) * sizeof(float)).as<float>() : nullptr;
+    float* const scaled = any_tempo ? m.work(WORK_TEMPO, std::max<size_t>((size_t)B * (size_t)wide_t, 1) * sizeof(float)).as<float>() : nullptr;
     std::vector<PartRow> part((size_t)B);
     for (int i = 0; i < B; i++) {
         PartRow& r = part[(size_t)i];
-        r.src = pcm->as<float>() + (size_t)i * decoded; r.n = (int64_t)nf[i] * spf; r.st = st;
-        if (kept) r.trimmed = kept + (size_t)i * decoded;
-        if (shifted) r.shifted = shifted + (size_t)i * (size_t)wide_p;
-        if (scaled) r.scaled = scaled + (size_t)i * (size_t)wide_t;
+        r.src = pcm->as<float>() + (size_t)i * decoded; r.n = (int64_t)nf[i] * spf; r.st = join->stages[(size_t)idx[(size_t)i]];
+        if (r.st.trim) r.trimmed = kept + (size_t)i * decoded;
+        if (r.st.pitch) r.shifted = shifted + (size_t)i * (size_t)wide_p;
+        if (r.st.tempo) r.scaled = scaled + (size_t)i * (size_t)wide_t;
     }
     parts_launch(m, part, s, [&](const char* what) { mark(what); }, "part");
+    // a list's volumes, on the parts as the tempo left them: the fixed gains, and for the levels the loudness rows' measuring launches, whose gain
+    // words k_join_gain reads (no host round trip, no pass that rewrites the samples)
+    std::vector<PartGain> pg;
+    if (!join->vol.empty()) {
+        std::vector<const float*> x((size_t)B);
+        std::vector<int64_t> len((size_t)B);
+        std::vector<PartVolume> vol((size_t)B);
+        for (int i = 0; i < B; i++) { x[(size_t)i] = part[(size_t)i].out; len[(size_t)i] = part[(size_t)i].n_out; vol[(size_t)i] = join->vol[(size_t)idx[(size_t)i]]; }
+        pg = part_gains_launch(m, x, len, vol, s);
+        for (int i = 0; i < B; i++) {
+            float* const to = join->gains + idx[(size_t)i];
+            *to = pg[(size_t)i].fixed ? pg[(size_t)i].g : 1.0f;
+            if (pg[(size_t)i].word) PTTS_HIP(hipMemcpyAsync(to, pg[(size_t)i].word, sizeof(float), hipMemcpyDeviceToHost, s));   // (page-locked: nothing waits)
+        }
+    }
     std::vector<JoinRow> rows;
     for (int i = 0; i < B; i++) {
         ptts_join_part& p = join->parts[idx[(size_t)i]];
         const int64_t n = part[(size_t)i].n_out;
         const bool first = join->n_prev < 0;
+        const JoinLens l = first ? JoinLens{} : join->seam[(size_t)idx[(size_t)i] - 1];   // the seam in front of the part
         const int64_t k = first ? 0 : join_seam(l.xfade, join->n_prev, n);
         const int64_t off = first ? 0 : join->at + l.gap - k;
-        const int64_t k_next = i + 1 < B ? join_seam(l.xfade, n, part[(size_t)i + 1].n_out) : 0;   // (the group's last row stores its tail whole)
+        const int64_t k_next = i + 1 < B ? join_seam(join->seam[(size_t)idx[(size_t)i]].xfade, n, part[(size_t)i + 1].n_out) : 0;   // (the group's last row stores its tail whole)
         if (off + n > join->cap) throw Error(PTTS_EINVAL, "ptts-hip: internal: the joined row is smaller than the text");
         JoinRow r{};
         r.src = part[(size_t)i].out;
@@ -645,6 +674,13 @@ void Chunk::deliver_joined(const int32_t* nf, const int32_t* eos) {
         rows.push_back(r);
         p.offset = off; p.n_samples = n;
         join->at = off + n; join->n_prev = n; join->frames += nf[i];
+    }
+    if (!join->vol.empty()) {   // the gain form where a table has a gain (join_gain_launch); the tail of an earlier group lies in the joined row, scaled
+        std::vector<JoinGainRow> grows;
+        for (int i = 0; i < B; i++) grows.push_back(join_gain_row(rows[(size_t)i], pg[(size_t)i], i ? &pg[(size_t)i - 1] : nullptr));
+        join_gain_launch(m, grows, s);
+        mark("join");
+        return;
     }
     join_launch(m, rows, s);   // behind the decode (stream2 has been waited for); the next group's decode waits for s (decode_upto)
     mark("join");
@@ -779,7 +815,7 @@ struct JoinStream {
     const ptts_join_stream_opts& so;
     const ptts_request& eg;          // the join options' chain and egress, as a request states its own
     DspSpec spec;                    // the chain, resolved before anything launched
-    int64_t hold = 0, fade_in = 0;   // max(K, Fo); the fade in's samples, not clamped
+    int64_t fade_in = 0;             // the fade in's samples, not clamped
     void* host = nullptr;            // the result's buffer, allocated for the step budgets' bound
     char* stage = nullptr;           // where the egress stores when it cannot store into `host` itself (device, indexed like `host`)
     double* carry = nullptr;         // the chain's carried states (device, [kCarryDoubles])
@@ -795,8 +831,7 @@ struct JoinStream {
         if (ev) (void)hipEventDestroy(ev);
         result_free(host);
     }
-    void setup(const ptts_join_opts& o, const JoinLens& lens, int64_t bound, hipStream_t s) {
-        hold = join_stream_hold(o, lens);
+    void setup(int64_t bound, hipStream_t s) {
         fade_in = spec.fade_in_ms > 0 ? (int64_t)(spec.fade_in_ms / 1000.0 * (double)kNativeRate) : 0;
         const size_t bytes = (size_t)std::max<int64_t>(1, egress_length(eg, bound)) * pcm_bytes(eg.pcm_format);
         host = result_alloc(bytes);
@@ -807,8 +842,8 @@ struct JoinStream {
         PTTS_HIP(hipMemsetAsync(carry, 0, kCarryDoubles * sizeof(double), s));
         PTTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    // behind a group's k_join: `at` samples are joined; last: no part follows
-    void window(float* row, int64_t at, bool last, hipStream_t s) {
+    // behind a group's k_join: `at` samples are joined; last: no part follows; hold: max(K, Fo), K the crossfade of the seam behind the group
+    void window(float* row, int64_t at, bool last, int64_t hold, hipStream_t s) {
         int64_t P = last ? at : std::max(done, join_stream_ready(at, hold));
         if (!last && at < fade_in) P = done;   // the fade in is clamped by the final length: not known to exceed it yet
         if (P > done || last) {
@@ -852,7 +887,8 @@ struct JoinStream {
 };
 }  // namespace
 
-void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts) {
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts,
+                     const JoinPartsList* list) {
     std::lock_guard<std::mutex> lock(m.mu);
     m.use_device();
     const Desc& d = m.d;
@@ -872,25 +908,65 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
     if (e.empty() && so && (so->first_group < 0 || so->first_group > mb))
         e = strfmt("join: stream: first_group %d is not 0 (max_batch) or from 1 to max_batch (%d)", so->first_group, mb);
     if (!e.empty()) refuse(e);
+    for (int i = 0; list && list->gains && i < n; i++) list->gains[i] = 1.0f;
+    if (list) {   // the list's seams and volumes (join.h), resolved against the pair of the join options
+        JoinSeams seams;
+        e = join_parts_error(list->po, n, sink.lens, &seams, &sink.vol);
+        if (!e.empty()) refuse(e);
+        sink.seam = std::move(seams.lens);
+        sink.gains = static_cast<float*>(m.part_gains.ensure((size_t)n * sizeof(float)));
+        for (int i = 0; i < n; i++) sink.gains[i] = 1.0f;
+    } else {
+        sink.seam.assign((size_t)n, sink.lens);
+    }
     const bool streamed = so && so->pcm_callback;
     DspSpec spec;
+    sink.stages.assign((size_t)n, PartStages{});
     if (o.dsp) {   // the trim and the tempo of the parts, resolved once: the chain below never sees them
         e = dsp_resolve(o.dsp, &spec);
         if (!e.empty()) refuse("join: " + e);
-        sink.trm = spec.trm;
-        sink.pit = spec.pit;
-        sink.tmp = spec.tmp;
-        PitchSteps run{sink.tmp.speed, false, spec.tempo};
+        if (const char* f = !list ? nullptr : spec.trim ? "trim" : spec.pitch ? "pitch" : spec.formant ? "formant" : spec.tempo ? "tempo" : nullptr)
+            refuse(strfmt("join: parts: the ext handle's %s belongs in the list (ptts_part_opts) of a call with per-part options", f));
+        sink.trm.assign(1, spec.trm);
+        sink.pit.assign(1, spec.pit);
+        sink.tmp.assign(1, spec.tmp);
+        PitchSteps run{sink.tmp[0].speed, false, spec.tempo};
         if (spec.pitch) {   // the pair (speed, pitch) becomes the tempo's effective speed; either step may be the identity, and then it is not run
             e = pitch_steps(spec.pit.p, spec.tempo ? spec.tmp.speed : 1000, &run);
             if (!e.empty()) refuse("join: " + e);
-            sink.tmp.speed = run.E;
+            sink.tmp[0].speed = run.E;
         }
-        sink.stages = PartStages{spec.trim ? &sink.trm : nullptr, run.resample ? &sink.pit : nullptr, run.tempo ? &sink.tmp : nullptr};
+        PartStages all{spec.trim ? &sink.trm[0] : nullptr, run.resample ? &sink.pit[0] : nullptr, run.tempo ? &sink.tmp[0] : nullptr};
         if (spec.formant && run.resample) {   // keep the formants around that resample: the pair (option, pitch) is resolved here too
             e = formant_pitch_error(spec.pit.p);
             if (!e.empty()) refuse("join: " + e);
-            sink.stages.formant = true;
+            all.formant = true;
+        }
+        sink.stages.assign((size_t)n, all);
+    }
+    if (list) {   // every part's own stages, each pair (tempo, pitch) resolved to its effective speed: as ptts_formant_rows resolves a row
+        sink.trm.resize((size_t)n); sink.pit.resize((size_t)n); sink.tmp.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            const ptts_part_opts po = part_opts_known(list->po, i);
+            const auto part_refuse = [&](const std::string& why) { if (!why.empty()) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: parts: part %d: ", i) + why); } };
+            if (po.formant && !po.pitch) part_refuse("formant is set without pitch: the option keeps the formants around the pitch's resample");
+            if (po.trim) part_refuse(trim_opts_error(po.trim));
+            if (po.pitch) part_refuse(pitch_opts_error(po.pitch));
+            if (po.formant) part_refuse(formant_opts_error(po.formant));
+            if (po.tempo) part_refuse(tempo_opts_error(po.tempo));
+            PartStages& st = sink.stages[(size_t)i];
+            if (po.trim) { sink.trm[(size_t)i] = trim_design(*po.trim); st.trim = &sink.trm[(size_t)i]; }
+            PitchSteps run{po.tempo ? po.tempo->speed_permille : 1000, false, po.tempo != nullptr};
+            if (po.pitch) {
+                part_refuse(pitch_steps(po.pitch->pitch_permille, run.E, &run));
+                if (run.resample) { sink.pit[(size_t)i] = pitch_design(*po.pitch); st.pitch = &sink.pit[(size_t)i]; }
+            }
+            sink.tmp[(size_t)i].speed = run.E;
+            if (run.tempo) st.tempo = &sink.tmp[(size_t)i];
+            if (po.formant && po.formant->keep && st.pitch) {
+                part_refuse(formant_pitch_error(st.pitch->p));
+                st.formant = true;
+            }
         }
     }
     if (streamed) {   // window after window only the causal stages run
@@ -911,9 +987,10 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (l != lsd) { parts[i].status = PTTS_EINVAL; refuse(strfmt("join: request %d has lsd_steps %d and request 0 has %d: the groups would leave text order", i, l, lsd)); }
         // (the trim only shortens; pitch_resample_length and tempo_length are monotone)
         const int64_t budget = (int64_t)std::min(resolve_max_steps(q), mimi_frame_limit(d)) * spf;
-        const int64_t shifted = sink.stages.pitch ? pitch_resample_length(budget, sink.pit.p) : budget;
-        const int64_t scaled = sink.stages.tempo ? tempo_length(shifted, sink.tmp.speed) : shifted;
-        bound += std::max(budget, std::max(shifted, scaled)) + (i ? sink.lens.gap : 0);
+        const PartStages& st = sink.stages[(size_t)i];
+        const int64_t shifted = st.pitch ? pitch_resample_length(budget, st.pitch->p) : budget;
+        const int64_t scaled = st.tempo ? tempo_length(shifted, st.tempo->speed) : shifted;
+        bound += std::max(budget, std::max(shifted, scaled)) + (i ? sink.seam[(size_t)i - 1].gap : 0);
     }
     if (bound >= kJoinMaxSamples) refuse(strfmt("join: the step budgets allow %lld samples, the joined length must stay below 2^31", (long long)bound));
     ptts_request eg{};   // the chain and the egress of the joined row, as a request states its own: results_deliver serves it like one
@@ -926,7 +1003,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         if (streamed) {
             js.reset(new JoinStream(m, *so, eg));
             js->spec = spec;
-            js->setup(o, sink.lens, bound, s);
+            js->setup(bound, s);
         }
         // ---- the groups, as generate() cuts them; a streamed call's first group may be smaller ----
         for (int o0 = 0, size = so && so->first_group ? so->first_group : mb; o0 < n && sink.fail == PTTS_OK; o0 += size, size = mb) {
@@ -939,7 +1016,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
                 throw;
             }
             // the group's hand-over, queued behind its k_join and in front of the next group's prefill; nothing waits for it here
-            if (js && sink.fail == PTTS_OK) js->window(sink.row, sink.at, o0 + size >= n, s);
+            if (js && sink.fail == PTTS_OK) js->window(sink.row, sink.at, o0 + size >= n, join_stream_hold(o, sink.seam[(size_t)idx.back()]), s);
         }
         if (sink.fail != PTTS_OK) throw Error(sink.fail, sink.fail_msg);
         if (js) {   // every sample has been handed over from the buffer the result now owns
@@ -950,6 +1027,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
             set_result_buffer(*out, eg.pcm_format, js->host);
             js->host = nullptr;
             out->status = PTTS_OK;
+            for (int i = 0; list && list->gains && i < n; i++) list->gains[i] = sink.gains[i];
             return;
         }
         // ---- the chain, once over the joined audio; the egress of one row ----
@@ -960,6 +1038,7 @@ void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_
         results_deliver(m, g, false, sink.row, sink.at, nullptr, 0, s);
         PTTS_HIP(hipStreamSynchronize(s));
         if (out->status != PTTS_OK) throw Error(out->status, "ptts-hip: out of host memory");
+        for (int i = 0; list && list->gains && i < n; i++) list->gains[i] = sink.gains[i];
     } catch (const Error& err) {
         (void)hipStreamSynchronize(s);   // nothing queued still writes the buffer that goes back
         js.reset();                      // (a streamed call: both streams drained, then its buffer freed)

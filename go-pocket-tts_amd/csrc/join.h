@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/ptts.h"
 
@@ -44,5 +45,39 @@ std::string join_plan(const int64_t* n, int32_t rows, const JoinLens& l, int64_t
 
 // the joined audio of in[0 .. rows) into out[0, total): every sample written once
 void join_host(const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
+
+// ---- per-part options (include/ptts.h ptts_part_opts): a seam of its own behind every part, a volume per part ----
+
+constexpr double kPartMinGainDb = -60.0, kPartMaxGainDb = 24.0;
+constexpr int32_t kPartMinLevel = -7000, kPartMaxLevel = -100;
+
+// element i of a caller's list: its elements lie po[0].size bytes apart (join_parts_error has checked the sizes)
+inline const ptts_part_opts& part_opts_at(const ptts_part_opts* po, int32_t i) {
+    return *reinterpret_cast<const ptts_part_opts*>(reinterpret_cast<const char*>(po) + (size_t)i * po->size);
+}
+// the bytes of an element that this library knows, the rest read as 0
+ptts_part_opts part_opts_known(const ptts_part_opts* po, int32_t i);
+
+// the seams of a list: lens[i] is the seam BEHIND part i, in samples ([rows]; the last one is unused)
+struct JoinSeams { std::vector<JoinLens> lens; };
+// A part's volume, resolved: a fixed gain is applied to every sample (apply), a level's is measured -- on the host by a PartLevelGain, on the
+// device by the loudness rows' kernels -- and applied where it is not 1
+struct PartVolume { float g = 1.0f; bool fixed = false; double target_lufs = 0.0; bool level = false; };
+// the gain ptts_loudness_normalize(x, n, target_lufs, NULL) applies (loudness.cpp measures it: this file and join.cpp build without it)
+using PartLevelGain = float (*)(const float* x, int64_t n, double target_lufs);
+
+// empty: the list is well formed as far as the host join goes, *seams (optional) has the seams resolved against dflt (the pair of the join options)
+// and *vol (optional: the volume fields are then not read) the volumes; otherwise the message, naming the field and the part index
+std::string join_parts_error(const ptts_part_opts* po, int32_t rows, const JoinLens& dflt, JoinSeams* seams, std::vector<PartVolume>* vol);
+// one seam's pair against dflt: the rule of the list; what: "part 3" in the message
+std::string part_seam_error(const char* what, double gap_ms, double crossfade_ms, const JoinLens& dflt, JoinLens* out);
+// join_plan with a seam of its own behind every part
+std::string join_parts_plan(const int64_t* n, int32_t rows, const JoinSeams& s, int64_t* offsets, int64_t* seams, int64_t* total);
+// join_host with the seams of the list and the parts' gains: g[i] multiplies every sample of part i where apply[i] is set (one f32 product, in
+// front of the seam arithmetic), the other parts move as their bits
+void join_parts_host(const float* const* in, const int64_t* n, int32_t rows, const JoinSeams& s, const float* g, const bool* apply, float* out);
+// ptts_join_parts (capi_rows.cpp hands in loudness.cpp's measurement): the checks, the parts' gains, join_parts_host.  PTTS_OK, or PTTS_EINVAL with the message set
+int join_parts_run(const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* o, const ptts_part_opts* po, float* out, float* gains,
+                   PartLevelGain level_gain);
 
 }  // namespace ptts

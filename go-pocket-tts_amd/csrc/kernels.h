@@ -358,6 +358,7 @@ static_assert(sizeof(DspRow) == 112, "a turn of the DSP ring holds 256 of them")
 struct DspLaunch {
     bool any_norm, any_dc, any_loud, apply; const DspScan* scan; const LoudScan* loud; bool any_eq = false; const EqScan* eqs = nullptr;
     bool any_open = false;   // a row is open: the summaries cover every tile of the longest window
+    bool gain_only = false;  // the loudness rows' gain with its 1 / peak ceiling and nothing else: k_dsp_peak and k_loud_*, no sample is rewritten (level_launch)
 };
 // rows_dev: device copy of the n rows; max_tiles: the most tiles a row's window has (a one-shot row: ceil(n / kDspTile))
 void launch_dsp(const DspRow* rows_dev, int n, int max_tiles, const DspLaunch& p, hipStream_t stream);
@@ -448,6 +449,20 @@ struct JoinRow {
 static_assert(sizeof(JoinRow) == 48, "a turn of the join ring holds 256 of them");
 // rows_dev: device copy of the n rows; max_tiles: the largest ceil((gap + n + 3) / kJoinTile) of a row (three more: the destination's 16-byte grid)
 void launch_join(const JoinRow* rows_dev, int n, int max_tiles, hipStream_t stream);
+// The gain form (join.hip, k_join_gain; include/ptts.h ptts_part_opts): a row of a table in which some part has a volume.  The part's gain and
+// the gain of its predecessor's tail (seam rows whose prev is the predecessor's own buffer; a tail in the joined row is already scaled) are each
+// none, an immediate f32 that multiplies every sample, or a device word holding one -- a loudness row's gain as k_loud_gate left it (kernels.h
+// DspRow::loud + 1), which multiplies where it is not 1.  A table without a gain goes to k_join
+enum JoinGainFlags : int32_t { JOIN_GAIN_IMM = 1, JOIN_GAIN_WORD = 2, JOIN_PREV_IMM = 4, JOIN_PREV_WORD = 8 };
+struct JoinGainRow {
+    JoinRow r;
+    const float* gw;       // JOIN_GAIN_WORD: the part's gain (device)
+    const float* gw_prev;  // JOIN_PREV_WORD: the predecessor's
+    float g, g_prev;       // JOIN_GAIN_IMM, JOIN_PREV_IMM
+    int32_t flags, pad;
+};
+static_assert(sizeof(JoinGainRow) == 80, "a turn of the gain join's ring holds 256 of them");
+void launch_join_gain(const JoinGainRow* rows_dev, int n, int max_tiles, hipStream_t stream);
 
 // Silence control of the parts of a joined text (trim.hip, trim.h has the rule, trim.cpp the host statement): in front
 // of k_join, from one buffer into another.  k_trim_mark (every tile: its first and last loud index, what its inner pauses lose), k_trim_carry

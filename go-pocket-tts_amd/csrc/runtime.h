@@ -121,8 +121,9 @@ enum WorkSlot : size_t {
     WORK_FORMANT_COEFFS = 39,    // parts_launch, rows that keep their formants: the frames' coefficients, [K][24] a row, one row behind the other
     WORK_FORMANT_RESIDUAL = 40,  // ... their residuals, what k_pitch_resample reads for them
     WORK_FORMANT_SHIFTED = 41,   // ... and their resampled residuals, what k_formant_shape reads
+    WORK_PART_LEVEL = 42,        // level_launch: the peak words and loudness blocks of the parts with a `level`; until the k_join_gain launch that reads their gain words has run (stream order)
 };
-constexpr size_t kWorkSlots = 42;   // one past the largest value above (14 and 21-23 have no holder and stay empty DevBufs)
+constexpr size_t kWorkSlots = 43;   // one past the largest value above (14 and 21-23 have no holder and stay empty DevBufs)
 
 // ---- rate and format conversion of delivered audio (resample.cpp; k_resample in resample.hip) ----
 constexpr int kNativeRate = 24000;            // the decoder's rate: requests at 0 / 24000 in f32 or PCM16 are delivered as before, without k_resample
@@ -194,12 +195,14 @@ struct Model {
     RowRing<LimRow, kLimMaxDesigns * kLimScanBytes> lim_ring;   // the limiter kernels', likewise
     RowRing<DeRow, kDeMaxDesigns * kDeScanBytes> de_ring;       // the de-esser kernels', likewise
     RowRing<JoinRow> join_ring;     // k_join's (join_launch, dsp_device.cpp)
+    RowRing<JoinGainRow> join_gain_ring;   // k_join_gain's (join_gain_launch, dsp_device.cpp)
     RowRing<TrimRow, kTrimMaxDesigns * kTrimScanBytes> trim_ring;   // the trim kernels', a table's designs behind its rows (parts_launch, dsp_device.cpp)
     RowRing<TempoRow, kTempoMaxDesigns * kTempoScanBytes> tempo_ring;   // the tempo kernels', likewise (parts_launch, dsp_device.cpp)
     RowRing<PitchRow, kPitchMaxDesigns * kPitchScanBytes> pitch_ring;   // k_pitch_resample's, likewise (parts_launch, dsp_device.cpp)
     std::unique_ptr<UploadedTable> pitch_image;   // ... and its table, from the first call that names a pitch on
     RowRing<FormantRow> formant_ring;          // the formant kernels' (parts_launch, dsp_device.cpp)
     std::unique_ptr<UploadedTable> formant_tables;   // ... and their float64 tables (formant.h formant_tables), uploaded the same way on first use
+    PinnedBuf part_gains;           // generate_joined with a list: the parts' gains, [n] floats, where the levels' words are copied to (read under Model::mu, behind a stream wait)
     PinnedBuf trim_info;            // parts_launch: the ptts_trim_info records of its rows with a trim, grown to their count (read under Model::mu, behind a stream wait)
     RowRing<DspRow, kDspMaxEq * kDspEqBytes> dsp_ring;   // the DSP kernels', a table's equalisers behind its rows (dsp_device.cpp)
     int fc_inject = 0;   // test hook: the next k_flow_cluster launch (plain launches) runs with FlowClusterArgs::inject = this, once
@@ -510,12 +513,32 @@ std::string request_error(const Desc& d, const ptts_request& q);   // empty: the
 // row and the egress of one row into *out.  parts: [n] or null.  Throws for a refusal (nothing launched) and for a failed chunk
 // so (include/ptts.h ptts_generate_joined_streamed; null: ptts_generate_joined): the first group's size, and with a pcm_callback the chain runs
 // window after window behind each group's k_join (DspJob's windows) and the audio that is final is handed over from a host function
-void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts);
+// list (include/ptts.h ptts_generate_joined_parts; null: one setting for the whole call): one ptts_part_opts per part -- its stages, its volume and the
+// seam behind it -- and where the parts' gains go ([n] or null)
+struct JoinPartsList { const ptts_part_opts* po; float* gains; };
+void generate_joined(Model& m, const ptts_request* reqs, int n, const ptts_join_opts& o, const ptts_join_stream_opts* so, ptts_result* out, ptts_join_part* parts,
+                     const JoinPartsList* list = nullptr);
 // k_join over a list of rows on s, one launch per RowRing::kRows rows
 void join_launch(Model& m, const std::vector<JoinRow>& rows, hipStream_t s);
 // ptts_join_rows: the parts packed into one device buffer with the joined row behind them, uploaded, join_launch, the joined row back, one wait.
 // Takes Model::mu.  The lengths are planned (join_plan) and out holds the joined length
 void join_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinLens& l, float* out);
+// Per-part options (include/ptts.h ptts_part_opts; join.h).  A part's volume on the device: none, a fixed gain, or a level whose gain the loudness
+// rows' measuring kernels leave in a device word (level_launch)
+struct PartGain { bool fixed = false; float g = 1.0f; const float* word = nullptr; };
+// the measuring launches of the loudness rows (k_dsp_peak, k_loud_summary .. k_loud_gate) over device rows x[i][0, n[i]) with target power
+// target[i], on s: nothing is rewritten.  words[i] receives where row i's f32 gain lies (WORK_PART_LEVEL, valid until the model's next level_launch)
+void level_launch(Model& m, const std::vector<const float*>& x, const std::vector<int64_t>& n, const std::vector<double>& target, std::vector<const float*>& words,
+                  hipStream_t s);
+// k_join_gain over a list of rows on s, one launch per RowRing::kRows rows; a table of the list in which no row has a flag goes to k_join
+void join_gain_launch(Model& m, const std::vector<JoinGainRow>& rows, hipStream_t s);
+// a JoinRow with its gains: mine the part's, prev (null: none, or a tail that lies in the joined row and is already scaled) its predecessor's
+JoinGainRow join_gain_row(const JoinRow& r, const PartGain& mine, const PartGain* prev);
+// the parts' volumes on device rows x[i][0, n[i]): the fixed gains as they are, the levels' words from one level_launch over the rows that have one
+std::vector<PartGain> part_gains_launch(Model& m, const std::vector<const float*>& x, const std::vector<int64_t>& n, const std::vector<PartVolume>& vol, hipStream_t s);
+// ptts_join_parts_rows: join_rows_device with the seams of the list and the parts' volumes; gains (optional, [rows]) receives the gains applied
+void join_parts_rows_device(Model& m, const float* const* in, const int64_t* n, int32_t rows, const JoinSeams& seams, const std::vector<PartVolume>& vol, float* out,
+                            float* gains);
 // What one part of a joined text gets in front of the join (and one row of ptts_trim_rows, ptts_tempo_rows, ptts_pitch_rows), resolved: the trim,
 // then the resampling step of the pitch (p is not 1000), then the tempo (behind a pitch it carries the effective speed E, pitch.h pitch_steps).
 // Null: the step is not run.  formant (with a pitch alone): the resampling step runs on the row's residual, between k_formant_whiten and k_formant_shape

@@ -183,6 +183,29 @@ class JoinStreamOpts(C.Structure):   # ptts_join_stream_opts
         self._cb = pcm_callback   # (borrowed by the struct: kept alive with it)
 
 
+class PartOpts(C.Structure):   # ptts_part_opts
+    """One part's prosody in a joined call (ptts_part_opts): its trim, pitch, formant option and tempo (a TrimOpts, PitchOpts, FormantOpts, TempoOpts;
+    None: none), its volume -- gain_db -60 .. +24 (0: none) or level, a loudness target in 0.01 LUFS (0: off), not both -- and the seam BEHIND it:
+    gap_ms / crossfade_ms, both negative (the default) for the pair of the JoinOpts.  size: sizeof as the caller compiled it (None: this mirror's)."""
+    _fields_ = [("size", C.c_uint32), ("level", C.c_int32), ("trim", C.POINTER(TrimOpts)), ("pitch", C.POINTER(PitchOpts)), ("formant", C.POINTER(FormantOpts)),
+                ("tempo", C.POINTER(TempoOpts)), ("gain_db", C.c_double), ("gap_ms", C.c_double), ("crossfade_ms", C.c_double)]
+
+    def __init__(self, gain_db: float = 0.0, level: int = 0, gap_ms: float = -1.0, crossfade_ms: float = -1.0, trim: Optional[TrimOpts] = None,
+                 pitch: Optional[PitchOpts] = None, formant: Optional[FormantOpts] = None, tempo: Optional[TempoOpts] = None, size: Optional[int] = None):
+        ptr = lambda v: C.pointer(v) if v is not None else None  # noqa: E731
+        super().__init__(C.sizeof(PartOpts) if size is None else int(size), int(level), ptr(trim), ptr(pitch), ptr(formant), ptr(tempo), float(gain_db),
+                         float(gap_ms), float(crossfade_ms))
+        self._borrowed = (trim, pitch, formant, tempo)   # (borrowed by the struct: kept alive with it)
+
+
+def _part_list(parts_opts):
+    """A sequence of PartOpts as the contiguous list the C entry points take (the elements' borrowed structs stay alive with the sequence)."""
+    arr = (PartOpts * max(len(parts_opts), 1))()
+    for i, p in enumerate(parts_opts):
+        C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(PartOpts))
+    return arr
+
+
 class JoinPart(C.Structure):   # ptts_join_part: one chunk of a joined call, offset and n_samples at 24 kHz in the joined audio
     _fields_ = [("offset", C.c_int64), ("n_samples", C.c_int64), ("n_frames", C.c_int32), ("eos_step", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -254,6 +277,7 @@ ABI_SYMBOLS = [
     "ptts_dsp_ext_set_limiter", "ptts_limit_apply", "ptts_limit_rows",
     "ptts_dsp_ext_set_deesser", "ptts_deess_apply", "ptts_deess_band", "ptts_deess_rows",
     "ptts_join_length", "ptts_join", "ptts_join_rows", "ptts_generate_joined", "ptts_generate_joined_streamed", "ptts_join_stream_ready",
+    "ptts_join_parts_length", "ptts_join_parts", "ptts_join_parts_rows", "ptts_join_parts_stream_ready", "ptts_generate_joined_parts",
     "ptts_trim_plan", "ptts_trim_apply", "ptts_trim_rows", "ptts_dsp_ext_set_trim",
     "ptts_tempo_length", "ptts_tempo_plan", "ptts_tempo_apply", "ptts_tempo_rows", "ptts_dsp_ext_set_tempo",
     "ptts_pitch_speed", "ptts_pitch_resample_length", "ptts_pitch_resample", "ptts_pitch_length", "ptts_pitch_apply", "ptts_pitch_table",
@@ -384,6 +408,14 @@ def lib():
                                                     C.POINTER(JoinPart)]
         L.ptts_join_stream_ready.restype = C.c_int64
         L.ptts_join_stream_ready.argtypes = [C.POINTER(JoinOpts), C.c_int64]
+        L.ptts_join_parts_length.restype = C.c_int64
+        L.ptts_join_parts_length.argtypes = [_IP, C.c_int32, C.POINTER(JoinOpts), C.POINTER(PartOpts), _IP]
+        L.ptts_join_parts.argtypes = [C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), C.POINTER(PartOpts), _FP, _FP]
+        L.ptts_join_parts_rows.argtypes = [C.c_void_p, C.POINTER(_FP), _IP, C.c_int32, C.POINTER(JoinOpts), C.POINTER(PartOpts), _FP, _FP]
+        L.ptts_join_parts_stream_ready.restype = C.c_int64
+        L.ptts_join_parts_stream_ready.argtypes = [C.POINTER(JoinOpts), C.POINTER(PartOpts), C.c_int64]
+        L.ptts_generate_joined_parts.argtypes = [C.c_void_p, C.POINTER(_Request), C.c_int32, C.POINTER(JoinOpts), C.POINTER(PartOpts), C.POINTER(JoinStreamOpts),
+                                                 C.POINTER(_Result), C.POINTER(JoinPart), _FP]
         L.ptts_trim_plan.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, C.POINTER(TrimInfo)]
         L.ptts_trim_apply.argtypes = [C.POINTER(TrimOpts), _FP, C.c_int64, _FP, C.POINTER(TrimInfo)]
         L.ptts_trim_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TrimOpts)), C.POINTER(_FP), _IP, C.c_int32, C.POINTER(_FP), C.POINTER(TrimInfo)]
@@ -618,10 +650,12 @@ class GenerateResult:
 @dataclass
 class JoinedResult:
     """One joined call's result: the whole text's audio in the join options' egress format; n_frames summed over the chunks; parts: a JoinPart per
-    chunk (offset and n_samples at 24 kHz in the joined audio, in front of the egress; n_frames; eos_step; status)."""
+    chunk (offset and n_samples at 24 kHz in the joined audio, in front of the egress; n_frames; eos_step; status); gains: a call with a list of
+    PartOpts: the f32 gain applied to every part (None otherwise)."""
     pcm: np.ndarray
     n_frames: int
     parts: list
+    gains: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -1008,6 +1042,18 @@ class Model:
         _check(lib().ptts_join_rows(self.h, pp, _ip(ns), n, C.byref(o), _fp(out)))
         return out[:join_length(ns[:n], o)]
 
+    def join_parts_rows(self, parts, parts_opts, join: Optional[JoinOpts] = None, gains: bool = False):
+        """ptts_join_parts_rows: join_parts() on the device, by the kernels a joined call with a list runs: one upload, the loudness rows' measuring
+        kernels for the levels, k_join_gain (k_join for a table without a gain), one download.  gains: also the f32 gain of every part."""
+        rows, n, pp, ns = _join_in(parts)
+        o = join if join is not None else JoinOpts()
+        po = _part_list(parts_opts)
+        total = join_parts_length(ns[:n], parts_opts, o)
+        out = np.empty(max(total, 1), np.float32)
+        g = np.ones(max(n, 1), np.float32)
+        _check(lib().ptts_join_parts_rows(self.h, pp, _ip(ns), n, C.byref(o), po, _fp(out), _fp(g)))
+        return (out[:total], g[:n]) if gains else out[:total]
+
     def pcm_encode(self, x, pcm_format: int) -> np.ndarray:
         """ptts_pcm_encode: the device egress conversion of 24 kHz f32 samples into PCM_F32 / PCM_S16 / PCM_ULAW / PCM_ALAW."""
         x = _f32(x).reshape(-1)
@@ -1157,13 +1203,17 @@ class Model:
 
 
     def generate_joined(self, token_lists: Sequence[Sequence[int]], cfgs: Sequence[RuntimeGenerateConfig], join: Optional[JoinOpts] = None,
-                        pcm_callback=None, first_group: Optional[int] = None, stream: Optional[JoinStreamOpts] = None) -> JoinedResult:
+                        pcm_callback=None, first_group: Optional[int] = None, stream: Optional[JoinStreamOpts] = None,
+                        parts: Optional[Sequence[PartOpts]] = None) -> JoinedResult:
         """ptts_generate_joined: the chunks of one text, generated as generate_batch generates them, joined on the device (gap or crossfade), the
         chain of `join` run once over the joined audio, one egress.  The cfgs carry no post-processing, rate or format of their own.  A failed call
         raises PttsError with the chunks' records in its `parts`.
         pcm_callback(offset, samples), first_group or stream (a JoinStreamOpts as it is) make it ptts_generate_joined_streamed: the audio is handed
-        over group by group, from a library thread, while the later groups run; offsets count samples of the egress, `samples` is a copy in its format."""
+        over group by group, from a library thread, while the later groups run; offsets count samples of the egress, `samples` is a copy in its format.
+        parts (one PartOpts per chunk) makes it ptts_generate_joined_parts: each part's own trim, pitch, tempo and volume and the seam behind it; the
+        result then carries the parts' gains (JoinedResult.gains)."""
         n = len(token_lists)
+        part_opts = parts
         reqs = (_Request * max(n, 1))()
         parts = (JoinPart * max(n, 1))()
         res = _Result()
@@ -1177,7 +1227,14 @@ class Model:
                 dt = np.dtype(_PCM_DTYPES.get(int(o.pcm_format), "<f4"))
                 cb = _PCM_CB(lambda _u, off, cnt, ptr: pcm_callback(int(off), np.frombuffer(C.string_at(ptr, int(cnt) * dt.itemsize), dtype=dt)))
             stream = JoinStreamOpts(first_group or 0, cb)
-        if stream is not None:
+        gains = None
+        if part_opts is not None:
+            if len(part_opts) != n:
+                raise PttsError(PTTS_EINVAL, "generate_joined: parts holds %d PartOpts for %d chunks" % (len(part_opts), n))
+            gains = np.ones(max(n, 1), np.float32)
+            rc = lib().ptts_generate_joined_parts(self.h, reqs, n, C.byref(o), _part_list(part_opts), C.byref(stream) if stream is not None else None,
+                                                  C.byref(res), parts, _fp(gains))
+        elif stream is not None:
             rc = lib().ptts_generate_joined_streamed(self.h, reqs, n, C.byref(o), C.byref(stream), C.byref(res), parts)
         else:
             rc = lib().ptts_generate_joined(self.h, reqs, n, C.byref(o), C.byref(res), parts)
@@ -1196,7 +1253,10 @@ class Model:
         else:
             lib().ptts_free_result(C.byref(res))
             pcm = np.zeros(0, _PCM_DTYPES[fmt])
-        return JoinedResult(pcm, int(res.n_frames), records)
+        out = JoinedResult(pcm, int(res.n_frames), records)
+        if gains is not None:
+            out.gains = gains[:n]
+        return out
 
 
 class DeviceVoice:
@@ -2204,6 +2264,38 @@ def join_stream_ready(join: Optional[JoinOpts], joined: int) -> int:
     if rc < 0:
         _check(-rc)
     return rc
+
+
+def join_parts_length(lengths, parts_opts, join: Optional[JoinOpts] = None, offsets: bool = False):
+    """ptts_join_parts_length: join_length with the seam behind every part taken from its PartOpts.  Host."""
+    ns = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    offs = np.zeros(max(ns.size, 1), np.int64)
+    o = join if join is not None else JoinOpts()
+    total = int(lib().ptts_join_parts_length(_ip(ns) if ns.size else None, ns.size, C.byref(o), _part_list(parts_opts), _ip(offs)))
+    if total < 0:
+        _check(-total)
+    return (total, offs[:ns.size]) if offsets else total
+
+
+def join_parts_stream_ready(join: Optional[JoinOpts], last: PartOpts, joined: int) -> int:
+    """ptts_join_parts_stream_ready: join_stream_ready with the crossfade of the seam behind the part `last` describes.  No GPU."""
+    o = join if join is not None else JoinOpts()
+    rc = int(lib().ptts_join_parts_stream_ready(C.byref(o), C.byref(last), int(joined)))
+    if rc < 0:
+        _check(-rc)
+    return rc
+
+
+def join_parts(parts, parts_opts, join: Optional[JoinOpts] = None, gains: bool = False):
+    """ptts_join_parts: the parts (mono f32 at 24 kHz, in order), each at its PartOpts' volume, as one utterance with the seam of its PartOpts behind
+    every part.  gains: also the f32 gain of every part.  Host: the statement of what Model.join_parts_rows and a joined call with a list compute."""
+    rows, n, pp, ns = _join_in(parts)
+    o = join if join is not None else JoinOpts()
+    total = join_parts_length(ns[:n], parts_opts, o)
+    out = np.empty(max(total, 1), np.float32)
+    g = np.ones(max(n, 1), np.float32)
+    _check(lib().ptts_join_parts(pp, _ip(ns), n, C.byref(o), _part_list(parts_opts), _fp(out), _fp(g)))
+    return (out[:total], g[:n]) if gains else out[:total]
 
 
 def join(parts, join: Optional[JoinOpts] = None) -> np.ndarray:

@@ -814,6 +814,55 @@ int  ptts_formant_rows(ptts_model* m, const ptts_formant_opts* const* f /* [rows
                        int64_t* n_out /* [rows] */);
 int  ptts_dsp_ext_set_formant(ptts_dsp_ext* e, const ptts_formant_opts* f);
 
+/* Per-part prosody of a joined text: a list of one ptts_part_opts per part states that part's trim, pitch (with or
+ * without its formants), tempo and volume, and the seam BEHIND it -- a longer break after a heading, one sentence slower, a quote at another
+ * pitch, an aside quieter.  The order of such a call: trim -> pitch resample (formants kept where asked) -> tempo at the effective speed ->
+ * volume -> join -> the chain of `dsp` / `loudness` once -> egress; the pair (tempo, pitch) is resolved to E per part before anything
+ * launches, and a refusal names the part index and both values.
+ *   The list.  po[0 .. rows); every element carries the same `size`, which is also the distance in bytes from one element to the next (the
+ *     rules of ptts_dsp_ext_opts.size apply to each element).  The structs a part's pointers name are borrowed for the call.
+ *   Seams.  For the seam behind part i: gap_ms and crossfade_ms both negative -- the pair of ptts_join_opts; otherwise a negative field reads
+ *     as 0, each is a value from 0 to 2000 and at most one is above 0; NaN is refused.  The last part's fields are range-checked and otherwise
+ *     unused.  G and K of the join's statement become G_i and K_i = min(K_i, n_i / 2, n_(i+1) / 2) of the seam behind part i.
+ *   Volume.  gain_db != 0: every sample of the part becomes the f32 product x * g, g = (float)pow(10, gain_db / 20), rounded once, nothing
+ *     fused.  level != 0: the part is what ptts_loudness_normalize(part, n, level / 100.0, NULL) makes of it as the tempo left it: its gain
+ *     includes the 1 / peak ceiling and is 1 (the samples stay as they are) when no block passes the gates.  Neither: the part's bits move as
+ *     ptts_join moves them.  In a crossfade a and b of the formula are the scaled samples.
+ * ptts_join_parts_length: ptts_join_length with per-seam G_i, K_i.  Reads only size, gap_ms and crossfade_ms of each element.  Host.
+ * ptts_join_parts: the statement of volume plus join.  Reads only size, level, gain_db, gap_ms and crossfade_ms of each element; gains
+ *     (optional, [rows]) receives the f32 gain applied to part i, 1.0f for none.  Host.
+ * ptts_join_parts_rows: the same on the device, by the kernels the call runs (k_join_gain where a part of the table has a gain, k_join where
+ *     none has; for `level` the measuring kernels of the loudness rows, whose gain word the join reads), shaped like ptts_join_rows.  It gives
+ *     ptts_join_parts' bits.
+ * ptts_join_parts_stream_ready: ptts_join_stream_ready with K taken from the seam behind the part `last` describes.
+ * ptts_generate_joined_parts: ptts_generate_joined_streamed (so NULL: not streamed, every group holds max_batch parts) with the list po [n],
+ *     required.  parts[i].offset and .n_samples count the final audio; gains (optional, [n]) receives the parts' gains.  The bound on the
+ *     joined length takes, per part, the largest of its step budget, its resampled and its final length, plus the per-seam gaps; 2^31 is
+ *     refused.  In a streamed call K of P_g is the crossfade resolved for the seam behind group g's last part.
+ *   PTTS_EINVAL, nothing launched, naming the field and the part index: any bad field; level together with gain_db; formant without pitch; a
+ *     dsp->ext handle that itself carries a trim, pitch, formant or tempo ("join: parts: ... belongs in the list"); and everything
+ *     ptts_generate_joined_streamed refuses, in its own words. */
+typedef struct ptts_part_opts {
+    uint32_t size;                       /* sizeof(ptts_part_opts) as the caller compiled it; the rules of ptts_dsp_ext_opts.size */
+    int32_t  level;                      /* 0: off; else this part's loudness target in 0.01 LUFS, -7000 .. -100; not with gain_db != 0 */
+    const ptts_trim_opts*    trim;       /* NULL: this part is not trimmed */
+    const ptts_pitch_opts*   pitch;      /* NULL: none */
+    const ptts_formant_opts* formant;    /* NULL: none; needs pitch, its own range rules apply */
+    const ptts_tempo_opts*   tempo;      /* NULL: none */
+    double   gain_db;                    /* -60 .. +24, finite; 0: none */
+    double   gap_ms;                     /* the seam BEHIND this part */
+    double   crossfade_ms;
+} ptts_part_opts;                        /* 64 bytes */
+int64_t ptts_join_parts_length(const int64_t* n, int32_t rows, const ptts_join_opts* o, const ptts_part_opts* po, int64_t* offsets /* optional [rows] */);
+int  ptts_join_parts(const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* o, const ptts_part_opts* po, float* out,
+                     float* gains /* optional [rows] */);
+int  ptts_join_parts_rows(ptts_model* m, const float* const* in, const int64_t* n, int32_t rows, const ptts_join_opts* o, const ptts_part_opts* po,
+                          float* out, float* gains /* optional [rows] */);
+int64_t ptts_join_parts_stream_ready(const ptts_join_opts* o, const ptts_part_opts* last, int64_t joined);
+int  ptts_generate_joined_parts(ptts_model* m, const ptts_request* reqs, int32_t n, const ptts_join_opts* o, const ptts_part_opts* po /* [n] */,
+                                const ptts_join_stream_opts* so /* NULL: not streamed */, ptts_result* out, ptts_join_part* parts /* [n], optional */,
+                                float* gains /* optional [n] */);
+
 /* ---- Text front end (internal/text/prepare.go, chunk.go) -------------------------------------------------
  * What Synthesize does before it calls the runtime: normalise the text, cut it into sentence-based chunks of <= max_tokens
  * tokens, and derive each chunk's step budget and EOS tail.  The SentencePiece encoder is the caller's. */
@@ -1074,7 +1123,9 @@ int  ptts_wav_header(uint8_t* out, int32_t cap, int32_t sample_rate, int32_t pcm
  * ptts_pitch_apply, ptts_pitch_table, ptts_pitch_rows, ptts_dsp_ext_set_pitch;
  * the new struct ptts_formant_opts, likewise, with ptts_formant_frames, ptts_formant_analyse, ptts_formant_whiten, ptts_formant_shape,
  * ptts_formant_apply, ptts_formant_rows, ptts_dsp_ext_set_formant;
- * the new struct ptts_deesser_opts, likewise, with ptts_dsp_ext_set_deesser, ptts_deess_apply, ptts_deess_band, ptts_deess_rows */
+ * the new struct ptts_deesser_opts, likewise, with ptts_dsp_ext_set_deesser, ptts_deess_apply, ptts_deess_band, ptts_deess_rows;
+ * the new struct ptts_part_opts, likewise, with ptts_join_parts_length, ptts_join_parts, ptts_join_parts_rows, ptts_join_parts_stream_ready,
+ * ptts_generate_joined_parts */
 const char* ptts_version(void);
 
 /* Test and measurement hooks (launch census, in-kernel stamps, micro-benchmarks, staged observation points of the decoder, the fault injection of
