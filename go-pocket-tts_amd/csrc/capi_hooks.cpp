@@ -536,52 +536,95 @@ int ptts_debug_gemm(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t var
     });
 }
 
-int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t splitk, const float* x, const float* planes, int32_t psplit, const float* pbias,
-                           const float* ln_w, const float* ln_b, float eps, const float* W, const float* bias, const float* R, int32_t out_planes, float* out,
-                           float* x_out) {
+// The AR step's 128+-row linears (csrc/tall.hip) on host operands: ONE launch of k_rowprep, ONE of k_tall, or the two chained.  Neither kernel bounds a load or
+// a store by a buffer size, so every leading dimension and stride is checked against the buffers allocated here (`rows` rows each) before anything is uploaded;
+// the widths themselves (D = 512 / 1024, K % 128, N % 4) are the predicates' to refuse.
+int ptts_debug_tall(const ptts_tall_args* pa) {
     return guard([&] {
-        require_device();
-        if (!x || !W || !out || M <= 0 || N <= 0 || K <= 0 || K % 128) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: bad arguments");
-        const size_t mk = (size_t)M * K, mn = (size_t)M * N;
-        const int S = std::max(1, (int)splitk);
-        // the weights in the step kernels' fragment order, rounded to bf16: the loader's packer (K % 128 == 0, so its super-steps are whole)
-        std::vector<uint8_t> wt(step_tiled_bytes((size_t)N, (size_t)K, 2));
-        pack_step_tiled(W, (size_t)N, (size_t)K, true, wt.data());
-        Stage st;
-        Tmp dAh(mk * 2), dAl(mk * 2), dOut((size_t)S * mn * 4), dCh(mn * 2), dCl(mn * 2), dXo(mk * 4);
-        const uint8_t* dW = st.in(wt.data(), wt.size());
-        const float *dB = st.in(bias, (size_t)N), *dR = st.in(R, mn);
-        if (ln_w) {   // the rows through k_rowprep: split-K planes + residual -> LayerNorm -> bf16 planes
-            PrepArgs pa;
-            pa.x = st.in(x, mk); pa.ldx = K; pa.ln_w = st.in(ln_w, (size_t)K); pa.ln_b = st.in(ln_b, (size_t)K); pa.eps = eps;
-            if (planes && psplit > 0) {
-                pa.pend = PendingSum{st.in(planes, (size_t)psplit * mk), psplit, (int64_t)mk, st.in(pbias, (size_t)K)};
-                pa.x_out = dXo.as<float>();
-            }
-            pa.yh = dAh.as<uint16_t>(); pa.yl = dAl.as<uint16_t>(); pa.ldy = K; pa.M = M; pa.D = K;
-            if (!rowprep_supported(pa)) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: rows not taken by k_rowprep");
-            launch_rowprep(pa, nullptr);
-        } else {      // the rows as they are: split on the host the way the kernels split (hi = bf16(x), lo = bf16(x - hi))
-            std::vector<uint16_t> hi(mk), lo(mk);
-            for (size_t i = 0; i < mk; i++) { hi[i] = f32_to_bf16_rne(x[i]); lo[i] = f32_to_bf16_rne(x[i] - bf16_to_f32(hi[i])); }
-            up(dAh.p, hi.data(), mk * 2); up(dAl.p, lo.data(), mk * 2);
+        const char* const me = "ptts_debug_tall";
+        if (!pa) throw Error(PTTS_EINVAL, strfmt("%s: null argument", me));
+        const ptts_tall_args& t = *pa;
+        put_str(t.launched, t.launched_cap, "");
+        const bool prep = t.op == PTTS_TALL_ROWPREP || t.op == PTTS_TALL_BOTH, prod = t.op == PTTS_TALL_TALL || t.op == PTTS_TALL_BOTH;
+        if (!prep && !prod) throw Error(PTTS_EINVAL, strfmt("%s: unknown op %d", me, t.op));
+        if (!t.x || t.M < 1 || t.rows < t.M || t.rows > 1024 || t.K < 1 || t.K > 8192)
+            throw Error(PTTS_EINVAL, strfmt("%s: bad arguments (x, 1 <= M <= rows <= 1024, 1 <= K <= 8192)", me));
+        const int M = t.M, K = t.K, N = t.N, S = t.splitk;
+        const size_t rows = (size_t)t.rows;
+        if (prep) {
+            if (t.ldx < K || t.ldy < K) throw Error(PTTS_EINVAL, strfmt("%s: ldx %lld or ldy %lld below the row width %d", me, (long long)t.ldx, (long long)t.ldy, K));
+            if (t.psplit < 0 || t.psplit > 16 || (t.psplit > 0) != (t.planes != nullptr)) throw Error(PTTS_EINVAL, strfmt("%s: psplit %d does not fit planes", me, t.psplit));
+            if (t.pbias && !t.planes) throw Error(PTTS_EINVAL, strfmt("%s: pbias without planes (k_rowprep would ignore it)", me));
+            if (t.psplit > 0 && t.pstride < (int64_t)rows * K) throw Error(PTTS_EINVAL, strfmt("%s: pstride %lld below rows K = %lld", me, (long long)t.pstride, (long long)rows * K));
         }
-        TallArgs t;
-        t.ah = dAh.as<uint16_t>(); t.al = dAl.as<uint16_t>(); t.lda = K; t.Wt = dW; t.bias = dB;
-        t.R = dR; t.ldr = N; t.M = M; t.N = N; t.K = K; t.epi = epi;
-        if (S > 1) { t.splitk = S; t.partial = dOut.as<float>(); t.zstride = (int64_t)mn; }
-        else if (out_planes) { t.ch = dCh.as<uint16_t>(); t.cl = dCl.as<uint16_t>(); t.ldp = N; }
-        else { t.C = dOut.as<float>(); t.ldc = N; }
-        if (!tall_supported(t)) throw Error(PTTS_EINVAL, "ptts_debug_tall_linear: shape not taken by k_tall");
-        PTTS_HIP(hipMemset(dOut.p, 0xff, (size_t)S * mn * 4));   // (NaN where the kernel stores nothing)
-        launch_tall(t, nullptr);
+        if (prod) {
+            if (!t.W || N < 1 || N > 8192) throw Error(PTTS_EINVAL, strfmt("%s: bad arguments (W, 1 <= N <= 8192)", me));
+            if (t.form != 0 && t.form != 32 && t.form != 64) throw Error(PTTS_EINVAL, strfmt("%s: form %d: k_tall has blocks of 32 and 64 rows", me, t.form));
+            if (S < 1 || S > 16) throw Error(PTTS_EINVAL, strfmt("%s: splitk %d outside [1, 16]", me, S));
+            if (prep ? t.lda != t.ldy : t.lda < K) throw Error(PTTS_EINVAL, strfmt("%s: lda %lld (at least K; chained: ldy)", me, (long long)t.lda));
+            if (t.R && t.ldr < N) throw Error(PTTS_EINVAL, strfmt("%s: ldr %lld below N", me, (long long)t.ldr));
+            if ((t.ch != nullptr) != (t.cl != nullptr) || (t.ch && t.ldp < N)) throw Error(PTTS_EINVAL, strfmt("%s: ch / cl / ldp %lld do not fit", me, (long long)t.ldp));
+            if ((S > 1 || !t.ch) && !t.out) throw Error(PTTS_EINVAL, strfmt("%s: no result buffer", me));
+            if (S > 1 && t.zstride < (int64_t)rows * N) throw Error(PTTS_EINVAL, strfmt("%s: zstride %lld below rows N = %lld", me, (long long)t.zstride, (long long)rows * N));
+            if (S == 1 && !t.ch && t.ldc < N) throw Error(PTTS_EINVAL, strfmt("%s: ldc %lld below N", me, (long long)t.ldc));
+        }
+        require_device();
+        Stage st;
+        PrepArgs p;
+        TallArgs g;
+        uint16_t *dYh = nullptr, *dYl = nullptr, *dCh = nullptr, *dCl = nullptr;
+        float *dXo = nullptr, *dYo = nullptr, *dOut = nullptr;
+        size_t out_elems = 0;
+        int form = 0, grid[3] = {rowprep_blocks(M), 1, 1};
+        if (prep) {
+            dYh = st.out<uint16_t>(rows * t.ldy); dYl = st.out<uint16_t>(rows * t.ldy);
+            dXo = st.out(rows * K); dYo = st.out(rows * K);
+            p.x = st.in(t.x, rows * t.ldx); p.ldx = t.ldx;
+            if (t.psplit > 0) p.pend = PendingSum{st.in(t.planes, (size_t)t.psplit * t.pstride), t.psplit, t.pstride, st.in(t.pbias, (size_t)K)};
+            p.x_out = t.want_x_out ? dXo : nullptr; p.y_out = t.want_y_out ? dYo : nullptr;
+            p.ln_w = st.in(t.ln_w, (size_t)K); p.ln_b = st.in(t.ln_b, (size_t)K); p.eps = t.eps;
+            p.yh = dYh; p.yl = dYl; p.ldy = t.ldy; p.M = M; p.D = K;
+            if (!rowprep_supported(p)) throw Error(PTTS_EINVAL, strfmt("%s: refused by rowprep_supported", me));
+        }
+        if (prod) {
+            // the weights in the step kernels' fragment order, rounded to bf16: the loader's packer
+            std::vector<uint8_t> wt(step_tiled_bytes((size_t)N, (size_t)K, 2));
+            pack_step_tiled(t.W, (size_t)N, (size_t)K, true, wt.data());
+            if (prep) { g.ah = dYh; g.al = dYl; }
+            else {   // the rows as they are: split on the host the way the kernels split (hi = bf16(x), lo = bf16(x - hi))
+                const size_t n = rows * t.lda;
+                std::vector<uint16_t> hi(n), lo(n);
+                for (size_t i = 0; i < n; i++) { hi[i] = f32_to_bf16_rne(t.x[i]); lo[i] = f32_to_bf16_rne(t.x[i] - bf16_to_f32(hi[i])); }
+                g.ah = st.in(hi.data(), n); g.al = st.in(lo.data(), n);
+            }
+            g.lda = t.lda; g.Wt = st.in(wt.data(), wt.size()); g.bias = st.in(t.bias, (size_t)N);
+            if (t.R) { g.R = st.in(t.R, rows * t.ldr); g.ldr = t.ldr; }
+            g.M = M; g.N = N; g.K = K; g.epi = t.epi;
+            if (S > 1) { out_elems = (size_t)S * t.zstride; dOut = st.out(out_elems); g.splitk = S; g.partial = dOut; g.zstride = t.zstride; }
+            else if (!t.ch) { out_elems = rows * t.ldc; dOut = st.out(out_elems); g.C = dOut; g.ldc = t.ldc; }
+            if (t.ch) { dCh = st.out<uint16_t>(rows * t.ldp); dCl = st.out<uint16_t>(rows * t.ldp); g.ch = dCh; g.cl = dCl; g.ldp = t.ldp; }
+            if (!tall_supported(g)) throw Error(PTTS_EINVAL, strfmt("%s: refused by tall_supported", me));
+            form = t.form ? t.form : tall_rows(M);
+            tall_grid(g, form, grid);
+        }
+        LaunchScope launches;
+        launches.run([&] {
+            if (prep) launch_rowprep(p, nullptr);
+            if (prod) launch_tall_as(g, form, nullptr);
+        });
+        PTTS_HIP(hipGetLastError());
         PTTS_HIP(hipDeviceSynchronize());
-        if (S == 1 && out_planes) {
-            std::vector<uint16_t> hi(mn), lo(mn);
-            down(hi.data(), dCh.p, mn * 2); down(lo.data(), dCl.p, mn * 2);
-            for (size_t i = 0; i < mn; i++) out[i] = bf16_to_f32(hi[i]) + bf16_to_f32(lo[i]);
-        } else down(out, dOut.p, (size_t)S * mn * 4);
-        if (x_out && ln_w && planes && psplit > 0) down(x_out, dXo.p, mk * 4);
+        put_str(t.launched, t.launched_cap, launches.str());
+        if (t.form_out) *t.form_out = form;
+        if (t.grid) for (int i = 0; i < 3; i++) t.grid[i] = grid[i];
+        if (prep) {
+            if (t.x_out) down(t.x_out, dXo, rows * K * 4);
+            if (t.y_out) down(t.y_out, dYo, rows * K * 4);
+            if (t.yh) down(t.yh, dYh, rows * t.ldy * 2);
+            if (t.yl) down(t.yl, dYl, rows * t.ldy * 2);
+        }
+        if (dOut && t.out) down(t.out, dOut, out_elems * 4);
+        if (dCh) { down(t.ch, dCh, rows * t.ldp * 2); down(t.cl, dCl, rows * t.ldp * 2); }
     });
 }
 

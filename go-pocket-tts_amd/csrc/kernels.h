@@ -144,6 +144,9 @@ struct PrepArgs {   // x' = x + pend (the planes in order, then the bias) -> x_o
 static_assert(sizeof(PrepArgs) == 120 && offsetof(PrepArgs, x_out) == 48, "k_rowprep takes it by value: the layout stays");
 bool rowprep_supported(const PrepArgs& a);
 void launch_rowprep(const PrepArgs& a, hipStream_t stream);
+int rowprep_blocks(int M);           // its grid: one wave per row, four rows per block
+// splitk > 1 keeps k_skinny's convention: with R, plane 0 = R + (sums_0 + bias) and the other planes raw sums; without R every plane holds raw sums and a bias
+// is the consumer's business (PendingSum::bias) -- tall_supported refuses splitk > 1 with a bias and no R, which the kernel would drop in silence.
 struct TallArgs {   // C[M,N] = epi(A[M,K] * W[N,K]^T + bias), A = ah + al (bf16 planes), W the fragment-ordered bf16 copy (Linear::wt)
     const uint16_t* ah = nullptr; const uint16_t* al = nullptr; int64_t lda = 0;
     const void* Wt = nullptr; const float* bias = nullptr;
@@ -155,7 +158,12 @@ struct TallArgs {   // C[M,N] = epi(A[M,K] * W[N,K]^T + bias), A = ah + al (bf16
 };
 constexpr int kTallMinRows = 128;   // from this many rows the step's in_proj / linear1 / linear2 run on k_tall (below, k_skinny's one-block-per-CU shape wins)
 bool tall_supported(const TallArgs& a);
-void launch_tall(const TallArgs& a, hipStream_t stream);
+void launch_tall(const TallArgs& a, hipStream_t stream);   // = launch_tall_as(a, tall_rows(a.M))
+// its launch form: blocks of 32 or 64 rows x 64 columns x a K slice (tall_grid).  tall_rows is the only place that chooses for production (32 up to 128 rows, 64
+// above); launch_tall_as with the other form is for the kernel's test hook, any other `rows` is PTTS_EINVAL
+int tall_rows(int M);
+void tall_grid(const TallArgs& a, int rows, int grid[3]);
+void launch_tall_as(const TallArgs& a, int rows, hipStream_t stream);
 
 struct LnArgs {
     const float* x = nullptr; RowMap xmap;

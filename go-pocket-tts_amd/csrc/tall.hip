@@ -159,17 +159,27 @@ bool tall_supported(const TallArgs& a) {
     if (a.K % TL_KC || a.N % 4 || a.lda % 8 || !aligned16(a.ah) || !aligned16(a.al) || !aligned16(a.Wt)) return false;
     if (a.bias && !aligned16(a.bias)) return false;
     if (a.R && (a.ldr % 4 || !aligned16(a.R))) return false;
-    if (a.splitk > 1) return a.partial && aligned16(a.partial) && a.zstride % 4 == 0 && a.epi == EPI_NONE && !a.ch;
+    // split-K: plane 0 = R + (sums_0 + bias) with R, raw sums in every plane without -- a bias without R would be dropped in silence (the kernel adds it inside
+    // the residual branch only), so it is refused: without R the bias is the consumer's (PendingSum::bias)
+    if (a.splitk > 1) return a.partial && aligned16(a.partial) && a.zstride % 4 == 0 && a.epi == EPI_NONE && !a.ch && !(a.bias && !a.R);
     if (a.epi != EPI_NONE && a.epi != EPI_GELU && a.epi != EPI_RESADD) return false;
     if (a.epi == EPI_RESADD && !a.R) return false;
     if (a.ch) return a.cl && a.ldp % 4 == 0 && (reinterpret_cast<uintptr_t>(a.ch) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.cl) & 7) == 0;
     return a.C && a.ldc % 4 == 0 && aligned16(a.C);
 }
 
-void launch_tall(const TallArgs& a, hipStream_t stream) {
+int tall_rows(int M) { return M <= 128 ? 32 : 64; }
+
+void tall_grid(const TallArgs& a, int rows, int grid[3]) {
+    grid[0] = (a.N + TL_COLS - 1) / TL_COLS; grid[1] = (a.M + rows - 1) / rows; grid[2] = std::max(1, a.splitk);
+}
+
+void launch_tall_as(const TallArgs& a, int rows, hipStream_t stream) {
+    if (rows != 32 && rows != 64) throw Error(PTTS_EINVAL, strfmt("ptts-hip: internal: k_tall has blocks of 32 and 64 rows, not %d", rows));
     note_launch("k_tall");
-    const int rows = a.M <= 128 ? 32 : 64;
-    const dim3 grid((unsigned)((a.N + TL_COLS - 1) / TL_COLS), (unsigned)((a.M + rows - 1) / rows), (unsigned)std::max(1, a.splitk));
+    int g[3];
+    tall_grid(a, rows, g);
+    const dim3 grid((unsigned)g[0], (unsigned)g[1], (unsigned)g[2]);
     if (rows == 32) {
         if (a.ch) hipLaunchKernelGGL((k_tall<true, 32>), grid, dim3(512), 0, stream, a);
         else hipLaunchKernelGGL((k_tall<false, 32>), grid, dim3(512), 0, stream, a);
@@ -179,9 +189,12 @@ void launch_tall(const TallArgs& a, hipStream_t stream) {
     }
 }
 
+void launch_tall(const TallArgs& a, hipStream_t stream) { launch_tall_as(a, tall_rows(a.M), stream); }
+
 // ------------------------------------------------------------------------------------------------
 // k_rowprep: one wave per row.  x' = x + (sum of pend's planes, in order) + its bias -> x_out; LayerNorm(x') (affine) -> bf16 hi / lo planes (+ the f32 rows to y_out).
-// The arithmetic is k_skinny's fused prologue (PRO_LN | PRO_AFFINE | PRO_PARTIAL), instruction for instruction: a row normalises to the same bits on either path.
+// The arithmetic is k_skinny's fused prologue (PRO_LN | PRO_AFFINE | PRO_PARTIAL), instruction for instruction: a row normalises to the same bits on either path
+// (held by tests/test_gpu_tall.py test_rowprep_has_the_bits_of_the_step_kernels_prologue: x_out and y_out of both kernels on the same operands, as bits).
 // ------------------------------------------------------------------------------------------------
 template <int NJ>
 __global__ __launch_bounds__(256) void k_rowprep(PrepArgs a) {
@@ -254,9 +267,11 @@ bool rowprep_supported(const PrepArgs& a) {
            (!a.y_out || aligned16(a.y_out));
 }
 
+int rowprep_blocks(int M) { return (M + 3) / 4; }
+
 void launch_rowprep(const PrepArgs& a, hipStream_t stream) {
     note_launch("k_rowprep");
-    const dim3 grid((unsigned)((a.M + 3) / 4));
+    const dim3 grid((unsigned)rowprep_blocks(a.M));
     if (a.D == 1024) hipLaunchKernelGGL(k_rowprep<4>, grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_rowprep<2>, grid, dim3(256), 0, stream, a);
 }

@@ -31,6 +31,7 @@ _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int64)
 _DP = C.POINTER(C.c_double)
 _I32P = C.POINTER(C.c_int32)
+_U16P = C.POINTER(C.c_uint16)
 _STEP_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
 _PCM_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 
@@ -288,7 +289,7 @@ ABI_SYMBOLS = [
 # the test / measurement hooks of include/ptts_debug.h: exported by libptts_hooks.so, never by libptts_hip.so (checked by __graft_entry__.build())
 HOOK_SYMBOLS = [
     "ptts_decode_stages", "ptts_mimi_layer_piece", "ptts_debug_last_attention_kernel", "ptts_debug_launch_counts", "ptts_debug_flow_cluster_inject",
-    "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall_linear",
+    "ptts_debug_time_skinny", "ptts_debug_skinny_stamps", "ptts_debug_gemm", "ptts_debug_step_stamps", "ptts_debug_tall",
     "ptts_debug_encode_stages", "ptts_debug_resample_launches", "ptts_debug_dsp_blocked_host",
     "ptts_debug_loudness_energies", "ptts_debug_kweighting", "ptts_debug_step_linear", "ptts_debug_true_peak_taps", "ptts_debug_true_peak_oversample",
     "ptts_debug_dsp_opts_error", "ptts_debug_resblock", "ptts_debug_resblock_plan", "ptts_debug_seanet_pack", "ptts_debug_plan_seanet_frags",
@@ -540,6 +541,9 @@ class _Keep:
 
     def i32(self, a):
         return self._ptr(a, np.int32, _I32P)
+
+    def u16(self, a):
+        return self._ptr(a, np.uint16, _U16P)
 
 
 def _census_dict(buf) -> dict:
@@ -1568,31 +1572,100 @@ def op_attention_positions(q, k, v, posq, posk, context: int) -> np.ndarray:
     return out
 
 
+TALL_OPS = {"rowprep": 1, "tall": 2, "both": 3}   # PTTS_TALL_*
+
+
+class _TallArgs(C.Structure):   # ptts_tall_args
+    _fields_ = ([(n, C.c_int32) for n in ("op", "M", "rows", "N", "K", "epi", "splitk", "form", "psplit", "want_x_out", "want_y_out")] + [("eps", C.c_float)] +
+                [(n, C.c_int64) for n in ("ldx", "ldy", "lda", "ldc", "ldr", "ldp", "pstride", "zstride", "launched_cap")] +
+                [(n, _FP) for n in ("x", "planes", "pbias", "ln_w", "ln_b", "W", "bias", "R", "out", "x_out", "y_out")] +
+                [(n, _U16P) for n in ("ch", "cl", "yh", "yl")] +
+                [("form_out", _I32P), ("grid", _I32P), ("launched", C.c_char_p)])
+
+
+def debug_tall(op, x, *, M=None, K=None, w=None, bias=None, residual=None, epi=0, splitk=1, form=0, ln=None, planes=None, pbias=None, want_x_out=True,
+               want_y_out=True, out_planes=False, ldy=None, lda=None, ldc=None, ldp=None, zstride=None):
+    """k_rowprep and k_tall (csrc/tall.hip) on host operands (ptts_debug_tall, include/ptts_debug.h): op is a key of TALL_OPS.  x [rows, ldx] ("tall": [rows,
+    lda]); the launch is told of M rows (default: all) of width K (default: ln's weight's, "tall": w's).  ln = (weight, bias, eps); planes [psplit, pstride], each plane
+    holding dense [M, K] rows; w [N, K]; residual [rows, ldr].  Returns a dict of whole buffers, 0xff bytes where nothing was stored: "out" ([rows, ldc] f32, or
+    the planes [splitk, zstride]; None with out_planes), "ch" / "cl" ([rows, ldp] bf16 bits, with out_planes), "x_out" / "y_out" [rows, K], "yh" / "yl" [rows, ldy]
+    bf16 bits (None for "tall"), "form" (the block height launched), "grid", "launched" ({kernel: count}).  A refusal raises PttsError with the same dict as
+    its `partial` attribute."""
+    x = _f32(x)
+    rows = int(x.shape[0])
+    prep, prod = op in ("rowprep", "both"), op in ("tall", "both")
+    w = _f32(w) if w is not None else None
+    if K is not None:
+        k = int(K)
+    elif prep:
+        k = int(np.asarray(ln[0]).shape[0]) if ln is not None else int(x.shape[1])
+    else:
+        k = int(w.shape[1]) if w is not None else int(x.shape[1])
+    n = int(w.shape[0]) if w is not None else 0
+    m = rows if M is None else int(M)
+    s = int(splitk)
+    a, keep = _TallArgs(), _Keep()
+    a.op, a.M, a.rows, a.N, a.K, a.epi, a.splitk, a.form = TALL_OPS[op], m, rows, n, k, int(epi), s, int(form)
+    a.want_x_out, a.want_y_out = (1 if want_x_out else 0), (1 if want_y_out else 0)
+    a.launched_cap = 256
+    a.x, a.W, a.bias, a.pbias = keep.f32(x), keep.f32(w), keep.f32(bias), keep.f32(pbias)
+    res = {"out": None, "ch": None, "cl": None, "x_out": None, "y_out": None, "yh": None, "yl": None}
+    if prep:
+        a.ldx = x.shape[1]
+        a.ldy = k if ldy is None else int(ldy)
+        if ln is not None:
+            a.ln_w, a.ln_b, a.eps = keep.f32(ln[0]), keep.f32(ln[1]), float(ln[2])
+        if planes is not None:
+            planes = _f32(planes)
+            a.psplit, a.pstride = planes.shape[0], planes.size // max(planes.shape[0], 1)
+        a.planes = keep.f32(planes)
+        res["x_out"], res["y_out"] = np.empty((rows, k), np.float32), np.empty((rows, k), np.float32)
+        res["yh"], res["yl"] = np.empty((rows, max(int(a.ldy), 0)), np.uint16), np.empty((rows, max(int(a.ldy), 0)), np.uint16)
+        a.x_out, a.y_out, a.yh, a.yl = keep.f32(res["x_out"]), keep.f32(res["y_out"]), keep.u16(res["yh"]), keep.u16(res["yl"])
+    if prod:
+        a.lda = int(lda) if lda is not None else (int(a.ldy) if prep else x.shape[1])
+        if residual is not None:
+            residual = _f32(residual)
+            a.ldr = residual.shape[1]
+        a.R = keep.f32(residual)
+        a.ldc, a.ldp = (n if ldc is None else int(ldc)), (n if ldp is None else int(ldp))
+        a.zstride = rows * n if zstride is None else int(zstride)
+        if s > 1 or not out_planes:
+            res["out"] = np.empty((s, max(int(a.zstride), 0)) if s > 1 else (rows, max(int(a.ldc), 0)), np.float32)
+        if out_planes:
+            res["ch"], res["cl"] = np.empty((rows, max(int(a.ldp), 0)), np.uint16), np.empty((rows, max(int(a.ldp), 0)), np.uint16)
+        a.out, a.ch, a.cl = keep.f32(res["out"]), keep.u16(res["ch"]), keep.u16(res["cl"])
+    fo, grid, launched = (C.c_int32 * 1)(), (C.c_int32 * 3)(), C.create_string_buffer(256)
+    a.form_out, a.grid, a.launched = C.cast(fo, _I32P), C.cast(grid, _I32P), C.cast(launched, C.c_char_p)
+    rc = hooks().ptts_debug_tall(C.byref(a))
+    res.update(form=int(fo[0]), grid=tuple(int(g) for g in grid), launched=_census_dict(launched))
+    try:
+        _check(rc)
+    except PttsError as e:
+        e.partial = res
+        raise
+    return res
+
+
+def _bf16_bits_f32(u):
+    return (np.ascontiguousarray(u, np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
 def debug_tall_linear(x, w, *, bias=None, residual=None, epi=0, splitk=1, ln=None, planes=None, pbias=None, out_planes=False):
-    """The AR step's 128+-row linear (csrc/tall.hip) on host operands (ptts_debug_tall_linear): `ln` = (weight, bias, eps) sends the rows through k_rowprep
-    (with `planes` [psplit, M, K] and `pbias` summed in first); returns (out [splitk or 1, M, N] squeezed, updated rows or None)."""
+    """debug_tall in its first form: `ln` = (weight, bias, eps) sends the rows through k_rowprep (with `planes` [psplit, M, K] and `pbias` summed in first),
+    then k_tall as production launches it; returns (out [splitk or 1, M, N] squeezed -- hi + lo with out_planes --, updated rows or None)."""
     x, w = _f32(x), _f32(w)
-    m, k = x.shape
+    m = x.shape[0]
     n = w.shape[0]
     s = max(1, int(splitk))
-    out = np.empty((s, m, n), np.float32)
-    lw = lb = None
-    eps = 1e-5
-    if ln is not None:
-        lw, lb, eps = _f32(ln[0]), _f32(ln[1]), float(ln[2])
-    pl = _f32(planes) if planes is not None else None
-    pb = _f32(pbias) if pbias is not None else None
-    b = _f32(bias) if bias is not None else None
-    r = _f32(residual) if residual is not None else None
-    xo = np.empty((m, k), np.float32) if (pl is not None and ln is not None) else None
-    nul = C.cast(None, _FP)
-    H = hooks()
-    H.ptts_debug_tall_linear.argtypes = [C.c_int32] * 5 + [_FP, _FP, C.c_int32, _FP, _FP, _FP, C.c_float, _FP, _FP, _FP, C.c_int32, _FP, _FP]
-    _check(H.ptts_debug_tall_linear(m, n, k, int(epi), s, _fp(x), _fp(pl) if pl is not None else nul, 0 if pl is None else pl.shape[0],
-                                    _fp(pb) if pb is not None else nul, _fp(lw) if lw is not None else nul, _fp(lb) if lb is not None else nul, eps,
-                                    _fp(w), _fp(b) if b is not None else nul, _fp(r) if r is not None else nul, 1 if out_planes else 0, _fp(out),
-                                    _fp(xo) if xo is not None else nul))
-    return (out[0] if s == 1 else out), xo
+    pend = ln is not None and planes is not None
+    r = debug_tall("both" if ln is not None else "tall", x, w=w, bias=bias, residual=residual, epi=epi, splitk=s, ln=ln, planes=planes if pend else None,
+                   pbias=pbias if pend else None, out_planes=bool(out_planes) and s == 1)
+    if out_planes and s == 1:
+        out = _bf16_bits_f32(r["ch"]) + _bf16_bits_f32(r["cl"])
+    else:
+        out = r["out"].reshape((s, m, n) if s > 1 else (m, n))
+    return out, (r["x_out"] if pend else None)
 
 
 class _FlowClusterArgs(C.Structure):   # ptts_flow_cluster_args

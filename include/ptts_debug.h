@@ -46,14 +46,42 @@ int ptts_debug_step_stamps(ptts_batch* b, int32_t lsd_steps, uint64_t* out /* [c
 int ptts_debug_gemm(int32_t M, int32_t N, int32_t K, int32_t w_bf16, int32_t variant, int32_t epi, int32_t iters, float* avg_us,
                     float* maxdiff);
 
-/* The AR step's linears at 128+ rows (csrc/tall.hip), stand-alone on host operands: with ln_w the rows go through k_rowprep first (x' = x + sum of the
- * `psplit` planes [psplit][M][K] + pbias -> x_out; LayerNorm(x') -> bf16 hi / lo planes), without it x is split on the host; then
- * out = epi(A W^T + bias) by k_tall (W [N][K] row-major, rounded to bf16 by the hook; epi 0 none, 1 GELU, 4 residual add of R [M][N]); splitk > 1: `out`
- * receives the planes [splitk][M][N] (plane 0 carries R + bias); out_planes: the result leaves through the bf16 hi / lo planes the next product reads
- * (hi + lo is returned). */
-int ptts_debug_tall_linear(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t splitk, const float* x, const float* planes, int32_t psplit, const float* pbias,
-                           const float* ln_w, const float* ln_b, float eps, const float* W, const float* bias, const float* R, int32_t out_planes, float* out,
-                           float* x_out);
+/* The AR step's linears at 128+ rows (csrc/tall.hip) stand-alone on host operands: ONE launch of k_rowprep, ONE of k_tall, or the two chained.
+ *   op PTTS_TALL_ROWPREP  launch_rowprep: x' = x + (((p_0 + p_1) + ...) + pbias) -> x_out; LayerNorm(x') (biased variance, affine ln_w / ln_b [K], eps) -> y_out
+ *                         and its bf16 split yh / yl.  The row width D is K.
+ *      PTTS_TALL_TALL     launch_tall_as: out = epi(x W^T + bias); x is split into its bf16 hi / lo planes [rows][lda] on the host the way the kernels split
+ *      PTTS_TALL_BOTH     the first, then the second on yh / yl (lda must equal ldy)
+ *   Every per-row buffer holds `rows` >= M rows; the launch is told of M.  Rows behind M and columns behind a width are there to be found unchanged.
+ *   k_rowprep: x [rows][ldx]; planes [psplit][pstride] (a plane's rows dense [M][K]; pstride >= rows K; NULL with psplit 0: no pending sum, x_out is not
+ *   written); pbias [K] or NULL; x_out, y_out [rows][K] f32 (want_x_out / want_y_out 0: the kernel is passed a null pointer); yh, yl [rows][ldy] bf16 bits.
+ *   k_tall: W [N][K] f32 row-major, rounded to bf16 and packed by the loader's packer; bias [N] or NULL; R [rows][ldr] or NULL; epi 0 none, 1 GELU, 4 residual
+ *   add (kernels.h Epi); form 0: tall_rows(M) picks as in production, 32 / 64: that block height.  The result leaves
+ *     splitk > 1: as the planes out [splitk][zstride] (a plane's rows dense [M][N]; zstride >= rows N).  k_skinny's convention: with R, plane 0 =
+ *                 R + (sums_0 + bias) and the others raw sums; without R every plane holds raw sums and a bias is refused (it would be dropped: it is the
+ *                 consumer's through PendingSum::bias);
+ *     ch != NULL: as bf16 bits ch / cl [rows][ldp] (the hi / lo planes the next product reads);
+ *     otherwise:  as out [rows][ldc] f32.
+ * Every result (out, ch, cl, x_out, y_out, yh, yl; any may be NULL where the form does not need it) is filled with 0xff bytes before the launch and returned whole.
+ * form_out: the block height launched (0 for ROWPREP); grid [3]: the last launch's grid as the launcher's own functions give it (tall_grid / rowprep_blocks);
+ * launched (launched_cap bytes): the census of the call ("kernel=count;"), empty after a refusal.
+ * PTTS_EINVAL with a message, before anything is uploaded or launched -- no call can take an access outside these buffers:
+ *   an unknown op; a form other than 0, 32, 64; M < 1, rows < M or rows > 1024; N or K outside [1, 8192]; a leading dimension below its width (ldx, ldy, lda < K;
+ *   ldc, ldr, ldp < N); pstride < rows K; zstride < rows N; psplit outside [0, 16] or not matching planes; pbias without planes; splitk outside [1, 16];
+ *   a null operand or result of the form; BOTH with lda != ldy; whatever rowprep_supported / tall_supported refuse. */
+#define PTTS_TALL_ROWPREP 1
+#define PTTS_TALL_TALL 2
+#define PTTS_TALL_BOTH 3
+typedef struct ptts_tall_args {
+    int32_t op, M, rows, N, K, epi, splitk, form, psplit, want_x_out, want_y_out;
+    float eps;
+    int64_t ldx, ldy, lda, ldc, ldr, ldp, pstride, zstride, launched_cap;
+    const float *x, *planes, *pbias, *ln_w, *ln_b, *W, *bias, *R;
+    float *out, *x_out, *y_out;
+    uint16_t *ch, *cl, *yh, *yl;
+    int32_t *form_out, *grid;
+    char* launched;
+} ptts_tall_args;
+int ptts_debug_tall(const ptts_tall_args* a);
 
 /* The step linear (csrc/skinny.hip: k_skinny, the kernel every AR step spends its time in) stand-alone on host operands.  C = epi(prologue(x) W^T + bias):
  *   x [M][lda] (lda >= K), W [N][K] f32 row-major; wfmt 0: f32 weights, 1: rounded to bf16, 2: per-row int8 (w_eff [N][K] receives W^ = q s, w_scale [N] the

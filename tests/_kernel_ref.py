@@ -1,5 +1,6 @@
 """What the value-level kernel tests share (test_gpu_step_linear, _attn_step, _attn_window, _many_row_gemm, _mimi_fused, _seanet_block,
-_flow_cluster_values, _tall, and _step_edge with its reference module _step_edge_ref: ptts_debug_step_edge): the bf16 number format as the kernels round it, the activation functions in float64, the 0xff fill the hooks put
+_flow_cluster_values, _step_edge with its reference module _step_edge_ref: ptts_debug_step_edge, and _tall with its reference module _tall_ref, itself checked
+without a GPU by test_tall_ref: ptts_debug_tall): the bf16 number format as the kernels round it, the activation functions in float64, the 0xff fill the hooks put
 into every output buffer before a launch, and the error-against-bound check.  A helper that one file needs in another form (scipy's erf, a
 bound taken at the worst element, an f32 restatement of a kernel's own function) stays in that file."""
 import math
